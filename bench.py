@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- watermark frames/s decoded (sync + LLR + SCL-8) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts N rank processes itself -- fresh children,
@@ -34,6 +34,10 @@ Further driver-timed legs in the same JSON line (`legs`), each bracketed by barr
   c5        BASELINE config 5 SURROGATE (no MP3 codec in the image -- echoseal_amd/workloads.lossy_channel; NOT MP3):
             list size swept over 1/4/8/16, payload bit error rate and frames/s.
 
+--dump-outputs DIR: after the timed steps, rank 0 writes the arrays its last timed step returned (sync results, LLRs, list-decoder
+results, selection) as DIR/<name>.npy in float32 / float64, under 64 MB in all: two builds run with the same arguments decode the same
+windows and can be compared file by file.
+
 Extra objects:
   roofline      es_xcorr32_kernel<17,2048> -- the kernel north_star grades against the HBM roofline -- in the timed c3_unfused leg:
                 algorithmic bytes per launch (16 136 B per window, SURVEY.md section 8d) / mean launch duration against 8 TB/s;
@@ -57,9 +61,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The pipelines run on up to eight HIP streams; the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues
-# (default 4), and streams that share a queue serialise.  Must be set before HIP starts (echoseal_amd.engine does the same on import).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 KEY = b"\xAA" * 32
 XCORR_BYTES_PER_WINDOW = 4 * 2048 + 4 * (2048 - 62)       # 16 136 B
@@ -71,6 +72,9 @@ HBM_PEAK_GBS = 8000.0                                       # MI355X_MICROARCH.m
 FP64_ISSUE_PEAK_GWIPS = 256 * 4 * 2.4 / 4.0
 CLOCK_GHZ = 2.4
 N_SIMD = 1024
+DUMP_BYTES_MAX = 63 * 10 ** 6                              # --dump-outputs: array data of all files (64 MB with the .npy headers)
+DUMP_RECORDS = 65536                                       # records kept of the per-record arrays (a seeded sample beyond)
+DUMP_RECORDS_WIDE = 512                                    # records kept of the per-sample arrays (band-passed rows, LLRs, candidate bits)
 
 
 def parse_args(argv=None):
@@ -96,7 +100,13 @@ def parse_args(argv=None):
                     help="N = 1 only: initialise the process group (RCCL for --backend nccl) at world size 1 and run every collective of the N > 1 "
                          "path (schedule broadcast, barrier, all_reduce) through it -- lets one GPU load librccl and exercise the calls")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 on fewer GPUs)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all (seeded samples of records beyond that)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -252,13 +262,13 @@ def run_rank(a) -> None:
     L = a.list_size
     eng = RxEngine(local, list_size_max=max(16, L))
     tx = WatermarkEmbedder(KEY)
-    # Eight hardware queues: every pipeline of this process runs on the SAME eight streams (four made at high priority for the grouped
+    # Eight streams: every pipeline of this process runs on the SAME eight streams (four made at high priority for the grouped
     # pipeline's front ends, four further ones: list-decoder streams of the grouped pipeline, lanes of the 65 536-record launches)
     front_streams = pipeline_streams(dev, a.front_lanes, priority=-1)
     back_streams = pipeline_streams(dev, max(a.scl_streams, min(a.big_lanes, 8 - a.front_lanes)))
     big_streams = (back_streams + front_streams)[:a.big_lanes]                # the lanes of the 65 536-record launches
     if len(big_streams) < a.big_lanes:
-        raise SystemExit(f"--big-lanes {a.big_lanes}: the process keeps {len(back_streams) + len(front_streams)} streams (GPU_MAX_HW_QUEUES = 8)")
+        raise SystemExit(f"--big-lanes {a.big_lanes}: the process keeps {len(back_streams) + len(front_streams)} streams")
     out_legs = {}
 
     # ============================================================ headline: C3, weak scaling
@@ -291,8 +301,8 @@ def run_rank(a) -> None:
     ev3 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
 
     def c3_step(k=None):
-        sy, _llr, scl, _done = pipe3.submit(win, band3, pn3, start="peak", select=True, xcorr_events=None if k is None else ev3[k])
-        return sy, scl
+        sy, llr, scl, _done = pipe3.submit(win, band3, pn3, start="peak", select=True, xcorr_events=None if k is None else ev3[k])
+        return sy, llr, scl
 
     # Untimed preparation: every lane's context / kernels run once before the clock starts (first launches allocate and upload
     # code), then the W warm-up steps the contract asks for.
@@ -306,11 +316,14 @@ def run_rank(a) -> None:
     barrier()
     t0 = time.perf_counter()
     for k in range(a.steps):
-        sy3, scl3 = c3_step(k)
+        sy3, llr3, scl3 = c3_step(k)
     host_enqueue_s = time.perf_counter() - t0
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     gc.enable()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, sy3, llr3, scl3)
+    del llr3
     fused_ms = float(np.mean([s.elapsed_time(e) for s, e in ev3])) if a.steps else float("nan")
     payload3, ok3, _which3 = scl3.selected
     if int((ok3 == -2).sum().item()) or int((scl3.ncand < 0).sum().item()):
@@ -428,7 +441,7 @@ def run_rank(a) -> None:
         barrier()
         ts = time.perf_counter()
         for _ in range(ns):
-            sys_, scls_ = c3_step()
+            sys_, _llrs, scls_ = c3_step()
         barrier()
         dts = max_over_ranks(time.perf_counter() - ts)
         gc.enable()
@@ -437,7 +450,7 @@ def run_rank(a) -> None:
                                     "value": world * Bw * ns / dts, "unit": "frames/s", "scaling": "weak", "steps": ns, "seconds": dts,
                                     "ms_per_step": 1e3 * dts / ns, "ratio_to_the_headline": (world * Bw * ns / dts) / (total * a.steps / dt),
                                     "results_identical_to_the_headline": same_s}
-        del sys_, scls_
+        del sys_, _llrs, scls_
     del pk_s, npk_s, payload_s, ok_s, sy3, scl3, payload3, ok3, pk, npk
     win_h = band_h = pn_h = None
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
@@ -637,6 +650,49 @@ def run_rank(a) -> None:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+def _sample_records(n: int, k: int, seed: int):
+    """Indices of k of n records: all of them when k >= n, else a sorted sample drawn with a fixed seed."""
+    import numpy as np
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(d: str, sy, llr, scl) -> None:
+    """--dump-outputs: the arrays the headline's last timed step handed its caller (SyncResult, LLRs, SclResult and the selection),
+    as DIR/<name>.npy in float32 (integers below 2^24) or float64.  Per-record arrays keep DUMP_RECORDS records, per-sample arrays
+    DUMP_RECORDS_WIDE, each a seeded sample when the batch is larger (indices in records.npy / records_wide.npy); both shrink until
+    the files fit in DUMP_BYTES_MAX.  Same arguments, same inputs, same files."""
+    import numpy as np
+    import torch
+    f32, f64 = np.float32, np.float64
+    payload, ok, which = scl.selected
+    per_record = [("sync_thr", sy.thr, f64), ("sync_peaks", sy.peaks, f32), ("sync_npeaks", sy.npeaks, f64), ("sync_flags", sy.flags, f32),
+                  ("scl_hard_ok", scl.hard_ok, f32), ("scl_cand_metric", scl.cand_metric, f64), ("scl_cand_ok", scl.cand_ok, f32),
+                  ("scl_ncand", scl.ncand, f32), ("payload", payload, f32), ("ok", ok, f32), ("which", which, f32)]
+    per_sample = [("sync_y", sy.y, f64), ("llr", llr, f32),
+                  ("scl_hard_info", scl.hard_info, f32), ("scl_cand_info", scl.cand_info, f32)]
+
+    def row_bytes(arrays):
+        return sum(int(np.prod(t.shape[1:])) * np.dtype(dt).itemsize for _, t, dt in arrays) + 8
+    B = int(sy.peaks.shape[0])
+    k = min(B, DUMP_RECORDS)
+    while k > 1 and k * row_bytes(per_record) + min(k, DUMP_RECORDS_WIDE) * row_bytes(per_sample) > DUMP_BYTES_MAX:
+        k //= 2
+    rows, wide = _sample_records(B, k, 1), _sample_records(B, min(k, DUMP_RECORDS_WIDE), 2)
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for sel, arrays, idx_name in ((rows, per_record, "records"), (wide, per_sample, "records_wide")):
+        index = torch.from_numpy(sel).to(sy.peaks.device)
+        for name, t, dt in arrays:
+            a = t.index_select(0, index).cpu().numpy().astype(dt)
+            np.save(os.path.join(d, name + ".npy"), a)
+            total += a.nbytes
+        np.save(os.path.join(d, idx_name + ".npy"), sel.astype(f64))
+        total += sel.size * 8
+    print(f"bench.py: wrote the last timed step's outputs to {d} ({total / 1e6:.1f} MB)", file=sys.stderr, flush=True)
 
 
 def scl_roofline(head_fps, c4_fps, L, listed_share=1.0):

@@ -26,20 +26,16 @@ from . import _native as nat
 from .tables import pack_tables
 
 # The streaming pipelines run on up to eight HIP streams.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues
-# (default 4) and streams that share a queue serialise: with the default, every arrangement with more than four streams is slower,
-# silently (a third of the grouped pipeline's rate).  The variable is read when HIP initialises, so it is set here when that has not
-# happened yet; DecodePipeline warns when more streams are alive than the budget this module could establish.
-HW_QUEUES_WANTED = 8
-if "GPU_MAX_HW_QUEUES" not in os.environ and not torch.cuda.is_initialized():
-    os.environ["GPU_MAX_HW_QUEUES"] = str(HW_QUEUES_WANTED)
-_HWQ_ENV_AT_IMPORT = os.environ.get("GPU_MAX_HW_QUEUES")      # None: HIP was already up, without the variable
+# (default 4) and streams that share a queue serialise, silently.  The variable belongs to the process's environment: this module reads
+# it and never sets it; DecodePipeline warns when more streams are alive than the budget it names.
+_HWQ_ENV_AT_IMPORT = os.environ.get("GPU_MAX_HW_QUEUES")      # None: the runtime's default
 _LIVE_STREAMS = [0]                                            # streams made through pipeline_streams and not yet given back (a plain count:
                                                                # weak references to torch.cuda.Stream objects crash the interpreter's final GC)
 
 
 def hw_queue_budget() -> int:
     """Hardware queues the process's HIP streams are spread over, as far as this module can tell: GPU_MAX_HW_QUEUES as it stood
-    when the module was imported (set by the module itself if HIP had not started), else the runtime's default of 4."""
+    when the module was imported, else the runtime's default of 4."""
     try:
         return max(1, int(_HWQ_ENV_AT_IMPORT)) if _HWQ_ENV_AT_IMPORT is not None else 4
     except ValueError:
@@ -56,9 +52,8 @@ def pipeline_streams(device, n: int, priority: int = 0) -> list:
         gc.collect()                                # (pipelines that are garbage but not yet collected still count their streams)
     if _LIVE_STREAMS[0] > hw_queue_budget():
         warnings.warn(f"DecodePipeline: {_LIVE_STREAMS[0]} pipeline streams are alive but the HIP runtime has {hw_queue_budget()} hardware queues "
-                      f"(GPU_MAX_HW_QUEUES{'=' + _HWQ_ENV_AT_IMPORT if _HWQ_ENV_AT_IMPORT else ' was not set before HIP initialised'}): streams that share a "
-                      "queue serialise.  Set GPU_MAX_HW_QUEUES=8 before the first GPU call (importing echoseal_amd.engine first does it), "
-                      "and hand existing streams to further pipelines (streams=...).", RuntimeWarning, stacklevel=3)
+                      f"(GPU_MAX_HW_QUEUES{'=' + _HWQ_ENV_AT_IMPORT if _HWQ_ENV_AT_IMPORT else ' not set'}): streams that share a "
+                      "queue serialise.  Hand existing streams to further pipelines (streams=...).", RuntimeWarning, stacklevel=3)
     return out
 
 
@@ -538,8 +533,8 @@ class DecodePipeline:
       * neither (round 1): the front end on one stream (LLR on a side stream), the list decoder on one of `scl_streams`
         further streams, at most `depth` batches in flight.
 
-    Results are complete after `wait(result)` / `synchronize()`.  A process should keep at most GPU_MAX_HW_QUEUES (8) HIP
-    streams alive: pass `streams=` (lanes: a list; grouped: (front-end streams, list-decoder streams)) to build a further pipeline on
+    Results are complete after `wait(result)` / `synchronize()`.  Beyond hw_queue_budget() live HIP streams, streams share
+    hardware queues and serialise: pass `streams=` (lanes: a list; grouped: (front-end streams, list-decoder streams)) to build a further pipeline on
     existing ones; more live pipeline streams than hardware queues raises a RuntimeWarning (hw_queue_budget)."""
 
     def __init__(self, eng: "RxEngine", *, list_size: int = 8, scl_streams: int = 2, depth: int | None = None, lanes: int = 0,
@@ -595,7 +590,7 @@ class DecodePipeline:
         if self.lanes:
             # (lane 0 on the caller's own stream was measured slower: 1.29 M against 1.43 M frames/s at 7 lanes)
             # `streams`: HIP streams to run the lanes on instead of new ones -- a process that builds several pipelines should hand
-            # the same streams to each: beyond GPU_MAX_HW_QUEUES (8) live streams, streams share hardware queues and serialise
+            # the same streams to each: beyond hw_queue_budget() live streams, streams share hardware queues and serialise
             self.lane_streams = list(streams)[:self.lanes] if streams is not None else self._mk(dev, self.lanes)
             if len(self.lane_streams) != self.lanes:
                 raise ValueError("streams: one per lane")

@@ -623,6 +623,7 @@ def test_front_batch_equals_separate_calls(engine):
 def test_front_end_context_and_stream_budget(engine):
     """es_create(device, 0): a front-end context runs everything but the list decoder and says so; pipelines warn when more streams are
     alive than the HIP runtime has hardware queues."""
+    import os
     import warnings
     from echoseal_amd._native import NativeError
     from echoseal_amd.engine import RxEngine, DecodePipeline, hw_queue_budget, pipeline_streams
@@ -634,7 +635,7 @@ def test_front_end_context_and_stream_budget(engine):
     assert torch.equal(y, y2) and torch.equal(peaks, peaks2) and torch.equal(llr, llr2)
     with pytest.raises(NativeError, match="front-end context"):
         fe.scl(llr, list_size=8)
-    assert hw_queue_budget() >= 4
+    assert hw_queue_budget() == int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))      # the environment's value, never one the module set
     keep = []
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")

@@ -1,6 +1,5 @@
 """Large batches through the lane pipeline: does the front end of chunk k+1 overlap the list decoder of chunk k?"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import echoseal_amd._native as nat

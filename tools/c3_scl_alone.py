@@ -1,7 +1,6 @@
 """The stages of one headline (C3) step run alone, one after the other on one stream: 65 536 windows of 2 048 as bench.py builds them
 (clean frames resampled +-5 %, offset, in noise at -15 dB), front end (band-pass + fused sync + LLR) and SCL-8 on ITS LLRs."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import echoseal_amd._native as nat

@@ -1,6 +1,5 @@
 """CPU cost of enqueueing one pipeline step (lanes mode) vs the GPU time per step."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from echoseal_amd import workloads as WL

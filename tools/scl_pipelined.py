@@ -1,7 +1,6 @@
 """SCL-8 alone, pipelined: N engines on N streams, each launching 65 536-frame batches back to back (no front end) -- the steady-state rate of
 the list decoder when the tails of one launch are filled by the next.  python3 tools/scl_pipelined.py [LANES] [BUILD]"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import echoseal_amd._native as nat
