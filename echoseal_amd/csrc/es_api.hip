@@ -542,6 +542,16 @@ int es_softplus_batch(es_ctx* ctx, const double* t_dev, int64_t n, double* out_d
     return es_launch_softplus(ctx, t_dev, n, out_dev, (hipStream_t)stream);
 }
 
+int es_polar_f_batch(es_ctx* ctx, const double* a_dev, const double* b_dev, int64_t n, double* out_dev, int32_t* bad_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (n < 0) return fail(ctx, ES_EINVAL, "es_polar_f_batch: negative count");
+    if (n == 0) return ES_OK;
+    if (!a_dev || !b_dev || !out_dev || !bad_dev) return fail(ctx, ES_EINVAL, "es_polar_f_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_polar_f_dev(ctx, a_dev, b_dev, n, out_dev, bad_dev, (hipStream_t)stream);
+}
+
 int es_aead_check_batch(es_ctx* ctx, const uint8_t* key32_host, const uint8_t* blobs_dev, int64_t n, int group,
                         const uint32_t* ctr_dev, uint8_t* ok_dev, uint8_t* plain_dev, void* stream)
 {

@@ -42,6 +42,7 @@
 // which lets es_math.h address its entries without adding a base.
 #define ES_EXP_TAB_LDS_ADDR 0u
 #include "es_scl_common.h"
+#include "es_softplus_dev.h"
 #include <type_traits>
 #ifndef ES_WIDE_GBATCH
 #define ES_WIDE_GBATCH 8                          /* load pairs in flight in the lane-serial g loops (divides 8; 8: +1 % over 4, measured) */
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                         if (d == 1) { pa = a.is_f64 ? llr64[j] : (double)llr32[j]; pb = a.is_f64 ? llr64[j + S] : (double)llr32[j + S]; }
                         else if (d <= DL) { pa = A[(long long)(2 * S + j) * L + fp0]; pb = A[(long long)(2 * S + j + S) * L + fp0]; }
                         else { pa = W.low[rs + j][fp0]; pb = W.low[rs + j + S][fp0]; }
-                        const double v = es_polar_f(pa, pb, tab);
+                        const double v = es_polar_f_slg(pa, pb, tab);
                         if (d < DL) A[(long long)(S + j) * L + fp0] = v; else W.low[rd + j][fp0] = v;
                     }
                     group_sync();
@@ -615,7 +616,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                             for (int u = 0; u < 32; ++u) {
                                 const int j = j0 + u;
                                 ld(j < 255 ? j + 1 : 255, qn);
-                                dst2[(long long)j * L] = es_polar_f(g1(q[0], q[1], (wa >> u) & 1u), g1(q[2], q[3], (wb >> u) & 1u), tab);
+                                dst2[(long long)j * L] = es_polar_f_slg(g1(q[0], q[1], (wa >> u) & 1u), g1(q[2], q[3], (wb >> u) & 1u), tab);
                                 #pragma unroll
                                 for (int k = 0; k < 4; ++k) q[k] = qn[k];
                             }
@@ -642,7 +643,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                                 const double y = es_polar_g(g1(q[4], q[5], (w1c >> u) & 1u), g1(q[6], q[7], (w1d >> u) & 1u), (w2b >> u) & 1u);   // ... and j + 128
                                 dst2[(long long)j * L] = x;
                                 dst2[(long long)(j + 128) * L] = y;
-                                dst3[(long long)j * L] = es_polar_f(x, y, tab);
+                                dst3[(long long)j * L] = es_polar_f_slg(x, y, tab);
                                 #pragma unroll
                                 for (int k = 0; k < 8; ++k) q[k] = qn[k];
                             }
@@ -682,14 +683,14 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                             const double g1 = es_polar_g(q[0], q[1], u1), g2 = es_polar_g(q[2], q[3], u2);
                             dst[(long long)j * L] = g1;
                             dst[(long long)(j + H) * L] = g2;
-                            stB(j, es_polar_f(g1, g2, tab));
+                            stB(j, es_polar_f_slg(g1, g2, tab));
                         };
                         auto pair_ff = [&](int j, const double (&q)[4]) {
-                            const double f1 = es_polar_f(q[0], q[1], tab);
+                            const double f1 = es_polar_f_slg(q[0], q[1], tab);
                             dst[(long long)j * L] = f1;
-                            const double f2 = es_polar_f(q[2], q[3], tab);
+                            const double f2 = es_polar_f_slg(q[2], q[3], tab);
                             dst[(long long)(j + H) * L] = f2;
-                            stB(j, es_polar_f(f1, f2, tab));
+                            stB(j, es_polar_f_slg(f1, f2, tab));
                         };
                         const int blk = H < 32 ? H : 32;
                         for (int i0 = 0; i0 < H; i0 += blk) {
@@ -759,13 +760,13 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                         int bad = 0;
                         ld_slab(0, a0, b0_); ld_slab(1, a1, b1_); ld_slab(2, a2, b2_);
                         for (int j = 0; ; j += 3) {
-                            dst[(long long)j * L] = es_polar_f_fast(a0, b0_, tab, &bad);
+                            dst[(long long)j * L] = es_polar_f_sl(a0, b0_, tab, &bad);
                             if (j + 1 >= S) break;
                             ld_slab(j + 3 < S ? j + 3 : S - 1, a0, b0_);
-                            dst[(long long)(j + 1) * L] = es_polar_f_fast(a1, b1_, tab, &bad);
+                            dst[(long long)(j + 1) * L] = es_polar_f_sl(a1, b1_, tab, &bad);
                             if (j + 2 >= S) break;
                             ld_slab(j + 4 < S ? j + 4 : S - 1, a1, b1_);
-                            dst[(long long)(j + 2) * L] = es_polar_f_fast(a2, b2_, tab, &bad);
+                            dst[(long long)(j + 2) * L] = es_polar_f_sl(a2, b2_, tab, &bad);
                             if (j + 3 >= S) break;
                             ld_slab(j + 5 < S ? j + 5 : S - 1, a2, b2_);
                         }
@@ -774,13 +775,13 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                         double a0, b0_, a1, b1_, a2, b2_;
                         ld_slab(0, a0, b0_); ld_slab(1, a1, b1_); ld_slab(2, a2, b2_);
                         for (int j = 0; ; j += 3) {
-                            dst[(long long)j * L] = es_polar_f(a0, b0_, tab);
+                            dst[(long long)j * L] = es_polar_f_slg(a0, b0_, tab);
                             if (j + 1 >= S) break;
                             ld_slab(j + 3 < S ? j + 3 : S - 1, a0, b0_);
-                            dst[(long long)(j + 1) * L] = es_polar_f(a1, b1_, tab);
+                            dst[(long long)(j + 1) * L] = es_polar_f_slg(a1, b1_, tab);
                             if (j + 2 >= S) break;
                             ld_slab(j + 4 < S ? j + 4 : S - 1, a1, b1_);
-                            dst[(long long)(j + 2) * L] = es_polar_f(a2, b2_, tab);
+                            dst[(long long)(j + 2) * L] = es_polar_f_slg(a2, b2_, tab);
                             if (j + 3 >= S) break;
                             ld_slab(j + 5 < S ? j + 5 : S - 1, a2, b2_);
                         }
@@ -791,11 +792,11 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                         for (int j = 0; j < S - 2; ++j) {
                             double na, nb;
                             ld_slab(j + 2, na, nb);
-                            dst[(long long)j * L] = es_polar_f(pa, pb, tab);
+                            dst[(long long)j * L] = es_polar_f_slg(pa, pb, tab);
                             pa = qa; pb = qb; qa = na; qb = nb;
                         }
-                        dst[(long long)(S - 2) * L] = es_polar_f(pa, pb, tab);
-                        dst[(long long)(S - 1) * L] = es_polar_f(qa, qb, tab);
+                        dst[(long long)(S - 2) * L] = es_polar_f_slg(pa, pb, tab);
+                        dst[(long long)(S - 1) * L] = es_polar_f_slg(qa, qb, tab);
 #endif
                     }
                     pa_ = p8_set(pa_, d - 1, p);
@@ -827,7 +828,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                             #pragma unroll
                             for (int u = 0; u < C; ++u) { x[u] = src(c + u); x[C + u] = src(c + u + S); }
                             #pragma unroll
-                            for (int u = 0; u < C; ++u) W.low[rd + c + u][p] = es_polar_f_fast(x[u], x[C + u], tab, &bad);
+                            for (int u = 0; u < C; ++u) W.low[rd + c + u][p] = es_polar_f_sl(x[u], x[C + u], tab, &bad);
                         }
                         if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) {          // rare: the level again with the generic form
                             #pragma unroll 1
@@ -838,7 +839,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                         #pragma unroll
                         for (int u = 0; u < 2 * S; ++u) x[u] = src(u);
                         #pragma unroll 2
-                        for (int j = 0; j < S; ++j) W.low[rd + j][p] = es_polar_f(x[j], x[j + S], tab);
+                        for (int j = 0; j < S; ++j) W.low[rd + j][p] = es_polar_f_slg(x[j], x[j + S], tab);
                     }
                     if constexpr (d <= 8) pa_ = p8_set(pa_, d - 1, p); else pb_ = p8_set(pb_, 5, p);
                 };
@@ -855,7 +856,7 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
 #if ES_WIDE_DEFER & 8
                     else {
                         int bad = 0;
-                        lam = es_polar_f_fast_sp(xa, xb, tab, &sp_diff, &sp_sum, &bad);
+                        lam = es_polar_f_sl_sp(xa, xb, tab, &sp_diff, &sp_sum, &bad);
                         if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) lam = es_polar_f_sp(xa, xb, tab, &sp_diff, &sp_sum);
                     }
 #else
@@ -1087,7 +1088,36 @@ int launch_wide(es_ctx* ctx, WideArgs a, int64_t B, hipStream_t st)
     return ES_OK;
 }
 
+// Diagnostic: the list decoder's f as its hot loops evaluate it (es_softplus_dev.h, exp table at LDS address 0), for a test against the host.
+__global__ __launch_bounds__(256) void es_polar_f_dev_kernel(const double* __restrict__ a, const double* __restrict__ b, long long n,
+                                                             const uint64_t* __restrict__ exp_tab, double* __restrict__ out, int* __restrict__ bad)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    uint64_t* const tab = reinterpret_cast<uint64_t*>(smem_raw);
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_raw != ES_EXP_TAB_LDS_ADDR) __builtin_trap();   // never: no static LDS in this file
+    for (int i = threadIdx.x; i < ES_EXP_TAB_WORDS; i += blockDim.x) tab[i] = exp_tab[i];
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        double sd, ss;
+        int bd = 0;
+        out[i] = es_polar_f_sl_sp(a[i], b[i], tab, &sd, &ss, &bd);
+        out[n + i] = sd;
+        out[2 * n + i] = ss;
+        bad[i] = bd;
+    }
+}
+
 }  // namespace
+
+int es_launch_polar_f_dev(es_ctx* ctx, const double* a, const double* b, int64_t n, double* out, int* bad, hipStream_t st)
+{
+    long long blocks = (n + 255) / 256;
+    if (blocks > (long long)ctx->num_cu * 16) blocks = (long long)ctx->num_cu * 16;
+    hipLaunchKernelGGL(es_polar_f_dev_kernel, dim3((unsigned)blocks), dim3(256), ES_EXP_TAB_WORDS * sizeof(uint64_t), st,
+                       a, b, (long long)n, ctx->d_exp_tab, out, bad);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
 
 // Scratch for this file's kernels: per resident workgroup of Lm lanes 1024*Lm doubles + WIDE_AUX_PER_PATH*Lm bytes.
 // Lists of up to 64 paths run in blocks of 256 lanes, so every context that has the scratch has it for 256-lane blocks.

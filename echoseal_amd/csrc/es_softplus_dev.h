@@ -1,0 +1,129 @@
+/* es_softplus_dev.h -- the straight-line softplus of es_math.h (es_softplus_neg_fast) with fewer vector instructions, and the
+ * f(a, b) built on it.  Same bits for every operand, same range flag; tests/test_softplus_dev.py compares it with es_math.h's
+ * es_polar_f_fast_sp on the host, tests/test_softplus_dev_gpu.py on the device.
+ *
+ * es_softplus_neg_fast evaluates four results and picks one with three 64-bit selects (two v_cndmask each):
+ *     res0 = f - (hfsq - sR)                                   k == 0
+ *     resk = ln2_hi - ((hfsq - (sR + (ln2_lo + c))) - f)       k == 1
+ *     resc = ln2_hi - ((Rc - (ln2_lo + c)) - f)                 k == 1 and |f| < 2^-20 (fdlibm's corner)
+ *     rt   = y - y*y*0.5                                        y < 2^-29
+ * All four are ONE expression  kf*ln2_hi - ((P - (Q + kf*(ln2_lo + c))) - f)  with
+ *     kf = 0 (k == 0) or 1,   Q = sR, or 0 in the corner and below 2^-29,   P = hfsq * (1 - kc*(2/3)*f),  kc = 1 in the corner,
+ * because IEEE-754 round-to-nearest is sign-symmetric (x - y == -(y - x) bit for bit, and 0 - x == -x except 0 - (+0) == +0):
+ *   k == 0:  fma(0, ln2_hi, -W) == -W == f - (hfsq - sR) where W = (hfsq - sR) - f (W is +0 when f == hfsq - sR, never -0: f > 0);
+ *            fma(0, ln2_lo + c, sR) == sR (sR > 0);  below 2^-29 Q == 0 gives -(hfsq - y) == y - hfsq, and hfsq is formed as
+ *            (f*f)*0.5 -- rt's rounding; elsewhere f*f is a normal number (|f| >= 2^-53 or 0), where (f*f)*0.5 == (0.5*f)*f.
+ *   k == 1:  fma(1, x, y) rounds x + y once, as the adds do; 1 - 1*g == 1 - g and 1 - 0*g == 1 (fma rounds once);
+ *            in the corner Q + (ln2_lo + c) == ln2_lo + c (that sum is never -0: x + -x is +0 under round-to-nearest).
+ * kf and kc are 0.0 / 1.0, whose low words are zero: one 32-bit select each.  The three 64-bit selects of the result become
+ * one (Q), and the arithmetic of res0, resc and rt (8 float64 instructions per softplus) is gone. */
+#ifndef ES_SOFTPLUS_DEV_H
+#define ES_SOFTPLUS_DEV_H
+
+#include "es_math.h"
+
+/* 0.0 or 1.0 by a flag: a select of the high word only */
+ES_HD double es_flag01(int on) { return es_u2d((uint64_t)(on ? 0x3ff00000u : 0u) << 32); }
+
+/* log1p(exp(t)) for t <= 0, bit-identical to es_softplus_neg_fast (the ES_SOFTPLUS_CORNER 1 form); *ok = 0 outside |t| < 512 */
+ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
+{
+    /* ---- exp(t), main path of es_exp (as es_softplus_neg_fast) ---- */
+    double kd = ES_FMA(t, ES_EXP_INVLN2N, ES_EXP_SHIFT);
+    const uint64_t ki = es_d2u(kd);
+    kd = kd - ES_EXP_SHIFT;
+    double r = ES_FMA(kd, ES_EXP_NLN2HI, t);
+    r = ES_FMA(kd, ES_EXP_NLN2LO, r);
+    const uint32_t idx = 2u * (uint32_t)(ki & 127u);
+#if defined(__HIP_DEVICE_COMPILE__) && defined(ES_EXP_TAB_LDS_ADDR)
+    typedef __attribute__((address_space(3))) const uint64_t es_lds_u64;
+    es_lds_u64* const te = (es_lds_u64*)(uint32_t)((ES_EXP_TAB_LDS_ADDR) + idx * 8u);
+    const double tail = es_u2d(te[0]);
+    const uint64_t sbits = te[1] + (ki << 45);
+    (void)tab;
+#else
+    const double tail = es_u2d(tab[idx]);
+    const uint64_t sbits = tab[idx + 1] + (ki << 45);
+#endif
+    const double p23 = ES_FMA(r, ES_EXP_C3, ES_EXP_C2);
+    const double tr = r + tail;
+    const double r2 = r * r;
+    const double p45 = ES_FMA(r, ES_EXP_C5, ES_EXP_C4);
+    const double tq = ES_FMA(p23, r2, tr);
+    const double r4 = r2 * r2;
+    const double tmp = ES_FMA(r4, p45, tq);
+    const double scale = es_u2d(sbits);
+    const double y = ES_FMA(scale, tmp, scale);           /* in (0, 1] */
+
+    /* ---- log1p(y) ---- */
+    const int32_t hy = es_hi32(y);
+    const int tiny29 = hy < 0x3e200000;                   /* y < 2^-29 */
+    const int k0 = hy < 0x3FDA827A;                       /* y < sqrt(2)-1: k = 0, f = y */
+    const double u = 1.0 + y;
+    const uint32_t hu0 = (uint32_t)es_hi32(u);
+    const int corner = (uint32_t)(hu0 - 0x3FFFFFFDu) < 3u;   /* k == 1 and |f| < 2^-20 (see es_softplus_neg_fast) */
+    const double cn1 = y - (u - 1.0);
+    const double f1 = ES_FMA(u, 0.5, -1.0);
+    const double f = k0 ? y : f1;
+    const double c = es_div_normal(cn1, u);
+    const double hfsq = f * f * 0.5;
+    const double s = es_div_normal(f, 2.0 + f);
+    const double z = s * s;
+    const double R1 = z * ES_LP1;
+    const double z2 = z * z;
+    const double R2 = ES_LP2 + z * ES_LP3;
+    const double z4 = z2 * z2;
+    const double R3 = ES_LP4 + z * ES_LP5;
+    const double z6 = z4 * z2;
+    const double R4 = ES_LP6 + z * ES_LP7;
+    const double R = ((R1 + z2 * R2) + z4 * R3) + z6 * R4;
+    const double sR = s * (hfsq + R);
+    const double kf = es_flag01(!k0);
+    const double kc = es_flag01(corner);
+    const double P = hfsq * ES_FMA(-kc, 0.66666666666666666 * f, 1.0);
+    const double Q = (corner | tiny29) ? 0.0 : sR;
+    const double W = (P - ES_FMA(kf, ES_LN2_LO + c, Q)) - f;
+    *ok = (__builtin_fabs(t) < 512.0);
+    return ES_FMA(kf, ES_LN2_HI, -W);
+}
+
+/* es_polar_f_fast_sp with es_softplus_neg_sl: the same value, softplus pair and *bad (or-ed in) */
+ES_HD double es_polar_f_sl_sp(double a, double b, const uint64_t* tab, double* sp_diff, double* sp_sum, int* bad)
+{
+    const double d1 = a - b;
+    const double sum = a + b;
+    int ok1, ok2;
+    const double L1 = es_softplus_neg_sl(-__builtin_fabs(d1), tab, &ok1);
+    const double L2 = es_softplus_neg_sl(-__builtin_fabs(sum), tab, &ok2);
+    *bad |= !(ok1 & ok2);
+    *sp_diff = L1;
+    *sp_sum = L2;
+    const double r1 = es_max_num(a, b) + L1;
+    const double r2 = es_max_num(sum, 0.0) + L2;
+    return r1 - r2;
+}
+
+ES_HD double es_polar_f_sl(double a, double b, const uint64_t* tab, int* bad)
+{
+    double s0, s1;
+    return es_polar_f_sl_sp(a, b, tab, &s0, &s1, bad);
+}
+
+/* es_polar_f (generic softplus right after an evaluation out of range) with es_softplus_neg_sl */
+ES_HD double es_polar_f_slg(double a, double b, const uint64_t* tab)
+{
+    const double d1 = a - b;
+    const double sum = a + b;
+    const double t1 = -__builtin_fabs(d1);
+    const double t2 = -__builtin_fabs(sum);
+    int ok1, ok2;
+    double L1 = es_softplus_neg_sl(t1, tab, &ok1);
+    double L2 = es_softplus_neg_sl(t2, tab, &ok2);
+    if (!ok1) L1 = es_softplus_neg_generic(t1, tab);
+    if (!ok2) L2 = es_softplus_neg_generic(t2, tab);
+    const double r1 = es_max_num(a, b) + L1;
+    const double r2 = es_max_num(sum, 0.0) + L2;
+    return r1 - r2;
+}
+
+#endif /* ES_SOFTPLUS_DEV_H */

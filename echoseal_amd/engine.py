@@ -332,6 +332,16 @@ class RxEngine:
         nat.check(self._ctx, self._lib.es_softplus_batch(self._ctx, _ptr(t), t.numel(), _ptr(out), self._stream()), "es_softplus_batch")
         return out
 
+    def polar_f(self, a: torch.Tensor, b: torch.Tensor):
+        """Diagnostic: f(a, b) and its two softplus terms as the lane-per-path list decoder's hot loops evaluate them on the device
+        (float64 in; returns float64 [3, n] and the int32 out-of-range flag [n])."""
+        a = a.contiguous(); b = b.contiguous()
+        out = torch.empty((3, a.numel()), dtype=torch.float64, device=a.device)
+        bad = torch.empty(a.numel(), dtype=torch.int32, device=a.device)
+        nat.check(self._ctx, self._lib.es_polar_f_batch(self._ctx, _ptr(a), _ptr(b), a.numel(), _ptr(out), _ptr(bad), self._stream()),
+                  "es_polar_f_batch")
+        return out, bad
+
     def polar_encode(self, info: torch.Tensor) -> torch.Tensor:
         info = info.contiguous()
         B = info.shape[0]

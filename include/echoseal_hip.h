@@ -241,6 +241,11 @@ int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int6
  * test compare the device arithmetic with the host C library bit for bit.  t_dev, out_dev float64 [n].                   */
 int es_softplus_batch(es_ctx* ctx, const double* t_dev, int64_t n, double* out_dev, void* stream);
 
+/* Diagnostic: f(a[i], b[i]) as the lane-per-path list decoder's hot loops evaluate it on the device (es_softplus_dev.h), with its two
+ * softplus terms: out_dev float64 [3][n] = f, log1p(exp(-|a-b|)), log1p(exp(-|a+b|)); bad_dev int32 [n] = 1 where |a-b| or |a+b| is
+ * outside the straight-line form's range (the three values are then unspecified).  a_dev, b_dev float64 [n].                          */
+int es_polar_f_batch(es_ctx* ctx, const double* a_dev, const double* b_dev, int64_t n, double* out_dev, int32_t* bad_dev, void* stream);
+
 /* Tuning knobs; results never depend on them.  es_scl_batch has three mappings of list paths to lanes for lists of up to
  * 32 paths: one frame per wavefront (a path owns 64/L lanes: lowest latency, one wavefront per SIMD), several frames per
  * wavefront (a path owns 4 or 2 lanes: 16 or 32 paths per wavefront, three wavefronts per SIMD), and one lane per path (64/L
