@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
+import threading
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -63,11 +65,23 @@ def sum_f32(a): a = _c(a, np.float32); return np.float32(lib().eso_sum_f32(_p(a)
 _K = [448]                        # K of the code the polar functions below use (eso_polar_set_k); 448 unless a test says otherwise
 
 
+_MAP_GUARD = threading.Lock()     # guards _MAPS_RUNNING
+_MAPS_RUNNING = [0]               # threaded maps (map_records) in progress: the code's K must not change under them
+
+
+def _set_k(K):
+    with _MAP_GUARD:
+        if _MAPS_RUNNING[0]:
+            raise RuntimeError("oracle.code_k: the polar code cannot change while map_records runs")
+        old = lib().eso_polar_set_k(int(K)); _K[0] = int(K)
+        return old
+
+
 class code_k:
     """`with oracle.code_k(512): ...` -- the polar functions inside use Polar(1024, 512)+CRC-8 (rtwm/fastpolar.py:209-234 takes any K)."""
     def __init__(self, K): self.K = int(K)
-    def __enter__(self): self.old = lib().eso_polar_set_k(self.K); _K[0] = self.K; return self
-    def __exit__(self, *exc): lib().eso_polar_set_k(self.old); _K[0] = self.old
+    def __enter__(self): self.old = _set_k(self.K); return self
+    def __exit__(self, *exc): _set_k(self.old)
 
 
 def polar_tables():
@@ -98,6 +112,47 @@ def polar_decode(llr, L):
     llr = _c(llr, np.float64); info = np.zeros(_K[0] - 8, np.uint8); tl = ctypes.c_int(0)
     ok = lib().eso_polar_decode(_p(llr), int(L), _p(info), ctypes.byref(tl))
     return info, bool(ok), bool(tl.value)
+
+
+# ------------------------------------------------------------------------------- threaded map over records
+def map_threads() -> int:
+    """Worker threads of map_records: the CPUs this process may run on, at most 16."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def map_records(fn, n: int, *, chunk: int = 64, threads: int | None = None) -> list:
+    """fn(lo, hi) -> list of mismatch descriptors for records lo .. hi-1; -> the concatenated lists in record order.
+
+    Threads, not processes: the caller may have a GPU open, which forked children would inherit.  The C calls release the
+    GIL (ctypes), so the oracle's work runs in parallel.  fn should compare inside the worker and return only what differs,
+    so that no caller ever holds the oracle's outputs for a whole batch.  The polar tables (built lazily by the C code) are
+    built here, before any thread starts, and code_k refuses to change the code while a map runs."""
+    with _MAP_GUARD:
+        _MAPS_RUNNING[0] += 1
+    try:
+        polar_tables()                              # builds the tables of the current K once, single-threaded
+        bounds = [(lo, min(n, lo + chunk)) for lo in range(0, n, chunk)]
+        nt = threads or map_threads()
+        if nt == 1 or len(bounds) <= 1:
+            parts = [fn(lo, hi) for lo, hi in bounds]
+        else:
+            with ThreadPoolExecutor(max_workers=nt) as ex:
+                parts = list(ex.map(lambda b: fn(*b), bounds))
+    finally:
+        with _MAP_GUARD:
+            _MAPS_RUNNING[0] -= 1
+    return [m for part in parts for m in part]
+
+
+def first_diff(a, b):
+    """Index (flat) of the first element whose bits differ between two arrays of one shape, or None; -1 when the shapes differ.
+    Floats are compared as bits: -0.0 != 0.0, and a NaN equals only the same NaN."""
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype.itemsize != b.dtype.itemsize:
+        return -1
+    u = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    d = np.flatnonzero(a.reshape(-1).view(u) != b.reshape(-1).view(u))
+    return int(d[0]) if d.size else None
 
 
 # ------------------------------------------------------------------------------- DSP
@@ -143,6 +198,29 @@ def decode_frame(frame_f32, ba, tpl, taps, pn_full_bits, L=8, start=0):
     info, ok, took = polar_decode(l.astype(np.float64), L)
     return dict(y=y, corr=corr, thr=thr, peaks=peaks, npeaks=tot, fallback=fb, llr=l, best_s=best_s,
                 info=np.packbits(info).tobytes(), ok=ok, took_list=took)
+
+
+def headline_record(frame_f32, ba, tpl, taps, pn_full_bits, L=8):
+    """One record of the benchmark's config-3 step as the reference computes it: band-pass, sync, LLR (variant 0) at the first
+    detected peak, hard decision, and -- only when the hard decision fails its CRC -- the SCL-L list; then the candidate
+    selection with validator None.  Candidate rows of a settled record are zeros (what the compacted list decoder writes)."""
+    y = lfilter(ba[:9], ba[9:], frame_f32)
+    corr = ncc(y, tpl)
+    thr, _, _ = cfar_threshold(corr)
+    peaks, tot, fb = pick_peaks(corr, thr)
+    st = int(peaks[0]) if tot else 0
+    l, _, _, _ = llr(y[st:st + 1215], pn_full_bits[191:1215], taps)
+    l64 = l.astype(np.float64)
+    hinfo, hok = polar_hard(l64)
+    hard = np.packbits(hinfo)
+    if hok:
+        n, ci, cm, cc = 0, np.zeros((L, hard.size), np.uint8), np.zeros(L), np.zeros(L, np.uint8)
+    else:
+        n, bits, cm, cc = scl_list(l64, L)
+        ci = np.packbits(bits, axis=1)
+    payload, ok, which = select_validated(None, 0, hard, hok, ci, cc, cm, n)
+    return dict(y=y, thr=thr, peaks=peaks, npeaks=tot, fallback=fb, llr=l, hard_info=hard, hard_ok=hok, ncand=n,
+                cand_info=ci, cand_metric=cm, cand_ok=cc, payload=np.frombuffer(payload, np.uint8), ok=ok, which=which)
 
 
 def decode_header(frame, hdr_pn_bits, taps):

@@ -471,10 +471,15 @@ def test_config3_noisy_jittered_windows(engine, oracle):
         st = int(peaks[0])
         o, obs, _, _ = oracle.llr(yy[st:st + 1215], np.unpackbits(pn[i])[191:1215], taps[bi, :ntaps[bi]])
         assert np.array_equal(o, L[i])
-        nn, ci, cm, cc = oracle.scl_list(o.astype(np.float64), 8)
-        if int(res.ncand[i]):
+        hinfo, hok = oracle.polar_hard(o.astype(np.float64))
+        assert np.packbits(hinfo).tobytes() == res.hard_info[i].cpu().numpy().tobytes() and hok == bool(res.hard_ok[i])
+        assert (int(res.ncand[i]) == 0) == hok, i                        # compaction: no list exactly when the hard decision passes
+        if not hok:
+            nn, ci, cm, cc = oracle.scl_list(o.astype(np.float64), 8)
+            assert int(res.ncand[i]) == nn
             assert np.array_equal(np.packbits(ci, axis=1), res.cand_info[i].cpu().numpy())
-            assert np.array_equal(cm, res.cand_metric[i].cpu().numpy())
+            assert np.array_equal(cm.view(np.uint64), res.cand_metric[i].cpu().numpy().view(np.uint64))
+            assert np.array_equal(cc, res.cand_ok[i].cpu().numpy())
 
 
 def _adversarial_records(rng, n, T):
