@@ -260,17 +260,8 @@ int es_pick_exact_batch(es_ctx* ctx, const float* corr32_dev, const double* y_de
     if (!corr32_dev || !y_dev || !band_dev || !thr_dev || !peaks_dev || !npeaks_dev || !flags_dev)
         return fail(ctx, ES_EINVAL, "es_pick_exact_batch: null pointer");
     DeviceGuard g(ctx->device);
-    const int n_lags = T - (ES_PRE_L - 1);
-    /* float64 workspace for the (rare) records the float32 screen cannot settle; grows monotonically,
-       so after a warm-up call nothing is allocated on the launch path */
-    const size_t need = (size_t)B * n_lags * sizeof(double);
-    if (need > ctx->ws_corr_bytes) { const int rc0 = es_reserve(ctx, B, T); if (rc0) return rc0; }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = es_launch_pick_exact(ctx, corr32_dev, y_dev, B, T, band_dev, thr_dev, peaks_dev, npeaks_dev, flags_dev, st);
-    if (rc) return rc;
-    rc = es_launch_xcorr_flagged(ctx, y_dev, B, T, band_dev, ctx->d_ws_corr, flags_dev, st);
-    if (rc) return rc;
-    return es_launch_pick_flagged(ctx, ctx->d_ws_corr, B, n_lags, thr_dev, peaks_dev, npeaks_dev, flags_dev, st);
+    return es_launch_pick_exact(ctx, corr32_dev, y_dev, B, T, band_dev, thr_dev, peaks_dev, npeaks_dev, flags_dev,
+                                (hipStream_t)stream);
 }
 
 int es_sync_fused_batch(es_ctx* ctx, const float* y32_dev, const double* y_dev, int64_t B, int T,

@@ -8,7 +8,7 @@
 //   es_xcorr32_kernel   y32 (float32, written by the band-pass next to y64) -> corr32 (float32).
 //                       4 860 B in, 4 612 B out per record: the traffic SURVEY.md section 8(d)
 //                       prices the correlation kernel at.  FP32 FMAs, taps in scalar registers.
-//   es_pick_exact_wave_kernel  works on corr32 with a rigorous error bound DELTA (|corr32 - corr64| <=
+//   sync_pick_row       works on corr32 with a rigorous error bound DELTA (|corr32 - corr64| <=
 //                       DELTA), and re-evaluates in float64 -- with exactly the arithmetic of
 //                       es_xcorr_kernel / oracle/c/eso_dsp.c -- every value that lies within reach
 //                       of a decision: the order statistics' neighbourhoods (order statistics are
@@ -16,7 +16,10 @@
 //                       of the band [m32 - 2 DELTA, m32 + 2 DELTA]), the threshold crossers and the
 //                       rivals of a local maximum.  thr / peaks / npeaks come out bit-identical to
 //                       the all-float64 path; records with too many ambiguous values (constant
-//                       signals, exact repeats) are flagged and redone by the float64 kernels.
+//                       signals, exact repeats) are flagged and settled by sync_exact_row from
+//                       float64 re-evaluations alone.  The one picker serves both forms: the fused
+//                       kernel calls it on the row it keeps in LDS, es_pick_exact_wave_kernel on a
+//                       corr32 row it copies there.
 //
 // Error bound: inputs rounded to f32 (2 x 2^-24 relative), 63-term FMA chain (63 x 2^-24 of
 // sum|y||tpl| <= e_y by Cauchy-Schwarz, |tpl| = 1), energy and sqrt (~2e-6 relative), approximate
@@ -26,6 +29,24 @@
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Address-space-typed memory.  The picker runs out of line, where the compiler cannot infer what a generic pointer points to:
+// it emits flat_* instructions, and through one it once merged two LDS doubles into an 8-byte-aligned flat_load_dwordx4, a
+// memory-aperture violation that aborted the queue (see corr64_window).  So every pointer the picker is handed is typed: LDS
+// through address_space(3), global memory through address_space(1) (tests/test_sync_code_objects.py holds the ISA to it).
+typedef __attribute__((address_space(3))) unsigned char lds_u8;
+typedef __attribute__((address_space(3))) float lds_float;
+typedef __attribute__((address_space(3))) double lds_double;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(1))) const double glb_cdouble;
+typedef __attribute__((address_space(1))) double glb_double;
+typedef __attribute__((address_space(1))) int32_t glb_int;
+typedef __attribute__((address_space(1))) uint8_t glb_u8;
+
+__device__ __forceinline__ void lds_add(lds_u32* p, uint32_t v)
+{
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 
 __device__ __forceinline__ void wave_fence_lds()
 {
@@ -51,13 +72,20 @@ constexpr double DELTA = 3e-5;
 // sees 4 bytes per sample in and <= 150 bytes per record out ("4 860 + <= 64 B" per frame).
 constexpr int XF_WAVES = 2;                         // waves per block of the fused kernel (a block = 2 records in flight)
 constexpr int XF_MIN_WAVES = 3;                     // <= 168 VGPRs: a fused-sync wave fits the slot one list-decoder wave (168) leaves behind
-struct FusedArgs {
+struct FusedArgs {                                  // the picker's operands as the kernels receive them
     const double* y64;                              // [B][T] float64 band-passed records (exact re-evaluations)
     double* thr; int32_t* peaks; int32_t* npeaks; uint8_t* flags;
 };
+struct RowOut {                                     // one record's outputs
+    glb_double* thr; glb_int* peaks; glb_int* npeaks; glb_u8* flag;
+};
+__device__ __forceinline__ RowOut row_out(const FusedArgs& fo, long long rec)
+{
+    return RowOut{(glb_double*)fo.thr + rec, (glb_int*)fo.peaks + rec * ES_MAX_PEAKS, (glb_int*)fo.npeaks + rec, (glb_u8*)fo.flags + rec};
+}
 struct PwFixed;
-__device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, const double* tpl, long long rec, int lane,
-                              const FusedArgs& fo);
+typedef __attribute__((address_space(3))) PwFixed lds_PwFixed;
+__device__ void sync_pick_row(lds_PwFixed& S, lds_float* c, int n, glb_cdouble* yr, glb_cdouble* tpl, RowOut o, int lane);
 __host__ __device__ __forceinline__ size_t xf_lds_per_wave(int ns2, int n_lags);
 __host__ __device__ __forceinline__ int xf_head_floats(int ns2);
 
@@ -65,7 +93,7 @@ __host__ __device__ __forceinline__ int xf_head_floats(int ns2);
 // R = lags per lane.  R = 19 (one wave per frame-sized record) moves the fewest LDS bytes per FMA and is the
 // large-batch kernel; R = 5 spreads a record over four waves so that a 1 024-record launch still puts four
 // waves on every SIMD (latency-bound regime).  The screen value may differ in the last ulps between the two
-// (energy summation order); both satisfy the DELTA bound, and es_pick_exact_wave_kernel is exact for either.
+// (energy summation order); both satisfy the DELTA bound, and sync_pick_row is exact for either.
 // TC = record length known at compile time (0: use the argument).  With TC = 1 215 (a frame) every bounds
 // test of the load / store loops folds away.
 // FUSED = true (es_sync_fused_batch): an item is still a (record, segment) pair, but a wave walks ALL segments of its record,
@@ -86,8 +114,8 @@ void es_xcorr32_kernel(const float* __restrict__ y, long long B,
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: item, record, band are scalar
     const int n_lags = T - (ES_PRE_L - 1);
-    float* s = FUSED ? reinterpret_cast<float*>(xf_smem + wv * xf_lds_per_wave(NS + 2, n_lags)) : s_buf[wv];
-    float* const crow = s + xf_head_floats(NS + 2);                           // FUSED: the record's screen row
+    lds_float* const s = FUSED ? (lds_float*)((lds_u8*)xf_smem + wv * xf_lds_per_wave(NS + 2, n_lags)) : (lds_float*)s_buf[wv];
+    lds_float* const crow = s + xf_head_floats(NS + 2);                       // FUSED: the record's screen row
     const int nseg = (n_lags + SEG - 1) / SEG;
     const long long n_items = B * nseg;
     // non-fused: consecutive items go to consecutive waves.  Fused: a wave takes the nseg items of one record, then
@@ -140,7 +168,7 @@ void es_xcorr32_kernel(const float* __restrict__ y, long long B,
         // offset, odd lags the ones that start at an odd offset, so the tap pairs are the same 32 aligned
         // SGPR pairs for every lag.  The 64th "tap" is zero; the sample it meets is the next lane's (or
         // the zero pad), finite unless the record already holds a NaN/Inf, which flags the record anyway.
-        const float* w = s + lane * R;
+        const lds_float* w = s + lane * R;
         f32x2 acc[R];
         #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = f32x2{0.0f, 0.0f};
@@ -186,8 +214,8 @@ void es_xcorr32_kernel(const float* __restrict__ y, long long B,
         // sqrt(en) >= 1e-6 makes the reference's "+ 1e-12" a relative 1e-6 effect (inside DELTA): one rsq
         // instead of sqrt + rcp.  Near-silent windows, and energies outside float32 range (|y| beyond
         // ~1e18, which would make the quotient silently wrong), take the careful form for the whole wave;
-        // an overflowed energy becomes NaN, which sends the record to the float64 kernels.
-        float* const dst = FUSED ? crow + lag0 : s;                           // FUSED: straight into the record's row
+        // an overflowed energy becomes NaN, which flags the record (settled from float64 values alone).
+        lds_float* const dst = FUSED ? crow + lag0 : s;                       // FUSED: straight into the record's row
         const int nl = (n_lags - lag0 < SEG) ? n_lags - lag0 : SEG;
         if (__builtin_amdgcn_ballot_w64(!(emin >= 1.0e-12f && emax < 3.0e38f)) == 0) {
             #pragma unroll
@@ -202,8 +230,8 @@ void es_xcorr32_kernel(const float* __restrict__ y, long long B,
         wave_fence_lds();
         if constexpr (FUSED) {
             if (lag0 + SEG >= n_lags) {                                       // last segment: the row is complete
-                PwFixed& S = *reinterpret_cast<PwFixed*>(s);             // the samples are dead by now: their LDS serves the picker
-                sync_pick_row(S, crow, n_lags, fo.y64 + rec * T, tabs->tpl[bi], rec, lane, fo);
+                lds_PwFixed& S = *reinterpret_cast<lds_PwFixed*>(s);         // the samples are dead by now: their LDS serves the picker
+                sync_pick_row(S, crow, n_lags, (glb_cdouble*)fo.y64 + rec * T, (glb_cdouble*)tabs->tpl[bi], row_out(fo, rec), lane);
             }
         } else {
             float* cr = corr + rec * n_lags + lag0;
@@ -225,7 +253,7 @@ void es_xcorr32_kernel(const float* __restrict__ y, long long B,
 // ------------------------------------------------------------------------------------ exact value
 // corr64 of one lag, bit-identical to es_xcorr_kernel / eso_ncc: FMA chain over ascending taps;
 // energy = (head + core) + tail over the 19-lag chunk the lag belongs to.
-__device__ double corr64_at(const double* __restrict__ yr, int i, const double* __restrict__ tpl)
+__device__ double corr64_at(glb_cdouble* __restrict__ yr, int i, glb_cdouble* __restrict__ tpl)
 {
     const int c = i - i % XC_R;
     // (unrolled by nine: the nine loads of a group are issued together -- one round trip per group instead of one per sample; the value's
@@ -257,8 +285,7 @@ __device__ double corr64_at(const double* __restrict__ yr, int i, const double* 
 // (w is an LDS pointer, not a generic one: through a generic pointer the compiler merges neighbouring doubles into 16-byte flat loads at
 // 8-byte alignment -- fine for global memory, a memory violation when the address resolves to LDS on this target: that is how the first
 // version of this routine aborted the queue.  With the address space known it emits 8-byte-aligned ds_read2_b64.)
-typedef __attribute__((address_space(3))) double xl_lds_double;
-__device__ __forceinline__ double corr64_window(const xl_lds_double* w, int r, const double* __restrict__ tpl)
+__device__ __forceinline__ double corr64_window(const lds_double* w, int r, glb_cdouble* __restrict__ tpl)
 {
     double num = 0.0;
     #pragma unroll 9
@@ -287,11 +314,10 @@ __device__ __forceinline__ double corr64_window(const xl_lds_double* w, int r, c
 // loads of its own: ~16 dependent trips to a row that no cache holds (0.4 ms of the fused kernel's 1.0 ms per 65 536 windows, by ablation).
 constexpr int XL_G = 6, XL_W = ES_PRE_L + XC_R - 1, XL_STRIDE = 84;    // 81 samples per window; 6 x 84 doubles = 4 032 B
 template <typename FL, typename FO>
-__device__ __forceinline__ void corr64_list(double* stage, int cnt, const double* __restrict__ yr, int n, const double* __restrict__ tpl, int lane, FL lag_of, FO out)
+__device__ __forceinline__ void corr64_list(lds_double* stage, int cnt, glb_cdouble* __restrict__ yr, int n, glb_cdouble* __restrict__ tpl, int lane, FL lag_of, FO out)
 {
     static_assert(XL_G * XL_STRIDE * 8 <= 4096 && XL_W <= XL_STRIDE && XL_W - 64 <= 64, "stage area");
     const int last = n + ES_PRE_L - 2;                                  // last sample of the record (n lags of ES_PRE_L taps)
-    xl_lds_double* const st = (xl_lds_double*)stage;                    // (`stage` is LDS: see corr64_window)
     for (int g0 = 0; g0 < cnt; g0 += XL_G) {
         const int ng = cnt - g0 < XL_G ? cnt - g0 : XL_G;
         double v0[XL_G], v1[XL_G];
@@ -307,11 +333,11 @@ __device__ __forceinline__ void corr64_list(double* stage, int cnt, const double
         }
         #pragma unroll
         for (int w = 0; w < XL_G; ++w) {
-            st[w * XL_STRIDE + lane] = v0[w];
-            if (lane < XL_W - 64) st[w * XL_STRIDE + 64 + lane] = v1[w];
+            stage[w * XL_STRIDE + lane] = v0[w];
+            if (lane < XL_W - 64) stage[w * XL_STRIDE + 64 + lane] = v1[w];
         }
         wave_fence_lds();
-        if (lane < ng) out(g0 + lane, corr64_window(st + lane * XL_STRIDE, rr, tpl));
+        if (lane < ng) out(g0 + lane, corr64_window(stage + lane * XL_STRIDE, rr, tpl));
         wave_fence_lds();
     }
 }
@@ -337,7 +363,7 @@ __device__ __forceinline__ float key_f32(uint32_t k)
 //   Order statistics: |screen - exact| <= d, and order statistics are 1-Lipschitz in the sup norm, so the exact k-th
 //   value is the (k - #below)-th of the exact values of the band [m32 - 2d, m32 + 2d] around the float32 order statistic.
 // Records that would need more than PW_CAP exact values (or more than 64 rivals of one candidate) are flagged
-// (reason codes 1..5) and redone by the float64 kernels inside the same es_pick_exact_batch call.
+// (reason codes 1..5) and settled by the same wave from float64 re-evaluations alone (sync_exact_row).
 constexpr int PW_WAVES = 4;
 constexpr int PW_CAP = 192;
 
@@ -357,7 +383,7 @@ __device__ __forceinline__ int lanes_below(unsigned long long m)
 
 // k-th smallest 32-bit key of key(i), i in [0,n), by one wave: 4 passes of 8 bits
 template <typename F>
-__device__ uint32_t pw_select(PwFixed& S, int n, int k, int lane, F key)
+__device__ uint32_t pw_select(lds_PwFixed& S, int n, int k, int lane, F key)
 {
     uint32_t prefix = 0;
     int kk = k;
@@ -366,10 +392,10 @@ __device__ uint32_t pw_select(PwFixed& S, int n, int k, int lane, F key)
         for (int b = 0; b < 4 * PW_HCOPIES; ++b) (&S.hist[0][0])[lane + 64 * b] = 0;
         wave_fence_lds();
         const uint32_t himask = (shift == 24) ? 0u : (~0u << (shift + 8));
-        uint32_t* const myh = S.hist[lane & (PW_HCOPIES - 1)];
+        lds_u32* const myh = S.hist[lane & (PW_HCOPIES - 1)];
         for (int i = lane; i < n; i += 64) {
             const uint32_t kx = key(i);
-            if ((kx & himask) == prefix) atomicAdd(&myh[(kx >> shift) & 255u], 1u);
+            if ((kx & himask) == prefix) lds_add(&myh[(kx >> shift) & 255u], 1u);
         }
         wave_fence_lds();
         uint32_t h[4];
@@ -405,7 +431,7 @@ __device__ uint32_t pw_select(PwFixed& S, int n, int k, int lane, F key)
 // Exact order statistics k_lo <= k_hi of exact(i) from a screen with |screen - exact| <= d.  Results in r0, r1;
 // false = the band does not fit (record must be flagged).
 template <typename FS, typename FE>
-__device__ bool pw_exact_stats(PwFixed& S, int n, int k_lo, int k_hi, double d, int lane, FS screen, FE exact,
+__device__ bool pw_exact_stats(lds_PwFixed& S, int n, int k_lo, int k_hi, double d, int lane, FS screen, FE exact,
                                double& r0, double& r1)
 {
     auto key = [&](int i) { return f32_key((float)screen(i)); };
@@ -495,7 +521,7 @@ __device__ __forceinline__ double key_f64(uint64_t k)
 }
 
 template <typename F>
-__device__ double pw_select64(PwFixed& S, int n, int k, int lane, F val)
+__device__ double pw_select64(lds_PwFixed& S, int n, int k, int lane, F val)
 {
     uint64_t prefix = 0;
     int kk = k;
@@ -504,10 +530,10 @@ __device__ double pw_select64(PwFixed& S, int n, int k, int lane, F val)
         for (int b = 0; b < 4 * PW_HCOPIES; ++b) (&S.hist[0][0])[lane + 64 * b] = 0;
         wave_fence_lds();
         const uint64_t himask = (shift == 56) ? 0ULL : (~0ULL << (shift + 8));
-        uint32_t* const myh = S.hist[lane & (PW_HCOPIES - 1)];
+        lds_u32* const myh = S.hist[lane & (PW_HCOPIES - 1)];
         for (int i = lane; i < n; i += 64) {
             const uint64_t kx = f64_key(val(i));
-            if ((kx & himask) == prefix) atomicAdd(&myh[(uint32_t)(kx >> shift) & 255u], 1u);
+            if ((kx & himask) == prefix) lds_add(&myh[(uint32_t)(kx >> shift) & 255u], 1u);
         }
         wave_fence_lds();
         uint32_t h[4];
@@ -540,15 +566,14 @@ __device__ double pw_select64(PwFixed& S, int n, int k, int lane, F val)
     return key_f64(prefix);
 }
 
-__device__ __noinline__ void sync_exact_row(PwFixed& S, int n, const double* yr, const double* tpl, long long rec, int lane,
-                                            const FusedArgs& fo)
+__device__ __noinline__ void sync_exact_row(lds_PwFixed& S, int n, glb_cdouble* yr, glb_cdouble* tpl, RowOut o, int lane)
 {
     const int min_distance = ES_FRAME_LEN / 2;
-    auto ex = [&](int i) { return corr64_at(yr, i, tpl); };
+    auto ex = [=](int i) { return corr64_at(yr, i, tpl); };
     double med;
     if (n & 1) med = pw_select64(S, n, n / 2, lane, ex);
     else { const double lo = pw_select64(S, n, n / 2 - 1, lane, ex), hi = pw_select64(S, n, n / 2, lane, ex); med = (lo + hi) / 2.0; }
-    auto dev = [&](int i) { return __builtin_fabs(corr64_at(yr, i, tpl) - med); };
+    auto dev = [=](int i) { return __builtin_fabs(corr64_at(yr, i, tpl) - med); };
     double mad;
     if (n & 1) mad = pw_select64(S, n, n / 2, lane, dev);
     else { const double lo = pw_select64(S, n, n / 2 - 1, lane, dev), hi = pw_select64(S, n, n / 2, lane, dev); mad = (lo + hi) / 2.0; }
@@ -574,7 +599,7 @@ __device__ __noinline__ void sync_exact_row(PwFixed& S, int n, const double* yr,
                 if (__ballot((j < hi) && ex(j) > cv)) bigger = true;
             }
             if (bigger) continue;
-            if (lane == 0 && total < ES_MAX_PEAKS) fo.peaks[rec * ES_MAX_PEAKS + total] = ci;
+            if (lane == 0 && total < ES_MAX_PEAKS) o.peaks[total] = ci;
             ++total;
         }
     }
@@ -598,20 +623,20 @@ __device__ __noinline__ void sync_exact_row(PwFixed& S, int n, const double* yr,
             }
             #pragma unroll
             for (int qd = 0; qd < 5; ++qd) if (qd == r) taken[qd] = bi;
-            if (lane == 0) fo.peaks[rec * ES_MAX_PEAKS + r] = bi;
+            if (lane == 0) o.peaks[r] = bi;
         }
-        if (lane == 0) fo.npeaks[rec] = kmax | (1 << 30);
+        if (lane == 0) *o.npeaks = kmax | (1 << 30);
         total = kmax;
     } else if (lane == 0) {
-        fo.npeaks[rec] = total;
+        *o.npeaks = total;
     }
-    if (lane >= total && lane < ES_MAX_PEAKS) fo.peaks[rec * ES_MAX_PEAKS + lane] = -1;
-    if (lane == 0) fo.thr[rec] = thr;
+    if (lane >= total && lane < ES_MAX_PEAKS) o.peaks[lane] = -1;
+    if (lane == 0) *o.thr = thr;
 }
 
 // ------------------------------------------------------------------------------------ fused sync: threshold + peaks of one row
-// One wave, the float32 screen row c[0..n) in LDS.  Same decisions as es_pick_exact_wave_kernel (hence as the float64
-// path), reached with far fewer passes over the row in the common case:
+// One wave, the float32 screen row c[0..n) in LDS: the fused kernel's own row, or the corr32 row es_pick_exact_wave_kernel
+// copies there.  Same decisions as the float64 path (es_pick_kernel), reached with few passes over the row in the common case:
 //   * ONE linear 256-bin histogram of the row (bins of 1/128 over [-1, 1): correlation values spread over them, so the
 //     LDS atomics hardly collide -- the radix select's first digit, sign + exponent, takes a handful of values).
 //   * Saturation test.  thr = min(med + 4.5 * 1.4826 * MAD, 0.95).  The histogram brackets the median,
@@ -620,27 +645,26 @@ __device__ __noinline__ void sync_exact_row(PwFixed& S, int n, const double* yr,
 //     n - k_lo values are that far out, the k_lo-th absolute deviation -- hence the MAD -- is >= r_j.  When
 //     lo(bl) - d + 6.6717 * r_j >= 0.95 + 1e-6 the minimum is 0.95 whatever the exact median and MAD are, and neither
 //     is computed.  (Band-passed noise, and clean frames too, have MAD ~0.2: the threshold saturates on every workload of
-//     BASELINE.json; records where it does not take the exact order statistics of es_pick_exact_wave_kernel.)
+//     BASELINE.json; records where it does not take the exact order statistics, pw_exact_stats.)
 //   * Threshold crossers are looked for only if the histogram has a value at or above thr - d.
 //   * Fallback (no peak): the five largest exact correlations lie among the screen values >= lo(b*) - 2d, b* = the
 //     highest bin with at least five values at or above it -- read off the histogram, no selection pass.
-// Flags (record redone by the float64 kernels): 1 non-finite screen, 2/3 order-statistic band too wide, 4 too many rivals
-// of a candidate within DELTA, 5 fallback list too long.
-__device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, const double* tpl, long long rec, int lane,
-                              const FusedArgs& fo)
+// Flags (record settled by sync_exact_row): 1 non-finite screen, 2/3 order-statistic band too wide, 4 too many rivals
+// of a candidate within DELTA, 5 fallback list too long; 0 = settled from the screen.
+__device__ void sync_pick_row(lds_PwFixed& S, lds_float* c, int n, glb_cdouble* yr, glb_cdouble* tpl, RowOut o, int lane)
 {
     const int min_distance = ES_FRAME_LEN / 2;
     // a record the screen cannot settle: reason code to flags (informational), then the exact row by this same wave
     auto flag_out = [&](int code) {
-        if (lane == 0) fo.flags[rec] = (uint8_t)code;
+        if (lane == 0) *o.flag = (uint8_t)code;
         wave_fence_lds();
-        sync_exact_row(S, n, yr, tpl, rec, lane, fo);
+        sync_exact_row(S, n, yr, tpl, o, lane);
     };
-    auto exact_corr = [&](int i) { return corr64_at(yr, i, tpl); };
+    auto exact_corr = [=](int i) { return corr64_at(yr, i, tpl); };
     const int k_hi = n / 2, k_lo = (n & 1) ? n / 2 : n / 2 - 1;
     constexpr double BINW = 1.0 / 128.0;
     constexpr double MARG = 2.5 * DELTA;                                // screen error both ways + float32 binning slack
-    uint32_t* const cum = reinterpret_cast<uint32_t*>(S.val);           // cum[b] = number of values in bins < b, b = 0..256
+    lds_u32* const cum = reinterpret_cast<lds_u32*>(S.val);             // cum[b] = number of values in bins < b, b = 0..256
 
     // ---- histogram
     #pragma unroll
@@ -648,7 +672,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
     wave_fence_lds();
     int bad = 0;
     {
-        uint32_t* const myh = S.hist[lane & (PW_HCOPIES - 1)];
+        lds_u32* const myh = S.hist[lane & (PW_HCOPIES - 1)];
         for (int i0 = lane; i0 < n; i0 += 64 * 8) {                     // eight row values read before the first histogram update (LDS reads
             float v8[8];                                                //  and LDS atomics: in a plain loop each read waited behind the last update)
             #pragma unroll
@@ -660,7 +684,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
                     bad |= !(__builtin_fabsf(v) < 1e30f);               // inf / nan / absurd: screen unusable
                     int b = (int)((v + 1.0f) * 128.0f);
                     b = b < 0 ? 0 : (b > 255 ? 255 : b);
-                    atomicAdd(&myh[b], 1u);
+                    lds_add(&myh[b], 1u);
                 }
             }
         }
@@ -710,10 +734,10 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
             thr = 0.95;
         } else {
             double r0, r1;
-            if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [&](int i) { return (double)c[i]; }, exact_corr, r0, r1)) { flag_out(2); return; }
+            if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [=](int i) { return (double)c[i]; }, exact_corr, r0, r1)) { flag_out(2); return; }
             const double med = (n & 1) ? r0 : (r0 + r1) / 2.0;
-            if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [&](int i) { return __builtin_fabs((double)c[i] - med); },
-                                [&](int i) { return __builtin_fabs(corr64_at(yr, i, tpl) - med); }, r0, r1)) { flag_out(3); return; }
+            if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [=](int i) { return __builtin_fabs((double)c[i] - med); },
+                                [=](int i) { return __builtin_fabs(corr64_at(yr, i, tpl) - med); }, r0, r1)) { flag_out(3); return; }
             const double mad = ((n & 1) ? r0 : (r0 + r1) / 2.0) + 1e-12;
             thr = med + 4.5 * 1.4826 * mad;
             if (0.95 < thr) thr = 0.95;
@@ -721,7 +745,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
         }
     }
 
-    // ---- threshold crossers in ascending order; each one is settled exactly (as in es_pick_exact_wave_kernel)
+    // ---- threshold crossers in ascending order; each one is settled exactly
     int total = 0;
     bool overflow = false;
     bool any_cross = true;
@@ -730,7 +754,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
         bt = bt < 0 ? 0 : (bt > 255 ? 255 : bt);
         any_cross = cum[256] - cum[bt] > 0;
     }
-    double* const stage = reinterpret_cast<double*>(&S.hist[0][0]);    // the histogram copies are dead from here on (a later select rebuilds them): corr64_list's windows
+    lds_double* const stage = reinterpret_cast<lds_double*>(&S.hist[0][0]);   // the histogram copies are dead from here on (a later select rebuilds them): corr64_list's windows
     auto lane_f64 = [](double v, int src) {                             // v of lane `src` (wave-uniform)
         const uint64_t u = __builtin_bit_cast(uint64_t, v);
         const uint32_t lo = (uint32_t)es_wave_read_lane((int)(uint32_t)u, src), hi = (uint32_t)es_wave_read_lane((int)(uint32_t)(u >> 32), src);
@@ -768,7 +792,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
                 corr64_list(stage, namb, yr, n, tpl, lane, [&](int w) { return S.list[w]; }, [&](int, double jv) { beats |= jv > cv; });
                 if (__ballot(beats)) return;
             }
-            if (lane == 0 && total < ES_MAX_PEAKS) fo.peaks[rec * ES_MAX_PEAKS + total] = ci;
+            if (lane == 0 && total < ES_MAX_PEAKS) o.peaks[total] = ci;
             ++total;
         };
         for (int g0 = 0; g0 < nc && !overflow; g0 += XL_G) {            // the chunk's candidates, XL_G exact values at a time (value of candidate g0 + w in lane w)
@@ -792,7 +816,7 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
             const int bstar = es_wave_read_lane(mine, 63 - (int)__builtin_clzll(m));      // bin 0 always qualifies (n >= kmax)
             lo = (bstar == 0) ? -1e300 : (-1.0 + bstar * BINW) - 2.0 * DELTA - 1e-6;
         } else {
-            const float t5 = key_f32(pw_select(S, n, n - kmax, lane, [&](int i) { return f32_key(c[i]); }));
+            const float t5 = key_f32(pw_select(S, n, n - kmax, lane, [=](int i) { return f32_key(c[i]); }));
             lo = (double)t5 - 2.0 * DELTA;
         }
         int nb = 0;
@@ -815,145 +839,37 @@ __device__ void sync_pick_row(PwFixed& S, float* c, int n, const double* yr, con
                 const double vj = S.val[j]; const int ij = S.list[j];
                 before += (vj > v) || (vj == v && ij > ii);
             }
-            if (before < kmax) fo.peaks[rec * ES_MAX_PEAKS + before] = ii;
+            if (before < kmax) o.peaks[before] = ii;
         }
-        if (lane == 0) fo.npeaks[rec] = kmax | (1 << 30);
+        if (lane == 0) *o.npeaks = kmax | (1 << 30);
         total = kmax;
         wave_fence_lds();
     } else if (lane == 0) {
-        fo.npeaks[rec] = total;
+        *o.npeaks = total;
     }
-    if (lane >= total && lane < ES_MAX_PEAKS) fo.peaks[rec * ES_MAX_PEAKS + lane] = -1;         // unused tail of the row
-    if (lane == 0) { fo.thr[rec] = thr; fo.flags[rec] = 0; }
+    if (lane >= total && lane < ES_MAX_PEAKS) o.peaks[lane] = -1;                               // unused tail of the row
+    if (lane == 0) { *o.thr = thr; *o.flag = 0; }
 }
 
-__global__ __launch_bounds__(64 * PW_WAVES) void es_pick_exact_wave_kernel(const float* __restrict__ corr32,
-        const double* __restrict__ y, long long B, int T, const uint8_t* __restrict__ band,
-        const es_band_tables* __restrict__ tabs, double* __restrict__ thr_out, int32_t* __restrict__ peaks,
-        int32_t* __restrict__ npeaks, uint8_t* __restrict__ flags)
+// The two-kernel form's picker: a wave copies a record's corr32 row into its LDS row (the layout of a fused-sync wave without the
+// staged samples: PwFixed, then the row) and settles it with the same sync_pick_row.  The picker is compiled once for all its
+// callers, to the register budget of the most demanding one: this kernel asks for the fused kernel's XF_MIN_WAVES so as not to
+// loosen it.
+__global__ __launch_bounds__(64 * PW_WAVES, XF_MIN_WAVES) void es_pick_exact_wave_kernel(const float* __restrict__ corr32, long long B, int T,
+        const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs, FusedArgs fo)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char pw_smem[];
     const int n = T - (ES_PRE_L - 1);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __builtin_amdgcn_s_setprio(2);      // front-end kernel: issue ahead of a resident list-decoder wave
-    const size_t per_wave = sizeof(PwFixed) + (((size_t)n * 4 + 15) & ~(size_t)15);
-    PwFixed& S = *reinterpret_cast<PwFixed*>(pw_smem + wv * per_wave);
-    float* const c = reinterpret_cast<float*>(pw_smem + wv * per_wave + sizeof(PwFixed));
-    const int min_distance = ES_FRAME_LEN / 2;
+    lds_PwFixed& S = *reinterpret_cast<lds_PwFixed*>((lds_u8*)pw_smem + wv * xf_lds_per_wave(0, n));
+    lds_float* const c = reinterpret_cast<lds_float*>(&S) + xf_head_floats(0);
     const long long stride = (long long)gridDim.x * PW_WAVES;
     for (long long rec = (long long)blockIdx.x * PW_WAVES + wv; rec < B; rec += stride) {
         const float* cg = corr32 + rec * n;
-        const double* yr = y + rec * T;
-        const double* tpl = tabs->tpl[band[rec]];
-        int bad = 0;
-        for (int i = lane; i < n; i += 64) {
-            const float v = cg[i];
-            c[i] = v;
-            bad |= !(__builtin_fabsf(v) < 1e30f);                       // inf / nan / absurd: screen unusable
-        }
+        for (int i = lane; i < n; i += 64) c[i] = cg[i];
         wave_fence_lds();
-        if (__ballot(bad)) { if (lane == 0) flags[rec] = 1; continue; }   // reason 1: non-finite screen
-        auto exact_corr = [&](int i) { return corr64_at(yr, i, tpl); };
-        const int k_hi = n / 2, k_lo = (n & 1) ? n / 2 : n / 2 - 1;
-
-        // ---- median and MAD (exact)
-        double r0, r1;
-        if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [&](int i) { return (double)c[i]; }, exact_corr, r0, r1)) {
-            if (lane == 0) flags[rec] = 2;                               // reason 2: median band too wide
-            continue;
-        }
-        const double med = (n & 1) ? r0 : (r0 + r1) / 2.0;
-        if (!pw_exact_stats(S, n, k_lo, k_hi, DELTA, lane, [&](int i) { return __builtin_fabs((double)c[i] - med); },
-                            [&](int i) { return __builtin_fabs(corr64_at(yr, i, tpl) - med); }, r0, r1)) {
-            if (lane == 0) flags[rec] = 3;                               // reason 3: MAD band too wide
-            continue;
-        }
-        const double mad = ((n & 1) ? r0 : (r0 + r1) / 2.0) + 1e-12;
-        double thr = med + 4.5 * 1.4826 * mad;
-        if (0.95 < thr) thr = 0.95;
-
-        // ---- threshold crossers in ascending order; each one is settled exactly
-        int total = 0;
-        bool overflow = false;
-        for (int base = 0; base < n && !overflow; base += 64) {
-            const int i = base + lane;
-            const bool cand = (i < n) && ((double)c[i] >= thr - DELTA);
-            unsigned long long m = __ballot(cand);
-            if (!m) continue;
-            const double cv_mine = cand ? corr64_at(yr, i, tpl) : 0.0;   // all candidates of the chunk at once
-            while (m && !overflow) {
-                const int bit = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const int ci = base + bit;
-                const double cv = __shfl(cv_mine, bit);
-                if (cv < thr) continue;
-                int lo = ci - min_distance; if (lo < 0) lo = 0;
-                int hi = ci + min_distance + 1; if (hi > n) hi = n;
-                bool bigger = false;
-                int namb = 0;
-                for (int j0 = lo; j0 < hi && !bigger; j0 += 64) {
-                    const int j = j0 + lane;
-                    const bool in = j < hi;
-                    const double s32 = in ? (double)c[j] : 0.0;
-                    const bool big = in && s32 > cv + DELTA;
-                    const bool amb = in && !big && s32 >= cv - DELTA && j != ci;   // rival within reach: settle exactly
-                    if (__ballot(big)) { bigger = true; break; }
-                    const unsigned long long ma = __ballot(amb);
-                    const int pos = namb + lanes_below(ma);
-                    if (amb && pos < 64) S.list[pos] = j;
-                    namb += __popcll(ma);
-                }
-                if (bigger) continue;
-                if (namb > 64) { overflow = true; break; }
-                if (namb > 0) {
-                    wave_fence_lds();
-                    const bool have = lane < namb;
-                    const double jv = have ? corr64_at(yr, S.list[lane], tpl) : 0.0;
-                    const bool beats = have && jv > cv;
-                    wave_fence_lds();
-                    if (__ballot(beats)) continue;
-                }
-                if (lane == 0 && total < ES_MAX_PEAKS) peaks[rec * ES_MAX_PEAKS + total] = ci;
-                ++total;
-            }
-        }
-        if (overflow) { if (lane == 0) flags[rec] = 4; continue; }       // reason 4: too many rivals within DELTA
-
-        if (total == 0) {
-            // ---- fallback: five largest exact correlations (descending; equal values -> higher index)
-            const int kmax = n < 5 ? n : 5;
-            const float t5 = key_f32(pw_select(S, n, n - kmax, lane, [&](int i) { return f32_key(c[i]); }));
-            const double lo = (double)t5 - 2.0 * DELTA;
-            int nb = 0;
-            for (int i0 = 0; i0 < n; i0 += 64) {
-                const int i = i0 + lane;
-                const bool in = (i < n) && ((double)c[i] >= lo);
-                const unsigned long long mb = __ballot(in);
-                const int pos = nb + lanes_below(mb);
-                if (in && pos < PW_CAP) S.list[pos] = i;
-                nb += __popcll(mb);
-            }
-            if (nb > PW_CAP) { if (lane == 0) flags[rec] = 5; continue; }   // reason 5: fallback list too long
-            wave_fence_lds();
-            for (int idx = lane; idx < nb; idx += 64) S.val[idx] = corr64_at(yr, S.list[idx], tpl);
-            wave_fence_lds();
-            for (int idx = lane; idx < nb; idx += 64) {
-                const double v = S.val[idx]; const int ii = S.list[idx];
-                int before = 0;                                          // how many sort ahead of me
-                for (int j = 0; j < nb; ++j) {
-                    const double vj = S.val[j]; const int ij = S.list[j];
-                    before += (vj > v) || (vj == v && ij > ii);
-                }
-                if (before < kmax) peaks[rec * ES_MAX_PEAKS + before] = ii;
-            }
-            if (lane == 0) npeaks[rec] = kmax | (1 << 30);
-            total = kmax;
-            wave_fence_lds();
-        } else if (lane == 0) {
-            npeaks[rec] = total;
-        }
-        if (lane >= total && lane < ES_MAX_PEAKS) peaks[rec * ES_MAX_PEAKS + lane] = -1;        // unused tail of the row
-        if (lane == 0) { thr_out[rec] = thr; flags[rec] = 0; }
+        sync_pick_row(S, c, n, (glb_cdouble*)fo.y64 + rec * T, (glb_cdouble*)tabs->tpl[band[rec]], row_out(fo, rec), lane);
     }
 }
 
@@ -990,19 +906,17 @@ int es_launch_pick_exact(es_ctx* ctx, const float* corr32, const double* y, int6
                          double* thr, int32_t* peaks, int32_t* npeaks, uint8_t* flags, hipStream_t st)
 {
     if (T - (ES_PRE_L - 1) > PX_MAXN) { ctx->err = "es_pick_exact_batch: more than 4096 lags; use the float64 path"; return ES_EINVAL; }
-    const int n = T - (ES_PRE_L - 1);
-    const size_t per_wave = sizeof(PwFixed) + (((size_t)n * 4 + 15) & ~(size_t)15);
-    const size_t lds = per_wave * PW_WAVES;
+    const size_t lds = PW_WAVES * xf_lds_per_wave(0, T - (ES_PRE_L - 1));
     if (!ctx->pick_attr_set) {           // per context (= per device): the attribute belongs to the device's copy of the kernel
         ES_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&es_pick_exact_wave_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PW_WAVES * (sizeof(PwFixed) + PX_MAXN * 4))));
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PW_WAVES * xf_lds_per_wave(0, PX_MAXN))));
         ctx->pick_attr_set = true;
     }
     long long blocks = (B + PW_WAVES - 1) / PW_WAVES;
     const long long cap = (long long)ctx->num_cu * 16;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_pick_exact_wave_kernel, dim3((unsigned)blocks), dim3(64 * PW_WAVES), lds, st, corr32, y, (long long)B, T,
-                       band, ctx->d_tables, thr, peaks, npeaks, flags);
+    hipLaunchKernelGGL(es_pick_exact_wave_kernel, dim3((unsigned)blocks), dim3(64 * PW_WAVES), lds, st, corr32, (long long)B, T,
+                       band, ctx->d_tables, FusedArgs{y, thr, peaks, npeaks, flags});
     ES_HIP_CHECK(ctx, hipGetLastError());
     return ES_OK;
 }

@@ -87,7 +87,7 @@ class SyncResult:
     peaks: torch.Tensor        # [B,32] int32
     npeaks: torch.Tensor       # [B] int32 (count; bit 30 = fallback branch)
     corr32: torch.Tensor | None = None   # float32 screen (sync_fast only)
-    flags: torch.Tensor | None = None    # records redone in float64 (sync_fast only)
+    flags: torch.Tensor | None = None    # reason code 1..5 of records settled from float64 values alone, else 0 (sync_fast only)
     y32: torch.Tensor | None = None
 
 
@@ -185,7 +185,7 @@ class RxEngine:
         return corr
 
     def pick_exact(self, corr32: torch.Tensor, y: torch.Tensor, band: torch.Tensor):
-        """thr / peaks / npeaks identical to pick(xcorr(y)); also returns the per-record redo flags."""
+        """thr / peaks / npeaks identical to pick(xcorr(y)); also returns the per-record flags (reason codes 1..5, 0 = settled from the screen)."""
         B, T = y.shape
         thr = torch.empty(B, dtype=torch.float64, device=self.device)
         peaks = torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=self.device)     # the kernels write whole rows (-1 = unused)

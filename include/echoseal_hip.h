@@ -108,8 +108,10 @@ int es_pick_batch(es_ctx* ctx, const double* corr_dev, int64_t B, int n_lags, do
  *   es_xcorr32_batch     corr32_dev [B][T-62] float32 from y32_dev: 4 860 B in + 4 612 B out per
  *                        1215-sample record -- the HBM-graded kernel
  *   es_pick_exact_batch  thr/peaks/npeaks from corr32 with float64 re-evaluation of every value
- *                        near a decision; flags_dev [B] = 1 where the record had to be redone by the
- *                        float64 kernels (done inside the call).  T - 62 <= 4096.                   */
+ *                        near a decision, by the picker of es_sync_fused_batch (same results, flags
+ *                        included); records the screen cannot settle are settled from float64
+ *                        re-evaluations alone, and flags_dev [B] holds the reason code 1..5 (0 =
+ *                        settled from the screen), for information.  No workspace.  T - 62 <= 4096. */
 int es_bpf2_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T,
                   const uint8_t* band_dev, double* y_dev, float* y32_dev, void* stream);
 int es_xcorr32_batch(es_ctx* ctx, const float* y32_dev, int64_t B, int T, const uint8_t* band_dev,
@@ -139,10 +141,10 @@ int es_front_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, in
                    const uint8_t* pn_dev, const int32_t* start_dev, double* y_dev, float* y32_dev, double* thr_dev,
                    int32_t* peaks_dev, int32_t* npeaks_dev, uint8_t* flags_dev, float* llr_dev, void* stream);
 
-/* Size the context's float64 correlation workspace (used by es_sync_batch without corr_dev, and by the redo pass of
- * es_pick_exact_batch) for batches of up to B_max records of T_max samples.  Allocation synchronises
- * the device: call this once, outside any stream capture; afterwards those entry points only enqueue.  Without it they
- * grow the workspace themselves the first time a larger batch arrives (same effect as calling es_reserve there).
+/* Size the context's float64 correlation workspace (used by es_sync_batch without corr_dev) for batches of up to B_max
+ * records of T_max samples.  Allocation synchronises the device: call this once, outside any stream capture; afterwards
+ * es_sync_batch only enqueues.  Without it es_sync_batch grows the workspace itself the first time a larger batch arrives
+ * (same effect as calling es_reserve there).
  * es_reserve does not cover the list decoder: its slabs are allocated by es_create, and the 1.6 GB lane-per-path slab of contexts with
  * list_size_max <= 32 by es_set_option "scl_lane_slab" / "scl_lanes" = 1 -- set those before the first enqueue-only call as well.
  * Streams: the float64 workspace is shared by every call on the context (one stream at a time for the entry points that use it).  The list
