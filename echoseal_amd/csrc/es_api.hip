@@ -300,6 +300,27 @@ int es_front_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, in
     return es_llr_batch(ctx, y_dev, B, T, start_dev, band_dev, pn_dev, 0, llr_dev, nullptr, nullptr, stream);
 }
 
+int es_front_peak_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T, const uint8_t* band_dev,
+                        const uint8_t* pn_dev, double* y_dev, float* y32_dev, double* thr_dev, int32_t* peaks_dev,
+                        int32_t* npeaks_dev, uint8_t* flags_dev, float* llr_dev, void* stream)
+{
+    /* es_bpf2_batch -> es_sync_fused_batch -> es_llr_at_batch at each record's first peak (peaks_dev[i * ES_MAX_PEAKS], -1 = none
+       read as 0), variant 0.  Every argument is checked before the first launch, so a bad call enqueues nothing. */
+    ES_REQUIRE_READY(ctx);
+    if (B < 0 || T < 0) return fail(ctx, ES_EINVAL, "es_front_peak_batch: negative size");
+    if (dtype != ES_DTYPE_F32 && dtype != ES_DTYPE_I16) return fail(ctx, ES_EINVAL, "es_front_peak_batch: dtype must be f32 or i16");
+    if (B == 0) return ES_OK;
+    if (T < ES_PRE_L) return fail(ctx, ES_EINVAL, "es_front_peak_batch: record shorter than the 63-chip template");
+    if (T - (ES_PRE_L - 1) > 4096) return fail(ctx, ES_EINVAL, "es_front_peak_batch: more than 4096 lags; use the float64 path");
+    if (!frames_dev || !band_dev || !pn_dev || !y_dev || !y32_dev || !thr_dev || !peaks_dev || !npeaks_dev || !flags_dev || !llr_dev)
+        return fail(ctx, ES_EINVAL, "es_front_peak_batch: null pointer");
+    int rc = es_bpf2_batch(ctx, frames_dev, dtype, B, T, band_dev, y_dev, y32_dev, stream);
+    if (rc != ES_OK) return rc;
+    rc = es_sync_fused_batch(ctx, y32_dev, y_dev, B, T, band_dev, thr_dev, peaks_dev, npeaks_dev, flags_dev, stream);
+    if (rc != ES_OK) return rc;
+    return es_llr_at_batch(ctx, y_dev, B, T, B, nullptr, peaks_dev, ES_MAX_PEAKS, band_dev, pn_dev, 0, llr_dev, nullptr, nullptr, stream);
+}
+
 int es_reserve(es_ctx* ctx, int64_t B_max, int T_max)
 {
     if (!ctx) return ES_EINVAL;
@@ -386,6 +407,38 @@ int es_header_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const in
     DeviceGuard g(ctx->device);
     return es_launch_header(ctx, y_dev, B, T, start_dev, band_dev, hdr_pn_dev, ok_dev, val_dev, score_dev,
                             best_s_dev, (hipStream_t)stream);
+}
+
+int es_llr_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int64_t B, const int32_t* row_dev,
+                    const int32_t* start_dev, int start_stride, const uint8_t* band_dev, const uint8_t* pn_dev, int variant,
+                    float* llr_dev, int32_t* best_s_dev, float* score_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (B < 0 || T < 0 || n_rows < 0) return fail(ctx, ES_EINVAL, "es_llr_at_batch: negative size");
+    if (start_stride < 1) return fail(ctx, ES_EINVAL, "es_llr_at_batch: start_stride must be >= 1");
+    if (variant != 0 && variant != 1) return fail(ctx, ES_EINVAL, "es_llr_at_batch: variant must be 0 or 1");
+    if (B == 0) return ES_OK;
+    if (n_rows < 1) return fail(ctx, ES_EINVAL, "es_llr_at_batch: no rows to read");
+    if (!y_dev || !band_dev || !pn_dev || !llr_dev) return fail(ctx, ES_EINVAL, "es_llr_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_llr_at(ctx, y_dev, n_rows, T, B, row_dev, start_dev, start_stride, band_dev, pn_dev, variant, llr_dev,
+                            best_s_dev, score_dev, (hipStream_t)stream);
+}
+
+int es_header_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int64_t B, const int32_t* row_dev,
+                       const int32_t* start_dev, int start_stride, const uint8_t* band_dev, const uint8_t* hdr_pn_dev,
+                       uint8_t* ok_dev, int32_t* val_dev, float* score_dev, int32_t* best_s_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (B < 0 || T < 0 || n_rows < 0) return fail(ctx, ES_EINVAL, "es_header_at_batch: negative size");
+    if (start_stride < 1) return fail(ctx, ES_EINVAL, "es_header_at_batch: start_stride must be >= 1");
+    if (B == 0) return ES_OK;
+    if (n_rows < 1) return fail(ctx, ES_EINVAL, "es_header_at_batch: no rows to read");
+    if (!y_dev || !band_dev || !hdr_pn_dev || !ok_dev || !val_dev || !score_dev)
+        return fail(ctx, ES_EINVAL, "es_header_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_header_at(ctx, y_dev, n_rows, T, B, row_dev, start_dev, start_stride, band_dev, hdr_pn_dev, ok_dev, val_dev,
+                               score_dev, best_s_dev, (hipStream_t)stream);
 }
 
 int es_scl_batch(es_ctx* ctx, const void* llr_dev, int dtype, int64_t B, int list_size,

@@ -153,5 +153,11 @@ int es_launch_select(es_ctx* ctx, const uint8_t* key32, const uint32_t* ctr, int
                      const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
+int es_launch_llr_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
+                     int start_stride, const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s, float* score,
+                     hipStream_t st);
+int es_launch_header_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
+                        int start_stride, const uint8_t* band, const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score,
+                        int32_t* best_s, hipStream_t st);
 
 #endif

@@ -280,11 +280,33 @@ __device__ unsigned long long g_llr_dbg[16];
 #define LLR_STAMP(k) do { } while (0)
 #endif
 
-template <int MAXT>
+// Record addressing.  AT = false (es_llr_batch / es_header_batch): record i is row i of y, its frame starts at start[i] (NULL = 0).
+// AT = true (the *_at entry points): record i is row r = row[i] (NULL = i) from s = max(start[i * start_stride], 0) (NULL = 0); a row
+// outside [0, n_rows) reads as a start at T, i.e. an empty frame, and nothing of y is read for it.  Band, PN rows and every output are
+// indexed by i in both.  The row offset is formed in 64 bits.
+template <bool AT>
+__device__ __forceinline__ void rec_addr(long long i, long long B, int T, const int32_t* __restrict__ start,
+        const int32_t* __restrict__ row, long long n_rows, int start_stride, int& st, long long& roff)
+{
+    if constexpr (!AT) {
+        st = (i < B && start) ? start[i] : 0;
+        roff = 0;                                                    // (unused: the row is the record, y + i * T at the point of use)
+    } else {
+        int s = (i < B && start) ? start[i * start_stride] : 0;
+        const long long r = (i < B && row) ? (long long)row[i] : i;
+        if (s < 0) s = 0;                                            // clamp(min=0) / decode_frame(start="peak")
+        const bool in = r >= 0 && r < n_rows;
+        st = in ? s : T;
+        roff = in ? r * T : 0;
+    }
+}
+
+template <int MAXT, bool AT>
 __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const double* __restrict__ y, long long B,
         int T, const int32_t* __restrict__ start, const uint8_t* __restrict__ band,
         const uint8_t* __restrict__ pn_rows, int variant, const es_band_tables* __restrict__ tabs,
-        float* __restrict__ llr, int32_t* __restrict__ best_s_out, float* __restrict__ score_out)
+        float* __restrict__ llr, int32_t* __restrict__ best_s_out, float* __restrict__ score_out,
+        const int32_t* __restrict__ row, long long n_rows, int start_stride)
 {
     constexpr int MAX_RX = LlrSizes<MAXT>::MAX_RX, MF_PAD = LlrSizes<MAXT>::MF_PAD;
     __shared__ __attribute__((aligned(16))) LlrWaveLds<MAXT> s_w[LW_WAVES];
@@ -298,7 +320,8 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
     const int nt0 = tabs->ntaps[0], nt1 = tabs->ntaps[1], nt2 = tabs->ntaps[2], nt3 = tabs->ntaps[3];
     static_assert(LW_WAVES == 1, "the record index below is the block index: wave-uniform by construction, so that the metadata loads are scalar");
     long long rec = (long long)blockIdx.x;
-    int st_next = (rec < B && start) ? start[rec] : 0;
+    int st_next; long long ro_next;
+    rec_addr<AT>(rec, B, T, start, row, n_rows, start_stride, st_next, ro_next);
     int bi_next = (rec < B) ? band[rec] : 0;
     for (; rec < B; rec += stride) {
 #ifdef ES_LLR_STAMPS
@@ -306,6 +329,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
 #endif
         float* out = llr + rec * NPAY;
         const int st0 = st_next;
+        const long long roff = ro_next;
         const int bi = bi_next;
         int flen = T - st0; if (flen > ES_FRAME_LEN) flen = ES_FRAME_LEN;
         const int ntaps = bi == 0 ? nt0 : bi == 1 ? nt1 : bi == 2 ? nt2 : nt3;
@@ -315,11 +339,11 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             for (int i = lane; i < NPAY; i += 64) out[i] = 0.0f;
             if (lane == 0) { if (best_s_out) best_s_out[rec] = 0; if (score_out) { score_out[2 * rec] = -1.0f; score_out[2 * rec + 1] = -1.0f; } }
             const long long nrec = rec + stride;                      // (the next record's metadata: see below)
-            st_next = (nrec < B && start) ? start[nrec] : 0;
+            rec_addr<AT>(nrec, B, T, start, row, n_rows, start_stride, st_next, ro_next);
             bi_next = (nrec < B) ? band[nrec] : 0;
             continue;
         }
-        const double* fr = y + rec * T + st0;
+        const double* fr = (AT ? y + roff : y + rec * T) + st0;
         const int prefix = mem < PAYLOAD_START ? mem : PAYLOAD_START; // :327
         const int nfull = prefix + npl;
         LLR_STAMP(8);
@@ -337,7 +361,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             for (int k = 0; k < (MF_PAD + 63) / 64; ++k) { const int i = lane + 64 * k; tp[k] = tabs->taps[bi][i < ntaps ? i : ntaps - 1]; }
             {   // the next record's metadata: scalar loads that complete under the wait for this record's samples
                 const long long nrec = rec + stride;
-                st_next = (nrec < B && start) ? start[nrec] : 0;
+                rec_addr<AT>(nrec, B, T, start, row, n_rows, start_stride, st_next, ro_next);
                 bi_next = (nrec < B) ? band[nrec] : 0;
             }
             for (int i = lane; i < MF_PAD; i += 64) { W.a.mf.rx[i] = 0.0f; W.a.mf.rx[MF_PAD + MAX_RX + i] = 0.0f; }
@@ -548,11 +572,12 @@ __device__ __forceinline__ float slot_leaf_sum(int n, int j, F get)
     return r;
 }
 
-template <int MAXT>
+template <int MAXT, bool AT>
 __global__ __launch_bounds__(64) void es_header_kernel(const double* __restrict__ y, long long B, int T,
         const int32_t* __restrict__ start, const uint8_t* __restrict__ band, const uint8_t* __restrict__ hdr_pn,
         const es_band_tables* __restrict__ tabs, uint8_t* __restrict__ ok_out, int32_t* __restrict__ val_out,
-        float* __restrict__ score_out, int32_t* __restrict__ best_s_out)
+        float* __restrict__ score_out, int32_t* __restrict__ best_s_out,
+        const int32_t* __restrict__ row, long long n_rows, int start_stride)
 {
     __shared__ float s_rx[ES_PRE_L + ES_HDR_L];
     constexpr int HD_MAXWIN = LlrSizes<MAXT>::HD_MAXWIN;
@@ -563,7 +588,8 @@ __global__ __launch_bounds__(64) void es_header_kernel(const double* __restrict_
     __shared__ float s_sums[16];
     const int lane = threadIdx.x;
     for (long long rec = blockIdx.x; rec < B; rec += gridDim.x) {
-        const int st0 = start ? start[rec] : 0;
+        int st0; long long roff;
+        rec_addr<AT>(rec, B, T, start, row, n_rows, start_stride, st0, roff);
         const int flen = T - st0;
         if (st0 < 0 || flen < ES_PRE_L + ES_HDR_L) {                   // :461-462
             if (lane == 0) { ok_out[rec] = 0; val_out[rec] = 0; score_out[rec] = 0.0f; if (best_s_out) best_s_out[rec] = 0; }
@@ -574,7 +600,7 @@ __global__ __launch_bounds__(64) void es_header_kernel(const double* __restrict_
         const int mem = ntaps - 1;
         const int prefix = mem < ES_PRE_L ? mem : ES_PRE_L;            // :466
         const int nfull = prefix + ES_HDR_L;
-        const double* fr = y + rec * T + st0;
+        const double* fr = (AT ? y + roff : y + rec * T) + st0;
         for (int i = lane; i < nfull; i += 64) s_rx[i] = (float)fr[ES_PRE_L - prefix + i];
         for (int i = lane; i < ntaps; i += 64) s_h[i] = tabs->taps[bi][i];
         const uint8_t* pnr = hdr_pn + rec * (ES_HDR_L / 8);
@@ -659,11 +685,11 @@ int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t*
     const long long cap = (long long)ctx->num_cu * 64 / LW_WAVES;
     if (blocks > cap) blocks = cap;
     if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL(es_llr_wave_kernel<ES_MAX_TAPS_FAST>, dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score);
+        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS_FAST, false>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
+                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, nullptr, 0LL, 1);
     else                                                                      // long matched filters (fs_target other than 48 000): 41 KB of LDS per wave
-        hipLaunchKernelGGL(es_llr_wave_kernel<ES_MAX_TAPS>, dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score);
+        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS, false>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
+                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, nullptr, 0LL, 1);
 #ifdef ES_LLR_STAMPS
     {   // diagnostic build only: share of the phases, summed over the records of this launch
         unsigned long long h[16]; static const unsigned long long z[16] = {0};
@@ -686,11 +712,46 @@ int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32
     const long long cap = (long long)ctx->num_cu * 32;
     if (blocks > cap) blocks = cap;
     if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL(es_header_kernel<ES_MAX_TAPS_FAST>, dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s);
+        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS_FAST, false>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
+                           hdr_pn, ctx->d_tables, ok, val, score, best_s, nullptr, 0LL, 1);
     else
-        hipLaunchKernelGGL(es_header_kernel<ES_MAX_TAPS>, dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s);
+        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS, false>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
+                           hdr_pn, ctx->d_tables, ok, val, score, best_s, nullptr, 0LL, 1);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+// The peak-addressed forms (es_llr_at_batch / es_header_at_batch): the same kernels and grids, record i read at (row[i], start[i * stride]).
+int es_launch_llr_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
+                     int start_stride, const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s, float* score,
+                     hipStream_t st)
+{
+    long long blocks = (B + LW_WAVES - 1) / LW_WAVES;
+    const long long cap = (long long)ctx->num_cu * 64 / LW_WAVES;
+    if (blocks > cap) blocks = cap;
+    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
+        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS_FAST, true>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
+                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, row, (long long)n_rows, start_stride);
+    else
+        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS, true>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
+                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, row, (long long)n_rows, start_stride);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+int es_launch_header_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
+                        int start_stride, const uint8_t* band, const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score,
+                        int32_t* best_s, hipStream_t st)
+{
+    long long blocks = B;
+    const long long cap = (long long)ctx->num_cu * 32;
+    if (blocks > cap) blocks = cap;
+    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
+        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS_FAST, true>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
+                           hdr_pn, ctx->d_tables, ok, val, score, best_s, row, (long long)n_rows, start_stride);
+    else
+        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS, true>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
+                           hdr_pn, ctx->d_tables, ok, val, score, best_s, row, (long long)n_rows, start_stride);
     ES_HIP_CHECK(ctx, hipGetLastError());
     return ES_OK;
 }

@@ -4,8 +4,8 @@ Host orchestration (band order, counter candidates, AEAD validation, anti-replay
 Python as in the reference; every numeric stage runs on the GPU through echoseal_amd.engine:
 
     _scan_band_multi_frame  -> es_bpf / es_xcorr / es_pick        (rtwm/detector.py:59-99)
-    _decode_header          -> es_header_batch                    (rtwm/detector.py:452-515)
-    _llr                    -> es_llr_batch                       (rtwm/detector.py:296-416)
+    _decode_header          -> es_header_batch, es_header_at_batch at the peaks of a scan (rtwm/detector.py:452-515)
+    _llr                    -> es_llr_batch, es_llr_at_batch at the peaks of a scan       (rtwm/detector.py:296-416)
     polar decode            -> es_scl_batch + host validator scan (rtwm/fastpolar.py:254-359)
 
 Constructing a detector needs no GPU (keys, static sequences); the first numeric call creates the
@@ -35,6 +35,15 @@ EPS = 1e-12
 
 MAX_TRIES = 400          # rtwm/detector.py:107
 PEAK_LIMIT = 25          # rtwm/detector.py:108
+
+
+class _Frames:
+    """Where the frames of a scan lie, without copying them: frame j = y[rows[j], starts[j] : starts[j] + 1215] of the band-passed
+    records y (device, float64), read in place by es_header_at_batch / es_llr_at_batch.  rows, starts: host int arrays."""
+    __slots__ = ("y", "rows", "starts")
+
+    def __init__(self, y, rows: np.ndarray, starts: np.ndarray) -> None:
+        self.y, self.rows, self.starts = y, rows, starts
 
 
 class WatermarkDetector:
@@ -148,7 +157,7 @@ class WatermarkDetector:
                         break
                     batch.append((j, r)); n += m
                 flat = [(j, p) for (j, r) in batch for p in plans[j][r][0]]
-                res = self._decode_pairs_grouped([(scans[j]["frames"], p[0], p[2]) for j, p in flat]) if flat else []
+                res = self._decode_pairs_grouped([(scans[j]["src"], p[0], p[2]) for j, p in flat]) if flat else []
                 at = 0
                 for (j, r) in batch:
                     m = len(plans[j][r][0])
@@ -173,7 +182,8 @@ class WatermarkDetector:
         eng = self.engine
         g, nb, M = len(signals), len(bands), signals[0].size
         x = self._dev(np.repeat(np.stack(signals), nb, axis=0), signals[0].dtype)      # row = clip * nb + band (float32, or int16 samples)
-        bid = self._dev(np.tile(np.array([self._band_id(b) for b in bands]), g), np.uint8)
+        bid_h = np.tile(np.array([self._band_id(b) for b in bands], np.uint8), g)
+        bid = self._dev(bid_h, np.uint8)
         sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
         npk = (sy.npeaks.cpu().numpy() & 0xFFFF)
         pk = sy.peaks.cpu().numpy()
@@ -182,17 +192,17 @@ class WatermarkDetector:
             for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
                 if st + FRAME_LEN <= M:                                     # rtwm/detector.py:112-113
                     rows.append(r); starts.append(int(st))
-        frames = None
+        src = None
         hdr = (np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0))
-        if rows:
-            rt = torch.tensor(rows, device=eng.device)
-            cols = torch.tensor(starts, device=eng.device)[:, None] + torch.arange(FRAME_LEN, device=eng.device)[None, :]
-            frames = sy.y[rt[:, None], cols].contiguous()                  # [P, 1215] float64: y[start : start + 1215]
-            okh, val, score = eng.header(frames, bid[rt].contiguous(),
-                                         self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8))
-            hdr = (okh.cpu().numpy().astype(bool), val.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64))
         rows_a = np.array(rows, np.int64)
-        return [{"bands": bands, "frames": frames, "rows": rows_a - c * nb, "sel": np.flatnonzero((rows_a // nb) == c) if rows else np.zeros(0, np.int64),
+        if rows:
+            # frame j = sy.y[rows[j], starts[j] : starts[j] + 1215], read in place (no [P, 1215] copy)
+            src = _Frames(sy.y, rows_a, np.array(starts, np.int64))
+            okh, val, score = eng.header(sy.y, self._dev(bid_h[rows_a], np.uint8),
+                                         self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8),
+                                         rows=self._dev(rows_a, np.int32), start=self._dev(src.starts, np.int32))
+            hdr = (okh.cpu().numpy().astype(bool), val.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64))
+        return [{"bands": bands, "src": src, "rows": rows_a - c * nb, "sel": np.flatnonzero((rows_a // nb) == c) if rows else np.zeros(0, np.int64),
                  "starts": np.array(starts, np.int64), "hdr": hdr} for c in range(g)]
 
     def _scan_plan(self, scan, bi: int):
@@ -249,7 +259,7 @@ class WatermarkDetector:
             if self._hdr_trace is not None:
                 self._hdr_trace.extend(hdr_log)
             return False
-        results = self._decode_pairs(scan["frames"], [p[0] for p in plan], [p[2] for p in plan])
+        results = self._decode_pairs(scan["src"], [p[0] for p in plan], [p[2] for p in plan])
         return self._scan_replay(scan, bi, plan, hdr_log, results)
 
     def verify_raw_frame(self, signal: np.ndarray) -> bool:
@@ -342,12 +352,12 @@ class WatermarkDetector:
         ctrs = list(ctrs)
         if not ctrs:
             return []
-        frames = self._dev(np.asarray(frame, dtype=np.float64).reshape(1, -1), np.float64)
-        return self._decode_pairs(frames, [0] * len(ctrs), ctrs)
+        y = self._dev(np.asarray(frame, dtype=np.float64).reshape(1, -1), np.float64)
+        return self._decode_pairs(_Frames(y, np.zeros(1, np.int64), np.zeros(1, np.int64)), [0] * len(ctrs), ctrs)
 
     def _decode_pairs_grouped(self, triples) -> list[list[bytes | None]]:
-        """_decode_pairs for (frames tensor, row, ctr) triples that may come from several clips (each clip has its own
-        frames tensor): consecutive triples of one tensor go through one call."""
+        """_decode_pairs for (frames, frame index, ctr) triples that may come from several clips (each group of equally long clips
+        has its own _Frames): consecutive triples of one _Frames go through one call."""
         out: list = []
         k = 0
         while k < len(triples):
@@ -375,9 +385,10 @@ class WatermarkDetector:
         return out
 
     def _decode_pairs_chunk(self, frames, rows, ctrs) -> list[list[bytes | None]]:
-        """The same for (frame, counter) pairs: frames = device tensor [P, <=1215] float64, pair i = (frames[rows[i]], ctrs[i]).
-        One batch: two demodulations (PN variants 0 / 1), one list decode of the 4 B sign / variant combinations, one
-        validation + selection (es_select_batch with the AEAD key) -- no host round trip per candidate."""
+        """The same for (frame, counter) pairs: frames = _Frames, pair i = (frame rows[i] of it, ctrs[i]).
+        One batch: two demodulations (PN variants 0 / 1) read in place at the frames' (row, start), one list decode of the 4 B
+        sign / variant combinations, one validation + selection (es_select_batch with the AEAD key) -- no host round trip per
+        candidate."""
         from .engine import select_payload
         import torch
         eng = self.engine
@@ -385,11 +396,12 @@ class WatermarkDetector:
         if L > eng.list_size_max:
             raise NotImplementedError(f"list_size={L}: the HIP decoder supports list sizes up to {eng.list_size_max}")
         B = len(ctrs)
-        y = frames[torch.tensor(rows, device=eng.device)].contiguous()
+        j = np.asarray(rows, np.int64)
+        at = {"rows": self._dev(frames.rows[j], np.int32), "start": self._dev(frames.starts[j], np.int32)}
         # PN rows and band indices of the candidate counters straight from the device schedule (es_schedule_batch)
         pn, bands = eng.schedule(self.sec._prng.sub_key, self._band_key, ctrs=torch.tensor(ctrs, dtype=torch.int64))
-        l0 = eng.llr(y, bands, pn, variant=0)
-        l1 = eng.llr(y, bands, pn, variant=1)
+        l0 = eng.llr(frames.y, bands, pn, variant=0, **at)
+        l1 = eng.llr(frames.y, bands, pn, variant=1, **at)
         res = eng.scl(torch.cat((l0, -l0, l1, -l1), dim=0), list_size=L, skip_if_hard_ok=False)
         key = getattr(self._aead, "_key", None)
         if key is not None:

@@ -61,6 +61,11 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def _peak_start(start: str) -> None:
+    if start != "peak":
+        raise ValueError(f'start must be a tensor, None or "peak", not {start!r}')
+
+
 @dataclass
 class SclResult:
     hard_info: torch.Tensor    # [B,55] uint8 (engines of another code: [B, ceil((K - 8) / 8)])
@@ -208,9 +213,10 @@ class RxEngine:
                                                            _ptr(npeaks), _ptr(flags), self._stream()), "es_sync_fused_batch")
         return thr, peaks, npeaks, flags
 
-    def front(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | None = None,
+    def front(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | str | None = None,
               out: torch.Tensor | None = None):
-        """bpf2 -> sync_fused -> llr (variant 0) in one library call (es_front_batch): -> (y, thr, peaks, npeaks, flags, llr)."""
+        """bpf2 -> sync_fused -> llr (variant 0) in one library call (es_front_batch): -> (y, thr, peaks, npeaks, flags, llr).
+        start="peak": the demodulator reads each record at its first detected peak (es_front_peak_batch; no peak = 0)."""
         if frames.dim() != 2 or frames.dtype not in (torch.float32, torch.int16):
             raise ValueError("frames must be float32 or int16 [B, T]")
         frames = frames.contiguous()
@@ -226,9 +232,16 @@ class RxEngine:
             out = torch.empty((B, 1024), dtype=torch.float32, device=dev)
         elif out.shape != (B, 1024) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 [B, 1024] tensor")
-        nat.check(self._ctx, self._lib.es_front_batch(self._ctx, _ptr(frames), nat.ES_DTYPE_I16 if frames.dtype == torch.int16 else nat.ES_DTYPE_F32,
-                                                      B, T, _ptr(band), _ptr(pn_rows), _ptr(start), _ptr(y), _ptr(y32), _ptr(thr), _ptr(peaks),
-                                                      _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()), "es_front_batch")
+        dt = nat.ES_DTYPE_I16 if frames.dtype == torch.int16 else nat.ES_DTYPE_F32
+        if isinstance(start, str):
+            _peak_start(start)
+            nat.check(self._ctx, self._lib.es_front_peak_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(pn_rows), _ptr(y), _ptr(y32),
+                                                               _ptr(thr), _ptr(peaks), _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()),
+                      "es_front_peak_batch")
+        else:
+            nat.check(self._ctx, self._lib.es_front_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(pn_rows), _ptr(start), _ptr(y),
+                                                          _ptr(y32), _ptr(thr), _ptr(peaks), _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()),
+                      "es_front_batch")
         return y, thr, peaks, npeaks, flags, out
 
     def reserve(self, B_max: int, T_max: int) -> None:
@@ -274,25 +287,67 @@ class RxEngine:
         return SyncResult(y, corr if keep_corr else None, thr, peaks, npeaks)
 
     # ------------------------------------------------------------------ soft demod
-    def llr(self, y: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | None = None,
-            variant: int = 0, want_diag: bool = False, out: torch.Tensor | None = None):
-        B, T = y.shape
+    def _at(self, y: torch.Tensor, start, rows, peaks):
+        """Record addressing of the peak-addressed entry points: -> (B, row int32 [B] or None, start int32 or None, stride)."""
+        if isinstance(start, str):
+            _peak_start(start)
+            if peaks is None or peaks.dim() != 2 or peaks.shape[1] != nat.ES_MAX_PEAKS or peaks.dtype != torch.int32 or not peaks.is_contiguous():
+                raise ValueError('start="peak" needs peaks=: the contiguous int32 [B, 32] peaks of a sync call')
+            start, stride = peaks, nat.ES_MAX_PEAKS
+        elif peaks is not None:
+            raise ValueError('peaks= goes with start="peak"')
+        else:
+            stride = 1
+            if start is not None:
+                start = self._dev(start, torch.int32).reshape(-1)
+        if rows is not None:
+            rows = self._dev(rows, torch.int32).reshape(-1)
+            B = rows.numel()
+        else:
+            B = y.shape[0]
+        if start is not None and start.numel() < (B - 1) * stride + 1 and B > 0:
+            raise ValueError("start: one entry per record")
+        return B, rows, start, stride
+
+    def llr(self, y: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | str | None = None,
+            variant: int = 0, want_diag: bool = False, out: torch.Tensor | None = None, rows: torch.Tensor | None = None,
+            peaks: torch.Tensor | None = None):
+        """Batched _llr (rtwm/detector.py:296-416).  Record i = y[i] from start[i] (None = 0): es_llr_batch.
+        In place, without gathering frames (es_llr_at_batch): rows= reads record i from y[rows[i]]; start="peak" with peaks= (the
+        [B, 32] peaks of a sync call) starts it at the first detected peak (none: 0).  band, pn_rows and the outputs follow i."""
+        T = y.shape[1]
+        at = rows is not None or peaks is not None or isinstance(start, str)
+        if at:
+            B, rows, st, stride = self._at(y, start, rows, peaks)
+        else:
+            B = y.shape[0]
         if out is None:
             out = torch.empty((B, 1024), dtype=torch.float32, device=self.device)
         elif out.shape != (B, 1024) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 [B, 1024] tensor")
         best_s = torch.empty(B, dtype=torch.int32, device=self.device) if want_diag else None
         score = torch.empty((B, 2), dtype=torch.float32, device=self.device) if want_diag else None
-        nat.check(self._ctx, self._lib.es_llr_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(pn_rows),
-                                                    int(variant), _ptr(out), _ptr(best_s), _ptr(score),
-                                                    self._stream()), "es_llr_batch")
+        if at:
+            nat.check(self._ctx, self._lib.es_llr_at_batch(self._ctx, _ptr(y), y.shape[0], T, B, _ptr(rows), _ptr(st), stride, _ptr(band),
+                                                           _ptr(pn_rows), int(variant), _ptr(out), _ptr(best_s), _ptr(score),
+                                                           self._stream()), "es_llr_at_batch")
+        else:
+            nat.check(self._ctx, self._lib.es_llr_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(pn_rows),
+                                                        int(variant), _ptr(out), _ptr(best_s), _ptr(score),
+                                                        self._stream()), "es_llr_batch")
         return (out, best_s, score) if want_diag else out
 
-    def header(self, y: torch.Tensor, band: torch.Tensor, hdr_pn: torch.Tensor, *, start: torch.Tensor | None = None,
-               want_diag: bool = False):
+    def header(self, y: torch.Tensor, band: torch.Tensor, hdr_pn: torch.Tensor, *, start: torch.Tensor | str | None = None,
+               want_diag: bool = False, rows: torch.Tensor | None = None, peaks: torch.Tensor | None = None):
         """Batched _decode_header (rtwm/detector.py:452-515) -> (ok uint8[B], val int32[B], score float32[B]);
-        want_diag: also the chosen shift, (ok, val, score, best_s int32[B])."""
-        B, T = y.shape
+        want_diag: also the chosen shift, (ok, val, score, best_s int32[B]).  rows= / start="peak" with peaks=: in place, as for llr
+        (es_header_at_batch)."""
+        T = y.shape[1]
+        at = rows is not None or peaks is not None or isinstance(start, str)
+        if at:
+            B, rows, st, stride = self._at(y, start, rows, peaks)
+        else:
+            B = y.shape[0]
         if hdr_pn.shape[0] == 1 and B > 1:
             hdr_pn = hdr_pn.expand(B, 16)
         hdr_pn = hdr_pn.contiguous()
@@ -300,9 +355,14 @@ class RxEngine:
         val = torch.empty(B, dtype=torch.int32, device=self.device)
         score = torch.empty(B, dtype=torch.float32, device=self.device)
         best_s = torch.empty(B, dtype=torch.int32, device=self.device) if want_diag else None
-        nat.check(self._ctx, self._lib.es_header_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(hdr_pn),
-                                                       _ptr(ok), _ptr(val), _ptr(score), _ptr(best_s), self._stream()),
-                  "es_header_batch")
+        if at:
+            nat.check(self._ctx, self._lib.es_header_at_batch(self._ctx, _ptr(y), y.shape[0], T, B, _ptr(rows), _ptr(st), stride, _ptr(band),
+                                                              _ptr(hdr_pn), _ptr(ok), _ptr(val), _ptr(score), _ptr(best_s), self._stream()),
+                      "es_header_at_batch")
+        else:
+            nat.check(self._ctx, self._lib.es_header_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(hdr_pn),
+                                                           _ptr(ok), _ptr(val), _ptr(score), _ptr(best_s), self._stream()),
+                      "es_header_batch")
         return (ok, val, score, best_s) if want_diag else (ok, val, score)
 
     # ------------------------------------------------------------------ FEC
@@ -503,31 +563,39 @@ class RxEngine:
 
     # ------------------------------------------------------------------ metric unit
     def decode_batch(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *,
-                     start: torch.Tensor | None = None, list_size: int = 8, keep_corr: bool = False):
-        """sync + LLR(variant 0 at `start`, default 0) + SCL-L for every record.
+                     start: torch.Tensor | str | None = None, list_size: int = 8, keep_corr: bool = False):
+        """sync + LLR(variant 0 at `start`, default 0; "peak" = each record's first detected peak) + SCL-L for every record.
 
         After the band-pass the chain forks: correlation + peak picking and the demodulator (frame
         start known) both only need `y`, so the LLR kernel runs on a side HIP stream beside them;
-        the branches are joined before the list decoder starts."""
+        the branches are joined before the list decoder starts.  With start="peak" the demodulator
+        needs the peaks: it runs after sync, on the caller's stream, reading them in place."""
         main = torch.cuda.current_stream(self.device)
-        if getattr(self, "_side", None) is None:
+        peak = isinstance(start, str)
+        if peak:
+            _peak_start(start)
+        elif getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(self.device)
         fast = (not keep_corr) and frames.shape[1] - 62 <= self.FAST_MAX_LAGS
         if fast:      # float32 correlation screen + exact float64 fix-ups (identical thr / peaks)
             y, y32 = self.bpf2(frames, band)
         else:
             y = self.bpf(frames, band)
-        self._side.wait_stream(main)
-        with torch.cuda.stream(self._side):      # the demodulator only needs y: it runs beside sync
-            llr = self.llr(y, band, pn_rows, start=start, variant=0)
+        if not peak:
+            self._side.wait_stream(main)
+            with torch.cuda.stream(self._side):      # the demodulator only needs y: it runs beside sync
+                llr = self.llr(y, band, pn_rows, start=start, variant=0)
         if fast:
             corr = None
             thr, peaks, npeaks, _flags = self.sync_fused(y, y32, band)
         else:
             corr = self.xcorr(y, band)
             thr, peaks, npeaks = self.pick(corr)
-        main.wait_stream(self._side)             # join before SCL, which wants the chip to itself
-        llr.record_stream(main)
+        if peak:
+            llr = self.llr(y, band, pn_rows, start="peak", peaks=peaks, variant=0)
+        else:
+            main.wait_stream(self._side)             # join before SCL, which wants the chip to itself
+            llr.record_stream(main)
         scl = self.scl(llr, list_size=list_size, skip_if_hard_ok=True)
         return SyncResult(y, corr if keep_corr else None, thr, peaks, npeaks), llr, scl
 
@@ -629,7 +697,7 @@ class DecodePipeline:
     def submit(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *,
                start: torch.Tensor | None = None, xcorr_events=None, select: bool = False, inputs_ready: bool = False):
         """Enqueue one batch.  inputs_ready (grouped arrangement): skip the wait on the caller's stream -- for INPUTS known to be
-        complete on the device (10 us of host time per batch; it covers the inputs only: the group's own buffers are ordered by the pipeline).  start: frame starts [B] (None = 0; "peak" = the first detected peak of each record, lanes only);
+        complete on the device (10 us of host time per batch; it covers the inputs only: the group's own buffers are ordered by the pipeline).  start: frame starts [B] (None = 0; "peak" = the first detected peak of each record, read in place by the demodulator);
         select (lanes only): also run the candidate selection (es_select_batch, validator None) on the lane's stream --
         the result is attached to the returned SclResult as `.selected = (payload, ok, which)`."""
         eng = self.eng
@@ -649,9 +717,8 @@ class DecodePipeline:
                 thr, peaks, npeaks, flags = e.sync_fused(y, y32, band)        # correlation screen + exact picking, one kernel
                 if xcorr_events is not None:
                     xcorr_events[1].record()
-                if isinstance(start, str):                                    # "peak": demodulate at the first detected peak
-                    start = peaks[:, 0].clamp(min=0).contiguous()
-                llr = e.llr(y, band, pn_rows, start=start, variant=0)
+                # "peak": demodulate at the first detected peak, read in place from the peaks (no kernel in between)
+                llr = e.llr(y, band, pn_rows, start=start, peaks=peaks if isinstance(start, str) else None, variant=0)
                 scl = e.scl(llr, list_size=self.list_size, skip_if_hard_ok=True)
                 if select:
                     scl.selected = e.select(scl)
@@ -663,18 +730,22 @@ class DecodePipeline:
         self.front.wait_stream(torch.cuda.current_stream(eng.device))   # inputs were produced on the caller's stream
         if len(self._inflight) >= self.depth:                           # at most `depth` batches in flight
             self.front.wait_event(self._inflight.pop(0))
+        peak = isinstance(start, str)                                   # "peak": the demodulator follows sync on the front stream
         with torch.cuda.stream(self.front):
             y, y32 = eng.bpf2(frames, band)
-            if self.side is not self.front:
-                self.side.wait_stream(self.front)
-            with torch.cuda.stream(self.side):
-                llr = eng.llr(y, band, pn_rows, start=start, variant=0)
+            if not peak:
+                if self.side is not self.front:
+                    self.side.wait_stream(self.front)
+                with torch.cuda.stream(self.side):
+                    llr = eng.llr(y, band, pn_rows, start=start, variant=0)
             if xcorr_events is not None:
                 xcorr_events[0].record()
             thr, peaks, npeaks, flags = eng.sync_fused(y, y32, band)
             if xcorr_events is not None:
                 xcorr_events[1].record()
-            if self.side is not self.front:
+            if peak:
+                llr = eng.llr(y, band, pn_rows, start=start, peaks=peaks, variant=0)
+            elif self.side is not self.front:
                 self.front.wait_stream(self.side)
             ready = torch.cuda.Event()
             ready.record()
@@ -719,7 +790,7 @@ class DecodePipeline:
         slot = g.count
         rows = g.llr[slot * B:(slot + 1) * B]
         with torch.cuda.stream(st):
-            if xcorr_events is None and not isinstance(start, str):              # the three launches through one library call
+            if xcorr_events is None:                                          # the three launches through one library call
                 y, thr, peaks, npeaks, flags, _ = e.front(frames, band, pn_rows, start=start, out=rows)
             else:
                 y, y32 = e.bpf2(frames, band)
@@ -728,9 +799,7 @@ class DecodePipeline:
                 thr, peaks, npeaks, flags = e.sync_fused(y, y32, band)
                 if xcorr_events is not None:
                     xcorr_events[1].record()
-                if isinstance(start, str):
-                    start = peaks[:, 0].clamp(min=0).contiguous()
-                e.llr(y, band, pn_rows, start=start, variant=0, out=rows)
+                e.llr(y, band, pn_rows, start=start, peaks=peaks if isinstance(start, str) else None, variant=0, out=rows)
             ready = torch.cuda.Event()
             ready.record()
         for t in (frames, band, pn_rows):

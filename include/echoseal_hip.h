@@ -25,8 +25,10 @@ extern "C" {
 #endif
 
 /* Version of this ABI.  2 (round 4): the tap table of es_set_tables has a row stride of ES_MAX_TAPS = 576 floats (1: 160), the
- * `nflag` parameters are gone, es_info_bytes / es_front_batch exist.  A binder must compare es_abi_version() with the ES_ABI_VERSION it
- * was written against and refuse a mismatch (echoseal_amd/_native.py:load does; the stub in INTEGRATION.md does). */
+ * `nflag` parameters are gone, es_info_bytes / es_front_batch exist.  Added within 2 (no existing signature or behaviour changed):
+ * es_llr_at_batch, es_header_at_batch, es_front_peak_batch -- demodulation and header decode at detected peaks.  A binder must
+ * compare es_abi_version() with the ES_ABI_VERSION it was written against and refuse a mismatch (echoseal_amd/_native.py:load
+ * does; the stub in INTEGRATION.md does). */
 #define ES_ABI_VERSION   2
 
 #define ES_OK            0
@@ -141,6 +143,15 @@ int es_front_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, in
                    const uint8_t* pn_dev, const int32_t* start_dev, double* y_dev, float* y32_dev, double* thr_dev,
                    int32_t* peaks_dev, int32_t* npeaks_dev, uint8_t* flags_dev, float* llr_dev, void* stream);
 
+/* es_front_batch with the demodulator at each record's FIRST DETECTED PEAK: es_bpf2_batch, es_sync_fused_batch and
+ * es_llr_at_batch(row_dev = NULL, start_dev = peaks_dev, start_stride = ES_MAX_PEAKS, variant 0) enqueued on `stream` in that order.
+ * A record without a peak (peaks_dev[i][0] = -1) is demodulated from 0, as clamp(min=0) would.  No host step and no other kernel
+ * between sync and the demodulator.  T - 62 <= 4096.
+ *   replaces rtwm/detector.py:59-99 + 110-161 (frame = y[start : start+1215] at the peak, then _llr) for a batch of records */
+int es_front_peak_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T, const uint8_t* band_dev,
+                        const uint8_t* pn_dev, double* y_dev, float* y32_dev, double* thr_dev, int32_t* peaks_dev,
+                        int32_t* npeaks_dev, uint8_t* flags_dev, float* llr_dev, void* stream);
+
 /* Size the context's float64 correlation workspace (used by es_sync_batch without corr_dev) for batches of up to B_max
  * records of T_max samples.  Allocation synchronises the device: call this once, outside any stream capture; afterwards
  * es_sync_batch only enqueues.  Without it es_sync_batch grows the workspace itself the first time a larger batch arrives
@@ -183,6 +194,24 @@ int es_llr_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const int32
 int es_header_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const int32_t* start_dev,
                     const uint8_t* band_dev, const uint8_t* hdr_pn_dev, uint8_t* ok_dev, int32_t* val_dev,
                     float* score_dev, int32_t* best_s_dev, void* stream);
+
+/* Peak-addressed forms of the two calls above: record i is read in place from row r of y at start s,
+ *   r = row_dev ? row_dev[i] : i,   s = start_dev ? max(start_dev[i * start_stride], 0) : 0,
+ * i.e. output i is what es_llr_batch / es_header_batch give for the gathered record y[r] with start s (bit for bit), with no
+ * gathered copy.  band_dev, pn_dev / hdr_pn_dev and every output are indexed by i, not by r.
+ *   y_dev        [n_rows][T] float64 band-passed records (n_rows >= 1 when B > 0)
+ *   row_dev      [B] int32 (nullable); a row outside [0, n_rows) gives the output of a start at or past T (an empty frame) and
+ *                reads nothing of y
+ *   start_dev    int32, element i at start_dev[i * start_stride] (nullable); start_stride >= 1 -- ES_MAX_PEAKS with the peaks_dev
+ *                of a sync call means "the first detected peak" (-1 = none: read as 0)
+ *   replaces the frame = y[start : start+1215] step of _scan_band_multi_frame (rtwm/detector.py:110-161) before _llr /
+ *   _decode_header                                                                                                           */
+int es_llr_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int64_t B, const int32_t* row_dev,
+                    const int32_t* start_dev, int start_stride, const uint8_t* band_dev, const uint8_t* pn_dev, int variant,
+                    float* llr_dev, int32_t* best_s_dev, float* score_dev, void* stream);
+int es_header_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int64_t B, const int32_t* row_dev,
+                       const int32_t* start_dev, int start_stride, const uint8_t* band_dev, const uint8_t* hdr_pn_dev,
+                       uint8_t* ok_dev, int32_t* val_dev, float* score_dev, int32_t* best_s_dev, void* stream);
 
 /* Polar(1024,448)+CRC-8 decode: hard-decision shortcut and successive-cancellation list.
  *   replaces PolarCode.decode (rtwm/fastpolar.py:254-359) up to validator selection
