@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- watermark frames/s decoded (sync + LLR + SCL-8) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set up, the untimed preparation, W warm-up steps, the K timed steps,
+--dump-outputs if given, and the JSON line.  --full adds everything else this file measures or checks: a sequential pass of the
+headline's step (stage breakdown, results compared with the timed steps), the legs, `roofline` / `roofline_fused` and the CPU baseline.
 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts N rank processes itself -- fresh children,
 before anything in the parent touches the GPU -- polls all of them, and tears the job down on the first failure.
@@ -17,7 +21,7 @@ beside the list decoders of others.  N > 1: weak scaling -- rank r decodes its o
 [r * 65 536, (r + 1) * 65 536)); rank 0 derives the key/PN schedule of all counters and broadcasts it once (RCCL) before the
 timed region; the data path has no collective.  At --steps 20 the timed region is ~0.5 s of steady work.
 
-Further driver-timed legs in the same JSON line (`legs`), each bracketed by barrier + synchronize like the headline:
+Further driver-timed legs in the same JSON line (`legs`, --full only), each bracketed by barrier + synchronize like the headline:
   c2        BASELINE config 2: batches of 1 024 clean 1215-sample frames through the grouped streaming pipeline (the front ends of
             16 batches on four streams fill one LLR buffer, one list-decoder launch per group), --c2-steps batches.
   c2_lanes  the same batches through seven whole-chain lanes (one list-decoder launch per batch): rows within ~3 ms of submission.
@@ -38,7 +42,7 @@ Further driver-timed legs in the same JSON line (`legs`), each bracketed by barr
 results, selection) as DIR/<name>.npy in float32 / float64, under 64 MB in all: two builds run with the same arguments decode the same
 windows and can be compared file by file.
 
-Extra objects:
+Extra objects (roofline_scl in every run -- it takes no run of its own -- the others with --full only):
   roofline      es_xcorr32_kernel<17,2048> -- the kernel north_star grades against the HBM roofline -- in the timed c3_unfused leg:
                 algorithmic bytes per launch (16 136 B per window, SURVEY.md section 8d) / mean launch duration against 8 TB/s;
                 `traffic` from the committed PMC passes.  NOT on the headline path (the product's sync is the fused kernel): labelled so.
@@ -84,7 +88,9 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--windows", type=int, default=65536, help="C3 windows per GPU per step (BASELINE config 3 = 65 536)")
     ap.add_argument("--list-size", type=int, default=8)
-    ap.add_argument("--legs", default="auto", help="comma list of c2,c2_lanes,c3_unfused,c3_pcie,c3_sustained,c4,c5 (auto: all at N = 1, c2 + c4 at N > 1; none: headline only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the sequential check pass, the legs (--legs), the roofline objects and the CPU baseline")
+    ap.add_argument("--legs", default="auto", help="--full: comma list of c2,c2_lanes,c3_unfused,c3_pcie,c3_sustained,c4,c5 (auto: all at N = 1, c2 + c4 at N > 1; none: no leg)")
     ap.add_argument("--sustained-steps", type=int, default=150, help="steps of the c3_sustained leg (~19 ms each)")
     ap.add_argument("--big-lanes", type=int, default=8, help="pipeline lanes of the headline and of the c4 leg (launches of 65 536 records): up to 8")
     ap.add_argument("--frames", type=int, default=1024, help="frame records per batch of the c2 legs (C2 = 1024)")
@@ -106,6 +112,8 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full and a.legs not in ("auto", "none"):
+        ap.error(f"--legs {a.legs}: legs run with --full only")
     return a
 
 
@@ -259,6 +267,8 @@ def run_rank(a) -> None:
     from echoseal_amd import workloads as WL
 
     legs = {"auto": ["c2", "c2_lanes", "c3_unfused", "c3_pcie", "c3_sustained", "c4", "c5"] if world == 1 else ["c2", "c4"], "none": []}.get(a.legs, a.legs.split(","))
+    if not a.full:
+        legs = []
     L = a.list_size
     eng = RxEngine(local, list_size_max=max(16, L))
     tx = WatermarkEmbedder(KEY)
@@ -370,9 +380,11 @@ def run_rank(a) -> None:
         stage_ms = {n: float(np.mean([s[i].elapsed_time(s[i + 1]) for s in st])) for i, n in enumerate(names)}
         return dts, float(np.mean([s.elapsed_time(e) for s, e in xe])), stage_ms, res
 
-    eng.set_option("scl_multi", -1); eng.set_option("scl_lane_slab", 1)
-    _dts, _x, stage_ms, (pk_s, npk_s, payload_s, ok_s) = c3_seq(True, 1)
-    same_as_seq = bool(torch.equal(pk, pk_s) and torch.equal(npk, npk_s) and torch.equal(payload3, payload_s) and torch.equal(ok3, ok_s))
+    stage_ms = same_as_seq = pk_s = npk_s = payload_s = ok_s = None
+    if a.full:
+        eng.set_option("scl_multi", -1); eng.set_option("scl_lane_slab", 1)
+        _dts, _x, stage_ms, (pk_s, npk_s, payload_s, ok_s) = c3_seq(True, 1)
+        same_as_seq = bool(torch.equal(pk, pk_s) and torch.equal(npk, npk_s) and torch.equal(payload3, payload_s) and torch.equal(ok3, ok_s))
 
     # ============================================================ leg c3_unfused: the screen through HBM (the `roofline` kernel)
     roof = None
@@ -453,7 +465,7 @@ def run_rank(a) -> None:
         del sys_, _llrs, scls_
     del pk_s, npk_s, payload_s, ok_s, sy3, scl3, payload3, ok3, pk, npk
     win_h = band_h = pn_h = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         ns = min(Bw, 1024)
         win_h, band_h, pn_h = win[:ns].cpu().numpy(), band3[:ns].cpu().numpy(), pn3[:ns].cpu().numpy()
     del win, off, pn3, band3, pipe3
@@ -602,8 +614,6 @@ def run_rank(a) -> None:
         out_legs["c5"] = c5_leg(eng, a, torch, np, WL)
 
     if rank == 0:
-        fused_alone_ms = stage_ms["sync_fused"]                      # the launch alone (one sequential step, HIP events around it)
-        achf = FUSED_BYTES_PER_WINDOW * Bw / (fused_alone_ms * 1e-3) / 1e9
         out = {
             "metric": "watermark frames/sec decoded (sync+LLR+SCL-8) @ 48 kHz",
             "value": total * a.steps / dt, "unit": "frames/s", "n_gpus": world, "steps": a.steps,
@@ -621,27 +631,30 @@ def run_rank(a) -> None:
                                      f"list decoders of others; one list-decoder launch of {Bw} frames per step (one lane per path, 64/L frames per wave)",
                        "untimed_preparation": "one step per lane (first launches allocate scratch and upload code), then the --warmup steps; the garbage collector is off inside the timed region",
                        "host_enqueue_ms_of_the_timed_steps": 1e3 * host_enqueue_s, "timed_region_ms": 1e3 * dt,
-                       "stage_ms_one_step_alone": stage_ms, "results_identical_to_a_sequential_pass": same_as_seq,
+                       **({"stage_ms_one_step_alone": stage_ms, "results_identical_to_a_sequential_pass": same_as_seq} if a.full else {}),
                        "frames_through_list_decoder": head["listed"], "frames_with_crc_ok": head["crc_ok"],
                        "windows_with_a_top5_peak_within_2_samples_of_the_true_offset": found, "fallback_records": head["fallback"],
                        "records_settled_by_the_exact_float64_row": head["exact_rows"]},
             "legs": out_legs,
         }
-        roof_fused = {"kernel": "es_xcorr32_kernel<17,2048,FUSED> (es_sync_fused_batch: screen row kept in LDS, threshold and peaks settled in the same kernel)",
-                      "bound": "hbm", "achieved": achf, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achf / HBM_PEAK_GBS,
-                      "traffic": ((_profile_json("r04_xcorr32_pmc_traffic.json") or _profile_json("r02_xcorr32_pmc_traffic.json") or {}).get("c3_launch_fused", {}).get("hbm_bytes_per_launch") if Bw == 65536 else None),
-                      "launch_ms": fused_alone_ms, "launch_ms_inside_the_timed_steps": fused_ms,
-                      "algorithmic_bytes_per_launch": FUSED_BYTES_PER_WINDOW * Bw, "on_headline_path": True,
-                      "note": "8 192 B of samples in + <= 150 B out per window (SURVEY 8d fused figure); bound by LDS passes and float64 re-evaluations, not by HBM -- "
-                              "it exists to take 2 x 7 944 B per window of screen traffic and two launches away",
-                      "where": "`launch_ms` (and `achieved` / `frac`): HIP events around the launch in one sequential step, nothing beside it; "
-                               f"`launch_ms_inside_the_timed_steps`: the same events inside the timed headline steps ({a.steps} steps), where the launch is queued beside "
-                               "other lanes' list decoders and the events span their time too -- reported, not used"}
-        if roof is not None:
-            out["roofline"] = roof
-            out["roofline_fused"] = roof_fused
-        else:
-            out["roofline"] = roof_fused                  # no c3_unfused leg in this run: the sync kernel of the headline steps
+        if a.full:
+            fused_alone_ms = stage_ms["sync_fused"]                  # the launch alone (one sequential step, HIP events around it)
+            achf = FUSED_BYTES_PER_WINDOW * Bw / (fused_alone_ms * 1e-3) / 1e9
+            roof_fused = {"kernel": "es_xcorr32_kernel<17,2048,FUSED> (es_sync_fused_batch: screen row kept in LDS, threshold and peaks settled in the same kernel)",
+                          "bound": "hbm", "achieved": achf, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achf / HBM_PEAK_GBS,
+                          "traffic": ((_profile_json("r04_xcorr32_pmc_traffic.json") or _profile_json("r02_xcorr32_pmc_traffic.json") or {}).get("c3_launch_fused", {}).get("hbm_bytes_per_launch") if Bw == 65536 else None),
+                          "launch_ms": fused_alone_ms, "launch_ms_inside_the_timed_steps": fused_ms,
+                          "algorithmic_bytes_per_launch": FUSED_BYTES_PER_WINDOW * Bw, "on_headline_path": True,
+                          "note": "8 192 B of samples in + <= 150 B out per window (SURVEY 8d fused figure); bound by LDS passes and float64 re-evaluations, not by HBM -- "
+                                  "it exists to take 2 x 7 944 B per window of screen traffic and two launches away",
+                          "where": "`launch_ms` (and `achieved` / `frac`): HIP events around the launch in one sequential step, nothing beside it; "
+                                   f"`launch_ms_inside_the_timed_steps`: the same events inside the timed headline steps ({a.steps} steps), where the launch is queued beside "
+                                   "other lanes' list decoders and the events span their time too -- reported, not used"}
+            if roof is not None:
+                out["roofline"] = roof
+                out["roofline_fused"] = roof_fused
+            else:
+                out["roofline"] = roof_fused                  # no c3_unfused leg in this run: the sync kernel of the headline steps
         scl_roof = scl_roofline(head_fps_per_gpu, out_legs.get("c4", {}).get("value", 0.0) / world if "c4" in out_legs else None, L, head["listed"] / Bw)
         if scl_roof:
             out["roofline_scl"] = scl_roof

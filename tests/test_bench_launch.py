@@ -48,8 +48,8 @@ def test_failing_rank_tears_the_job_down_within_seconds():
 
 @pytest.mark.gpu
 def test_two_rank_rehearsal_and_checksum_independent_of_world_size():
-    """The default N > 1 line (headline C3 + legs c2 and c4) at two ranks (gloo rehearsal, both ranks on the one GPU), sized down."""
-    common = ["--steps", "2", "--warmup", "1", "--windows", "8192", "--legs", "c2,c4", "--c2-steps", "40", "--c4-frames", "16384", "--c4-chunk", "4096",
+    """The --full N > 1 line (headline C3 + legs c2 and c4) at two ranks (gloo rehearsal, both ranks on the one GPU), sized down."""
+    common = ["--steps", "2", "--warmup", "1", "--windows", "8192", "--full", "--legs", "c2,c4", "--c2-steps", "40", "--c4-frames", "16384", "--c4-chunk", "4096",
               "--no-cpu-baseline"]
     one = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + common, env=_env(), capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -68,7 +68,7 @@ def test_two_rank_rehearsal_and_checksum_independent_of_world_size():
 
 def _forced(backend, extra=()):
     return subprocess.run([sys.executable, BENCH, "--gpus", "1", "--backend", backend, "--force-collectives", "--steps", "2", "--warmup", "1",
-                           "--windows", "4096", "--legs", "c2,c4", "--c2-steps", "20", "--c4-frames", "8192", "--c4-chunk", "4096", "--no-cpu-baseline",
+                           "--windows", "4096", "--full", "--legs", "c2,c4", "--c2-steps", "20", "--c4-frames", "8192", "--c4-chunk", "4096", "--no-cpu-baseline",
                            *extra], env=_env(), capture_output=True, text=True, timeout=900)
 
 
@@ -85,7 +85,7 @@ def test_rccl_runs_once_at_world_size_one():
     assert j["n_gpus"] == 1 and j["config"]["backend"] == "nccl (RCCL)" and c["process_group"]
     assert c["broadcast"] >= 3 and c["barrier"] >= 10 and c["all_reduce"] >= 6, c
     assert j["config"]["results_identical_to_a_sequential_pass"] and j["legs"]["c2"]["sync_offsets_ok"]
-    plain = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "4096", "--legs", "c4",
+    plain = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "4096", "--full", "--legs", "c4",
                             "--c4-frames", "8192", "--c4-chunk", "4096", "--no-cpu-baseline"], env=_env(), capture_output=True, text=True, timeout=900)
     assert plain.returncode == 0, plain.stderr[-2000:]
     j0 = json.loads(plain.stdout.strip().splitlines()[-1])

@@ -5,11 +5,11 @@
 R=$(pwd)
 OUT=$R/gpurun_out/r3/final
 rm -rf $OUT; mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_a.json 2> $OUT/bench_a.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_b.json 2> $OUT/bench_b.err
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_a.json 2> $OUT/bench_a.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_b.json 2> $OUT/bench_b.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cd $R
 bash tools/collect_pmc_r03.sh final > /dev/null 2>&1
 python - <<'PY'
