@@ -92,7 +92,10 @@ es_ctx* es_create(int device, int list_size_max)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible"; return nullptr; }
     if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; return nullptr; }
-    if (list_size_max < 0 || list_size_max > ES_MAX_LIST) { g_create_err = "list_size_max must be in [0, 256] (0: a front-end context without list-decoder scratch)"; return nullptr; }
+    if (list_size_max < 0 || list_size_max > ES_MAX_LIST) {
+        g_create_err = "list_size_max must be in [0, " + std::to_string(ES_MAX_LIST) + "] (0: a front-end context without list-decoder scratch)";
+        return nullptr;
+    }
     es_ctx* ctx = new (std::nothrow) es_ctx();
     if (!ctx) { g_create_err = "out of host memory"; return nullptr; }
     ctx->device = device;
@@ -126,8 +129,11 @@ es_ctx* es_create(int device, int list_size_max)
         return nullptr;
     }
     ctx->wide_enabled = list_size_max > 32;
-    ctx->wide_scratch_bytes = es_scl_wide_scratch_bytes(ctx, &ctx->wide_slots);
-    if (hipMalloc(&ctx->d_wide_slot_bits, 128 * sizeof(unsigned)) != hipSuccess || hipMemset(ctx->d_wide_slot_bits, 0, 128 * sizeof(unsigned)) != hipSuccess) {
+    ctx->wide_scratch_bytes = es_scl_wide_scratch_bytes(ctx, &ctx->wide_lanes);
+    ctx->wide_slot_words = (int)((ctx->wide_lanes / 64 + 31) / 32);                 /* a bit per one-wave block of the slab, at least 128 words */
+    if (ctx->wide_slot_words < 128) ctx->wide_slot_words = 128;
+    if (hipMalloc(&ctx->d_wide_slot_bits, ctx->wide_slot_words * sizeof(unsigned)) != hipSuccess ||
+        hipMemset(ctx->d_wide_slot_bits, 0, ctx->wide_slot_words * sizeof(unsigned)) != hipSuccess) {
         g_create_err = "device allocation of the slab slot bitmap failed";
         es_destroy(ctx);
         return nullptr;
@@ -553,7 +559,7 @@ int es_set_option(es_ctx* ctx, const char* name, int value)
         if (value == 1 && !ctx->d_wide_scratch) {             // one lane per path: the slab of es_scl_wide.hip (allocated here, never in an enqueue call)
             DeviceGuard g(ctx->device);
             ctx->wide_enabled = true;
-            ctx->wide_scratch_bytes = es_scl_wide_scratch_bytes(ctx, &ctx->wide_slots);
+            ctx->wide_scratch_bytes = es_scl_wide_scratch_bytes(ctx, &ctx->wide_lanes);
             if (hipMalloc(&ctx->d_wide_scratch, ctx->wide_scratch_bytes) != hipSuccess) {
                 ctx->d_wide_scratch = nullptr; ctx->wide_enabled = false;
                 return fail(ctx, ES_ENOMEM, "es_set_option: device allocation of the lane-per-path scratch slab failed");

@@ -39,9 +39,9 @@ struct es_ctx {
     double* d_scl_scratch = nullptr;  size_t scl_scratch_bytes = 0;
     unsigned* d_slot_bits = nullptr;  /* bitmap of the slab slots of es_scl_multi_kernel (one bit per resident block) */
     double* d_ws_corr = nullptr;      size_t ws_corr_bytes = 0;
-    void*   d_wide_scratch = nullptr; size_t wide_scratch_bytes = 0; int wide_slots = 0;   /* lane-per-path list decoder (es_scl_wide.hip): list sizes 64..256, and shorter lists with scl_lanes = 1 */
+    void*   d_wide_scratch = nullptr; size_t wide_scratch_bytes = 0; long long wide_lanes = 0;   /* lane-per-path list decoder (es_scl_wide.hip): list sizes 64..1024, and shorter lists with scl_lanes = 1; its slab in lanes */
     bool    wide_enabled = false;
-    unsigned* d_wide_slot_bits = nullptr;                 /* its slab slot bitmap (128 words: up to 3 072 one-wave blocks) */
+    unsigned* d_wide_slot_bits = nullptr; int wide_slot_words = 0;   /* its slab slot bitmap (>= 128 words: a slot per one-wave block of the slab, 3 072 / 4 096 on 256 CUs) */
     uint8_t* d_sbox = nullptr;        /* AES S-box (es_schedule_batch) */
     uint8_t* d_hdr_pn = nullptr;      /* packed header PN (es_tx_frames_batch) */
     /* Who is using a scratch slab (es_slab_enter).  Domain 0 = d_scl_scratch (es_scl.hip, es_scl_multi.hip),
@@ -56,7 +56,7 @@ struct es_ctx {
     unsigned cursor_next = 0;         /* eager launches rotate over the first ES_CURSOR_RING - ES_CURSOR_CAPTURED counters */
     unsigned cursor_captured = 0;     /* launches recorded into a stream capture keep a counter of their own for the life of the context (the graph may replay at any time) */
     bool pick_attr_set = false;       /* per-device kernel attributes already raised for this context's device */
-    unsigned wide_attr_mask = 0;      /* bit per instantiation of the lane-per-path list decoder (its list capacity 1 .. 256) */
+    unsigned wide_attr_mask = 0;      /* bit per instantiation of the lane-per-path list decoder (list capacity 1 .. 1024, kind of code): es_scl_wide.hip wide_attr_bit */
     /* tuning (es_set_option) */
     int scl_lanes = 0;                /* lanes per path of the multi-frame list decoder: 4 (16 paths per wave), 2 (32 paths per wave), 0 = by batch size */
     int scl_prio = 0;                 /* wave priority of the lane-per-path list decoder's launches (0..3) */
@@ -91,7 +91,6 @@ __device__ __forceinline__ uint32_t es_wave_incl_scan_u32(uint32_t x)
 __device__ __forceinline__ int es_wave_read_lane(int v, int src) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src)); }
 #endif
 
-static inline int es_wide_lanes_max(const es_ctx*) { return 256; }   /* lanes of the largest block of es_scl_wide.hip: the slab is sized in such blocks */
 /* kernels exist for power-of-two list sizes; a context created for list_size_max serves every size up to the next one */
 static inline int es_list_cap(int lmax) { int c = 1; while (c < lmax) c <<= 1; return c; }
 
@@ -106,7 +105,7 @@ int es_slab_leave(es_ctx* ctx, int domain, int shape, bool shareable, hipStream_
 
 /* launchers implemented in the kernel translation units */
 size_t es_scl_scratch_bytes(const es_ctx* ctx);
-size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, int* slots_out);
+size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, long long* lanes_out);
 size_t es_scl_multi_scratch_bytes(const es_ctx* ctx);
 #define ES_CURSOR_RING 1024
 #define ES_CURSOR_CAPTURED 256                                   /* of them: set aside for launches recorded into stream captures (never reused) */
@@ -117,6 +116,9 @@ int es_launch_scl_multi(es_ctx* ctx, const void* llr, int dtype, int64_t B, int 
 int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
                        uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
                        uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
+int es_launch_scl_wide_large(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,   /* L = 257..1024 (es_scl_wide_large.hip) */
+                             uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
+                             uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
 int es_launch_scl(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
                   uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
                   uint8_t* cand_ok, int32_t* ncand, hipStream_t st);

@@ -1,4 +1,4 @@
-// es_scl_wide.hip -- successive-cancellation LIST decoder with ONE LANE PER PATH: lists of 64, 128 and 256 paths (one frame
+// es_scl_wide.hip -- successive-cancellation LIST decoder with ONE LANE PER PATH: lists of 64 to 1024 paths (one frame
 // per block of L lanes; the detector's default list size is 256, rtwm/detector.py:27 -- this kernel is what lets
 // WatermarkDetector(key).verify(...) run unchanged), and shorter lists as 64/L whole frames per one-wave block -- the
 // throughput mapping of large launches.  Same arithmetic and the same bookkeeping idea as es_scl.hip (per-depth slot
@@ -9,7 +9,7 @@
 //     wave touch one contiguous row; a lane walks a node's elements serially.  DL = 7 in one-wave blocks, 8 in blocks of several waves.
 //     The g half of depth 1 (bits 512..) is never stored: llr[e + 512] +- llr[e], formed on the fly where it is consumed (ES_WIDE_L1R).
 //   * depths DL..9 (8 + 4 + 2 values at DL = 7): LDS, [element][slot]; depth 10 (the leaf LLR): a register.
-//   * slot pointers (which slot holds my data at depth d): one byte per depth packed in two 64-bit registers,
+//   * slot pointers (which slot holds my data at depth d): one byte per depth packed in two 64-bit registers (16 bits above 256 paths),
 //     partial-sum blocks of 1..16 bits in one 32-bit register (as in es_scl.hip), of 32 and 64 bits in LDS by
 //     slot, of 128 / 256 / 512 bits (read a few times per frame) in the slab.
 //   * a sort moves registers only.  One-wave blocks: the survivor of rank r -- lane r -- fetches sorted element r and its parent's
@@ -40,7 +40,14 @@
 // Values are bit-identical to the reference list decoder for the same reason as in es_scl.hip (es_math.h).
 // This file's kernels use dynamic LDS only, with the exp table first in it: the table sits at LDS address 0 (checked at kernel start),
 // which lets es_math.h address its entries without adding a base.
+//
+// Lists of 257..1024 paths (capacities 512 and 1024: 8 and 16 waves per block) are instantiated in a translation unit of their own,
+// es_scl_wide_large.hip, which includes this file with ES_WIDE_LARGE_TU = 1: the compiler's inlining choices for the helpers every
+// instantiation calls depend on how many instantiations a unit holds, and the tuned ones of lists up to 256 stay as they are.
 #define ES_EXP_TAB_LDS_ADDR 0u
+#ifndef ES_WIDE_LARGE_TU
+#define ES_WIDE_LARGE_TU 0
+#endif
 #include "es_scl_common.h"
 #include "es_softplus_dev.h"
 #include <type_traits>
@@ -101,25 +108,51 @@ constexpr int WIDE_AUX_PER_PATH = MWIN_MAX * 6 + 28 * 4 + 16 * 4;
 constexpr int wide_dl(bool one_wave) { return one_wave ? ES_WIDE_LDS_DEPTH : 8; }
 constexpr int wide_low_row(int DL, int d) { int r = 0; for (int k = DL; k < d; ++k) r += N >> k; return r; }
 
-// What follows a path through a sort.  Several waves per frame (NB = 2: double-buffered by information index, a wave may still be reading
-// while another is a sort further): every path publishes it to LDS and the survivor of rank r reads its parent's.  ONE wave per block
-// (NB = 1): nothing is stored -- the survivor fetches its parent's registers with ds_bpermute (the lanes of a wave run in lock step).
-template <int L, int NB>
+// Slot pointers of a path (which slot holds its data at a depth): one byte per depth in a 64-bit word while slots fit a byte (L <= 256),
+// else 16 bits per depth over two words (entries 0..3 in `lo`, 4..7 in `hi`).  The partial-sum word also carries the depth-9 LLR pointer
+// (entry 5) and, while published, the window ancestor (bits 48.. of the one word / entry 6 of the pair).
+struct WidePtr16 { uint64_t lo, hi; };
+template <int L> using wide_ptr_t = std::conditional_t<(L > 256), WidePtr16, uint64_t>;
+
+__device__ __forceinline__ uint64_t p8_set(uint64_t w, int k, int v) { const int sh = 8 * k; return (w & ~(255ULL << sh)) | ((uint64_t)(uint32_t)v << sh); }
+__device__ __forceinline__ int p8_get(uint64_t w, int k) { return (int)((w >> (8 * k)) & 255ULL); }
+__device__ __forceinline__ WidePtr16 p8_set(WidePtr16 w, int k, int v)
+{
+    const int sh = 16 * (k & 3);
+    const uint64_t m = ~(0xFFFFULL << sh), x = (uint64_t)(uint32_t)v << sh;
+    if (k < 4) w.lo = (w.lo & m) | x; else w.hi = (w.hi & m) | x;
+    return w;
+}
+__device__ __forceinline__ int p8_get(WidePtr16 w, int k) { return (int)(((k < 4 ? w.lo : w.hi) >> (16 * (k & 3))) & 0xFFFFULL); }
+// (L > 256) a path's pointers at slot s: the LLR tree's (depths 1..8, `a`) and the partial sums' (depths 1..5, depth-9 LLR pointer, `b`)
+__device__ __forceinline__ WidePtr16 wide_ptr_fill_a(int s) { const uint64_t r = (uint64_t)(uint32_t)s * 0x0001000100010001ULL; return WidePtr16{r, r}; }
+__device__ __forceinline__ WidePtr16 wide_ptr_fill_b(int s) { const uint64_t r = (uint64_t)(uint32_t)s * 0x0001000100010001ULL; return WidePtr16{r, r & 0xFFFFFFFFULL}; }
+// ... the partial-sum pointers with the window ancestor beside them (entry 6: published through a sort), and back
+__device__ __forceinline__ WidePtr16 wide_ptr_join(WidePtr16 b, uint32_t anc) { b.hi |= (uint64_t)anc << 32; return b; }
+__device__ __forceinline__ void wide_ptr_split(WidePtr16 t, WidePtr16& b, uint32_t& anc) { anc = (uint32_t)(t.hi >> 32) & 0xFFFFu; t.hi &= 0xFFFFFFFFULL; b = t; }
+
+// What follows a path through a sort.  Several waves per frame: every path publishes it to LDS and the survivor of rank r reads its
+// parent's -- double-buffered by information index (NBUF = 2: a wave may still be reading while another is a sort further) up to 512
+// paths; at 1024 paths two buffers do not fit beside the rest (LDS), so ONE buffer with a barrier before every write to it.  ONE wave
+// per block: nothing is stored -- the survivor fetches its parent's registers with ds_bpermute (the lanes of a wave run in lock step).
+template <int L, int NBUF>
 struct WidePub {
-    double   skey[NB][2 * L];           // cross-wave sort stages and the read-out
-    double   xsp[NB][2][L];             // softplus pair of the even sibling,
-    uint64_t xpa[NB][L];                // ... LLR-tree slot pointers,
-    uint64_t xpb[NB][L];                // ... partial-sum slot pointers | depth-9 pointer << 40 | window ancestor << 48,
-    uint32_t xb0[NB][L];                // ... partial sums of 1..16 bits,
-    uint32_t xhist[NB][L];              // ... bits of the current trace-back window
-    uint16_t sidx[NB][2 * L];
+    double   skey[NBUF][2 * L];         // cross-wave sort stages and the read-out
+    double   xsp[NBUF][2][L];           // softplus pair of the even sibling,
+    wide_ptr_t<L> xpa[NBUF][L];         // ... LLR-tree slot pointers,
+    wide_ptr_t<L> xpb[NBUF][L];         // ... partial-sum slot pointers, depth-9 pointer and window ancestor (wide_ptr_join),
+    uint32_t xb0[NBUF][L];              // ... partial sums of 1..16 bits,
+    uint32_t xhist[NBUF][L];            // ... bits of the current trace-back window
+    uint16_t sidx[NBUF][2 * L];
 };
+struct WidePubBperm { };
 #ifndef ES_WIDE_GATHER_BPERM
 #define ES_WIDE_GATHER_BPERM 1                    /* one-wave blocks: survivors take their parent's state with ds_bpermute (0: through LDS, as blocks of several waves do) */
 #endif
-#if ES_WIDE_GATHER_BPERM
-template <int L> struct WidePub<L, 1> { };
-#endif
+// buffers of the published state: NB = 1 one wave per block, 2 several
+constexpr int wide_pub_bufs(int L, int NB) { return (NB == 2 && L > 512) ? 1 : NB; }
+template <int L, int NB>
+using wide_pub_t = std::conditional_t<NB == 1 && ES_WIDE_GATHER_BPERM, WidePubBperm, WidePub<L, wide_pub_bufs(L, NB)>>;
 
 template <int L, int NB>
 struct WideLds {
@@ -129,11 +162,8 @@ struct WideLds {
     double   low[NLOW][L];              // depths DL..9, by slot (also: the hard decision's 184 bytes and the final ordering's metrics, outside the list loop)
     uint32_t betaM[3][L];               // partial-sum blocks of 32 (row 0) and 64 bits (1, 2), by slot (wider ones, touched a few times per frame: slab)
     int      flag;
-    WidePub<L, NB> pub;                 // (the frames drawn from the cursor, up to 64 ints per one-wave block, borrow row 1 of `low` before the list loop starts)
+    wide_pub_t<L, NB> pub;              // (the frames drawn from the cursor, up to 64 ints per one-wave block, borrow row 1 of `low` before the list loop starts)
 };
-
-__device__ __forceinline__ uint64_t p8_set(uint64_t w, int k, int v) { const int sh = 8 * k; return (w & ~(255ULL << sh)) | ((uint64_t)(uint32_t)v << sh); }
-__device__ __forceinline__ int p8_get(uint64_t w, int k) { return (int)((w >> (8 * k)) & 255ULL); }
 
 // lane l <-> lane l ^ D inside a wave, D a constant after unrolling
 __device__ __forceinline__ int wxor_b32(int v, int D)
@@ -223,6 +253,7 @@ __device__ __forceinline__ void ce_inlane(uint32_t& lo0, uint32_t& hi0, uint32_t
 template <int L, int LF>
 __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, uint32_t& i1, const int p, const int pl, WideLds<L, (LF > 64 ? 2 : 1)>& W, int& buf)
 {
+    constexpr int NBUF = wide_pub_bufs(L, LF > 64 ? 2 : 1);     // 1: one buffer, a barrier before each write to it (see WidePub)
 #if ES_WIDE_SORT_ASM
     uint64_t u0, u1; __builtin_memcpy(&u0, &k0, 8); __builtin_memcpy(&u1, &k1, 8);
     uint32_t lo0 = (uint32_t)u0, hi0 = (uint32_t)(u0 >> 32), lo1 = (uint32_t)u1, hi1 = (uint32_t)(u1 >> 32);
@@ -245,6 +276,7 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
                     if constexpr (LF > 64) {
                         if (dl >= 64) {
                             cross = true;
+                            if constexpr (NBUF == 1) __syncthreads();
                             W.pub.skey[buf][2 * p] = __builtin_bit_cast(double, ((uint64_t)hi0 << 32) | lo0);
                             W.pub.skey[buf][2 * p + 1] = __builtin_bit_cast(double, ((uint64_t)hi1 << 32) | lo1);
                             W.pub.sidx[buf][2 * p] = (uint16_t)i0; W.pub.sidx[buf][2 * p + 1] = (uint16_t)i1;
@@ -253,7 +285,7 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
                             const uint64_t x0 = __builtin_bit_cast(uint64_t, W.pub.skey[buf][2 * o]), x1 = __builtin_bit_cast(uint64_t, W.pub.skey[buf][2 * o + 1]);
                             a0 = (uint32_t)x0; b0 = (uint32_t)(x0 >> 32); a1 = (uint32_t)x1; b1 = (uint32_t)(x1 >> 32);
                             c0 = W.pub.sidx[buf][2 * o]; c1 = W.pub.sidx[buf][2 * o + 1];
-                            buf ^= 1;
+                            if constexpr (NBUF == 2) buf ^= 1;
                         }
                     }
                     if (!cross) {
@@ -286,13 +318,14 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
                 if constexpr (LF > 64) {
                     if (dl >= 64) {
                         cross = true;
+                        if constexpr (NBUF == 1) __syncthreads();
                         W.pub.skey[buf][2 * p] = k0; W.pub.skey[buf][2 * p + 1] = k1;
                         W.pub.sidx[buf][2 * p] = (uint16_t)i0; W.pub.sidx[buf][2 * p + 1] = (uint16_t)i1;
                         __syncthreads();
                         const int o = p ^ dl;
                         ok0 = W.pub.skey[buf][2 * o]; ok1 = W.pub.skey[buf][2 * o + 1];
                         oi0 = W.pub.sidx[buf][2 * o]; oi1 = W.pub.sidx[buf][2 * o + 1];
-                        buf ^= 1;
+                        if constexpr (NBUF == 2) buf ^= 1;
                     }
                 }
                 if (!cross) {
@@ -394,15 +427,17 @@ __device__ __forceinline__ int hard_decision_wave(const WideArgs& a, long long f
 // GK: any code Polar(1024, K) + CRC-8, 9 <= K <= 1024 (the reference's PolarCode takes any K, rtwm/fastpolar.py:209-234): K, the row width
 // and the number of trace-back windows are run-time values (a.n_info, a.info_bytes).  The default instantiation (K = 448, everything the
 // reference itself instantiates) keeps them as compile-time constants: its code is unchanged by the existence of the other.
+constexpr int wide_wps(int L) { return L == 1024 ? 4 : L == 512 ? 2 : ES_WIDE_WPS; }     // waves per SIMD: 512 / 1024 paths -- one block per CU
 template <int L, int LF, bool GK = false>
-__global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
+__global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
 {
     constexpr int MW = GK ? MWIN_MAX : MWIN_W;           // rows of the trace-back arrays in the aux slab
     const int NIB = GK ? a.info_bytes : ES_INFO_BYTES;   // bytes of a packed information row
     constexpr bool WAVE = (LF <= 64);                // the block is one wave
     constexpr int FRG = L / LF;                      // frames per block
     constexpr int NB = WAVE ? 1 : 2;
-    static_assert(LF >= 1 && LF <= L && (L % 64) == 0 && L <= 256 && (WAVE ? L == 64 : L == LF), "shape");
+    constexpr int NBUF = wide_pub_bufs(L, NB);       // published-state buffers (WidePub); 1 with several waves: a barrier before each write
+    static_assert(LF >= 1 && LF <= L && (L % 64) == 0 && L <= 1024 && (WAVE ? L == 64 : L == LF), "shape");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     WideLds<L, NB>& W = *reinterpret_cast<WideLds<L, NB>*>(smem_raw);
     if (a.prio == 1) __builtin_amdgcn_s_setprio(1); else if (a.prio == 2) __builtin_amdgcn_s_setprio(2); else if (a.prio >= 3) __builtin_amdgcn_s_setprio(3);
@@ -555,9 +590,14 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
 
         // ---------------- list decoding (fastpolar.py:278-330)
         // slot of my LLR block at depth d = 1..8: byte d-1 (every path starts as a copy of its frame's path 0)
-        uint64_t pa_ = (uint64_t)(uint32_t)fp0 * 0x0101010101010101ULL;
+        // (L > 256: 16 bits per depth, WidePtr16)
+        wide_ptr_t<L> pa_, pb_;
+        if constexpr (L > 256) { pa_ = wide_ptr_fill_a(fp0); pb_ = wide_ptr_fill_b(fp0); }
+        else {
+        pa_ = (uint64_t)(uint32_t)fp0 * 0x0101010101010101ULL;
         // slot of my partial-sum block at depth d = 1..5: byte d-1; byte 5: LLR slot at depth 9
-        uint64_t pb_ = (uint64_t)(uint32_t)fp0 * 0x0000010101010101ULL;
+        pb_ = (uint64_t)(uint32_t)fp0 * 0x0000010101010101ULL;
+        }
         uint32_t b0 = 0;                  // partial-sum blocks of S = 1..16 bits, block of S bits at bit S
         uint32_t hist = 0, anc = 0;       // trace-back window
         double metric = 0.0, lam = 0.0, sp_diff = 0.0, sp_sum = 0.0, lp_odd = 0.0;
@@ -913,14 +953,17 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                     }
                 } else {
                 // publish what follows a path through the sort
-                const int xb = (NB == 2) ? (info_idx & 1) : 0;
+                const int xb = (NBUF == 2) ? (info_idx & 1) : 0;
+                if constexpr (!WAVE && NBUF == 1) __syncthreads();         // one buffer: every wave has read the last sort's
                 W.pub.xpa[xb][p] = pa_;
-                W.pub.xpb[xb][p] = pb_ | ((uint64_t)(wstart ? (uint32_t)pl : anc) << 48);
+                if constexpr (L > 256) W.pub.xpb[xb][p] = wide_ptr_join(pb_, wstart ? (uint32_t)pl : anc);
+                else W.pub.xpb[xb][p] = pb_ | ((uint64_t)(wstart ? (uint32_t)pl : anc) << 48);
                 W.pub.xb0[xb][p] = b0;
                 W.pub.xhist[xb][p] = wstart ? 0u : hist;
                 if (!(i & 1)) { W.pub.xsp[xb][0][p] = sp_diff; W.pub.xsp[xb][1][p] = sp_sum; }
                 int buf = 0;
                 wide_sort<L, LF>(k0, i0, k1, i1, p, pl, W, buf);
+                if constexpr (!WAVE && NBUF == 1) __syncthreads();         // one buffer: every wave has read the last cross-wave stage
                 W.pub.skey[buf][2 * p] = k0; W.pub.skey[buf][2 * p + 1] = k1;
                 W.pub.sidx[buf][2 * p] = (uint16_t)i0; W.pub.sidx[buf][2 * p + 1] = (uint16_t)i1;
                 if constexpr (WAVE) wave_fence_lds(); else __syncthreads();
@@ -929,9 +972,12 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
                 const int parent = fp0 + ((int)(myc >> 1) & (LF - 1));
                 bit = myc & 1u;
                 pa_ = W.pub.xpa[xb][parent];
+                if constexpr (L > 256) wide_ptr_split(W.pub.xpb[xb][parent], pb_, anc);
+                else {
                 const uint64_t t = W.pub.xpb[xb][parent];
                 pb_ = t & 0xFFFFFFFFFFFFULL;
                 anc = (uint32_t)(t >> 48);
+                }
                 b0 = W.pub.xb0[xb][parent];
                 hist = (W.pub.xhist[xb][parent] << 1) | bit;
                 if (!(i & 1)) lp_odd = W.pub.xsp[xb][bit ? 0 : 1][parent];
@@ -1056,38 +1102,87 @@ __global__ __launch_bounds__(L, ES_WIDE_WPS) void es_scl_wide_kernel(WideArgs a)
 }
 
 
+// es_ctx::wide_attr_mask bit of an instantiation: capacities 1..256 at bits 0..8 (run-time K: 9..17), 512 and 1024 at 18, 19 (20, 21)
+constexpr unsigned wide_attr_bit(int LF, bool GK)
+{
+    return LF <= 256 ? (unsigned)LF << (GK ? 9 : 0) : 1u << (18 + (LF == 1024 ? 1 : 0) + (GK ? 2 : 0));
+}
+
 template <int L, int LF, bool GK = false>
 int launch_wide(es_ctx* ctx, WideArgs a, int64_t B, hipStream_t st)
 {
     const size_t lds = sizeof(WideLds<L, (LF > 64 ? 2 : 1)>);
     static_assert((sizeof(WideLds<256, 2>) + 1279) / 1280 * 1280 * 3 <= 160 * 1024, "three workgroups per CU at L = 256 (LDS is handed out in 1 280-byte granules)");
     static_assert((sizeof(WideLds<128, 2>) + 1279) / 1280 * 1280 * 6 <= 160 * 1024, "six two-wave workgroups per CU at L = 128");
+    static_assert((sizeof(WideLds<512, 2>) + 1279) / 1280 * 1280 <= 160 * 1024 && (sizeof(WideLds<512, 2>) + 1279) / 1280 * 1280 * 2 > 160 * 1024,
+                  "one workgroup per CU at L = 512 (wide_cu_lanes counts 512 lanes for it)");
+    static_assert((sizeof(WideLds<1024, 2>) + 1279) / 1280 * 1280 <= 160 * 1024, "one workgroup per CU at L = 1024 (single-buffered WidePub)");
 #if ES_WIDE_GATHER_BPERM && ES_WIDE_LDS_DEPTH >= 7
     static_assert((sizeof(WideLds<64, 1>) + 1279) / 1280 * 1280 * 4 * ES_WIDE_WPS <= 160 * 1024, "4 x ES_WIDE_WPS one-wave workgroups per CU");
 #endif
     static_assert((LF & (LF - 1)) == 0, "power of two");
-    constexpr unsigned attr_bit = (unsigned)LF << (GK ? 9 : 0);        // one instantiation per list capacity (and per kind of code)
+    constexpr unsigned attr_bit = wide_attr_bit(LF, GK);               // one instantiation per list capacity (and per kind of code)
     if (!(ctx->wide_attr_mask & attr_bit)) {                           // per context (= per device): the attribute belongs to the device's copy of the kernel
         ES_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&es_scl_wide_kernel<L, LF, GK>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ctx->wide_attr_mask |= attr_bit;
     }
-    // One slab slot per resident workgroup.  The slab is sized in units of the context's largest block (Lm lanes); a smaller block
-    // gets Lm / L times as many slots out of the same bytes.
-    const int Lm = es_wide_lanes_max(ctx);
+    // One slab slot per resident workgroup.  The slab is sized in lanes (es_scl_wide_scratch_bytes); a block of L lanes gets
+    // wide_lanes / L slots out of it.
     constexpr int FRB = L / LF;                                     // frames per block
     const long long blocks = (B + FRB - 1) / FRB;                    // one frame group per wave / block; the hardware keeps <= 3 blocks (L = 128: 5) per CU resident
     if (blocks >= (1LL << 31)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }
     a.slot_bits = ctx->d_wide_slot_bits;
-    a.n_slots = ctx->wide_slots * (Lm / L);
+    a.n_slots = (int)(ctx->wide_lanes / L);
     a.slot_words = (a.n_slots + 31) / 32;
-    { const int rc = es_slab_enter(ctx, 1, 0x300 | L, true, st); if (rc) return rc; }       // slot stride depends on the block's lanes only
+    if (a.slot_words > ctx->wide_slot_words) { ctx->err = "es_scl_batch: the lane-per-path slab has more slots than its bitmap"; return ES_EINVAL; }   // (never: es_create sizes both)
+    constexpr int shape = 0x30000 | L;                               // slot stride depends on the block's lanes only (one tag per block size)
+    { const int rc = es_slab_enter(ctx, 1, shape, true, st); if (rc) return rc; }
     hipLaunchKernelGGL((es_scl_wide_kernel<L, LF, GK>), dim3((unsigned)blocks), dim3(L), lds, st, a);
     ES_HIP_CHECK(ctx, hipGetLastError());
-    { const int rc = es_slab_leave(ctx, 1, 0x300 | L, true, st); if (rc) return rc; }
+    { const int rc = es_slab_leave(ctx, 1, shape, true, st); if (rc) return rc; }
     return ES_OK;
 }
 
+// Arguments of a launch (and its frame counter, when the frames are drawn from one).
+int wide_args(es_ctx* ctx, WideArgs& a, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
+              uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric, uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+{
+    a = WideArgs{};
+    a.llr = llr; a.is_f64 = (dtype == ES_DTYPE_F64); a.B = B;
+    a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
+    a.alpha = reinterpret_cast<double*>(ctx->d_wide_scratch);
+    a.aux = reinterpret_cast<unsigned char*>(ctx->d_wide_scratch) + (size_t)ctx->wide_lanes * N * sizeof(double);
+    a.hard_info = hard_info; a.hard_ok = hard_ok; a.cand_info = cand_info;
+    a.cand_metric = cand_metric; a.cand_ok = cand_ok; a.ncand = ncand;
+    a.skip_if_hard_ok = skip_if_hard_ok;
+    a.lsz = L;
+    a.prio = ctx->scl_prio;
+    a.n_info = ctx->n_info; a.info_bytes = (ctx->n_info - 8 + 7) / 8;
+    if (skip_if_hard_ok && ES_WIDE_COMPACT) {             // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes)
+        if (B >= (1LL << 31) - (1LL << 24)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }   // (the counter runs past B by one draw per block)
+        const int rc = es_cursor_next(ctx, st, &a.cursor);
+        if (rc) return rc;
+        ES_HIP_CHECK(ctx, hipMemsetAsync(a.cursor, 0, sizeof(int), st));
+    }
+    return ES_OK;
+}
+
+#if ES_WIDE_LARGE_TU
+}  // namespace
+
+// Lists of 257..1024 paths (es_scl_wide_large.hip): capacities 512 and 1024, one block per CU.
+int es_launch_scl_wide_large(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
+                             uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
+                             uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+{
+    WideArgs a;
+    { const int rc = wide_args(ctx, a, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st); if (rc) return rc; }
+    const bool gk = ctx->n_info != KINFO;
+    if (L <= 512) return gk ? launch_wide<512, 512, true>(ctx, a, B, st) : launch_wide<512, 512>(ctx, a, B, st);
+    return gk ? launch_wide<1024, 1024, true>(ctx, a, B, st) : launch_wide<1024, 1024>(ctx, a, B, st);
+}
+#else
 // Diagnostic: the list decoder's f as its hot loops evaluate it (es_softplus_dev.h, exp table at LDS address 0), for a test against the host.
 __global__ __launch_bounds__(256) void es_polar_f_dev_kernel(const double* __restrict__ a, const double* __restrict__ b, long long n,
                                                              const uint64_t* __restrict__ exp_tab, double* __restrict__ out, int* __restrict__ bad)
@@ -1119,15 +1214,24 @@ int es_launch_polar_f_dev(es_ctx* ctx, const double* a, const double* b, int64_t
     return ES_OK;
 }
 
-// Scratch for this file's kernels: per resident workgroup of Lm lanes 1024*Lm doubles + WIDE_AUX_PER_PATH*Lm bytes.
-// Lists of up to 64 paths run in blocks of 256 lanes, so every context that has the scratch has it for 256-lane blocks.
-size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, int* slots_out)
+// Lanes of this file's workgroups one CU holds at most, over the block sizes a context serves (the slab holds a slot per resident
+// workgroup): 4 x ES_WIDE_WPS one-wave blocks = ES_WIDE_WPS blocks of 256 lanes = 2 x ES_WIDE_WPS of 128 (768 lanes); ONE block of 512
+// lanes (its LDS, checked in launch_wide) or of 1024.
+static int wide_cu_lanes(const es_ctx* ctx)
 {
-    if (!ctx->wide_enabled) { *slots_out = 0; return 0; }
-    const size_t Lm = (size_t)es_wide_lanes_max(ctx);
-    const int slots = ctx->num_cu * ES_WIDE_WPS * (int)(256 / Lm);          // 4 x ES_WIDE_WPS waves per CU
-    *slots_out = slots;
-    return (size_t)slots * (N * Lm * sizeof(double) + (size_t)WIDE_AUX_PER_PATH * Lm);
+    const int small = 4 * ES_WIDE_WPS * 64;
+    const int big = ctx->list_size_max > 256 ? es_list_cap(ctx->list_size_max) : 0;
+    return big > small ? big : small;
+}
+
+// Scratch for this file's kernels: per lane of a resident workgroup 1024 doubles + WIDE_AUX_PER_PATH bytes, for as many lanes as the CUs
+// hold at most over the block sizes the context serves (wide_cu_lanes); a block of L lanes takes L of them as one slot.
+size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, long long* lanes_out)
+{
+    if (!ctx->wide_enabled) { *lanes_out = 0; return 0; }
+    const long long lanes = (long long)ctx->num_cu * wide_cu_lanes(ctx);
+    *lanes_out = lanes;
+    return (size_t)lanes * (N * sizeof(double) + (size_t)WIDE_AUX_PER_PATH);
 }
 
 int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
@@ -1135,24 +1239,11 @@ int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L
                        uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
 {
     if (!ctx->d_wide_scratch) { ctx->err = "es_scl_batch: this context has no scratch for the lane-per-path list decoder (list_size_max <= 32 and scl_lanes 1 never requested before es_reserve)"; return ES_EINVAL; }
-    WideArgs a{};
-    a.llr = llr; a.is_f64 = (dtype == ES_DTYPE_F64); a.B = B;
-    a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
-    const size_t Lm = (size_t)es_wide_lanes_max(ctx);
-    a.alpha = reinterpret_cast<double*>(ctx->d_wide_scratch);
-    a.aux = reinterpret_cast<unsigned char*>(ctx->d_wide_scratch) + (size_t)ctx->wide_slots * N * Lm * sizeof(double);
-    a.hard_info = hard_info; a.hard_ok = hard_ok; a.cand_info = cand_info;
-    a.cand_metric = cand_metric; a.cand_ok = cand_ok; a.ncand = ncand;
-    a.skip_if_hard_ok = skip_if_hard_ok;
-    a.lsz = L;
-    a.prio = ctx->scl_prio;
-    a.n_info = ctx->n_info; a.info_bytes = (ctx->n_info - 8 + 7) / 8;
-    if (skip_if_hard_ok && ES_WIDE_COMPACT) {             // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes)
-        if (B >= (1LL << 31) - (1LL << 24)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }   // (the counter runs past B by one draw per block)
-        const int rc = es_cursor_next(ctx, st, &a.cursor);
-        if (rc) return rc;
-        ES_HIP_CHECK(ctx, hipMemsetAsync(a.cursor, 0, sizeof(int), st));
-    }
+    if (L > ES_MAX_LIST || L < 1) { ctx->err = "list_size must be in 1..1024"; return ES_EINVAL; }
+    if (L > 256)                                          // capacities 512 and 1024: a translation unit of their own (es_scl_wide_large.hip)
+        return es_launch_scl_wide_large(ctx, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st);
+    WideArgs a;
+    { const int rc = wide_args(ctx, a, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st); if (rc) return rc; }
     int LP = 1; while (LP < L) LP <<= 1;                  // kernel capacity: the next power of two
     if (ctx->n_info != KINFO) switch (LP) {               // a code other than the reference's own K = 448: the run-time-K instantiations
         case 1:   return launch_wide<64, 1, true>(ctx, a, B, st);
@@ -1179,3 +1270,4 @@ int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L
         default: ctx->err = "list_size must be in 1..256"; return ES_EINVAL;
     }
 }
+#endif

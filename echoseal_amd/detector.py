@@ -69,10 +69,14 @@ class WatermarkDetector:
     # ------------------------------------------------------------------ engine plumbing
     @property
     def engine(self):
-        if self._engine is None or self._engine.fs != self.fs_target:
-            from .fastpolar import engine_for_fs
+        from .fastpolar import SMALL_LIST_MAX, check_list_size
+        check_list_size(self._list_size)
+        large = self._list_size > SMALL_LIST_MAX
+        if self._engine is None or self._engine.fs != self.fs_target or (large and self._engine.list_size_max < self._list_size):
+            from .fastpolar import engine_for_fs, engine_for_large_list
             try:
-                self._engine = engine_for_fs(self.fs_target)       # tables (band-pass, template, taps) of this rate
+                # tables (band-pass, template, taps) of this rate; lists above 256 paths: the large-list engine
+                self._engine = engine_for_large_list(fs=self.fs_target) if large else engine_for_fs(self.fs_target)
             except ValueError as e:                                 # SciPy's own error (band above Nyquist) passes through, as in the reference
                 if "taps" not in str(e):
                     raise

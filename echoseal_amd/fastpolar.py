@@ -66,6 +66,34 @@ def engine_for_fs(fs: int):
     return _other_fs[1]
 
 
+SMALL_LIST_MAX = 256   # the process-wide engines' list_size_max; a longer list runs on `engine_for_large_list`
+_large = None          # ((K, fs), engine) of the last list above SMALL_LIST_MAX that was asked for
+
+
+def engine_for_large_list(K: int = 448, fs: int = 48_000):
+    """The engine lists of SMALL_LIST_MAX + 1 .. ES_MAX_LIST (1024) paths run on: list_size_max = ES_MAX_LIST, tables for fs, code K.
+    Built on first use only (its lane-per-path slab is ~2.2 GB; callers who never ask for a long list do not pay for it), one at a time
+    like `engine_for`: asking for another (K, fs) closes it."""
+    global _large
+    if _large is None or _large[0] != (K, fs):
+        import torch
+        from ._native import ES_MAX_LIST
+        from .engine import RxEngine
+        if _large is not None:
+            _large[1].close()
+            _large = None
+        _large = ((K, fs), RxEngine(torch.cuda.current_device() if torch.cuda.is_available() else 0, list_size_max=ES_MAX_LIST,
+                                    fs=fs, code_k=K))
+    return _large[1]
+
+
+def check_list_size(L: int) -> None:
+    """Lists above ES_MAX_LIST are not served (before any GPU work)."""
+    from ._native import ES_MAX_LIST
+    if L > ES_MAX_LIST:
+        raise NotImplementedError(f"list_size={L}: the HIP decoder supports list sizes up to {ES_MAX_LIST}")
+
+
 def _reliability_order(N: int) -> np.ndarray:
     rel = np.asarray(Q_NMAX_1024, dtype=np.int64)
     if rel.size != N:
@@ -144,7 +172,8 @@ class PolarCode:
             raise NotImplementedError("the HIP decoder serves Polar(1024, K) + CRC-8 (DESIGN.md section 7)")
         import torch
         from .engine import select_payload
-        eng = engine_for(self.K)
+        check_list_size(self.list_size)
+        eng = engine_for(self.K) if self.list_size <= SMALL_LIST_MAX else engine_for_large_list(self.K)
         if self.list_size > eng.list_size_max:
             raise NotImplementedError(f"list_size={self.list_size}: the HIP decoder supports list sizes up to {eng.list_size_max}")
         host = np.ascontiguousarray(llr, dtype=np.float32 if llr.dtype == np.float32 else np.float64)

@@ -47,7 +47,7 @@ extern "C" {
 #define ES_MAX_TAPS     576   /* row stride of the tap table: the reference's taps are 93..131 long at fs_target = 48 000, 550 at 44 100 (rtwm/detector.py:260-294) */
 #define ES_MAX_TAPS_FAST 160  /* up to here the demodulator runs its small-footprint instantiation */
 #define ES_MAX_PEAKS     32   /* detector consumes at most 25 peaks per scan (rtwm/detector.py:108) */
-#define ES_MAX_LIST     256   /* any list size 1..256; the mapping of paths to lanes is chosen per launch (es_set_option) */
+#define ES_MAX_LIST    1024   /* any list size 1..1024; the mapping of paths to lanes is chosen per launch (es_set_option) */
 #define ES_PN_BYTES     152   /* ceil(1215 / 8): packed PN row of one frame counter */
 
 #define ES_DTYPE_F32      0
@@ -56,8 +56,8 @@ extern "C" {
 
 typedef struct es_ctx es_ctx;
 
-/* Context: binds a device, owns table / scratch memory.  list_size_max 1..256: the largest list es_scl_batch will be asked for (sizes
- * the list decoder's scratch slabs, 0.4 GB; above 32 also the 1.6 GB lane-per-path slab).  list_size_max = 0: a FRONT-END context --
+/* Context: binds a device, owns table / scratch memory.  list_size_max 1..1024: the largest list es_scl_batch will be asked for (sizes
+ * the list decoder's scratch slabs, 0.4 GB; above 32 also the 1.6 GB lane-per-path slab, 2.2 GB above 512).  list_size_max = 0: a FRONT-END context --
  * every entry point except es_scl_batch, no list-decoder scratch at all (what a pipeline's band-pass / sync / demodulator streams use). */
 es_ctx*     es_create(int device, int list_size_max);
 void        es_destroy(es_ctx* ctx);
@@ -216,7 +216,7 @@ int es_header_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, 
 /* Polar(1024,448)+CRC-8 decode: hard-decision shortcut and successive-cancellation list.
  *   replaces PolarCode.decode (rtwm/fastpolar.py:254-359) up to validator selection
  *   llr_dev         [B][1024] ES_DTYPE_F32 or ES_DTYPE_F64
- *   list_size       1..256 (<= the context's list_size_max); any size, as in the reference: a size that is not a power of
+ *   list_size       1..1024 (<= the context's list_size_max); any size, as in the reference: a size that is not a power of
  *                   two runs on the next power of two's kernel with the surplus paths switched off
  *   skip_if_hard_ok non-zero: records whose hard decision passes CRC skip the list loop
  *                   (the reference's behaviour when validator is None, fastpolar.py:268-276); the lane-per-path kernel then
@@ -282,7 +282,7 @@ int es_polar_f_batch(es_ctx* ctx, const double* a_dev, const double* b_dev, int6
  * wavefront (a path owns 4 or 2 lanes: 16 or 32 paths per wavefront, three wavefronts per SIMD), and one lane per path (64/L
  * frames per wavefront, every lane busy at every tree depth: fewest instructions per frame, but a wavefront carries 64/L
  * frames through the whole decode, so it wants tens of thousands of frames per launch; the kernel that also serves lists of
- * 64..256 paths).  "scl_multi": -1 (default) chooses by batch size, 0 forces one frame per wavefront, 1 several.
+ * 64..1024 paths).  "scl_multi": -1 (default) chooses by batch size, 0 forces one frame per wavefront, 1 several.
  * "scl_lanes": lanes per path of the latter -- 4, 2, 1, or 0 (default: by batch size; 1 only when the context has that
  * kernel's scratch slab).  "scl_lane_slab" = 1 allocates that slab (1.6 GB; contexts created with list_size_max > 32 have
  * it from the start) without forcing anything: an allocation, so it belongs next to es_create / es_reserve, never between
