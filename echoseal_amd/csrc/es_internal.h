@@ -91,6 +91,12 @@ __device__ __forceinline__ uint32_t es_wave_incl_scan_u32(uint32_t x)
 __device__ __forceinline__ int es_wave_read_lane(int v, int src) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src)); }
 #endif
 
+/* Tiling of the sync correlation, shared by the float64 kernel (es_sync.hip) and the float32 screen (es_sync32.hip): a wave covers a segment
+ * of 64 lanes x XC_R consecutive lags (19 is odd: a lane stride of 19 words is free of LDS bank conflicts), a block is XC_WAVES waves. */
+constexpr int XC_R = 19;
+constexpr int XC_SEG = 64 * XC_R;                  /* lags per wave */
+constexpr int XC_WAVES = 4;
+
 /* kernels exist for power-of-two list sizes; a context created for list_size_max serves every size up to the next one */
 static inline int es_list_cap(int lmax) { int c = 1; while (c < lmax) c <<= 1; return c; }
 

@@ -20,6 +20,7 @@
 //
 // Build with -ffp-contract=off.
 #include "es_internal.h"
+#include "es_wave.h"
 #include <cstdio>
 
 namespace {
@@ -29,10 +30,7 @@ constexpr int PAYLOAD_START = ES_PRE_L + ES_HDR_L;   // 191
 // Sizes that follow from the longest matched filter the kernel must hold.  Two instantiations: ES_MAX_TAPS_FAST (160: the taps of the
 // default fs_target = 48 000 are 93..131 long) and ES_MAX_TAPS (576: any fs_target the reference's band plan admits down to 44 100 Hz, where
 // the 18-22 kHz band sits at Nyquist and the cascade's impulse response needs 550 taps; rtwm/detector.py:260-294).
-#ifndef ES_LLR_MF_R
-#define ES_LLR_MF_R 7
-#endif
-constexpr int MF_R = ES_LLR_MF_R;                              // matched-filter outputs per thread (odd: a lane stride of 7 words is free of LDS bank conflicts; 6 was two-way)
+constexpr int MF_R = 7;                                        // matched-filter outputs per thread (odd: a lane stride of 7 words is free of LDS bank conflicts; 6 was two-way)
 template <int MAXT> struct LlrSizes {
     static constexpr int MAX_RX = NPAY + MAXT;                             // prefix + payload
     static constexpr int MAX_WIN = NPAY + 2 * MAXT + 8;                    // matched-filter window
@@ -97,23 +95,6 @@ __device__ __forceinline__ float wave_pairwise_sum(const PwPlan& p, int lane, F 
     return r;
 }
 
-// lane l <-> lane l ^ S through the data-parallel primitives (quad_perm for 1, 2; a row shift each way and a
-// select for 4, 8); 16 and 32 go through ds_bpermute.
-template <int S>
-__device__ __forceinline__ float xor_lanes_f32(float x, int lane)
-{
-    int v; __builtin_memcpy(&v, &x, 4);
-    int r;
-    if constexpr (S == 1) r = __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);
-    else if constexpr (S == 2) r = __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);
-    else if constexpr (S == 4 || S == 8) {
-        const int up = __builtin_amdgcn_mov_dpp(v, 0x100 + S, 0xf, 0xf, true);     // row_shl:S (lane l gets l+S)
-        const int dn = __builtin_amdgcn_mov_dpp(v, 0x110 + S, 0xf, 0xf, true);     // row_shr:S (lane l gets l-S)
-        r = (lane & S) ? dn : up;
-    } else r = __shfl_xor(v, S);
-    float o; __builtin_memcpy(&o, &r, 4); return o;
-}
-
 // The shift search evaluates the same pairwise tree hundreds of times per record on NON-NEGATIVE data (|win|), which
 // allows a latency-free form: every lane issues all the LDS reads of its leaf up front (absent elements read as
 // +0.0, and x + (+0.0) == x exactly for x >= +0), then adds in NumPy's order.  A leaf is at most 128 long (NumPy
@@ -160,17 +141,6 @@ __device__ __forceinline__ float wave_pairwise_sum_nonneg_abs(const PwLane& g, i
     r = r + xor_lanes_f32<16>(r, lane);
     r = r + xor_lanes_f32<32>(r, lane);
     return r;
-}
-
-__device__ __forceinline__ uint32_t f32_key(float x)
-{
-    uint32_t b; __builtin_memcpy(&b, &x, 4);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k)
-{
-    const uint32_t b = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float x; __builtin_memcpy(&x, &b, 4); return x;
 }
 
 // k-th smallest of the wave's keys by ONE wave: four 8-bit-digit passes on four private LDS histograms (lane & 3: the leading byte of a

@@ -44,13 +44,7 @@ struct MCfg {
 };
 constexpr int MWIN = KINFO / 32;                   // trace-back windows of 32 information bits
 constexpr int MWPB = 4;                            // waves per block
-#ifndef ES_MULTI_MINW
-#define ES_MULTI_MINW 3                            // waves per SIMD the register allocation must allow (LDS admits that many blocks per CU)
-#endif
-#ifndef ES_MULTI_ILP
-#define ES_MULTI_ILP 1                             // independent f evaluations in flight per lane in the slot-storage loops
-#endif
-constexpr int MMINW = ES_MULTI_MINW;
+constexpr int MMINW = 3;                           // waves per SIMD the register allocation must allow (LDS admits that many blocks per CU)
 template <int PP> constexpr int mslab_doubles() { return MCfg<PP>::NP * MCfg<PP>::GSLOT + (MCfg<PP>::TBW_GLOBAL ? MWIN * MCfg<PP>::NP / 2 : 0); }   // per wave
 
 template <int L, int PP>
@@ -263,15 +257,7 @@ __global__ __launch_bounds__(64 * MWPB, ((L <= 8 || PP == 2) ? MMINW : 1)) void 
                         }
                     } else {
                         int j = j0;
-#if ES_MULTI_ILP == 2
-                        for (; j + jst < S; j += 2 * jst) {        // two independent f chains in flight
-                            double a0, c0, a1, c1; load_pair(j, a0, c0); load_pair(j + jst, a1, c1);
-                            const double o0 = es_polar_f(a0, c0, tab);
-                            const double o1 = es_polar_f(a1, c1, tab);
-                            store_out(j, o0); store_out(j + jst, o1);
-                        }
-#endif
-                        // one f (= two interleaved softplus chains) in flight per lane: the other waves of the SIMD hide the rest
+                        // one f (= two interleaved softplus chains) in flight per lane: the other waves of the SIMD hide the rest (two were no faster)
                         if constexpr (C::PREFETCH) {
                             // ... and the NEXT pair of parents already on its way (past the end: this lane's last element again)
                             if (j < S) {
@@ -357,17 +343,6 @@ __global__ __launch_bounds__(64 * MWPB, ((L <= 8 || PP == 2) ? MMINW : 1)) void 
                     for (int h = S >> 1; h >= P; h >>= 1) {           // nodes of 2h values -> children of h values
                         const int lh = 31 - __builtin_clz((unsigned)h);
                         int idx = q;
-#if ES_MULTI_ILP == 2
-                        for (; idx + P < (S >> 1); idx += 2 * P) {    // two independent f chains in flight
-                            const int e0 = ((idx >> lh) << (lh + 1)) + (idx & (h - 1));
-                            const int e1 = (((idx + P) >> lh) << (lh + 1)) + ((idx + P) & (h - 1));
-                            const double a0 = ld(e0), c0 = ld(e0 + h), a1 = ld(e1), c1 = ld(e1 + h);
-                            const double o0 = es_polar_f(a0, c0, tab);
-                            const double o1 = es_polar_f(a1, c1, tab);
-                            st(e0, o0); st(e0 + h, es_polar_g(a0, c0, 0u));
-                            st(e1, o1); st(e1 + h, es_polar_g(a1, c1, 0u));
-                        }
-#endif
                         for (; idx < (S >> 1); idx += P) {
                             const int e0 = ((idx >> lh) << (lh + 1)) + (idx & (h - 1));
                             const double a0 = ld(e0), c0 = ld(e0 + h);

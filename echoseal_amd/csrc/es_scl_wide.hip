@@ -7,7 +7,7 @@
 // Where things live (lane p owns path p and slot p of every slot-indexed store):
 //   * LLR tree depths 1..DL-1 (512..16 values per path): a scratch slab laid out [element][slot] (no cache holds it), so the lanes of a
 //     wave touch one contiguous row; a lane walks a node's elements serially.  DL = 7 in one-wave blocks, 8 in blocks of several waves.
-//     The g half of depth 1 (bits 512..) is never stored: llr[e + 512] +- llr[e], formed on the fly where it is consumed (ES_WIDE_L1R).
+//     The g half of depth 1 (bits 512..) is never stored: llr[e + 512] +- llr[e], formed on the fly where it is consumed (float32 channel LLRs).
 //   * depths DL..9 (8 + 4 + 2 values at DL = 7): LDS, [element][slot]; depth 10 (the leaf LLR): a register.
 //   * slot pointers (which slot holds my data at depth d): one byte per depth packed in two 64-bit registers (16 bits above 256 paths),
 //     partial-sum blocks of 1..16 bits in one 32-bit register (as in es_scl.hip), of 32 and 64 bits in LDS by
@@ -51,33 +51,11 @@
 #include "es_scl_common.h"
 #include "es_softplus_dev.h"
 #include <type_traits>
-#ifndef ES_WIDE_GBATCH
-#define ES_WIDE_GBATCH 8                          /* load pairs in flight in the lane-serial g loops (divides 8; 8: +1 % over 4, measured) */
-#endif
-
-#ifndef ES_WIDE_WPS
-#define ES_WIDE_WPS 3                             /* waves per SIMD the kernel is compiled for (168 VGPRs at 3) */
-#endif
-#ifndef ES_WIDE_FUSE_GF
-#define ES_WIDE_FUSE_GF 1                         /* 1: the g at the top of a step and the f level below it in one pass (slab levels 2..6); 3: also pairs of f levels */
-#endif
-#ifndef ES_WIDE_DEFER
-#define ES_WIDE_DEFER 12                          /* where the generic softplus is a deferred cold path instead of a branch after each evaluation: 1 slab f loops, 2 depth 8, 4 depth 9, 8 depth 10 */
-#endif
-#ifndef ES_WIDE_COMPACT
-#define ES_WIDE_COMPACT 1                         /* skip_if_hard_ok: blocks draw frames from a counter until they hold a full group that failed the hard decision (0: fixed groups, settled frames ride along as idle lanes) */
-#endif
-#ifndef ES_WIDE_FDIST
-#define ES_WIDE_FDIST 2                           /* f loops: operand pairs requested this many f evaluations ahead (1: rotation by copy; 2: unrolled by three) */
-#endif
-#ifndef ES_WIDE_L1R
-#define ES_WIDE_L1R 1                             /* the g half of tree depth 1 is never stored: its elements are llr[e + 512] +- llr[e] by one partial-sum bit, formed on the fly by the two passes that consume them (bits 512 and 768) */
-#endif
-#ifndef ES_WIDE_LDS_DEPTH
-#define ES_WIDE_LDS_DEPTH 7                       /* one-wave blocks: first LLR-tree depth kept in LDS (7: 8 + 4 + 2 rows of doubles by slot; 8: round 3's layout; 6 needs two waves per SIMD) */
-#endif
 
 namespace {
+
+constexpr int WIDE_GBATCH = 8;                    // load pairs in flight in the lane-serial g loops (divides 8; 8: +1 % over 4, measured)
+constexpr int WIDE_WPS = 3;                       // waves per SIMD the kernel is compiled for (168 VGPRs at 3)
 
 struct WideArgs {
     const void* llr; int is_f64; long long B;
@@ -105,7 +83,8 @@ constexpr int WIDE_AUX_PER_PATH = MWIN_MAX * 6 + 28 * 4 + 16 * 4;
 // LLR-tree depths DL..9 live in LDS, [element][slot]: depth d at rows [wide_low_row(DL, d), +1024 >> d).  A block that is one wave keeps depth 7
 // there too (DL = 7: a step whose top is depth 7 or below then touches the slab only to READ depth 6, and the values that are written and
 // read back within a few hundred cycles never leave the CU); blocks of several waves hold a frame of 128 / 256 paths and have no LDS to spare.
-constexpr int wide_dl(bool one_wave) { return one_wave ? ES_WIDE_LDS_DEPTH : 8; }
+// (one-wave blocks: 7 = 8 + 4 + 2 rows of doubles by slot; 8 was round 3's layout; 6 needs two waves per SIMD)
+constexpr int wide_dl(bool one_wave) { return one_wave ? 7 : 8; }
 constexpr int wide_low_row(int DL, int d) { int r = 0; for (int k = DL; k < d; ++k) r += N >> k; return r; }
 
 // Slot pointers of a path (which slot holds its data at a depth): one byte per depth in a 64-bit word while slots fit a byte (L <= 256),
@@ -146,13 +125,10 @@ struct WidePub {
     uint16_t sidx[NBUF][2 * L];
 };
 struct WidePubBperm { };
-#ifndef ES_WIDE_GATHER_BPERM
-#define ES_WIDE_GATHER_BPERM 1                    /* one-wave blocks: survivors take their parent's state with ds_bpermute (0: through LDS, as blocks of several waves do) */
-#endif
 // buffers of the published state: NB = 1 one wave per block, 2 several
 constexpr int wide_pub_bufs(int L, int NB) { return (NB == 2 && L > 512) ? 1 : NB; }
 template <int L, int NB>
-using wide_pub_t = std::conditional_t<NB == 1 && ES_WIDE_GATHER_BPERM, WidePubBperm, WidePub<L, wide_pub_bufs(L, NB)>>;
+using wide_pub_t = std::conditional_t<NB == 1, WidePubBperm, WidePub<L, wide_pub_bufs(L, NB)>>;
 
 template <int L, int NB>
 struct WideLds {
@@ -177,26 +153,12 @@ __device__ __forceinline__ int wxor_b32(int v, int D)
         default: return __shfl_xor(v, 32);
     }
 }
-__device__ __forceinline__ double wxor_f64(double x, int D)
-{
-    uint64_t u; __builtin_memcpy(&u, &x, 8);
-    const uint32_t lo = (uint32_t)wxor_b32((int)(uint32_t)u, D);
-    const uint32_t hi = (uint32_t)wxor_b32((int)(uint32_t)(u >> 32), D);
-    u = ((uint64_t)hi << 32) | lo;
-    double r; __builtin_memcpy(&r, &u, 8); return r;
-}
 
-__device__ __forceinline__ bool cand_before(double ka, uint32_t ia, double kb, uint32_t ib) { return (ka < kb) || (ka == kb && ia < ib); }
-
-#ifndef ES_WIDE_SORT_ASM
-#define ES_WIDE_SORT_ASM 1
-#endif
-#if ES_WIDE_SORT_ASM
 // Compare-exchange steps of the sort network, written out: path metrics are sums of non-negative penalties (or +inf for a dead
 // lane), so their bit patterns order like their values and (metric, index) compares as the 96-bit unsigned number hi:lo:index --
 // ONE borrow chain of three subtractions leaves "mine sorts before the partner's" in VCC, and with the partner in a lane that DPP
 // reaches the partner's words are an operand modifier of the subtractions and of the three selects: 6 vector instructions per
-// element and stage where the compiler's rendering of cand_before() + selects takes 10.  With the DPP modifier the subtraction is
+// element and stage where the compiler's rendering of the plain C++ compare (ka < kb || (ka == kb && ia < ib)) + selects takes 10.  With the DPP modifier the subtraction is
 // partner - mine (the modified operand is the minuend; tools/ub/ub_dppvcc.hip), so VCC = "the partner sorts before mine" and keeping
 // mine is VCC xor take_min (equal elements are two dead lanes' identical fillers: either may be kept).  (s_nop 1: a DPP operand must
 // not have been written by the two preceding vector instructions; the compiler cannot see into the block.)  tools/ub/ub_sortce.hip
@@ -246,7 +208,6 @@ __device__ __forceinline__ void ce_inlane(uint32_t& lo0, uint32_t& hi0, uint32_t
                  : "s"(amask) : "vcc", "scc");
     lo0 = nlo0; hi0 = nhi0; ix0 = nix0;
 }
-#endif
 
 // Bitonic network over 2L (key, index) pairs, element e = 2 * lane + b held as (k0, i0) / (k1, i1); ascending on exit.
 // (LF < L: independent networks over aligned groups of LF lanes -- one per frame; pl = lane index within the frame)
@@ -254,7 +215,6 @@ template <int L, int LF>
 __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, uint32_t& i1, const int p, const int pl, WideLds<L, (LF > 64 ? 2 : 1)>& W, int& buf)
 {
     constexpr int NBUF = wide_pub_bufs(L, LF > 64 ? 2 : 1);     // 1: one buffer, a barrier before each write to it (see WidePub)
-#if ES_WIDE_SORT_ASM
     uint64_t u0, u1; __builtin_memcpy(&u0, &k0, 8); __builtin_memcpy(&u1, &k1, 8);
     uint32_t lo0 = (uint32_t)u0, hi0 = (uint32_t)(u0 >> 32), lo1 = (uint32_t)u1, hi1 = (uint32_t)(u1 >> 32);
     #pragma unroll
@@ -300,52 +260,6 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
     }
     u0 = ((uint64_t)hi0 << 32) | lo0; u1 = ((uint64_t)hi1 << 32) | lo1;
     __builtin_memcpy(&k0, &u0, 8); __builtin_memcpy(&k1, &u1, 8);
-#else
-    #pragma unroll
-    for (int k = 2; k <= 2 * LF; k <<= 1) {
-        const bool asc = ((2 * pl) & k) == 0;                    // k == 2 LF: always ascending
-        #pragma unroll
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            if (j == 1) {                                        // partner = the lane's other element
-                const bool sw = cand_before(k1, i1, k0, i0) == asc;
-                const double tk = sw ? k1 : k0; const uint32_t ti = sw ? i1 : i0;
-                k1 = sw ? k0 : k1; i1 = sw ? i0 : i1; k0 = tk; i0 = ti;
-            } else {
-                const int dl = j >> 1;                           // partner lane p ^ dl, same b
-                const bool take_min = (((pl & dl) == 0) == asc);
-                double ok0 = 0, ok1 = 0; uint32_t oi0 = 0, oi1 = 0;
-                bool cross = false;
-                if constexpr (LF > 64) {
-                    if (dl >= 64) {
-                        cross = true;
-                        if constexpr (NBUF == 1) __syncthreads();
-                        W.pub.skey[buf][2 * p] = k0; W.pub.skey[buf][2 * p + 1] = k1;
-                        W.pub.sidx[buf][2 * p] = (uint16_t)i0; W.pub.sidx[buf][2 * p + 1] = (uint16_t)i1;
-                        __syncthreads();
-                        const int o = p ^ dl;
-                        ok0 = W.pub.skey[buf][2 * o]; ok1 = W.pub.skey[buf][2 * o + 1];
-                        oi0 = W.pub.sidx[buf][2 * o]; oi1 = W.pub.sidx[buf][2 * o + 1];
-                        if constexpr (NBUF == 2) buf ^= 1;
-                    }
-                }
-                if (!cross) {
-                    ok0 = wxor_f64(k0, dl); ok1 = wxor_f64(k1, dl);
-                    oi0 = (uint32_t)wxor_b32((int)i0, dl); oi1 = (uint32_t)wxor_b32((int)i1, dl);
-                }
-                const bool m0 = cand_before(k0, i0, ok0, oi0) == take_min;   // keep mine?
-                const bool m1 = cand_before(k1, i1, ok1, oi1) == take_min;
-                k0 = m0 ? k0 : ok0; i0 = m0 ? i0 : oi0;
-                k1 = m1 ? k1 : ok1; i1 = m1 ? i1 : oi1;
-            }
-        }
-    }
-#endif
-}
-
-// cold path of the slab f loops: the whole level again with the generic softplus where a lane needs it (values identical for the others)
-__device__ __attribute__((noinline)) void f_level_exact(const double* par, double* dst, int S, int L, const uint64_t* tab)
-{
-    for (int j = 0; j < S; ++j) dst[(long long)j * L] = es_polar_f(par[(long long)j * L], par[(long long)(j + S) * L], tab);
 }
 
 // hard decision -> butterfly -> data bits -> CRC of one frame by one wave (fastpolar.py:260-268); returns the CRC verdict to every lane
@@ -427,7 +341,7 @@ __device__ __forceinline__ int hard_decision_wave(const WideArgs& a, long long f
 // GK: any code Polar(1024, K) + CRC-8, 9 <= K <= 1024 (the reference's PolarCode takes any K, rtwm/fastpolar.py:209-234): K, the row width
 // and the number of trace-back windows are run-time values (a.n_info, a.info_bytes).  The default instantiation (K = 448, everything the
 // reference itself instantiates) keeps them as compile-time constants: its code is unchanged by the existence of the other.
-constexpr int wide_wps(int L) { return L == 1024 ? 4 : L == 512 ? 2 : ES_WIDE_WPS; }     // waves per SIMD: 512 / 1024 paths -- one block per CU
+constexpr int wide_wps(int L) { return L == 1024 ? 4 : L == 512 ? 2 : WIDE_WPS; }     // waves per SIMD: 512 / 1024 paths -- one block per CU
 template <int L, int LF, bool GK = false>
 __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
 {
@@ -633,7 +547,6 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 // --- depths top..DL-1: slab to slab, the lane walks the node
                 bool have_dl = false;                                               // depth DL already formed (in LDS) by a fused pass of this step
                 int d_first = top;
-#if ES_WIDE_L1R
                 // Depth 1 of the SECOND half of the code word (bits 512..) is g(llr[e], llr[e + 512], u1[e]) = llr[e + 512] +- llr[e]: one bit of the
                 // 512-bit partial-sum block picks one of two values that the frame's channel LLRs already hold.  It is never stored (512 doubles written
                 // and twice read per path otherwise: 8.5 % of the slab traffic, and a 512-element load-add-store loop): the two passes that consume it --
@@ -693,7 +606,6 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     d_first = 3;
                     if (i == 768) { pa_ = p8_set(pa_, 2, p); d_first = 4; }
                 }
-#endif
                 for (int d = d_first; d < DL; ++d) {
                     const int S = N >> d;
                     const bool is_g = (i >> (NLEV - d)) & 1;
@@ -704,10 +616,11 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     // control flow between a load and its use, and the compiler then waits for ALL outstanding loads (s_waitcnt vmcnt(0)) right
                     // after issuing each pair -- the batches below would run one memory round trip per pair instead of GBATCH pairs in flight.
                     auto ld_slab = [&](int j, double& pa, double& pb) { pa = par[(long long)j * L]; pb = par[(long long)(j + S) * L]; };
-#if ES_WIDE_FUSE_GF
-                    if (d > 1 && d < (DL < 7 ? DL : 7) && (is_g || (ES_WIDE_FUSE_GF & 2) || ((ES_WIDE_FUSE_GF & 4) && d + 1 == DL))) {
-                        // Two levels in ONE pass: level d (the g of the bit just decided when it is the top of the step, else an f) and the f
-                        // level below it.  The two level-d results that make an f operand pair -- elements i and i + S/2 -- are formed
+                    if (d > 1 && d < 7 && is_g) {
+                        // Two levels in ONE pass: level d, the g of the bit just decided at the top of a step, and the f level below it.
+                        // (Fusing pairs of f levels as well measured no gain.  Its arm -- pair_ff and the !is_g loop -- can no longer be reached
+                        // but stays in the text: without it the compiler allocates the kernel's registers differently, and the tuned code object
+                        // is to stay as it is.)  The two level-d results that make an f operand pair -- elements i and i + S/2 -- are formed
                         // together, stored (their g child reads them later) and consumed from registers, so that level d+1 does not read
                         // back what was written S elements earlier (at these sizes from the Infinity Cache or HBM).
                         const int bs = (is_g && d <= 5) ? p8_get(pb_, d - 1) : 0;
@@ -768,7 +681,6 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                         pa_ = p8_set(pa_, d - 1, p);
                         continue;
                     }
-#endif
                     if (is_g) {
                         const int bs = (d <= 5) ? p8_get(pb_, d - 1) : 0;
                         auto g_level = [&](auto ld) {
@@ -776,12 +688,12 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                                 uint32_t wbits; int nb;
                                 if (S >= 32) { wbits = beta_ld((S + j0) >> 5, bs); nb = 32; }
                                 else { wbits = b0 >> S; nb = S; }
-                                for (int u = 0; u < nb; u += ES_WIDE_GBATCH) {     // (g is an add: the loop is memory latency) GBATCH independent load pairs in flight
-                                    double xa[ES_WIDE_GBATCH], xb[ES_WIDE_GBATCH];
+                                for (int u = 0; u < nb; u += WIDE_GBATCH) {     // (g is an add: the loop is memory latency) GBATCH independent load pairs in flight
+                                    double xa[WIDE_GBATCH], xb[WIDE_GBATCH];
                                     #pragma unroll
-                                    for (int v = 0; v < ES_WIDE_GBATCH; ++v) ld(j0 + u + v, xa[v], xb[v]);
+                                    for (int v = 0; v < WIDE_GBATCH; ++v) ld(j0 + u + v, xa[v], xb[v]);
                                     #pragma unroll
-                                    for (int v = 0; v < ES_WIDE_GBATCH; ++v) dst[(long long)(j0 + u + v) * L] = es_polar_g(xa[v], xb[v], (wbits >> (u + v)) & 1u);
+                                    for (int v = 0; v < WIDE_GBATCH; ++v) dst[(long long)(j0 + u + v) * L] = es_polar_g(xa[v], xb[v], (wbits >> (u + v)) & 1u);
                                 }
                             }
                         };
@@ -790,28 +702,9 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                         else g_level([&](int j, double& pa, double& pb) { pa = (double)llr32[j]; pb = (double)llr32[j + S]; });
                     } else {
                         // an f level is never the top of a step (the top is the g whose bit was just decided): d >= 2, operands from the slab
-#if ES_WIDE_FDIST == 2
                         // three operand pairs in rotation, the loop unrolled by three so that the rotation is a renaming, not a copy (a copy of a
                         // register that a load is still filling waits for the load): the operands of element j + 3 are requested right after
                         // f(j) and used two f evaluations later.  Loads past the end re-read the last element (S >= 8).
-                        // The loop body is straight-line: operands outside the range of the straight-line softplus (|t| >= 512) only raise `bad`, and the level is then redone with the generic form in a cold loop after it.
-#if ES_WIDE_DEFER & 1
-                        double a0, b0_, a1, b1_, a2, b2_;
-                        int bad = 0;
-                        ld_slab(0, a0, b0_); ld_slab(1, a1, b1_); ld_slab(2, a2, b2_);
-                        for (int j = 0; ; j += 3) {
-                            dst[(long long)j * L] = es_polar_f_sl(a0, b0_, tab, &bad);
-                            if (j + 1 >= S) break;
-                            ld_slab(j + 3 < S ? j + 3 : S - 1, a0, b0_);
-                            dst[(long long)(j + 1) * L] = es_polar_f_sl(a1, b1_, tab, &bad);
-                            if (j + 2 >= S) break;
-                            ld_slab(j + 4 < S ? j + 4 : S - 1, a1, b1_);
-                            dst[(long long)(j + 2) * L] = es_polar_f_sl(a2, b2_, tab, &bad);
-                            if (j + 3 >= S) break;
-                            ld_slab(j + 5 < S ? j + 5 : S - 1, a2, b2_);
-                        }
-                        if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) f_level_exact(par, dst, S, L, tab);     // rare
-#else
                         double a0, b0_, a1, b1_, a2, b2_;
                         ld_slab(0, a0, b0_); ld_slab(1, a1, b1_); ld_slab(2, a2, b2_);
                         for (int j = 0; ; j += 3) {
@@ -825,30 +718,17 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                             if (j + 3 >= S) break;
                             ld_slab(j + 5 < S ? j + 5 : S - 1, a2, b2_);
                         }
-#endif
-#else
-                        double pa, pb, qa, qb;                                   // operands of elements j+1 and j+2 are on their way while f(j) runs (S >= 8)
-                        ld_slab(0, pa, pb); ld_slab(1, qa, qb);
-                        for (int j = 0; j < S - 2; ++j) {
-                            double na, nb;
-                            ld_slab(j + 2, na, nb);
-                            dst[(long long)j * L] = es_polar_f_slg(pa, pb, tab);
-                            pa = qa; pb = qb; qa = na; qb = nb;
-                        }
-                        dst[(long long)(S - 2) * L] = es_polar_f_slg(pa, pb, tab);
-                        dst[(long long)(S - 1) * L] = es_polar_f_slg(qa, qb, tab);
-#endif
                     }
                     pa_ = p8_set(pa_, d - 1, p);
                 }
                 // --- depths DL..9 in LDS: level DL from the slab (unless a fused pass has just formed it), the others LDS -> LDS; S = 1024 >> d
-                // elements by slot.  (ES_WIDE_DEFER: the generic softplus as a cold path after the level instead of a branch per evaluation --
-                // bit 1 depth 8, bit 2 depth 9; levels of 8 or 16 elements always.)
+                // elements by slot.  (The generic softplus is a cold path after the level, instead of a branch after each evaluation, at every depth
+                // but 8: at levels of 8 or 16 elements and at depths 9 and 10.  Depth 8 -- 4 elements -- keeps the branch.)
                 auto low_level = [&](auto dc, auto from_slab) {
                     constexpr int d = decltype(dc)::value;
                     constexpr int S = N >> d;
                     constexpr bool SLAB = decltype(from_slab)::value;
-                    constexpr bool DEFER = S > 4 || (d == 8 ? (ES_WIDE_DEFER & 2) : (ES_WIDE_DEFER & 4)) != 0;
+                    constexpr bool DEFER = S > 4 || d == 9;                           // all but depth 8
                     constexpr int rs = wide_low_row(DL, d - 1), rd = wide_low_row(DL, d);
                     constexpr int C = S < 4 ? S : 4;                                  // f evaluations per chunk (registers are indexed statically: no private arrays)
                     const int ps = p8_get(pa_, d - 2);                                // slot of my depth d-1 block
@@ -885,7 +765,6 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 };
                 using std::integral_constant;
                 if (top <= DL && !have_dl) low_level(integral_constant<int, DL>{}, std::true_type{});
-                if constexpr (DL < 7) { if (top <= 7) low_level(integral_constant<int, 7>{}, std::false_type{}); }
                 if constexpr (DL < 8) { if (top <= 8) low_level(integral_constant<int, 8>{}, std::false_type{}); }
                 if (top <= 9) low_level(integral_constant<int, 9>{}, std::false_type{});
                 // --- depth 10: LDS -> register
@@ -893,15 +772,11 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     const int ps = p8_get(pb_, 5);
                     const double xa = W.low[lrow(9)][ps], xb = W.low[lrow(9) + 1][ps];
                     if (i & 1) lam = es_polar_g(xa, xb, (b0 >> 1) & 1u);
-#if ES_WIDE_DEFER & 8
-                    else {
+                    else {                                                // (generic softplus as a cold path, as at depth 9)
                         int bad = 0;
                         lam = es_polar_f_sl_sp(xa, xb, tab, &sp_diff, &sp_sum, &bad);
                         if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) lam = es_polar_f_sp(xa, xb, tab, &sp_diff, &sp_sum);
                     }
-#else
-                    else lam = es_polar_f_sp(xa, xb, tab, &sp_diff, &sp_sum);
-#endif
                 }
                 dirty = true;
             }
@@ -927,7 +802,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 const bool wstart = (info_idx & 31) == 0;
                 const int keep = nc < a.lsz ? nc : a.lsz;          // a.lsz <= LF: lists of any size run on the next power of two's kernel
                 const int myr = pl < keep ? pl : 0;                // dead paths mirror rank 0
-                if constexpr (WAVE && ES_WIDE_GATHER_BPERM) {
+                if constexpr (WAVE) {
                     // One wave: the survivor of rank r takes sorted element r and then its parent's state straight from the registers of the
                     // lanes that hold them (ds_bpermute: no LDS storage, no fence -- the lanes of a wave run in lock step).
                     int buf = 0;
@@ -986,7 +861,6 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 cnt = keep;
                 ++info_idx;
                 if constexpr (!WAVE) dirty = false;                // every wave passed the sort's barriers after its reads
-                else if constexpr (!ES_WIDE_GATHER_BPERM) wave_fence_lds();   // (one wave: the published rows are rewritten two sorts later, in order)
             }
 
             // --- partial sums: fold upward while the node is a right child (fastpolar.py:156-183); each lane its own path
@@ -1117,9 +991,7 @@ int launch_wide(es_ctx* ctx, WideArgs a, int64_t B, hipStream_t st)
     static_assert((sizeof(WideLds<512, 2>) + 1279) / 1280 * 1280 <= 160 * 1024 && (sizeof(WideLds<512, 2>) + 1279) / 1280 * 1280 * 2 > 160 * 1024,
                   "one workgroup per CU at L = 512 (wide_cu_lanes counts 512 lanes for it)");
     static_assert((sizeof(WideLds<1024, 2>) + 1279) / 1280 * 1280 <= 160 * 1024, "one workgroup per CU at L = 1024 (single-buffered WidePub)");
-#if ES_WIDE_GATHER_BPERM && ES_WIDE_LDS_DEPTH >= 7
-    static_assert((sizeof(WideLds<64, 1>) + 1279) / 1280 * 1280 * 4 * ES_WIDE_WPS <= 160 * 1024, "4 x ES_WIDE_WPS one-wave workgroups per CU");
-#endif
+    static_assert((sizeof(WideLds<64, 1>) + 1279) / 1280 * 1280 * 4 * WIDE_WPS <= 160 * 1024, "4 x WIDE_WPS one-wave workgroups per CU");
     static_assert((LF & (LF - 1)) == 0, "power of two");
     constexpr unsigned attr_bit = wide_attr_bit(LF, GK);               // one instantiation per list capacity (and per kind of code)
     if (!(ctx->wide_attr_mask & attr_bit)) {                           // per context (= per device): the attribute belongs to the device's copy of the kernel
@@ -1159,7 +1031,7 @@ int wide_args(es_ctx* ctx, WideArgs& a, const void* llr, int dtype, int64_t B, i
     a.lsz = L;
     a.prio = ctx->scl_prio;
     a.n_info = ctx->n_info; a.info_bytes = (ctx->n_info - 8 + 7) / 8;
-    if (skip_if_hard_ok && ES_WIDE_COMPACT) {             // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes)
+    if (skip_if_hard_ok) {                                // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes, as they did in fixed groups)
         if (B >= (1LL << 31) - (1LL << 24)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }   // (the counter runs past B by one draw per block)
         const int rc = es_cursor_next(ctx, st, &a.cursor);
         if (rc) return rc;
@@ -1215,11 +1087,11 @@ int es_launch_polar_f_dev(es_ctx* ctx, const double* a, const double* b, int64_t
 }
 
 // Lanes of this file's workgroups one CU holds at most, over the block sizes a context serves (the slab holds a slot per resident
-// workgroup): 4 x ES_WIDE_WPS one-wave blocks = ES_WIDE_WPS blocks of 256 lanes = 2 x ES_WIDE_WPS of 128 (768 lanes); ONE block of 512
+// workgroup): 4 x WIDE_WPS one-wave blocks = WIDE_WPS blocks of 256 lanes = 2 x WIDE_WPS of 128 (768 lanes); ONE block of 512
 // lanes (its LDS, checked in launch_wide) or of 1024.
 static int wide_cu_lanes(const es_ctx* ctx)
 {
-    const int small = 4 * ES_WIDE_WPS * 64;
+    const int small = 4 * WIDE_WPS * 64;
     const int big = ctx->list_size_max > 256 ? es_list_cap(ctx->list_size_max) : 0;
     return big > small ? big : small;
 }

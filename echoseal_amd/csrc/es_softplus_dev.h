@@ -25,7 +25,7 @@
 /* 0.0 or 1.0 by a flag: a select of the high word only */
 ES_HD double es_flag01(int on) { return es_u2d((uint64_t)(on ? 0x3ff00000u : 0u) << 32); }
 
-/* log1p(exp(t)) for t <= 0, bit-identical to es_softplus_neg_fast (the ES_SOFTPLUS_CORNER 1 form); *ok = 0 outside |t| < 512 */
+/* log1p(exp(t)) for t <= 0, bit-identical to es_softplus_neg_fast (log1p's |f| < 2^-20 corner included); *ok = 0 outside |t| < 512 */
 ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
 {
     /* ---- exp(t), main path of es_exp (as es_softplus_neg_fast) ---- */

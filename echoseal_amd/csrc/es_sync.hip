@@ -13,14 +13,9 @@
 //
 // Build with -ffp-contract=off.
 #include "es_internal.h"
+#include "es_wave.h"
 
 namespace {
-
-__device__ __forceinline__ void wave_fence_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // ------------------------------------------------------------------------------------------ BPF
 // The recursion is serial in time, so parallelism is ACROSS records: one lane per record, 64
@@ -205,119 +200,15 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void es_bpf_quad_kernel(const void* 
 // Lane 7 has no upper neighbour: its source lane 8 is disabled, so the move leaves lane 7's register at the -0.0 it was given at the
 // start and -0.0 + t == t for every t, signed zeros included (an exact "no neighbour").  Arithmetic and its order are SciPy's
 // direct-form-II-transposed loop (separate multiply and add), as in the other two kernels; bit-exactness is pinned by the same tests.
-#ifndef ES_BPF_ROW_TWO_WAVES
-#define ES_BPF_ROW_TWO_WAVES 1                      /* the recursion's wave does no global memory traffic: a second wave of the block loads and stores */
-#endif
-#ifndef ES_BPF_ROW2_UNROLL
-#define ES_BPF_ROW2_UNROLL 1
-#endif
-#ifndef ES_BPF_ROW_FMAC
-#define ES_BPF_ROW_FMAC 0                          /* 1: a[k+1] y through v_fmac_f64_dpp (same bits, same speed: measured) */
-#endif
+// (Folding the broadcast of y into the multiply, v_fmac_f64_dpp onto -0.0, gave the same bits at the same speed: not kept.)
 constexpr int BR_TT = 32;                           // samples per tile
 constexpr int BR_RECS = 4;                          // records per wave (one per DPP row)
 
-template <bool I16>
-__global__ __launch_bounds__(64) void es_bpf_row_kernel(const void* __restrict__ frames,
-        long long B, int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
-        double* __restrict__ y, float* __restrict__ y32)
-{
-    __shared__ double s_x[BR_RECS][BR_TT];
-    __shared__ double s_y[BR_RECS][BR_TT];
-    const int lane = threadIdx.x;
-    __builtin_amdgcn_s_setprio(3);
-    const long long rec0 = (long long)blockIdx.x * BR_RECS;
-    const int row = lane >> 4, k = lane & 15;
-    const long long rec = rec0 + row;
-    const bool live = rec < B;
-    const int bi = live ? band[rec] : 0;
-    const bool owner = k < 8;                         // holds z[k]
-    const double b0 = tabs->ba[bi][0];
-    const double bk = owner ? tabs->ba[bi][k + 1] : 0.0, ak = owner ? tabs->ba[bi][9 + k + 1] : 0.0;
-    double z = 0.0;
-    // staging: the 16 lanes of a row cover 32 samples of their record, two each
-    float2 pre;
-    auto fetch = [&](int t0) {
-        float v0 = 0.0f, v1 = 0.0f;
-        const int t = t0 + 2 * k;
-        if (live) {
-            if (I16) {
-                const int16_t* f = (const int16_t*)frames + rec * T;
-                if (t < T) v0 = (float)f[t] * (1.0f / 32768.0f);          // PCM16 as soundfile.read hands it to the reference: exact in float32
-                if (t + 1 < T) v1 = (float)f[t + 1] * (1.0f / 32768.0f);
-            } else {
-                const float* f = (const float*)frames + rec * T;
-                if (t < T) v0 = f[t];
-                if (t + 1 < T) v1 = f[t + 1];
-            }
-        }
-        pre = make_float2(v0, v1);
-    };
-    fetch(0);
-    // the neighbour register: written by the row_shl:1 moves in lanes 0..6, never in lane 7 (its source lane is off) -> stays -0.0 there
-    uint32_t nb_lo = 0u, nb_hi = 0x80000000u;
-    for (int t0 = 0; t0 < T; t0 += BR_TT) {
-        s_x[row][2 * k] = (double)pre.x; s_x[row][2 * k + 1] = (double)pre.y;
-        wave_fence_lds();
-        if (t0 + BR_TT < T) fetch(t0 + BR_TT);          // in flight while this tile is filtered
-        if (owner) {
-            // samples past the end of the record are zeros (their outputs are never stored): the tile is always walked in full
-            #pragma unroll 1
-            for (int tb = 0; tb < BR_TT; tb += 8) {
-                double xs[8], ys[8];
-                #pragma unroll
-                for (int u = 0; u < 8; ++u) xs[u] = s_x[row][tb + u];
-                #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const double xn = xs[u];
-                    const double t = xn * bk;                                       // b[k+1] x
-                    const double yn = z + b0 * xn;                                  // lane 0: y = z[0] + b[0] x
-#if ES_BPF_ROW_FMAC
-                    // a[k+1] y with y taken from lane 0 of the row INSIDE the multiply: v_fmac_f64_dpp (the one float64 arithmetic instruction
-                    // that takes a DPP operand) onto -0.0 -- fma(y, a, -0.0) is the correctly rounded product, signed zeros included -- so that
-                    // the broadcast is not a link of its own in the sample-to-sample dependency chain (add -> multiply -> subtract)
-                    double va = -0.0;
-                    asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(va) : "v"(yn), "v"(ak));
-#else
-                    const double yb = __builtin_amdgcn_update_dpp(yn, yn, 0x150, 0xf, 0xf, false);      // row_newbcast:0 (every active lane is written: `old` is never kept)
-                    const double va = yb * ak;
-#endif
-                    uint64_t zu; __builtin_memcpy(&zu, &z, 8);
-                    nb_lo = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_lo, (int)(uint32_t)zu, 0x101, 0xf, 0xf, false);          // row_shl:1: lane k <- lane k+1
-                    nb_hi = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_hi, (int)(uint32_t)(zu >> 32), 0x101, 0xf, 0xf, false);
-                    const uint64_t nu = ((uint64_t)nb_hi << 32) | nb_lo;
-                    double z_nb; __builtin_memcpy(&z_nb, &nu, 8);
-                    z = (z_nb + t) - va;                                            // z[k] = (z[k+1] + b[k+1] x) - a[k+1] y
-                    ys[u] = yn;
-                }
-                if (k == 0) {
-                    #pragma unroll
-                    for (int u = 0; u < 8; ++u) s_y[row][tb + u] = ys[u];
-                }
-            }
-        }
-        wave_fence_lds();
-        if (live) {
-            #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int t = t0 + 2 * k + h;
-                if (t < T) {
-                    const double v = s_y[row][2 * k + h];
-                    y[rec * T + t] = v;
-                    if (y32) y32[rec * T + t] = (float)v;
-                }
-            }
-        }
-        wave_fence_lds();
-    }
-}
-
-// ---------------------------------------------------------------------------------------- BPF (row, two waves)
-// The same recursion with the memory traffic taken OUT of the recursion's wave: in the one-wave form the wait for the prefetched samples
-// is an `s_waitcnt vmcnt(0)` (the stores of the previous tile sit behind conditional branches, so the compiler cannot count them), i.e. once
-// per 32 samples the recursion stands still until the previous tile's stores are acknowledged -- a third of the time on long records.
-// Here a block is two waves: wave 1 loads tile k+1 into LDS and stores tile k-1 from LDS while wave 0 filters tile k (LDS to LDS); one
-// workgroup barrier per tile.  Arithmetic, lane roles and the -0.0 neighbour of lane 7 exactly as in es_bpf_row_kernel.
+// The memory traffic is kept OUT of the recursion's wave: a one-wave form, which also loaded and stored, waited for its prefetched samples
+// with an `s_waitcnt vmcnt(0)` (the stores of the previous tile sit behind conditional branches, so the compiler cannot count them), i.e. once
+// per 32 samples the recursion stood still until the previous tile's stores were acknowledged -- a third of the time on long records.
+// So a block is two waves: wave 1 loads tile k+1 into LDS and stores tile k-1 from LDS while wave 0 filters tile k (LDS to LDS); one
+// workgroup barrier per tile.
 template <bool I16>
 __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict__ frames,
         long long B, int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
@@ -389,15 +280,11 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
     const double b0 = tabs->ba[bi][0];
     const double bk = owner ? tabs->ba[bi][k + 1] : 0.0, ak = owner ? tabs->ba[bi][9 + k + 1] : 0.0;
     double z = 0.0;
-    uint32_t nb_lo = 0u, nb_hi = 0x80000000u;         // -0.0: what lane 7 keeps as its "neighbour" (see es_bpf_row_kernel)
+    uint32_t nb_lo = 0u, nb_hi = 0x80000000u;         // -0.0: what lane 7 keeps as its "neighbour" (written by the row_shl:1 moves in lanes 0..6 only)
     __syncthreads();                                  // tile 0 is staged
     for (int kt = 0; kt < ntiles; ++kt) {
         if (owner) {
-#if ES_BPF_ROW2_UNROLL
             #pragma unroll                                          // all of the tile's LDS reads can be issued ahead of the recursion
-#else
-            #pragma unroll 1
-#endif
             for (int tb = 0; tb < BR_TT; tb += 8) {
                 double xs[8], ys[8];
                 #pragma unroll
@@ -428,7 +315,7 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
 
 // ---------------------------------------------------------------------------------------- xcorr
 // One WAVE per (record, segment of 64 x 19 = 1216 lags).  The 1216 + 62 samples the segment needs
-// are staged in LDS with coalesced 8-byte loads; lane l then owns the chunk of XC_R = 19
+// are staged in LDS with coalesced 8-byte loads; lane l then owns the chunk of XC_R = 19 (es_internal.h)
 // consecutive lags starting at 19 l and walks the 81 samples they share ONCE (register sliding
 // window, fully unrolled): per template tap one ds_read_b64 feeds 19 FMAs whose tap operand is a
 // scalar register.  19 is odd, so lane l reads 8-byte word 19 l + m and (19 l) mod 32 is a
@@ -436,10 +323,7 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
 // partial sums shared by the chunk (core / head / tail, see oracle/c/eso_dsp.c) instead of 63 adds
 // per lag.  Results go back through the same LDS buffer so that HBM sees whole rows.
 // FP64 VALU work per lag: 63 FMA + ~7 for the energy + sqrt/div; no MFMA (no shared operand).
-constexpr int XC_R = 19;
-constexpr int XC_SEG = 64 * XC_R;                  // lags per wave
 constexpr int XC_NS = XC_SEG + ES_PRE_L - 1;       // samples per wave: 1278
-constexpr int XC_WAVES = 4;
 
 __global__ __launch_bounds__(64 * XC_WAVES) void es_xcorr_kernel(const double* __restrict__ y, long long B,
         int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
@@ -528,17 +412,6 @@ __global__ __launch_bounds__(64 * XC_WAVES) void es_xcorr_kernel(const double* _
 // come out sorted and a flood of equal values cannot serialise on one thread.
 constexpr int PK_THREADS = 256;
 constexpr int PK_LDS_N = 4096;
-
-__device__ __forceinline__ uint64_t f64_key(double x)
-{
-    uint64_t b; __builtin_memcpy(&b, &x, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ double key_f64(uint64_t k)
-{
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-    double x; __builtin_memcpy(&x, &b, 8); return x;
-}
 
 // k-th smallest (0-based) of v[i] (ABSDEV: |v[i] - center|).  All threads return the value.
 // (NT threads per block: 256, or 1024 for rows that do not fit LDS -- a 5 s recording is 240 000 lags per band)
@@ -770,17 +643,10 @@ int es_launch_bpf(es_ctx* ctx, const void* frames, int dtype, int64_t B, int T, 
     // the four-lanes-per-record kernel anyway: up to four such waves per SIMD
     if (B <= (long long)ctx->num_cu * 4 * 4 * BR_RECS / 4) {
         const unsigned blocks = (unsigned)((B + BR_RECS - 1) / BR_RECS);
-#if ES_BPF_ROW_TWO_WAVES
         if (dtype == ES_DTYPE_I16)
             hipLaunchKernelGGL(es_bpf_row2_kernel<true>, dim3(blocks), dim3(128), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
         else
             hipLaunchKernelGGL(es_bpf_row2_kernel<false>, dim3(blocks), dim3(128), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
-#else
-        if (dtype == ES_DTYPE_I16)
-            hipLaunchKernelGGL(es_bpf_row_kernel<true>, dim3(blocks), dim3(64), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
-        else
-            hipLaunchKernelGGL(es_bpf_row_kernel<false>, dim3(blocks), dim3(64), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
-#endif
         ES_HIP_CHECK(ctx, hipGetLastError());
         return ES_OK;
     }

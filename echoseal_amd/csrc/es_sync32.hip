@@ -25,6 +25,7 @@
 // sum|y||tpl| <= e_y by Cauchy-Schwarz, |tpl| = 1), energy and sqrt (~2e-6 relative), approximate
 // rcp/sqrt (1e-6): |corr32 - corr64| < 8e-6 for |corr| <= 1.  DELTA = 3e-5.
 #include "es_internal.h"
+#include "es_wave.h"
 
 namespace {
 
@@ -48,18 +49,7 @@ __device__ __forceinline__ void lds_add(lds_u32* p, uint32_t v)
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-__device__ __forceinline__ void wave_fence_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-constexpr int XC_R = 19;                            // must equal es_sync.hip / oracle XC_CHUNK
-constexpr int XC_SEG = 64 * XC_R;
-constexpr int XC_WAVES = 4;
-#ifndef XC_GRID_PER_CU
-#define XC_GRID_PER_CU 16                            // blocks per CU the grid is capped at (grid-stride beyond)
-#endif
+constexpr int XC_BLOCKS_PER_CU = 16;                // blocks per CU the grid is capped at (grid-stride beyond)
 constexpr int XC_MIN_WAVES = 4;                     // waves per SIMD the register allocation must allow
 constexpr int XC_T_WINDOW = 2048;                   // BASELINE config 3: 2 048-sample windows (1 986 lags)
 constexpr int XC_R_WINDOW = 17;                     // two waves per window: 2 x 64 x 17 = 2 176 >= 1 986 lags (19 would compute 2 432)
@@ -345,17 +335,6 @@ __device__ __forceinline__ void corr64_list(lds_double* stage, int cnt, glb_cdou
 // ------------------------------------------------------------------------------------ pick (exact)
 constexpr int PX_MAXN = 4096;
 
-__device__ __forceinline__ uint32_t f32_key(float x)
-{
-    uint32_t b; __builtin_memcpy(&b, &x, 4);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k)
-{
-    const uint32_t b = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float x; __builtin_memcpy(&x, &b, 4); return x;
-}
-
 // One WAVE per record (a block-per-record version spent its time in ~100 block barriers per record): the float32
 // row sits in LDS, order statistics are 8-bit-digit radix selects on per-wave LDS histograms (ds_add, wave scan, no
 // barrier), band / candidate lists are built with ballots, and all the float64 re-evaluations of a step run in
@@ -375,11 +354,6 @@ struct PwFixed {
     int      list[PW_CAP];
     double   val[PW_CAP];
 };
-
-__device__ __forceinline__ int lanes_below(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // k-th smallest 32-bit key of key(i), i in [0,n), by one wave: 4 passes of 8 bits
 template <typename F>
@@ -509,17 +483,6 @@ __host__ __device__ __forceinline__ size_t xf_lds_per_wave(int ns2, int n_lags)
 // looks at.  Same rules and tie-breaks as es_pick_kernel: exact order statistics by 8-bit radix select on the monotone
 // 64-bit image of the doubles, NMS window +-607, fallback = five largest, equal values -> higher index first.  Slow
 // (16+ passes of ~200 float64 operations per lag) and meant to be: such records are degenerate.
-__device__ __forceinline__ uint64_t f64_key(double x)
-{
-    uint64_t b; __builtin_memcpy(&b, &x, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ double key_f64(uint64_t k)
-{
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-    double x; __builtin_memcpy(&x, &b, 8); return x;
-}
-
 template <typename F>
 __device__ double pw_select64(lds_PwFixed& S, int n, int k, int lane, F val)
 {
@@ -878,7 +841,7 @@ __global__ __launch_bounds__(64 * PW_WAVES, XF_MIN_WAVES) void es_pick_exact_wav
 int es_launch_xcorr32(es_ctx* ctx, const float* y32, int64_t B, int T, const uint8_t* band, float* corr32, hipStream_t st)
 {
     const int n_lags = T - (ES_PRE_L - 1);
-    const long long cap = (long long)ctx->num_cu * XC_GRID_PER_CU;
+    const long long cap = (long long)ctx->num_cu * XC_BLOCKS_PER_CU;
     // fewer single-segment items than two waves per SIMD: split records four ways
     const bool small = B * ((n_lags + XC_SEG - 1) / XC_SEG) < (long long)ctx->num_cu * 8;
     const bool win2k = !small && T == XC_T_WINDOW;              // config-3 windows: two waves per window, 17 lags per lane, compile-time bounds

@@ -36,7 +36,7 @@ def _report(mism, what):
 
 def _slab_slots(dev) -> int:
     """Slots of the lane-per-path list decoder's scratch slab for one-wave (64-lane) blocks, list_size_max <= 64:
-    num_cu x ES_WIDE_WPS (3, waves per SIMD the kernel is built for) x 4 (es_scl_wide_scratch_bytes sizes the slab in
+    num_cu x WIDE_WPS (3, waves per SIMD the kernel is built for) x 4 (es_scl_wide_scratch_bytes sizes the slab in
     256-lane blocks; launch_wide cuts each into four 64-lane slots)."""
     return torch.cuda.get_device_properties(dev).multi_processor_count * 3 * 4
 

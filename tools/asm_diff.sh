@@ -1,0 +1,42 @@
+#!/bin/bash
+# tools/asm_diff.sh OLD_TREE NEW_TREE [FILE.hip ...]  -> per source file: "identical", or the symbols whose device assembly differs
+# Compiles every file of the Makefile's SRCS (or the files named) in both trees to gfx950 assembly with the Makefile's flags, per-file flags
+# included, and compares whole lines.  Only the __hip_cuid_<hash> symbol (a hash of the source text) is masked.  For a refactor that must
+# not change a kernel: git worktree add /tmp/parent HEAD^ && tools/asm_diff.sh /tmp/parent .
+# OUT=dir keeps the .s files there (default: a fresh temporary directory); JOBS=n compiles n files at a time (default 8).
+set -e
+old=$(realpath "$1"); new=$(realpath "$2"); shift 2
+out=${OUT:-$(mktemp -d)}; mkdir -p "$out/old" "$out/new"
+mk=$new/echoseal_amd/csrc/Makefile
+srcs=${*:-$(sed -n 's/^SRCS *:= *//p' "$mk")}
+flags=$(sed -n 's/^HIPFLAGS *?= *//p' "$mk" | sed 's/\$(ARCH)/gfx950/')
+
+for side in old new; do
+  for f in $srcs; do
+    tree=$old; [ $side = new ] && tree=$new
+    [ -f "$tree/echoseal_amd/csrc/$f" ] || continue
+    per_file=$(sed -n "s/^FLAGS_${f%.hip} := //p" "$tree/echoseal_amd/csrc/Makefile")
+    echo "cd $tree/echoseal_amd/csrc && /opt/rocm/bin/hipcc $flags $per_file -Wno-unused-command-line-argument --cuda-device-only -S $f -o $out/$side/${f%.hip}.s"
+  done
+done | xargs -P "${JOBS:-8}" -d '\n' -n 1 sh -c
+
+status=0
+for f in $srcs; do
+  for side in old new; do
+    sed 's/__hip_cuid_[0-9a-f]*/__hip_cuid_X/g' "$out/$side/${f%.hip}.s" > "$out/$side/${f%.hip}.masked"
+  done
+  if cmp -s "$out/old/${f%.hip}.masked" "$out/new/${f%.hip}.masked"; then
+    echo "$f: identical ($(wc -l < "$out/new/${f%.hip}.s") lines)"
+  else
+    status=1
+    echo "$f: DIFFERS in"
+    # every differing line is counted under the function label, kernel descriptor or metadata block it belongs to
+    for side in old new; do
+      awk '!meta && /^[_A-Za-z][_A-Za-z0-9.$]*:/ { sym = $1 } /^[ \t]*\.amdhsa_kernel / { sym = $2 " (kernel descriptor)" } /^[ \t]*\.amdgpu_metadata/ { meta = 1; sym = "(metadata)" }
+           { print sym "\t" $0 }' "$out/$side/${f%.hip}.masked" > "$out/$side/${f%.hip}.bysym"
+    done
+    diff "$out/old/${f%.hip}.bysym" "$out/new/${f%.hip}.bysym" | sed -n 's/^[<>] \([^\t]*\)\t.*/\1/p' | sort | uniq -c | sed 's/^/   /'
+  fi
+done
+echo "assembly kept in $out"
+exit $status
