@@ -65,6 +65,7 @@ SIGNATURES = {
     "es_polar_encode_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "es_schedule_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_void_p, ctypes.c_uint32, c_int64, c_void_p, c_void_p, c_void_p]),
     "es_tx_frames_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_char_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "es_mix_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "es_resample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "es_set_option": (c_int, [c_void_p, c_char_p, c_int]),
     "es_softplus_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

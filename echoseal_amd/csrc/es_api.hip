@@ -526,6 +526,22 @@ int es_tx_frames_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_r
                                (hipStream_t)stream);
 }
 
+int es_mix_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n, int block, const float* chips_dev, int64_t chips_stride,
+                 const int64_t* chip_off_dev, double alpha, double floor, float* out_dev, double* scale_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;                        /* no tables involved: any context serves it, a front-end one included */
+    if (block < 1) return fail(ctx, ES_EINVAL, "es_mix_batch: block must be >= 1");
+    if (R < 0 || n < 0 || chips_stride < 0) return fail(ctx, ES_EINVAL, "es_mix_batch: negative size");
+    if (R == 0 || n == 0) return ES_OK;
+    if (!x_dev || !chips_dev || !out_dev) return fail(ctx, ES_EINVAL, "es_mix_batch: null pointer");
+    if (out_dev != x_dev && out_dev < x_dev + R * n && x_dev < out_dev + R * n)
+        return fail(ctx, ES_EINVAL, "es_mix_batch: out_dev partly overlaps x_dev (only out_dev == x_dev may alias)");
+    if (chips_stride < 1 || (!chip_off_dev && chips_stride < n))
+        return fail(ctx, ES_EINVAL, "es_mix_batch: a chip row is shorter than the recording (chips_stride < n at offset 0)");
+    DeviceGuard g(ctx->device);
+    return es_launch_mix(ctx, x_dev, R, n, block, chips_dev, chips_stride, chip_off_dev, alpha, floor, out_dev, scale_dev, (hipStream_t)stream);
+}
+
 int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int64_t n_in, const void* h_tf_dev, int h_per_phase,
                       int up, int down, int64_t y0, int64_t n_out, void* out_dev, void* stream)
 {

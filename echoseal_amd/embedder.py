@@ -40,6 +40,8 @@ class WatermarkEmbedder:
     def __init__(self, key32: bytes, params: TxParams | None = None) -> None:
         self.p = params or TxParams()
         self.sec = SecureChannel(key32)
+        self._key32 = key32
+        self._engine = None
         self._band_key = getattr(self.sec, "band_key", key32)
         self.frame_ctr = 0
         self._chip_buf: np.ndarray | None = None
@@ -64,6 +66,35 @@ class WatermarkEmbedder:
         peak = float(np.max(np.abs(chips))) + EPS
         scale = min(scale, headroom / peak) if peak > 0.0 else 0.0
         return x + chips * scale
+
+    def embed(self, samples: np.ndarray, *, block: int = 1024, engine=None) -> np.ndarray:
+        """The stream `process` returns for successive `block`-sized slices of `samples`, computed on the GPU in one batch
+        (RxEngine.embed); frame_ctr and the pending chips advance as they would.  Payloads come from `_build_payload`, one per
+        new frame, as in `process`.  engine: an RxEngine to run on (default: a front-end engine on device 0, made once)."""
+        import torch
+        from .engine import EmbedResult, RxEngine
+        if engine is None:
+            if self._engine is None:
+                self._engine = RxEngine(0, list_size_max=0)
+            engine = self._engine
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        FL = self.p.preamble.size + HDR_L + self.p.N
+        buf = np.empty(0, np.float32) if self._chip_buf is None else self._chip_buf
+        tail = np.zeros((1, FL), np.float32)
+        tail[0, FL - buf.size:] = buf
+        carry = EmbedResult(None, None, np.array([(FL - buf.size) % FL]), torch.from_numpy(tail))
+        ctr0 = self.frame_ctr
+        payloads = []
+        for _ in range(max(0, -(-(x.size - buf.size) // FL))):
+            payloads.append(np.frombuffer(self._build_payload(), np.uint8))
+            self.frame_ctr = (self.frame_ctr + 1) % (2 ** 32)
+        pl = np.stack(payloads)[None] if payloads else np.zeros((1, 0, 55), np.uint8)
+        res = engine.embed(self._key32, x, ctr0=ctr0, block=block, payloads=torch.from_numpy(pl), carry=carry,
+                           target_rel_db=self.p.target_rel_db, floor_rel_dbfs=self.p.floor_rel_dbfs)
+        assert int(res.ctr[0]) == self.frame_ctr
+        off = int(res.off[0])
+        self._chip_buf = res.tail[0, off:].cpu().numpy() if off else np.empty(0, np.float32)
+        return res.audio.cpu().numpy()
 
     # ------------------------------------------------------------------ internals
     def _frame_symbols(self, ctr: int, payload: bytes) -> np.ndarray:

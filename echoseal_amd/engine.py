@@ -96,6 +96,15 @@ class SyncResult:
     y32: torch.Tensor | None = None
 
 
+@dataclass
+class EmbedResult:
+    audio: torch.Tensor        # [R,n] float32 watermarked recordings ([n] for 1-D input)
+    ctr: np.ndarray            # [R] int64: counter of the next frame to generate (WatermarkEmbedder.frame_ctr after the same process() calls)
+    off: np.ndarray            # [R] int64: chips of the current frame already used (0 = nothing pending)
+    tail: torch.Tensor         # [R,1215] float32: the current frame; its chips from `off` on are what process() keeps in its buffer
+    scale: torch.Tensor | None = None   # [R, ceil(n / block)] float64 gain of every block (want_scale)
+
+
 class RxEngine:
     def __init__(self, device: int | torch.device = 0, *, list_size_max: int = 32, fs: int = 48_000, code_k: int = 448):
         """code_k: information positions of the polar code (data bits + CRC-8).  448 is the reference's own code (rtwm/polar_fast.py:8-9);
@@ -486,6 +495,12 @@ class RxEngine:
         from .crypto import SecureChannel
         sec = SecureChannel(key32)
         ctr = torch.arange(ctr0, ctr0 + n, dtype=torch.int64, device=self.device)
+        payloads = self._synthetic_payloads(sec, ctr, seed)
+        return self.make_frames(sec, key32, ctr, payloads), payloads
+
+    def _synthetic_payloads(self, sec, ctr: torch.Tensor, seed: int) -> torch.Tensor:
+        """Sealed payloads uint8 [len(ctr),55] of `synthetic_frames` for the int64 device counters `ctr`."""
+        n = ctr.numel()
         # 31 random bytes per frame from a counter-based hash of (seed, ctr, byte index), so that a frame does not
         # depend on how the counter range is cut into batches or shards (32-bit multiply-xorshift rounds in int64)
         h = (ctr[:, None] * 31 + torch.arange(31, dtype=torch.int64, device=self.device)[None, :] + (int(seed) & 0xFFFFFF) * 1_000_003) & 0xFFFFFFFF
@@ -498,8 +513,105 @@ class RxEngine:
         for k in range(4):
             plain[:, 4 + k] = ((ctr >> (8 * (3 - k))) & 0xFF).to(torch.uint8)
         plain[:, 8:27] = rnd[:, :19]
-        payloads = self.aead_seal(sec._aead._key, rnd[:, 19:31].contiguous(), plain)
-        return self.make_frames(sec, key32, ctr, payloads), payloads
+        return self.aead_seal(sec._aead._key, rnd[:, 19:31].contiguous(), plain)
+
+    # ------------------------------------------------------------------ level mix: frames -> watermarked recordings
+    def mix(self, x: torch.Tensor, chips: torch.Tensor, *, block: int = 1024, chip_off=None, target_rel_db: float = -10.0,
+            floor_rel_dbfs: float = -35.0, want_scale: bool = False, out: torch.Tensor | None = None):
+        """WatermarkEmbedder.process (rtwm/embedder.py:44-75) for every `block`-sized slice of every recording, bit for bit
+        (es_mix_batch): x float32 [R, n]; chips float32 [R, stride], row r the chip stream of recording r (frames of consecutive
+        counters back to back); sample t takes chips[r, chip_off[r] + t] (chip_off: int64 [R], None = 0).  out=x mixes in place.
+        -> marked audio [R, n]; want_scale: (audio, scale float64 [R, ceil(n / block)])."""
+        from .utils import db_to_lin
+        if x.dim() != 2 or chips.dim() != 2 or x.dtype != torch.float32 or chips.dtype != torch.float32 or chips.shape[0] != x.shape[0]:
+            raise ValueError("x must be float32 [R, n] and chips float32 [R, stride]")
+        x = x.contiguous(); chips = chips.contiguous()
+        R, n = x.shape
+        if chip_off is not None:
+            chip_off = self._dev(chip_off, torch.int64).reshape(-1)
+            if chip_off.numel() != R:
+                raise ValueError("chip_off: one offset per recording")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of x's shape")
+        block = int(block)
+        scale = torch.empty((R, (n + block - 1) // block if block >= 1 else 0), dtype=torch.float64, device=self.device) if want_scale else None
+        nat.check(self._ctx, self._lib.es_mix_batch(self._ctx, _ptr(x), R, n, block, _ptr(chips), chips.shape[1], _ptr(chip_off),
+                                                    db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), _ptr(out), _ptr(scale),
+                                                    self._stream()), "es_mix_batch")
+        return (out, scale) if want_scale else out
+
+    def embed(self, key32: bytes, audio, *, ctr0=0, block: int = 1024, payloads=None, carry=None, seed: int | None = None,
+              session_nonce: bytes | None = None, target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False):
+        """Whole watermarked recordings: the reference's transmit chain (seal -> polar encode -> header -> PN spread -> band-pass ->
+        level mix, rtwm/embedder.py) for a batch, one frame-generator call and one mix launch.  audio float32 [R, n] (or [n]);
+        recording r is what a WatermarkEmbedder with frame_ctr = ctr0[r] returns from process() over successive `block`-sized slices.
+        payloads: sealed uint8 [R, nf, 55] for the new frames of counters ctr0[r] + k (mod 2^32); None: plaintext b"ESAL" | ctr | nonce8 |
+        pad11 sealed under a 12-byte nonce, with random bytes from `secrets` as the reference (session_nonce: the 8 bytes a session keeps),
+        or, with seed=, the deterministic bytes of `synthetic_frames`.  carry: the EmbedResult of the call this one continues (its pending
+        chips are used first, as process() keeps them in its buffer).  -> EmbedResult."""
+        from .crypto import SecureChannel
+        import secrets as _secrets
+        FL = nat.ES_FRAME_LEN
+        x = audio if torch.is_tensor(audio) else torch.as_tensor(np.asarray(audio))
+        one_d = x.dim() == 1
+        if one_d:
+            x = x.reshape(1, -1)
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("audio must be float32 [R, n] or [n]")
+        x = self._dev(x, torch.float32)
+        R, n = x.shape
+        sec = SecureChannel(key32)
+        c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1), (R,))) if np.ndim(ctr0) else np.full(R, int(ctr0), np.int64)
+        if carry is not None:
+            if carry.tail.shape != (R, FL):
+                raise ValueError("carry: the EmbedResult of a call over the same recordings")
+            off_in = np.asarray(carry.off, dtype=np.int64).reshape(R)
+            start = np.where(off_in > 0, off_in, FL)           # position of the first chip in a row = [pending frame | new frames]
+            lead = 1
+        else:
+            start = np.zeros(R, np.int64)
+            lead = 0
+        end = start + n                                         # chips of the row consumed after this call
+        new = (end + FL - 1) // FL - lead                       # new frames each recording generates (process() makes exactly these)
+        nf = int(max(0, new.max())) if R else 0
+        if payloads is not None:
+            payloads = self._dev(payloads, torch.uint8)
+            if payloads.dim() != 3 or payloads.shape[0] != R or payloads.shape[2] != 55 or payloads.shape[1] < nf:
+                raise ValueError(f"payloads must be uint8 [R, nf >= {nf}, 55]")
+            nf = payloads.shape[1] if nf else 0
+            payloads = payloads[:, :nf]
+        ctr = (torch.from_numpy(c0).to(self.device)[:, None] + torch.arange(nf, dtype=torch.int64, device=self.device)[None, :]) & 0xFFFFFFFF
+        if nf and R:
+            if payloads is None and seed is not None:
+                payloads = self._synthetic_payloads(sec, ctr.reshape(-1), seed)
+            elif payloads is None:
+                sn = _secrets.token_bytes(8) if session_nonce is None else bytes(session_nonce)
+                if len(sn) != 8:
+                    raise ValueError("session_nonce must be 8 bytes")
+                plain = np.empty((R * nf, 27), np.uint8)
+                plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
+                plain[:, 4:8] = ctr.reshape(-1).cpu().numpy().astype(">u4").view(np.uint8).reshape(-1, 4)
+                plain[:, 8:16] = np.frombuffer(sn, np.uint8)
+                plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * R * nf), np.uint8).reshape(-1, 11)
+                nonces = np.frombuffer(_secrets.token_bytes(12 * R * nf), np.uint8).reshape(-1, 12)
+                payloads = self.aead_seal(sec._aead._key, torch.from_numpy(nonces.copy()), torch.from_numpy(plain))
+            frames = self.make_frames(sec, getattr(sec, "band_key", key32), ctr.reshape(-1), payloads.reshape(R * nf, 55)).reshape(R, nf * FL)
+        else:
+            frames = torch.empty((R, 0), dtype=torch.float32, device=self.device)
+        chips = torch.cat((carry.tail.to(self.device), frames), dim=1) if lead else frames
+        res = self.mix(x, chips, block=block, chip_off=torch.from_numpy(start) if lead else None, target_rel_db=target_rel_db,
+                       floor_rel_dbfs=floor_rel_dbfs, want_scale=want_scale) if n else (x.clone(), None)
+        out, scale = res if (want_scale or not n) else (res, None)
+        off = end % FL
+        slot = np.where(off > 0, end // FL, np.maximum(end // FL - 1, 0))      # the frame the stream stands in (pending chips from `off` on)
+        if chips.shape[1]:
+            idx = torch.from_numpy(slot).to(self.device)[:, None] * FL + torch.arange(FL, dtype=torch.int64, device=self.device)[None, :]
+            tail = torch.gather(chips, 1, idx)
+        else:
+            tail = torch.zeros((R, FL), dtype=torch.float32, device=self.device)
+        return EmbedResult(out[0] if one_d else out, (c0 + new) % (2 ** 32), off, tail, scale)
 
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)
     def _ctr_dev(self, ctrs) -> torch.Tensor:

@@ -258,6 +258,23 @@ int es_tx_frames_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_r
                        const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* hdr_pn16_host, int64_t B,
                        double* y_ws_dev, float* frames_dev, void* stream);
 
+/* Level mix, the last step of the transmit chain: replaces WatermarkEmbedder.process (rtwm/embedder.py:44-75) for a batch of
+ * recordings.  x_dev float32 [R][n]; recording r is cut into blocks of `block` samples (the last one may be short) and each block is
+ * what one process() call sees: in_rms = sqrt(mean(x * x)) + 1e-12 in float32 with NumPy's summation order (chunks of 8192 elements,
+ * each summed pairwise: echoseal_amd/csrc/es_mix.hip), scale = max(alpha * in_rms, floor), limited to (0.98 - max|x|) / (max|chips| + 1e-12)
+ * and to >= 0 (float64, Python's max / min, a NaN wins np.max), out = x + chips * (float)scale in float32.  alpha = db_to_lin(target_rel_db)
+ * and floor = db_to_lin(floor_rel_dbfs) come from the host.  chips_dev float32 [R][chips_stride]: row r is the chip stream of recording r,
+ * the frames of consecutive counters back to back (what es_tx_frames_batch writes for consecutive counters); sample t of recording r takes
+ * chips[r][chip_off[r] + t] (chip_off_dev int64 [R], NULL = 0).  chips_stride is the row stride and the row's length: an offset that
+ * leaves the row cannot be seen from the host, such reads are clamped to the row's first / last chip.  out_dev float32 [R][n]; out_dev == x_dev
+ * (in place) is allowed, any other overlap is ES_EINVAL.  scale_dev nullable float64 [R][ceil(n / block)]: the gain of every block.
+ * Bit-identical to the host code for every block length >= 1; blocks of 1024 samples (the reference's own, rtwm/audioio.py:18) in rows of
+ * n % 4 == 0 samples at 16-byte aligned pointers run one wavefront per block.  Needs no tables (works before es_set_tables and on a
+ * front-end context), only enqueues (capturable); R == 0 or n == 0 launches nothing.  NaN payloads other than those of the inputs are
+ * those of SSE arithmetic (an invalid operation gives the negative quiet NaN).                                                       */
+int es_mix_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n, int block, const float* chips_dev, int64_t chips_stride,
+                 const int64_t* chip_off_dev, double alpha, double floor, float* out_dev, double* scale_dev, void* stream);
+
 /* Input conditioning: the polyphase FIR inside resample_to (rtwm/utils.py:58-66 =
  * scipy.signal.resample_poly(audio, up, down) -> upfirdn, zero extension).  The caller designs the filter exactly as
  * SciPy does (firwin, Kaiser 5.0, scaled by `up`, padded) and passes it in SciPy's transposed / flipped polyphase layout
