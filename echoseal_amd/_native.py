@@ -25,6 +25,9 @@ ES_MAX_TAPS_FAST = 160
 ES_MAX_PEAKS = 32
 ES_MAX_LIST = 1024
 ES_PN_BYTES = 152
+ES_KEYRING_BYTES = 304
+ES_MAX_TRIES = 400
+ES_PEAK_LIMIT = 25
 ES_INFO_BYTES = 55
 ES_DTYPE_F32, ES_DTYPE_I16, ES_DTYPE_F64 = 0, 1, 2
 
@@ -74,6 +77,14 @@ SIGNATURES = {
     "es_aead_seal_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "es_select_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "es_keyring_derive_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "es_schedule_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "es_aead_check_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "es_select_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "es_plan_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                              c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -185,20 +185,19 @@ __global__ __launch_bounds__(256) void es_aead_check_kernel(AeadKey key, const u
         ok[i] = validate_blob(key, blobs + i * ES_INFO_BYTES, ctr[i / group], plain ? plain + i * 27 : nullptr) ? 1 : 0;
 }
 
-// PolarCode.decode's selection (rtwm/fastpolar.py:268-276, 332-359) for one frame per lane.
-__global__ __launch_bounds__(256) void es_select_kernel(AeadKey key, int use_key, const uint32_t* __restrict__ ctr, long long B, int L,
+// PolarCode.decode's selection (rtwm/fastpolar.py:268-276, 332-359) for frame f.  use_key == 2: a validator that accepts nothing
+// (the keyed kernel's record without a key).
+__device__ __forceinline__ void select_frame(const AeadKey& key, int use_key, uint32_t c, long long f, int L,
         const uint8_t* __restrict__ hard_info, const uint8_t* __restrict__ hard_ok, const uint8_t* __restrict__ cand_info,
         const double* __restrict__ cand_metric, const uint8_t* __restrict__ cand_ok, const int32_t* __restrict__ ncand,
         uint8_t* __restrict__ payload, int8_t* __restrict__ ok_out, int32_t* __restrict__ which_out)
 {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < B; f += stride) {
-        const uint32_t c = use_key ? ctr[f] : 0u;
+    {
         const uint8_t* src = hard_info + f * ES_INFO_BYTES;
         int which = -1, ok = 0;
         const int n = ncand[f];
         if (n < 0) ok = -2;                                        // the list decoder could not decode this record (es_scl_batch): nothing of its rows is defined
-        else if (hard_ok[f] && (!use_key || validate_blob(key, src, c, nullptr))) ok = 1;
+        else if (hard_ok[f] && (!use_key || (use_key == 1 && validate_blob(key, src, c, nullptr)))) ok = 1;
         else {
             if (n == 0) ok = -1;                                   // list loop was skipped: usage error, reported to the host
             else {
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(256) void es_select_kernel(AeadKey key, int use_key
                 const uint8_t* co = cand_ok + f * (long long)L;
                 for (int r = 0; r < n && !ok; ++r) {
                     if (co[r]) {
-                        if (!use_key || validate_blob(key, ci + (long long)r * ES_INFO_BYTES, c, nullptr)) { which = r; ok = 1; }
+                        if (!use_key || (use_key == 1 && validate_blob(key, ci + (long long)r * ES_INFO_BYTES, c, nullptr))) { which = r; ok = 1; }
                         else if (best_crc < 0 || cm[r] < cm[best_crc]) best_crc = r;
                     } else if (cm[r] < best_any_m) { best_any = r; best_any_m = cm[r]; }
                 }
@@ -220,6 +219,61 @@ __global__ __launch_bounds__(256) void es_select_kernel(AeadKey key, int use_key
         for (int k = 0; k < ES_INFO_BYTES; ++k) payload[f * ES_INFO_BYTES + k] = (ok == -2) ? (uint8_t)0 : src[k];
         ok_out[f] = (int8_t)ok;
         which_out[f] = which;
+    }
+}
+
+__global__ __launch_bounds__(256) void es_select_kernel(AeadKey key, int use_key, const uint32_t* __restrict__ ctr, long long B, int L,
+        const uint8_t* __restrict__ hard_info, const uint8_t* __restrict__ hard_ok, const uint8_t* __restrict__ cand_info,
+        const double* __restrict__ cand_metric, const uint8_t* __restrict__ cand_ok, const int32_t* __restrict__ ncand,
+        uint8_t* __restrict__ payload, int8_t* __restrict__ ok_out, int32_t* __restrict__ which_out)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < B; f += stride)
+        select_frame(key, use_key, use_key ? ctr[f] : 0u, f, L, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok_out, which_out);
+}
+
+// ---- keyed forms: the AEAD key of record r is the first 32 bytes of ring row key[r] (es_keyring.hip); a key index outside [0, N)
+// is a validator that accepts nothing, and reads nothing of the ring
+typedef __attribute__((address_space(1))) const uint32_t g_cu32;
+typedef __attribute__((address_space(1))) const int32_t g_ci32;
+
+__device__ __forceinline__ bool ring_aead_key(const uint8_t* ring, long long N, const int32_t* key_dev, long long r, AeadKey& k)
+{
+    const long long key = ((g_ci32*)key_dev)[r];
+    const bool have = key >= 0 && key < N;
+    g_cu32* row = (g_cu32*)(ring + (have ? key : 0) * ES_KEYRING_BYTES);
+    #pragma unroll
+    for (int i = 0; i < 8; ++i) k.w[i] = have ? row[i] : 0u;
+    return have;
+}
+
+__global__ __launch_bounds__(256) void es_aead_check_keyed_kernel(const uint8_t* __restrict__ ring, long long N,
+        const int32_t* __restrict__ key_dev, const uint8_t* __restrict__ blobs, long long n, int group,
+        const uint32_t* __restrict__ ctr, uint8_t* __restrict__ ok, uint8_t* __restrict__ plain)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        AeadKey k;
+        if (ring_aead_key(ring, N, key_dev, i / group, k))
+            ok[i] = validate_blob(k, blobs + i * ES_INFO_BYTES, ctr[i / group], plain ? plain + i * 27 : nullptr) ? 1 : 0;
+        else {
+            ok[i] = 0;
+            if (plain) for (int b = 0; b < 27; ++b) plain[i * 27 + b] = 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void es_select_keyed_kernel(const uint8_t* __restrict__ ring, long long N,
+        const int32_t* __restrict__ key_dev, const uint32_t* __restrict__ ctr, long long B, int L,
+        const uint8_t* __restrict__ hard_info, const uint8_t* __restrict__ hard_ok, const uint8_t* __restrict__ cand_info,
+        const double* __restrict__ cand_metric, const uint8_t* __restrict__ cand_ok, const int32_t* __restrict__ ncand,
+        uint8_t* __restrict__ payload, int8_t* __restrict__ ok_out, int32_t* __restrict__ which_out)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < B; f += stride) {
+        AeadKey k;
+        const int use_key = ring_aead_key(ring, N, key_dev, f, k) ? 1 : 2;
+        select_frame(k, use_key, ctr[f], f, L, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok_out, which_out);
     }
 }
 
@@ -266,6 +320,31 @@ int es_launch_select(es_ctx* ctx, const uint8_t* key32, const uint32_t* ctr, int
     AeadKey k{};
     if (key32) k = load_key(key32);
     hipLaunchKernelGGL(es_select_kernel, dim3((unsigned)blocks), dim3(256), 0, st, k, key32 ? 1 : 0, ctr, (long long)B, L,
+                       hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+int es_launch_aead_check_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* blobs, int64_t n, int group,
+                               const uint32_t* ctr, uint8_t* ok, uint8_t* plain, hipStream_t st)
+{
+    long long blocks = (n + 255) / 256;
+    const long long cap = (long long)ctx->num_cu * 8;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(es_aead_check_keyed_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ring, (long long)N, key, blobs, (long long)n,
+                       group, ctr, ok, plain);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t B, int L,
+                           const uint8_t* hard_info, const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric,
+                           const uint8_t* cand_ok, const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st)
+{
+    long long blocks = (B + 255) / 256;
+    const long long cap = (long long)ctx->num_cu * 8;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(es_select_keyed_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ring, (long long)N, key, ctr, (long long)B, L,
                        hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
     ES_HIP_CHECK(ctx, hipGetLastError());
     return ES_OK;

@@ -657,4 +657,72 @@ int es_select_batch(es_ctx* ctx, const uint8_t* key32_host, const uint32_t* ctr_
                             cand_ok_dev, ncand_dev, payload_dev, ok_dev, which_dev, (hipStream_t)stream);
 }
 
+int es_keyring_derive_batch(es_ctx* ctx, const uint8_t* master32_dev, int64_t N, uint8_t* ring_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (N < 0) return fail(ctx, ES_EINVAL, "es_keyring_derive_batch: negative count");
+    if (N == 0) return ES_OK;
+    if (!master32_dev || !ring_dev) return fail(ctx, ES_EINVAL, "es_keyring_derive_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_keyring_derive(ctx, master32_dev, N, ring_dev, (hipStream_t)stream);
+}
+
+int es_schedule_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint32_t* ctr_dev, int64_t n,
+                            uint8_t* pn_rows_dev, uint8_t* band_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (n < 0 || N < 0) return fail(ctx, ES_EINVAL, "es_schedule_keyed_batch: negative count");
+    if (n == 0 || (!pn_rows_dev && !band_dev)) return ES_OK;
+    if (N == 0) return fail(ctx, ES_EINVAL, "es_schedule_keyed_batch: records but an empty key ring (every key index is outside [0, N))");
+    if (!ring_dev || !key_dev || !ctr_dev) return fail(ctx, ES_EINVAL, "es_schedule_keyed_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_schedule_keyed(ctx, ring_dev, N, key_dev, ctr_dev, n, pn_rows_dev, band_dev, (hipStream_t)stream);
+}
+
+int es_aead_check_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* blobs_dev, int64_t n,
+                              int group, const uint32_t* ctr_dev, uint8_t* ok_dev, uint8_t* plain_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (n < 0 || N < 0 || group < 1) return fail(ctx, ES_EINVAL, "es_aead_check_keyed_batch: negative count or group < 1");
+    if (n == 0) return ES_OK;
+    if (N == 0) return fail(ctx, ES_EINVAL, "es_aead_check_keyed_batch: records but an empty key ring");
+    if (!ring_dev || !key_dev || !blobs_dev || !ctr_dev || !ok_dev) return fail(ctx, ES_EINVAL, "es_aead_check_keyed_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_aead_check_keyed(ctx, ring_dev, N, key_dev, blobs_dev, n, group, ctr_dev, ok_dev, plain_dev, (hipStream_t)stream);
+}
+
+int es_select_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint32_t* ctr_dev, int64_t B, int L,
+                          const uint8_t* hard_info_dev, const uint8_t* hard_ok_dev, const uint8_t* cand_info_dev,
+                          const double* cand_metric_dev, const uint8_t* cand_ok_dev, const int32_t* ncand_dev,
+                          uint8_t* payload_dev, int8_t* ok_dev, int32_t* which_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    ES_REQUIRE_DEFAULT_CODE(ctx, "es_select_keyed_batch");
+    if (B < 0 || N < 0 || L < 1) return fail(ctx, ES_EINVAL, "es_select_keyed_batch: negative count or list size < 1");
+    if (B == 0) return ES_OK;
+    if (N == 0) return fail(ctx, ES_EINVAL, "es_select_keyed_batch: records but an empty key ring");
+    if (!ring_dev || !key_dev || !ctr_dev || !hard_info_dev || !hard_ok_dev || !cand_info_dev || !cand_metric_dev || !cand_ok_dev ||
+        !ncand_dev || !payload_dev || !ok_dev || !which_dev) return fail(ctx, ES_EINVAL, "es_select_keyed_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_select_keyed(ctx, ring_dev, N, key_dev, ctr_dev, B, L, hard_info_dev, hard_ok_dev, cand_info_dev, cand_metric_dev,
+                                  cand_ok_dev, ncand_dev, payload_dev, ok_dev, which_dev, (hipStream_t)stream);
+}
+
+int es_plan_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev, const int32_t* hdr_base_dev,
+                  int64_t rows, int T, const uint8_t* hdr_ok_dev, const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N,
+                  int C, uint8_t* cand_slot_dev, uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (rows < 0 || N < 0 || P < 0 || T < 0) return fail(ctx, ES_EINVAL, "es_plan_batch: negative size");
+    if (rows == 0 || N == 0) return ES_OK;
+    if (rows * N > ((int64_t)1 << 31)) return fail(ctx, ES_EINVAL, "es_plan_batch: more than 2^31 (key, row) pairs in one call");
+    // the widest window ends at round((T - 1215) / 1215) + 200: the hop table must reach it
+    if (C < (T + ES_FRAME_LEN - 1) / ES_FRAME_LEN + 201) return fail(ctx, ES_EINVAL, "es_plan_batch: hop table narrower than ceil(T / 1215) + 201 counters");
+    if (!peaks_dev || !npeaks_dev || !rowband_dev || !hdr_base_dev || !hop_dev || !cand_slot_dev || !cand_ctr_dev || !count_dev ||
+        (P > 0 && (!hdr_ok_dev || !hdr_lo16_dev))) return fail(ctx, ES_EINVAL, "es_plan_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_plan(ctx, peaks_dev, npeaks_dev, rowband_dev, hdr_base_dev, rows, T, hdr_ok_dev, hdr_lo16_dev, P, hop_dev, N, C,
+                          cand_slot_dev, cand_ctr_dev, count_dev, looked_dev, (hipStream_t)stream);
+}
+
 }  // extern "C"

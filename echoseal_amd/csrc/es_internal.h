@@ -161,6 +161,19 @@ int es_launch_aead_check(es_ctx* ctx, const uint8_t* key32, const uint8_t* blobs
 int es_launch_select(es_ctx* ctx, const uint8_t* key32, const uint32_t* ctr, int64_t B, int L, const uint8_t* hard_info,
                      const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric, const uint8_t* cand_ok,
                      const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st);
+/* many keys at once (es_keyring.hip, es_aead.hip): ring rows of ES_KEYRING_BYTES, key = ring row of each record */
+int es_ensure_sbox(es_ctx* ctx);                                 /* ctx->d_sbox, created on first use (es_sched.hip) */
+int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st);
+int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t n,
+                             uint8_t* pn_rows, uint8_t* band, hipStream_t st);
+int es_launch_aead_check_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* blobs, int64_t n, int group,
+                               const uint32_t* ctr, uint8_t* ok, uint8_t* plain, hipStream_t st);
+int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t B, int L,
+                           const uint8_t* hard_info, const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric,
+                           const uint8_t* cand_ok, const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st);
+int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
+                   int64_t rows, int T, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
+                   uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 int es_launch_llr_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,

@@ -1,0 +1,254 @@
+// es_keyring.hip -- many keys at once: the key ring (everything the keyed kernels need of a 32-byte master key, derived on the
+// device), the key / PN / hop schedule of (key, counter) records, and the counter-candidate planning of the detector's scan for
+// every (key, clip, band).  Replaces, per key, SecureChannel.__init__ (rtwm/crypto.py:19-30: HKDF-SHA256), StreamPRNG.__init__
+// (rtwm/utils.py:86-88: BLAKE2s), the host-side expansion of es_sched.hip, and _scan_band_multi_frame's candidate loop
+// (rtwm/detector.py:105-142).
+//
+// Integer work throughout.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
+// registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
+// counter window across the lanes, order kept by ballot + count of lower lanes.  Global memory is reached through
+// address_space(1) pointers only.
+#include "es_internal.h"
+#include "es_crypto_dev.h"
+#include "es_wave.h"
+
+namespace {
+
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+typedef __attribute__((address_space(1))) const uint32_t g_cu32;
+typedef __attribute__((address_space(1))) const int32_t g_ci32;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+typedef __attribute__((address_space(1))) uint32_t g_u32;
+typedef __attribute__((address_space(1))) int32_t g_i32;
+
+// ring row, in 32-bit words (include/echoseal_hip.h): AEAD key | AES round keys | HMAC inner state | HMAC outer state | header PN | hop0
+constexpr int RW_AEAD = 0, RW_RK = 8, RW_IPAD = 52, RW_OPAD = 60, RW_HDR = 68, RW_HOP0 = 72, RW_WORDS = ES_KEYRING_BYTES / 4;
+static_assert(RW_WORDS == 76 && ES_KEYRING_BYTES % 16 == 0, "ring row layout");
+
+__device__ __forceinline__ void load_sbox(uint8_t* sbox, const uint8_t* sbox_g)
+{
+    sbox[threadIdx.x] = ((g_cu8*)sbox_g)[threadIdx.x];
+    __syncthreads();
+}
+
+// states after the 64-byte HMAC pad blocks of a key of eight big-endian words
+__device__ __forceinline__ void hmac256_pads(const uint32_t key[8], uint32_t ipad[8], uint32_t opad[8])
+{
+    uint32_t w[16];
+    #pragma unroll
+    for (int t = 0; t < 16; ++t) w[t] = 0x36363636u ^ (t < 8 ? key[t] : 0u);
+    #pragma unroll
+    for (int t = 0; t < 8; ++t) ipad[t] = c_IV256[t];
+    sha256_compress(ipad, w);
+    #pragma unroll
+    for (int t = 0; t < 16; ++t) w[t] = 0x5c5c5c5cu ^ (t < 8 ? key[t] : 0u);
+    #pragma unroll
+    for (int t = 0; t < 8; ++t) opad[t] = c_IV256[t];
+    sha256_compress(opad, w);
+}
+
+__global__ __launch_bounds__(256) void es_keyring_derive_kernel(const uint8_t* __restrict__ master_p, long long N,
+        const uint8_t* __restrict__ sbox_g, uint8_t* __restrict__ ring_p)
+{
+    __shared__ uint8_t sbox[256];
+    load_sbox(sbox, sbox_g);
+    es_lds_cu8* sb = (es_lds_cu8*)sbox;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < N; k += stride) {
+        g_cu8* mk = (g_cu8*)master_p + k * 32;
+        g_u32* row = (g_u32*)(ring_p + k * ES_KEYRING_BYTES);
+        uint32_t master[8];
+        #pragma unroll
+        for (int t = 0; t < 8; ++t)
+            master[t] = ((uint32_t)mk[4 * t] << 24) | ((uint32_t)mk[4 * t + 1] << 16) | ((uint32_t)mk[4 * t + 2] << 8) | mk[4 * t + 3];
+        uint32_t ip[8], op[8], w[16], prk[8], t1[8], t2[8];
+        // HKDF-Extract: PRK = HMAC(salt = 32 zero bytes, master)
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) prk[t] = 0;
+        hmac256_pads(prk, ip, op);
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) w[t] = master[t];
+        hmac256_short(ip, op, w, 8, prk);
+        // HKDF-Expand: T1 = HMAC(PRK, info | 01), T2 = HMAC(PRK, T1 | info | 02); info = "EchoSeal:KDF:v1" (15 bytes)
+        hmac256_pads(prk, ip, op);
+        w[0] = 0x4563686fu; w[1] = 0x5365616cu; w[2] = 0x3a4b4446u; w[3] = 0x3a763101u;
+        hmac256_short(ip, op, w, 4, t1);
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) w[t] = t1[t];
+        w[8] = 0x4563686fu; w[9] = 0x5365616cu; w[10] = 0x3a4b4446u; w[11] = 0x3a763102u;
+        hmac256_short(ip, op, w, 12, t2);
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) row[RW_AEAD + t] = __builtin_bswap32(t1[t]);        // ChaCha20 reads its key as little-endian words
+        // AES sub-key = BLAKE2s-128(PRNG seed = T2, person "EchoSeal"), then the 44 round-key words
+        uint32_t seed[8], sub[4], rk[44];
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) seed[t] = __builtin_bswap32(t2[t]);
+        blake2s_sub_key(seed, sub);
+        #pragma unroll
+        for (int t = 0; t < 4; ++t) rk[t] = __builtin_bswap32(sub[t]);
+        aes128_expand(rk, sb);
+        #pragma unroll
+        for (int t = 0; t < 44; ++t) row[RW_RK + t] = rk[t];
+        // hop key = the master key itself: HMAC pad states, and the band of counter 0
+        hmac256_pads(master, ip, op);
+        #pragma unroll
+        for (int t = 0; t < 8; ++t) { row[RW_IPAD + t] = ip[t]; row[RW_OPAD + t] = op[t]; }
+        w[0] = 0;
+        hmac256_short(ip, op, w, 1, t1);
+        // header PN = the first AES block of counter 0, bytes in stream order
+        uint32_t s[4] = {0u, 0u, 0u, 0u};
+        aes128_encrypt<10>(rk, sb, s);
+        #pragma unroll
+        for (int c = 0; c < 4; ++c) row[RW_HDR + c] = __builtin_bswap32(s[c]);
+        row[RW_HOP0] = (t1[0] >> 24) & 3u;
+        row[RW_HOP0 + 1] = 0; row[RW_HOP0 + 2] = 0; row[RW_HOP0 + 3] = 0;
+    }
+}
+
+// es_schedule_kernel (es_sched.hip) with the key material of record i read from ring row key[i]
+__global__ __launch_bounds__(256) void es_schedule_keyed_kernel(const uint8_t* __restrict__ ring_p, long long N,
+        const int32_t* __restrict__ key_p, const uint32_t* __restrict__ ctr_p, long long n, const uint8_t* __restrict__ sbox_g,
+        uint8_t* __restrict__ pn_p, uint8_t* __restrict__ band_p)
+{
+    __shared__ uint8_t sbox[256];
+    load_sbox(sbox, sbox_g);
+    es_lds_cu8* sb = (es_lds_cu8*)sbox;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const long long key = ((g_ci32*)key_p)[i];
+        const uint32_t ctr = ((g_cu32*)ctr_p)[i];
+        const bool have = key >= 0 && key < N;
+        g_cu32* row = (g_cu32*)(ring_p + (have ? key : 0) * ES_KEYRING_BYTES);
+        if (pn_p) {
+            g_u32* out = (g_u32*)(pn_p + i * ES_PN_BYTES);                            // 152-byte rows are 8-byte aligned
+            if (have) {
+                uint32_t rk[44];                                                      // once per record, not once per block
+                #pragma unroll
+                for (int t = 0; t < 44; ++t) rk[t] = row[RW_RK + t];
+                #pragma unroll 1
+                for (int j = 0; j < 10; ++j) {
+                    uint32_t s[4] = {0u, ctr, 0u, (uint32_t)j};                       // (ctr << 64 | j), big endian
+                    aes128_encrypt<10>(rk, sb, s);
+                    out[4 * j] = __builtin_bswap32(s[0]); out[4 * j + 1] = __builtin_bswap32(s[1]);
+                    if (j < 9) { out[4 * j + 2] = __builtin_bswap32(s[2]); out[4 * j + 3] = __builtin_bswap32(s[3]); }   // 152 = 9 * 16 + 8
+                }
+            } else {
+                #pragma unroll 1
+                for (int t = 0; t < ES_PN_BYTES / 4; ++t) out[t] = 0;
+            }
+        }
+        if (band_p) {
+            uint32_t b = 0;
+            if (have) {
+                uint32_t ip[8], op[8], w[16], tag[8];
+                #pragma unroll
+                for (int t = 0; t < 8; ++t) { ip[t] = row[RW_IPAD + t]; op[t] = row[RW_OPAD + t]; }
+                w[0] = ctr;                                                           // message = ctr_be32
+                hmac256_short(ip, op, w, 1, tag);
+                b = (tag[0] >> 24) & 3u;                                              // tag[0] % 4
+            }
+            ((g_u8*)band_p)[i] = (uint8_t)b;
+        }
+    }
+}
+
+// One wave per (key, row): the candidate (peak slot, counter) pairs of _scan_band_multi_frame in try order.
+__global__ __launch_bounds__(256) void es_plan_kernel(const int32_t* __restrict__ peaks_p, const int32_t* __restrict__ npeaks_p,
+        const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p, long long rows, int T,
+        const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p,
+        long long N, int C, uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p,
+        int32_t* __restrict__ looked_p)
+{
+    const int lane = threadIdx.x & 63;
+    const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+    if (pair >= N * rows) return;
+    const long long k = pair / rows, row = pair - k * rows;
+    g_ci32* peaks = (g_ci32*)peaks_p + row * ES_MAX_PEAKS;
+    g_cu8* hop = (g_cu8*)hop_p + k * (long long)C;
+    g_u8* slot_out = (g_u8*)slot_p + pair * ES_MAX_TRIES;
+    g_u32* ctr_out = (g_u32*)cctr_p + pair * ES_MAX_TRIES;
+    const int band = ((g_cu8*)rowband_p)[row];
+    int npk = ((g_ci32*)npeaks_p)[row] & 0xFFFF;
+    npk = npk < ES_PEAK_LIMIT ? npk : ES_PEAK_LIMIT;
+    const long long p0 = ((g_ci32*)base_p)[row];
+    int tried = 0, looked = 0;
+    #pragma unroll 1
+    for (int s = 0; s < npk && tried < ES_MAX_TRIES; ++s) {
+        const int start = peaks[s];
+        if (start < 0 || (long long)start + ES_FRAME_LEN > T) continue;               // only peaks that can hold a frame
+        const long long p = p0 + looked;
+        if (p < 0 || p >= P) break;                                                   // (a header table that does not cover the row: host error)
+        ++looked;
+        const bool hok = ((g_cu8*)hok_p)[k * P + p] != 0;
+        const int lo16 = ((g_ci32*)hlo_p)[k * P + p];
+        const int est = (int)((2LL * start + ES_FRAME_LEN) / (2 * ES_FRAME_LEN));     // round(start / 1215): 1215 is odd, no ties
+        bool wide = true;
+        if (!hok) {                                                                   // the +-3 window, gated by the hop alone
+            const int c = est - 3 + lane;
+            const bool v = lane < 7 && c >= 0 && c < C && hop[c] == band;
+            const unsigned long long m = __ballot(v);
+            if (m) {
+                const int pos = tried + lanes_below(m);
+                if (v && pos < ES_MAX_TRIES) { slot_out[pos] = (uint8_t)s; ctr_out[pos] = (uint32_t)c; }
+                tried += __popcll(m);
+                wide = false;
+            }
+        }
+        if (wide) {                                                                   // the +-200 window; with a header also gated by lo16
+            const int lo = est - 200 > 0 ? est - 200 : 0, hi = est + 200;
+            #pragma unroll 1
+            for (int c0 = lo; c0 <= hi && tried < ES_MAX_TRIES; c0 += 64) {
+                const int c = c0 + lane;
+                const bool v = c <= hi && c < C && hop[c] == band && (!hok || (c & 0xFFFF) == lo16);
+                const unsigned long long m = __ballot(v);
+                const int pos = tried + lanes_below(m);
+                if (v && pos < ES_MAX_TRIES) { slot_out[pos] = (uint8_t)s; ctr_out[pos] = (uint32_t)c; }
+                tried += __popcll(m);
+            }
+        }
+        tried = tried < ES_MAX_TRIES ? tried : ES_MAX_TRIES;
+    }
+    if (lane == 0) {
+        ((g_i32*)count_p)[pair] = tried;
+        if (looked_p) ((g_i32*)looked_p)[pair] = looked;
+    }
+}
+
+long long grid_for(const es_ctx* ctx, long long n)
+{
+    long long blocks = (n + 255) / 256;
+    const long long cap = (long long)ctx->num_cu * 8;
+    return blocks > cap ? cap : blocks;
+}
+
+}  // namespace
+
+int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
+{
+    if (const int rc = es_ensure_sbox(ctx)) return rc;
+    hipLaunchKernelGGL(es_keyring_derive_kernel, dim3((unsigned)grid_for(ctx, N)), dim3(256), 0, st, master32, (long long)N,
+                       (const uint8_t*)ctx->d_sbox, ring);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t n,
+                             uint8_t* pn_rows, uint8_t* band, hipStream_t st)
+{
+    if (const int rc = es_ensure_sbox(ctx)) return rc;
+    hipLaunchKernelGGL(es_schedule_keyed_kernel, dim3((unsigned)grid_for(ctx, n)), dim3(256), 0, st, ring, (long long)N, key, ctr,
+                       (long long)n, (const uint8_t*)ctx->d_sbox, pn_rows, band);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
+int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
+                   int64_t rows, int T, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
+                   uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st)
+{
+    const long long pairs = (long long)N * rows;                                      // one wave each, four waves per block
+    hipLaunchKernelGGL(es_plan_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, peaks, npeaks, rowband, hdr_base,
+                       (long long)rows, T, hdr_ok, hdr_lo16, (long long)P, hop, (long long)N, C, cand_slot, cand_ctr, count, looked);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}

@@ -7,6 +7,7 @@
 // Integer work: one lane per counter (10 AES blocks with the S-box in LDS, two SHA-256 compressions from the
 // precomputed inner / outer pad states).  Round keys and pad states are expanded on the host and passed by value.
 #include "es_internal.h"
+#include "es_crypto_dev.h"
 #include <cstring>
 
 namespace {
@@ -15,67 +16,6 @@ struct SchedKeys {
     uint32_t rk[44];          // AES-128 round keys, big-endian words (FIPS 197 w[0..43])
     uint32_t ipad[8], opad[8];  // SHA-256 states after the HMAC pad blocks
 };
-
-__device__ __forceinline__ uint32_t ror32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-
-__constant__ uint32_t c_K256[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
-    0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc,
-    0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147,
-    0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08,
-    0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208,
-    0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-
-__device__ void sha256_compress(uint32_t st[8], uint32_t w[16])
-{
-    uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-    #pragma unroll 1
-    for (int i = 0; i < 64; ++i) {
-        if (i >= 16) {
-            const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
-            const uint32_t s0 = ror32(w15, 7) ^ ror32(w15, 18) ^ (w15 >> 3);
-            const uint32_t s1 = ror32(w2, 17) ^ ror32(w2, 19) ^ (w2 >> 10);
-            w[i & 15] = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
-        }
-        const uint32_t t1 = h + (ror32(e, 6) ^ ror32(e, 11) ^ ror32(e, 25)) + ((e & f) ^ (~e & g)) + c_K256[i] + w[i & 15];
-        const uint32_t t2 = (ror32(a, 2) ^ ror32(a, 13) ^ ror32(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-    }
-    st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
-}
-
-__device__ __forceinline__ uint32_t xtime4(uint32_t x)      // xtime on four packed bytes
-{
-    return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1bu);
-}
-
-// columns are big-endian words: byte (row 0) in bits 31..24
-__device__ void aes128_encrypt(const SchedKeys& k, const uint8_t* sbox, uint32_t s[4])
-{
-    #pragma unroll
-    for (int c = 0; c < 4; ++c) s[c] ^= k.rk[c];
-    #pragma unroll 1
-    for (int r = 1; r <= 10; ++r) {
-        uint32_t t[4];
-        #pragma unroll
-        for (int c = 0; c < 4; ++c) {                              // SubBytes + ShiftRows
-            t[c] = ((uint32_t)sbox[s[c] >> 24] << 24) | ((uint32_t)sbox[(s[(c + 1) & 3] >> 16) & 255] << 16) |
-                   ((uint32_t)sbox[(s[(c + 2) & 3] >> 8) & 255] << 8) | (uint32_t)sbox[s[(c + 3) & 3] & 255];
-        }
-        if (r < 10) {
-            #pragma unroll
-            for (int c = 0; c < 4; ++c) {                          // MixColumns on a packed column
-                const uint32_t a = t[c], x2 = xtime4(a);
-                const uint32_t x3 = x2 ^ a;
-                // out_row_i = 2 a_i ^ 3 a_{i+1} ^ a_{i+2} ^ a_{i+3}; rotating left by 8 brings a_{i+1} to row i
-                t[c] = x2 ^ ((x3 << 8) | (x3 >> 24)) ^ ((a << 16) | (a >> 16)) ^ ((a << 24) | (a >> 8));
-            }
-        }
-        #pragma unroll
-        for (int c = 0; c < 4; ++c) s[c] = t[c] ^ k.rk[4 * r + c];
-    }
-}
 
 __global__ __launch_bounds__(256) void es_schedule_kernel(SchedKeys k, const uint8_t* __restrict__ sbox_g,
         const uint32_t* __restrict__ ctr_dev, uint32_t ctr0, long long n, uint8_t* __restrict__ pn, uint8_t* __restrict__ band)
@@ -90,7 +30,7 @@ __global__ __launch_bounds__(256) void es_schedule_kernel(SchedKeys k, const uin
         #pragma unroll 1
         for (int j = 0; j < 10; ++j) {
             uint32_t s[4] = {0u, ctr, 0u, (uint32_t)j};                           // (ctr << 64 | j), big endian
-            aes128_encrypt(k, sbox, s);
+            aes128_encrypt<1>(k.rk, sbox, s);
             const int nw = (j < 9) ? 4 : 2;                                          // 152 = 9 * 16 + 8
             for (int c = 0; c < nw; ++c) row[4 * j + c] = __builtin_bswap32(s[c]);
         }
@@ -153,15 +93,24 @@ void host_sha256_compress(uint32_t st[8], const uint8_t blk[64])
 
 }  // namespace
 
+// the AES S-box on the device, created on first use (es_schedule_batch and the key-ring entry points)
+int es_ensure_sbox(es_ctx* ctx)
+{
+    if (!ctx->d_sbox) {
+        uint8_t sb[256];
+        host_sbox(sb);
+        ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_sbox, 256));
+        ES_HIP_CHECK(ctx, hipMemcpy(ctx->d_sbox, sb, 256, hipMemcpyHostToDevice));
+    }
+    return ES_OK;
+}
+
 int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* band_key32, const uint32_t* ctr_dev,
                        uint32_t ctr0, int64_t n, uint8_t* pn_rows, uint8_t* band, hipStream_t st)
 {
     uint8_t sb[256];
     host_sbox(sb);
-    if (!ctx->d_sbox) {
-        ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_sbox, 256));
-        ES_HIP_CHECK(ctx, hipMemcpy(ctx->d_sbox, sb, 256, hipMemcpyHostToDevice));
-    }
+    if (const int rc = es_ensure_sbox(ctx)) return rc;
     SchedKeys k;
     uint8_t rk[176];
     std::memcpy(rk, aes_key16, 16);

@@ -105,6 +105,34 @@ class EmbedResult:
     scale: torch.Tensor | None = None   # [R, ceil(n / block)] float64 gain of every block (want_scale)
 
 
+@dataclass
+class KeyRing:
+    """Keys as device data (es_keyring_derive_batch): row k of `ring` holds what the keyed kernels need of key k (layout:
+    include/echoseal_hip.h)."""
+    ring: torch.Tensor         # [N, ES_KEYRING_BYTES] uint8
+    n: int
+
+    @property
+    def aead_key(self) -> torch.Tensor:      # [N, 32] uint8
+        return self.ring[:, 0:32]
+
+    @property
+    def hdr_pn(self) -> torch.Tensor:        # [N, 16] uint8 = np.packbits(pn_bits(0, 128)) of each key
+        return self.ring[:, 272:288]
+
+    @property
+    def hop0(self) -> torch.Tensor:          # [N] uint8: band index of counter 0
+        return self.ring[:, 288]
+
+
+@dataclass
+class PlanResult:
+    slot: torch.Tensor         # [N * rows, 400] uint8: index into the row's peaks, try order (entries past `count` undefined)
+    ctr: torch.Tensor          # [N * rows, 400] int32 (the counters' 32-bit words)
+    count: torch.Tensor        # [N * rows] int32
+    looked: torch.Tensor       # [N * rows] int32: fitting peaks looked at
+
+
 class RxEngine:
     def __init__(self, device: int | torch.device = 0, *, list_size_max: int = 32, fs: int = 48_000, code_k: int = 448):
         """code_k: information positions of the polar code (data bits + CRC-8).  448 is the reference's own code (rtwm/polar_fast.py:8-9);
@@ -467,6 +495,97 @@ class RxEngine:
                   "es_schedule_batch")
         return pn, band
 
+    # ------------------------------------------------------------------ many keys at once (es_keyring.hip)
+    def keyring(self, keys) -> KeyRing:
+        """The key ring of 32-byte master keys (a sequence of bytes objects, or uint8 [N, 32]), derived on the device."""
+        if torch.is_tensor(keys):
+            mk = keys
+        else:
+            keys = [bytes(k) for k in keys]
+            if any(len(k) != 32 for k in keys):
+                raise ValueError("master_key must be 32 bytes (256 bit)")
+            mk = torch.from_numpy(np.frombuffer(b"".join(keys), np.uint8).reshape(-1, 32).copy())
+        mk = self._dev(mk, torch.uint8)
+        if mk.dim() != 2 or mk.shape[1] != 32:
+            raise ValueError("keys must be 32 bytes each")
+        N = mk.shape[0]
+        ring = torch.empty((N, nat.ES_KEYRING_BYTES), dtype=torch.uint8, device=self.device)
+        nat.check(self._ctx, self._lib.es_keyring_derive_batch(self._ctx, _ptr(mk), N, _ptr(ring), self._stream()), "es_keyring_derive_batch")
+        return KeyRing(ring, N)
+
+    def _key_dev(self, ring: KeyRing, key_idx, n: int) -> torch.Tensor:
+        """Key indices as int32 on the device; indices the host can see (anything but a device tensor) are range-checked here."""
+        if not (torch.is_tensor(key_idx) and key_idx.is_cuda):
+            h = np.asarray(key_idx.numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
+            if h.size and (h.min() < 0 or h.max() >= ring.n):
+                raise ValueError(f"key index outside [0, {ring.n})")
+            key_idx = torch.from_numpy(h)
+        kd = self._dev(key_idx, torch.int32).reshape(-1)
+        if kd.numel() != n:
+            raise ValueError("one key index per record is required")
+        return kd
+
+    def schedule_keyed(self, ring: KeyRing, key_idx, ctrs, *, want_pn: bool = True, want_band: bool = True):
+        """`schedule` for records of several keys (es_schedule_keyed_batch): record i = (ring row key_idx[i], counter ctrs[i])
+        -> (pn [n,152] uint8 or None, band [n] uint8 or None).  want_pn=False skips the AES blocks (bands only)."""
+        cd = self._ctr_dev(ctrs).reshape(-1)
+        n = cd.numel()
+        kd = self._key_dev(ring, key_idx, n)
+        pn = torch.empty((n, 152), dtype=torch.uint8, device=self.device) if want_pn else None
+        band = torch.empty(n, dtype=torch.uint8, device=self.device) if want_band else None
+        if n and ring.n == 0:
+            raise ValueError("records but an empty key ring")
+        nat.check(self._ctx, self._lib.es_schedule_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(cd), n, _ptr(pn), _ptr(band),
+                                                               self._stream()), "es_schedule_keyed_batch")
+        return pn, band
+
+    def aead_check_keyed(self, ring: KeyRing, key_idx, blobs: torch.Tensor, ctrs, *, want_plain: bool = False):
+        """`aead_check` with the AEAD key of ring row key_idx[r] per row (per frame for [B,L,55]) (es_aead_check_keyed_batch)."""
+        if blobs.dtype != torch.uint8 or blobs.shape[-1] != 55 or blobs.dim() not in (2, 3):
+            raise ValueError("blobs must be uint8 [n,55] or [B,L,55]")
+        blobs = self._dev(blobs, torch.uint8)
+        group = blobs.shape[1] if blobs.dim() == 3 else 1
+        n = blobs.numel() // 55
+        ctrs = self._ctr_dev(ctrs).reshape(-1)
+        if ctrs.numel() * group != n:
+            raise ValueError("one expected counter per blob row (or per frame for [B,L,55]) is required")
+        kd = self._key_dev(ring, key_idx, ctrs.numel())
+        ok = torch.empty(blobs.shape[:-1], dtype=torch.uint8, device=self.device)
+        plain = torch.empty(blobs.shape[:-1] + (27,), dtype=torch.uint8, device=self.device) if want_plain else None
+        nat.check(self._ctx, self._lib.es_aead_check_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(blobs), n, group, _ptr(ctrs),
+                                                                 _ptr(ok), _ptr(plain), self._stream()), "es_aead_check_keyed_batch")
+        return (ok, plain) if want_plain else ok
+
+    def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T: int, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
+             hop: torch.Tensor) -> PlanResult:
+        """Counter candidates of every (key, row) in try order (es_plan_batch; the rules of _scan_band_multi_frame,
+        rtwm/detector.py:105-142).  peaks int32 [rows, 32] / npeaks int32 [rows] of a sync call over records of T samples, rowband
+        uint8 [rows] their bands, hdr_base int32 [rows] = index of the row's first fitting peak among the P fitting peaks of all
+        rows, hdr_ok uint8 / hdr_lo16 int32 [N, P] header results per (key, fitting peak), hop uint8 [N, C] band of (key, counter)."""
+        rows = peaks.shape[0]
+        if peaks.dim() != 2 or peaks.shape[1] != nat.ES_MAX_PEAKS or peaks.dtype != torch.int32 or npeaks.dtype != torch.int32 or npeaks.numel() != rows:
+            raise ValueError("peaks / npeaks: the int32 [rows, 32] / [rows] outputs of a sync call")
+        if hop.dim() != 2 or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [N, C]")
+        N, C = hop.shape
+        if hdr_ok.dtype != torch.uint8 or hdr_lo16.dtype != torch.int32 or hdr_ok.shape != hdr_lo16.shape or hdr_ok.dim() != 2 or hdr_ok.shape[0] != N:
+            raise ValueError("hdr_ok uint8 / hdr_lo16 int32 must be [N, P]")
+        P = hdr_ok.shape[1]
+        peaks = peaks.contiguous(); npeaks = npeaks.contiguous(); hop = hop.contiguous()
+        hdr_ok = hdr_ok.contiguous(); hdr_lo16 = hdr_lo16.contiguous()
+        rowband = self._dev(rowband, torch.uint8).reshape(-1)
+        hdr_base = self._dev(hdr_base, torch.int32).reshape(-1)
+        if rowband.numel() != rows or hdr_base.numel() != rows:
+            raise ValueError("rowband / hdr_base: one entry per row")
+        pairs = N * rows
+        res = PlanResult(torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.uint8, device=self.device),
+                         torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.int32, device=self.device),
+                         torch.empty(pairs, dtype=torch.int32, device=self.device), torch.empty(pairs, dtype=torch.int32, device=self.device))
+        nat.check(self._ctx, self._lib.es_plan_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows, int(T),
+                                                     _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(res.slot), _ptr(res.ctr),
+                                                     _ptr(res.count), _ptr(res.looked), self._stream()), "es_plan_batch")
+        return res
+
     def make_frames(self, sec, band_key32: bytes, ctrs, payloads: torch.Tensor) -> torch.Tensor:
         """Batch of transmitted frames on the device (WatermarkEmbedder.make_frames, rtwm/embedder.py:78-141):
         payloads uint8 [B,55] (already sealed) under frame counters `ctrs` -> float32 [B,1215].  `sec` is the
@@ -651,11 +770,30 @@ class RxEngine:
                                                           _ptr(blobs), self._stream()), "es_aead_seal_batch")
         return blobs
 
-    def select(self, scl: SclResult, *, key32: bytes | None = None, ctrs: torch.Tensor | None = None):
+    def select(self, scl: SclResult, *, key32: bytes | None = None, ctrs: torch.Tensor | None = None, ring: KeyRing | None = None,
+               key_idx=None):
         """Tail of PolarCode.decode (rtwm/fastpolar.py:268-276, 332-359) for every record of an SclResult, on the
         GPU: -> (payload [B,55] uint8, ok [B] int8, which [B] int32).  key32=None is validator=None; with a key the
-        validator is `aead_check` against ctrs [B].  ok = -1 marks records whose list loop had been skipped."""
+        validator is `aead_check` against ctrs [B].  ok = -1 marks records whose list loop had been skipped.
+        ring= with key_idx= [B]: the validator of record i uses the AEAD key of ring row key_idx[i] (es_select_keyed_batch)."""
         B, L = scl.cand_metric.shape
+        if ring is not None:
+            if key32 is not None or key_idx is None or ctrs is None:
+                raise ValueError("ring= goes with key_idx= and ctrs=, and without key32=")
+            ctrs = self._ctr_dev(ctrs)
+            if ctrs.numel() != B:
+                raise ValueError("one expected counter per record is required with a key")
+            kd = self._key_dev(ring, key_idx, B)
+            payload = torch.empty((B, 55), dtype=torch.uint8, device=self.device)
+            ok = torch.empty(B, dtype=torch.int8, device=self.device)
+            which = torch.empty(B, dtype=torch.int32, device=self.device)
+            nat.check(self._ctx, self._lib.es_select_keyed_batch(
+                self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(ctrs), B, L, _ptr(scl.hard_info), _ptr(scl.hard_ok), _ptr(scl.cand_info),
+                _ptr(scl.cand_metric), _ptr(scl.cand_ok), _ptr(scl.ncand), _ptr(payload), _ptr(ok), _ptr(which), self._stream()),
+                "es_select_keyed_batch")
+            return payload, ok, which
+        if key_idx is not None:
+            raise ValueError("key_idx= goes with ring=")
         if key32 is not None:
             if len(key32) != 32:
                 raise ValueError("AEAD key must be 32 bytes")

@@ -49,6 +49,9 @@ extern "C" {
 #define ES_MAX_PEAKS     32   /* detector consumes at most 25 peaks per scan (rtwm/detector.py:108) */
 #define ES_MAX_LIST    1024   /* any list size 1..1024; the mapping of paths to lanes is chosen per launch (es_set_option) */
 #define ES_PN_BYTES     152   /* ceil(1215 / 8): packed PN row of one frame counter */
+#define ES_KEYRING_BYTES 304  /* one key-ring row (es_keyring_derive_batch) */
+#define ES_MAX_TRIES    400   /* candidates per (key, band) scan (rtwm/detector.py:107) */
+#define ES_PEAK_LIMIT    25   /* peaks looked at per scan (rtwm/detector.py:108) */
 
 #define ES_DTYPE_F32      0
 #define ES_DTYPE_I16      1
@@ -336,6 +339,57 @@ int es_select_batch(es_ctx* ctx, const uint8_t* key32_host, const uint32_t* ctr_
                     const uint8_t* hard_info_dev, const uint8_t* hard_ok_dev, const uint8_t* cand_info_dev,
                     const double* cand_metric_dev, const uint8_t* cand_ok_dev, const int32_t* ncand_dev,
                     uint8_t* payload_dev, int8_t* ok_dev, int32_t* which_dev, void* stream);
+
+/* ---- many keys at once: "which of the N keys we issued marked this clip?" ---------------------------------------------
+ * Key ring: everything the keyed kernels need of a 32-byte master key, derived on the device, one lane per key.  Replaces
+ * SecureChannel.__init__ (rtwm/crypto.py:19-30: HKDF-SHA256(master, salt none, info "EchoSeal:KDF:v1", 64 bytes) -> AEAD key |
+ * PRNG seed), StreamPRNG.__init__ (rtwm/utils.py:86-88: BLAKE2s(seed, digest 16, person "EchoSeal") -> AES-128 key), the AES key
+ * expansion and HMAC pad blocks that es_schedule_batch does on the host, WatermarkDetector.__init__'s header PN
+ * (rtwm/detector.py:36: pn_bits(0, 128)) and the first band of its band order (rtwm/detector.py:46: choose_band(key, 0)).
+ * master32_dev [N][32]; ring_dev [N][ES_KEYRING_BYTES], 16-byte aligned.  Row layout (byte offsets):
+ *     0  AEAD key, 32 bytes as SecureChannel holds them
+ *    32  44 AES round-key words (FIPS 197 w[0..43], each a native uint32 whose top byte is the word's first byte)
+ *   208  SHA-256 state (8 native uint32) after the HMAC inner pad block of the hop key (= the master key, rtwm/detector.py:31)
+ *   240  the same after the outer pad block
+ *   272  header PN, 16 bytes = np.packbits(pn_bits(0, 128))
+ *   288  hop0 = band index of counter 0; 289..303 zero                                                                     */
+int es_keyring_derive_batch(es_ctx* ctx, const uint8_t* master32_dev, int64_t N, uint8_t* ring_dev, void* stream);
+
+/* es_schedule_batch for records of several keys: record i = (ring row key_dev[i], counter ctr_dev[i]); replaces the same reference
+ * lines (rtwm/crypto.py:46-48, rtwm/utils.py:27-36, 115-132) per (key, counter).  key_dev [n] int32, ctr_dev [n] uint32; outputs as
+ * es_schedule_batch.  Either output may be NULL; with pn_rows_dev == NULL the ten AES blocks are skipped (bands only: the hop
+ * table of es_plan_batch).  A key index outside [0, N) gives band 0 and a zero PN row and reads nothing of the ring (the indices
+ * are device data: the host cannot refuse them); N == 0 with n > 0 is ES_EINVAL.  Records sorted by key read the ring best. */
+int es_schedule_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint32_t* ctr_dev, int64_t n,
+                            uint8_t* pn_rows_dev, uint8_t* band_dev, void* stream);
+
+/* es_aead_check_batch / es_select_batch with the AEAD key of ring row key_dev[r] in place of key32_host, r = i / group for the
+ * check (one key and one counter per group) and r = the record for the selection (key_dev [B]); same outputs, same ok codes
+ * (-1 and -2 included).  A key index outside [0, N) is a validator that accepts nothing (ok 0, zero plaintext).              */
+int es_aead_check_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* blobs_dev, int64_t n,
+                              int group, const uint32_t* ctr_dev, uint8_t* ok_dev, uint8_t* plain_dev, void* stream);
+int es_select_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint32_t* ctr_dev, int64_t B, int L,
+                          const uint8_t* hard_info_dev, const uint8_t* hard_ok_dev, const uint8_t* cand_info_dev,
+                          const double* cand_metric_dev, const uint8_t* cand_ok_dev, const int32_t* ncand_dev,
+                          uint8_t* payload_dev, int8_t* ok_dev, int32_t* which_dev, void* stream);
+
+/* Candidate planning: replaces the (peak, counter) loop of _scan_band_multi_frame (rtwm/detector.py:105-142) for every
+ * (key, row) at once, row = one band-passed record of a sync call.  One wave per pair k * rows + r:
+ *   - of the first min(npeaks_dev[r] & 0xFFFF, ES_PEAK_LIMIT) entries of peaks_dev [rows][ES_MAX_PEAKS] only those with
+ *     0 <= start and start + 1215 <= T are looked at, in order, while fewer than ES_MAX_TRIES candidates are planned;
+ *   - the j-th of them (j from 0) has its header result at hdr_ok_dev / hdr_lo16_dev [k * P + hdr_base_dev[r] + j] (the outputs of
+ *     one es_header_at_batch over key-major (key, fitting peak) records; P = fitting peaks of all rows);
+ *   - ctr_est = (2 * start + 1215) / 2430 (= round(start / 1215)); header ok: counters of [max(0, ctr_est - 200), ctr_est + 200]
+ *     with (ctr & 0xFFFF) == lo16 and hop_dev[k * C + ctr] == rowband_dev[r]; else the +-3 window gated by the hop alone and,
+ *     only if that is empty, the +-200 window gated by the hop alone;
+ *   - at most ES_MAX_TRIES candidates per pair: the last peak's list is cut, later peaks are not looked at.
+ * hop_dev [N][C] uint8 = band of (key, counter), C >= ceil(T / 1215) + 201 (else ES_EINVAL): es_schedule_keyed_batch, bands only.
+ * Out, per pair: cand_slot_dev [N * rows][ES_MAX_TRIES] uint8 (index into the row's peaks) and cand_ctr_dev [..][ES_MAX_TRIES]
+ * uint32 in try order (entries past the count are not written), count_dev [N * rows] int32, looked_dev (nullable) = fitting peaks
+ * looked at (the length of the scan's header log).  Needs no tables, only enqueues.                                           */
+int es_plan_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev, const int32_t* hdr_base_dev,
+                  int64_t rows, int T, const uint8_t* hdr_ok_dev, const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N,
+                  int C, uint8_t* cand_slot_dev, uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream);
 
 #ifdef __cplusplus
 }
