@@ -290,62 +290,37 @@ AeadKey load_key(const uint8_t* key32)
 int es_launch_aead_check(es_ctx* ctx, const uint8_t* key32, const uint8_t* blobs, int64_t n, int group, const uint32_t* ctr,
                          uint8_t* ok, uint8_t* plain, hipStream_t st)
 {
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_aead_check_kernel, dim3((unsigned)blocks), dim3(256), 0, st, load_key(key32), blobs, (long long)n,
-                       group, ctr, ok, plain);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_aead_check_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, load_key(key32), blobs, (long long)n,
+                     group, ctr, ok, plain);
 }
 
 int es_launch_aead_seal(es_ctx* ctx, const uint8_t* key32, const uint8_t* nonces, const uint8_t* plain, int64_t n, uint8_t* blobs,
                         hipStream_t st)
 {
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_aead_seal_kernel, dim3((unsigned)blocks), dim3(256), 0, st, load_key(key32), nonces, plain, (long long)n, blobs);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_aead_seal_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, load_key(key32), nonces, plain, (long long)n, blobs);
 }
 
 int es_launch_select(es_ctx* ctx, const uint8_t* key32, const uint32_t* ctr, int64_t B, int L, const uint8_t* hard_info,
                      const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric, const uint8_t* cand_ok,
                      const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st)
 {
-    long long blocks = (B + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
     AeadKey k{};
     if (key32) k = load_key(key32);
-    hipLaunchKernelGGL(es_select_kernel, dim3((unsigned)blocks), dim3(256), 0, st, k, key32 ? 1 : 0, ctr, (long long)B, L,
-                       hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_select_kernel, es_grid(B, 256, ctx->num_cu * 8), 256, 0, st, k, key32 ? 1 : 0, ctr, (long long)B, L,
+                     hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
 }
 
 int es_launch_aead_check_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* blobs, int64_t n, int group,
                                const uint32_t* ctr, uint8_t* ok, uint8_t* plain, hipStream_t st)
 {
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_aead_check_keyed_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ring, (long long)N, key, blobs, (long long)n,
-                       group, ctr, ok, plain);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_aead_check_keyed_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, key, blobs, (long long)n,
+                     group, ctr, ok, plain);
 }
 
 int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t B, int L,
                            const uint8_t* hard_info, const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric,
                            const uint8_t* cand_ok, const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st)
 {
-    long long blocks = (B + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_select_keyed_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ring, (long long)N, key, ctr, (long long)B, L,
-                       hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_select_keyed_kernel, es_grid(B, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, key, ctr, (long long)B, L,
+                     hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, payload, ok, which);
 }

@@ -65,11 +65,13 @@ int es_slab_leave(es_ctx* ctx, int domain, int shape, bool shareable, hipStream_
 // A launch that draws its frames from a counter gets a counter of its own.  Eager launches rotate over the first ES_CURSOR_RING -
 // ES_CURSOR_CAPTURED counters (one is reused only after that many further launches of the context); a launch recorded into a stream
 // capture takes one of the last ES_CURSOR_CAPTURED for good -- its graph may be replayed at any time, beside any eager launch.
+#define ES_STR_(x) #x
+#define ES_STR(x) ES_STR_(x)
 int es_cursor_next(es_ctx* ctx, hipStream_t st, int** cursor)
 {
     if (capturing(st)) {
         if (ctx->cursor_captured >= ES_CURSOR_CAPTURED) {
-            ctx->err = "es_scl_batch: this context has recorded its 256 list-decoder launches with skip_if_hard_ok into stream captures; use another context";
+            ctx->err = "es_scl_batch: this context has recorded its " ES_STR(ES_CURSOR_CAPTURED) " list-decoder launches with skip_if_hard_ok into stream captures; use another context";
             return ES_ENOMEM;
         }
         *cursor = ctx->d_cursors + (ES_CURSOR_RING - 1 - ctx->cursor_captured++);
@@ -397,7 +399,7 @@ int es_llr_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const int32
     if (B == 0) return ES_OK;
     if (!y_dev || !band_dev || !pn_dev || !llr_dev) return fail(ctx, ES_EINVAL, "es_llr_batch: null pointer");
     DeviceGuard g(ctx->device);
-    return es_launch_llr(ctx, y_dev, B, T, start_dev, band_dev, pn_dev, variant, llr_dev, best_s_dev,
+    return es_launch_llr(ctx, y_dev, B, T, start_dev, {nullptr, 0, 1}, band_dev, pn_dev, variant, llr_dev, best_s_dev,
                          score_dev, (hipStream_t)stream);
 }
 
@@ -411,7 +413,7 @@ int es_header_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const in
     if (!y_dev || !band_dev || !hdr_pn_dev || !ok_dev || !val_dev || !score_dev)
         return fail(ctx, ES_EINVAL, "es_header_batch: null pointer");
     DeviceGuard g(ctx->device);
-    return es_launch_header(ctx, y_dev, B, T, start_dev, band_dev, hdr_pn_dev, ok_dev, val_dev, score_dev,
+    return es_launch_header(ctx, y_dev, B, T, start_dev, {nullptr, 0, 1}, band_dev, hdr_pn_dev, ok_dev, val_dev, score_dev,
                             best_s_dev, (hipStream_t)stream);
 }
 
@@ -427,8 +429,8 @@ int es_llr_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int
     if (n_rows < 1) return fail(ctx, ES_EINVAL, "es_llr_at_batch: no rows to read");
     if (!y_dev || !band_dev || !pn_dev || !llr_dev) return fail(ctx, ES_EINVAL, "es_llr_at_batch: null pointer");
     DeviceGuard g(ctx->device);
-    return es_launch_llr_at(ctx, y_dev, n_rows, T, B, row_dev, start_dev, start_stride, band_dev, pn_dev, variant, llr_dev,
-                            best_s_dev, score_dev, (hipStream_t)stream);
+    return es_launch_llr(ctx, y_dev, B, T, start_dev, {row_dev, n_rows, start_stride}, band_dev, pn_dev, variant, llr_dev,
+                         best_s_dev, score_dev, (hipStream_t)stream);
 }
 
 int es_header_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, int64_t B, const int32_t* row_dev,
@@ -443,8 +445,8 @@ int es_header_at_batch(es_ctx* ctx, const double* y_dev, int64_t n_rows, int T, 
     if (!y_dev || !band_dev || !hdr_pn_dev || !ok_dev || !val_dev || !score_dev)
         return fail(ctx, ES_EINVAL, "es_header_at_batch: null pointer");
     DeviceGuard g(ctx->device);
-    return es_launch_header_at(ctx, y_dev, n_rows, T, B, row_dev, start_dev, start_stride, band_dev, hdr_pn_dev, ok_dev, val_dev,
-                               score_dev, best_s_dev, (hipStream_t)stream);
+    return es_launch_header(ctx, y_dev, B, T, start_dev, {row_dev, n_rows, start_stride}, band_dev, hdr_pn_dev, ok_dev, val_dev,
+                            score_dev, best_s_dev, (hipStream_t)stream);
 }
 
 int es_scl_batch(es_ctx* ctx, const void* llr_dev, int dtype, int64_t B, int list_size,
@@ -462,12 +464,13 @@ int es_scl_batch(es_ctx* ctx, const void* llr_dev, int dtype, int64_t B, int lis
     if (!llr_dev || !hard_info_dev || !hard_ok_dev || !cand_info_dev || !cand_metric_dev || !cand_ok_dev || !ncand_dev)
         return fail(ctx, ES_EINVAL, "es_scl_batch: null pointer");
     DeviceGuard g(ctx->device);
+    const es_scl_io io{llr_dev, dtype, B, list_size, skip_if_hard_ok, hard_info_dev, hard_ok_dev, cand_info_dev, cand_metric_dev, cand_ok_dev, ncand_dev};
+    const hipStream_t st = (hipStream_t)stream;
     if (ctx->n_info != ES_POLAR_K && !ctx->d_wide_scratch)
         return fail(ctx, ES_EINVAL, "es_scl_batch: a code other than K = 448 runs on the lane-per-path kernel only, and this context has no scratch for it (list_size_max <= 32 and scl_lanes 1 never requested before es_reserve)");
     if (list_size > 32 || ctx->n_info != ES_POLAR_K)
-        return es_launch_scl_wide(ctx, llr_dev, dtype, B, list_size, skip_if_hard_ok, hard_info_dev, hard_ok_dev,
-                                  cand_info_dev, cand_metric_dev, cand_ok_dev, ncand_dev, (hipStream_t)stream);
-    int lp = 1; while (lp < list_size) lp <<= 1;              // the kernels are built for powers of two; any size runs on the next one
+        return es_launch_scl_wide(ctx, io, st);
+    const int lp = es_list_cap(list_size);                    // the kernels are built for powers of two; any size runs on the next one
     // Which mapping?  Measured on one MI355X (tools/mapping_sweep.py, round 3; milliseconds per launch at L = 8):
     //      B        one frame per wave   4 lanes per path   2 lanes per path   1 lane per path
     //    2 048            1.68                 2.02               2.89              3.46
@@ -482,8 +485,7 @@ int es_scl_batch(es_ctx* ctx, const void* llr_dev, int dtype, int64_t B, int lis
     const long long wide_min = (lp <= 8 ? 1024LL : lp == 16 ? 768LL : 256LL) * ctx->num_cu / 256;      // (L = 2: 4.3 against 4.6 ms at 32 768 frames, 6.9 against 8.1 at 65 536)
     const bool lane_auto = ctx->scl_lanes == 0 && ctx->scl_multi < 0 && ctx->d_wide_scratch && lp >= 2 && wide_waves >= wide_min;
     if ((ctx->scl_lanes == 1 && ctx->scl_multi != 0) || lane_auto)
-        return es_launch_scl_wide(ctx, llr_dev, dtype, B, list_size, skip_if_hard_ok, hard_info_dev, hard_ok_dev,
-                                  cand_info_dev, cand_metric_dev, cand_ok_dev, ncand_dev, (hipStream_t)stream);
+        return es_launch_scl_wide(ctx, io, st);
     if (lp <= 32) {
         // Several frames per wave (es_scl_multi.hip, 16/L frames per wave at four lanes per path) against one frame per wave: the
         // break-even is ~3 000 frames for L <= 8 (1.5 of the former's waves per SIMD at L = 8), ~1 500 frames for L = 16, ~512 for L = 32
@@ -491,12 +493,9 @@ int es_scl_batch(es_ctx* ctx, const void* llr_dev, int dtype, int64_t B, int lis
         // blocks -- wins as soon as the batch exceeds one wave per SIMD).
         const bool fits = lp <= 8 ? B >= 12LL * ctx->num_cu : B >= (lp == 16 ? 6LL : 2LL) * ctx->num_cu + (lp == 32);
         const bool multi = ctx->scl_multi == 1 || (ctx->scl_multi < 0 && fits);
-        if (multi)
-            return es_launch_scl_multi(ctx, llr_dev, dtype, B, list_size, skip_if_hard_ok, hard_info_dev, hard_ok_dev,
-                                       cand_info_dev, cand_metric_dev, cand_ok_dev, ncand_dev, (hipStream_t)stream);
+        if (multi) return es_launch_scl_multi(ctx, io, st);
     }
-    return es_launch_scl(ctx, llr_dev, dtype, B, list_size, skip_if_hard_ok, hard_info_dev, hard_ok_dev,
-                         cand_info_dev, cand_metric_dev, cand_ok_dev, ncand_dev, (hipStream_t)stream);
+    return es_launch_scl(ctx, io, st);
 }
 
 int es_schedule_batch(es_ctx* ctx, const uint8_t* aes_key16_host, const uint8_t* band_key32_host, const uint32_t* ctr_dev,

@@ -73,6 +73,23 @@ struct es_ctx {
     } while (0)
 
 #if defined(__HIPCC__)
+/* Grid of a launch whose blocks stride over the items: a block per `per_block` items, at most `cap_blocks` (each launcher's own multiple of
+ * num_cu, chosen for its kernel). */
+static inline unsigned es_grid(long long items, long long per_block, long long cap_blocks)
+{
+    const long long blocks = (items + per_block - 1) / per_block;
+    return (unsigned)(blocks < cap_blocks ? blocks : cap_blocks);
+}
+/* The one way a kernel is launched and a failed launch reported (ctx->err as ES_HIP_CHECK words it). */
+template <typename... P, typename... A>
+__attribute__((always_inline)) static inline int es_launch(es_ctx* ctx, void (*kernel)(P...), unsigned grid, unsigned block, size_t lds,
+                                                            hipStream_t st, A&&... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, std::forward<A>(args)...);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    return ES_OK;
+}
+
 /* Inclusive prefix sum over the 64 lanes of a wave on the data-parallel primitives (row_shr 1, 2, 4, 8 inside the rows of 16, then the two
  * row broadcasts): six dependent vector adds of a few cycles each, where six __shfl_up were six LDS-crossbar round trips (~100 cycles each).
  * Lanes without a source keep the `old` operand, 0. */
@@ -109,6 +126,15 @@ static inline int es_list_cap(int lmax) { int c = 1; while (c < lmax) c <<= 1; r
 int es_slab_enter(es_ctx* ctx, int domain, int shape, bool shareable, hipStream_t st);
 int es_slab_leave(es_ctx* ctx, int domain, int shape, bool shareable, hipStream_t st);
 
+/* What a list-decoder launch reads and writes: es_scl_batch fills it once, after validation (L = the caller's list size). */
+struct es_scl_io {
+    const void* llr; int dtype; int64_t B; int L; int skip_if_hard_ok;
+    uint8_t* hard_info; uint8_t* hard_ok; uint8_t* cand_info; double* cand_metric; uint8_t* cand_ok; int32_t* ncand;
+};
+/* Which row and sample record i of a demodulator / header launch reads.  {nullptr, 0, 1}: plain, row i from start[i].  n_rows >= 1
+ * (the *_at entry points): row row[i] (NULL = i) of n_rows, from start[i * start_stride]. */
+struct es_rec_at { const int32_t* row; int64_t n_rows; int start_stride; };
+
 /* launchers implemented in the kernel translation units */
 size_t es_scl_scratch_bytes(const es_ctx* ctx);
 size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, long long* lanes_out);
@@ -116,18 +142,10 @@ size_t es_scl_multi_scratch_bytes(const es_ctx* ctx);
 #define ES_CURSOR_RING 1024
 #define ES_CURSOR_CAPTURED 256                                   /* of them: set aside for launches recorded into stream captures (never reused) */
 int es_cursor_next(es_ctx* ctx, hipStream_t st, int** cursor);   /* a frame counter for one launch on `st` (es_api.hip) */
-int es_launch_scl_multi(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                        uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                        uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
-int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                       uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                       uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
-int es_launch_scl_wide_large(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,   /* L = 257..1024 (es_scl_wide_large.hip) */
-                             uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                             uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
-int es_launch_scl(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                  uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                  uint8_t* cand_ok, int32_t* ncand, hipStream_t st);
+int es_launch_scl_multi(es_ctx* ctx, const es_scl_io& io, hipStream_t st);
+int es_launch_scl_wide(es_ctx* ctx, const es_scl_io& io, hipStream_t st);
+int es_launch_scl_wide_large(es_ctx* ctx, const es_scl_io& io, hipStream_t st);   /* L = 257..1024 (es_scl_wide_large.hip) */
+int es_launch_scl(es_ctx* ctx, const es_scl_io& io, hipStream_t st);
 int es_launch_softplus(es_ctx* ctx, const double* t, int64_t n, double* out, hipStream_t st);
 int es_launch_polar_f_dev(es_ctx* ctx, const double* a, const double* b, int64_t n, double* out, int* bad, hipStream_t st);
 int es_launch_polar_encode(es_ctx* ctx, const uint8_t* info, int64_t B, uint8_t* code, hipStream_t st);
@@ -142,7 +160,7 @@ int es_launch_xcorr(es_ctx* ctx, const double* y, int64_t B, int T, const uint8_
                     hipStream_t st);
 int es_launch_pick(es_ctx* ctx, const double* corr, int64_t B, int n_lags, double* thr, int32_t* peaks,
                    int32_t* npeaks, hipStream_t st);
-int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start,
+int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at,
                   const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s,
                   float* score, hipStream_t st);
 
@@ -174,13 +192,7 @@ int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const in
 int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
                    int64_t rows, int T, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
                    uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
-int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const uint8_t* band,
+int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
-int es_launch_llr_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
-                     int start_stride, const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s, float* score,
-                     hipStream_t st);
-int es_launch_header_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
-                        int start_stride, const uint8_t* band, const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score,
-                        int32_t* best_s, hipStream_t st);
 
 #endif

@@ -214,32 +214,21 @@ __global__ __launch_bounds__(256) void es_plan_kernel(const int32_t* __restrict_
     }
 }
 
-long long grid_for(const es_ctx* ctx, long long n)
-{
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    return blocks > cap ? cap : blocks;
-}
-
 }  // namespace
 
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
 {
     if (const int rc = es_ensure_sbox(ctx)) return rc;
-    hipLaunchKernelGGL(es_keyring_derive_kernel, dim3((unsigned)grid_for(ctx, N)), dim3(256), 0, st, master32, (long long)N,
-                       (const uint8_t*)ctx->d_sbox, ring);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_keyring_derive_kernel, es_grid(N, 256, ctx->num_cu * 8), 256, 0, st, master32, (long long)N,
+                     (const uint8_t*)ctx->d_sbox, ring);
 }
 
 int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t n,
                              uint8_t* pn_rows, uint8_t* band, hipStream_t st)
 {
     if (const int rc = es_ensure_sbox(ctx)) return rc;
-    hipLaunchKernelGGL(es_schedule_keyed_kernel, dim3((unsigned)grid_for(ctx, n)), dim3(256), 0, st, ring, (long long)N, key, ctr,
-                       (long long)n, (const uint8_t*)ctx->d_sbox, pn_rows, band);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_schedule_keyed_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, key, ctr,
+                     (long long)n, (const uint8_t*)ctx->d_sbox, pn_rows, band);
 }
 
 int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
@@ -247,8 +236,6 @@ int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, con
                    uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st)
 {
     const long long pairs = (long long)N * rows;                                      // one wave each, four waves per block
-    hipLaunchKernelGGL(es_plan_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, peaks, npeaks, rowband, hdr_base,
-                       (long long)rows, T, hdr_ok, hdr_lo16, (long long)P, hop, (long long)N, C, cand_slot, cand_ctr, count, looked);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_plan_kernel, (unsigned)((pairs + 3) / 4), 256, 0, st, peaks, npeaks, rowband, hdr_base,
+                     (long long)rows, T, hdr_ok, hdr_lo16, (long long)P, hop, (long long)N, C, cand_slot, cand_ctr, count, looked);
 }

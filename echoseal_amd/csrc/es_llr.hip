@@ -647,19 +647,19 @@ __global__ __launch_bounds__(64) void es_header_kernel(const double* __restrict_
 
 }  // namespace
 
-int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start,
+// The (MAXT, AT) instantiation of a kernel for the context's longest matched filter and the records' addressing.  MAXT: long filters
+// (fs_target other than 48 000) take 41 KB of LDS per wave.  AT: the peak-addressed forms (es_llr_at_batch / es_header_at_batch) run the
+// same kernels on the same grids, record i read at (row[i], start[i * stride]); plain addressing keeps its own instantiations.
+#define ES_BY_TAPS_AT(kernel, ctx, at)                                                                                      \
+    ((ctx)->max_ntaps <= ES_MAX_TAPS_FAST ? ((at).n_rows ? kernel<ES_MAX_TAPS_FAST, true> : kernel<ES_MAX_TAPS_FAST, false>) \
+                                          : ((at).n_rows ? kernel<ES_MAX_TAPS, true> : kernel<ES_MAX_TAPS, false>))
+
+int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at,
                   const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s,
                   float* score, hipStream_t st)
 {
-    long long blocks = (B + LW_WAVES - 1) / LW_WAVES;
-    const long long cap = (long long)ctx->num_cu * 64 / LW_WAVES;
-    if (blocks > cap) blocks = cap;
-    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS_FAST, false>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, nullptr, 0LL, 1);
-    else                                                                      // long matched filters (fs_target other than 48 000): 41 KB of LDS per wave
-        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS, false>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, nullptr, 0LL, 1);
+    const int rc = es_launch(ctx, ES_BY_TAPS_AT(es_llr_wave_kernel, ctx, at), es_grid(B, LW_WAVES, ctx->num_cu * 64 / LW_WAVES), 64 * LW_WAVES, 0, st,
+                             y, (long long)B, T, start, band, pn, variant, ctx->d_tables, llr, best_s, score, at.row, (long long)at.n_rows, at.start_stride);
 #ifdef ES_LLR_STAMPS
     {   // diagnostic build only: share of the phases, summed over the records of this launch
         unsigned long long h[16]; static const unsigned long long z[16] = {0};
@@ -671,57 +671,12 @@ int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t*
         fprintf(stderr, "\n");
     }
 #endif
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return rc;
 }
 
-int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const uint8_t* band,
+int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st)
 {
-    long long blocks = B;
-    const long long cap = (long long)ctx->num_cu * 32;
-    if (blocks > cap) blocks = cap;
-    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS_FAST, false>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s, nullptr, 0LL, 1);
-    else
-        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS, false>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s, nullptr, 0LL, 1);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
-}
-
-// The peak-addressed forms (es_llr_at_batch / es_header_at_batch): the same kernels and grids, record i read at (row[i], start[i * stride]).
-int es_launch_llr_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
-                     int start_stride, const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s, float* score,
-                     hipStream_t st)
-{
-    long long blocks = (B + LW_WAVES - 1) / LW_WAVES;
-    const long long cap = (long long)ctx->num_cu * 64 / LW_WAVES;
-    if (blocks > cap) blocks = cap;
-    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS_FAST, true>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, row, (long long)n_rows, start_stride);
-    else
-        hipLaunchKernelGGL((es_llr_wave_kernel<ES_MAX_TAPS, true>), dim3((unsigned)blocks), dim3(64 * LW_WAVES), 0, st, y, (long long)B, T,
-                           start, band, pn, variant, ctx->d_tables, llr, best_s, score, row, (long long)n_rows, start_stride);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
-}
-
-int es_launch_header_at(es_ctx* ctx, const double* y, int64_t n_rows, int T, int64_t B, const int32_t* row, const int32_t* start,
-                        int start_stride, const uint8_t* band, const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score,
-                        int32_t* best_s, hipStream_t st)
-{
-    long long blocks = B;
-    const long long cap = (long long)ctx->num_cu * 32;
-    if (blocks > cap) blocks = cap;
-    if (ctx->max_ntaps <= ES_MAX_TAPS_FAST)
-        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS_FAST, true>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s, row, (long long)n_rows, start_stride);
-    else
-        hipLaunchKernelGGL((es_header_kernel<ES_MAX_TAPS, true>), dim3((unsigned)blocks), dim3(64), 0, st, y, (long long)B, T, start, band,
-                           hdr_pn, ctx->d_tables, ok, val, score, best_s, row, (long long)n_rows, start_stride);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, ES_BY_TAPS_AT(es_header_kernel, ctx, at), es_grid(B, 1, ctx->num_cu * 32), 64, 0, st,
+                     y, (long long)B, T, start, band, hdr_pn, ctx->d_tables, ok, val, score, best_s, at.row, (long long)at.n_rows, at.start_stride);
 }

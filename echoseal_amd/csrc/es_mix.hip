@@ -270,22 +270,13 @@ int es_launch_mix(es_ctx* ctx, const float* x, int64_t R, int64_t n, int block, 
     // one wave per block: the reference's own block length, rows and pointers that allow 16-byte accesses
     if (block == 1024 && n % 4 == 0 && n >= 1024 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0) {
         const long long nfull = n / 1024;
-        long long wg = (R * nfull + 3) / 4;
-        if (wg > cap) wg = cap;
-        hipLaunchKernelGGL(es_mix_wave_kernel, dim3((unsigned)wg), dim3(MIX_THREADS), 0, st, x, (long long)R, (long long)n, nfull, chips,
-                           (long long)chips_stride, (const long long*)chip_off, alpha, floor_lin, out, scale_out, nblk);
-        ES_HIP_CHECK(ctx, hipGetLastError());
+        const int rc = es_launch(ctx, es_mix_wave_kernel, es_grid(R * nfull, 4, cap), MIX_THREADS, 0, st, x, (long long)R, (long long)n, nfull, chips,
+                                 (long long)chips_stride, (const long long*)chip_off, alpha, floor_lin, out, scale_out, nblk);
+        if (rc != ES_OK) return rc;
         b_first = nfull; b_count = nblk - nfull;                              // the short last block of each row, if any
         if (b_count == 0) return ES_OK;
     }
-    long long wg = R * b_count;
-    if (wg > cap) wg = cap;
-    if (block <= MIX_CHUNK)
-        hipLaunchKernelGGL(es_mix_block_kernel<true>, dim3((unsigned)wg), dim3(MIX_THREADS), 0, st, x, (long long)R, (long long)n, (long long)block,
-                           b_first, b_count, chips, (long long)chips_stride, (const long long*)chip_off, alpha, floor_lin, out, scale_out, nblk);
-    else
-        hipLaunchKernelGGL(es_mix_block_kernel<false>, dim3((unsigned)wg), dim3(MIX_THREADS), 0, st, x, (long long)R, (long long)n, (long long)block,
-                           b_first, b_count, chips, (long long)chips_stride, (const long long*)chip_off, alpha, floor_lin, out, scale_out, nblk);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, block <= MIX_CHUNK ? es_mix_block_kernel<true> : es_mix_block_kernel<false>, es_grid(R * b_count, 1, cap), MIX_THREADS, 0, st,
+                     x, (long long)R, (long long)n, (long long)block, b_first, b_count, chips, (long long)chips_stride, (const long long*)chip_off,
+                     alpha, floor_lin, out, scale_out, nblk);
 }

@@ -35,15 +35,10 @@ __global__ __launch_bounds__(256) void es_resample_kernel(const T* __restrict__ 
 int es_launch_resample(es_ctx* ctx, const void* x, int dtype, int64_t B, int64_t n_x, const void* h_tf, int hpp, int up, int down,
                        int64_t y0, int64_t n_out, void* out, hipStream_t st)
 {
-    long long blocks = (B * n_out + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 32;
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = es_grid(B * n_out, 256, ctx->num_cu * 32);
     if (dtype == ES_DTYPE_F32)
-        hipLaunchKernelGGL(es_resample_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (long long)B,
-                           (long long)n_x, (const float*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (float*)out);
-    else
-        hipLaunchKernelGGL(es_resample_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)x, (long long)B,
-                           (long long)n_x, (const double*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (double*)out);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+        return es_launch(ctx, es_resample_kernel<float>, blocks, 256, 0, st, (const float*)x, (long long)B,
+                         (long long)n_x, (const float*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (float*)out);
+    return es_launch(ctx, es_resample_kernel<double>, blocks, 256, 0, st, (const double*)x, (long long)B,
+                     (long long)n_x, (const double*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (double*)out);
 }

@@ -132,11 +132,6 @@ int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* ban
     host_sha256_compress(k.ipad, pad);
     std::memset(pad, 0x5c, 64); for (int i = 0; i < 32; ++i) pad[i] ^= band_key32[i];
     host_sha256_compress(k.opad, pad);
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_schedule_kernel, dim3((unsigned)blocks), dim3(256), 0, st, k, ctx->d_sbox, ctr_dev, ctr0, (long long)n,
-                       pn_rows, band);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_schedule_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, k, ctx->d_sbox, ctr_dev, ctr0, (long long)n,
+                     pn_rows, band);
 }

@@ -662,8 +662,7 @@ int launch_scl(es_ctx* ctx, const SclArgs& a0, int64_t B, hipStream_t st)
     a.dbg = dbg;
 #endif
     { const int rc = es_slab_enter(ctx, 0, 0x100 | L, false, st); if (rc) return rc; }     // slab indexed by block: never shared between streams
-    hipLaunchKernelGGL(es_scl_kernel<L>, dim3((unsigned)blocks), dim3(64 * WPB), 0, st, a);
-    ES_HIP_CHECK(ctx, hipGetLastError());
+    { const int rc = es_launch(ctx, es_scl_kernel<L>, (unsigned)blocks, 64 * WPB, 0, st, a); if (rc) return rc; }
     { const int rc = es_slab_leave(ctx, 0, 0x100 | L, false, st); if (rc) return rc; }
 #ifdef ES_SCL_STAMPS
     {   // diagnostic build only: print the per-segment cycle shares of the first frames
@@ -695,20 +694,11 @@ size_t es_scl_scratch_bytes(const es_ctx* ctx)
     return need;
 }
 
-int es_launch_scl(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                  uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                  uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+int es_launch_scl(es_ctx* ctx, const es_scl_io& io, hipStream_t st)
 {
-    SclArgs a{};
-    a.dbg = nullptr;
-    a.llr = llr; a.is_f64 = (dtype == ES_DTYPE_F64); a.B = B;
-    a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
-    a.hard_info = hard_info; a.hard_ok = hard_ok; a.cand_info = cand_info;
-    a.cand_metric = cand_metric; a.cand_ok = cand_ok; a.ncand = ncand;
-    a.skip_if_hard_ok = skip_if_hard_ok;
-    a.lsz = L;
-    int LP = 1; while (LP < L) LP <<= 1;                  // kernel capacity: the next power of two
-    switch (LP) {
+    const SclArgs a = scl_args(ctx, io);
+    const int64_t B = io.B;
+    switch (es_list_cap(io.L)) {                          // kernel capacity: the next power of two
         case 1:  return launch_scl<1>(ctx, a, B, st);
         case 2:  return launch_scl<2>(ctx, a, B, st);
         case 4:  return launch_scl<4>(ctx, a, B, st);
@@ -721,19 +711,10 @@ int es_launch_scl(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int
 
 int es_launch_softplus(es_ctx* ctx, const double* t, int64_t n, double* out, hipStream_t st)
 {
-    long long blocks = (n + 255) / 256;
-    if (blocks > (long long)ctx->num_cu * 16) blocks = (long long)ctx->num_cu * 16;
-    hipLaunchKernelGGL(es_softplus_kernel, dim3((unsigned)blocks), dim3(256), 0, st, t, (long long)n, ctx->d_exp_tab, out);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_softplus_kernel, es_grid(n, 256, ctx->num_cu * 16), 256, 0, st, t, (long long)n, ctx->d_exp_tab, out);
 }
 
 int es_launch_polar_encode(es_ctx* ctx, const uint8_t* info, int64_t B, uint8_t* code, hipStream_t st)
 {
-    long long blocks = (B + 3) / 4;
-    if (blocks > (long long)ctx->num_cu * 8) blocks = (long long)ctx->num_cu * 8;
-    hipLaunchKernelGGL(es_polar_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, st, info,
-                       (long long)B, ctx->d_data_pos, code);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_polar_encode_kernel, es_grid(B, 4, ctx->num_cu * 8), 256, 0, st, info, (long long)B, ctx->d_data_pos, code);
 }

@@ -27,6 +27,19 @@ struct SclArgs {
     int lsz;                                  // the caller's list size (<= the kernel's template capacity L): paths kept per sort, row stride of the outputs
 };
 
+// What every launch of es_scl.hip / es_scl_multi.hip passes alike; the launchers add their slab.
+inline SclArgs scl_args(const es_ctx* ctx, const es_scl_io& io)
+{
+    SclArgs a{};
+    a.llr = io.llr; a.is_f64 = (io.dtype == ES_DTYPE_F64); a.B = io.B;
+    a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
+    a.hard_info = io.hard_info; a.hard_ok = io.hard_ok; a.cand_info = io.cand_info;
+    a.cand_metric = io.cand_metric; a.cand_ok = io.cand_ok; a.ncand = io.ncand;
+    a.skip_if_hard_ok = io.skip_if_hard_ok;
+    a.lsz = io.L;
+    return a;
+}
+
 __device__ __forceinline__ uint64_t ptr_set(uint64_t p, int depth, int slot)
 {
     const int sh = 6 * (depth - 1);

@@ -574,8 +574,7 @@ int launch_multi(es_ctx* ctx, const SclArgs& a0, int64_t B, hipStream_t st)
     a.scratch = ctx->d_scl_scratch;
     a.slot_bits = ctx->d_slot_bits; a.n_slots = n_slots; a.slot_words = (n_slots + 31) / 32;
     { const int rc = es_slab_enter(ctx, 0, 0x200 | PP, true, st); if (rc) return rc; }      // slot stride depends on PP only
-    hipLaunchKernelGGL((es_scl_multi_kernel<L, PP>), dim3((unsigned)blocks), dim3(64 * MWPB), 0, st, a);
-    ES_HIP_CHECK(ctx, hipGetLastError());
+    { const int rc = es_launch(ctx, es_scl_multi_kernel<L, PP>, (unsigned)blocks, 64 * MWPB, 0, st, a); if (rc) return rc; }
     { const int rc = es_slab_leave(ctx, 0, 0x200 | PP, true, st); if (rc) return rc; }
     return ES_OK;
 }
@@ -588,19 +587,11 @@ size_t es_scl_multi_scratch_bytes(const es_ctx* ctx)
     return (size_t)ctx->num_cu * MMINW * MWPB * per_wave * sizeof(double);
 }
 
-int es_launch_scl_multi(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                        uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                        uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+int es_launch_scl_multi(es_ctx* ctx, const es_scl_io& io, hipStream_t st)
 {
-    SclArgs a{};
-    a.dbg = nullptr;
-    a.llr = llr; a.is_f64 = (dtype == ES_DTYPE_F64); a.B = B;
-    a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
-    a.hard_info = hard_info; a.hard_ok = hard_ok; a.cand_info = cand_info;
-    a.cand_metric = cand_metric; a.cand_ok = cand_ok; a.ncand = ncand;
-    a.skip_if_hard_ok = skip_if_hard_ok;
-    a.lsz = L;
-    int LP = 1; while (LP < L) LP <<= 1;                  // kernel capacity: the next power of two
+    const SclArgs a = scl_args(ctx, io);
+    const int64_t B = io.B;
+    const int LP = es_list_cap(io.L);                     // kernel capacity: the next power of two
     // lanes per path (es_set_option "scl_lanes": 2, 4, or 0 = choose): two lanes per path need fewer instructions per frame
     // (measured 2.15 M against 2.03 M frames/s at 65 536 frames) but a wave then carries 32/L frames and takes 1.6x as long, so
     // the choice falls on it once the batch gives every wave slot of the chip at least two such waves

@@ -1010,29 +1010,27 @@ int launch_wide(es_ctx* ctx, WideArgs a, int64_t B, hipStream_t st)
     if (a.slot_words > ctx->wide_slot_words) { ctx->err = "es_scl_batch: the lane-per-path slab has more slots than its bitmap"; return ES_EINVAL; }   // (never: es_create sizes both)
     constexpr int shape = 0x30000 | L;                               // slot stride depends on the block's lanes only (one tag per block size)
     { const int rc = es_slab_enter(ctx, 1, shape, true, st); if (rc) return rc; }
-    hipLaunchKernelGGL((es_scl_wide_kernel<L, LF, GK>), dim3((unsigned)blocks), dim3(L), lds, st, a);
-    ES_HIP_CHECK(ctx, hipGetLastError());
+    { const int rc = es_launch(ctx, es_scl_wide_kernel<L, LF, GK>, (unsigned)blocks, L, lds, st, a); if (rc) return rc; }
     { const int rc = es_slab_leave(ctx, 1, shape, true, st); if (rc) return rc; }
     return ES_OK;
 }
 
 // Arguments of a launch (and its frame counter, when the frames are drawn from one).
-int wide_args(es_ctx* ctx, WideArgs& a, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-              uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric, uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+int wide_args(es_ctx* ctx, WideArgs& a, const es_scl_io& io, hipStream_t st)
 {
     a = WideArgs{};
-    a.llr = llr; a.is_f64 = (dtype == ES_DTYPE_F64); a.B = B;
+    a.llr = io.llr; a.is_f64 = (io.dtype == ES_DTYPE_F64); a.B = io.B;
     a.frozen = ctx->frozen; a.data_pos = ctx->d_data_pos; a.exp_tab = ctx->d_exp_tab;
     a.alpha = reinterpret_cast<double*>(ctx->d_wide_scratch);
     a.aux = reinterpret_cast<unsigned char*>(ctx->d_wide_scratch) + (size_t)ctx->wide_lanes * N * sizeof(double);
-    a.hard_info = hard_info; a.hard_ok = hard_ok; a.cand_info = cand_info;
-    a.cand_metric = cand_metric; a.cand_ok = cand_ok; a.ncand = ncand;
-    a.skip_if_hard_ok = skip_if_hard_ok;
-    a.lsz = L;
+    a.hard_info = io.hard_info; a.hard_ok = io.hard_ok; a.cand_info = io.cand_info;
+    a.cand_metric = io.cand_metric; a.cand_ok = io.cand_ok; a.ncand = io.ncand;
+    a.skip_if_hard_ok = io.skip_if_hard_ok;
+    a.lsz = io.L;
     a.prio = ctx->scl_prio;
     a.n_info = ctx->n_info; a.info_bytes = (ctx->n_info - 8 + 7) / 8;
-    if (skip_if_hard_ok) {                                // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes, as they did in fixed groups)
-        if (B >= (1LL << 31) - (1LL << 24)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }   // (the counter runs past B by one draw per block)
+    if (io.skip_if_hard_ok) {                                // frames drawn from a counter: see the kernel (settled frames never ride along as idle lanes, as they did in fixed groups)
+        if (io.B >= (1LL << 31) - (1LL << 24)) { ctx->err = "es_scl_batch: batch too large for one launch"; return ES_EINVAL; }   // (the counter runs past B by one draw per block)
         const int rc = es_cursor_next(ctx, st, &a.cursor);
         if (rc) return rc;
         ES_HIP_CHECK(ctx, hipMemsetAsync(a.cursor, 0, sizeof(int), st));
@@ -1040,19 +1038,40 @@ int wide_args(es_ctx* ctx, WideArgs& a, const void* llr, int dtype, int64_t B, i
     return ES_OK;
 }
 
+// The instantiation for a list of L paths: its capacity is the next power of two (this translation unit's share of them).  GK: a code
+// other than the reference's own K = 448, on the run-time-K instantiations.
+template <bool GK>
+int launch_wide_for(es_ctx* ctx, const es_scl_io& io, hipStream_t st)
+{
+    WideArgs a;
+    { const int rc = wide_args(ctx, a, io, st); if (rc) return rc; }
+    switch (es_list_cap(io.L)) {
+#if ES_WIDE_LARGE_TU
+        case 512:  return launch_wide<512, 512, GK>(ctx, a, io.B, st);
+        case 1024: return launch_wide<1024, 1024, GK>(ctx, a, io.B, st);
+        default: ctx->err = "list_size must be in 1..1024"; return ES_EINVAL;
+#else
+        case 1:   return launch_wide<64, 1, GK>(ctx, a, io.B, st);
+        case 2:   return launch_wide<64, 2, GK>(ctx, a, io.B, st);
+        case 4:   return launch_wide<64, 4, GK>(ctx, a, io.B, st);
+        case 8:   return launch_wide<64, 8, GK>(ctx, a, io.B, st);
+        case 16:  return launch_wide<64, 16, GK>(ctx, a, io.B, st);
+        case 32:  return launch_wide<64, 32, GK>(ctx, a, io.B, st);
+        case 64:  return launch_wide<64, 64, GK>(ctx, a, io.B, st);
+        case 128: return launch_wide<128, 128, GK>(ctx, a, io.B, st);
+        case 256: return launch_wide<256, 256, GK>(ctx, a, io.B, st);
+        default: ctx->err = "list_size must be in 1..256"; return ES_EINVAL;
+#endif
+    }
+}
+
 #if ES_WIDE_LARGE_TU
 }  // namespace
 
 // Lists of 257..1024 paths (es_scl_wide_large.hip): capacities 512 and 1024, one block per CU.
-int es_launch_scl_wide_large(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                             uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                             uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+int es_launch_scl_wide_large(es_ctx* ctx, const es_scl_io& io, hipStream_t st)
 {
-    WideArgs a;
-    { const int rc = wide_args(ctx, a, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st); if (rc) return rc; }
-    const bool gk = ctx->n_info != KINFO;
-    if (L <= 512) return gk ? launch_wide<512, 512, true>(ctx, a, B, st) : launch_wide<512, 512>(ctx, a, B, st);
-    return gk ? launch_wide<1024, 1024, true>(ctx, a, B, st) : launch_wide<1024, 1024>(ctx, a, B, st);
+    return ctx->n_info != KINFO ? launch_wide_for<true>(ctx, io, st) : launch_wide_for<false>(ctx, io, st);
 }
 #else
 // Diagnostic: the list decoder's f as its hot loops evaluate it (es_softplus_dev.h, exp table at LDS address 0), for a test against the host.
@@ -1078,12 +1097,8 @@ __global__ __launch_bounds__(256) void es_polar_f_dev_kernel(const double* __res
 
 int es_launch_polar_f_dev(es_ctx* ctx, const double* a, const double* b, int64_t n, double* out, int* bad, hipStream_t st)
 {
-    long long blocks = (n + 255) / 256;
-    if (blocks > (long long)ctx->num_cu * 16) blocks = (long long)ctx->num_cu * 16;
-    hipLaunchKernelGGL(es_polar_f_dev_kernel, dim3((unsigned)blocks), dim3(256), ES_EXP_TAB_WORDS * sizeof(uint64_t), st,
-                       a, b, (long long)n, ctx->d_exp_tab, out, bad);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_polar_f_dev_kernel, es_grid(n, 256, ctx->num_cu * 16), 256, ES_EXP_TAB_WORDS * sizeof(uint64_t), st,
+                     a, b, (long long)n, ctx->d_exp_tab, out, bad);
 }
 
 // Lanes of this file's workgroups one CU holds at most, over the block sizes a context serves (the slab holds a slot per resident
@@ -1106,40 +1121,11 @@ size_t es_scl_wide_scratch_bytes(const es_ctx* ctx, long long* lanes_out)
     return (size_t)lanes * (N * sizeof(double) + (size_t)WIDE_AUX_PER_PATH);
 }
 
-int es_launch_scl_wide(es_ctx* ctx, const void* llr, int dtype, int64_t B, int L, int skip_if_hard_ok,
-                       uint8_t* hard_info, uint8_t* hard_ok, uint8_t* cand_info, double* cand_metric,
-                       uint8_t* cand_ok, int32_t* ncand, hipStream_t st)
+int es_launch_scl_wide(es_ctx* ctx, const es_scl_io& io, hipStream_t st)
 {
     if (!ctx->d_wide_scratch) { ctx->err = "es_scl_batch: this context has no scratch for the lane-per-path list decoder (list_size_max <= 32 and scl_lanes 1 never requested before es_reserve)"; return ES_EINVAL; }
-    if (L > ES_MAX_LIST || L < 1) { ctx->err = "list_size must be in 1..1024"; return ES_EINVAL; }
-    if (L > 256)                                          // capacities 512 and 1024: a translation unit of their own (es_scl_wide_large.hip)
-        return es_launch_scl_wide_large(ctx, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st);
-    WideArgs a;
-    { const int rc = wide_args(ctx, a, llr, dtype, B, L, skip_if_hard_ok, hard_info, hard_ok, cand_info, cand_metric, cand_ok, ncand, st); if (rc) return rc; }
-    int LP = 1; while (LP < L) LP <<= 1;                  // kernel capacity: the next power of two
-    if (ctx->n_info != KINFO) switch (LP) {               // a code other than the reference's own K = 448: the run-time-K instantiations
-        case 1:   return launch_wide<64, 1, true>(ctx, a, B, st);
-        case 2:   return launch_wide<64, 2, true>(ctx, a, B, st);
-        case 4:   return launch_wide<64, 4, true>(ctx, a, B, st);
-        case 8:   return launch_wide<64, 8, true>(ctx, a, B, st);
-        case 16:  return launch_wide<64, 16, true>(ctx, a, B, st);
-        case 32:  return launch_wide<64, 32, true>(ctx, a, B, st);
-        case 64:  return launch_wide<64, 64, true>(ctx, a, B, st);
-        case 128: return launch_wide<128, 128, true>(ctx, a, B, st);
-        case 256: return launch_wide<256, 256, true>(ctx, a, B, st);
-        default: ctx->err = "list_size must be in 1..256"; return ES_EINVAL;
-    }
-    switch (LP) {
-        case 1:   return launch_wide<64, 1>(ctx, a, B, st);
-        case 2:   return launch_wide<64, 2>(ctx, a, B, st);
-        case 4:   return launch_wide<64, 4>(ctx, a, B, st);
-        case 8:   return launch_wide<64, 8>(ctx, a, B, st);
-        case 16:  return launch_wide<64, 16>(ctx, a, B, st);
-        case 32:  return launch_wide<64, 32>(ctx, a, B, st);
-        case 64:  return launch_wide<64, 64>(ctx, a, B, st);
-        case 128: return launch_wide<128, 128>(ctx, a, B, st);
-        case 256: return launch_wide<256, 256>(ctx, a, B, st);
-        default: ctx->err = "list_size must be in 1..256"; return ES_EINVAL;
-    }
+    if (io.L > ES_MAX_LIST || io.L < 1) { ctx->err = "list_size must be in 1..1024"; return ES_EINVAL; }
+    if (io.L > 256) return es_launch_scl_wide_large(ctx, io, st);          // capacities 512 and 1024: a translation unit of their own (es_scl_wide_large.hip)
+    return ctx->n_info != KINFO ? launch_wide_for<true>(ctx, io, st) : launch_wide_for<false>(ctx, io, st);
 }
 #endif

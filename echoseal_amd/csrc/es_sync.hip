@@ -636,6 +636,9 @@ __global__ __launch_bounds__(NT) void es_pick_kernel(const double* __restrict__ 
 
 }  // namespace
 
+// the int16 or float32 instantiation of a band-pass kernel, by the frames' dtype
+#define ES_BPF_BY_DTYPE(kernel, dtype) ((dtype) == ES_DTYPE_I16 ? kernel<true> : kernel<false>)
+
 int es_launch_bpf(es_ctx* ctx, const void* frames, int dtype, int64_t B, int T, const uint8_t* band,
                   double* y, float* y32, hipStream_t st)
 {
@@ -643,35 +646,16 @@ int es_launch_bpf(es_ctx* ctx, const void* frames, int dtype, int64_t B, int T, 
     // the four-lanes-per-record kernel anyway: up to four such waves per SIMD
     if (B <= (long long)ctx->num_cu * 4 * 4 * BR_RECS / 4) {
         const unsigned blocks = (unsigned)((B + BR_RECS - 1) / BR_RECS);
-        if (dtype == ES_DTYPE_I16)
-            hipLaunchKernelGGL(es_bpf_row2_kernel<true>, dim3(blocks), dim3(128), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
-        else
-            hipLaunchKernelGGL(es_bpf_row2_kernel<false>, dim3(blocks), dim3(128), 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
-        ES_HIP_CHECK(ctx, hipGetLastError());
-        return ES_OK;
+        return es_launch(ctx, ES_BPF_BY_DTYPE(es_bpf_row2_kernel, dtype), blocks, 128, 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
     }
     if (B < 262144) {                               // four lanes per record: 4x the waves
         const long long per_block = (long long)BQ_RECS * BQ_WAVES;
         const unsigned blocks = (unsigned)((B + per_block - 1) / per_block);
-        if (dtype == ES_DTYPE_I16)
-            hipLaunchKernelGGL(es_bpf_quad_kernel<true>, dim3(blocks), dim3(64 * BQ_WAVES), 0, st, frames,
-                               (long long)B, T, band, ctx->d_tables, y, y32);
-        else
-            hipLaunchKernelGGL(es_bpf_quad_kernel<false>, dim3(blocks), dim3(64 * BQ_WAVES), 0, st, frames,
-                               (long long)B, T, band, ctx->d_tables, y, y32);
-        ES_HIP_CHECK(ctx, hipGetLastError());
-        return ES_OK;
+        return es_launch(ctx, ES_BPF_BY_DTYPE(es_bpf_quad_kernel, dtype), blocks, 64 * BQ_WAVES, 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
     }
     const long long recs_per_block = 64LL * BPF_WAVES;
     const unsigned blocks = (unsigned)((B + recs_per_block - 1) / recs_per_block);
-    if (dtype == ES_DTYPE_I16)
-        hipLaunchKernelGGL(es_bpf_kernel<true>, dim3(blocks), dim3(64 * BPF_WAVES), 0, st, frames,
-                           (long long)B, T, band, ctx->d_tables, y, y32);
-    else
-        hipLaunchKernelGGL(es_bpf_kernel<false>, dim3(blocks), dim3(64 * BPF_WAVES), 0, st, frames,
-                           (long long)B, T, band, ctx->d_tables, y, y32);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, ES_BPF_BY_DTYPE(es_bpf_kernel, dtype), blocks, 64 * BPF_WAVES, 0, st, frames, (long long)B, T, band, ctx->d_tables, y, y32);
 }
 
 
@@ -680,27 +664,16 @@ int es_launch_xcorr(es_ctx* ctx, const double* y, int64_t B, int T, const uint8_
 {
     const int n_lags = T - (ES_PRE_L - 1);
     const long long nseg = (n_lags + XC_SEG - 1) / XC_SEG;
-    long long blocks = (B * nseg + XC_WAVES - 1) / XC_WAVES;
-    const long long cap = (long long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_xcorr_kernel, dim3((unsigned)blocks), dim3(64 * XC_WAVES), 0, st, y, (long long)B,
-                       T, band, ctx->d_tables, corr);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_xcorr_kernel, es_grid(B * nseg, XC_WAVES, ctx->num_cu * 16), 64 * XC_WAVES, 0, st, y, (long long)B,
+                     T, band, ctx->d_tables, corr);
 }
 
 int es_launch_pick(es_ctx* ctx, const double* corr, int64_t B, int n_lags, double* thr, int32_t* peaks,
                    int32_t* npeaks, hipStream_t st)
 {
-    long long blocks = B;
-    const long long cap = (long long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = es_grid(B, 1, ctx->num_cu * 16);
     if (n_lags <= PK_LDS_N)
-        hipLaunchKernelGGL((es_pick_kernel<true, PK_THREADS>), dim3((unsigned)blocks), dim3(PK_THREADS), 0, st, corr,
-                           (long long)B, n_lags, thr, peaks, npeaks);
-    else                                              // long rows (recordings): one block per row, so make it a big one
-        hipLaunchKernelGGL((es_pick_kernel<false, 1024>), dim3((unsigned)blocks), dim3(1024), 0, st, corr,
-                           (long long)B, n_lags, thr, peaks, npeaks);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+        return es_launch(ctx, es_pick_kernel<true, PK_THREADS>, blocks, PK_THREADS, 0, st, corr, (long long)B, n_lags, thr, peaks, npeaks);
+    // long rows (recordings): one block per row, so make it a big one
+    return es_launch(ctx, es_pick_kernel<false, 1024>, blocks, 1024, 0, st, corr, (long long)B, n_lags, thr, peaks, npeaks);
 }

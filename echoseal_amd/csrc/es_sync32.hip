@@ -847,22 +847,10 @@ int es_launch_xcorr32(es_ctx* ctx, const float* y32, int64_t B, int T, const uin
     const bool win2k = !small && T == XC_T_WINDOW;              // config-3 windows: two waves per window, 17 lags per lane, compile-time bounds
     const int seg = small ? 64 * XC_R_SMALL : (win2k ? 64 * XC_R_WINDOW : XC_SEG);
     const long long nseg = (n_lags + seg - 1) / seg;
-    long long blocks = (B * nseg + XC_WAVES - 1) / XC_WAVES;
-    if (blocks > cap) blocks = cap;
-    if (small)
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R_SMALL, 0, false>), dim3((unsigned)blocks), dim3(64 * XC_WAVES), 0, st, y32,
-                           (long long)B, T, band, ctx->d_tables, corr32, FusedArgs{});
-    else if (win2k)
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R_WINDOW, XC_T_WINDOW, false>), dim3((unsigned)blocks), dim3(64 * XC_WAVES), 0, st, y32,
-                           (long long)B, T, band, ctx->d_tables, corr32, FusedArgs{});
-    else if (T == ES_FRAME_LEN)
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R, ES_FRAME_LEN, false>), dim3((unsigned)blocks), dim3(64 * XC_WAVES), 0, st, y32,
-                           (long long)B, T, band, ctx->d_tables, corr32, FusedArgs{});
-    else
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R, 0, false>), dim3((unsigned)blocks), dim3(64 * XC_WAVES), 0, st, y32,
-                           (long long)B, T, band, ctx->d_tables, corr32, FusedArgs{});
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    const auto kernel = small ? es_xcorr32_kernel<XC_R_SMALL, 0, false>
+                      : win2k ? es_xcorr32_kernel<XC_R_WINDOW, XC_T_WINDOW, false>
+                      : T == ES_FRAME_LEN ? es_xcorr32_kernel<XC_R, ES_FRAME_LEN, false> : es_xcorr32_kernel<XC_R, 0, false>;
+    return es_launch(ctx, kernel, es_grid(B * nseg, XC_WAVES, cap), 64 * XC_WAVES, 0, st, y32, (long long)B, T, band, ctx->d_tables, corr32, FusedArgs{});
 }
 
 int es_launch_pick_exact(es_ctx* ctx, const float* corr32, const double* y, int64_t B, int T, const uint8_t* band,
@@ -875,13 +863,8 @@ int es_launch_pick_exact(es_ctx* ctx, const float* corr32, const double* y, int6
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PW_WAVES * xf_lds_per_wave(0, PX_MAXN))));
         ctx->pick_attr_set = true;
     }
-    long long blocks = (B + PW_WAVES - 1) / PW_WAVES;
-    const long long cap = (long long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_pick_exact_wave_kernel, dim3((unsigned)blocks), dim3(64 * PW_WAVES), lds, st, corr32, (long long)B, T,
-                       band, ctx->d_tables, FusedArgs{y, thr, peaks, npeaks, flags});
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    return es_launch(ctx, es_pick_exact_wave_kernel, es_grid(B, PW_WAVES, ctx->num_cu * 16), 64 * PW_WAVES, lds, st, corr32, (long long)B, T,
+                     band, ctx->d_tables, FusedArgs{y, thr, peaks, npeaks, flags});
 }
 
 int es_launch_sync_fused(es_ctx* ctx, const float* y32, const double* y, int64_t B, int T, const uint8_t* band, double* thr,
@@ -894,19 +877,8 @@ int es_launch_sync_fused(es_ctx* ctx, const float* y32, const double* y, int64_t
     const long long nseg = (n_lags + 64 * R - 1) / (64 * R);
     if ((long long)B * nseg >= (1LL << 31)) { ctx->err = "es_sync_fused_batch: batch too large for one launch"; return ES_EINVAL; }
     const size_t lds = XF_WAVES * xf_lds_per_wave(64 * R + ES_PRE_L - 1 + 2, n_lags);
-    long long blocks = (B + XF_WAVES - 1) / XF_WAVES;
-    const long long cap = (long long)ctx->num_cu * 32;
-    if (blocks > cap) blocks = cap;
-    const FusedArgs fo{y, thr, peaks, npeaks, flags};
-    if (win2k)
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R_WINDOW, XC_T_WINDOW, true>), dim3((unsigned)blocks), dim3(64 * XF_WAVES), lds, st, y32,
-                           (long long)B, T, band, ctx->d_tables, (float*)nullptr, fo);
-    else if (T == ES_FRAME_LEN)
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R, ES_FRAME_LEN, true>), dim3((unsigned)blocks), dim3(64 * XF_WAVES), lds, st, y32,
-                           (long long)B, T, band, ctx->d_tables, (float*)nullptr, fo);
-    else
-        hipLaunchKernelGGL((es_xcorr32_kernel<XC_R, 0, true>), dim3((unsigned)blocks), dim3(64 * XF_WAVES), lds, st, y32,
-                           (long long)B, T, band, ctx->d_tables, (float*)nullptr, fo);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    const auto kernel = win2k ? es_xcorr32_kernel<XC_R_WINDOW, XC_T_WINDOW, true>
+                      : T == ES_FRAME_LEN ? es_xcorr32_kernel<XC_R, ES_FRAME_LEN, true> : es_xcorr32_kernel<XC_R, 0, true>;
+    return es_launch(ctx, kernel, es_grid(B, XF_WAVES, ctx->num_cu * 32), 64 * XF_WAVES, lds, st, y32, (long long)B, T, band, ctx->d_tables, (float*)nullptr,
+                     FusedArgs{y, thr, peaks, npeaks, flags});
 }

@@ -68,17 +68,11 @@ int es_launch_tx_frames(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows
 {
     if (!ctx->d_hdr_pn) ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_hdr_pn, 16));
     ES_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_hdr_pn, hdr_pn16, 16, hipMemcpyHostToDevice, st));
-    long long blocks = B;
     const long long cap = (long long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(es_tx_symbols_kernel, dim3((unsigned)blocks), dim3(256), 0, st, code, pn_rows, ctr, pre_bits,
+    int rc = es_launch(ctx, es_tx_symbols_kernel, es_grid(B, 1, cap), 256, 0, st, code, pn_rows, ctr, pre_bits,
                        ctx->d_hdr_pn, (long long)B, frames);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    const int rc = es_launch_bpf(ctx, frames, ES_DTYPE_F32, B, ES_FRAME_LEN, band, y_ws, nullptr, st);
     if (rc != ES_OK) return rc;
-    long long fb = (B + 3) / 4;
-    if (fb > cap) fb = cap;
-    hipLaunchKernelGGL(es_tx_finish_kernel, dim3((unsigned)fb), dim3(256), 0, st, y_ws, (long long)B, frames);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    return ES_OK;
+    rc = es_launch_bpf(ctx, frames, ES_DTYPE_F32, B, ES_FRAME_LEN, band, y_ws, nullptr, st);
+    if (rc != ES_OK) return rc;
+    return es_launch(ctx, es_tx_finish_kernel, es_grid(B, 4, cap), 256, 0, st, y_ws, (long long)B, frames);
 }

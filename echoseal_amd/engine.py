@@ -61,6 +61,9 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+_FRAME_DTYPES = {torch.int16: nat.ES_DTYPE_I16, torch.float32: nat.ES_DTYPE_F32}     # what the band-pass reads
+
+
 def _peak_start(start: str) -> None:
     if start != "peak":
         raise ValueError(f'start must be a tensor, None or "peak", not {start!r}')
@@ -184,18 +187,32 @@ class RxEngine:
             t = t.to(dtype)
         return t.to(self.device, non_blocking=True).contiguous()
 
-    # ------------------------------------------------------------------ sync stage
-    def bpf(self, frames: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
+    def _frames(self, frames: torch.Tensor):
+        """The records of a band-pass call, checked: -> (contiguous frames, their native dtype code, B, T)."""
         if frames.dim() != 2:
             raise ValueError("frames must be [B, T]")
-        if frames.dtype == torch.int16:
-            dt = nat.ES_DTYPE_I16
-        elif frames.dtype == torch.float32:
-            dt = nat.ES_DTYPE_F32
-        else:
+        dt = _FRAME_DTYPES.get(frames.dtype)
+        if dt is None:
             raise ValueError("frames must be float32 or int16")
-        frames = frames.contiguous()
-        B, T = frames.shape
+        return frames.contiguous(), dt, frames.shape[0], frames.shape[1]
+
+    def _peak_out(self, B: int, flags: bool = True):
+        """Outputs of a peak picker: thr, peaks (the kernels write whole rows, -1 = unused), npeaks, flags (None unless asked for)."""
+        dev = self.device
+        return (torch.empty(B, dtype=torch.float64, device=dev), torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=dev),
+                torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev) if flags else None)
+
+    def _llr_out(self, out: torch.Tensor | None, B: int) -> torch.Tensor:
+        """The demodulator's output rows: the caller's, checked, or new ones."""
+        if out is None:
+            return torch.empty((B, 1024), dtype=torch.float32, device=self.device)
+        if out.shape != (B, 1024) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [B, 1024] tensor")
+        return out
+
+    # ------------------------------------------------------------------ sync stage
+    def bpf(self, frames: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
+        frames, dt, B, T = self._frames(frames)
         y = torch.empty((B, T), dtype=torch.float64, device=self.device)
         nat.check(self._ctx, self._lib.es_bpf_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(y),
                                                     self._stream()), "es_bpf_batch")
@@ -203,16 +220,7 @@ class RxEngine:
 
     def bpf2(self, frames: torch.Tensor, band: torch.Tensor):
         """Band-pass with both outputs: y (float64) and y32 = (float)y."""
-        if frames.dim() != 2:
-            raise ValueError("frames must be [B, T]")
-        if frames.dtype == torch.int16:
-            dt = nat.ES_DTYPE_I16
-        elif frames.dtype == torch.float32:
-            dt = nat.ES_DTYPE_F32
-        else:
-            raise ValueError("frames must be float32 or int16")
-        frames = frames.contiguous()
-        B, T = frames.shape
+        frames, dt, B, T = self._frames(frames)
         y = torch.empty((B, T), dtype=torch.float64, device=self.device)
         y32 = torch.empty((B, T), dtype=torch.float32, device=self.device)
         nat.check(self._ctx, self._lib.es_bpf2_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(y), _ptr(y32),
@@ -229,10 +237,7 @@ class RxEngine:
     def pick_exact(self, corr32: torch.Tensor, y: torch.Tensor, band: torch.Tensor):
         """thr / peaks / npeaks identical to pick(xcorr(y)); also returns the per-record flags (reason codes 1..5, 0 = settled from the screen)."""
         B, T = y.shape
-        thr = torch.empty(B, dtype=torch.float64, device=self.device)
-        peaks = torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=self.device)     # the kernels write whole rows (-1 = unused)
-        npeaks = torch.empty(B, dtype=torch.int32, device=self.device)
-        flags = torch.empty(B, dtype=torch.uint8, device=self.device)
+        thr, peaks, npeaks, flags = self._peak_out(B)
         nat.check(self._ctx, self._lib.es_pick_exact_batch(self._ctx, _ptr(corr32), _ptr(y), B, T, _ptr(band), _ptr(thr),
                                                            _ptr(peaks), _ptr(npeaks), _ptr(flags), self._stream()),
                   "es_pick_exact_batch")
@@ -242,10 +247,7 @@ class RxEngine:
         """Correlation screen + exact threshold / peak picking in ONE kernel (the screen row never leaves LDS):
         -> (thr, peaks, npeaks, flags), identical to pick(xcorr(y))."""
         B, T = y.shape
-        thr = torch.empty(B, dtype=torch.float64, device=self.device)
-        peaks = torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=self.device)
-        npeaks = torch.empty(B, dtype=torch.int32, device=self.device)
-        flags = torch.empty(B, dtype=torch.uint8, device=self.device)
+        thr, peaks, npeaks, flags = self._peak_out(B)
         nat.check(self._ctx, self._lib.es_sync_fused_batch(self._ctx, _ptr(y32), _ptr(y), B, T, _ptr(band), _ptr(thr), _ptr(peaks),
                                                            _ptr(npeaks), _ptr(flags), self._stream()), "es_sync_fused_batch")
         return thr, peaks, npeaks, flags
@@ -254,22 +256,11 @@ class RxEngine:
               out: torch.Tensor | None = None):
         """bpf2 -> sync_fused -> llr (variant 0) in one library call (es_front_batch): -> (y, thr, peaks, npeaks, flags, llr).
         start="peak": the demodulator reads each record at its first detected peak (es_front_peak_batch; no peak = 0)."""
-        if frames.dim() != 2 or frames.dtype not in (torch.float32, torch.int16):
-            raise ValueError("frames must be float32 or int16 [B, T]")
-        frames = frames.contiguous()
-        B, T = frames.shape
-        dev = self.device
-        y = torch.empty((B, T), dtype=torch.float64, device=dev)
-        y32 = torch.empty((B, T), dtype=torch.float32, device=dev)
-        thr = torch.empty(B, dtype=torch.float64, device=dev)
-        peaks = torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=dev)
-        npeaks = torch.empty(B, dtype=torch.int32, device=dev)
-        flags = torch.empty(B, dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty((B, 1024), dtype=torch.float32, device=dev)
-        elif out.shape != (B, 1024) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [B, 1024] tensor")
-        dt = nat.ES_DTYPE_I16 if frames.dtype == torch.int16 else nat.ES_DTYPE_F32
+        frames, dt, B, T = self._frames(frames)
+        y = torch.empty((B, T), dtype=torch.float64, device=self.device)
+        y32 = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        thr, peaks, npeaks, flags = self._peak_out(B)
+        out = self._llr_out(out, B)
         if isinstance(start, str):
             _peak_start(start)
             nat.check(self._ctx, self._lib.es_front_peak_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(pn_rows), _ptr(y), _ptr(y32),
@@ -310,9 +301,7 @@ class RxEngine:
 
     def pick(self, corr: torch.Tensor):
         B, n = corr.shape
-        thr = torch.empty(B, dtype=torch.float64, device=self.device)
-        peaks = torch.empty((B, nat.ES_MAX_PEAKS), dtype=torch.int32, device=self.device)     # the kernels write whole rows (-1 = unused)
-        npeaks = torch.empty(B, dtype=torch.int32, device=self.device)
+        thr, peaks, npeaks, _ = self._peak_out(B, flags=False)
         nat.check(self._ctx, self._lib.es_pick_batch(self._ctx, _ptr(corr), B, n, _ptr(thr), _ptr(peaks),
                                                      _ptr(npeaks), self._stream()), "es_pick_batch")
         return thr, peaks, npeaks
@@ -358,10 +347,7 @@ class RxEngine:
             B, rows, st, stride = self._at(y, start, rows, peaks)
         else:
             B = y.shape[0]
-        if out is None:
-            out = torch.empty((B, 1024), dtype=torch.float32, device=self.device)
-        elif out.shape != (B, 1024) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [B, 1024] tensor")
+        out = self._llr_out(out, B)
         best_s = torch.empty(B, dtype=torch.int32, device=self.device) if want_diag else None
         score = torch.empty((B, 2), dtype=torch.float32, device=self.device) if want_diag else None
         if at:

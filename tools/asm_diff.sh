@@ -4,6 +4,9 @@
 # included, and compares whole lines.  Only the __hip_cuid_<hash> symbol (a hash of the source text) is masked.  For a refactor that must
 # not change a kernel: git worktree add /tmp/parent HEAD^ && tools/asm_diff.sh /tmp/parent .
 # OUT=dir keeps the .s files there (default: a fresh temporary directory); JOBS=n compiles n files at a time (default 8).
+# BY_SYMBOL=1: a file that differs as a whole is compared again symbol by symbol -- each function's lines, its kernel descriptor and its
+# metadata entry under its name, the rest of the file in place, the function numbers in local labels (.LBB3_7) masked -- and passes as
+# "same per symbol" if only the order in which the compiler emitted the functions changed (a host-side change can move an instantiation).
 set -e
 old=$(realpath "$1"); new=$(realpath "$2"); shift 2
 out=${OUT:-$(mktemp -d)}; mkdir -p "$out/old" "$out/new"
@@ -20,6 +23,21 @@ for side in old new; do
   done
 done | xargs -P "${JOBS:-8}" -d '\n' -n 1 sh -c
 
+# by_symbol FILE: every line under the symbol it belongs to, symbols sorted by name, lines of one symbol in file order
+by_symbol() {
+  sed -E 's/\.L(BB|JTI|CPI)[0-9]+_/.L\1_/g; s/\.Lfunc_(begin|end)[0-9]+/.Lfunc_\1/g; s/([= ])BB[0-9]+_/\1BB_/g' "$1" | awk '
+    function flush(   i) { for (i = 0; i < n; ++i) print name "\t" buf[i]; n = 0; name = "" }
+    /^\t\.text$/ { next }                                                       # (a bare section switch: present or not by what follows)
+    /^\t\.p2alignl|^\t\.section\t\.AMDGPU\.gpr_maximums/ { sym = "~tail" }       # after the last function: padding, maxima, objects
+    /^\t\.section\t\.text\./ { sym = $2; sub(/^\.text\./, "", sym); sub(/,.*/, "", sym) }
+    /; -- Begin function / { sym = $NF }
+    /^amdhsa\.kernels:/ { print "~meta\t" $0; meta = 1; next }
+    meta && /^  - \./ { flush() }                                               # a kernel entry of the metadata: filed under its .name
+    meta && /^amdhsa\.target:/ { flush(); meta = 0; sym = "~meta" }
+    meta { buf[n++] = $0; if ($1 == ".name:") name = $2; next }
+    { print sym "\t" $0 }' | sort -s -t "$(printf '\t')" -k1,1
+}
+
 status=0
 for f in $srcs; do
   for side in old new; do
@@ -27,6 +45,9 @@ for f in $srcs; do
   done
   if cmp -s "$out/old/${f%.hip}.masked" "$out/new/${f%.hip}.masked"; then
     echo "$f: identical ($(wc -l < "$out/new/${f%.hip}.s") lines)"
+  elif [ -n "$BY_SYMBOL" ] && by_symbol "$out/old/${f%.hip}.masked" > "$out/old/${f%.hip}.sorted" && by_symbol "$out/new/${f%.hip}.masked" > "$out/new/${f%.hip}.sorted" &&
+       cmp -s "$out/old/${f%.hip}.sorted" "$out/new/${f%.hip}.sorted"; then
+    echo "$f: same per symbol, functions emitted in another order ($(grep -c -- '-- Begin function' "$out/new/${f%.hip}.s") functions)"
   else
     status=1
     echo "$f: DIFFERS in"
