@@ -389,6 +389,32 @@ int es_sync_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int
     return es_pick_batch(ctx, corr, B, n_lags, thr_dev, peaks_dev, npeaks_dev, stream);
 }
 
+int es_sync_ragged_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T, const int32_t* len_dev,
+                         const uint8_t* band_dev, double* y_dev, double* corr_dev, double* thr_dev,
+                         int32_t* peaks_dev, int32_t* npeaks_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (T < ES_PRE_L) return fail(ctx, ES_EINVAL, "es_sync_ragged_batch: rows shorter than the 63-chip template");
+    if (B <= 0) return B == 0 ? ES_OK : fail(ctx, ES_EINVAL, "es_sync_ragged_batch: negative batch");
+    if (dtype != ES_DTYPE_F32 && dtype != ES_DTYPE_I16) return fail(ctx, ES_EINVAL, "es_sync_ragged_batch: dtype must be f32 or i16");
+    if (!frames_dev || !len_dev || !band_dev || !y_dev || !thr_dev || !peaks_dev || !npeaks_dev)
+        return fail(ctx, ES_EINVAL, "es_sync_ragged_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    double* corr = corr_dev;
+    if (!corr) {                                          // the workspace of es_sync_batch, sized for rows of T
+        const size_t need = (size_t)B * (T - (ES_PRE_L - 1)) * sizeof(double);
+        if (need > ctx->ws_corr_bytes) { const int rc0 = es_reserve(ctx, B, T); if (rc0) return rc0; }
+        corr = ctx->d_ws_corr;
+    }
+    // the band-pass runs every stored row to T: it is causal with zero initial state, so y[i][0 : len[i]] is the record's own output
+    // whatever the padding holds; correlation and pick then stop at each record's end
+    int rc = es_launch_bpf(ctx, frames_dev, dtype, B, T, band_dev, y_dev, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = es_launch_xcorr_ragged(ctx, y_dev, B, T, len_dev, band_dev, corr, (hipStream_t)stream);
+    if (rc) return rc;
+    return es_launch_pick_ragged(ctx, corr, B, T, len_dev, thr_dev, peaks_dev, npeaks_dev, (hipStream_t)stream);
+}
+
 int es_llr_batch(es_ctx* ctx, const double* y_dev, int64_t B, int T, const int32_t* start_dev,
                  const uint8_t* band_dev, const uint8_t* pn_dev, int variant, float* llr_dev,
                  int32_t* best_s_dev, float* score_dev, void* stream)
@@ -722,6 +748,24 @@ int es_plan_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_d
     DeviceGuard g(ctx->device);
     return es_launch_plan(ctx, peaks_dev, npeaks_dev, rowband_dev, hdr_base_dev, rows, T, hdr_ok_dev, hdr_lo16_dev, P, hop_dev, N, C,
                           cand_slot_dev, cand_ctr_dev, count_dev, looked_dev, (hipStream_t)stream);
+}
+
+int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev,
+                         const int32_t* hdr_base_dev, int64_t rows, const int32_t* len_dev, int T_max, const uint8_t* hdr_ok_dev,
+                         const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N, int C, uint8_t* cand_slot_dev,
+                         uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (rows < 0 || N < 0 || P < 0 || T_max < 0) return fail(ctx, ES_EINVAL, "es_plan_ragged_batch: negative size");
+    if (rows == 0 || N == 0) return ES_OK;
+    if (rows * N > ((int64_t)1 << 31)) return fail(ctx, ES_EINVAL, "es_plan_ragged_batch: more than 2^31 (key, row) pairs in one call");
+    // the widest window ends at round((T_max - 1215) / 1215) + 200: the hop table must reach it
+    if (C < (T_max + ES_FRAME_LEN - 1) / ES_FRAME_LEN + 201) return fail(ctx, ES_EINVAL, "es_plan_ragged_batch: hop table narrower than ceil(T_max / 1215) + 201 counters");
+    if (!peaks_dev || !npeaks_dev || !rowband_dev || !hdr_base_dev || !len_dev || !hop_dev || !cand_slot_dev || !cand_ctr_dev || !count_dev ||
+        (P > 0 && (!hdr_ok_dev || !hdr_lo16_dev))) return fail(ctx, ES_EINVAL, "es_plan_ragged_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_plan_ragged(ctx, peaks_dev, npeaks_dev, rowband_dev, hdr_base_dev, rows, len_dev, hdr_ok_dev, hdr_lo16_dev, P, hop_dev,
+                                 N, C, cand_slot_dev, cand_ctr_dev, count_dev, looked_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -160,6 +160,11 @@ int es_launch_xcorr(es_ctx* ctx, const double* y, int64_t B, int T, const uint8_
                     hipStream_t st);
 int es_launch_pick(es_ctx* ctx, const double* corr, int64_t B, int n_lags, double* thr, int32_t* peaks,
                    int32_t* npeaks, hipStream_t st);
+/* records of unequal length in rows of T: len [B] samples of each record, clamped to [0, T] on the device (es_sync.hip) */
+int es_launch_xcorr_ragged(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* len, const uint8_t* band, double* corr,
+                           hipStream_t st);
+int es_launch_pick_ragged(es_ctx* ctx, const double* corr, int64_t B, int T, const int32_t* len, double* thr, int32_t* peaks,
+                          int32_t* npeaks, hipStream_t st);
 int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at,
                   const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s,
                   float* score, hipStream_t st);
@@ -192,6 +197,9 @@ int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const in
 int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
                    int64_t rows, int T, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
                    uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
+int es_launch_plan_ragged(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
+                          int64_t rows, const int32_t* len, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop,
+                          int64_t N, int C, uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 

@@ -325,82 +325,12 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
 // FP64 VALU work per lag: 63 FMA + ~7 for the energy + sqrt/div; no MFMA (no shared operand).
 constexpr int XC_NS = XC_SEG + ES_PRE_L - 1;       // samples per wave: 1278
 
-__global__ __launch_bounds__(64 * XC_WAVES) void es_xcorr_kernel(const double* __restrict__ y, long long B,
-        int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
-        double* __restrict__ corr)
-{
-    __shared__ double s_buf[XC_WAVES][XC_NS + 2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double* s = s_buf[wv];
-    const int n_lags = T - (ES_PRE_L - 1);
-    const int nseg = (n_lags + XC_SEG - 1) / XC_SEG;
-    const long long n_items = B * nseg;
-    const long long stride = (long long)gridDim.x * XC_WAVES;
-    for (long long item = (long long)blockIdx.x * XC_WAVES + wv; item < n_items; item += stride) {
-        const long long rec = item / nseg;
-        const int lag0 = (int)(item % nseg) * XC_SEG;
-        const double* yr = y + rec * T + lag0;
-        const int nsamp = (T - lag0 < XC_NS) ? T - lag0 : XC_NS;
-        {   // all 20 row loads are issued before the first one is consumed (one HBM round trip, not 20)
-            double stage[(XC_NS + 63) / 64];
-            #pragma unroll
-            for (int u = 0; u < (XC_NS + 63) / 64; ++u) { const int i = lane + 64 * u; stage[u] = (i < nsamp) ? yr[i] : 0.0; }
-            #pragma unroll
-            for (int u = 0; u < (XC_NS + 63) / 64; ++u) { const int i = lane + 64 * u; if (i < XC_NS) s[i] = stage[u]; }
-        }
-        // wave-uniform band index -> template taps come through scalar loads
-        const double* tpl = tabs->tpl[__builtin_amdgcn_readfirstlane((int)band[rec])];
-        wave_fence_lds();
-
-        const double* w = s + lane * XC_R;
-        double num[XC_R];
-        #pragma unroll
-        for (int r = 0; r < XC_R; ++r) num[r] = 0.0;
-        // en[r] first collects head[r] (descending partial sums of the first 18 squares), then
-        // + core (squares 18..62, ascending), then + tail (squares 63..62+r, ascending): all >= 0.
-        double en[XC_R], sq_head[XC_R - 1];
-        double core = 0.0, tail_run = 0.0;
-        // sample m meets lag r at tap k = m - r (0 <= k < 63)
-        #define XC_FMAS(m, v)                                                                   \
-            _Pragma("unroll") for (int r = 0; r < XC_R; ++r) {                                  \
-                const int k = (m) - r;                                                          \
-                if (k >= 0 && k < ES_PRE_L) num[r] = __builtin_fma((v), tpl[k], num[r]);        \
-            }
-        #pragma unroll
-        for (int m = 0; m < XC_R - 1; ++m) {                     // samples 0..17: head squares
-            const double v = w[m];
-            sq_head[m] = v * v;
-            XC_FMAS(m, v)
-        }
-        en[XC_R - 1] = 0.0;
-        #pragma unroll
-        for (int r = XC_R - 2; r >= 0; --r) en[r] = en[r + 1] + sq_head[r];
-        #pragma unroll
-        for (int m = XC_R - 1; m < ES_PRE_L; ++m) {              // samples 18..62: common core
-            const double v = w[m];
-            core = core + v * v;
-            XC_FMAS(m, v)
-        }
-        #pragma unroll
-        for (int r = 0; r < XC_R; ++r) en[r] = en[r] + core;
-        #pragma unroll
-        for (int m = ES_PRE_L; m < ES_PRE_L - 1 + XC_R; ++m) {   // samples 63..80: m = 62 + r closes lag r
-            const double v = w[m];
-            tail_run = tail_run + v * v;
-            en[m - (ES_PRE_L - 1)] = en[m - (ES_PRE_L - 1)] + tail_run;
-            XC_FMAS(m, v)
-        }
-        #undef XC_FMAS
-        wave_fence_lds();                           // every lane has finished reading its window
-        #pragma unroll
-        for (int r = 0; r < XC_R; ++r) s[lane * XC_R + r] = num[r] / (__builtin_sqrt(en[r]) + 1e-12);
-        wave_fence_lds();
-        const int nl = (n_lags - lag0 < XC_SEG) ? n_lags - lag0 : XC_SEG;
-        double* cr = corr + rec * n_lags + lag0;
-        for (int i = lane; i < nl; i += 64) cr[i] = s[i];
-        wave_fence_lds();
-    }
-}
+#define ES_RAGGED 0
+#include "es_xcorr_body.inc"
+#undef ES_RAGGED
+#define ES_RAGGED 1          // the same kernel for records of unequal length
+#include "es_xcorr_body.inc"
+#undef ES_RAGGED
 
 // ----------------------------------------------------------------------------------------- pick
 // One 256-thread block per record.  The correlation row is staged in LDS when it fits (<= 4096
@@ -530,109 +460,12 @@ __device__ bool block_threshold_saturates(const double* v, int n, uint32_t* s_hi
     return r;
 }
 
-template <bool IN_LDS, int NT>
-__global__ __launch_bounds__(NT) void es_pick_kernel(const double* __restrict__ corr, long long B,
-        int n, double* __restrict__ thr_out, int32_t* __restrict__ peaks, int32_t* __restrict__ npeaks)
-{
-    __shared__ double s_row[IN_LDS ? PK_LDS_N : 1];
-    __shared__ uint32_t s_hist[256];
-    __shared__ uint64_t s_pref;
-    __shared__ int s_k;
-    __shared__ double s_bv[NT];
-    __shared__ int s_bi[NT];
-    __shared__ int s_taken[5];
-    __shared__ int s_flag;
-    __shared__ uint32_t s_cnt;
-    const int min_distance = ES_FRAME_LEN / 2;        // 607
-
-    for (long long rec = blockIdx.x; rec < B; rec += gridDim.x) {
-        const double* cg = corr + rec * n;
-        const double* c = cg;
-        if (IN_LDS) {
-            for (int i = threadIdx.x; i < n; i += NT) s_row[i] = cg[i];
-            c = s_row;
-        }
-        __syncthreads();
-        double thr = 0.95;
-        if (!block_threshold_saturates<NT>(c, n, s_hist, &s_k)) {      // (usually proven in one pass; else the exact order statistics)
-            const double med = block_median<false, NT>(c, n, 0.0, s_hist, &s_pref, &s_k);
-            const double mad = block_median<true, NT>(c, n, med, s_hist, &s_pref, &s_k) + 1e-12;
-            thr = med + 4.5 * 1.4826 * mad;
-            if (0.95 < thr) thr = 0.95;
-        }
-
-        // ascending scan over lags >= thr; each candidate is checked by the whole block
-        int total = 0;
-        for (int base = 0; base < n; base += NT) {
-            const int i = base + threadIdx.x;
-            const bool cand = (i < n) && !(c[i] < thr);
-            unsigned long long mask[NT / 64];
-            if (threadIdx.x == 0) s_cnt = 0;
-            __syncthreads();
-            const unsigned long long bal = __ballot(cand);
-            if ((threadIdx.x & 63) == 0) { ((unsigned long long*)s_bv)[threadIdx.x >> 6] = bal; if (bal) atomicOr(&s_cnt, 1u); }
-            __syncthreads();
-            if (s_cnt == 0) continue;                  // no candidate among these 256 lags (uniform)
-            #pragma unroll
-            for (int w = 0; w < NT / 64; ++w) mask[w] = ((unsigned long long*)s_bv)[w];
-            __syncthreads();
-            for (int w = 0; w < NT / 64; ++w) {
-                unsigned long long m = mask[w];
-                while (m) {                            // uniform across the block
-                    const int bit = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const int ci = base + 64 * w + bit;
-                    const double cv = c[ci];
-                    int lo = ci - min_distance; if (lo < 0) lo = 0;
-                    int hi = ci + min_distance + 1; if (hi > n) hi = n;
-                    int bigger = 0;
-                    for (int j = lo + threadIdx.x; j < hi; j += NT) bigger |= (c[j] > cv);
-                    if (__syncthreads_or(bigger) == 0) {
-                        if (threadIdx.x == 0 && total < ES_MAX_PEAKS) peaks[rec * ES_MAX_PEAKS + total] = ci;
-                        ++total;
-                    }
-                }
-            }
-        }
-
-        if (total == 0) {
-            // fallback: five largest correlations, descending; equal values -> higher index first
-            const int kmax = n < 5 ? n : 5;
-            for (int r = 0; r < kmax; ++r) {
-                double bv = 0.0; int bidx = -1;
-                for (int i = threadIdx.x; i < n; i += NT) {
-                    bool used = false;
-                    for (int qd = 0; qd < r; ++qd) used |= (s_taken[qd] == i);
-                    if (used) continue;
-                    const double ci = c[i];
-                    if (bidx < 0 || ci > bv || (ci == bv && i > bidx)) { bv = ci; bidx = i; }
-                }
-                s_bv[threadIdx.x] = bv; s_bi[threadIdx.x] = bidx;
-                __syncthreads();
-                for (int sft = NT / 2; sft > 0; sft >>= 1) {
-                    if (threadIdx.x < sft) {
-                        const double ov = s_bv[threadIdx.x + sft]; const int oi = s_bi[threadIdx.x + sft];
-                        const double mv = s_bv[threadIdx.x]; const int mi = s_bi[threadIdx.x];
-                        if (oi >= 0 && (mi < 0 || ov > mv || (ov == mv && oi > mi))) {
-                            s_bv[threadIdx.x] = ov; s_bi[threadIdx.x] = oi;
-                        }
-                    }
-                    __syncthreads();
-                }
-                if (threadIdx.x == 0) { s_taken[r] = s_bi[0]; peaks[rec * ES_MAX_PEAKS + r] = s_bi[0]; }
-                __syncthreads();
-            }
-            if (threadIdx.x == 0) npeaks[rec] = kmax | (1 << 30);
-            total = kmax;
-        } else if (threadIdx.x == 0) {
-            npeaks[rec] = total;
-        }
-        if ((int)threadIdx.x >= total && threadIdx.x < ES_MAX_PEAKS) peaks[rec * ES_MAX_PEAKS + threadIdx.x] = -1;   // unused tail
-        if (threadIdx.x == 0) thr_out[rec] = thr;
-        (void)s_flag;
-        __syncthreads();
-    }
-}
+#define ES_RAGGED 0
+#include "es_pick_body.inc"
+#undef ES_RAGGED
+#define ES_RAGGED 1          // the same kernel for records of unequal length
+#include "es_pick_body.inc"
+#undef ES_RAGGED
 
 }  // namespace
 
@@ -676,4 +509,21 @@ int es_launch_pick(es_ctx* ctx, const double* corr, int64_t B, int n_lags, doubl
         return es_launch(ctx, es_pick_kernel<true, PK_THREADS>, blocks, PK_THREADS, 0, st, corr, (long long)B, n_lags, thr, peaks, npeaks);
     // long rows (recordings): one block per row, so make it a big one
     return es_launch(ctx, es_pick_kernel<false, 1024>, blocks, 1024, 0, st, corr, (long long)B, n_lags, thr, peaks, npeaks);
+}
+
+int es_launch_xcorr_ragged(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* len, const uint8_t* band, double* corr,
+                           hipStream_t st)
+{
+    const int n_lags = T - (ES_PRE_L - 1);
+    const long long nseg = (n_lags + XC_SEG - 1) / XC_SEG;
+    return es_launch(ctx, es_xcorr_ragged_kernel, es_grid(B * nseg, XC_WAVES, ctx->num_cu * 16), 64 * XC_WAVES, 0, st, y, (long long)B,
+                     T, len, band, ctx->d_tables, corr);
+}
+
+int es_launch_pick_ragged(es_ctx* ctx, const double* corr, int64_t B, int T, const int32_t* len, double* thr, int32_t* peaks,
+                          int32_t* npeaks, hipStream_t st)
+{
+    // rows of any length up to T - 62, read from global memory: the big block of es_launch_pick's long rows
+    return es_launch(ctx, es_pick_ragged_kernel<1024>, es_grid(B, 1, ctx->num_cu * 16), 1024, 0, st, corr, (long long)B, T, len, thr,
+                     peaks, npeaks);
 }

@@ -36,6 +36,26 @@ EPS = 1e-12
 MAX_TRIES = 400          # rtwm/detector.py:107
 PEAK_LIMIT = 25          # rtwm/detector.py:108
 
+# Padded samples (sync rows x longest clip) of one launch over clips of unequal length.  A memory bound, not a tuned value: a padded row
+# sample costs 20 bytes on the device (float32 in, float64 y, float64 corr), so 2^26 of them are 1.3 GB.
+RAGGED_ROW_SAMPLES = 1 << 26
+
+
+def ragged_buckets(lengths, rows_per_clip: int, budget: int) -> list[list[int]]:
+    """Cut clips into launches: indices sorted by length (equal lengths in input order, hence adjacent), then taken greedily while
+    rows x longest clip = len(bucket) * rows_per_clip * max(length) <= budget.  A clip that is over the budget on its own still gets a
+    bucket, alone.  -> buckets of indices, lengths ascending within each and from bucket to bucket."""
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    out: list[list[int]] = []
+    cur: list[int] = []
+    for i in order:
+        if cur and (len(cur) + 1) * rows_per_clip * int(lengths[i]) > budget:      # lengths ascend: clip i would be the longest
+            out.append(cur); cur = []
+        cur.append(i)
+    if cur:
+        out.append(cur)
+    return out
+
 
 class _Frames:
     """Where the frames of a scan lie, without copying them: frame j = y[rows[j], starts[j] : starts[j] + 1215] of the band-passed
@@ -120,33 +140,30 @@ class WatermarkDetector:
     def verify_batch(self, clips, fs_in) -> list[bool]:
         """verify() for several recordings ("full batched verify()"): the result, the order of tries
         and the evolution of `session_nonce` are those of calling the reference's verify() on the clips one after the other
-        (rtwm/detector.py:44-53, 105-152); what is batched is the GPU work.  Per group of equally long clips: ONE sync launch
+        (rtwm/detector.py:44-53, 105-152); what is batched is the GPU work.  Clips of one sample type share launches whatever their
+        lengths (ragged_buckets: sorted by length, rows x longest clip <= RAGGED_ROW_SAMPLES per launch).  Per launch: ONE sync launch
         sequence over (clips x 4 bands) records, ONE header decode over every peak that can hold a frame and ONE demodulate +
-        list-decode + validate batch over the (peak, counter) candidates of all clips and bands; the host then walks clip by clip
-        and band by band in the reference's order with its early returns."""
+        list-decode + validate batch over the (peak, counter) candidates of all clips and bands; the host then walks clip by clip,
+        in input order, and band by band in the reference's order with its early returns."""
         fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
         signals = [np.asarray(self._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
         signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
         order = self._band_order()
         scans: list = [None] * len(signals)
-        groups: dict[int, list[int]] = {}
-        for i, sgl in enumerate(signals):
-            groups.setdefault((sgl.size, sgl.dtype == np.int16), []).append(i)
-        for (size, _is_i16), idx in groups.items():
-            if size < PRE_L:                                                # rtwm/detector.py:71-73
-                continue
+        launches = self._launches(signals, len(order))
+        for idx in launches:
             for i, sc in zip(idx, self._scan_prepare([signals[i] for i in idx], order)):
                 scans[i] = sc
         # Decoding is stateless (the validator's verdict depends on blob and counter only; nonce bookkeeping happens on the host, in
         # _accept), so it is batched ahead of the walk; the WALK is clip by clip and band by band, in the reference's order with its
         # early returns.  When the walk needs a (clip, band) that is not decoded yet, that band and -- in walk order: the clip's
-        # further bands, then the later clips of the group -- as many further ones as fit under a cap on the candidates per batch go
+        # further bands, then the later clips of its launch -- as many further ones as fit under a cap on the candidates per batch go
         # through ONE demodulate + list-decode + validate batch.  A lone clip (a few hundred candidates) is decoded in one batch,
         # as before; a hundred unwatermarked clips at list size 256 (4 x 400 candidates x 4 variants each) no longer ask for
         # gigabytes of candidate rows at once, and what an early return makes unnecessary is bounded by the cap.
         plans: dict[int, list] = {i: [self._scan_plan(scans[i], bi) for bi in range(len(order))] for i in range(len(signals)) if scans[i] is not None}
         cache: dict[tuple[int, int], list] = {}
-        group_of = {i: idx for idx in groups.values() for i in idx}
+        group_of = {i: walk for walk in map(sorted, launches) for i in walk}         # a launch's clips in input order
         cap = self._pair_cap()
 
         def need(i: int, bi: int) -> list:
@@ -180,21 +197,42 @@ class WatermarkDetector:
             out.append(ok)
         return out
 
+    @staticmethod
+    def _launches(signals: list, nb: int) -> list[list[int]]:
+        """Which clips share a sync launch: by sample type, then ragged_buckets over the lengths.  Clips shorter than the template
+        (rtwm/detector.py:71-73) are in none.  The memory budget holds for clips of one length too: a group of equally long clips above
+        RAGGED_ROW_SAMPLES (100 clips of 5 s in four bands, say), one sync call before, is now several, each on the equal-length path;
+        the results and the walk are the same, need()'s look-ahead stops at the launch."""
+        out: list[list[int]] = []
+        for i16 in (False, True):
+            idx = [i for i, sg in enumerate(signals) if (sg.dtype == np.int16) == i16 and sg.size >= PRE_L]
+            out += [[idx[k] for k in b] for b in ragged_buckets([signals[i].size for i in idx], nb, RAGGED_ROW_SAMPLES)]
+        return out
+
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
     def _scan_prepare(self, signals: list, bands: list) -> list:
         import torch
         eng = self.engine
-        g, nb, M = len(signals), len(bands), signals[0].size
-        x = self._dev(np.repeat(np.stack(signals), nb, axis=0), signals[0].dtype)      # row = clip * nb + band (float32, or int16 samples)
+        g, nb = len(signals), len(bands)
+        sizes = [sg.size for sg in signals]
+        M = max(sizes)
         bid_h = np.tile(np.array([self._band_id(b) for b in bands], np.uint8), g)
         bid = self._dev(bid_h, np.uint8)
-        sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
+        if min(sizes) == M:
+            x = self._dev(np.repeat(np.stack(signals), nb, axis=0), signals[0].dtype)      # row = clip * nb + band (float32, or int16 samples)
+            sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
+        else:                                                               # unequal lengths: rows padded to the longest clip
+            pad = np.zeros((g, M), signals[0].dtype)
+            for c, sg in enumerate(signals):
+                pad[c, :sg.size] = sg
+            x = self._dev(np.repeat(pad, nb, axis=0), signals[0].dtype)
+            sy = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)
         npk = (sy.npeaks.cpu().numpy() & 0xFFFF)
         pk = sy.peaks.cpu().numpy()
         rows, starts = [], []
         for r in range(g * nb):
             for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
-                if st + FRAME_LEN <= M:                                     # rtwm/detector.py:112-113
+                if st + FRAME_LEN <= sizes[r // nb]:                        # rtwm/detector.py:112-113, against the clip's own length
                     rows.append(r); starts.append(int(st))
         src = None
         hdr = (np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0))

@@ -312,6 +312,27 @@ class RxEngine:
         thr, peaks, npeaks = self.pick(corr)
         return SyncResult(y, corr if keep_corr else None, thr, peaks, npeaks)
 
+    def _lens(self, lens, rows: int) -> torch.Tensor:
+        """Per-row sample counts as the int32 [rows] device tensor the ragged entry points read."""
+        lens = self._dev(lens, torch.int32).reshape(-1)
+        if lens.numel() != rows:
+            raise ValueError("lens: one sample count per row")
+        return lens
+
+    def sync_ragged(self, frames: torch.Tensor, lens, band: torch.Tensor, *, keep_corr: bool = False) -> SyncResult:
+        """sync() for records of unequal length in one batch (es_sync_ragged_batch): record i = frames[i, :lens[i]], the rest of the
+        row is padding that may hold anything.  thr / peaks / npeaks, y[i, :lens[i]] and corr[i, :lens[i] - 62] are those of
+        sync(frames[i:i+1, :lens[i]]), bit for bit; a record shorter than 63 samples has no peak (npeaks 0, thr 0).  y and corr past a
+        record's end are unspecified."""
+        frames, dt, B, T = self._frames(frames)
+        lens = self._lens(lens, B)
+        y = torch.empty((B, T), dtype=torch.float64, device=self.device)
+        corr = torch.empty((B, max(T - 62, 0)), dtype=torch.float64, device=self.device) if keep_corr else None
+        thr, peaks, npeaks, _ = self._peak_out(B, flags=False)
+        nat.check(self._ctx, self._lib.es_sync_ragged_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(lens), _ptr(band), _ptr(y), _ptr(corr),
+                                                            _ptr(thr), _ptr(peaks), _ptr(npeaks), self._stream()), "es_sync_ragged_batch")
+        return SyncResult(y, corr, thr, peaks, npeaks)
+
     # ------------------------------------------------------------------ soft demod
     def _at(self, y: torch.Tensor, start, rows, peaks):
         """Record addressing of the peak-addressed entry points: -> (B, row int32 [B] or None, start int32 or None, stride)."""
@@ -542,10 +563,11 @@ class RxEngine:
                                                                  _ptr(ok), _ptr(plain), self._stream()), "es_aead_check_keyed_batch")
         return (ok, plain) if want_plain else ok
 
-    def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T: int, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
+    def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
              hop: torch.Tensor) -> PlanResult:
         """Counter candidates of every (key, row) in try order (es_plan_batch; the rules of _scan_band_multi_frame,
-        rtwm/detector.py:105-142).  peaks int32 [rows, 32] / npeaks int32 [rows] of a sync call over records of T samples, rowband
+        rtwm/detector.py:105-142).  peaks int32 [rows, 32] / npeaks int32 [rows] of a sync call over records of T samples -- an int, or
+        for the rows of a sync_ragged call their sample counts, an integer tensor / array [rows] (es_plan_ragged_batch) --, rowband
         uint8 [rows] their bands, hdr_base int32 [rows] = index of the row's first fitting peak among the P fitting peaks of all
         rows, hdr_ok uint8 / hdr_lo16 int32 [N, P] header results per (key, fitting peak), hop uint8 [N, C] band of (key, counter)."""
         rows = peaks.shape[0]
@@ -567,6 +589,14 @@ class RxEngine:
         res = PlanResult(torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.uint8, device=self.device),
                          torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.int32, device=self.device),
                          torch.empty(pairs, dtype=torch.int32, device=self.device), torch.empty(pairs, dtype=torch.int32, device=self.device))
+        if torch.is_tensor(T) or isinstance(T, np.ndarray):
+            t_max = int(T.max()) if rows else 0                     # (the bound on the hop table's width)
+            lens = self._lens(T, rows)
+            nat.check(self._ctx, self._lib.es_plan_ragged_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows,
+                                                                _ptr(lens), t_max, _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C,
+                                                                _ptr(res.slot), _ptr(res.ctr), _ptr(res.count), _ptr(res.looked),
+                                                                self._stream()), "es_plan_ragged_batch")
+            return res
         nat.check(self._ctx, self._lib.es_plan_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows, int(T),
                                                      _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(res.slot), _ptr(res.ctr),
                                                      _ptr(res.count), _ptr(res.looked), self._stream()), "es_plan_batch")

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._native import ES_MAX_PEAKS, ES_MAX_TRIES, NativeError
-from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, PRE_L, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
+from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
 from .utils import BAND_PLAN
 
 assert MAX_TRIES == ES_MAX_TRIES
@@ -93,6 +93,10 @@ class _SyncTap:
         self.last = self._eng.sync(*a, **k)
         return self.last
 
+    def sync_ragged(self, *a, **k):
+        self.last = self._eng.sync_ragged(*a, **k)
+        return self.last
+
 
 class WatermarkIdentifier:
     """identify(audio, fs_in) -> one entry per key: a KeyMatch, or None where WatermarkDetector(key).verify would return False.
@@ -123,7 +127,7 @@ class WatermarkIdentifier:
 
     def identify_batch(self, clips, fs_in):
         """identify() for several recordings -> one list of per-key entries per clip (with .trace: (those, per clip the per-key
-        traces)).  Clips of equal length share their launches."""
+        traces)).  Clips of one sample type share their launches whatever their lengths (WatermarkDetector._launches)."""
         N = len(self.keys)
         clips = list(clips)
         out = [[None] * N for _ in clips]
@@ -132,24 +136,22 @@ class WatermarkIdentifier:
             fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
             signals = [np.asarray(self._det._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
             signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
-            groups: dict = {}
-            for i, sg in enumerate(signals):
-                groups.setdefault((sg.size, sg.dtype == np.int16), []).append(i)
             per_call = max(1, PAIR_BUDGET // (N * NB))
-            for (size, _i16), idx in groups.items():
-                if size < PRE_L:                                            # rtwm/detector.py:71-73
-                    continue
+            for idx in self._det._launches(signals, NB):                    # (clips shorter than the template are in none)
                 for at in range(0, len(idx), per_call):
                     part = idx[at:at + per_call]
                     self._group([signals[i] for i in part], [out[i] for i in part], [traces[i] for i in part])
         return (out, traces) if self.trace else out
 
-    # ------------------------------------------------------------------ one group of equally long clips
+    # ------------------------------------------------------------------ one group of clips that share their launches
     def _group(self, sigs, out, traces) -> None:
         import torch
         eng = self.engine
         dev = eng.device
-        N, g, M = len(self.keys), len(sigs), sigs[0].size
+        N, g = len(self.keys), len(sigs)
+        sizes = np.array([sg.size for sg in sigs], np.int32)
+        M = int(sizes.max())                                                # the longest clip: row length of the sync call
+        M_rows = np.repeat(sizes, NB)                                       # samples of each sync row's own clip
         R = g * NB                                                          # sync rows: row = clip * 4 + band index
         if self._ring is None or self._ring.ring.device != dev:
             self._ring = eng.keyring(self.keys)
@@ -176,7 +178,8 @@ class WatermarkIdentifier:
         cc = torch.arange(C, dtype=torch.int64, device=dev).repeat(N)
         _, hop = eng.schedule_keyed(ring, kk, cc, want_pn=False)
         rowband = np.tile(np.arange(NB, dtype=np.uint8), g)
-        plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M, okh.reshape(N, P), val.reshape(N, P), hop.reshape(N, C))
+        plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M if int(sizes.min()) == M else M_rows, okh.reshape(N, P), val.reshape(N, P),
+                        hop.reshape(N, C))
         count = plan.count.cpu().numpy().astype(np.int64).reshape(N, R)
         hop0 = ring.hop0.cpu().numpy().astype(np.int64)
         order = np.array([[h] + [b for b in range(NB) if b != h] for h in range(NB)], np.int64)[hop0]      # [N, 4]: rtwm/detector.py:46-52
@@ -184,7 +187,7 @@ class WatermarkIdentifier:
         if self.trace:
             looked = plan.looked.cpu().numpy().reshape(N, R)
             hdr_h = (okh.cpu().numpy().reshape(N, P), val.cpu().numpy().reshape(N, P), score.cpu().numpy().astype(np.float64).reshape(N, P))
-            fit = (pk_h >= 0) & (pk_h + FRAME_LEN <= M) & (np.arange(ES_MAX_PEAKS)[None, :] < np.minimum(sy.npeaks.cpu().numpy() & 0xFFFF, PEAK_LIMIT)[:, None])
+            fit = (pk_h >= 0) & (pk_h + FRAME_LEN <= M_rows[:, None]) & (np.arange(ES_MAX_PEAKS)[None, :] < np.minimum(sy.npeaks.cpu().numpy() & 0xFFFF, PEAK_LIMIT)[:, None])
             fit_rank = np.cumsum(fit, axis=1) - 1                           # header-log index of a peak slot
 
             def hdr_log(k, r, n):

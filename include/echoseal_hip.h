@@ -175,6 +175,24 @@ int es_sync_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int
                   const uint8_t* band_dev, double* y_dev, double* corr_dev /* nullable */,
                   double* thr_dev, int32_t* peaks_dev, int32_t* npeaks_dev, void* stream);
 
+/* es_sync_batch for records of unequal length in one batch (the float64 path: any row length).
+ *   frames_dev [B][T] ES_DTYPE_F32 or ES_DTYPE_I16: T is the row stride, T >= 63
+ *   len_dev    [B] int32: record i is frames[i][0 : len[i]], len[i] clamped to [0, T] on the device
+ *   y_dev      [B][T], corr_dev (nullable) [B][T-62]: the row strides are those of T
+ * For len[i] >= 63 record i gets what es_sync_batch gives for it alone with T = len[i], bit for bit: thr, the whole peaks row, npeaks
+ * with its bit-30 fallback flag, y[i][0 : len[i]] and (when corr_dev is given) corr[i][0 : len[i]-62].  For len[i] < 63: npeaks 0, thr
+ * 0.0 and a peaks row of -1, the reference's return for a record shorter than the template (rtwm/detector.py:71-73).
+ * Samples of a row past len[i] may hold anything, NaN and +-inf included: no output listed above depends on them (the band-pass is
+ * causal with zero initial state and runs the stored row to T; correlation and pick stop at the record's end).
+ * y[i][len[i] : T] and corr[i][len[i]-62 : T-62] are UNSPECIFIED.  The peak-addressed calls (es_llr_at_batch, es_header_at_batch) on
+ * such a y with this T are therefore defined only for frames that lie inside their record, start + 1215 <= len[row]; a frame that
+ * runs past its record's end would be read from the unspecified tail.
+ * Argument checks as es_sync_batch (T >= 63, B == 0 enqueues nothing, null pointers are refused, len_dev among them); the same
+ * workspace rule: after es_reserve(B, T) the call only enqueues, so it can be captured in a graph.                              */
+int es_sync_ragged_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T, const int32_t* len_dev,
+                         const uint8_t* band_dev, double* y_dev, double* corr_dev /* nullable */,
+                         double* thr_dev, int32_t* peaks_dev, int32_t* npeaks_dev, void* stream);
+
 /* Soft demodulation of the payload of one frame per record:
  *   replaces WatermarkDetector._llr (rtwm/detector.py:296-416)
  *   y_dev      [B][T] float64 band-passed records
@@ -390,6 +408,16 @@ int es_select_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const
 int es_plan_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev, const int32_t* hdr_base_dev,
                   int64_t rows, int T, const uint8_t* hdr_ok_dev, const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N,
                   int C, uint8_t* cand_slot_dev, uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream);
+
+/* es_plan_batch for the rows of an es_sync_ragged_batch call: len_dev [rows] int32 takes the place of T in the test of which peaks
+ * can hold a frame, 0 <= start and start + 1215 <= len_dev[r]; T_max (the longest record) that of T in the bound on the hop table,
+ * C >= ceil(T_max / 1215) + 201.  The lengths are taken as given, not clamped (there is no row stride here to clamp them to): T_max
+ * must be at least every len_dev[r]; with a larger length the counters a window reaches past the hop table are skipped (every hop read
+ * is guarded by ctr < C), so the call stays in bounds but plans fewer candidates than the rules give.  Everything else -- outputs, try order, the ES_MAX_TRIES cut -- as es_plan_batch.                 */
+int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev,
+                         const int32_t* hdr_base_dev, int64_t rows, const int32_t* len_dev, int T_max, const uint8_t* hdr_ok_dev,
+                         const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N, int C, uint8_t* cand_slot_dev,
+                         uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream);
 
 #ifdef __cplusplus
 }
