@@ -567,6 +567,41 @@ int es_mix_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n, int bloc
     return es_launch_mix(ctx, x_dev, R, n, block, chips_dev, chips_stride, chip_off_dev, alpha, floor, out_dev, scale_dev, (hipStream_t)stream);
 }
 
+int es_mix_ragged_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_stride, const int64_t* len_dev, int block,
+                        const float* chips_dev, int64_t chips_total, const int64_t* chip_base_dev, const int64_t* chip_cnt_dev,
+                        double alpha, double floor, float* out_dev, double* scale_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;                        /* no tables involved: any context serves it, a front-end one included */
+    if (block < 1) return fail(ctx, ES_EINVAL, "es_mix_ragged_batch: block must be >= 1");
+    if (R < 0 || n_stride < 0 || chips_total < 0) return fail(ctx, ES_EINVAL, "es_mix_ragged_batch: negative size");
+    if (R == 0 || n_stride == 0) return ES_OK;
+    if (!x_dev || !len_dev || !chips_dev || !chip_base_dev || !chip_cnt_dev || !out_dev)
+        return fail(ctx, ES_EINVAL, "es_mix_ragged_batch: null pointer");
+    if (out_dev != x_dev && out_dev < x_dev + R * n_stride && x_dev < out_dev + R * n_stride)
+        return fail(ctx, ES_EINVAL, "es_mix_ragged_batch: out_dev partly overlaps x_dev (only out_dev == x_dev may alias)");
+    if (chips_total == 0) return ES_OK;                /* no record has a chip: every record is of length 0 */
+    DeviceGuard g(ctx->device);
+    return es_launch_mix_ragged(ctx, {x_dev, R, n_stride, len_dev, block, chips_dev, chips_total, chip_base_dev, chip_cnt_dev, alpha, floor,
+                                      out_dev, scale_dev}, (hipStream_t)stream);
+}
+
+int es_tx_frames_keyed_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
+                             const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* ring_dev, int64_t N,
+                             const int32_t* key_dev, int64_t B, double* y_ws_dev, float* frames_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (B < 0 || N < 0) return fail(ctx, ES_EINVAL, "es_tx_frames_keyed_batch: negative count");
+    if (B == 0) return ES_OK;
+    if (N == 0) return fail(ctx, ES_EINVAL, "es_tx_frames_keyed_batch: frames but an empty key ring (every key index is outside [0, N))");
+    if (!code_dev || !pn_rows_dev || !band_dev || !ctr_dev || !preamble8_host || !ring_dev || !key_dev || !y_ws_dev || !frames_dev)
+        return fail(ctx, ES_EINVAL, "es_tx_frames_keyed_batch: null pointer");
+    unsigned long long pre = 0;
+    for (int i = 0; i < 8; ++i) pre = (pre << 8) | preamble8_host[i];      // 63 MLS bits, MSB first, in the top 63 bits
+    DeviceGuard g(ctx->device);
+    return es_launch_tx_frames_keyed(ctx, code_dev, pn_rows_dev, band_dev, ctr_dev, pre, ring_dev, N, key_dev, B, y_ws_dev, frames_dev,
+                                     (hipStream_t)stream);
+}
+
 int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int64_t n_in, const void* h_tf_dev, int h_per_phase,
                       int up, int down, int64_t y0, int64_t n_out, void* out_dev, void* stream)
 {
@@ -714,6 +749,18 @@ int es_aead_check_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, c
     if (!ring_dev || !key_dev || !blobs_dev || !ctr_dev || !ok_dev) return fail(ctx, ES_EINVAL, "es_aead_check_keyed_batch: null pointer");
     DeviceGuard g(ctx->device);
     return es_launch_aead_check_keyed(ctx, ring_dev, N, key_dev, blobs_dev, n, group, ctr_dev, ok_dev, plain_dev, (hipStream_t)stream);
+}
+
+int es_aead_seal_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* nonces_dev,
+                             const uint8_t* plain_dev, int64_t n, uint8_t* blobs_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (n < 0 || N < 0) return fail(ctx, ES_EINVAL, "es_aead_seal_keyed_batch: negative count");
+    if (n == 0) return ES_OK;
+    if (N == 0) return fail(ctx, ES_EINVAL, "es_aead_seal_keyed_batch: records but an empty key ring (every key index is outside [0, N))");
+    if (!ring_dev || !key_dev || !nonces_dev || !plain_dev || !blobs_dev) return fail(ctx, ES_EINVAL, "es_aead_seal_keyed_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_aead_seal_keyed(ctx, ring_dev, N, key_dev, nonces_dev, plain_dev, n, blobs_dev, (hipStream_t)stream);
 }
 
 int es_select_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint32_t* ctr_dev, int64_t B, int L,

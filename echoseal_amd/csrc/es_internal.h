@@ -173,6 +173,17 @@ int es_launch_tx_frames(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows
                         unsigned long long pre_bits, const uint8_t* hdr_pn16, int64_t B, double* y_ws, float* frames, hipStream_t st);
 int es_launch_mix(es_ctx* ctx, const float* x, int64_t R, int64_t n, int block, const float* chips, int64_t chips_stride,
                   const int64_t* chip_off, double alpha, double floor_lin, float* out, double* scale_out, hipStream_t st);
+/* records of unequal length in rows of n_stride, chips from one flat pool (es_mix_ragged_batch; es_mix.hip) */
+struct es_mix_ragged_args {
+    const float* x; int64_t R; int64_t n_stride; const int64_t* len; int block;
+    const float* chips; int64_t chips_total; const int64_t* chip_base; const int64_t* chip_cnt;
+    double alpha; double floor_lin; float* out; double* scale_out;
+};
+int es_launch_mix_ragged(es_ctx* ctx, const es_mix_ragged_args& a, hipStream_t st);
+/* es_launch_tx_frames with the header PN of frame f read from ring row key[f] (es_tx.hip): no host memory, only enqueues */
+int es_launch_tx_frames_keyed(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows, const uint8_t* band, const uint32_t* ctr,
+                              unsigned long long pre_bits, const uint8_t* ring, int64_t N, const int32_t* key, int64_t B, double* y_ws,
+                              float* frames, hipStream_t st);
 int es_launch_resample(es_ctx* ctx, const void* x, int dtype, int64_t B, int64_t n_x, const void* h_tf, int hpp, int up, int down,
                        int64_t y0, int64_t n_out, void* out, hipStream_t st);
 int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* band_key32, const uint32_t* ctr_dev,
@@ -191,6 +202,8 @@ int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const 
                              uint8_t* pn_rows, uint8_t* band, hipStream_t st);
 int es_launch_aead_check_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* blobs, int64_t n, int group,
                                const uint32_t* ctr, uint8_t* ok, uint8_t* plain, hipStream_t st);
+int es_launch_aead_seal_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* nonces, const uint8_t* plain,
+                              int64_t n, uint8_t* blobs, hipStream_t st);
 int es_launch_select_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t B, int L,
                            const uint8_t* hard_info, const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric,
                            const uint8_t* cand_ok, const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st);

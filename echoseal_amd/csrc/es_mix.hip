@@ -20,6 +20,10 @@
 // tree of a chunk (depth <= 7 for n <= 8192) is laid out as a binary heap, thread k = node k; blocks of up to 8192 samples stay in
 // registers for the final pass, longer ones are read again.
 //
+// Both kernels are written once, in es_mix_body.inc, and compiled twice: for recordings of one length (es_mix_batch) and for records of
+// unequal length in rows of one stride that take their chips from one flat pool of frames (es_mix_ragged_batch: the same block arithmetic;
+// a record's blocks are those of its own length, block slots past its end do no work and write nothing).
+//
 // A product or sum that is invalid (inf * 0, inf - inf) gives the negative quiet NaN the host's SSE arithmetic gives; NaNs that are
 // already in x or the chips propagate unchanged on both.
 #include "es_internal.h"
@@ -78,75 +82,6 @@ __device__ __forceinline__ long long clamp_ll(long long v, long long hi) { retur
 constexpr int WV_PAD = 8;                                       // floats between the leaves in LDS: lane 8*leaf + j reads bank 8*leaf + j + 8i
 constexpr int WV_ROW = 8 * (MIX_LEAF + WV_PAD);
 
-__global__ __launch_bounds__(MIX_THREADS) void es_mix_wave_kernel(const float* __restrict__ x, long long R, long long n, long long nfull,
-        const float* __restrict__ chips, long long chips_stride, const long long* __restrict__ chip_off, double alpha, double floor_lin,
-        float* __restrict__ out, double* __restrict__ scale_out, long long nblk)
-{
-    __shared__ __attribute__((aligned(16))) float sq[MIX_THREADS / 64][WV_ROW];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float* a = sq[wv];
-    const long long total = R * nfull;
-    for (long long g = (long long)blockIdx.x * (MIX_THREADS / 64) + wv; g < total; g += (long long)gridDim.x * (MIX_THREADS / 64)) {
-        const long long r = g / nfull, b = g - r * nfull;
-        const long long t0 = b * 1024;
-        const float* xp = x + r * n + t0;
-        const long long c0 = (chip_off ? chip_off[r] : 0) + t0;                // first chip of the block within row r
-        const float* cp = chips + r * chips_stride;
-        const bool c_fast = c0 >= 0 && c0 + 1024 <= chips_stride && (((uintptr_t)(cp + c0)) & 15) == 0;   // wave-uniform
-        float4 xv[4], cv[4];
-        #pragma unroll
-        for (int k = 0; k < 4; ++k) xv[k] = *reinterpret_cast<const float4*>(xp + 256 * k + 4 * lane);
-        if (c_fast) {
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) cv[k] = *reinterpret_cast<const float4*>(cp + c0 + 256 * k + 4 * lane);
-        } else {                                                               // unaligned rows, and offsets that leave the row (clamped)
-            const long long hi = chips_stride - 1;
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const long long e = c0 + 256 * k + 4 * lane;
-                cv[k].x = cp[clamp_ll(e, hi)]; cv[k].y = cp[clamp_ll(e + 1, hi)];
-                cv[k].z = cp[clamp_ll(e + 2, hi)]; cv[k].w = cp[clamp_ll(e + 3, hi)];
-            }
-        }
-        float mx = 0.0f, mc = 0.0f;
-        #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e = 256 * k + 4 * lane;                                  // four samples of one leaf
-            float4 q;
-            q.x = xv[k].x * xv[k].x; q.y = xv[k].y * xv[k].y; q.z = xv[k].z * xv[k].z; q.w = xv[k].w * xv[k].w;
-            *reinterpret_cast<float4*>(a + e + WV_PAD * (e >> 7)) = q;
-            mx = max_nan(max_nan(max_nan(max_nan(mx, __builtin_fabsf(xv[k].x)), __builtin_fabsf(xv[k].y)), __builtin_fabsf(xv[k].z)), __builtin_fabsf(xv[k].w));
-            mc = max_nan(max_nan(max_nan(max_nan(mc, __builtin_fabsf(cv[k].x)), __builtin_fabsf(cv[k].y)), __builtin_fabsf(cv[k].z)), __builtin_fabsf(cv[k].w));
-        }
-        wave_fence_lds();
-        const float* al = a + (MIX_LEAF + WV_PAD) * (lane >> 3) + (lane & 7);  // accumulator j = lane & 7 of leaf lane >> 3
-        float s = al[0];
-        #pragma unroll
-        for (int i = 1; i < 16; ++i) s += al[8 * i];
-        wave_fence_lds();                                                      // the next block of this wave overwrites the row
-        s = s + xor_lanes_f32<1>(s, lane);                                     // (r0+r1) ...
-        s = s + xor_lanes_f32<2>(s, lane);                                     // (r0+r1)+(r2+r3) ...
-        s = s + xor_lanes_f32<4>(s, lane);                                     // the leaf
-        s = s + xor_lanes_f32<8>(s, lane);                                     // 256
-        s = s + __shfl_xor(s, 16);                                             // 512
-        s = s + __shfl_xor(s, 32);                                             // 1024: one chunk
-        s = 0.0f + s;
-        mx = wave_max_nan(mx); mc = wave_max_nan(mc);
-        const double scale = mix_scale(s, 1024, mx, mc, alpha, floor_lin);
-        if (scale_out && lane == 0) scale_out[r * nblk + b] = scale;
-        const float sf = (float)scale;
-        float* op = out + r * n + t0;
-        #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float4 o;
-            o.x = mix_one(xv[k].x, cv[k].x, sf); o.y = mix_one(xv[k].y, cv[k].y, sf);
-            o.z = mix_one(xv[k].z, cv[k].z, sf); o.w = mix_one(xv[k].w, cv[k].w, sf);
-            *reinterpret_cast<float4*>(op + 256 * k + 4 * lane) = o;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- any block length
 __device__ __forceinline__ int sq_at(int e) { return e + (e >> 7); }          // LDS index of square e: leaves 128 apart land on different banks
 
 // sum of a run of n <= 128 squares starting at element `off` of the chunk
@@ -170,94 +105,34 @@ __device__ __forceinline__ float leaf_sum(const float* sq, int off, int n)
     return res;
 }
 
-// KEEP: the block is one chunk (m <= 8192) and stays in registers for the final pass
-template <bool KEEP>
-__global__ __launch_bounds__(MIX_THREADS) void es_mix_block_kernel(const float* __restrict__ x, long long R, long long n, long long block,
-        long long b_first, long long b_count, const float* __restrict__ chips, long long chips_stride, const long long* __restrict__ chip_off,
-        double alpha, double floor_lin, float* __restrict__ out, double* __restrict__ scale_out, long long nblk)
+// records of unequal length (es_mix_ragged_batch): an index clamped to the record's own chips
+__device__ __forceinline__ long long clamp_lh(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Record r of a ragged batch: its length clamped to [0, n] (the rule of es_sync_ragged_batch), and its chips [base, base + cnt) cut to the
+// pool -> chips[lo .. hi].  A record without a chip is a record of length 0.  (No sum here can overflow: base + cnt is formed only where
+// base < 0 < cnt or where cnt <= total - base.)
+__device__ __forceinline__ long long ragged_record(long long len, long long n, long long base, long long cnt, long long total,
+                                                   long long& lo, long long& hi)
 {
-    __shared__ float sq[MIX_CHUNK + MIX_CHUNK / MIX_LEAF];
-    __shared__ float node[256];                                                // sums of the split tree's nodes, heap order
-    __shared__ float red[2][MIX_THREADS / 64];
-    __shared__ float sum_sh;
-    const int t = threadIdx.x;
-    const long long total = R * b_count;
-    const long long hi = chips_stride - 1;
-
-    // heap node t: children 2t+1 and 2t+2; its path from the root is the bits of t+1 below the leading one, most significant first
-    const int depth = 31 - __builtin_clz((unsigned)t + 1u);
-
-    for (long long g = blockIdx.x; g < total; g += gridDim.x) {
-        const long long r = g / b_count, b = b_first + (g - r * b_count);
-        const long long t0 = b * block;
-        const long long m = (n - t0 < block) ? (n - t0) : block;
-        const float* xp = x + r * n + t0;
-        const float* cp = chips + r * chips_stride;
-        const long long c0 = (chip_off ? chip_off[r] : 0) + t0;
-        float xr[KEEP ? MIX_KEEP : 1], cr[KEEP ? MIX_KEEP : 1];
-        float mx = 0.0f, mc = 0.0f, s = 0.0f;                                  // s: thread 0 adds the chunk sums left to right
-
-        for (long long ch = 0; ch < m; ch += MIX_CHUNK) {
-            const int nc = (int)((m - ch < MIX_CHUNK) ? (m - ch) : MIX_CHUNK);
-            __syncthreads();                                                   // the previous chunk (or block) has been summed
-            if constexpr (KEEP) {
-                #pragma unroll
-                for (int i = 0; i < MIX_KEEP; ++i) {
-                    const int e = t + MIX_THREADS * i;
-                    if (e < nc) {
-                        xr[i] = xp[e]; cr[i] = cp[clamp_ll(c0 + e, hi)];
-                        sq[sq_at(e)] = xr[i] * xr[i];
-                        mx = max_nan(mx, __builtin_fabsf(xr[i])); mc = max_nan(mc, __builtin_fabsf(cr[i]));
-                    }
-                }
-            } else {
-                for (int e = t; e < nc; e += MIX_THREADS) {
-                    const float xv = xp[ch + e], cv = cp[clamp_ll(c0 + ch + e, hi)];
-                    sq[sq_at(e)] = xv * xv;
-                    mx = max_nan(mx, __builtin_fabsf(xv)); mc = max_nan(mc, __builtin_fabsf(cv));
-                }
-            }
-            // this thread's node of the chunk's split tree
-            int off = 0, len = nc;
-            bool valid = t < 255;
-            for (int d = depth - 1; d >= 0 && valid; --d) {
-                if (len <= MIX_LEAF) { valid = false; break; }
-                const int n2 = (len >> 1) & ~7;
-                if (((t + 1) >> d) & 1) { off += n2; len -= n2; } else len = n2;
-            }
-            const bool leaf = valid && len <= MIX_LEAF;
-            __syncthreads();
-            if (leaf) node[t] = leaf_sum(sq, off, len);
-            for (int d = 7; d >= 0; --d) {                                     // inner nodes, deepest first (a tree of n <= 8192 is at most 7 deep)
-                __syncthreads();
-                if (valid && !leaf && depth == d) node[t] = node[2 * t + 1] + node[2 * t + 2];
-            }
-            __syncthreads();
-            if (t == 0) s += node[0];
-        }
-
-        mx = wave_max_nan(mx); mc = wave_max_nan(mc);
-        if ((t & 63) == 0) { red[0][t >> 6] = mx; red[1][t >> 6] = mc; }
-        if (t == 0) sum_sh = s;
-        __syncthreads();
-        mx = red[0][0]; mc = red[1][0];
-        #pragma unroll
-        for (int w = 1; w < MIX_THREADS / 64; ++w) { mx = max_nan(mx, red[0][w]); mc = max_nan(mc, red[1][w]); }
-        const double scale = mix_scale(sum_sh, m, mx, mc, alpha, floor_lin);
-        if (scale_out && t == 0) scale_out[r * nblk + b] = scale;
-        const float sf = (float)scale;
-        float* op = out + r * n + t0;
-        if constexpr (KEEP) {
-            #pragma unroll
-            for (int i = 0; i < MIX_KEEP; ++i) {
-                const int e = t + MIX_THREADS * i;
-                if (e < (int)m) op[e] = mix_one(xr[i], cr[i], sf);
-            }
-        } else {
-            for (long long e = t; e < m; e += MIX_THREADS) op[e] = mix_one(xp[e], cp[clamp_ll(c0 + e, hi)], sf);
-        }
-    }
+    lo = base < 0 ? 0 : base;
+    long long end = lo;                                                        // exclusive
+    if (cnt > 0 && base < total) end = base < 0 ? base + cnt : (cnt > total - base ? total : base + cnt);
+    if (end > total) end = total;
+    hi = end - 1;
+    if (end <= lo) return 0;
+    return len < 0 ? 0 : (len > n ? n : len);
 }
+
+#define ES_RAGGED 0
+#define MIX_CHIP_AT(i) clamp_ll(i, hi)
+#include "es_mix_body.inc"
+#undef MIX_CHIP_AT
+#undef ES_RAGGED
+#define ES_RAGGED 1          // the same kernels for records of unequal length in one row stride, chips from one pool
+#define MIX_CHIP_AT(i) clamp_lh(i, lo, hi)
+#include "es_mix_body.inc"
+#undef MIX_CHIP_AT
+#undef ES_RAGGED
 
 }  // namespace
 
@@ -279,4 +154,26 @@ int es_launch_mix(es_ctx* ctx, const float* x, int64_t R, int64_t n, int block, 
     return es_launch(ctx, block <= MIX_CHUNK ? es_mix_block_kernel<true> : es_mix_block_kernel<false>, es_grid(R * b_count, 1, cap), MIX_THREADS, 0, st,
                      x, (long long)R, (long long)n, (long long)block, b_first, b_count, chips, (long long)chips_stride, (const long long*)chip_off,
                      alpha, floor_lin, out, scale_out, nblk);
+}
+
+int es_launch_mix_ragged(es_ctx* ctx, const es_mix_ragged_args& a, hipStream_t st)
+{
+    const long long nblk = (a.n_stride + a.block - 1) / a.block;
+    const long long cap = (long long)ctx->num_cu * 2048;                      // the kernels stride over what a larger batch adds
+    const long long* len = (const long long*)a.len; const long long* base = (const long long*)a.chip_base; const long long* cnt = (const long long*)a.chip_cnt;
+    int tail_only = 0;
+    // one wave per full block under the conditions of es_launch_mix; which slots are full blocks only the device knows
+    if (a.block == 1024 && a.n_stride % 4 == 0 && ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0) {
+        const long long nfull = a.n_stride / 1024;
+        if (nfull) {
+            const int rc = es_launch(ctx, es_mix_ragged_wave_kernel, es_grid(a.R * nfull, 4, cap), MIX_THREADS, 0, st, a.x, (long long)a.R,
+                                     (long long)a.n_stride, nfull, len, a.chips, (long long)a.chips_total, base, cnt, a.alpha, a.floor_lin, a.out,
+                                     a.scale_out, nblk);
+            if (rc != ES_OK) return rc;
+        }
+        tail_only = 1;                                                        // the short last block of each record, if any
+    }
+    return es_launch(ctx, a.block <= MIX_CHUNK ? es_mix_ragged_block_kernel<true> : es_mix_ragged_block_kernel<false>,
+                     es_grid(tail_only ? a.R : a.R * nblk, 1, cap), MIX_THREADS, 0, st, a.x, (long long)a.R, (long long)a.n_stride, (long long)a.block,
+                     tail_only, len, a.chips, (long long)a.chips_total, base, cnt, a.alpha, a.floor_lin, a.out, a.scale_out, nblk);
 }

@@ -109,6 +109,60 @@ class EmbedResult:
 
 
 @dataclass
+class EmbedClip:
+    """One clip of RxEngine.embed_batch."""
+    audio: torch.Tensor        # [len] float32, the watermarked clip (a view into its launch's padded tensor)
+    ctr: int                   # counter of the next frame to generate (WatermarkEmbedder.frame_ctr after process() over the clip)
+    off: int                   # chips of the current frame already used (0 = nothing pending)
+    scale: torch.Tensor | None = None   # [ceil(len / block)] float64 gain of every block (want_scale)
+
+
+# Padded samples (clips x longest clip of the launch) one embed_batch launch may hold.  Bytes per padded sample: the float32 row that
+# is mixed in place, 4, and its staging copy on the host, not on the device; per REAL sample, roughly one chip each: the frames
+# float32, 4, the band-pass workspace float64, 8, code bits 1024 / 1215 and PN rows 152 / 1215, 1 -- so at most 17 bytes per padded
+# sample and 2^26 samples stay under 1.2 GB.  A memory bound, not a tuned value.
+EMBED_ROW_SAMPLES = 1 << 26
+
+
+@dataclass
+class EmbedLayout:
+    """Where the frames of a batch of clips lie (embed_layout)."""
+    nf: np.ndarray             # [R] int64 frames clip r generates: ceil(len_r / 1215)
+    clip: np.ndarray           # [F] int64 clip of each frame of the flat frame list (clip by clip, counters ascending)
+    ctr: np.ndarray            # [F] int64 counter of each frame: (ctr0[clip] + k) mod 2^32
+    chip_base: np.ndarray      # [R] int64 = 1215 * index of clip r's first frame in the flat list
+    chip_cnt: np.ndarray       # [R] int64 = 1215 * nf[r]
+    ctr_next: np.ndarray       # [R] int64 counter after the clip: (ctr0 + nf) mod 2^32
+    off: np.ndarray            # [R] int64 chips of the last frame already used: len mod 1215
+
+
+def embed_layout(lengths, ctr0) -> EmbedLayout:
+    """The frames a batch of clips generates, as WatermarkEmbedder.process does whatever the block size (rtwm/embedder.py:44-62: a
+    frame is made whenever the chip buffer runs short): clip r of lengths[r] samples starting at counter ctr0[r] (a scalar serves
+    every clip) makes ceil(lengths[r] / 1215) frames of consecutive counters mod 2^32.  A pure host function."""
+    FL = nat.ES_FRAME_LEN
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if n.size and n.min() < 0:
+        raise ValueError("negative clip length")
+    c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.int64(int(ctr0)), n.shape)) & 0xFFFFFFFF
+    nf = (n + FL - 1) // FL
+    first = np.cumsum(nf) - nf
+    clip = np.repeat(np.arange(n.size, dtype=np.int64), nf)
+    k = np.arange(int(nf.sum()), dtype=np.int64) - first[clip]
+    return EmbedLayout(nf, clip, (c0[clip] + k) & 0xFFFFFFFF, first * FL, nf * FL, (c0 + nf) & 0xFFFFFFFF, n % FL)
+
+
+def embed_launches(lengths, ctr0, budget: int | None = None) -> list:
+    """How embed_batch cuts a batch into launches: detector.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES) (clips sorted by length, taken
+    while clips x longest clip stays within the budget), each launch with the frame layout of its own clips.  -> [(indices into the
+    batch, EmbedLayout of those clips in that order)]; results go back to the indices, so the caller sees input order."""
+    from .detector import ragged_buckets
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.int64(int(ctr0)), n.shape))
+    return [(idx, embed_layout(n[idx], c0[idx])) for idx in ragged_buckets(n, 1, EMBED_ROW_SAMPLES if budget is None else budget)]
+
+
+@dataclass
 class KeyRing:
     """Keys as device data (es_keyring_derive_batch): row k of `ring` holds what the keyed kernels need of key k (layout:
     include/echoseal_hip.h)."""
@@ -635,6 +689,11 @@ class RxEngine:
 
     def _synthetic_payloads(self, sec, ctr: torch.Tensor, seed: int) -> torch.Tensor:
         """Sealed payloads uint8 [len(ctr),55] of `synthetic_frames` for the int64 device counters `ctr`."""
+        nonces, plain = self._synthetic_plain(ctr, seed)
+        return self.aead_seal(sec._aead._key, nonces, plain)
+
+    def _synthetic_plain(self, ctr: torch.Tensor, seed: int):
+        """What `_synthetic_payloads` seals: -> (nonces uint8 [n,12], plaintexts uint8 [n,27]) of the int64 device counters `ctr`."""
         n = ctr.numel()
         # 31 random bytes per frame from a counter-based hash of (seed, ctr, byte index), so that a frame does not
         # depend on how the counter range is cut into batches or shards (32-bit multiply-xorshift rounds in int64)
@@ -648,7 +707,7 @@ class RxEngine:
         for k in range(4):
             plain[:, 4 + k] = ((ctr >> (8 * (3 - k))) & 0xFF).to(torch.uint8)
         plain[:, 8:27] = rnd[:, :19]
-        return self.aead_seal(sec._aead._key, rnd[:, 19:31].contiguous(), plain)
+        return rnd[:, 19:31].contiguous(), plain
 
     # ------------------------------------------------------------------ level mix: frames -> watermarked recordings
     def mix(self, x: torch.Tensor, chips: torch.Tensor, *, block: int = 1024, chip_off=None, target_rel_db: float = -10.0,
@@ -747,6 +806,155 @@ class RxEngine:
         else:
             tail = torch.zeros((R, FL), dtype=torch.float32, device=self.device)
         return EmbedResult(out[0] if one_d else out, (c0 + new) % (2 ** 32), off, tail, scale)
+
+    # ------------------------------------------------------------------ the transmit chain for many keys and unequal lengths
+    def seal_keyed(self, ring: KeyRing, key_idx, nonces: torch.Tensor, plain: torch.Tensor) -> torch.Tensor:
+        """`aead_seal` with the AEAD key of ring row key_idx[i] per blob (es_aead_seal_keyed_batch): nonces uint8 [n,12],
+        plain uint8 [n,27] -> blobs uint8 [n,55].  A device key index outside the ring gives a zero blob."""
+        nonces = self._dev(nonces, torch.uint8); plain = self._dev(plain, torch.uint8)
+        if nonces.dim() != 2 or nonces.shape[1] != 12 or plain.shape != (nonces.shape[0], 27):
+            raise ValueError("nonces must be [n,12] and plain [n,27]")
+        n = nonces.shape[0]
+        kd = self._key_dev(ring, key_idx, n)
+        if n and ring.n == 0:
+            raise ValueError("records but an empty key ring")
+        blobs = torch.empty((n, 55), dtype=torch.uint8, device=self.device)
+        nat.check(self._ctx, self._lib.es_aead_seal_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(nonces), _ptr(plain), n,
+                                                                _ptr(blobs), self._stream()), "es_aead_seal_keyed_batch")
+        return blobs
+
+    def make_frames_keyed(self, ring: KeyRing, key_idx, ctrs, payloads: torch.Tensor) -> torch.Tensor:
+        """`make_frames` for frames of several keys: frame i carries payloads[i] (uint8 [B,55], already sealed) under counter ctrs[i]
+        and the key of ring row key_idx[i] -> float32 [B,1215] (es_polar_encode_batch, es_schedule_keyed_batch,
+        es_tx_frames_keyed_batch: nothing is derived or copied from the host)."""
+        from .utils import mseq_63
+        cd = self._ctr_dev(ctrs).reshape(-1)
+        B = cd.numel()
+        payloads = self._dev(payloads, torch.uint8)
+        if payloads.shape != (B, 55):
+            raise ValueError("payloads must be uint8 [B,55], one per counter")
+        kd = self._key_dev(ring, key_idx, B)
+        if B and ring.n == 0:
+            raise ValueError("records but an empty key ring")
+        code = self.polar_encode(payloads)
+        pn, band = self.schedule_keyed(ring, kd, cd.to(torch.int64) & 0xFFFFFFFF)
+        pre8 = np.packbits(np.concatenate((mseq_63().astype(np.uint8), np.zeros(1, np.uint8)))).tobytes()
+        y_ws = torch.empty((B, 1215), dtype=torch.float64, device=self.device)
+        frames = torch.empty((B, 1215), dtype=torch.float32, device=self.device)
+        nat.check(self._ctx, self._lib.es_tx_frames_keyed_batch(self._ctx, _ptr(code), _ptr(pn), _ptr(band), _ptr(cd), pre8, _ptr(ring.ring),
+                                                                ring.n, _ptr(kd), B, _ptr(y_ws), _ptr(frames), self._stream()),
+                  "es_tx_frames_keyed_batch")
+        return frames
+
+    def mix_ragged(self, x: torch.Tensor, lens, chips: torch.Tensor, chip_base, chip_cnt, *, block: int = 1024, target_rel_db: float = -10.0,
+                   floor_rel_dbfs: float = -35.0, want_scale: bool = False, out: torch.Tensor | None = None):
+        """`mix` for recordings of unequal length (es_mix_ragged_batch): x float32 [R, stride], record r = x[r, :lens[r]]; chips ONE flat
+        float32 pool, sample t of record r takes chips[chip_base[r] + t], reads clamped to the record's chip_cnt[r] chips (lens,
+        chip_base, chip_cnt: int64 [R]).  Every block of a record is mixed as `mix` mixes the record alone.  out[r, lens[r]:] and the
+        scales of block slots past a record's end are NOT written: give `out` (out=x mixes in place) to decide what they hold.
+        -> marked audio [R, stride]; want_scale: (audio, scale float64 [R, ceil(stride / block)])."""
+        from .utils import db_to_lin
+        if x.dim() != 2 or x.dtype != torch.float32 or chips.dtype != torch.float32:
+            raise ValueError("x must be float32 [R, stride] and chips a float32 pool")
+        x = x.contiguous(); chips = chips.contiguous().reshape(-1)
+        R, n = x.shape
+        lens, chip_base, chip_cnt = (self._dev(v, torch.int64).reshape(-1) for v in (lens, chip_base, chip_cnt))
+        if lens.numel() != R or chip_base.numel() != R or chip_cnt.numel() != R:
+            raise ValueError("lens, chip_base, chip_cnt: one entry per recording")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of x's shape")
+        block = int(block)
+        scale = torch.empty((R, (n + block - 1) // block if block >= 1 else 0), dtype=torch.float64, device=self.device) if want_scale else None
+        nat.check(self._ctx, self._lib.es_mix_ragged_batch(self._ctx, _ptr(x), R, n, _ptr(lens), block, _ptr(chips), chips.numel(), _ptr(chip_base),
+                                                           _ptr(chip_cnt), db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), _ptr(out),
+                                                           _ptr(scale), self._stream()), "es_mix_ragged_batch")
+        return (out, scale) if want_scale else out
+
+    def embed_batch(self, keys, key_idx, clips, *, ctr0=0, block: int = 1024, payloads=None, seed: int | None = None, session_nonces=None,
+                    target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False) -> list:
+        """`embed` for clips of unequal length, each under its own key and start counter: entry i is, bit for bit, what
+        embed(keys[key_idx[i]], clips[i], ctr0=ctr0[i], block=block, payloads=payloads[i]) returns -- the loop this call replaces is its
+        definition (and through it the host WatermarkEmbedder.process, rtwm/embedder.py:44-168).
+        keys: a KeyRing or a sequence of 32-byte keys; clips: 1-D float32 arrays / tensors of any lengths, 0 included; ctr0: a scalar or
+        one value per clip (wraps at 2^32).  Clip i generates ceil(len_i / 1215) frames of counters ctr0_i + k whatever the block.
+        payloads: per clip sealed uint8 [nf_i, 55]; seed=: the bytes embed(seed=) draws for each counter, sealed under the clip's key;
+        neither: plaintext b"ESAL" | ctr | nonce8 | pad11 with `secrets` randomness sealed on the device, nonce8 one per clip
+        (session_nonces: 8 bytes per clip, default fresh).
+        The clips are cut into launches by detector.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its clips into one
+        [clips, longest rounded up to 4] tensor and runs ONE sequence whatever the number of keys and lengths: keyed seal (if needed) ->
+        polar encode -> keyed schedule -> keyed frame generator -> ragged mix, over a flat frame list (embed_layout).
+        Continuing a stream across calls (`carry`) stays with `embed`.  -> [EmbedClip], one per clip in input order."""
+        ring = keys if isinstance(keys, KeyRing) else self.keyring(keys)
+        clips = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in clips]
+        R = len(clips)
+        if any(c.dim() != 1 or c.dtype != torch.float32 for c in clips):
+            raise ValueError("clips must be 1-D float32 arrays or tensors")
+        kidx = np.asarray(key_idx.cpu().numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
+        if kidx.size != R:
+            raise ValueError("one key index per clip is required")
+        if R and (kidx.min() < 0 or kidx.max() >= ring.n):
+            raise ValueError(f"key index outside [0, {ring.n})")
+        lengths = np.array([c.numel() for c in clips], np.int64)
+        if np.ndim(ctr0) and np.size(ctr0) != R:
+            raise ValueError("ctr0: a scalar or one value per clip")
+        lay = embed_layout(lengths, ctr0)
+        c0 = (lay.ctr_next - lay.nf) & 0xFFFFFFFF
+        if payloads is not None:
+            payloads = [np.zeros((0, 55), np.uint8) if p is None else np.asarray(p.cpu().numpy() if torch.is_tensor(p) else p) for p in payloads]
+            if len(payloads) != R or any(p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 55 or p.shape[0] < f for p, f in zip(payloads, lay.nf)):
+                raise ValueError("payloads: per clip uint8 [nf >= ceil(len / 1215), 55]")
+        elif seed is None:
+            import secrets as _secrets
+            if session_nonces is None:
+                session_nonces = [_secrets.token_bytes(8) for _ in range(R)]
+            session_nonces = [bytes(sn) for sn in session_nonces]
+            if len(session_nonces) != R or any(len(sn) != 8 for sn in session_nonces):
+                raise ValueError("session_nonces: 8 bytes per clip")
+        out: list = [None] * R
+        for idx, sub in embed_launches(lengths, c0):
+            F = sub.clip.size
+            kf = kidx[idx][sub.clip]                                   # key of every frame of the launch
+            stride = (int(lengths[idx].max()) + 3) // 4 * 4
+            if F == 0:                                                  # clips of no samples: nothing to generate or to mix
+                for j, i in enumerate(idx):
+                    empty = torch.empty(0, dtype=torch.float32, device=self.device)
+                    out[i] = EmbedClip(empty, int(sub.ctr_next[j]), 0, torch.empty(0, dtype=torch.float64, device=self.device) if want_scale else None)
+                continue
+            if all(not c.is_cuda for c in clips):                      # one staging array, one copy
+                pad = np.zeros((len(idx), stride), np.float32)
+                for j, i in enumerate(idx):
+                    pad[j, :lengths[i]] = clips[i].numpy()
+                x = torch.from_numpy(pad).to(self.device)
+            else:
+                x = torch.zeros((len(idx), stride), dtype=torch.float32, device=self.device)
+                for j, i in enumerate(idx):
+                    x[j, :lengths[i]] = clips[i].to(self.device)
+            ctr_d = torch.from_numpy(sub.ctr).to(self.device)
+            kf_d = torch.from_numpy(kf.astype(np.int32)).to(self.device)
+            if payloads is not None:
+                blobs = torch.from_numpy(np.concatenate([payloads[i][:f] for i, f in zip(idx, sub.nf)])).to(self.device)
+            elif seed is not None:
+                nonces, plain = self._synthetic_plain(ctr_d, seed)
+                blobs = self.seal_keyed(ring, kf_d, nonces, plain)
+            else:
+                plain = np.empty((F, 27), np.uint8)
+                plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
+                plain[:, 4:8] = sub.ctr.astype(">u4").view(np.uint8).reshape(-1, 4)
+                plain[:, 8:16] = np.frombuffer(b"".join(session_nonces[i] for i in idx), np.uint8).reshape(-1, 8)[sub.clip]
+                plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * F), np.uint8).reshape(-1, 11)
+                nonces = np.frombuffer(_secrets.token_bytes(12 * F), np.uint8).reshape(-1, 12)
+                blobs = self.seal_keyed(ring, kf_d, torch.from_numpy(nonces.copy()), torch.from_numpy(plain))
+            frames = self.make_frames_keyed(ring, kf_d, ctr_d, blobs)
+            res = self.mix_ragged(x, torch.from_numpy(lengths[idx]), frames, torch.from_numpy(sub.chip_base), torch.from_numpy(sub.chip_cnt),
+                                  block=block, target_rel_db=target_rel_db, floor_rel_dbfs=floor_rel_dbfs, want_scale=want_scale, out=x)
+            marked, scale = res if want_scale else (res, None)
+            for j, i in enumerate(idx):
+                n_i = int(lengths[i])
+                out[i] = EmbedClip(marked[j, :n_i], int(sub.ctr_next[j]), int(sub.off[j]),
+                                   scale[j, :(n_i + block - 1) // block] if want_scale else None)
+        return out
 
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)
     def _ctr_dev(self, ctrs) -> torch.Tensor:

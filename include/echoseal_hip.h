@@ -419,6 +419,42 @@ int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* n
                          const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N, int C, uint8_t* cand_slot_dev,
                          uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream);
 
+/* ---- the transmit side for many keys: clips of unequal length, each marked under its own key, in one launch sequence ----------
+ * es_aead_seal_batch with the ChaCha20 key of ring row key_dev[i] (read as es_aead_check_keyed_batch reads it) in place of key32_host:
+ * SecureChannel.seal (rtwm/crypto.py:33-37) per (key, blob), what WatermarkEmbedder._build_payload puts into a frame
+ * (rtwm/embedder.py:153-168).  key_dev [n] int32, nonces_dev [n][12], plain_dev [n][27] -> blobs_dev [n][55].  A key index outside
+ * [0, N) reads nothing of the ring and writes a zero blob (the indices are device data: the host cannot refuse them); N == 0 with
+ * n > 0 is ES_EINVAL.  Needs no tables, only enqueues.                                                                            */
+int es_aead_seal_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* nonces_dev,
+                             const uint8_t* plain_dev, int64_t n, uint8_t* blobs_dev, void* stream);
+
+/* es_tx_frames_batch (rtwm/embedder.py:78-141) for frames of several keys: the header PN of frame f (rtwm/embedder.py:50, 105:
+ * pn_bits(0, 128) of the frame's key) is the 16 bytes at offset 272 of ring row key_dev[f]; pn_rows_dev and band_dev come from
+ * es_schedule_keyed_batch over the same (key, counter) records.  Band-pass and peak rule are those of es_tx_frames_batch.  key_dev [B]
+ * int32; a key index outside [0, N) gives a header PN of zero bytes and reads nothing of the ring; N == 0 with B > 0 is ES_EINVAL.
+ * Unlike es_tx_frames_batch it copies nothing from host memory (preamble8_host is read during the call and travels by value):
+ * it only enqueues and can be captured into a graph.                                                                              */
+int es_tx_frames_keyed_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
+                             const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* ring_dev, int64_t N,
+                             const int32_t* key_dev, int64_t B, double* y_ws_dev, float* frames_dev, void* stream);
+
+/* es_mix_batch (WatermarkEmbedder.process, rtwm/embedder.py:44-75) for recordings of unequal length.  x_dev / out_dev float32
+ * [R][n_stride]; record r is x[r][0 : len[r]], len_dev [R] int64 clamped to [0, n_stride] on the device (the rule of
+ * es_sync_ragged_batch).  The record is cut into ceil(len[r] / block) blocks, the last one possibly short, and each block gets exactly the
+ * gain and the output es_mix_batch gives the record alone with n = len[r].  chips_dev is ONE flat float32 pool of chips_total chips, the
+ * frames back to back as the frame generator writes them; sample t of record r takes chips[chip_base[r] + t] (chip_base_dev,
+ * chip_cnt_dev [R] int64).  Chip reads are clamped to [chip_base[r], chip_base[r] + chip_cnt[r] - 1], that range is clamped to the
+ * pool (no read ever leaves it), and a record whose clamped range is empty is treated as a record of length 0.
+ * Samples of a row past len[r] may hold anything.  out[r][len[r]:] and the scale_dev entries of block slots past a record's last block
+ * are NOT written: in place the padding survives, otherwise whatever the caller put there.  out_dev == x_dev is allowed, any other
+ * overlap is ES_EINVAL.  scale_dev nullable float64 [R][ceil(n_stride / block)].
+ * With block == 1024, n_stride % 4 == 0 and 16-byte aligned x_dev / out_dev the full blocks run one wavefront per block and each
+ * record's short last block on the workgroup kernel; otherwise every block runs on the workgroup kernel.  Block slots wholly past a
+ * record's end do no work.  Needs no tables, only enqueues (capturable); R == 0 or n_stride == 0 launches nothing.               */
+int es_mix_ragged_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_stride, const int64_t* len_dev, int block,
+                        const float* chips_dev, int64_t chips_total, const int64_t* chip_base_dev, const int64_t* chip_cnt_dev,
+                        double alpha, double floor, float* out_dev, double* scale_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
