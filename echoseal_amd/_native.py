@@ -30,6 +30,7 @@ ES_MAX_TRIES = 400
 ES_PEAK_LIMIT = 25
 ES_INFO_BYTES = 55
 ES_DTYPE_F32, ES_DTYPE_I16, ES_DTYPE_F64 = 0, 1, 2
+ES_RESAMPLE_DESC_WORDS, ES_RESAMPLE_TILE = 8, 1024     # es_resample_ragged_batch: int64 words per record, outputs per workgroup
 
 # name -> (restype, argtypes); kept next to the header so a test can check both agree
 SIGNATURES = {
@@ -70,6 +71,8 @@ SIGNATURES = {
     "es_tx_frames_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_char_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "es_mix_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "es_resample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "es_resample_ragged_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64,
+                                         c_void_p]),
     "es_set_option": (c_int, [c_void_p, c_char_p, c_int]),
     "es_softplus_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "es_polar_f_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

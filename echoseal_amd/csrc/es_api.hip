@@ -615,6 +615,25 @@ int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int6
     return es_launch_resample(ctx, x_dev, dtype, B, n_in, h_tf_dev, h_per_phase, up, down, y0, n_out, out_dev, (hipStream_t)stream);
 }
 
+int es_resample_ragged_batch(es_ctx* ctx, const void* pool_dev, int dtype, int64_t pool_n, const void* filt_dev, int64_t filt_n,
+                             const int64_t* desc_dev, int64_t R, int rep, float* out_dev, int64_t out_stride, int64_t max_out,
+                             void* stream)
+{
+    if (!ctx) return ES_EINVAL;                        /* no tables involved: any context serves it, a front-end one included */
+    if (rep < 1) return fail(ctx, ES_EINVAL, "es_resample_ragged_batch: rep must be >= 1");
+    if (pool_n < 0 || filt_n < 0 || R < 0 || out_stride < 0 || max_out < 0) return fail(ctx, ES_EINVAL, "es_resample_ragged_batch: negative size");
+    if (dtype != ES_DTYPE_I16 && dtype != ES_DTYPE_F32 && dtype != ES_DTYPE_F64)
+        return fail(ctx, ES_EINVAL, "es_resample_ragged_batch: dtype must be i16, f32 or f64");
+    if (R == 0 || max_out == 0 || out_stride == 0) return ES_OK;
+    if (!pool_dev || !filt_dev || !desc_dev || !out_dev) return fail(ctx, ES_EINVAL, "es_resample_ragged_batch: null pointer");
+    if (max_out > out_stride) max_out = out_stride;    /* the kernel clamps every n_out to the row */
+    if (R > (int64_t)0x7fffffff / ((max_out + ES_RESAMPLE_TILE - 1) / ES_RESAMPLE_TILE))
+        return fail(ctx, ES_EINVAL, "es_resample_ragged_batch: more than 2^31 - 1 tiles in one launch");
+    DeviceGuard g(ctx->device);
+    return es_launch_resample_ragged(ctx, {pool_dev, dtype, pool_n, filt_dev, filt_n, desc_dev, R, rep, out_dev, out_stride, max_out},
+                                     (hipStream_t)stream);
+}
+
 int es_set_option(es_ctx* ctx, const char* name, int value)
 {
     if (!ctx || !name) return ES_EINVAL;

@@ -186,6 +186,12 @@ int es_launch_tx_frames_keyed(es_ctx* ctx, const uint8_t* code, const uint8_t* p
                               float* frames, hipStream_t st);
 int es_launch_resample(es_ctx* ctx, const void* x, int dtype, int64_t B, int64_t n_x, const void* h_tf, int hpp, int up, int down,
                        int64_t y0, int64_t n_out, void* out, hipStream_t st);
+/* clips of unequal length and rate from one flat pool, filters from another, a descriptor per record (es_resample_ragged_batch; es_resample.hip) */
+struct es_resample_ragged_args {
+    const void* pool; int dtype; int64_t pool_n; const void* filt; int64_t filt_n; const int64_t* desc; int64_t R; int rep;
+    float* out; int64_t out_stride; int64_t max_out;
+};
+int es_launch_resample_ragged(es_ctx* ctx, const es_resample_ragged_args& a, hipStream_t st);
 int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* band_key32, const uint32_t* ctr_dev,
                        uint32_t ctr0, int64_t n, uint8_t* pn_rows, uint8_t* band, hipStream_t st);
 int es_launch_aead_seal(es_ctx* ctx, const uint8_t* key32, const uint8_t* nonces, const uint8_t* plain, int64_t n, uint8_t* blobs,

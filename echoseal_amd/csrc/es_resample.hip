@@ -30,6 +30,113 @@ __global__ __launch_bounds__(256) void es_resample_kernel(const T* __restrict__ 
     }
 }
 
+
+// ---- a queue of clips of unequal length and rate in ONE launch (es_resample_ragged_batch) ----------------------------------
+// Record r is described by ES_RESAMPLE_DESC_WORDS int64 words (what utils.resample_plan returns, plus where its samples and its filter lie
+// in two flat pools).  One workgroup per (record, tile of RS_TILE consecutive outputs): the tile's input window is staged into LDS once with
+// coalesced loads (int16 converted there), the rate pair's polyphase table too where it fits (else it is read through L2); lane l computes
+// outputs l, l + 256, ... of the tile.  The 64-bit arithmetic of (phase, input index) is done once per tile, for its first output; a lane
+// reaches its own output by adding doubled steps (down mod up, down div up) with a carry, in 32 bits, and moves on by the step of 256
+// outputs: no division per output.  The arithmetic of one output is es_resample_kernel's: accumulator from +0, products in ascending input
+// index, multiply and add rounded separately, in SciPy's output type; float64 is rounded once to float32 on store.
+constexpr int RS_TILE = ES_RESAMPLE_TILE;
+constexpr int RS_THREADS = 256;
+constexpr int RS_WIN_MAX = 4352;                   // window samples in LDS: 1024 outputs at down / up = 4 and 85 taps need 4 181
+constexpr int RS_FILT_MAX = 3584;                  // table values in LDS: 44.1 -> 48 kHz has 160 x 21 = 3 360
+constexpr int RS_RATE_MAX = 1 << 20;               // up, down above it: the record is refused (32-bit steps inside a tile)
+static_assert(RS_TILE % RS_THREADS == 0 && (RS_WIN_MAX + RS_FILT_MAX) * sizeof(double) <= 65536, "tile / LDS geometry");
+
+template <typename S> struct rs_compute { typedef float type; };
+template <> struct rs_compute<double> { typedef double type; };
+__device__ __forceinline__ float rs_load(const short* p) { return (float)*p / 32768.0f; }
+__device__ __forceinline__ float rs_load(const float* p) { return *p; }
+__device__ __forceinline__ double rs_load(const double* p) { return *p; }
+
+// one output: taps m_lo .. m_hi of phase row hp over the window xw (either in LDS or in global memory)
+template <typename T, typename XP, typename HP>
+__device__ __forceinline__ T rs_dot(XP xw, HP hp, int m_lo, int m_hi)
+{
+    T acc = (T)0;
+    for (int m = m_lo; m <= m_hi; ++m) { const T p = (T)rs_load(xw + m) * hp[m]; acc = acc + p; }
+    return acc;
+}
+
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void es_resample_ragged_kernel(const S* __restrict__ pool, long long pool_n,
+        const typename rs_compute<S>::type* __restrict__ filt, long long filt_n, const long long* __restrict__ desc, long long R, int rep,
+        long long tiles_per_rec, float* __restrict__ out, long long out_stride)
+{
+    typedef typename rs_compute<S>::type T;
+    __shared__ T s_x[RS_WIN_MAX];
+    __shared__ T s_h[RS_FILT_MAX];
+    const int tid = threadIdx.x;
+    const long long items = R * tiles_per_rec;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        const long long r = item / tiles_per_rec, tile = item - r * tiles_per_rec;
+        const long long* d = desc + r * ES_RESAMPLE_DESC_WORDS;
+        long long in_off = d[0], n_in = d[1];
+        const long long up_l = d[2], down_l = d[3], h_off = d[4], hpp_l = d[5], y0 = d[6];
+        long long n_out = d[7] < out_stride ? d[7] : out_stride;
+        const long long k0 = tile * RS_TILE;
+        if (k0 >= n_out) continue;                                          // a tile past its record's end leaves at once (block-uniform)
+        // a bad descriptor reads nothing outside the pools: samples from the record's own [in_off, in_off + n_in) inside the pool only
+        if (in_off < 0 || in_off > pool_n) { in_off = 0; n_in = 0; }
+        if (n_in < 0) n_in = 0;
+        if (n_in > pool_n - in_off) n_in = pool_n - in_off;
+        const S* x = pool + in_off;
+        float* o = out + (r * rep) * out_stride + k0;
+        const int cnt = (int)(n_out - k0 < RS_TILE ? n_out - k0 : RS_TILE);     // outputs of this tile
+        if (up_l == down_l) {                                               // identity: copied (int16 converted), never through the accumulator
+            for (int k = tid; k < cnt; k += RS_THREADS) {
+                if (k0 + k >= n_in) break;
+                const float v = (float)rs_load(x + k0 + k);
+                for (int c = 0; c < rep; ++c) o[c * out_stride + k] = v;
+            }
+            continue;
+        }
+        if (up_l < 1 || down_l < 1 || up_l > RS_RATE_MAX || down_l > RS_RATE_MAX || hpp_l < 1 || hpp_l > RS_RATE_MAX || y0 < 0 || h_off < 0 ||
+            up_l * hpp_l > filt_n - h_off || up_l * hpp_l > (1ll << 30))
+            continue;                                                       // no filter inside the pool: nothing is written
+        const int up = (int)up_l, down = (int)down_l, hpp = (int)hpp_l;
+        const T* h = filt + h_off;
+        // the tile's first output, in 64 bits, once
+        const long long yy = y0 + k0;
+        const long long x0 = (yy / up) * down + ((yy % up) * down) / up;    // = yy * down / up without the wide product
+        const int t0 = (int)(((yy % up) * down) % up);
+        const int dm = down % up, dq = down / up;
+        const long long base = x0 - hpp + 1;                                // pool index (record-relative) of window sample 0
+        const long long span = ((long long)(cnt - 1) * down + t0) / up + hpp;   // window samples of this tile
+        const int neg = base < 0 ? (int)(-base > RS_RATE_MAX ? RS_RATE_MAX : -base) : 0;      // window samples before the record
+        const long long last = n_in - 1 - base;                             // window index of the record's last sample
+        const int hi_rel = (int)(last < -1 ? -1 : (last > span - 1 ? span - 1 : last));
+        const bool x_lds = span <= RS_WIN_MAX, h_lds = up * hpp <= RS_FILT_MAX;
+        if (x_lds)
+            for (int j = tid; j < (int)span; j += RS_THREADS)
+                s_x[j] = (j >= neg && j <= hi_rel) ? (T)rs_load(x + (base + j)) : (T)0;
+        if (h_lds)
+            for (int j = tid; j < up * hpp; j += RS_THREADS) s_h[j] = h[j];
+        __syncthreads();
+        // this lane's first output: t0 plus `tid` steps, by doubling
+        int p = t0, q = 0, sp = dm, sq = dq;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            if ((tid >> b) & 1) { p += sp; q += sq; if (p >= up) { p -= up; ++q; } }
+            sq += sq; sp += sp; if (sp >= up) { sp -= up; ++sq; }
+        }                                                                   // (sp, sq) is now the step of RS_THREADS outputs
+        for (int k = tid; k < cnt; k += RS_THREADS) {
+            int m_lo = neg - q; if (m_lo < 0) m_lo = 0;
+            int m_hi = hi_rel - q; if (m_hi > hpp - 1) m_hi = hpp - 1;
+            T acc;
+            if (x_lds) acc = h_lds ? rs_dot<T>(s_x + q, s_h + p * hpp, m_lo, m_hi) : rs_dot<T>(s_x + q, h + p * hpp, m_lo, m_hi);
+            else       acc = h_lds ? rs_dot<T>(x + (base + q), s_h + p * hpp, m_lo, m_hi) : rs_dot<T>(x + (base + q), h + p * hpp, m_lo, m_hi);
+            const float v = (float)acc;
+            for (int c = 0; c < rep; ++c) o[c * out_stride + k] = v;
+            p += sp; q += sq; if (p >= up) { p -= up; ++q; }
+        }
+        __syncthreads();                                                    // the next item of this block restages the LDS
+    }
+}
+
 }  // namespace
 
 int es_launch_resample(es_ctx* ctx, const void* x, int dtype, int64_t B, int64_t n_x, const void* h_tf, int hpp, int up, int down,
@@ -41,4 +148,21 @@ int es_launch_resample(es_ctx* ctx, const void* x, int dtype, int64_t B, int64_t
                          (long long)n_x, (const float*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (float*)out);
     return es_launch(ctx, es_resample_kernel<double>, blocks, 256, 0, st, (const double*)x, (long long)B,
                      (long long)n_x, (const double*)h_tf, hpp, up, down, (long long)y0, (long long)n_out, (double*)out);
+}
+
+int es_launch_resample_ragged(es_ctx* ctx, const es_resample_ragged_args& a, hipStream_t st)
+{
+    const long long tiles = (a.max_out + RS_TILE - 1) / RS_TILE;
+    const unsigned blocks = es_grid(a.R * tiles, 1, 0x7fffffffll);
+    if (a.dtype == ES_DTYPE_I16)
+        return es_launch(ctx, es_resample_ragged_kernel<short>, blocks, RS_THREADS, 0, st, (const short*)a.pool, (long long)a.pool_n,
+                         (const float*)a.filt, (long long)a.filt_n, (const long long*)a.desc, (long long)a.R, a.rep, tiles, a.out,
+                         (long long)a.out_stride);
+    if (a.dtype == ES_DTYPE_F32)
+        return es_launch(ctx, es_resample_ragged_kernel<float>, blocks, RS_THREADS, 0, st, (const float*)a.pool, (long long)a.pool_n,
+                         (const float*)a.filt, (long long)a.filt_n, (const long long*)a.desc, (long long)a.R, a.rep, tiles, a.out,
+                         (long long)a.out_stride);
+    return es_launch(ctx, es_resample_ragged_kernel<double>, blocks, RS_THREADS, 0, st, (const double*)a.pool, (long long)a.pool_n,
+                     (const double*)a.filt, (long long)a.filt_n, (const long long*)a.desc, (long long)a.R, a.rep, tiles, a.out,
+                     (long long)a.out_stride);
 }

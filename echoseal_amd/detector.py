@@ -3,6 +3,7 @@
 Host orchestration (band order, counter candidates, AEAD validation, anti-replay nonce) is plain
 Python as in the reference; every numeric stage runs on the GPU through echoseal_amd.engine:
 
+    resample_to             -> es_resample_ragged_batch            (rtwm/utils.py:58-66; clips of a batch call at other rates)
     _scan_band_multi_frame  -> es_bpf / es_xcorr / es_pick        (rtwm/detector.py:59-99)
     _decode_header          -> es_header_batch, es_header_at_batch at the peaks of a scan (rtwm/detector.py:452-515)
     _llr                    -> es_llr_batch, es_llr_at_batch at the peaks of a scan       (rtwm/detector.py:296-416)
@@ -21,7 +22,7 @@ from .crypto import SecureChannel
 from .polar_fast import N_DEFAULT
 from .primitives import InvalidTag
 from .tables import matched_filter_taps
-from .utils import BAND_PLAN, BandHop, butter_bandpass, choose_band, mseq_63, resample_to  # noqa: F401 (re-exported)
+from .utils import BAND_PLAN, BandHop, butter_bandpass, choose_band, mseq_63, resample_to, resampled_length  # noqa: F401 (re-exported)
 
 PRE_BITS = mseq_63()
 PRE_L = len(PRE_BITS)
@@ -64,6 +65,21 @@ class _Frames:
 
     def __init__(self, y, rows: np.ndarray, starts: np.ndarray) -> None:
         self.y, self.rows, self.starts = y, rows, starts
+
+
+class _DeviceRows:
+    """The clips of one launch, conditioned and already on the device (RxEngine.resample_ragged): rows float32 [clips * bands, stride],
+    row = clip * bands + band, clip c in the first sizes[c] samples of its rows.  What _scan_prepare takes in place of host signals."""
+    __slots__ = ("rows", "sizes")
+
+    def __init__(self, rows, sizes) -> None:
+        self.rows, self.sizes = rows, [int(n) for n in sizes]
+
+    def __len__(self) -> int:
+        return len(self.sizes)
+
+
+_DEVICE_SAMPLE_TYPES = (np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int16))      # what es_resample_ragged_batch reads
 
 
 class WatermarkDetector:
@@ -130,6 +146,38 @@ class WatermarkDetector:
         signal, _ = resample_to(self.fs_target, audio, fs_in)
         return signal
 
+    # Clips at other rates than fs_target: conditioned on the device, a launch's clips in ONE es_resample_ragged_batch
+    # launch that writes the padded rows of the sync call, a row per band -- no sample makes a round trip through the host.
+    def _mixed_rates(self, clips, fs_list) -> bool:
+        """Does any 1-D, non-empty clip need another rate?  (Otherwise the call runs the code it always ran.)"""
+        return any(f != self.fs_target and np.ndim(c) == 1 and np.size(c) for c, f in zip(clips, fs_list))
+
+    def _raw_clips(self, clips, fs_list):
+        """-> ([(1-D samples, their rate)], resampled lengths).  1-D non-empty int16 / float32 / float64 clips stay as they came; anything
+        else (2-D, empty, other sample types) is conditioned on the host as before and enters at fs_target."""
+        raw, sizes = [], []
+        for c, f in zip(clips, fs_list):
+            a = np.asarray(c)
+            if a.ndim != 1 or not a.size or a.dtype not in _DEVICE_SAMPLE_TYPES:
+                a = np.asarray(self._conditioned(a, f)).reshape(-1)
+                a, f = (a if a.dtype == np.int16 else a.astype(np.float32, copy=False)), self.fs_target
+            raw.append((a, int(f)))
+            sizes.append(resampled_length(a.size, int(f), self.fs_target))
+        return raw, sizes
+
+    @staticmethod
+    def _launches_mixed(raw, sizes, nb: int) -> list[list[int]]:
+        """_launches over the RESAMPLED lengths, by sample type as the clips came (a resampling launch reads one sample type)."""
+        out: list[list[int]] = []
+        for dt in _DEVICE_SAMPLE_TYPES:
+            idx = [i for i, (a, _) in enumerate(raw) if a.dtype == dt and sizes[i] >= PRE_L]
+            out += [[idx[k] for k in b] for b in ragged_buckets([sizes[i] for i in idx], nb, RAGGED_ROW_SAMPLES)]
+        return out
+
+    def _device_rows(self, raw, nb: int) -> _DeviceRows:
+        rows, lens = self.engine.resample_ragged([a for a, _ in raw], [f for _, f in raw], self.fs_target, rep=nb)
+        return _DeviceRows(rows, lens)
+
     def _band_order(self):
         hop0 = self._hop.band(0)
         return [hop0] + [b for b in BAND_PLAN if b != hop0]                 # rtwm/detector.py:46-52
@@ -146,6 +194,8 @@ class WatermarkDetector:
         list-decode + validate batch over the (peak, counter) candidates of all clips and bands; the host then walks clip by clip,
         in input order, and band by band in the reference's order with its early returns."""
         fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        if self._mixed_rates(clips, fs_list):
+            return self._verify_scans(*self._scans_mixed(clips, fs_list))
         signals = [np.asarray(self._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
         signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
         order = self._band_order()
@@ -154,6 +204,22 @@ class WatermarkDetector:
         for idx in launches:
             for i, sc in zip(idx, self._scan_prepare([signals[i] for i in idx], order)):
                 scans[i] = sc
+        return self._verify_scans(scans, launches, order)
+
+    def _scans_mixed(self, clips, fs_list):
+        """The scans of a call with clips at other rates: launches cut by the resampled lengths, each launch's clips raw ->
+        resample_ragged (a row per band) -> sync.  -> (scans, launches, band order)."""
+        order = self._band_order()
+        raw, sizes = self._raw_clips(clips, fs_list)
+        scans: list = [None] * len(raw)
+        launches = self._launches_mixed(raw, sizes, len(order))
+        for idx in launches:
+            for i, sc in zip(idx, self._scan_prepare(self._device_rows([raw[i] for i in idx], len(order)), order)):
+                scans[i] = sc
+        return scans, launches, order
+
+    def _verify_scans(self, scans: list, launches: list, order: list) -> list[bool]:
+        """Decode and walk the prepared scans of a verify_batch call (scans[i] None: clip i is shorter than the template)."""
         # Decoding is stateless (the validator's verdict depends on blob and counter only; nonce bookkeeping happens on the host, in
         # _accept), so it is batched ahead of the walk; the WALK is clip by clip and band by band, in the reference's order with its
         # early returns.  When the walk needs a (clip, band) that is not decoded yet, that band and -- in walk order: the clip's
@@ -161,7 +227,7 @@ class WatermarkDetector:
         # through ONE demodulate + list-decode + validate batch.  A lone clip (a few hundred candidates) is decoded in one batch,
         # as before; a hundred unwatermarked clips at list size 256 (4 x 400 candidates x 4 variants each) no longer ask for
         # gigabytes of candidate rows at once, and what an early return makes unnecessary is bounded by the cap.
-        plans: dict[int, list] = {i: [self._scan_plan(scans[i], bi) for bi in range(len(order))] for i in range(len(signals)) if scans[i] is not None}
+        plans: dict[int, list] = {i: [self._scan_plan(scans[i], bi) for bi in range(len(order))] for i in range(len(scans)) if scans[i] is not None}
         cache: dict[tuple[int, int], list] = {}
         group_of = {i: walk for walk in map(sorted, launches) for i in walk}         # a launch's clips in input order
         cap = self._pair_cap()
@@ -187,7 +253,7 @@ class WatermarkDetector:
             return cache[(i, bi)]
 
         out = []
-        for i in range(len(signals)):
+        for i in range(len(scans)):
             ok = False
             if scans[i] is not None:
                 for bi, (plan, hdr_log) in enumerate(plans[i]):
@@ -214,11 +280,20 @@ class WatermarkDetector:
         import torch
         eng = self.engine
         g, nb = len(signals), len(bands)
-        sizes = [sg.size for sg in signals]
+        on_dev = isinstance(signals, _DeviceRows)                           # conditioned on the device: rows and sizes instead of host signals
+        sizes = signals.sizes if on_dev else [sg.size for sg in signals]
         M = max(sizes)
         bid_h = np.tile(np.array([self._band_id(b) for b in bands], np.uint8), g)
         bid = self._dev(bid_h, np.uint8)
-        if min(sizes) == M:
+        if on_dev:
+            if signals.rows.shape[0] != g * nb:
+                raise ValueError("device rows: one row per clip and band")
+            if min(sizes) == M:
+                x = signals.rows[:, :M]                                     # (made contiguous on the device where the stride is longer)
+                sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
+            else:
+                sy = eng.sync_ragged(signals.rows, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)
+        elif min(sizes) == M:
             x = self._dev(np.repeat(np.stack(signals), nb, axis=0), signals[0].dtype)      # row = clip * nb + band (float32, or int16 samples)
             sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
         else:                                                               # unequal lengths: rows padded to the longest clip

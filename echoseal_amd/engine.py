@@ -62,6 +62,9 @@ def _ptr(t: torch.Tensor | None) -> int | None:
 
 
 _FRAME_DTYPES = {torch.int16: nat.ES_DTYPE_I16, torch.float32: nat.ES_DTYPE_F32}     # what the band-pass reads
+_RESAMPLE_DTYPES = {torch.int16: (nat.ES_DTYPE_I16, np.int16), torch.float32: (nat.ES_DTYPE_F32, np.float32),
+                    torch.float64: (nat.ES_DTYPE_F64, np.float64)}              # what es_resample_ragged_batch reads
+RESAMPLE_TILE = nat.ES_RESAMPLE_TILE                                           # outputs per workgroup of es_resample_ragged_kernel
 
 
 def _peak_start(start: str) -> None:
@@ -180,6 +183,14 @@ class KeyRing:
     @property
     def hop0(self) -> torch.Tensor:          # [N] uint8: band index of counter 0
         return self.ring[:, 288]
+
+
+@dataclass
+class DevicePlan:
+    """A utils.ConditionPlan whose filter pool and descriptors are on the device (RxEngine.condition_upload)."""
+    plan: object               # utils.ConditionPlan (host)
+    filt: torch.Tensor         # filter pool, float32 or float64 (never empty: one zero where no record has a filter)
+    desc: torch.Tensor         # [R, 8] int64
 
 
 @dataclass
@@ -535,6 +546,57 @@ class RxEngine:
                                                          x.shape[0], x.shape[1], _ptr(hd), hpp, up, down, y0, n_out, _ptr(out),
                                                          self._stream()), "es_resample_batch")
         return out[0] if one_d else out
+
+    def condition_upload(self, lengths, fs_list, fs_target: int, dtype) -> "DevicePlan":
+        """utils.condition_plan with its descriptors and filter pool on the device: made once for a queue shape, it lets resample_ragged
+        run without any host copy (device clips, plan=), e.g. inside a stream capture."""
+        from .utils import condition_plan
+        plan = condition_plan(lengths, fs_list, fs_target, dtype)
+        filt = torch.from_numpy(plan.filters if plan.filters.size else np.zeros(1, plan.filters.dtype)).to(self.device, non_blocking=True)
+        return DevicePlan(plan, filt, torch.from_numpy(plan.desc).to(self.device, non_blocking=True))
+
+    def resample_ragged(self, clips, fs_list, fs_target: int, *, rep: int = 1, out: torch.Tensor | None = None, plan: "DevicePlan | None" = None):
+        """resample_to for a group of clips of any lengths and rates in ONE launch (es_resample_ragged_batch): clips = 1-D host arrays
+        or device tensors of ONE sample type (int16, float32 or float64), fs_list one rate or one per clip.  -> (rows float32
+        [len(clips) * rep, stride], lens int64 host array): rows i * rep .. i * rep + rep - 1 all hold clip i conditioned to fs_target in
+        their first lens[i] samples -- scipy.signal.resample_poly(x).astype(float32) bit for bit (int16 as x / 32768 first; equal rates:
+        the samples themselves) --, the rest of a row is never written (new rows: zeros).  stride = the longest output rounded up to 4:
+        the padded rows sync_ragged reads.  Host clips are uploaded once, unpadded; nothing comes back to the host.  plan = the
+        condition_upload of these lengths, rates and sample type: fs_list and fs_target are then not looked at."""
+        clips = list(clips)
+        rep = int(rep)
+        if rep < 1:
+            raise ValueError("rep must be >= 1")
+        ts = [c if torch.is_tensor(c) else torch.from_numpy(np.require(c, requirements=["C", "W"])) for c in clips]      # (a read-only array is copied)
+        if any(t.dim() != 1 for t in ts):
+            raise ValueError("resample_ragged takes 1-D clips")
+        dtypes = {t.dtype for t in ts}
+        if len(dtypes) > 1 or (dtypes and next(iter(dtypes)) not in _RESAMPLE_DTYPES):
+            raise ValueError("resample_ragged: clips of one sample type, int16, float32 or float64")
+        tdt = next(iter(dtypes)) if dtypes else torch.float32
+        dt, np_dt = _RESAMPLE_DTYPES[tdt]
+        if plan is None:
+            plan = self.condition_upload([t.numel() for t in ts], fs_list, fs_target, np_dt)
+        elif plan.plan.desc[:, 1].tolist() != [t.numel() for t in ts] or plan.filt.dtype != (torch.float64 if tdt == torch.float64 else torch.float32):
+            raise ValueError("plan: made for other lengths or another sample type")
+        filt, desc, plan = plan.filt, plan.desc, plan.plan
+        lens = plan.n_out
+        R = len(ts)
+        longest = int(lens.max()) if R else 0
+        stride = (longest + 3) // 4 * 4
+        if out is None:
+            out = torch.zeros((R * rep, stride), dtype=torch.float32, device=self.device)
+        elif out.shape != (R * rep, stride) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 [{R * rep}, {stride}] tensor on the engine's device")
+        if R == 0 or longest == 0:
+            return out, lens
+        if all(t.device == self.device for t in ts):
+            pool = torch.cat(ts)                                            # device clips: gathered on the device
+        else:
+            pool = torch.cat([t.cpu() for t in ts]).to(self.device, non_blocking=True)      # ONE upload, unpadded
+        nat.check(self._ctx, self._lib.es_resample_ragged_batch(self._ctx, _ptr(pool), dt, pool.numel(), _ptr(filt), filt.numel(), _ptr(desc), R,
+                                                                rep, _ptr(out), stride, longest, self._stream()), "es_resample_ragged_batch")
+        return out, lens
 
     # ------------------------------------------------------------------ key / PN / hop schedule (SURVEY 8 a18, f-3)
     def schedule(self, aes_key16: bytes, band_key32: bytes, ctrs=None, *, ctr0: int = 0, n: int | None = None):

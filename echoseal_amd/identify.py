@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._native import ES_MAX_PEAKS, ES_MAX_TRIES, NativeError
-from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
+from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector, _DeviceRows
 from .utils import BAND_PLAN
 
 assert MAX_TRIES == ES_MAX_TRIES
@@ -134,6 +134,14 @@ class WatermarkIdentifier:
         traces = [[([], []) for _ in range(N)] for _ in clips]
         if N:
             fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+            if self._det._mixed_rates(clips, fs_list):                      # clips at other rates: conditioned on the device
+                raw, sizes = self._det._raw_clips(clips, fs_list)
+                per_call = max(1, PAIR_BUDGET // (N * NB))
+                for idx in self._det._launches_mixed(raw, sizes, NB):
+                    for at in range(0, len(idx), per_call):
+                        part = idx[at:at + per_call]
+                        self._group(self._det._device_rows([raw[i] for i in part], NB), [out[i] for i in part], [traces[i] for i in part])
+                return (out, traces) if self.trace else out
             signals = [np.asarray(self._det._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
             signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
             per_call = max(1, PAIR_BUDGET // (N * NB))
@@ -149,7 +157,7 @@ class WatermarkIdentifier:
         eng = self.engine
         dev = eng.device
         N, g = len(self.keys), len(sigs)
-        sizes = np.array([sg.size for sg in sigs], np.int32)
+        sizes = np.array(sigs.sizes if isinstance(sigs, _DeviceRows) else [sg.size for sg in sigs], np.int32)
         M = int(sizes.max())                                                # the longest clip: row length of the sync call
         M_rows = np.repeat(sizes, NB)                                       # samples of each sync row's own clip
         R = g * NB                                                          # sync rows: row = clip * 4 + band index

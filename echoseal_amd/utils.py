@@ -11,6 +11,7 @@ from __future__ import annotations
 import hashlib
 import hmac
 import math
+from dataclasses import dataclass
 from typing import Tuple
 
 import numpy as np
@@ -78,6 +79,12 @@ def resample_to(fs_target: int, audio: np.ndarray, fs_orig: int) -> tuple[np.nda
     return resample_poly(audio, fs_target // g, fs_orig // g), fs_target
 
 
+def resampled_length(n_in: int, fs_orig: int, fs_target: int) -> int:
+    """Samples resample_to returns for n_in samples: ceil(n_in * up / down) (scipy.signal.resample_poly)."""
+    g = math.gcd(int(fs_orig), int(fs_target))
+    return -(-int(n_in) * (int(fs_target) // g) // (int(fs_orig) // g))
+
+
 def resample_plan(n_in: int, up: int, down: int, dtype):
     """Everything scipy.signal.resample_poly(x, up, down) does in Python before its compiled loop (SciPy 1.15: Kaiser-5.0
     `firwin` design of 20*max(up,down)+1 taps scaled by `up`, zero padding that centres the output, the kept output
@@ -113,6 +120,51 @@ def resample_plan(n_in: int, up: int, down: int, dtype):
     hf[: len(h)] = h
     h_tf = np.ascontiguousarray(hf.reshape(-1, up).T[:, ::-1].ravel())
     return h_tf, padlen // up, up, down, n_pre_remove, n_out, np.dtype(ctype)
+
+
+@dataclass
+class ConditionPlan:
+    """Host side of es_resample_ragged_batch for clips of one sample type: desc int64 [R, 8] = (offset of the clip in the flat sample
+    pool, n_in, up, down, offset of its filter in `filters`, taps per phase, first kept output, n_out) -- words 2, 3 and 5..7 and the
+    filter are resample_plan's; an identity record (equal rates) has up = down = 1 and no filter; `filters`: one copy per distinct
+    filter, in the compute type (float64 for float64 samples, else float32); n_out int64 [R] = the resampled lengths."""
+    desc: np.ndarray
+    filters: np.ndarray
+    n_out: np.ndarray
+
+
+def condition_plan(lengths, fs_list, fs_target: int, dtype) -> ConditionPlan:
+    """The descriptors that condition clips of `lengths` samples at rates `fs_list` (one rate, or one per clip) to fs_target in one launch.
+    Clips lie back to back in the sample pool, in input order.  int16 samples are resampled as float32 (x / 32768, resample_to's input
+    after soundfile.read); filters are compared by their bytes, not by the rate pair, so two rate pairs with one table share it."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.int16), np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("condition_plan: samples must be int16, float32 or float64")
+    ctype = np.dtype(np.float64) if dtype == np.float64 else np.dtype(np.float32)
+    n = [int(v) for v in lengths]
+    fs = [int(f) for f in fs_list] if isinstance(fs_list, (list, tuple, np.ndarray)) else [int(fs_list)] * len(n)
+    if len(fs) != len(n) or any(v < 0 for v in n) or any(f < 1 for f in fs) or int(fs_target) < 1:
+        raise ValueError("condition_plan: one positive rate per clip, no negative length")
+    desc = np.zeros((len(n), 8), np.int64)
+    pool: list[np.ndarray] = []
+    seen: dict[bytes, int] = {}
+    at = off = 0
+    for r, (n_in, f) in enumerate(zip(n, fs)):
+        plan = resample_plan(n_in, int(fs_target), f, ctype)
+        if plan is None:
+            desc[r] = (off, n_in, 1, 1, 0, 0, 0, n_in)
+        else:
+            h_tf, hpp, up, down, y0, n_out, ct = plan
+            assert ct == ctype
+            key = h_tf.tobytes()
+            if key not in seen:
+                seen[key] = at
+                pool.append(h_tf)
+                at += h_tf.size
+            desc[r] = (off, n_in, up, down, seen[key], hpp, y0, n_out)
+        off += n_in
+    filters = np.concatenate(pool) if pool else np.zeros(0, ctype)
+    return ConditionPlan(desc, filters, desc[:, 7].copy())
 
 
 class StreamPRNG:

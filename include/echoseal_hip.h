@@ -301,9 +301,31 @@ int es_mix_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n, int bloc
  * SciPy does (firwin, Kaiser 5.0, scaled by `up`, padded) and passes it in SciPy's transposed / flipped polyphase layout
  * (h_tf_dev, `up` phases of h_per_phase taps, element type = dtype); x_dev [B][n_in] and out_dev [B][n_out] have the same
  * element type (ES_DTYPE_F32 for float32 signals, ES_DTYPE_F64 otherwise: SciPy's output type).  Output k of a row is
- * sample y0 + k of the full upfirdn result (y0 = SciPy's n_pre_remove).  Bit-identical to SciPy 1.15's compiled loop. */
+ * sample y0 + k of the full upfirdn result (y0 = SciPy's n_pre_remove).  Bit-identical to SciPy 1.15's compiled loop.  One rate pair and
+ * one length per call, a lane per output with everything read through L2: the yardstick of es_resample_ragged_batch below, which is what
+ * the detector's batch calls use. */
 int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int64_t n_in, const void* h_tf_dev, int h_per_phase,
                       int up, int down, int64_t y0, int64_t n_out, void* out_dev, void* stream);
+
+/* The same conditioning for a queue of clips of unequal length AND rate in one launch: what a batch call needs before es_sync_ragged_batch.
+ * The clips' samples lie back to back, unpadded, in ONE pool (pool_dev, pool_n elements of `dtype`: ES_DTYPE_I16, ES_DTYPE_F32 or
+ * ES_DTYPE_F64), their polyphase filters, one copy per distinct filter, in another (filt_dev, filt_n elements: float32 for int16 and
+ * float32 samples, float64 for float64 samples -- SciPy's output type).  Record r is desc_dev[r][ES_RESAMPLE_DESC_WORDS] int64:
+ *   [0] offset of its first sample in the pool   [1] n_in   [2] up   [3] down   [4] offset of its filter in the filter pool
+ *   [5] taps per phase   [6] y0, first kept output of the full upfirdn result   [7] n_out
+ * -- [2], [3], [5], [6], [7] and the filter are what es_resample_batch takes (utils.resample_plan).  Output: out_dev float32, rows of
+ * out_stride; record r fills rows r * rep .. r * rep + rep - 1 with the same n_out values (rep >= 1: a sync row per band), samples past
+ * n_out of a row are never written.  Each value is es_resample_batch's, bit for bit: an int16 sample enters as (float)s / 32768.0f, a
+ * float64 record is computed in float64 and rounded once to float32 on store.  A record with up == down is copied (int16 converted),
+ * bit patterns and signed zeros kept.  The descriptors are device data the host cannot refuse: n_out is clamped to out_stride, reads to
+ * the record's own [offset, offset + n_in) inside the pool, and a record whose filter does not lie inside the filter pool (or with
+ * up, down or taps per phase outside [1, 2^20]) writes nothing.  max_out >= every n_out sizes the grid (tiles of ES_RESAMPLE_TILE
+ * outputs; a larger n_out is cut to it).  Needs no tables, only enqueues (capturable); R == 0 or max_out == 0 launches nothing. */
+#define ES_RESAMPLE_DESC_WORDS 8
+#define ES_RESAMPLE_TILE    1024
+int es_resample_ragged_batch(es_ctx* ctx, const void* pool_dev, int dtype, int64_t pool_n, const void* filt_dev, int64_t filt_n,
+                             const int64_t* desc_dev, int64_t R, int rep, float* out_dev, int64_t out_stride, int64_t max_out,
+                             void* stream);
 
 /* Diagnostic: out[i] = log1p(exp(t[i])) for t[i] <= 0 exactly as the list decoder's f / penalty evaluate it on the device
  * (np.logaddexp / np.log1p(np.exp(.)) of rtwm/fastpolar.py:18-23, 32-40 through the C library's exp and log1p) -- lets a
