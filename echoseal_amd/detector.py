@@ -15,48 +15,28 @@ print() debugging is not reproduced.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 
 from ._native import NativeError
 from .crypto import SecureChannel
 from .polar_fast import N_DEFAULT
 from .primitives import InvalidTag
+from .scan import FRAME_LEN, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, Launch, cut_launches, ragged_buckets, sync_launch  # noqa: F401 (re-exported)
 from .tables import matched_filter_taps
 from .utils import BAND_PLAN, BandHop, butter_bandpass, choose_band, mseq_63, resample_to, resampled_length  # noqa: F401 (re-exported)
 
 PRE_BITS = mseq_63()
-PRE_L = len(PRE_BITS)
 HDR_BITS = 16
 HDR_REPEAT = 8
 HDR_L = 128
-FRAME_LEN = PRE_L + HDR_L + N_DEFAULT
+assert PRE_L == len(PRE_BITS) and FRAME_LEN == PRE_L + HDR_L + N_DEFAULT
 TIGHT_DELTA = 3
 WIDE_DELTA = 200
 EPS = 1e-12
 
 MAX_TRIES = 400          # rtwm/detector.py:107
-PEAK_LIMIT = 25          # rtwm/detector.py:108
-
-# Padded samples (sync rows x longest clip) of one launch over clips of unequal length.  A memory bound, not a tuned value: a padded row
-# sample costs 20 bytes on the device (float32 in, float64 y, float64 corr), so 2^26 of them are 1.3 GB.
-RAGGED_ROW_SAMPLES = 1 << 26
-
-
-def ragged_buckets(lengths, rows_per_clip: int, budget: int) -> list[list[int]]:
-    """Cut clips into launches: indices sorted by length (equal lengths in input order, hence adjacent), then taken greedily while
-    rows x longest clip = len(bucket) * rows_per_clip * max(length) <= budget.  A clip that is over the budget on its own still gets a
-    bucket, alone.  -> buckets of indices, lengths ascending within each and from bucket to bucket."""
-    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
-    out: list[list[int]] = []
-    cur: list[int] = []
-    for i in order:
-        if cur and (len(cur) + 1) * rows_per_clip * int(lengths[i]) > budget:      # lengths ascend: clip i would be the longest
-            out.append(cur); cur = []
-        cur.append(i)
-    if cur:
-        out.append(cur)
-    return out
-
 
 class _Frames:
     """Where the frames of a scan lie, without copying them: frame j = y[rows[j], starts[j] : starts[j] + 1215] of the band-passed
@@ -67,19 +47,15 @@ class _Frames:
         self.y, self.rows, self.starts = y, rows, starts
 
 
-class _DeviceRows:
-    """The clips of one launch, conditioned and already on the device (RxEngine.resample_ragged): rows float32 [clips * bands, stride],
-    row = clip * bands + band, clip c in the first sizes[c] samples of its rows.  What _scan_prepare takes in place of host signals."""
-    __slots__ = ("rows", "sizes")
-
-    def __init__(self, rows, sizes) -> None:
-        self.rows, self.sizes = rows, [int(n) for n in sizes]
-
-    def __len__(self) -> int:
-        return len(self.sizes)
-
-
-_DEVICE_SAMPLE_TYPES = (np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int16))      # what es_resample_ragged_batch reads
+@dataclass
+class _Scan:
+    """What _scan_band_multi_frame needs for every band of one clip: the clip's peaks that can hold a frame, in (band, peak) order."""
+    bands: list
+    src: _Frames | None         # the frames of the clip's whole launch; None: no peak of it can hold a frame
+    rows: np.ndarray            # band index (into bands) of each of the clip's peaks
+    sel: np.ndarray             # their places in src and hdr
+    starts: np.ndarray          # of the whole launch, like src and hdr
+    hdr: tuple                  # header decodes under the detector's key: (ok, low 16 counter bits, score)
 
 
 class WatermarkDetector:
@@ -146,38 +122,6 @@ class WatermarkDetector:
         signal, _ = resample_to(self.fs_target, audio, fs_in)
         return signal
 
-    # Clips at other rates than fs_target: conditioned on the device, a launch's clips in ONE es_resample_ragged_batch
-    # launch that writes the padded rows of the sync call, a row per band -- no sample makes a round trip through the host.
-    def _mixed_rates(self, clips, fs_list) -> bool:
-        """Does any 1-D, non-empty clip need another rate?  (Otherwise the call runs the code it always ran.)"""
-        return any(f != self.fs_target and np.ndim(c) == 1 and np.size(c) for c, f in zip(clips, fs_list))
-
-    def _raw_clips(self, clips, fs_list):
-        """-> ([(1-D samples, their rate)], resampled lengths).  1-D non-empty int16 / float32 / float64 clips stay as they came; anything
-        else (2-D, empty, other sample types) is conditioned on the host as before and enters at fs_target."""
-        raw, sizes = [], []
-        for c, f in zip(clips, fs_list):
-            a = np.asarray(c)
-            if a.ndim != 1 or not a.size or a.dtype not in _DEVICE_SAMPLE_TYPES:
-                a = np.asarray(self._conditioned(a, f)).reshape(-1)
-                a, f = (a if a.dtype == np.int16 else a.astype(np.float32, copy=False)), self.fs_target
-            raw.append((a, int(f)))
-            sizes.append(resampled_length(a.size, int(f), self.fs_target))
-        return raw, sizes
-
-    @staticmethod
-    def _launches_mixed(raw, sizes, nb: int) -> list[list[int]]:
-        """_launches over the RESAMPLED lengths, by sample type as the clips came (a resampling launch reads one sample type)."""
-        out: list[list[int]] = []
-        for dt in _DEVICE_SAMPLE_TYPES:
-            idx = [i for i, (a, _) in enumerate(raw) if a.dtype == dt and sizes[i] >= PRE_L]
-            out += [[idx[k] for k in b] for b in ragged_buckets([sizes[i] for i in idx], nb, RAGGED_ROW_SAMPLES)]
-        return out
-
-    def _device_rows(self, raw, nb: int) -> _DeviceRows:
-        rows, lens = self.engine.resample_ragged([a for a, _ in raw], [f for _, f in raw], self.fs_target, rep=nb)
-        return _DeviceRows(rows, lens)
-
     def _band_order(self):
         hop0 = self._hop.band(0)
         return [hop0] + [b for b in BAND_PLAN if b != hop0]                 # rtwm/detector.py:46-52
@@ -194,29 +138,13 @@ class WatermarkDetector:
         list-decode + validate batch over the (peak, counter) candidates of all clips and bands; the host then walks clip by clip,
         in input order, and band by band in the reference's order with its early returns."""
         fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
-        if self._mixed_rates(clips, fs_list):
-            return self._verify_scans(*self._scans_mixed(clips, fs_list))
-        signals = [np.asarray(self._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
-        signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
         order = self._band_order()
-        scans: list = [None] * len(signals)
-        launches = self._launches(signals, len(order))
-        for idx in launches:
-            for i, sc in zip(idx, self._scan_prepare([signals[i] for i in idx], order)):
+        launches = cut_launches(clips, fs_list, self.fs_target, len(order), self._conditioned)
+        scans: list = [None] * len(clips)
+        for la in launches:
+            for i, sc in zip(la.idx, self._scan_prepare(la, order)):
                 scans[i] = sc
-        return self._verify_scans(scans, launches, order)
-
-    def _scans_mixed(self, clips, fs_list):
-        """The scans of a call with clips at other rates: launches cut by the resampled lengths, each launch's clips raw ->
-        resample_ragged (a row per band) -> sync.  -> (scans, launches, band order)."""
-        order = self._band_order()
-        raw, sizes = self._raw_clips(clips, fs_list)
-        scans: list = [None] * len(raw)
-        launches = self._launches_mixed(raw, sizes, len(order))
-        for idx in launches:
-            for i, sc in zip(idx, self._scan_prepare(self._device_rows([raw[i] for i in idx], len(order)), order)):
-                scans[i] = sc
-        return scans, launches, order
+        return self._verify_scans(scans, [la.idx for la in launches], order)
 
     def _verify_scans(self, scans: list, launches: list, order: list) -> list[bool]:
         """Decode and walk the prepared scans of a verify_batch call (scans[i] None: clip i is shorter than the template)."""
@@ -244,7 +172,7 @@ class WatermarkDetector:
                         break
                     batch.append((j, r)); n += m
                 flat = [(j, p) for (j, r) in batch for p in plans[j][r][0]]
-                res = self._decode_pairs_grouped([(scans[j]["src"], p[0], p[2]) for j, p in flat]) if flat else []
+                res = self._decode_pairs_grouped([(scans[j].src, p[0], p[2]) for j, p in flat]) if flat else []
                 at = 0
                 for (j, r) in batch:
                     m = len(plans[j][r][0])
@@ -263,79 +191,39 @@ class WatermarkDetector:
             out.append(ok)
         return out
 
-    @staticmethod
-    def _launches(signals: list, nb: int) -> list[list[int]]:
-        """Which clips share a sync launch: by sample type, then ragged_buckets over the lengths.  Clips shorter than the template
-        (rtwm/detector.py:71-73) are in none.  The memory budget holds for clips of one length too: a group of equally long clips above
-        RAGGED_ROW_SAMPLES (100 clips of 5 s in four bands, say), one sync call before, is now several, each on the equal-length path;
-        the results and the walk are the same, need()'s look-ahead stops at the launch."""
-        out: list[list[int]] = []
-        for i16 in (False, True):
-            idx = [i for i, sg in enumerate(signals) if (sg.dtype == np.int16) == i16 and sg.size >= PRE_L]
-            out += [[idx[k] for k in b] for b in ragged_buckets([signals[i].size for i in idx], nb, RAGGED_ROW_SAMPLES)]
-        return out
-
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
-    def _scan_prepare(self, signals: list, bands: list) -> list:
-        import torch
+    def _scan_prepare(self, signals, bands: list) -> list:
+        """signals: a Launch, or host signals at fs_target (one sample type, none shorter than the template) that make one."""
         eng = self.engine
-        g, nb = len(signals), len(bands)
-        on_dev = isinstance(signals, _DeviceRows)                           # conditioned on the device: rows and sizes instead of host signals
-        sizes = signals.sizes if on_dev else [sg.size for sg in signals]
-        M = max(sizes)
-        bid_h = np.tile(np.array([self._band_id(b) for b in bands], np.uint8), g)
-        bid = self._dev(bid_h, np.uint8)
-        if on_dev:
-            if signals.rows.shape[0] != g * nb:
-                raise ValueError("device rows: one row per clip and band")
-            if min(sizes) == M:
-                x = signals.rows[:, :M]                                     # (made contiguous on the device where the stride is longer)
-                sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
-            else:
-                sy = eng.sync_ragged(signals.rows, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)
-        elif min(sizes) == M:
-            x = self._dev(np.repeat(np.stack(signals), nb, axis=0), signals[0].dtype)      # row = clip * nb + band (float32, or int16 samples)
-            sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
-        else:                                                               # unequal lengths: rows padded to the longest clip
-            pad = np.zeros((g, M), signals[0].dtype)
-            for c, sg in enumerate(signals):
-                pad[c, :sg.size] = sg
-            x = self._dev(np.repeat(pad, nb, axis=0), signals[0].dtype)
-            sy = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)
-        npk = (sy.npeaks.cpu().numpy() & 0xFFFF)
-        pk = sy.peaks.cpu().numpy()
-        rows, starts = [], []
-        for r in range(g * nb):
-            for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
-                if st + FRAME_LEN <= sizes[r // nb]:                        # rtwm/detector.py:112-113, against the clip's own length
-                    rows.append(r); starts.append(int(st))
+        launch = signals if isinstance(signals, Launch) else Launch(list(range(len(signals))), [sg.size for sg in signals], signals, None, self.fs_target)
+        band_ids = np.array([self._band_id(b) for b in bands], np.uint8)
+        ss = sync_launch(eng, launch, band_ids)
+        nb, rows_a = ss.nb, ss.rows
         src = None
         hdr = (np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0))
-        rows_a = np.array(rows, np.int64)
-        if rows:
+        if rows_a.size:
             # frame j = sy.y[rows[j], starts[j] : starts[j] + 1215], read in place (no [P, 1215] copy)
-            src = _Frames(sy.y, rows_a, np.array(starts, np.int64))
-            okh, val, score = eng.header(sy.y, self._dev(bid_h[rows_a], np.uint8),
+            src = _Frames(ss.sy.y, rows_a, ss.starts)
+            okh, val, score = eng.header(ss.sy.y, self._dev(band_ids[rows_a % nb], np.uint8),
                                          self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8),
-                                         rows=self._dev(rows_a, np.int32), start=self._dev(src.starts, np.int32))
+                                         rows=self._dev(rows_a, np.int32), start=self._dev(ss.starts, np.int32))
             hdr = (okh.cpu().numpy().astype(bool), val.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64))
-        return [{"bands": bands, "src": src, "rows": rows_a - c * nb, "sel": np.flatnonzero((rows_a // nb) == c) if rows else np.zeros(0, np.int64),
-                 "starts": np.array(starts, np.int64), "hdr": hdr} for c in range(g)]
+        return [_Scan(bands, src, rows_a - c * nb, np.flatnonzero((rows_a // nb) == c), ss.starts, hdr) for c in range(len(ss.sizes))]
 
     def _scan_plan(self, scan, bi: int):
         """The candidate (peak, counter) pairs of one band in the reference's try order (rtwm/detector.py:105-140):
         -> (plan [(peak slot j, start, ctr, header-log index)], header log of the peaks looked at)."""
-        band = scan["bands"][bi]
-        sel = [int(j) for j in scan["sel"] if scan["rows"][j] == bi]       # this band's peaks, in peak order
+        band = scan.bands[bi]
+        sel = [int(j) for j in scan.sel if scan.rows[j] == bi]             # this band's peaks, in peak order
         plan: list[tuple[int, int, int, int]] = []
         hdr_log = []
         tried = 0
         for j in sel:
             if tried >= MAX_TRIES:
                 break
-            start = int(scan["starts"][j])
+            start = int(scan.starts[j])
             ctr_est = int(round(start / FRAME_LEN))
-            hdr_ok, ctr_lo16, score = bool(scan["hdr"][0][j]), int(scan["hdr"][1][j]), float(scan["hdr"][2][j])
+            hdr_ok, ctr_lo16, score = bool(scan.hdr[0][j]), int(scan.hdr[1][j]), float(scan.hdr[2][j])
             hdr_log.append((float(hdr_ok), float(ctr_lo16), score))
             cands: list[int] = []
             if hdr_ok:                                                      # rtwm/detector.py:122-127
@@ -357,7 +245,7 @@ class WatermarkDetector:
 
     def _scan_replay(self, scan, bi: int, plan, hdr_log, results) -> bool:
         """Walk one band's decoded candidates as the reference does (early return, traces, nonce bookkeeping in _accept)."""
-        band = scan["bands"][bi]
+        band = scan.bands[bi]
         for (j, start, ctr, h), blobs in zip(plan, results):
             if self._trace is not None:
                 self._trace.append((int(band[0]), int(start), int(ctr)))
@@ -376,7 +264,7 @@ class WatermarkDetector:
             if self._hdr_trace is not None:
                 self._hdr_trace.extend(hdr_log)
             return False
-        results = self._decode_pairs(scan["src"], [p[0] for p in plan], [p[2] for p in plan])
+        results = self._decode_pairs(scan.src, [p[0] for p in plan], [p[2] for p in plan])
         return self._scan_replay(scan, bi, plan, hdr_log, results)
 
     def verify_raw_frame(self, signal: np.ndarray) -> bool:

@@ -156,10 +156,10 @@ def embed_layout(lengths, ctr0) -> EmbedLayout:
 
 
 def embed_launches(lengths, ctr0, budget: int | None = None) -> list:
-    """How embed_batch cuts a batch into launches: detector.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES) (clips sorted by length, taken
+    """How embed_batch cuts a batch into launches: scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES) (clips sorted by length, taken
     while clips x longest clip stays within the budget), each launch with the frame layout of its own clips.  -> [(indices into the
     batch, EmbedLayout of those clips in that order)]; results go back to the indices, so the caller sees input order."""
-    from .detector import ragged_buckets
+    from .scan import ragged_buckets
     n = np.asarray(lengths, dtype=np.int64).reshape(-1)
     c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.int64(int(ctr0)), n.shape))
     return [(idx, embed_layout(n[idx], c0[idx])) for idx in ragged_buckets(n, 1, EMBED_ROW_SAMPLES if budget is None else budget)]
@@ -944,7 +944,7 @@ class RxEngine:
         payloads: per clip sealed uint8 [nf_i, 55]; seed=: the bytes embed(seed=) draws for each counter, sealed under the clip's key;
         neither: plaintext b"ESAL" | ctr | nonce8 | pad11 with `secrets` randomness sealed on the device, nonce8 one per clip
         (session_nonces: 8 bytes per clip, default fresh).
-        The clips are cut into launches by detector.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its clips into one
+        The clips are cut into launches by scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its clips into one
         [clips, longest rounded up to 4] tensor and runs ONE sequence whatever the number of keys and lengths: keyed seal (if needed) ->
         polar encode -> keyed schedule -> keyed frame generator -> ragged mix, over a flat frame list (embed_layout).
         Continuing a stream across calls (`carry`) stays with `embed`.  -> [EmbedClip], one per clip in input order."""

@@ -23,7 +23,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._native import ES_MAX_PEAKS, ES_MAX_TRIES, NativeError
-from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector, _DeviceRows
+from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
+from .scan import cut_launches, sync_launch
 from .utils import BAND_PLAN
 
 assert MAX_TRIES == ES_MAX_TRIES
@@ -75,29 +76,6 @@ def plan_reference(peaks, npeaks: int, M: int, band: int, hdr_ok, hdr_lo16, hop)
     return plan, looked
 
 
-class _SyncTap:
-    """An engine that remembers the SyncResult of its last sync call, so that WatermarkDetector._scan_prepare (conditioning and sync
-    are its code, not a copy of it) also hands over the peaks as the sync kernels wrote them."""
-
-    def __init__(self, eng) -> None:
-        self._eng, self.last = eng, None
-
-    def __getattr__(self, name):
-        return getattr(self._eng, name)
-
-    def sync_fast(self, *a, **k):
-        self.last = self._eng.sync_fast(*a, **k)
-        return self.last
-
-    def sync(self, *a, **k):
-        self.last = self._eng.sync(*a, **k)
-        return self.last
-
-    def sync_ragged(self, *a, **k):
-        self.last = self._eng.sync_ragged(*a, **k)
-        return self.last
-
-
 class WatermarkIdentifier:
     """identify(audio, fs_in) -> one entry per key: a KeyMatch, or None where WatermarkDetector(key).verify would return False.
     With `.trace = True` a call returns (matches, traces), traces[i] = (the `_trace`, the `_hdr_trace`) a fresh detector of key i
@@ -127,58 +105,42 @@ class WatermarkIdentifier:
 
     def identify_batch(self, clips, fs_in):
         """identify() for several recordings -> one list of per-key entries per clip (with .trace: (those, per clip the per-key
-        traces)).  Clips of one sample type share their launches whatever their lengths (WatermarkDetector._launches)."""
+        traces)).  Clips of one sample type share their launches whatever their lengths (scan.cut_launches)."""
         N = len(self.keys)
         clips = list(clips)
         out = [[None] * N for _ in clips]
         traces = [[([], []) for _ in range(N)] for _ in clips]
         if N:
             fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
-            if self._det._mixed_rates(clips, fs_list):                      # clips at other rates: conditioned on the device (DESIGN 4.12)
-                raw, sizes = self._det._raw_clips(clips, fs_list)
-                per_call = max(1, PAIR_BUDGET // (N * NB))
-                for idx in self._det._launches_mixed(raw, sizes, NB):
-                    for at in range(0, len(idx), per_call):
-                        part = idx[at:at + per_call]
-                        self._group(self._det._device_rows([raw[i] for i in part], NB), [out[i] for i in part], [traces[i] for i in part])
-                return (out, traces) if self.trace else out
-            signals = [np.asarray(self._det._conditioned(c, f)).reshape(-1) for c, f in zip(clips, fs_list)]
-            signals = [sg if sg.dtype == np.int16 else sg.astype(np.float32, copy=False) for sg in signals]
             per_call = max(1, PAIR_BUDGET // (N * NB))
-            for idx in self._det._launches(signals, NB):                    # (clips shorter than the template are in none)
-                for at in range(0, len(idx), per_call):
-                    part = idx[at:at + per_call]
-                    self._group([signals[i] for i in part], [out[i] for i in part], [traces[i] for i in part])
+            for la in cut_launches(clips, fs_list, self.fs_target, NB, self._det._conditioned):      # (clips shorter than the template are in none)
+                for at in range(0, len(la.idx), per_call):
+                    part = la.part(at, at + per_call)
+                    self._group(part, [out[i] for i in part.idx], [traces[i] for i in part.idx])
         return (out, traces) if self.trace else out
 
     # ------------------------------------------------------------------ one group of clips that share their launches
-    def _group(self, sigs, out, traces) -> None:
+    def _group(self, launch, out, traces) -> None:
         import torch
         eng = self.engine
         dev = eng.device
-        N, g = len(self.keys), len(sigs)
-        sizes = np.array(sigs.sizes if isinstance(sigs, _DeviceRows) else [sg.size for sg in sigs], np.int32)
-        M = int(sizes.max())                                                # the longest clip: row length of the sync call
-        M_rows = np.repeat(sizes, NB)                                       # samples of each sync row's own clip
+        N, g = len(self.keys), len(launch.idx)
         R = g * NB                                                          # sync rows: row = clip * 4 + band index
         if self._ring is None or self._ring.ring.device != dev:
             self._ring = eng.keyring(self.keys)
         ring = self._ring
-        tap = _SyncTap(eng)
-        real, self._det._engine = self._det._engine, tap
-        try:
-            scans = self._det._scan_prepare(sigs, list(BAND_PLAN))         # conditioning + sync once, whatever the number of keys
-        finally:
-            self._det._engine = real
-        src, sy = scans[0]["src"], tap.last
-        if src is None:                                                     # no peak can hold a frame: nothing to try for any key
+        scan = sync_launch(eng, launch, range(NB))                           # conditioning + sync once, whatever the number of keys
+        sy, y, rows_a, starts = scan.sy, scan.sy.y, scan.rows, scan.starts   # the P fitting peaks, in (row, peak) order
+        if not rows_a.size:                                                 # no peak can hold a frame: nothing to try for any key
             return
-        rows_a, starts = src.rows, src.starts                               # the P fitting peaks, in (row, peak) order
+        sizes = np.array(scan.sizes, np.int32)
+        M = int(sizes.max())                                                # the longest clip: row length of the sync call
+        M_rows = np.repeat(sizes, NB)                                       # samples of each sync row's own clip
         P = rows_a.size
         base = np.searchsorted(rows_a, np.arange(R)).astype(np.int32)
         # one header decode over (key, fitting peak), key-major, each key with its own header PN
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        okh, val, score = eng.header(src.y, t(np.tile(rows_a % NB, N), np.uint8), ring.hdr_pn.repeat_interleave(P, dim=0),
+        okh, val, score = eng.header(y, t(np.tile(rows_a % NB, N), np.uint8), ring.hdr_pn.repeat_interleave(P, dim=0),
                                      rows=t(np.tile(rows_a, N), np.int32), start=t(np.tile(starts, N), np.int32))
         # hop table: band of (key, counter) for every counter a window can reach
         C = -(-M // FRAME_LEN) + WIDE_DELTA + 1
@@ -231,8 +193,8 @@ class WatermarkIdentifier:
                     b = min(total, a + cap)
                     n = b - a
                     pn, bands = eng.schedule_keyed(ring, key_d[a:b], ctr_d[a:b])
-                    l0 = eng.llr(src.y, bands, pn, variant=0, rows=row_d[a:b], start=start_d[a:b])
-                    l1 = eng.llr(src.y, bands, pn, variant=1, rows=row_d[a:b], start=start_d[a:b])
+                    l0 = eng.llr(y, bands, pn, variant=0, rows=row_d[a:b], start=start_d[a:b])
+                    l1 = eng.llr(y, bands, pn, variant=1, rows=row_d[a:b], start=start_d[a:b])
                     res = eng.scl(torch.cat((l0, -l0, l1, -l1), dim=0), list_size=L, skip_if_hard_ok=False)
                     payload, ok, _which = eng.select(res, ring=ring, key_idx=key_d[a:b].repeat(4), ctrs=ctr_d[a:b].repeat(4))
                     okc = ok.cpu().numpy().reshape(4, n).T

@@ -1,0 +1,131 @@
+"""The scan front end of WatermarkDetector and WatermarkIdentifier: from a list of clips with their rates to sync results with the
+peaks that can hold a frame.  Host code only: the clips of a call are cut into launches (cut_launches), a launch's samples reach the
+device in one place (Launch.rows) and one sync call finds its peaks (sync_launch).  Nothing here is keyed: header decodes and everything
+after them belong to the callers.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from .utils import resampled_length
+
+PRE_L = 63               # chips of the sync template (utils.mseq_63)
+FRAME_LEN = 1215         # PRE_L + 128 header chips + 1024 code bits
+PEAK_LIMIT = 25          # rtwm/detector.py:108
+
+# Padded samples (sync rows x longest clip) of one launch over clips of unequal length.  A memory bound, not a tuned value: a padded row
+# sample costs 20 bytes on the device (float32 in, float64 y, float64 corr), so 2^26 of them are 1.3 GB.
+RAGGED_ROW_SAMPLES = 1 << 26
+
+_DEVICE_SAMPLE_TYPES = (np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int16))      # what es_resample_ragged_batch reads
+
+
+def ragged_buckets(lengths, rows_per_clip: int, budget: int) -> list[list[int]]:
+    """Cut clips into launches: indices sorted by length (equal lengths in input order, hence adjacent), then taken greedily while
+    rows x longest clip = len(bucket) * rows_per_clip * max(length) <= budget.  A clip that is over the budget on its own still gets a
+    bucket, alone.  -> buckets of indices, lengths ascending within each and from bucket to bucket."""
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    out: list[list[int]] = []
+    cur: list[int] = []
+    for i in order:
+        if cur and (len(cur) + 1) * rows_per_clip * int(lengths[i]) > budget:      # lengths ascend: clip i would be the longest
+            out.append(cur); cur = []
+        cur.append(i)
+    if cur:
+        out.append(cur)
+    return out
+
+
+def _dev(eng, arr: np.ndarray, dtype):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=dtype)).to(eng.device)
+
+
+@dataclass
+class Launch:
+    """The clips of one sync launch, all of one sample type.  rates None: host signals already at fs_target (int16 or float32);
+    otherwise raw samples as they came, clip c at rates[c]."""
+    idx: list            # positions of the clips in the call
+    sizes: list          # length of each clip at fs_target
+    clips: list          # 1-D host arrays
+    rates: list | None
+    fs_target: int
+
+    def part(self, a: int, b: int) -> "Launch":
+        return Launch(self.idx[a:b], self.sizes[a:b], self.clips[a:b], None if self.rates is None else self.rates[a:b], self.fs_target)
+
+    def rows(self, eng, nb: int):
+        """-> (device rows [clips * nb, >= longest clip], row = clip * nb + band, clip c in the first sizes[c] samples of its rows;
+        sizes).  The one place that decides how samples reach the device."""
+        if self.rates is not None:
+            # conditioned on the device: ONE es_resample_ragged_batch launch writes the padded rows, no sample makes a round trip
+            rows, lens = eng.resample_ragged(self.clips, self.rates, self.fs_target, rep=nb)
+            return rows, [int(n) for n in lens]
+        M = max(self.sizes)
+        if min(self.sizes) == M:
+            host = np.stack(self.clips)
+        else:                                                               # unequal lengths: rows padded to the longest clip
+            host = np.zeros((len(self.clips), M), self.clips[0].dtype)
+            for c, sg in enumerate(self.clips):
+                host[c, :sg.size] = sg
+        return _dev(eng, np.repeat(host, nb, axis=0), host.dtype), self.sizes
+
+
+def cut_launches(clips, fs_list, fs_target: int, nb: int, condition, budget: int = RAGGED_ROW_SAMPLES) -> list[Launch]:
+    """Which clips share a sync launch: by sample type, then ragged_buckets over the lengths at fs_target (nb sync rows per clip).
+    Clips shorter than the template (rtwm/detector.py:71-73) are in none.  A call whose 1-D non-empty clips are all at fs_target takes
+    the host path: signals as float32 or int16 (what the band-pass kernels read), launches float32 then int16.  A call with any such
+    clip at another rate takes the device path: int16 / float32 / float64 clips stay raw, bucketed by their resampled
+    lengths, launches float32, float64, int16; 2-D, empty and oddly typed clips enter as host signals at fs_target.
+    condition(clip, rate) -> the clip at fs_target, on the host; asked only where rate != fs_target.  The budget holds for clips of
+    one length too: an over-budget group of equally long clips is several launches, each on the equal-length sync path."""
+    mixed = any(f != fs_target and np.ndim(c) == 1 and np.size(c) for c, f in zip(clips, fs_list))
+    arrs, rates = [], []
+    for c, f in zip(clips, fs_list):
+        a = np.asarray(c)
+        if not (mixed and a.ndim == 1 and a.size and a.dtype in _DEVICE_SAMPLE_TYPES):
+            a = (np.asarray(condition(a, f)) if f != fs_target else a).reshape(-1)
+            a, f = (a if a.dtype == np.int16 else a.astype(np.float32, copy=False)), fs_target
+        arrs.append(a); rates.append(int(f))
+    sizes = [resampled_length(a.size, f, fs_target) for a, f in zip(arrs, rates)]
+    out: list[Launch] = []
+    for dt in _DEVICE_SAMPLE_TYPES:                                         # (host path: no float64 signal is left)
+        idx = [i for i, a in enumerate(arrs) if a.dtype == dt and sizes[i] >= PRE_L]
+        for b in ragged_buckets([sizes[i] for i in idx], nb, budget):
+            ids = [idx[k] for k in b]
+            out.append(Launch(ids, [sizes[i] for i in ids], [arrs[i] for i in ids], [rates[i] for i in ids] if mixed else None, fs_target))
+    return out
+
+
+@dataclass
+class SyncScan:
+    """One launch after sync.  Peak j that can hold a frame = sy.y[rows[j], starts[j] : starts[j] + 1215], in (row, peak) order."""
+    sy: object           # the SyncResult as the kernels wrote it
+    sizes: list          # samples of each clip
+    nb: int              # sync rows per clip
+    rows: np.ndarray     # int64
+    starts: np.ndarray   # int64
+
+
+def sync_launch(eng, launch: Launch, band_ids) -> SyncScan:
+    """Band-pass, correlate and pick peaks for every (clip, band) of a launch in one sync call: row = clip * len(band_ids) + band."""
+    import torch
+    nb = len(band_ids)
+    x, sizes = launch.rows(eng, nb)
+    bid = _dev(eng, np.tile(np.asarray(band_ids, np.uint8), len(sizes)), np.uint8)
+    M = max(sizes)
+    if min(sizes) < M:
+        sy = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)
+    else:
+        x = x[:, :M]                                                        # (device rows: made contiguous there where the stride is longer)
+        sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
+    npk = (sy.npeaks.cpu().numpy() & 0xFFFF)
+    pk = sy.peaks.cpu().numpy()
+    rows, starts = [], []
+    for r in range(len(sizes) * nb):
+        for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
+            if st + FRAME_LEN <= sizes[r // nb]:                            # rtwm/detector.py:112-113, against the clip's own length
+                rows.append(r); starts.append(int(st))
+    return SyncScan(sy, sizes, nb, np.array(rows, np.int64), np.array(starts, np.int64))

@@ -4,7 +4,7 @@ and past M - 1215, header results that hit and miss, and hop schedules that make
 windows, and lists that reach MAX_TRIES in the middle of a peak."""
 import numpy as np
 
-from echoseal_amd.detector import FRAME_LEN, WatermarkDetector
+from echoseal_amd.detector import FRAME_LEN, WatermarkDetector, _Scan
 from echoseal_amd.utils import BAND_PLAN
 
 MAX_PEAKS = 32
@@ -69,8 +69,8 @@ def detector_plan(s):
     det = WatermarkDetector(bytes(32), list_size=1)
     det._hop = _Hop(s.hop)
     nf = s.fit.size
-    scan = {"bands": [BAND_PLAN[s.band]], "sel": np.arange(nf), "rows": np.zeros(nf, np.int64), "starts": s.fit.astype(np.int64),
-            "hdr": (s.hdr_ok.astype(bool), s.hdr_lo16.astype(np.int64), np.zeros(nf))}
+    scan = _Scan(bands=[BAND_PLAN[s.band]], src=None, sel=np.arange(nf), rows=np.zeros(nf, np.int64), starts=s.fit.astype(np.int64),
+                 hdr=(s.hdr_ok.astype(bool), s.hdr_lo16.astype(np.int64), np.zeros(nf)))
     plan, hdr_log = det._scan_plan(scan, 0)
     return [(start, ctr, h) for (_j, start, ctr, h) in plan], len(hdr_log)
 

@@ -256,7 +256,7 @@ def test_detector_in_place_headers_and_llrs_equal_gathered_frames(engine):
     det = WatermarkDetector(KEY, list_size=2, engine=engine)
     order = det._band_order()
     scan = det._scan_prepare([g["clip"].astype(np.float32)], order)[0]
-    src = scan["src"]
+    src = scan.src
     P = src.rows.size
     assert P > 20
     dev = engine.device
@@ -266,9 +266,9 @@ def test_detector_in_place_headers_and_llrs_equal_gathered_frames(engine):
     bid = torch.tensor([det._band_id(order[int(r) % len(order)]) for r in src.rows], dtype=torch.uint8, device=dev)
     hp = torch.from_numpy(np.packbits(det.sec.pn_bits(0, 128)).reshape(1, 16)).to(dev)
     ok, val, score = engine.header(frames, bid, hp)
-    assert np.array_equal(ok.cpu().numpy().astype(bool), scan["hdr"][0])
-    assert np.array_equal(val.cpu().numpy().astype(np.int64), scan["hdr"][1])
-    assert np.array_equal(score.cpu().numpy().astype(np.float64), scan["hdr"][2])
+    assert np.array_equal(ok.cpu().numpy().astype(bool), scan.hdr[0])
+    assert np.array_equal(val.cpu().numpy().astype(np.int64), scan.hdr[1])
+    assert np.array_equal(score.cpu().numpy().astype(np.float64), scan.hdr[2])
     ctrs = [int(round(s / FRAME_LEN)) for s in src.starts]
     pn, bands = engine.schedule(det.sec._prng.sub_key, det._band_key, ctrs=torch.tensor(ctrs, dtype=torch.int64))
     at = dict(rows=torch.from_numpy(src.rows.astype(np.int32)).to(dev), start=torch.from_numpy(src.starts.astype(np.int32)).to(dev))

@@ -1,5 +1,5 @@
 """CPU-side checks of batching recordings of unequal length: the C ABI surface of the two ragged entry points, the cut of a queue of
-clips into launches (detector.ragged_buckets), and the candidate planner's host twin with a sample count of its own per row."""
+clips into launches (scan.ragged_buckets and scan.cut_launches; detector re-exports the former), and the candidate planner's host twin with a sample count of its own per row."""
 import ctypes
 import os
 import re
@@ -75,13 +75,59 @@ def test_ragged_buckets():
     assert len(_check_buckets(lengths, 4, RAGGED_ROW_SAMPLES)) <= 4
 
 
+def _unreached(clip, rate):
+    raise AssertionError("a 1-D clip at fs_target, or of a sample type the device conditions, was handed to the host's conditioning")
+
+
 def test_launches_group_by_sample_type_and_leave_short_clips_out():
-    from echoseal_amd.detector import WatermarkDetector
+    from echoseal_amd.scan import cut_launches
     f = lambda n: np.zeros(n, np.float32)
     i = lambda n: np.zeros(n, np.int16)
     signals = [f(5000), i(700), f(62), f(63), i(0), f(5000), i(64), f(100)]
-    assert WatermarkDetector._launches(signals, 4) == [[3, 7, 0, 5], [6, 1]]
-    assert WatermarkDetector._launches([f(10), i(62)], 4) == []
+    cut = lambda sigs: cut_launches(sigs, [48_000] * len(sigs), 48_000, 4, _unreached)
+    assert [la.idx for la in cut(signals)] == [[3, 7, 0, 5], [6, 1]]
+    assert [la.idx for la in cut([f(10), i(62)])] == []
+    assert all(la.rates is None and [c.size for c in la.clips] == la.sizes for la in cut(signals))
+
+
+# (sample type, samples, rate): lengths at 48 kHz from 60 to 4 354; clips 3, 6, 10 and 15 are shorter than the 63-chip template as they
+# come and not after resampling; 4, 5, 13 and 14 stay shorter; 0 / 2 / 7 and 1 / 8 are equally long at 48 kHz across rates and types
+MIXED_QUEUE = [("f4", 3000, 48_000), ("i2", 2900, 44_100), ("f8", 1000, 16_000), ("f4", 30, 16_000), ("i2", 62, 48_000), ("f4", 20, 16_000),
+               ("f8", 60, 44_100), ("f4", 2756, 44_100), ("i2", 3157, 48_000), ("f8", 4100, 48_000), ("f4", 57, 44_100), ("i2", 500, 16_000),
+               ("f4", 4000, 44_100), ("f8", 62, 48_000), ("f4", 56, 44_100), ("i2", 21, 16_000)]
+
+
+def test_cut_launches_over_a_mixed_rate_queue():
+    """The expected idx lists are what the detector's two launch cutters of the commit before scan.py (one for calls with a clip at
+    another rate, one for calls without) returned for these queues, run on the CPU; the small budget, 4 rows x 3 clips x 3 000 samples,
+    splits every sample type."""
+    from echoseal_amd.scan import RAGGED_ROW_SAMPLES, Launch, cut_launches
+    from echoseal_amd.utils import resampled_length
+    clips = [np.zeros(n, dt) for dt, n, _ in MIXED_QUEUE]
+    rates = [fs for _, _, fs in MIXED_QUEUE]
+    want = {RAGGED_ROW_SAMPLES: [[10, 3, 0, 7, 12], [6, 2, 9], [15, 11, 1, 8]],                       # float32, float64, int16
+            4 * 3 * 3000: [[10, 3, 0], [7, 12], [6, 2], [9], [15, 11], [1, 8]]}
+    sizes = [resampled_length(n, fs, 48_000) for _, n, fs in MIXED_QUEUE]
+    assert min(sizes) < 63 and sizes[3] >= 63 > MIXED_QUEUE[3][1]
+    for budget, idx in want.items():
+        kw = {} if budget == RAGGED_ROW_SAMPLES else {"budget": budget}
+        launches = cut_launches(clips, rates, 48_000, 4, _unreached, **kw)
+        assert [la.idx for la in launches] == idx
+        for la in launches:
+            assert la.sizes == [sizes[i] for i in la.idx] and la.rates == [rates[i] for i in la.idx] and la.fs_target == 48_000
+            assert all(la.clips[k] is clips[i] for k, i in enumerate(la.idx))          # raw, as they came
+            assert len({c.dtype for c in la.clips}) == 1
+            part = la.part(1, 3)
+            assert isinstance(part, Launch) and (part.idx, part.sizes, part.rates) == (la.idx[1:3], la.sizes[1:3], la.rates[1:3])
+            assert all(a is b for a, b in zip(part.clips, la.clips[1:3]))
+    # the same lengths, all at 48 kHz: the host form, float32 (float64 clips converted) then int16
+    host = [np.zeros(n, dt) for (dt, _, _), n in zip(MIXED_QUEUE, sizes)]
+    launches = cut_launches(host, [48_000] * len(host), 48_000, 4, _unreached)
+    assert [la.idx for la in launches] == [[10, 6, 3, 0, 2, 7, 9, 12], [15, 11, 1, 8]]
+    assert [la.clips[0].dtype for la in launches] == [np.float32, np.int16]
+    for la in launches:
+        assert la.rates is None and la.sizes == [sizes[i] for i in la.idx] == [c.size for c in la.clips]
+        assert len({c.dtype for c in la.clips}) == 1
 
 
 def test_plan_reference_with_a_length_per_row_equals_scan_plan():
