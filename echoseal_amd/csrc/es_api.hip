@@ -585,6 +585,67 @@ int es_mix_ragged_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_st
                                       out_dev, scale_dev}, (hipStream_t)stream);
 }
 
+namespace {
+/* The records of a stream launch as the host laid them out, rec_host [R][ES_STREAM_REC_WORDS] = (sid, off, len, chip_base, chip_cnt): refused
+ * here, before anything is enqueued, where the kernels could only clamp. */
+int check_stream_records(es_ctx* ctx, const int64_t* rec, int64_t R, int64_t n_stride, int64_t S, int64_t chips_total)
+{
+    std::vector<uint8_t> seen((size_t)S, 0);
+    for (int64_t r = 0; r < R; ++r) {
+        const int64_t sid = rec[ES_STREAM_REC_WORDS * r], off = rec[ES_STREAM_REC_WORDS * r + 1], len = rec[ES_STREAM_REC_WORDS * r + 2];
+        const int64_t base = rec[ES_STREAM_REC_WORDS * r + 3], cnt = rec[ES_STREAM_REC_WORDS * r + 4];
+        if (sid < 0 || sid >= S) return fail(ctx, ES_EINVAL, "stream records: a sid outside the table");
+        if (seen[(size_t)sid]) return fail(ctx, ES_EINVAL, "stream records: a stream named twice in one launch");
+        seen[(size_t)sid] = 1;
+        if (off < 0 || off >= ES_FRAME_LEN) return fail(ctx, ES_EINVAL, "stream records: off outside 0 .. 1214");
+        if (len < 0 || len > n_stride) return fail(ctx, ES_EINVAL, "stream records: a length outside 0 .. n_stride");
+        const int64_t end = (off > 0 ? off : ES_FRAME_LEN) + len;
+        if (cnt != ((end + ES_FRAME_LEN - 1) / ES_FRAME_LEN - 1) * ES_FRAME_LEN)
+            return fail(ctx, ES_EINVAL, "stream records: chip_cnt is not 1215 * the new frames the chunk needs");
+        if (base < 0 || cnt > chips_total || base > chips_total - cnt)
+            return fail(ctx, ES_EINVAL, "stream records: the pool is shorter than chip_base + chip_cnt");
+    }
+    return ES_OK;
+}
+}  // namespace
+
+int es_mix_stream_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_stride, const int64_t* len_dev, int block,
+                        const int64_t* sid_dev, int64_t S, const float* tail_dev, const int64_t* off_dev, const float* chips_dev,
+                        int64_t chips_total, const int64_t* chip_base_dev, const int64_t* chip_cnt_dev, const int64_t* rec_host,
+                        double alpha, double floor, float* out_dev, double* scale_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (block < 1) return fail(ctx, ES_EINVAL, "es_mix_stream_batch: block must be >= 1");
+    if (R < 0 || n_stride < 0 || chips_total < 0 || S < 0) return fail(ctx, ES_EINVAL, "es_mix_stream_batch: negative size");
+    if (R == 0 || n_stride == 0) return ES_OK;
+    if (!x_dev || !len_dev || !sid_dev || !tail_dev || !off_dev || !chip_base_dev || !chip_cnt_dev || !rec_host || !out_dev ||
+        (!chips_dev && chips_total > 0))
+        return fail(ctx, ES_EINVAL, "es_mix_stream_batch: null pointer");
+    if (out_dev != x_dev && out_dev < x_dev + R * n_stride && x_dev < out_dev + R * n_stride)
+        return fail(ctx, ES_EINVAL, "es_mix_stream_batch: out_dev partly overlaps x_dev (only out_dev == x_dev may alias)");
+    const int rc = check_stream_records(ctx, rec_host, R, n_stride, S, chips_total);
+    if (rc != ES_OK) return rc;
+    DeviceGuard g(ctx->device);
+    return es_launch_mix_stream(ctx, {x_dev, R, n_stride, len_dev, block, sid_dev, S, tail_dev, off_dev, chips_dev, chips_total, chip_base_dev,
+                                      chip_cnt_dev, alpha, floor, out_dev, scale_dev}, (hipStream_t)stream);
+}
+
+int es_stream_commit_batch(es_ctx* ctx, int64_t R, int64_t n_stride, const int64_t* len_dev, const int64_t* sid_dev, int64_t S,
+                           float* tail_dev, int64_t* ctr_dev, int64_t* off_dev, const float* chips_dev, int64_t chips_total,
+                           const int64_t* chip_base_dev, const int64_t* chip_cnt_dev, const int64_t* rec_host, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (R < 0 || n_stride < 0 || chips_total < 0 || S < 0) return fail(ctx, ES_EINVAL, "es_stream_commit_batch: negative size");
+    if (R == 0) return ES_OK;
+    if (!len_dev || !sid_dev || !tail_dev || !ctr_dev || !off_dev || !chip_base_dev || !chip_cnt_dev || !rec_host || (!chips_dev && chips_total > 0))
+        return fail(ctx, ES_EINVAL, "es_stream_commit_batch: null pointer");
+    const int rc = check_stream_records(ctx, rec_host, R, n_stride, S, chips_total);
+    if (rc != ES_OK) return rc;
+    DeviceGuard g(ctx->device);
+    return es_launch_stream_commit(ctx, {R, n_stride, len_dev, sid_dev, S, tail_dev, ctr_dev, off_dev, chips_dev, chips_total, chip_base_dev,
+                                         chip_cnt_dev}, (hipStream_t)stream);
+}
+
 int es_tx_frames_keyed_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
                              const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* ring_dev, int64_t N,
                              const int32_t* key_dev, int64_t B, double* y_ws_dev, float* frames_dev, void* stream)

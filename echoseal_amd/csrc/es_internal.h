@@ -180,6 +180,21 @@ struct es_mix_ragged_args {
     double alpha; double floor_lin; float* out; double* scale_out;
 };
 int es_launch_mix_ragged(es_ctx* ctx, const es_mix_ragged_args& a, hipStream_t st);
+/* chunks of live streams: record r continues stream sid[r] of a table of S (tail [S][1215], off [S]); its new frames lie in the pool
+ * (es_mix_stream_batch; es_mix.hip) */
+struct es_mix_stream_args {
+    const float* x; int64_t R; int64_t n_stride; const int64_t* len; int block;
+    const int64_t* sid; int64_t S; const float* tail; const int64_t* off;
+    const float* chips; int64_t chips_total; const int64_t* chip_base; const int64_t* chip_cnt;
+    double alpha; double floor_lin; float* out; double* scale_out;
+};
+int es_launch_mix_stream(es_ctx* ctx, const es_mix_stream_args& a, hipStream_t st);
+/* ... and the state of the pushed streams after that mix (es_stream_commit_batch; es_mix.hip) */
+struct es_stream_commit_args {
+    int64_t R; int64_t n_stride; const int64_t* len; const int64_t* sid; int64_t S; float* tail; int64_t* ctr; int64_t* off;
+    const float* chips; int64_t chips_total; const int64_t* chip_base; const int64_t* chip_cnt;
+};
+int es_launch_stream_commit(es_ctx* ctx, const es_stream_commit_args& a, hipStream_t st);
 /* es_launch_tx_frames with the header PN of frame f read from ring row key[f] (es_tx.hip): no host memory, only enqueues */
 int es_launch_tx_frames_keyed(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows, const uint8_t* band, const uint32_t* ctr,
                               unsigned long long pre_bits, const uint8_t* ring, int64_t N, const int32_t* key, int64_t B, double* y_ws,

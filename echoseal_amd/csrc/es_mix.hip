@@ -20,9 +20,12 @@
 // tree of a chunk (depth <= 7 for n <= 8192) is laid out as a binary heap, thread k = node k; blocks of up to 8192 samples stay in
 // registers for the final pass, longer ones are read again.
 //
-// Both kernels are written once, in es_mix_body.inc, and compiled twice: for recordings of one length (es_mix_batch) and for records of
+// Both kernels are written once, in es_mix_body.inc, and compiled three times: for recordings of one length (es_mix_batch), for records of
 // unequal length in rows of one stride that take their chips from one flat pool of frames (es_mix_ragged_batch: the same block arithmetic;
-// a record's blocks are those of its own length, block slots past its end do no work and write nothing).
+// a record's blocks are those of its own length, block slots past its end do no work and write nothing), and for chunks of live streams
+// (es_mix_stream_batch: the ragged form whose record first uses up the frame its stream stands in, read from the stream table where it
+// lies).  es_stream_commit_kernel then moves every pushed stream on (es_stream_commit_batch): a launch of its own, because many
+// workgroups of the mix read a stream's pending frame.
 //
 // A product or sum that is invalid (inf * 0, inf - inf) gives the negative quiet NaN the host's SSE arithmetic gives; NaNs that are
 // already in x or the chips propagate unchanged on both.
@@ -123,16 +126,73 @@ __device__ __forceinline__ long long ragged_record(long long len, long long n, l
     return len < 0 ? 0 : (len > n ? n : len);
 }
 
+// Record r of a stream batch, a chunk of stream s: its chips are the row [the frame the stream stands in | the record's new frames], and
+// its first sample takes row position `start` = off[s], or ES_FRAME_LEN where nothing is pending (off[s] = 0, and any off outside
+// 1 .. ES_FRAME_LEN - 1).  -> its length clamped to [0, n], 0 for a stream outside the table; the new chips cut to the pool as
+// ragged_record cuts them -> chips[lo .. hi], hi < lo where the record has none.
+__device__ __forceinline__ long long stream_record(long long len, long long n, long long s, long long S, const long long* __restrict__ off,
+                                                   long long base, long long cnt, long long total, long long& lo, long long& hi, long long& start)
+{
+    ragged_record(len, n, base, cnt, total, lo, hi);
+    start = ES_FRAME_LEN;
+    if (s < 0 || s >= S) return 0;
+    const long long o = off[s];
+    if (o > 0 && o < ES_FRAME_LEN) start = o;
+    return len < 0 ? 0 : (len > n ? n : len);
+}
+
+// chip i of a stream record, i counted in the pool as if the pending frame tl[0 .. ES_FRAME_LEN) lay right before the new frames (at pb):
+// below pb + ES_FRAME_LEN the pending frame, from there on the pool, clamped to the record's new chips (none: the pending frame's last chip)
+__device__ __forceinline__ float stream_chip(const float* __restrict__ tl, const float* __restrict__ cp, long long pb, long long i,
+                                             long long lo, long long hi)
+{
+    const long long p = i - pb;
+    const float* src = (p < ES_FRAME_LEN || hi < lo) ? tl + clamp_ll(p, ES_FRAME_LEN - 1) : cp + clamp_lh(i, lo, hi);     // one load
+    return *src;
+}
+
 #define ES_RAGGED 0
-#define MIX_CHIP_AT(i) clamp_ll(i, hi)
+#define MIX_CHIP(i) cp[clamp_ll(i, hi)]
 #include "es_mix_body.inc"
-#undef MIX_CHIP_AT
+#undef MIX_CHIP
 #undef ES_RAGGED
 #define ES_RAGGED 1          // the same kernels for records of unequal length in one row stride, chips from one pool
-#define MIX_CHIP_AT(i) clamp_lh(i, lo, hi)
+#define MIX_CHIP(i) cp[clamp_lh(i, lo, hi)]
 #include "es_mix_body.inc"
-#undef MIX_CHIP_AT
+#undef MIX_CHIP
 #undef ES_RAGGED
+#define ES_RAGGED 2          // ... and for chunks of live streams: the stream's pending frame first, then new frames from the pool
+#define MIX_CHIP(i) stream_chip(tl, cp, pb, i, lo, hi)
+#include "es_mix_body.inc"
+#undef MIX_CHIP
+#undef ES_RAGGED
+
+// After the mix of a stream batch: record r moves stream s = sid[r] on.  The chunk ends at row position end = start + len; the stream now
+// stands in frame slot = end / 1215 of the row when chips of it are left (end % 1215 > 0), in the frame it has just used up when the chunk
+// ended on a frame edge; slot 0 is the frame it stood in before, which stays.  One workgroup per record; records of one launch name
+// different streams (the host checks), so no two workgroups write one row.
+__global__ __launch_bounds__(MIX_THREADS) void es_stream_commit_kernel(long long R, long long n, const long long* __restrict__ rec_len,
+        const long long* __restrict__ sid, long long S, float* tails, long long* ctr, long long* off, const float* __restrict__ chips,
+        long long chips_total, const long long* __restrict__ chip_base, const long long* __restrict__ chip_cnt)
+{
+    for (long long r = blockIdx.x; r < R; r += gridDim.x) {
+        const long long s = sid[r];
+        long long lo, hi, start;
+        const long long len = stream_record(rec_len[r], n, s, S, off, chip_base[r], chip_cnt[r], chips_total, lo, hi, start);
+        if (s < 0 || s >= S) continue;                                         // block-uniform
+        const long long end = start + len, o = end % ES_FRAME_LEN;
+        const long long slot = o > 0 ? end / ES_FRAME_LEN : end / ES_FRAME_LEN - 1;          // end >= 1, and >= 1215 where o == 0
+        const long long src = chip_base[r] + (slot - 1) * ES_FRAME_LEN;
+        if (slot > 0 && src >= lo && src + ES_FRAME_LEN - 1 <= hi) {
+            for (int i = threadIdx.x; i < ES_FRAME_LEN; i += MIX_THREADS) tails[s * ES_FRAME_LEN + i] = chips[src + i];
+        }
+        __syncthreads();                                                       // every thread has read off[s]
+        if (threadIdx.x == 0) {
+            ctr[s] = (ctr[s] + (end + ES_FRAME_LEN - 1) / ES_FRAME_LEN - 1) & 0xFFFFFFFFll;
+            off[s] = o;
+        }
+    }
+}
 
 }  // namespace
 
@@ -176,4 +236,35 @@ int es_launch_mix_ragged(es_ctx* ctx, const es_mix_ragged_args& a, hipStream_t s
     return es_launch(ctx, a.block <= MIX_CHUNK ? es_mix_ragged_block_kernel<true> : es_mix_ragged_block_kernel<false>,
                      es_grid(tail_only ? a.R : a.R * nblk, 1, cap), MIX_THREADS, 0, st, a.x, (long long)a.R, (long long)a.n_stride, (long long)a.block,
                      tail_only, len, a.chips, (long long)a.chips_total, base, cnt, a.alpha, a.floor_lin, a.out, a.scale_out, nblk);
+}
+
+int es_launch_mix_stream(es_ctx* ctx, const es_mix_stream_args& a, hipStream_t st)
+{
+    const long long nblk = (a.n_stride + a.block - 1) / a.block;
+    const long long cap = (long long)ctx->num_cu * 2048;                      // the kernels stride over what a larger batch adds
+    const long long* len = (const long long*)a.len; const long long* sid = (const long long*)a.sid; const long long* off = (const long long*)a.off;
+    const long long* base = (const long long*)a.chip_base; const long long* cnt = (const long long*)a.chip_cnt;
+    int tail_only = 0;
+    // the cut of es_launch_mix_ragged: one wave per full block, each record's short last block on the workgroup kernel
+    if (a.block == 1024 && a.n_stride % 4 == 0 && ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0) {
+        const long long nfull = a.n_stride / 1024;
+        if (nfull) {
+            const int rc = es_launch(ctx, es_mix_stream_wave_kernel, es_grid(a.R * nfull, 4, cap), MIX_THREADS, 0, st, a.x, (long long)a.R,
+                                     (long long)a.n_stride, nfull, len, sid, (long long)a.S, a.tail, off, a.chips, (long long)a.chips_total, base, cnt,
+                                     a.alpha, a.floor_lin, a.out, a.scale_out, nblk);
+            if (rc != ES_OK) return rc;
+        }
+        tail_only = 1;
+    }
+    return es_launch(ctx, a.block <= MIX_CHUNK ? es_mix_stream_block_kernel<true> : es_mix_stream_block_kernel<false>,
+                     es_grid(tail_only ? a.R : a.R * nblk, 1, cap), MIX_THREADS, 0, st, a.x, (long long)a.R, (long long)a.n_stride, (long long)a.block,
+                     tail_only, len, sid, (long long)a.S, a.tail, off, a.chips, (long long)a.chips_total, base, cnt, a.alpha, a.floor_lin, a.out,
+                     a.scale_out, nblk);
+}
+
+int es_launch_stream_commit(es_ctx* ctx, const es_stream_commit_args& a, hipStream_t st)
+{
+    return es_launch(ctx, es_stream_commit_kernel, es_grid(a.R, 1, (long long)ctx->num_cu * 2048), MIX_THREADS, 0, st, (long long)a.R,
+                     (long long)a.n_stride, (const long long*)a.len, (const long long*)a.sid, (long long)a.S, a.tail, (long long*)a.ctr,
+                     (long long*)a.off, a.chips, (long long)a.chips_total, (const long long*)a.chip_base, (const long long*)a.chip_cnt);
 }

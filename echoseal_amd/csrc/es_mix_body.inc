@@ -1,10 +1,19 @@
-// es_mix_body.inc -- the two level-mix kernels, included twice by es_mix.hip: ES_RAGGED 0 = es_mix_wave_kernel / es_mix_block_kernel (every
-// recording n samples, chip row r of chips_stride chips), ES_RAGGED 1 = es_mix_ragged_wave_kernel / es_mix_ragged_block_kernel (recording r
-// has len[r] samples in a row of n, its chips lie at chip_base[r] of one flat pool).  The arithmetic of a block is one text; what differs is
-// where a block's samples and chips lie and which block slots exist.
+// es_mix_body.inc -- the two level-mix kernels, included three times by es_mix.hip: ES_RAGGED 0 = es_mix_wave_kernel / es_mix_block_kernel
+// (every recording n samples, chip row r of chips_stride chips), ES_RAGGED 1 = es_mix_ragged_wave_kernel / es_mix_ragged_block_kernel
+// (recording r has len[r] samples in a row of n, its chips lie at chip_base[r] of one flat pool), ES_RAGGED 2 = es_mix_stream_wave_kernel /
+// es_mix_stream_block_kernel (record r is a chunk of stream sid[r]: its chips are the rest of the stream's pending frame, tails[sid[r]] from
+// off[sid[r]] on, and then the record's new frames at chip_base[r] of the pool; both are read where they lie).  The arithmetic of a block
+// is one text; what differs is where a block's samples and chips lie and which block slots exist.  MIX_CHIP(i): chip i of the row or pool.
 
 // ---------------------------------------------------------------------------------------------------------------- block = 1024
-#if ES_RAGGED
+#if ES_RAGGED == 2
+// the ragged kernel's slots; c0 = pool index of the block's first chip, as if the pending frame lay in the pool right before chip_base[r]
+__global__ __launch_bounds__(MIX_THREADS) void es_mix_stream_wave_kernel(const float* __restrict__ x, long long R, long long n, long long nfull,
+        const long long* __restrict__ rec_len, const long long* __restrict__ sid, long long S, const float* __restrict__ tails,
+        const long long* __restrict__ off, const float* __restrict__ chips, long long chips_total, const long long* __restrict__ chip_base,
+        const long long* __restrict__ chip_cnt, double alpha, double floor_lin, float* __restrict__ out, double* __restrict__ scale_out,
+        long long nblk)
+#elif ES_RAGGED
 // slot g = (row r, block b) of R * nfull slots, nfull = n / 1024: only the slots that are full blocks of their record do work
 __global__ __launch_bounds__(MIX_THREADS) void es_mix_ragged_wave_kernel(const float* __restrict__ x, long long R, long long n, long long nfull,
         const long long* __restrict__ rec_len, const float* __restrict__ chips, long long chips_total, const long long* __restrict__ chip_base,
@@ -24,7 +33,15 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_wave_kernel(const float* _
         const long long r = g / nfull, b = g - r * nfull;
         const long long t0 = b * 1024;
         const float* xp = x + r * n + t0;
-#if ES_RAGGED
+#if ES_RAGGED == 2
+        long long lo, hi, start;                                               // the record's new chips: chips[lo .. hi] of the pool
+        if (t0 + 1024 > stream_record(rec_len[r], n, sid[r], S, off, chip_base[r], chip_cnt[r], chips_total, lo, hi, start)) continue;
+        const long long pb = chip_base[r] - ES_FRAME_LEN;                      // where the pending frame would start
+        const long long c0 = pb + start + t0;
+        const float* cp = chips;
+        const float* tl = tails + sid[r] * ES_FRAME_LEN;
+        const bool c_fast = start + t0 >= ES_FRAME_LEN && c0 >= lo && c0 + 1024 <= hi + 1 && (((uintptr_t)(cp + c0)) & 15) == 0;   // wave-uniform
+#elif ES_RAGGED
         long long lo, hi;                                                      // the record's chips: chips[lo .. hi] of the pool
         if (t0 + 1024 > ragged_record(rec_len[r], n, chip_base[r], chip_cnt[r], chips_total, lo, hi)) continue;   // wave-uniform
         const long long c0 = chip_base[r] + t0;                                // first chip of the block within the pool
@@ -41,23 +58,15 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_wave_kernel(const float* _
         if (c_fast) {
             #pragma unroll
             for (int k = 0; k < 4; ++k) cv[k] = *reinterpret_cast<const float4*>(cp + c0 + 256 * k + 4 * lane);
-        } else {                                                               // unaligned rows, and offsets that leave the row (clamped)
-#if ES_RAGGED
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const long long e = c0 + 256 * k + 4 * lane;
-                cv[k].x = cp[clamp_lh(e, lo, hi)]; cv[k].y = cp[clamp_lh(e + 1, lo, hi)];
-                cv[k].z = cp[clamp_lh(e + 2, lo, hi)]; cv[k].w = cp[clamp_lh(e + 3, lo, hi)];
-            }
-#else
+        } else {                                                               // unaligned rows, offsets that leave the row (clamped), two sources
+#if !ES_RAGGED
             const long long hi = chips_stride - 1;
+#endif
             #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const long long e = c0 + 256 * k + 4 * lane;
-                cv[k].x = cp[clamp_ll(e, hi)]; cv[k].y = cp[clamp_ll(e + 1, hi)];
-                cv[k].z = cp[clamp_ll(e + 2, hi)]; cv[k].w = cp[clamp_ll(e + 3, hi)];
+                cv[k].x = MIX_CHIP(e); cv[k].y = MIX_CHIP(e + 1); cv[k].z = MIX_CHIP(e + 2); cv[k].w = MIX_CHIP(e + 3);
             }
-#endif
         }
         float mx = 0.0f, mc = 0.0f;
         #pragma unroll
@@ -99,7 +108,14 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_wave_kernel(const float* _
 
 // ---------------------------------------------------------------------------------------------------------------- any block length
 // KEEP: the block is one chunk (m <= 8192) and stays in registers for the final pass
-#if ES_RAGGED
+#if ES_RAGGED == 2
+template <bool KEEP>
+__global__ __launch_bounds__(MIX_THREADS) void es_mix_stream_block_kernel(const float* __restrict__ x, long long R, long long n, long long block,
+        int tail_only, const long long* __restrict__ rec_len, const long long* __restrict__ sid, long long S, const float* __restrict__ tails,
+        const long long* __restrict__ off, const float* __restrict__ chips, long long chips_total, const long long* __restrict__ chip_base,
+        const long long* __restrict__ chip_cnt, double alpha, double floor_lin, float* __restrict__ out, double* __restrict__ scale_out,
+        long long nblk)
+#elif ES_RAGGED
 // tail_only: item g = record g's short last block (the full ones ran on the wave kernel); else item g = (row, block slot) of R * nblk
 template <bool KEEP>
 __global__ __launch_bounds__(MIX_THREADS) void es_mix_ragged_block_kernel(const float* __restrict__ x, long long R, long long n, long long block,
@@ -131,15 +147,26 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_block_kernel(const float* 
     for (long long g = blockIdx.x; g < total; g += gridDim.x) {
 #if ES_RAGGED
         const long long r = tail_only ? g : g / nblk;
+#if ES_RAGGED == 2
+        long long lo, hi, start;                                               // the record's new chips: chips[lo .. hi] of the pool
+        const long long nr = stream_record(rec_len[r], n, sid[r], S, off, chip_base[r], chip_cnt[r], chips_total, lo, hi, start);
+#else
         long long lo, hi;                                                      // the record's chips: chips[lo .. hi] of the pool
         const long long nr = ragged_record(rec_len[r], n, chip_base[r], chip_cnt[r], chips_total, lo, hi);
+#endif
         const long long b = tail_only ? nr / block : g - r * nblk;
         const long long t0 = b * block;
         if (t0 >= nr) continue;                                                // a slot past the record's end (block-uniform)
         const long long m = (nr - t0 < block) ? (nr - t0) : block;
         const float* xp = x + r * n + t0;
         const float* cp = chips;
+#if ES_RAGGED == 2
+        const long long pb = chip_base[r] - ES_FRAME_LEN;                      // where the pending frame would start
+        const long long c0 = pb + start + t0;
+        const float* tl = tails + sid[r] * ES_FRAME_LEN;
+#else
         const long long c0 = chip_base[r] + t0;
+#endif
 #else
         const long long r = g / b_count, b = b_first + (g - r * b_count);
         const long long t0 = b * block;
@@ -159,14 +186,14 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_block_kernel(const float* 
                 for (int i = 0; i < MIX_KEEP; ++i) {
                     const int e = t + MIX_THREADS * i;
                     if (e < nc) {
-                        xr[i] = xp[e]; cr[i] = cp[MIX_CHIP_AT(c0 + e)];
+                        xr[i] = xp[e]; cr[i] = MIX_CHIP(c0 + e);
                         sq[sq_at(e)] = xr[i] * xr[i];
                         mx = max_nan(mx, __builtin_fabsf(xr[i])); mc = max_nan(mc, __builtin_fabsf(cr[i]));
                     }
                 }
             } else {
                 for (int e = t; e < nc; e += MIX_THREADS) {
-                    const float xv = xp[ch + e], cv = cp[MIX_CHIP_AT(c0 + ch + e)];
+                    const float xv = xp[ch + e], cv = MIX_CHIP(c0 + ch + e);
                     sq[sq_at(e)] = xv * xv;
                     mx = max_nan(mx, __builtin_fabsf(xv)); mc = max_nan(mc, __builtin_fabsf(cv));
                 }
@@ -208,7 +235,7 @@ __global__ __launch_bounds__(MIX_THREADS) void es_mix_block_kernel(const float* 
                 if (e < (int)m) op[e] = mix_one(xr[i], cr[i], sf);
             }
         } else {
-            for (long long e = t; e < m; e += MIX_THREADS) op[e] = mix_one(xp[e], cp[MIX_CHIP_AT(c0 + e)], sf);
+            for (long long e = t; e < m; e += MIX_THREADS) op[e] = mix_one(xp[e], MIX_CHIP(c0 + e), sf);
         }
     }
 }

@@ -166,6 +166,64 @@ def embed_launches(lengths, ctr0, budget: int | None = None) -> list:
 
 
 @dataclass
+class StreamLayout:
+    """Where the frames of one tick of live streams lie (stream_layout)."""
+    start: np.ndarray          # [R] int64 position of the chunk's first chip in the row [pending frame | new frames]: off, or 1215 where off == 0
+    nf: np.ndarray             # [R] int64 new frames chunk r generates: ceil((start + len) / 1215) - 1
+    rec: np.ndarray            # [F] int64 chunk of each frame of the flat frame list (chunk by chunk, counters ascending)
+    ctr: np.ndarray            # [F] int64 counter of each frame: (ctr[rec] + k) mod 2^32
+    chip_base: np.ndarray      # [R] int64 = 1215 * index of chunk r's first new frame in the flat list
+    chip_cnt: np.ndarray       # [R] int64 = 1215 * nf[r]
+    ctr_next: np.ndarray       # [R] int64 the stream's counter after the chunk: (ctr + nf) mod 2^32
+    off_next: np.ndarray       # [R] int64 chips of the frame the stream then stands in already used: (start + len) mod 1215
+
+
+def stream_layout(off, ctr, lengths) -> StreamLayout:
+    """The frames one tick generates, as successive WatermarkEmbedder.process calls do (rtwm/embedder.py:44-62: a frame is made whenever
+    the chip buffer runs short): chunk r of lengths[r] samples continues a stream that has used off[r] chips of the frame it stands in
+    (0 = nothing pending) and makes its next frame under counter ctr[r].  It first uses up the 1215 - off[r] pending chips, then
+    ceil((start + len) / 1215) - 1 new frames of consecutive counters mod 2^32 -- what `embed` computes as `new` with carry=.  A pure
+    host function."""
+    FL = nat.ES_FRAME_LEN
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    off = np.asarray(off, dtype=np.int64).reshape(-1)
+    c0 = np.asarray(ctr, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
+    if off.shape != n.shape or c0.shape != n.shape:
+        raise ValueError("off, ctr, lengths: one entry per chunk")
+    if n.size and n.min() < 0:
+        raise ValueError("negative chunk length")
+    if off.size and (off.min() < 0 or off.max() >= FL):
+        raise ValueError(f"off outside [0, {FL})")
+    start = np.where(off > 0, off, FL)
+    end = start + n
+    nf = (end + FL - 1) // FL - 1
+    first = np.cumsum(nf) - nf
+    rec = np.repeat(np.arange(n.size, dtype=np.int64), nf)
+    k = np.arange(int(nf.sum()), dtype=np.int64) - first[rec]
+    return StreamLayout(start, nf, rec, (c0[rec] + k) & 0xFFFFFFFF, first * FL, nf * FL, (c0 + nf) & 0xFFFFFFFF, end % FL)
+
+
+@dataclass
+class StreamTable:
+    """The state of S live streams on the device (RxEngine.open_streams); RxEngine.embed_step marks chunks of any of them and moves
+    them on.  Row s is what EmbedResult.ctr / off / tail are for one stream."""
+    ring: KeyRing
+    key: torch.Tensor          # [S] int32 ring row of each stream
+    ctr: torch.Tensor          # [S] int64 counter of the next frame to generate, 0 .. 2^32 - 1
+    off: torch.Tensor          # [S] int64 chips of the current frame already used (0 = nothing pending)
+    tail: torch.Tensor         # [S, 1215] float32 the frame the stream stands in
+    nonce8: torch.Tensor       # [S, 8] uint8 session nonce, fixed when the stream is opened
+    key_host: np.ndarray       # [S] int64 host copy of `key`
+    ctr_host: np.ndarray       # [S] int64 host mirror of `ctr`: a tick lays out its frames without a copy from the device
+    off_host: np.ndarray       # [S] int64 host mirror of `off`
+    live: np.ndarray           # [S] bool; False: a closed row, free for add_streams
+
+    @property
+    def n(self) -> int:
+        return int(self.live.size)
+
+
+@dataclass
 class KeyRing:
     """Keys as device data (es_keyring_derive_batch): row k of `ring` holds what the keyed kernels need of key k (layout:
     include/echoseal_hip.h)."""
@@ -947,7 +1005,8 @@ class RxEngine:
         The clips are cut into launches by scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its clips into one
         [clips, longest rounded up to 4] tensor and runs ONE sequence whatever the number of keys and lengths: keyed seal (if needed) ->
         polar encode -> keyed schedule -> keyed frame generator -> ragged mix, over a flat frame list (embed_layout).
-        Continuing a stream across calls (`carry`) stays with `embed`.  -> [EmbedClip], one per clip in input order."""
+        Every clip starts a stream of its own; streams that continue across calls are `embed_step`'s (many streams, each under its
+        key, one sequence per tick) or, one key at a time, `embed(carry=)`'s.  -> [EmbedClip], one per clip in input order."""
         ring = keys if isinstance(keys, KeyRing) else self.keyring(keys)
         clips = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in clips]
         R = len(clips)
@@ -1016,6 +1075,170 @@ class RxEngine:
                 n_i = int(lengths[i])
                 out[i] = EmbedClip(marked[j, :n_i], int(sub.ctr_next[j]), int(sub.off[j]),
                                    scale[j, :(n_i + block - 1) // block] if want_scale else None)
+        return out
+
+    # ------------------------------------------------------------------ live streams: many keys, chunk by chunk
+    def _stream_rows(self, ring: KeyRing, key_idx, ctr0, session_nonces):
+        """Checked host rows of new streams -> (key int64 [n], ctr int64 [n], nonce8 uint8 [n, 8])."""
+        import secrets as _secrets
+        kidx = np.asarray(key_idx.cpu().numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
+        n = kidx.size
+        if n and (kidx.min() < 0 or kidx.max() >= ring.n):
+            raise ValueError(f"key index outside [0, {ring.n})")
+        if np.ndim(ctr0) and np.size(ctr0) != n:
+            raise ValueError("ctr0: a scalar or one value per stream")
+        c0 = (np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.full(n, int(ctr0), np.int64)) & 0xFFFFFFFF
+        if session_nonces is None:
+            session_nonces = [_secrets.token_bytes(8) for _ in range(n)]
+        session_nonces = [bytes(sn) for sn in session_nonces]
+        if len(session_nonces) != n or any(len(sn) != 8 for sn in session_nonces):
+            raise ValueError("session_nonces: 8 bytes per stream")
+        return kidx, c0, np.frombuffer(b"".join(session_nonces), np.uint8).reshape(n, 8).copy()
+
+    def open_streams(self, keys_or_ring, key_idx, *, ctr0=0, session_nonces=None) -> StreamTable:
+        """A table of len(key_idx) live streams: stream s is marked under keys[key_idx[s]], makes its first frame under counter ctr0[s]
+        (a scalar serves all, wraps at 2^32) and has nothing pending -- an embedder that has processed nothing.  session_nonces: the 8
+        bytes stream s puts into every plaintext it seals (default fresh per stream).  keys_or_ring: a KeyRing or 32-byte keys."""
+        ring = keys_or_ring if isinstance(keys_or_ring, KeyRing) else self.keyring(keys_or_ring)
+        kidx, c0, n8 = self._stream_rows(ring, key_idx, ctr0, session_nonces)
+        S = kidx.size
+        return StreamTable(ring, torch.from_numpy(kidx.astype(np.int32)).to(self.device), torch.from_numpy(c0).to(self.device),
+                           torch.zeros(S, dtype=torch.int64, device=self.device),
+                           torch.zeros((S, nat.ES_FRAME_LEN), dtype=torch.float32, device=self.device), torch.from_numpy(n8).to(self.device),
+                           kidx.copy(), c0.copy(), np.zeros(S, np.int64), np.ones(S, bool))
+
+    def add_streams(self, table: StreamTable, key_idx, *, ctr0=0, session_nonces=None) -> np.ndarray:
+        """More streams for `table` (arguments of open_streams): closed rows are used first, lowest first, then the table grows.
+        -> their stream ids, int64."""
+        kidx, c0, n8 = self._stream_rows(table.ring, key_idx, ctr0, session_nonces)
+        n, S = kidx.size, table.n
+        ids = np.concatenate((np.flatnonzero(~table.live)[:n], np.arange(S, S + n, dtype=np.int64)))[:n]
+        grow = int(np.count_nonzero(ids >= S))
+        if grow:
+            ext = lambda t, *shape: torch.cat((t, torch.zeros((grow,) + shape, dtype=t.dtype, device=t.device)))
+            table.key, table.ctr, table.off = ext(table.key), ext(table.ctr), ext(table.off)
+            table.tail, table.nonce8 = ext(table.tail, nat.ES_FRAME_LEN), ext(table.nonce8, 8)
+            table.key_host, table.ctr_host, table.off_host = (np.concatenate((a, np.zeros(grow, np.int64)))
+                                                              for a in (table.key_host, table.ctr_host, table.off_host))
+            table.live = np.concatenate((table.live, np.zeros(grow, bool)))
+        if n:
+            rows = torch.from_numpy(ids).to(self.device)
+            table.key[rows] = torch.from_numpy(kidx.astype(np.int32)).to(self.device)
+            table.ctr[rows] = torch.from_numpy(c0).to(self.device)
+            table.off[rows] = 0
+            table.tail[rows] = 0.0
+            table.nonce8[rows] = torch.from_numpy(n8).to(self.device)
+            table.key_host[ids], table.ctr_host[ids], table.off_host[ids], table.live[ids] = kidx, c0, 0, True
+        return ids
+
+    def close_streams(self, table: StreamTable, sid) -> None:
+        """Free the rows of streams `sid`: embed_step refuses them until add_streams hands the rows out again."""
+        table.live[self._stream_ids(table, sid)] = False
+
+    @staticmethod
+    def _stream_ids(table: StreamTable, sid) -> np.ndarray:
+        """Stream ids as int64, each inside the table, open and named once."""
+        ids = np.asarray(sid.cpu().numpy() if torch.is_tensor(sid) else sid, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= table.n):
+            raise ValueError(f"stream id outside [0, {table.n})")
+        if np.unique(ids).size != ids.size:
+            raise ValueError("a stream id appears twice in one call")
+        if not table.live[ids].all():
+            raise ValueError("a closed stream")
+        return ids
+
+    def embed_step(self, table: StreamTable, sid, chunks, *, block: int = 1024, payloads=None, seed: int | None = None,
+                   target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False) -> list:
+        """One tick of live streams: chunks[i] continues stream sid[i] of `table`, and the table moves on.  Entry i is, bit for bit, what
+        embed(keys[key[s]], chunks[i], ctr0=prev.ctr, carry=prev, block=block, ...) returns for s = sid[i], `prev` the EmbedResult of
+        that stream's previous chunk (none, and ctr0 = the stream's opening counter, for its first), and table.ctr / off / tail [s]
+        are then that call's EmbedResult.ctr / off / tail -- the per-stream loop this call replaces is its definition (and through it
+        WatermarkEmbedder.process over successive `block`-sized slices of every chunk, rtwm/embedder.py:44-75; the block grid starts
+        again at every chunk).  chunks: 1-D float32 arrays / tensors of any lengths, 0 included; sid: stream ids, each at most once;
+        streams not named are not touched.  payloads: per chunk sealed uint8 [>= new frames of the chunk, 55] (stream_layout says how
+        many); seed=: the bytes embed(seed=) draws for each counter, sealed under the stream's key; neither: plaintext b"ESAL" | ctr |
+        nonce8 | pad11 with `secrets` randomness sealed on the device, nonce8 the stream's own.
+        The chunks are cut into launches by scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its chunks into one
+        [chunks, longest rounded up to 4] tensor and runs ONE sequence whatever the number of streams and keys: keyed seal (if needed)
+        -> polar encode -> keyed schedule -> keyed frame generator -> stream mix (pending frame and new frames read where they lie) ->
+        commit, over the flat frame list stream_layout computes from the table's host mirror.  A call whose chunks are all empty
+        launches nothing.  -> [EmbedClip], one per chunk in input order."""
+        from .scan import ragged_buckets
+        from .utils import db_to_lin
+        FL = nat.ES_FRAME_LEN
+        ids = self._stream_ids(table, sid)
+        chunks = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in chunks]
+        R = len(chunks)
+        if any(c.dim() != 1 or c.dtype != torch.float32 for c in chunks):
+            raise ValueError("chunks must be 1-D float32 arrays or tensors")
+        if ids.size != R:
+            raise ValueError("one stream id per chunk is required")
+        block = int(block)
+        if block < 1:
+            raise ValueError("block must be >= 1")
+        lengths = np.array([c.numel() for c in chunks], np.int64)
+        whole = stream_layout(table.off_host[ids], table.ctr_host[ids], lengths)
+        if payloads is not None:
+            payloads = [np.zeros((0, 55), np.uint8) if p is None else np.asarray(p.cpu().numpy() if torch.is_tensor(p) else p) for p in payloads]
+            if len(payloads) != R or any(p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 55 or p.shape[0] < f for p, f in zip(payloads, whole.nf)):
+                raise ValueError("payloads: per chunk uint8 [nf >= the chunk's new frames, 55]")
+        no_scale = lambda: torch.empty(0, dtype=torch.float64, device=self.device) if want_scale else None
+        out: list = [None] * R
+        for idx in ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES):
+            rows = ids[idx]
+            if int(lengths[idx].max()) == 0:                            # chunks of no samples: nothing to mix, no stream moves
+                for i in idx:
+                    out[i] = EmbedClip(torch.empty(0, dtype=torch.float32, device=self.device), int(table.ctr_host[ids[i]]),
+                                       int(table.off_host[ids[i]]), no_scale())
+                continue
+            lay = stream_layout(table.off_host[rows], table.ctr_host[rows], lengths[idx])
+            F, n = lay.rec.size, len(idx)
+            stride = (int(lengths[idx].max()) + 3) // 4 * 4
+            if all(not c.is_cuda for c in chunks):                     # one staging array, one copy
+                pad = np.zeros((n, stride), np.float32)
+                for j, i in enumerate(idx):
+                    pad[j, :lengths[i]] = chunks[i].numpy()
+                x = torch.from_numpy(pad).to(self.device)
+            else:
+                x = torch.zeros((n, stride), dtype=torch.float32, device=self.device)
+                for j, i in enumerate(idx):
+                    x[j, :lengths[i]] = chunks[i].to(self.device)
+            rec = np.ascontiguousarray(np.stack((rows, table.off_host[rows], lengths[idx], lay.chip_base, lay.chip_cnt), axis=1))   # [n, 5]
+            rec_d = torch.from_numpy(np.ascontiguousarray(rec.T)).to(self.device)                                                    # [5, n]
+            if F:
+                fr = torch.from_numpy(np.stack((lay.ctr, table.key_host[rows][lay.rec], rows[lay.rec]))).to(self.device)            # [3, F]
+                ctr_d, kf_d = fr[0], fr[1].to(torch.int32)
+                if payloads is not None:
+                    blobs = torch.from_numpy(np.concatenate([payloads[i][:f] for i, f in zip(idx, lay.nf)])).to(self.device)
+                elif seed is not None:
+                    nonces, plain = self._synthetic_plain(ctr_d, seed)
+                    blobs = self.seal_keyed(table.ring, kf_d, nonces, plain)
+                else:
+                    import secrets as _secrets
+                    plain = np.empty((F, 27), np.uint8)
+                    plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
+                    plain[:, 4:8] = lay.ctr.astype(">u4").view(np.uint8).reshape(-1, 4)
+                    plain[:, 8:16] = 0
+                    plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * F), np.uint8).reshape(-1, 11)
+                    nonces = np.frombuffer(_secrets.token_bytes(12 * F), np.uint8).reshape(-1, 12)
+                    plain = torch.from_numpy(plain).to(self.device)
+                    plain[:, 8:16] = table.nonce8[fr[2]]                # the stream's own session nonce
+                    blobs = self.seal_keyed(table.ring, kf_d, torch.from_numpy(nonces.copy()), plain)
+                frames = self.make_frames_keyed(table.ring, kf_d, ctr_d, blobs)
+            else:
+                frames = None                                           # every chunk lives on its stream's pending frame
+            scale = torch.empty((n, (stride + block - 1) // block), dtype=torch.float64, device=self.device) if want_scale else None
+            tick = (n, stride, _ptr(rec_d[2]))
+            pool = (_ptr(frames), F * FL, _ptr(rec_d[3]), _ptr(rec_d[4]), rec.ctypes.data)
+            nat.check(self._ctx, self._lib.es_mix_stream_batch(self._ctx, _ptr(x), *tick, block, _ptr(rec_d[0]), table.n, _ptr(table.tail),
+                                                               _ptr(table.off), *pool, db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs),
+                                                               _ptr(x), _ptr(scale), self._stream()), "es_mix_stream_batch")
+            nat.check(self._ctx, self._lib.es_stream_commit_batch(self._ctx, *tick, _ptr(rec_d[0]), table.n, _ptr(table.tail), _ptr(table.ctr),
+                                                                  _ptr(table.off), *pool, self._stream()), "es_stream_commit_batch")
+            table.ctr_host[rows], table.off_host[rows] = lay.ctr_next, lay.off_next
+            for j, i in enumerate(idx):
+                n_i = int(lengths[i])
+                out[i] = EmbedClip(x[j, :n_i], int(lay.ctr_next[j]), int(lay.off_next[j]), scale[j, :(n_i + block - 1) // block] if want_scale else None)
         return out
 
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)

@@ -477,6 +477,37 @@ int es_mix_ragged_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_st
                         const float* chips_dev, int64_t chips_total, const int64_t* chip_base_dev, const int64_t* chip_cnt_dev,
                         double alpha, double floor, float* out_dev, double* scale_dev, void* stream);
 
+/* Live streams: many streams, each under its own key, marked chunk by chunk (the reference's WatermarkEmbedder.process keeps its chip
+ * buffer and counter between calls, rtwm/embedder.py:34-36,44-75).  A stream table of S rows holds per stream the frame it stands in,
+ * tail_dev float32 [S][1215], the chips of that frame already used, off_dev int64 [S] in 0 .. 1214 (0: nothing pending), and the counter
+ * of the next frame to generate, ctr_dev int64 [S] in 0 .. 2^32 - 1.
+ *
+ * es_mix_stream_batch is es_mix_ragged_batch for records that continue streams: record r = x[r][0 : len[r]] is a chunk of stream
+ * sid_dev[r] (int64 [R]).  Its chips are the row [tail[sid[r]] | the record's new frames at chips[chip_base[r] ..] of the flat pool]; its
+ * first sample takes row position start = off[sid[r]], or 1215 where off is 0, and the record needs
+ * ceil((start + len[r]) / 1215) - 1 new frames: chip_cnt[r] is 1215 times that.  Both sources are read where they lie.  Block grid,
+ * gains, kernels' cut and what is left unwritten are those of es_mix_ragged_batch; a chunk is mixed exactly as es_mix_batch mixes it alone
+ * with the concatenated row and chip_off = start.  The table is only read.
+ * rec_host [R][ES_STREAM_REC_WORDS] int64 = (sid, off, len, chip_base, chip_cnt) of every record as the host laid them out, checked
+ * before anything is enqueued: ES_EINVAL for a sid outside [0, S) or named twice, off outside 0 .. 1214, len outside 0 .. n_stride, a
+ * chip_cnt other than the one above, a pool shorter than chip_base + chip_cnt.  The device arrays must hold the same; what they hold
+ * instead is clamped as es_mix_ragged_batch clamps (a sid outside the table: a record of length 0; no read leaves table or pool).
+ * chips_dev may be NULL where chips_total == 0 (no record makes a new frame).  Only enqueues; R == 0 or n_stride == 0 launches nothing. */
+#define ES_STREAM_REC_WORDS 5
+int es_mix_stream_batch(es_ctx* ctx, const float* x_dev, int64_t R, int64_t n_stride, const int64_t* len_dev, int block,
+                        const int64_t* sid_dev, int64_t S, const float* tail_dev, const int64_t* off_dev, const float* chips_dev,
+                        int64_t chips_total, const int64_t* chip_base_dev, const int64_t* chip_cnt_dev, const int64_t* rec_host,
+                        double alpha, double floor, float* out_dev, double* scale_dev, void* stream);
+
+/* The state of the pushed streams after es_mix_stream_batch over the same records, enqueued behind it on the same stream (a launch of
+ * its own: many workgroups of the mix read a stream's tail).  With end = start + len[r]: off[sid] = end % 1215, ctr[sid] advances by the
+ * record's new frames mod 2^32, and tail[sid] becomes the frame the stream now stands in -- frame end / 1215 of the row where
+ * end % 1215 > 0, the frame just used up where the chunk ended on a frame edge, the old tail (left as it is) where that is row frame 0.
+ * Rows of streams the records do not name are not touched.  Arguments and refusals as above.                                      */
+int es_stream_commit_batch(es_ctx* ctx, int64_t R, int64_t n_stride, const int64_t* len_dev, const int64_t* sid_dev, int64_t S,
+                           float* tail_dev, int64_t* ctr_dev, int64_t* off_dev, const float* chips_dev, int64_t chips_total,
+                           const int64_t* chip_base_dev, const int64_t* chip_cnt_dev, const int64_t* rec_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
