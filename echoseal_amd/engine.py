@@ -24,6 +24,8 @@ import torch
 
 from . import _native as nat
 from .tables import pack_tables
+from .transmit import (EMBED_ROW_SAMPLES, EmbedClip, EmbedLayout, EmbedResult, StreamLayout, StreamTable, TxChain, _ptr, embed_launches, embed_layout,
+                       stream_layout)      # the transmit chain's public names stay importable from here
 
 # The streaming pipelines run on up to eight HIP streams.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues
 # (default 4) and streams that share a queue serialise, silently.  The variable belongs to the process's environment: this module reads
@@ -55,10 +57,6 @@ def pipeline_streams(device, n: int, priority: int = 0) -> list:
                       f"(GPU_MAX_HW_QUEUES{'=' + _HWQ_ENV_AT_IMPORT if _HWQ_ENV_AT_IMPORT else ' not set'}): streams that share a "
                       "queue serialise.  Hand existing streams to further pipelines (streams=...).", RuntimeWarning, stacklevel=3)
     return out
-
-
-def _ptr(t: torch.Tensor | None) -> int | None:
-    return None if t is None else t.data_ptr()
 
 
 _FRAME_DTYPES = {torch.int16: nat.ES_DTYPE_I16, torch.float32: nat.ES_DTYPE_F32}     # what the band-pass reads
@@ -103,127 +101,6 @@ class SyncResult:
 
 
 @dataclass
-class EmbedResult:
-    audio: torch.Tensor        # [R,n] float32 watermarked recordings ([n] for 1-D input)
-    ctr: np.ndarray            # [R] int64: counter of the next frame to generate (WatermarkEmbedder.frame_ctr after the same process() calls)
-    off: np.ndarray            # [R] int64: chips of the current frame already used (0 = nothing pending)
-    tail: torch.Tensor         # [R,1215] float32: the current frame; its chips from `off` on are what process() keeps in its buffer
-    scale: torch.Tensor | None = None   # [R, ceil(n / block)] float64 gain of every block (want_scale)
-
-
-@dataclass
-class EmbedClip:
-    """One clip of RxEngine.embed_batch."""
-    audio: torch.Tensor        # [len] float32, the watermarked clip (a view into its launch's padded tensor)
-    ctr: int                   # counter of the next frame to generate (WatermarkEmbedder.frame_ctr after process() over the clip)
-    off: int                   # chips of the current frame already used (0 = nothing pending)
-    scale: torch.Tensor | None = None   # [ceil(len / block)] float64 gain of every block (want_scale)
-
-
-# Padded samples (clips x longest clip of the launch) one embed_batch launch may hold.  Bytes per padded sample: the float32 row that
-# is mixed in place, 4, and its staging copy on the host, not on the device; per REAL sample, roughly one chip each: the frames
-# float32, 4, the band-pass workspace float64, 8, code bits 1024 / 1215 and PN rows 152 / 1215, 1 -- so at most 17 bytes per padded
-# sample and 2^26 samples stay under 1.2 GB.  A memory bound, not a tuned value.
-EMBED_ROW_SAMPLES = 1 << 26
-
-
-@dataclass
-class EmbedLayout:
-    """Where the frames of a batch of clips lie (embed_layout)."""
-    nf: np.ndarray             # [R] int64 frames clip r generates: ceil(len_r / 1215)
-    clip: np.ndarray           # [F] int64 clip of each frame of the flat frame list (clip by clip, counters ascending)
-    ctr: np.ndarray            # [F] int64 counter of each frame: (ctr0[clip] + k) mod 2^32
-    chip_base: np.ndarray      # [R] int64 = 1215 * index of clip r's first frame in the flat list
-    chip_cnt: np.ndarray       # [R] int64 = 1215 * nf[r]
-    ctr_next: np.ndarray       # [R] int64 counter after the clip: (ctr0 + nf) mod 2^32
-    off: np.ndarray            # [R] int64 chips of the last frame already used: len mod 1215
-
-
-def embed_layout(lengths, ctr0) -> EmbedLayout:
-    """The frames a batch of clips generates, as WatermarkEmbedder.process does whatever the block size (rtwm/embedder.py:44-62: a
-    frame is made whenever the chip buffer runs short): clip r of lengths[r] samples starting at counter ctr0[r] (a scalar serves
-    every clip) makes ceil(lengths[r] / 1215) frames of consecutive counters mod 2^32.  A pure host function."""
-    FL = nat.ES_FRAME_LEN
-    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    if n.size and n.min() < 0:
-        raise ValueError("negative clip length")
-    c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.int64(int(ctr0)), n.shape)) & 0xFFFFFFFF
-    nf = (n + FL - 1) // FL
-    first = np.cumsum(nf) - nf
-    clip = np.repeat(np.arange(n.size, dtype=np.int64), nf)
-    k = np.arange(int(nf.sum()), dtype=np.int64) - first[clip]
-    return EmbedLayout(nf, clip, (c0[clip] + k) & 0xFFFFFFFF, first * FL, nf * FL, (c0 + nf) & 0xFFFFFFFF, n % FL)
-
-
-def embed_launches(lengths, ctr0, budget: int | None = None) -> list:
-    """How embed_batch cuts a batch into launches: scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES) (clips sorted by length, taken
-    while clips x longest clip stays within the budget), each launch with the frame layout of its own clips.  -> [(indices into the
-    batch, EmbedLayout of those clips in that order)]; results go back to the indices, so the caller sees input order."""
-    from .scan import ragged_buckets
-    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.int64(int(ctr0)), n.shape))
-    return [(idx, embed_layout(n[idx], c0[idx])) for idx in ragged_buckets(n, 1, EMBED_ROW_SAMPLES if budget is None else budget)]
-
-
-@dataclass
-class StreamLayout:
-    """Where the frames of one tick of live streams lie (stream_layout)."""
-    start: np.ndarray          # [R] int64 position of the chunk's first chip in the row [pending frame | new frames]: off, or 1215 where off == 0
-    nf: np.ndarray             # [R] int64 new frames chunk r generates: ceil((start + len) / 1215) - 1
-    rec: np.ndarray            # [F] int64 chunk of each frame of the flat frame list (chunk by chunk, counters ascending)
-    ctr: np.ndarray            # [F] int64 counter of each frame: (ctr[rec] + k) mod 2^32
-    chip_base: np.ndarray      # [R] int64 = 1215 * index of chunk r's first new frame in the flat list
-    chip_cnt: np.ndarray       # [R] int64 = 1215 * nf[r]
-    ctr_next: np.ndarray       # [R] int64 the stream's counter after the chunk: (ctr + nf) mod 2^32
-    off_next: np.ndarray       # [R] int64 chips of the frame the stream then stands in already used: (start + len) mod 1215
-
-
-def stream_layout(off, ctr, lengths) -> StreamLayout:
-    """The frames one tick generates, as successive WatermarkEmbedder.process calls do (rtwm/embedder.py:44-62: a frame is made whenever
-    the chip buffer runs short): chunk r of lengths[r] samples continues a stream that has used off[r] chips of the frame it stands in
-    (0 = nothing pending) and makes its next frame under counter ctr[r].  It first uses up the 1215 - off[r] pending chips, then
-    ceil((start + len) / 1215) - 1 new frames of consecutive counters mod 2^32 -- what `embed` computes as `new` with carry=.  A pure
-    host function."""
-    FL = nat.ES_FRAME_LEN
-    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    off = np.asarray(off, dtype=np.int64).reshape(-1)
-    c0 = np.asarray(ctr, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
-    if off.shape != n.shape or c0.shape != n.shape:
-        raise ValueError("off, ctr, lengths: one entry per chunk")
-    if n.size and n.min() < 0:
-        raise ValueError("negative chunk length")
-    if off.size and (off.min() < 0 or off.max() >= FL):
-        raise ValueError(f"off outside [0, {FL})")
-    start = np.where(off > 0, off, FL)
-    end = start + n
-    nf = (end + FL - 1) // FL - 1
-    first = np.cumsum(nf) - nf
-    rec = np.repeat(np.arange(n.size, dtype=np.int64), nf)
-    k = np.arange(int(nf.sum()), dtype=np.int64) - first[rec]
-    return StreamLayout(start, nf, rec, (c0[rec] + k) & 0xFFFFFFFF, first * FL, nf * FL, (c0 + nf) & 0xFFFFFFFF, end % FL)
-
-
-@dataclass
-class StreamTable:
-    """The state of S live streams on the device (RxEngine.open_streams); RxEngine.embed_step marks chunks of any of them and moves
-    them on.  Row s is what EmbedResult.ctr / off / tail are for one stream."""
-    ring: KeyRing
-    key: torch.Tensor          # [S] int32 ring row of each stream
-    ctr: torch.Tensor          # [S] int64 counter of the next frame to generate, 0 .. 2^32 - 1
-    off: torch.Tensor          # [S] int64 chips of the current frame already used (0 = nothing pending)
-    tail: torch.Tensor         # [S, 1215] float32 the frame the stream stands in
-    nonce8: torch.Tensor       # [S, 8] uint8 session nonce, fixed when the stream is opened
-    key_host: np.ndarray       # [S] int64 host copy of `key`
-    ctr_host: np.ndarray       # [S] int64 host mirror of `ctr`: a tick lays out its frames without a copy from the device
-    off_host: np.ndarray       # [S] int64 host mirror of `off`
-    live: np.ndarray           # [S] bool; False: a closed row, free for add_streams
-
-    @property
-    def n(self) -> int:
-        return int(self.live.size)
-
-
-@dataclass
 class KeyRing:
     """Keys as device data (es_keyring_derive_batch): row k of `ring` holds what the keyed kernels need of key k (layout:
     include/echoseal_hip.h)."""
@@ -259,7 +136,7 @@ class PlanResult:
     looked: torch.Tensor       # [N * rows] int32: fitting peaks looked at
 
 
-class RxEngine:
+class RxEngine(TxChain):
     def __init__(self, device: int | torch.device = 0, *, list_size_max: int = 32, fs: int = 48_000, code_k: int = 448):
         """code_k: information positions of the polar code (data bits + CRC-8).  448 is the reference's own code (rtwm/polar_fast.py:8-9);
         any other 9 <= K <= 1024 (PolarCode(1024, K), rtwm/fastpolar.py:209-234) makes an engine whose `scl` is the only FEC entry point
@@ -678,7 +555,9 @@ class RxEngine:
 
     # ------------------------------------------------------------------ many keys at once (es_keyring.hip)
     def keyring(self, keys) -> KeyRing:
-        """The key ring of 32-byte master keys (a sequence of bytes objects, or uint8 [N, 32]), derived on the device."""
+        """The key ring of 32-byte master keys (a sequence of bytes objects, or uint8 [N, 32]), derived on the device (a KeyRing: itself)."""
+        if isinstance(keys, KeyRing):
+            return keys
         if torch.is_tensor(keys):
             mk = keys
         else:
@@ -694,13 +573,18 @@ class RxEngine:
         nat.check(self._ctx, self._lib.es_keyring_derive_batch(self._ctx, _ptr(mk), N, _ptr(ring), self._stream()), "es_keyring_derive_batch")
         return KeyRing(ring, N)
 
+    @staticmethod
+    def _key_host(ring: KeyRing, key_idx) -> np.ndarray:
+        """Key indices as int64 on the host (a device tensor is copied), each a row of the ring."""
+        h = np.asarray(key_idx.cpu().numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
+        if h.size and (h.min() < 0 or h.max() >= ring.n):
+            raise ValueError(f"key index outside [0, {ring.n})")
+        return h
+
     def _key_dev(self, ring: KeyRing, key_idx, n: int) -> torch.Tensor:
         """Key indices as int32 on the device; indices the host can see (anything but a device tensor) are range-checked here."""
         if not (torch.is_tensor(key_idx) and key_idx.is_cuda):
-            h = np.asarray(key_idx.numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
-            if h.size and (h.min() < 0 or h.max() >= ring.n):
-                raise ValueError(f"key index outside [0, {ring.n})")
-            key_idx = torch.from_numpy(h)
+            key_idx = torch.from_numpy(self._key_host(ring, key_idx))
         kd = self._dev(key_idx, torch.int32).reshape(-1)
         if kd.numel() != n:
             raise ValueError("one key index per record is required")
@@ -776,471 +660,6 @@ class RxEngine:
                                                      _ptr(res.count), _ptr(res.looked), self._stream()), "es_plan_batch")
         return res
 
-    def make_frames(self, sec, band_key32: bytes, ctrs, payloads: torch.Tensor) -> torch.Tensor:
-        """Batch of transmitted frames on the device (WatermarkEmbedder.make_frames, rtwm/embedder.py:78-141):
-        payloads uint8 [B,55] (already sealed) under frame counters `ctrs` -> float32 [B,1215].  `sec` is the
-        SecureChannel (PN sub-key, header PN), band_key32 the hop key."""
-        from .utils import mseq_63
-        cd = self._ctr_dev(ctrs)
-        B = cd.numel()
-        payloads = self._dev(payloads, torch.uint8)
-        if payloads.shape != (B, 55):
-            raise ValueError("payloads must be uint8 [B,55], one per counter")
-        code = self.polar_encode(payloads)
-        pn, band = self.schedule(sec._prng.sub_key, band_key32, cd.to(torch.int64) & 0xFFFFFFFF)
-        pre8 = np.packbits(np.concatenate((mseq_63().astype(np.uint8), np.zeros(1, np.uint8)))).tobytes()
-        hdr16 = np.packbits(sec.pn_bits(0, 128)).tobytes()
-        y_ws = torch.empty((B, 1215), dtype=torch.float64, device=self.device)
-        frames = torch.empty((B, 1215), dtype=torch.float32, device=self.device)
-        nat.check(self._ctx, self._lib.es_tx_frames_batch(self._ctx, _ptr(code), _ptr(pn), _ptr(band), _ptr(cd), pre8, hdr16, B,
-                                                          _ptr(y_ws), _ptr(frames), self._stream()), "es_tx_frames_batch")
-        return frames
-
-    def synthetic_frames(self, key32: bytes, ctr0: int, n: int, *, seed: int = 20260101):
-        """The benchmark workloads' frames for counters ctr0 .. ctr0+n-1, made wholly on the device (SURVEY 8d:
-        plaintext b"ESAL" | ctr_be32 | nonce8 | pad11 sealed with a 12-byte nonce, random bytes from a seeded torch
-        generator, then `make_frames`).  -> (frames float32 [n,1215], payloads uint8 [n,55]).  Input synthesis for
-        configs 3 and 4, where 65 536 .. 2^20 frames would take the host embedder minutes."""
-        from .crypto import SecureChannel
-        sec = SecureChannel(key32)
-        ctr = torch.arange(ctr0, ctr0 + n, dtype=torch.int64, device=self.device)
-        payloads = self._synthetic_payloads(sec, ctr, seed)
-        return self.make_frames(sec, key32, ctr, payloads), payloads
-
-    def _synthetic_payloads(self, sec, ctr: torch.Tensor, seed: int) -> torch.Tensor:
-        """Sealed payloads uint8 [len(ctr),55] of `synthetic_frames` for the int64 device counters `ctr`."""
-        nonces, plain = self._synthetic_plain(ctr, seed)
-        return self.aead_seal(sec._aead._key, nonces, plain)
-
-    def _synthetic_plain(self, ctr: torch.Tensor, seed: int):
-        """What `_synthetic_payloads` seals: -> (nonces uint8 [n,12], plaintexts uint8 [n,27]) of the int64 device counters `ctr`."""
-        n = ctr.numel()
-        # 31 random bytes per frame from a counter-based hash of (seed, ctr, byte index), so that a frame does not
-        # depend on how the counter range is cut into batches or shards (32-bit multiply-xorshift rounds in int64)
-        h = (ctr[:, None] * 31 + torch.arange(31, dtype=torch.int64, device=self.device)[None, :] + (int(seed) & 0xFFFFFF) * 1_000_003) & 0xFFFFFFFF
-        for _ in range(3):
-            h = (h * 0x45D9F3B) & 0xFFFFFFFF
-            h = h ^ (h >> 16)
-        rnd = (h & 0xFF).to(torch.uint8)
-        plain = torch.empty((n, 27), dtype=torch.uint8, device=self.device)
-        plain[:, :4] = torch.tensor(list(b"ESAL"), dtype=torch.uint8, device=self.device)
-        for k in range(4):
-            plain[:, 4 + k] = ((ctr >> (8 * (3 - k))) & 0xFF).to(torch.uint8)
-        plain[:, 8:27] = rnd[:, :19]
-        return rnd[:, 19:31].contiguous(), plain
-
-    # ------------------------------------------------------------------ level mix: frames -> watermarked recordings
-    def mix(self, x: torch.Tensor, chips: torch.Tensor, *, block: int = 1024, chip_off=None, target_rel_db: float = -10.0,
-            floor_rel_dbfs: float = -35.0, want_scale: bool = False, out: torch.Tensor | None = None):
-        """WatermarkEmbedder.process (rtwm/embedder.py:44-75) for every `block`-sized slice of every recording, bit for bit
-        (es_mix_batch): x float32 [R, n]; chips float32 [R, stride], row r the chip stream of recording r (frames of consecutive
-        counters back to back); sample t takes chips[r, chip_off[r] + t] (chip_off: int64 [R], None = 0).  out=x mixes in place.
-        -> marked audio [R, n]; want_scale: (audio, scale float64 [R, ceil(n / block)])."""
-        from .utils import db_to_lin
-        if x.dim() != 2 or chips.dim() != 2 or x.dtype != torch.float32 or chips.dtype != torch.float32 or chips.shape[0] != x.shape[0]:
-            raise ValueError("x must be float32 [R, n] and chips float32 [R, stride]")
-        x = x.contiguous(); chips = chips.contiguous()
-        R, n = x.shape
-        if chip_off is not None:
-            chip_off = self._dev(chip_off, torch.int64).reshape(-1)
-            if chip_off.numel() != R:
-                raise ValueError("chip_off: one offset per recording")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of x's shape")
-        block = int(block)
-        scale = torch.empty((R, (n + block - 1) // block if block >= 1 else 0), dtype=torch.float64, device=self.device) if want_scale else None
-        nat.check(self._ctx, self._lib.es_mix_batch(self._ctx, _ptr(x), R, n, block, _ptr(chips), chips.shape[1], _ptr(chip_off),
-                                                    db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), _ptr(out), _ptr(scale),
-                                                    self._stream()), "es_mix_batch")
-        return (out, scale) if want_scale else out
-
-    def embed(self, key32: bytes, audio, *, ctr0=0, block: int = 1024, payloads=None, carry=None, seed: int | None = None,
-              session_nonce: bytes | None = None, target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False):
-        """Whole watermarked recordings: the reference's transmit chain (seal -> polar encode -> header -> PN spread -> band-pass ->
-        level mix, rtwm/embedder.py) for a batch, one frame-generator call and one mix launch.  audio float32 [R, n] (or [n]);
-        recording r is what a WatermarkEmbedder with frame_ctr = ctr0[r] returns from process() over successive `block`-sized slices.
-        payloads: sealed uint8 [R, nf, 55] for the new frames of counters ctr0[r] + k (mod 2^32); None: plaintext b"ESAL" | ctr | nonce8 |
-        pad11 sealed under a 12-byte nonce, with random bytes from `secrets` as the reference (session_nonce: the 8 bytes a session keeps),
-        or, with seed=, the deterministic bytes of `synthetic_frames`.  carry: the EmbedResult of the call this one continues (its pending
-        chips are used first, as process() keeps them in its buffer).  -> EmbedResult."""
-        from .crypto import SecureChannel
-        import secrets as _secrets
-        FL = nat.ES_FRAME_LEN
-        x = audio if torch.is_tensor(audio) else torch.as_tensor(np.asarray(audio))
-        one_d = x.dim() == 1
-        if one_d:
-            x = x.reshape(1, -1)
-        if x.dim() != 2 or x.dtype != torch.float32:
-            raise ValueError("audio must be float32 [R, n] or [n]")
-        x = self._dev(x, torch.float32)
-        R, n = x.shape
-        sec = SecureChannel(key32)
-        c0 = np.array(np.broadcast_to(np.asarray(ctr0, dtype=np.int64).reshape(-1), (R,))) if np.ndim(ctr0) else np.full(R, int(ctr0), np.int64)
-        if carry is not None:
-            if carry.tail.shape != (R, FL):
-                raise ValueError("carry: the EmbedResult of a call over the same recordings")
-            off_in = np.asarray(carry.off, dtype=np.int64).reshape(R)
-            start = np.where(off_in > 0, off_in, FL)           # position of the first chip in a row = [pending frame | new frames]
-            lead = 1
-        else:
-            start = np.zeros(R, np.int64)
-            lead = 0
-        end = start + n                                         # chips of the row consumed after this call
-        new = (end + FL - 1) // FL - lead                       # new frames each recording generates (process() makes exactly these)
-        nf = int(max(0, new.max())) if R else 0
-        if payloads is not None:
-            payloads = self._dev(payloads, torch.uint8)
-            if payloads.dim() != 3 or payloads.shape[0] != R or payloads.shape[2] != 55 or payloads.shape[1] < nf:
-                raise ValueError(f"payloads must be uint8 [R, nf >= {nf}, 55]")
-            nf = payloads.shape[1] if nf else 0
-            payloads = payloads[:, :nf]
-        ctr = (torch.from_numpy(c0).to(self.device)[:, None] + torch.arange(nf, dtype=torch.int64, device=self.device)[None, :]) & 0xFFFFFFFF
-        if nf and R:
-            if payloads is None and seed is not None:
-                payloads = self._synthetic_payloads(sec, ctr.reshape(-1), seed)
-            elif payloads is None:
-                sn = _secrets.token_bytes(8) if session_nonce is None else bytes(session_nonce)
-                if len(sn) != 8:
-                    raise ValueError("session_nonce must be 8 bytes")
-                plain = np.empty((R * nf, 27), np.uint8)
-                plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
-                plain[:, 4:8] = ctr.reshape(-1).cpu().numpy().astype(">u4").view(np.uint8).reshape(-1, 4)
-                plain[:, 8:16] = np.frombuffer(sn, np.uint8)
-                plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * R * nf), np.uint8).reshape(-1, 11)
-                nonces = np.frombuffer(_secrets.token_bytes(12 * R * nf), np.uint8).reshape(-1, 12)
-                payloads = self.aead_seal(sec._aead._key, torch.from_numpy(nonces.copy()), torch.from_numpy(plain))
-            frames = self.make_frames(sec, getattr(sec, "band_key", key32), ctr.reshape(-1), payloads.reshape(R * nf, 55)).reshape(R, nf * FL)
-        else:
-            frames = torch.empty((R, 0), dtype=torch.float32, device=self.device)
-        chips = torch.cat((carry.tail.to(self.device), frames), dim=1) if lead else frames
-        res = self.mix(x, chips, block=block, chip_off=torch.from_numpy(start) if lead else None, target_rel_db=target_rel_db,
-                       floor_rel_dbfs=floor_rel_dbfs, want_scale=want_scale) if n else (x.clone(), None)
-        out, scale = res if (want_scale or not n) else (res, None)
-        off = end % FL
-        slot = np.where(off > 0, end // FL, np.maximum(end // FL - 1, 0))      # the frame the stream stands in (pending chips from `off` on)
-        if chips.shape[1]:
-            idx = torch.from_numpy(slot).to(self.device)[:, None] * FL + torch.arange(FL, dtype=torch.int64, device=self.device)[None, :]
-            tail = torch.gather(chips, 1, idx)
-        else:
-            tail = torch.zeros((R, FL), dtype=torch.float32, device=self.device)
-        return EmbedResult(out[0] if one_d else out, (c0 + new) % (2 ** 32), off, tail, scale)
-
-    # ------------------------------------------------------------------ the transmit chain for many keys and unequal lengths
-    def seal_keyed(self, ring: KeyRing, key_idx, nonces: torch.Tensor, plain: torch.Tensor) -> torch.Tensor:
-        """`aead_seal` with the AEAD key of ring row key_idx[i] per blob (es_aead_seal_keyed_batch): nonces uint8 [n,12],
-        plain uint8 [n,27] -> blobs uint8 [n,55].  A device key index outside the ring gives a zero blob."""
-        nonces = self._dev(nonces, torch.uint8); plain = self._dev(plain, torch.uint8)
-        if nonces.dim() != 2 or nonces.shape[1] != 12 or plain.shape != (nonces.shape[0], 27):
-            raise ValueError("nonces must be [n,12] and plain [n,27]")
-        n = nonces.shape[0]
-        kd = self._key_dev(ring, key_idx, n)
-        if n and ring.n == 0:
-            raise ValueError("records but an empty key ring")
-        blobs = torch.empty((n, 55), dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_aead_seal_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(nonces), _ptr(plain), n,
-                                                                _ptr(blobs), self._stream()), "es_aead_seal_keyed_batch")
-        return blobs
-
-    def make_frames_keyed(self, ring: KeyRing, key_idx, ctrs, payloads: torch.Tensor) -> torch.Tensor:
-        """`make_frames` for frames of several keys: frame i carries payloads[i] (uint8 [B,55], already sealed) under counter ctrs[i]
-        and the key of ring row key_idx[i] -> float32 [B,1215] (es_polar_encode_batch, es_schedule_keyed_batch,
-        es_tx_frames_keyed_batch: nothing is derived or copied from the host)."""
-        from .utils import mseq_63
-        cd = self._ctr_dev(ctrs).reshape(-1)
-        B = cd.numel()
-        payloads = self._dev(payloads, torch.uint8)
-        if payloads.shape != (B, 55):
-            raise ValueError("payloads must be uint8 [B,55], one per counter")
-        kd = self._key_dev(ring, key_idx, B)
-        if B and ring.n == 0:
-            raise ValueError("records but an empty key ring")
-        code = self.polar_encode(payloads)
-        pn, band = self.schedule_keyed(ring, kd, cd.to(torch.int64) & 0xFFFFFFFF)
-        pre8 = np.packbits(np.concatenate((mseq_63().astype(np.uint8), np.zeros(1, np.uint8)))).tobytes()
-        y_ws = torch.empty((B, 1215), dtype=torch.float64, device=self.device)
-        frames = torch.empty((B, 1215), dtype=torch.float32, device=self.device)
-        nat.check(self._ctx, self._lib.es_tx_frames_keyed_batch(self._ctx, _ptr(code), _ptr(pn), _ptr(band), _ptr(cd), pre8, _ptr(ring.ring),
-                                                                ring.n, _ptr(kd), B, _ptr(y_ws), _ptr(frames), self._stream()),
-                  "es_tx_frames_keyed_batch")
-        return frames
-
-    def mix_ragged(self, x: torch.Tensor, lens, chips: torch.Tensor, chip_base, chip_cnt, *, block: int = 1024, target_rel_db: float = -10.0,
-                   floor_rel_dbfs: float = -35.0, want_scale: bool = False, out: torch.Tensor | None = None):
-        """`mix` for recordings of unequal length (es_mix_ragged_batch): x float32 [R, stride], record r = x[r, :lens[r]]; chips ONE flat
-        float32 pool, sample t of record r takes chips[chip_base[r] + t], reads clamped to the record's chip_cnt[r] chips (lens,
-        chip_base, chip_cnt: int64 [R]).  Every block of a record is mixed as `mix` mixes the record alone.  out[r, lens[r]:] and the
-        scales of block slots past a record's end are NOT written: give `out` (out=x mixes in place) to decide what they hold.
-        -> marked audio [R, stride]; want_scale: (audio, scale float64 [R, ceil(stride / block)])."""
-        from .utils import db_to_lin
-        if x.dim() != 2 or x.dtype != torch.float32 or chips.dtype != torch.float32:
-            raise ValueError("x must be float32 [R, stride] and chips a float32 pool")
-        x = x.contiguous(); chips = chips.contiguous().reshape(-1)
-        R, n = x.shape
-        lens, chip_base, chip_cnt = (self._dev(v, torch.int64).reshape(-1) for v in (lens, chip_base, chip_cnt))
-        if lens.numel() != R or chip_base.numel() != R or chip_cnt.numel() != R:
-            raise ValueError("lens, chip_base, chip_cnt: one entry per recording")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of x's shape")
-        block = int(block)
-        scale = torch.empty((R, (n + block - 1) // block if block >= 1 else 0), dtype=torch.float64, device=self.device) if want_scale else None
-        nat.check(self._ctx, self._lib.es_mix_ragged_batch(self._ctx, _ptr(x), R, n, _ptr(lens), block, _ptr(chips), chips.numel(), _ptr(chip_base),
-                                                           _ptr(chip_cnt), db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), _ptr(out),
-                                                           _ptr(scale), self._stream()), "es_mix_ragged_batch")
-        return (out, scale) if want_scale else out
-
-    def embed_batch(self, keys, key_idx, clips, *, ctr0=0, block: int = 1024, payloads=None, seed: int | None = None, session_nonces=None,
-                    target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False) -> list:
-        """`embed` for clips of unequal length, each under its own key and start counter: entry i is, bit for bit, what
-        embed(keys[key_idx[i]], clips[i], ctr0=ctr0[i], block=block, payloads=payloads[i]) returns -- the loop this call replaces is its
-        definition (and through it the host WatermarkEmbedder.process, rtwm/embedder.py:44-168).
-        keys: a KeyRing or a sequence of 32-byte keys; clips: 1-D float32 arrays / tensors of any lengths, 0 included; ctr0: a scalar or
-        one value per clip (wraps at 2^32).  Clip i generates ceil(len_i / 1215) frames of counters ctr0_i + k whatever the block.
-        payloads: per clip sealed uint8 [nf_i, 55]; seed=: the bytes embed(seed=) draws for each counter, sealed under the clip's key;
-        neither: plaintext b"ESAL" | ctr | nonce8 | pad11 with `secrets` randomness sealed on the device, nonce8 one per clip
-        (session_nonces: 8 bytes per clip, default fresh).
-        The clips are cut into launches by scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its clips into one
-        [clips, longest rounded up to 4] tensor and runs ONE sequence whatever the number of keys and lengths: keyed seal (if needed) ->
-        polar encode -> keyed schedule -> keyed frame generator -> ragged mix, over a flat frame list (embed_layout).
-        Every clip starts a stream of its own; streams that continue across calls are `embed_step`'s (many streams, each under its
-        key, one sequence per tick) or, one key at a time, `embed(carry=)`'s.  -> [EmbedClip], one per clip in input order."""
-        ring = keys if isinstance(keys, KeyRing) else self.keyring(keys)
-        clips = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in clips]
-        R = len(clips)
-        if any(c.dim() != 1 or c.dtype != torch.float32 for c in clips):
-            raise ValueError("clips must be 1-D float32 arrays or tensors")
-        kidx = np.asarray(key_idx.cpu().numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
-        if kidx.size != R:
-            raise ValueError("one key index per clip is required")
-        if R and (kidx.min() < 0 or kidx.max() >= ring.n):
-            raise ValueError(f"key index outside [0, {ring.n})")
-        lengths = np.array([c.numel() for c in clips], np.int64)
-        if np.ndim(ctr0) and np.size(ctr0) != R:
-            raise ValueError("ctr0: a scalar or one value per clip")
-        lay = embed_layout(lengths, ctr0)
-        c0 = (lay.ctr_next - lay.nf) & 0xFFFFFFFF
-        if payloads is not None:
-            payloads = [np.zeros((0, 55), np.uint8) if p is None else np.asarray(p.cpu().numpy() if torch.is_tensor(p) else p) for p in payloads]
-            if len(payloads) != R or any(p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 55 or p.shape[0] < f for p, f in zip(payloads, lay.nf)):
-                raise ValueError("payloads: per clip uint8 [nf >= ceil(len / 1215), 55]")
-        elif seed is None:
-            import secrets as _secrets
-            if session_nonces is None:
-                session_nonces = [_secrets.token_bytes(8) for _ in range(R)]
-            session_nonces = [bytes(sn) for sn in session_nonces]
-            if len(session_nonces) != R or any(len(sn) != 8 for sn in session_nonces):
-                raise ValueError("session_nonces: 8 bytes per clip")
-        out: list = [None] * R
-        for idx, sub in embed_launches(lengths, c0):
-            F = sub.clip.size
-            kf = kidx[idx][sub.clip]                                   # key of every frame of the launch
-            stride = (int(lengths[idx].max()) + 3) // 4 * 4
-            if F == 0:                                                  # clips of no samples: nothing to generate or to mix
-                for j, i in enumerate(idx):
-                    empty = torch.empty(0, dtype=torch.float32, device=self.device)
-                    out[i] = EmbedClip(empty, int(sub.ctr_next[j]), 0, torch.empty(0, dtype=torch.float64, device=self.device) if want_scale else None)
-                continue
-            if all(not c.is_cuda for c in clips):                      # one staging array, one copy
-                pad = np.zeros((len(idx), stride), np.float32)
-                for j, i in enumerate(idx):
-                    pad[j, :lengths[i]] = clips[i].numpy()
-                x = torch.from_numpy(pad).to(self.device)
-            else:
-                x = torch.zeros((len(idx), stride), dtype=torch.float32, device=self.device)
-                for j, i in enumerate(idx):
-                    x[j, :lengths[i]] = clips[i].to(self.device)
-            ctr_d = torch.from_numpy(sub.ctr).to(self.device)
-            kf_d = torch.from_numpy(kf.astype(np.int32)).to(self.device)
-            if payloads is not None:
-                blobs = torch.from_numpy(np.concatenate([payloads[i][:f] for i, f in zip(idx, sub.nf)])).to(self.device)
-            elif seed is not None:
-                nonces, plain = self._synthetic_plain(ctr_d, seed)
-                blobs = self.seal_keyed(ring, kf_d, nonces, plain)
-            else:
-                plain = np.empty((F, 27), np.uint8)
-                plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
-                plain[:, 4:8] = sub.ctr.astype(">u4").view(np.uint8).reshape(-1, 4)
-                plain[:, 8:16] = np.frombuffer(b"".join(session_nonces[i] for i in idx), np.uint8).reshape(-1, 8)[sub.clip]
-                plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * F), np.uint8).reshape(-1, 11)
-                nonces = np.frombuffer(_secrets.token_bytes(12 * F), np.uint8).reshape(-1, 12)
-                blobs = self.seal_keyed(ring, kf_d, torch.from_numpy(nonces.copy()), torch.from_numpy(plain))
-            frames = self.make_frames_keyed(ring, kf_d, ctr_d, blobs)
-            res = self.mix_ragged(x, torch.from_numpy(lengths[idx]), frames, torch.from_numpy(sub.chip_base), torch.from_numpy(sub.chip_cnt),
-                                  block=block, target_rel_db=target_rel_db, floor_rel_dbfs=floor_rel_dbfs, want_scale=want_scale, out=x)
-            marked, scale = res if want_scale else (res, None)
-            for j, i in enumerate(idx):
-                n_i = int(lengths[i])
-                out[i] = EmbedClip(marked[j, :n_i], int(sub.ctr_next[j]), int(sub.off[j]),
-                                   scale[j, :(n_i + block - 1) // block] if want_scale else None)
-        return out
-
-    # ------------------------------------------------------------------ live streams: many keys, chunk by chunk
-    def _stream_rows(self, ring: KeyRing, key_idx, ctr0, session_nonces):
-        """Checked host rows of new streams -> (key int64 [n], ctr int64 [n], nonce8 uint8 [n, 8])."""
-        import secrets as _secrets
-        kidx = np.asarray(key_idx.cpu().numpy() if torch.is_tensor(key_idx) else key_idx, dtype=np.int64).reshape(-1)
-        n = kidx.size
-        if n and (kidx.min() < 0 or kidx.max() >= ring.n):
-            raise ValueError(f"key index outside [0, {ring.n})")
-        if np.ndim(ctr0) and np.size(ctr0) != n:
-            raise ValueError("ctr0: a scalar or one value per stream")
-        c0 = (np.asarray(ctr0, dtype=np.int64).reshape(-1) if np.ndim(ctr0) else np.full(n, int(ctr0), np.int64)) & 0xFFFFFFFF
-        if session_nonces is None:
-            session_nonces = [_secrets.token_bytes(8) for _ in range(n)]
-        session_nonces = [bytes(sn) for sn in session_nonces]
-        if len(session_nonces) != n or any(len(sn) != 8 for sn in session_nonces):
-            raise ValueError("session_nonces: 8 bytes per stream")
-        return kidx, c0, np.frombuffer(b"".join(session_nonces), np.uint8).reshape(n, 8).copy()
-
-    def open_streams(self, keys_or_ring, key_idx, *, ctr0=0, session_nonces=None) -> StreamTable:
-        """A table of len(key_idx) live streams: stream s is marked under keys[key_idx[s]], makes its first frame under counter ctr0[s]
-        (a scalar serves all, wraps at 2^32) and has nothing pending -- an embedder that has processed nothing.  session_nonces: the 8
-        bytes stream s puts into every plaintext it seals (default fresh per stream).  keys_or_ring: a KeyRing or 32-byte keys."""
-        ring = keys_or_ring if isinstance(keys_or_ring, KeyRing) else self.keyring(keys_or_ring)
-        kidx, c0, n8 = self._stream_rows(ring, key_idx, ctr0, session_nonces)
-        S = kidx.size
-        return StreamTable(ring, torch.from_numpy(kidx.astype(np.int32)).to(self.device), torch.from_numpy(c0).to(self.device),
-                           torch.zeros(S, dtype=torch.int64, device=self.device),
-                           torch.zeros((S, nat.ES_FRAME_LEN), dtype=torch.float32, device=self.device), torch.from_numpy(n8).to(self.device),
-                           kidx.copy(), c0.copy(), np.zeros(S, np.int64), np.ones(S, bool))
-
-    def add_streams(self, table: StreamTable, key_idx, *, ctr0=0, session_nonces=None) -> np.ndarray:
-        """More streams for `table` (arguments of open_streams): closed rows are used first, lowest first, then the table grows.
-        -> their stream ids, int64."""
-        kidx, c0, n8 = self._stream_rows(table.ring, key_idx, ctr0, session_nonces)
-        n, S = kidx.size, table.n
-        ids = np.concatenate((np.flatnonzero(~table.live)[:n], np.arange(S, S + n, dtype=np.int64)))[:n]
-        grow = int(np.count_nonzero(ids >= S))
-        if grow:
-            ext = lambda t, *shape: torch.cat((t, torch.zeros((grow,) + shape, dtype=t.dtype, device=t.device)))
-            table.key, table.ctr, table.off = ext(table.key), ext(table.ctr), ext(table.off)
-            table.tail, table.nonce8 = ext(table.tail, nat.ES_FRAME_LEN), ext(table.nonce8, 8)
-            table.key_host, table.ctr_host, table.off_host = (np.concatenate((a, np.zeros(grow, np.int64)))
-                                                              for a in (table.key_host, table.ctr_host, table.off_host))
-            table.live = np.concatenate((table.live, np.zeros(grow, bool)))
-        if n:
-            rows = torch.from_numpy(ids).to(self.device)
-            table.key[rows] = torch.from_numpy(kidx.astype(np.int32)).to(self.device)
-            table.ctr[rows] = torch.from_numpy(c0).to(self.device)
-            table.off[rows] = 0
-            table.tail[rows] = 0.0
-            table.nonce8[rows] = torch.from_numpy(n8).to(self.device)
-            table.key_host[ids], table.ctr_host[ids], table.off_host[ids], table.live[ids] = kidx, c0, 0, True
-        return ids
-
-    def close_streams(self, table: StreamTable, sid) -> None:
-        """Free the rows of streams `sid`: embed_step refuses them until add_streams hands the rows out again."""
-        table.live[self._stream_ids(table, sid)] = False
-
-    @staticmethod
-    def _stream_ids(table: StreamTable, sid) -> np.ndarray:
-        """Stream ids as int64, each inside the table, open and named once."""
-        ids = np.asarray(sid.cpu().numpy() if torch.is_tensor(sid) else sid, dtype=np.int64).reshape(-1)
-        if ids.size and (ids.min() < 0 or ids.max() >= table.n):
-            raise ValueError(f"stream id outside [0, {table.n})")
-        if np.unique(ids).size != ids.size:
-            raise ValueError("a stream id appears twice in one call")
-        if not table.live[ids].all():
-            raise ValueError("a closed stream")
-        return ids
-
-    def embed_step(self, table: StreamTable, sid, chunks, *, block: int = 1024, payloads=None, seed: int | None = None,
-                   target_rel_db: float = -10.0, floor_rel_dbfs: float = -35.0, want_scale: bool = False) -> list:
-        """One tick of live streams: chunks[i] continues stream sid[i] of `table`, and the table moves on.  Entry i is, bit for bit, what
-        embed(keys[key[s]], chunks[i], ctr0=prev.ctr, carry=prev, block=block, ...) returns for s = sid[i], `prev` the EmbedResult of
-        that stream's previous chunk (none, and ctr0 = the stream's opening counter, for its first), and table.ctr / off / tail [s]
-        are then that call's EmbedResult.ctr / off / tail -- the per-stream loop this call replaces is its definition (and through it
-        WatermarkEmbedder.process over successive `block`-sized slices of every chunk, rtwm/embedder.py:44-75; the block grid starts
-        again at every chunk).  chunks: 1-D float32 arrays / tensors of any lengths, 0 included; sid: stream ids, each at most once;
-        streams not named are not touched.  payloads: per chunk sealed uint8 [>= new frames of the chunk, 55] (stream_layout says how
-        many); seed=: the bytes embed(seed=) draws for each counter, sealed under the stream's key; neither: plaintext b"ESAL" | ctr |
-        nonce8 | pad11 with `secrets` randomness sealed on the device, nonce8 the stream's own.
-        The chunks are cut into launches by scan.ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES); each launch pads its chunks into one
-        [chunks, longest rounded up to 4] tensor and runs ONE sequence whatever the number of streams and keys: keyed seal (if needed)
-        -> polar encode -> keyed schedule -> keyed frame generator -> stream mix (pending frame and new frames read where they lie) ->
-        commit, over the flat frame list stream_layout computes from the table's host mirror.  A call whose chunks are all empty
-        launches nothing.  -> [EmbedClip], one per chunk in input order."""
-        from .scan import ragged_buckets
-        from .utils import db_to_lin
-        FL = nat.ES_FRAME_LEN
-        ids = self._stream_ids(table, sid)
-        chunks = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in chunks]
-        R = len(chunks)
-        if any(c.dim() != 1 or c.dtype != torch.float32 for c in chunks):
-            raise ValueError("chunks must be 1-D float32 arrays or tensors")
-        if ids.size != R:
-            raise ValueError("one stream id per chunk is required")
-        block = int(block)
-        if block < 1:
-            raise ValueError("block must be >= 1")
-        lengths = np.array([c.numel() for c in chunks], np.int64)
-        whole = stream_layout(table.off_host[ids], table.ctr_host[ids], lengths)
-        if payloads is not None:
-            payloads = [np.zeros((0, 55), np.uint8) if p is None else np.asarray(p.cpu().numpy() if torch.is_tensor(p) else p) for p in payloads]
-            if len(payloads) != R or any(p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 55 or p.shape[0] < f for p, f in zip(payloads, whole.nf)):
-                raise ValueError("payloads: per chunk uint8 [nf >= the chunk's new frames, 55]")
-        no_scale = lambda: torch.empty(0, dtype=torch.float64, device=self.device) if want_scale else None
-        out: list = [None] * R
-        for idx in ragged_buckets(lengths, 1, EMBED_ROW_SAMPLES):
-            rows = ids[idx]
-            if int(lengths[idx].max()) == 0:                            # chunks of no samples: nothing to mix, no stream moves
-                for i in idx:
-                    out[i] = EmbedClip(torch.empty(0, dtype=torch.float32, device=self.device), int(table.ctr_host[ids[i]]),
-                                       int(table.off_host[ids[i]]), no_scale())
-                continue
-            lay = stream_layout(table.off_host[rows], table.ctr_host[rows], lengths[idx])
-            F, n = lay.rec.size, len(idx)
-            stride = (int(lengths[idx].max()) + 3) // 4 * 4
-            if all(not c.is_cuda for c in chunks):                     # one staging array, one copy
-                pad = np.zeros((n, stride), np.float32)
-                for j, i in enumerate(idx):
-                    pad[j, :lengths[i]] = chunks[i].numpy()
-                x = torch.from_numpy(pad).to(self.device)
-            else:
-                x = torch.zeros((n, stride), dtype=torch.float32, device=self.device)
-                for j, i in enumerate(idx):
-                    x[j, :lengths[i]] = chunks[i].to(self.device)
-            rec = np.ascontiguousarray(np.stack((rows, table.off_host[rows], lengths[idx], lay.chip_base, lay.chip_cnt), axis=1))   # [n, 5]
-            rec_d = torch.from_numpy(np.ascontiguousarray(rec.T)).to(self.device)                                                    # [5, n]
-            if F:
-                fr = torch.from_numpy(np.stack((lay.ctr, table.key_host[rows][lay.rec], rows[lay.rec]))).to(self.device)            # [3, F]
-                ctr_d, kf_d = fr[0], fr[1].to(torch.int32)
-                if payloads is not None:
-                    blobs = torch.from_numpy(np.concatenate([payloads[i][:f] for i, f in zip(idx, lay.nf)])).to(self.device)
-                elif seed is not None:
-                    nonces, plain = self._synthetic_plain(ctr_d, seed)
-                    blobs = self.seal_keyed(table.ring, kf_d, nonces, plain)
-                else:
-                    import secrets as _secrets
-                    plain = np.empty((F, 27), np.uint8)
-                    plain[:, :4] = np.frombuffer(b"ESAL", np.uint8)
-                    plain[:, 4:8] = lay.ctr.astype(">u4").view(np.uint8).reshape(-1, 4)
-                    plain[:, 8:16] = 0
-                    plain[:, 16:27] = np.frombuffer(_secrets.token_bytes(11 * F), np.uint8).reshape(-1, 11)
-                    nonces = np.frombuffer(_secrets.token_bytes(12 * F), np.uint8).reshape(-1, 12)
-                    plain = torch.from_numpy(plain).to(self.device)
-                    plain[:, 8:16] = table.nonce8[fr[2]]                # the stream's own session nonce
-                    blobs = self.seal_keyed(table.ring, kf_d, torch.from_numpy(nonces.copy()), plain)
-                frames = self.make_frames_keyed(table.ring, kf_d, ctr_d, blobs)
-            else:
-                frames = None                                           # every chunk lives on its stream's pending frame
-            scale = torch.empty((n, (stride + block - 1) // block), dtype=torch.float64, device=self.device) if want_scale else None
-            tick = (n, stride, _ptr(rec_d[2]))
-            pool = (_ptr(frames), F * FL, _ptr(rec_d[3]), _ptr(rec_d[4]), rec.ctypes.data)
-            nat.check(self._ctx, self._lib.es_mix_stream_batch(self._ctx, _ptr(x), *tick, block, _ptr(rec_d[0]), table.n, _ptr(table.tail),
-                                                               _ptr(table.off), *pool, db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs),
-                                                               _ptr(x), _ptr(scale), self._stream()), "es_mix_stream_batch")
-            nat.check(self._ctx, self._lib.es_stream_commit_batch(self._ctx, *tick, _ptr(rec_d[0]), table.n, _ptr(table.tail), _ptr(table.ctr),
-                                                                  _ptr(table.off), *pool, self._stream()), "es_stream_commit_batch")
-            table.ctr_host[rows], table.off_host[rows] = lay.ctr_next, lay.off_next
-            for j, i in enumerate(idx):
-                n_i = int(lengths[i])
-                out[i] = EmbedClip(x[j, :n_i], int(lay.ctr_next[j]), int(lay.off_next[j]), scale[j, :(n_i + block - 1) // block] if want_scale else None)
-        return out
-
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)
     def _ctr_dev(self, ctrs) -> torch.Tensor:
         """Frame counters as the 32-bit words the kernels compare against (stored in an int32 tensor)."""
@@ -1265,19 +684,6 @@ class RxEngine:
         nat.check(self._ctx, self._lib.es_aead_check_batch(self._ctx, bytes(key32), _ptr(blobs), n, group, _ptr(ctrs), _ptr(ok),
                                                            _ptr(plain), self._stream()), "es_aead_check_batch")
         return (ok, plain) if want_plain else ok
-
-    def aead_seal(self, key32: bytes, nonces: torch.Tensor, plain: torch.Tensor) -> torch.Tensor:
-        """SecureChannel.seal for a batch of 27-byte plaintexts (rtwm/crypto.py:33-37): nonces uint8 [n,12],
-        plain uint8 [n,27] -> blobs uint8 [n,55] on the device."""
-        if len(key32) != 32:
-            raise ValueError("AEAD key must be 32 bytes")
-        nonces = self._dev(nonces, torch.uint8); plain = self._dev(plain, torch.uint8)
-        if nonces.dim() != 2 or nonces.shape[1] != 12 or plain.shape != (nonces.shape[0], 27):
-            raise ValueError("nonces must be [n,12] and plain [n,27]")
-        blobs = torch.empty((nonces.shape[0], 55), dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_aead_seal_batch(self._ctx, bytes(key32), _ptr(nonces), _ptr(plain), nonces.shape[0],
-                                                          _ptr(blobs), self._stream()), "es_aead_seal_batch")
-        return blobs
 
     def select(self, scl: SclResult, *, key32: bytes | None = None, ctrs: torch.Tensor | None = None, ring: KeyRing | None = None,
                key_idx=None):

@@ -3,7 +3,7 @@
 For keys k_0 .. k_{N-1}, mark_batch(clips, key_idx)[i] is exactly what a freshly built WatermarkEmbedder(k_{key_idx[i]}, params) with
 frame_ctr = ctr0[i] returns from process() over successive `block`-sized slices of clips[i] (rtwm/embedder.py:44-168) -- that
 single-key host path, pinned to the reference by tests/golden/embed_mix.npz, is the definition.  What differs is the work: the clips
-of a call, whatever their lengths and keys, share one launch sequence per memory-bounded group (RxEngine.embed_batch):
+of a call, whatever their lengths and keys, share one launch sequence per memory-bounded group (RxEngine.embed_batch, in transmit.py):
 
     keys -> es_keyring_derive_batch, once                     (rtwm/crypto.py:19-30, rtwm/utils.py:86-88)
     payloads -> es_aead_seal_keyed_batch                      (rtwm/embedder.py:153-168, rtwm/crypto.py:33-37)
@@ -66,11 +66,9 @@ class WatermarkIssuer:
         order.  payloads: per clip sealed uint8 [ceil(len / 1215), 55]; seed=: deterministic payloads (RxEngine.embed_batch); neither:
         fresh randomness per call, as the reference."""
         clips = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in clips]
-        kidx = np.asarray(key_idx, dtype=np.int64).reshape(-1)
+        kidx = self._key_indices(key_idx)
         if kidx.size != len(clips):
             raise ValueError("one key index per clip is required")
-        if kidx.size and (kidx.min() < 0 or kidx.max() >= len(self.keys)):
-            raise ValueError(f"key index outside [0, {len(self.keys)})")
         if not clips:
             return []
         res = self.engine.embed_batch(self._keyring(), kidx, clips, ctr0=ctr0, block=block, payloads=payloads, seed=seed,

@@ -202,7 +202,7 @@ def check_against_host(res, host, block):
 
 @pytest.mark.parametrize("block", [1024, 700])
 def test_embed_batch_equals_embed_and_the_host_embedder(eng, clip_case, block, monkeypatch):
-    import echoseal_amd.engine as E
+    import echoseal_amd.transmit as E
     clips, payloads, host = clip_case
     res = eng.embed_batch(KEYS, CLIP_KEY, clips, ctr0=CLIP_CTR0, block=block, payloads=payloads, want_scale=True)
     assert len(res) == len(clips)
@@ -226,7 +226,7 @@ def test_embed_batch_equals_embed_and_the_host_embedder(eng, clip_case, block, m
 
 
 def test_embed_batch_seeded_and_fresh_payloads(eng, clip_case, monkeypatch):
-    import echoseal_amd.engine as E
+    import echoseal_amd.transmit as E
     clips = clip_case[0]
     want = [eng.embed(KEYS[CLIP_KEY[i]], x, ctr0=CLIP_CTR0[i], seed=77) for i, x in enumerate(clips)]
     for budget in (E.EMBED_ROW_SAMPLES, 21_003):

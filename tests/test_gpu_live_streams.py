@@ -95,6 +95,19 @@ def test_ticks_equal_the_embed_carry_chain(engine, block):
     assert int(table.ctr_host[2]) < 10                                  # stream 2 has wrapped the 32-bit counter
 
 
+def test_ticks_cut_into_several_launches_equal_the_chain(engine, monkeypatch):
+    """A launch budget of 2431 padded samples cuts every tick into at least two launches: a bucket that mixes an empty chunk with a real
+    one, a chunk that exceeds the budget on its own, streams of one tick committed by different launches -- the same bits as one launch."""
+    import echoseal_amd.transmit as T
+    from echoseal_amd.scan import ragged_buckets
+    present = [[n for n in tick if n is not None] for tick in TICKS]
+    cuts = [[[lens[i] for i in bucket] for bucket in ragged_buckets(lens, 1, 2431)] for lens in present]
+    assert all(len(c) >= 2 for c in cuts), cuts
+    assert cuts[0] == [[1, 1214], [1215, 1215], [2431]] and cuts[2] == [[0, 7], [1024, 1214], [2431], [3000]]
+    monkeypatch.setattr(T, "EMBED_ROW_SAMPLES", 2431)
+    _chain_and_ticks(engine, KEYS, KEY_IDX, CTR0, TICKS, AMPL, 1024)
+
+
 @pytest.mark.parametrize("block,on_device", [(1024, True), (9000, False)])
 def test_every_kernel_path_equals_the_chain(engine, block, on_device):
     """block 1024: a lone stream from off == 0 has its new frames at pool offset 0, so whole blocks take the aligned 16-byte reads; the

@@ -84,6 +84,55 @@ def test_stream_layout_refuses():
             stream_layout(*bad)
 
 
+def test_shared_host_steps_of_the_embeds(monkeypatch):
+    """the helpers of echoseal_amd.transmit that need no engine: counters per row, clips, payload lists, session nonces, fresh plaintexts"""
+    torch = pytest.importorskip("torch")
+    from echoseal_amd import transmit as T
+    assert T._rows_ctr0(7, 3).tolist() == [7, 7, 7] and T._rows_ctr0(7, 3).dtype == np.int64
+    assert T._rows_ctr0([1, 2 ** 32 + 5, 3], 3).tolist() == [1, 2 ** 32 + 5, 3]                 # not yet reduced mod 2^32
+    assert T._rows_ctr0(np.array([4]), 1).tolist() == [4] and T._rows_ctr0(0, 0).size == 0
+    for bad in ([1, 2], [1, 2, 3, 4], [5]):
+        with pytest.raises(ValueError, match="ctr0: a scalar or one value per stream"):
+            T._rows_ctr0(bad, 3, "stream")
+    x = np.zeros(100, np.float32)
+    got = T._clips_1d([x, torch.zeros(5), x[:0]], "clips")
+    assert [tuple(t.shape) for t in got] == [(100,), (5,), (0,)] and all(t.dtype == torch.float32 for t in got)
+    assert T._clips_1d([], "clips") == []
+    for bad, word in ((x.astype(np.float64), "float32"), (x.astype(np.int16), "float32"), (x.reshape(2, 50), "1-D")):
+        with pytest.raises(ValueError, match="chunks must be .*" + word):
+            T._clips_1d([x, bad], "chunks")
+    nf = np.array([2, 0, 1])
+    rows = [np.zeros((2, 55), np.uint8), None, np.zeros((3, 55), np.uint8)]
+    assert [p.shape for p in T._clip_payloads(rows, nf, "payloads: refused")] == [(2, 55), (0, 55), (3, 55)]
+    for bad in ([np.zeros((1, 55), np.uint8), None, rows[2]], rows[:2], [rows[0], None, np.zeros((1, 54), np.uint8)],
+                [rows[0], None, np.zeros((1, 55), np.int8)]):
+        with pytest.raises(ValueError, match="payloads: refused"):
+            T._clip_payloads(bad, nf, "payloads: refused")
+    n8 = T._session_nonces([b"A" * 8, bytearray(b"B" * 8)], 2, "refused")
+    assert n8.dtype == np.uint8 and n8.shape == (2, 8) and n8.tobytes() == b"A" * 8 + b"B" * 8
+    fresh = T._session_nonces(None, 3, "refused")
+    assert fresh.shape == (3, 8) and len({r.tobytes() for r in fresh}) == 3 and T._session_nonces(None, 0, "refused").shape == (0, 8)
+    for bad, n in (([b"A" * 7], 1), ([b"A" * 9], 1), ([b"A" * 8], 2), ([b"A" * 8] * 3, 2)):
+        with pytest.raises(ValueError, match="refused"):
+            T._session_nonces(bad, n, "refused")
+    ctr = np.array([0, 1, 2 ** 32 - 1], np.int64)
+    rows8 = np.arange(24, dtype=np.uint8).reshape(3, 8)
+    seen = []
+    for nonce_rows, want in ((rows8, rows8), (None, np.zeros((3, 8), np.uint8)), (rows8[:1], np.repeat(rows8[:1], 3, axis=0))):
+        nonces, plain = T._fresh_plain(ctr, nonce_rows)
+        assert (nonces.dtype, nonces.shape, plain.dtype, plain.shape) == (np.uint8, (3, 12), np.uint8, (3, 27))
+        assert all(plain[k, :4].tobytes() == b"ESAL" and plain[k, 4:8].tobytes() == int(c).to_bytes(4, "big") for k, c in enumerate(ctr))
+        assert np.array_equal(plain[:, 8:16], want)
+        assert nonces.flags.writeable and plain.flags.writeable         # torch.from_numpy takes them as they are
+        seen += [r.tobytes() for r in nonces]
+    assert len(set(seen)) == 9                                          # a fresh AEAD nonce per blob, call after call
+    # the draws from `secrets` come in the order of the reference embedder: the pad bytes of all frames, then the AEAD nonces
+    calls = []
+    monkeypatch.setattr(T.secrets, "token_bytes", lambda n: (calls.append(n), bytes([len(calls)]) * n)[1])
+    nonces, plain = T._fresh_plain(ctr, None)
+    assert calls == [33, 36] and (plain[:, 16:27] == 1).all() and (nonces == 2).all()
+
+
 def test_entry_points_declared_bound_and_exported():
     import echoseal_amd._native as nat
     text = open(HEADER).read()
