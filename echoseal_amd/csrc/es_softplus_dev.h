@@ -1,6 +1,7 @@
 /* es_softplus_dev.h -- the straight-line softplus of es_math.h (es_softplus_neg_fast) with fewer vector instructions, and the
  * f(a, b) built on it.  Same bits for every operand, same range flag; tests/test_softplus_dev.py compares it with es_math.h's
- * es_polar_f_fast_sp on the host, tests/test_softplus_dev_gpu.py on the device.
+ * es_polar_f_fast_sp on the host, tests/test_softplus_dev_gpu.py on the device; tests/test_softplus_sl_edges.py and
+ * tests/test_softplus_sl_gpu.py do the same at the edges of the integer rewrites further down (scale bits, corner test, kc, range flag).
  *
  * es_softplus_neg_fast evaluates four results and picks one with three 64-bit selects (two v_cndmask each):
  *     res0 = f - (hfsq - sR)                                   k == 0
@@ -22,14 +23,56 @@
 
 #include "es_math.h"
 
-/* 0.0 or 1.0 by a flag: a select of the high word only */
-ES_HD double es_flag01(int on) { return es_u2d((uint64_t)(on ? 0x3ff00000u : 0u) << 32); }
+/* the double whose words are lo and hi */
+ES_HD double es_words2d(uint32_t lo, uint32_t hi) { return es_u2d(((uint64_t)hi << 32) | lo); }
 
-/* log1p(exp(t)) for t <= 0, bit-identical to es_softplus_neg_fast (log1p's |f| < 2^-20 corner included); *ok = 0 outside |t| < 512 */
-ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
+/* 0.0 or 1.0 by a flag: a select of the high word only, over the zero low word the caller passes */
+ES_HD double es_flag01(int on, uint32_t zero_lo) { return es_words2d(zero_lo, on ? 0x3ff00000u : 0u); }
+
+/* ES_EXP_SHIFT (0x1.8p+52) in a vector register pair the compiler knows nothing about.  Its low word is zero.  The flags kf and kc
+ * are pairs (zero low word, selected high word), and a 64-bit operand is an aligned register pair: two flags alive at once over ONE
+ * zero register cost a copy of it per softplus.  The fma that forms kd cannot read both of its constants from scalar registers, so
+ * ES_EXP_SHIFT is moved into a vector pair for every f anyway: kc takes that pair's low word for its own, and the copy is gone. */
+ES_HD double es_shift_reg(void)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double x;
+    asm volatile("v_mov_b64 %0, %1" : "=v"(x) : "s"(ES_EXP_SHIFT));
+    return x;
+#else
+    return ES_EXP_SHIFT;
+#endif
+}
+
+/* x, as a value the compiler knows nothing more about.  es_polar_f_slg reads a + b through it from its second range test on: that test's
+ * |a + b| is then formed where it is used, as an operand modifier of the compare, and not carried over from the first softplus. */
+ES_HD double es_opaque(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+
+typedef uint32_t __attribute__((may_alias)) es_u32_alias;
+
+/* hi + (k << 13) mod 2^32: the high word of (hi:lo) + (k << 45).  One v_lshl_add_u32 on the device -- as long as no 64-bit value is
+ * in sight: handed the table word as one uint64_t the compiler rebuilds a 64-bit add and an or from this, so the device reads its halves. */
+ES_HD uint32_t es_scale_hi(uint32_t hi, uint32_t k) { return hi + (k << 13); }
+
+/* log1p(exp(t)) for t <= 0 and |t| < 512, bit-identical to es_softplus_neg_fast (log1p's |f| < 2^-20 corner included); sh is ES_EXP_SHIFT (es_shift_reg).
+ * Beside the float64 sequence of the header comment:
+ *   scale bits  te1 + (ki << 45): the low word of ki << 45 is zero, so nothing carries into the high word, which alone changes, by
+ *               (ki << 13) mod 2^32 (bits 0..18 of ki): one 32-bit shift-add on the high register (es_scale_hi).
+ *   corner      the high word of u in 0x3FFFFFFD..0x3FFFFFFF is "hu0 > 0x3FFFFFFC" plus ONE more case, hu0 == 0x40000000: y <= 1 gives
+ *               u <= 2, so that is u == 2 (y == 1, t == 0).  There k0 is false, f = fma(2, 0.5, -1) == +0, hfsq == +0, s == +0, z == 0,
+ *               R == 0 and sR == +0 -- the Q == 0 that now replaces it -- and P == 0 * (1 - kc*0) == +0 for kc of 0 or 1: the same bits.
+ *   -kc         fma(kc, -g, 1) == fma(-kc, g, 1) (the product has the same sign and magnitude), which leaves ONE select constant,
+ *               0x3ff00000, for both flags. */
+ES_HD double es_softplus_neg_sl_sh(double t, const uint64_t* tab, double sh)
 {
     /* ---- exp(t), main path of es_exp (as es_softplus_neg_fast) ---- */
-    double kd = ES_FMA(t, ES_EXP_INVLN2N, ES_EXP_SHIFT);
+    double kd = ES_FMA(t, ES_EXP_INVLN2N, sh);
     const uint64_t ki = es_d2u(kd);
     kd = kd - ES_EXP_SHIFT;
     double r = ES_FMA(kd, ES_EXP_NLN2HI, t);
@@ -38,13 +81,16 @@ ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
 #if defined(__HIP_DEVICE_COMPILE__) && defined(ES_EXP_TAB_LDS_ADDR)
     typedef __attribute__((address_space(3))) const uint64_t es_lds_u64;
     es_lds_u64* const te = (es_lds_u64*)(uint32_t)((ES_EXP_TAB_LDS_ADDR) + idx * 8u);
+    typedef __attribute__((address_space(3))) const es_u32_alias es_lds_u32;
+    es_lds_u32* const tw = (es_lds_u32*)(uint32_t)((ES_EXP_TAB_LDS_ADDR) + idx * 8u);
     const double tail = es_u2d(te[0]);
-    const uint64_t sbits = te[1] + (ki << 45);
+    const uint32_t te1_lo = tw[2], te1_hi = tw[3];        /* the scale word as its halves: no 64-bit value to add to */
     (void)tab;
 #else
     const double tail = es_u2d(tab[idx]);
-    const uint64_t sbits = tab[idx + 1] + (ki << 45);
+    const uint32_t te1_lo = (uint32_t)tab[idx + 1], te1_hi = (uint32_t)(tab[idx + 1] >> 32);
 #endif
+    const double scale = es_words2d(te1_lo, es_scale_hi(te1_hi, (uint32_t)ki));
     const double p23 = ES_FMA(r, ES_EXP_C3, ES_EXP_C2);
     const double tr = r + tail;
     const double r2 = r * r;
@@ -52,7 +98,6 @@ ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
     const double tq = ES_FMA(p23, r2, tr);
     const double r4 = r2 * r2;
     const double tmp = ES_FMA(r4, p45, tq);
-    const double scale = es_u2d(sbits);
     const double y = ES_FMA(scale, tmp, scale);           /* in (0, 1] */
 
     /* ---- log1p(y) ---- */
@@ -61,7 +106,7 @@ ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
     const int k0 = hy < 0x3FDA827A;                       /* y < sqrt(2)-1: k = 0, f = y */
     const double u = 1.0 + y;
     const uint32_t hu0 = (uint32_t)es_hi32(u);
-    const int corner = (uint32_t)(hu0 - 0x3FFFFFFDu) < 3u;   /* k == 1 and |f| < 2^-20 (see es_softplus_neg_fast) */
+    const int corner = hu0 > 0x3FFFFFFCu;                 /* k == 1 and |f| < 2^-20 (see es_softplus_neg_fast), or u == 2 */
     const double cn1 = y - (u - 1.0);
     const double f1 = ES_FMA(u, 0.5, -1.0);
     const double f = k0 ? y : f1;
@@ -78,24 +123,29 @@ ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
     const double R4 = ES_LP6 + z * ES_LP7;
     const double R = ((R1 + z2 * R2) + z4 * R3) + z6 * R4;
     const double sR = s * (hfsq + R);
-    const double kf = es_flag01(!k0);
-    const double kc = es_flag01(corner);
-    const double P = hfsq * ES_FMA(-kc, 0.66666666666666666 * f, 1.0);
+    const double kf = es_flag01(!k0, 0u);
+    const double kc = es_flag01(corner, (uint32_t)es_d2u(sh));
+    const double P = hfsq * ES_FMA(kc, -(0.66666666666666666 * f), 1.0);
     const double Q = (corner | tiny29) ? 0.0 : sR;
     const double W = (P - ES_FMA(kf, ES_LN2_LO + c, Q)) - f;
-    *ok = (__builtin_fabs(t) < 512.0);
     return ES_FMA(kf, ES_LN2_HI, -W);
 }
 
-/* es_polar_f_fast_sp with es_softplus_neg_sl: the same value, softplus pair and *bad (or-ed in) */
-ES_HD double es_polar_f_sl_sp(double a, double b, const uint64_t* tab, double* sp_diff, double* sp_sum, int* bad)
+/* the same with the range flag: *ok = 0 outside |t| < 512 */
+ES_HD double es_softplus_neg_sl(double t, const uint64_t* tab, int* ok)
+{
+    *ok = (__builtin_fabs(t) < 512.0);
+    return es_softplus_neg_sl_sh(t, tab, es_shift_reg());
+}
+
+/* es_polar_f_fast_sp with es_softplus_neg_sl_sh: the same value, softplus pair and *bad (or-ed in) */
+ES_HD double es_polar_f_sl_sp_sh(double a, double b, const uint64_t* tab, double* sp_diff, double* sp_sum, int* bad, double sh)
 {
     const double d1 = a - b;
     const double sum = a + b;
-    int ok1, ok2;
-    const double L1 = es_softplus_neg_sl(-__builtin_fabs(d1), tab, &ok1);
-    const double L2 = es_softplus_neg_sl(-__builtin_fabs(sum), tab, &ok2);
-    *bad |= !(ok1 & ok2);
+    const double L1 = es_softplus_neg_sl_sh(-__builtin_fabs(d1), tab, sh);
+    const double L2 = es_softplus_neg_sl_sh(-__builtin_fabs(sum), tab, sh);
+    *bad |= !((__builtin_fabs(d1) < 512.0) & (__builtin_fabs(sum) < 512.0));
     *sp_diff = L1;
     *sp_sum = L2;
     const double r1 = es_max_num(a, b) + L1;
@@ -103,27 +153,40 @@ ES_HD double es_polar_f_sl_sp(double a, double b, const uint64_t* tab, double* s
     return r1 - r2;
 }
 
-ES_HD double es_polar_f_sl(double a, double b, const uint64_t* tab, int* bad)
+ES_HD double es_polar_f_sl_sp(double a, double b, const uint64_t* tab, double* sp_diff, double* sp_sum, int* bad)
 {
-    double s0, s1;
-    return es_polar_f_sl_sp(a, b, tab, &s0, &s1, bad);
+    return es_polar_f_sl_sp_sh(a, b, tab, sp_diff, sp_sum, bad, es_shift_reg());
 }
 
-/* es_polar_f (generic softplus right after an evaluation out of range) with es_softplus_neg_sl */
-ES_HD double es_polar_f_slg(double a, double b, const uint64_t* tab)
+ES_HD double es_polar_f_sl_sh(double a, double b, const uint64_t* tab, int* bad, double sh)
+{
+    double s0, s1;
+    return es_polar_f_sl_sp_sh(a, b, tab, &s0, &s1, bad, sh);
+}
+
+ES_HD double es_polar_f_sl(double a, double b, const uint64_t* tab, int* bad)
+{
+    return es_polar_f_sl_sh(a, b, tab, bad, es_shift_reg());
+}
+
+/* es_polar_f (generic softplus right after an evaluation out of range) with es_softplus_neg_sl_sh */
+ES_HD double es_polar_f_slg_sh(double a, double b, const uint64_t* tab, double sh)
 {
     const double d1 = a - b;
-    const double sum = a + b;
-    const double t1 = -__builtin_fabs(d1);
-    const double t2 = -__builtin_fabs(sum);
-    int ok1, ok2;
-    double L1 = es_softplus_neg_sl(t1, tab, &ok1);
-    double L2 = es_softplus_neg_sl(t2, tab, &ok2);
-    if (!ok1) L1 = es_softplus_neg_generic(t1, tab);
-    if (!ok2) L2 = es_softplus_neg_generic(t2, tab);
+    const double sum0 = a + b;
+    double L1 = es_softplus_neg_sl_sh(-__builtin_fabs(d1), tab, sh);
+    double L2 = es_softplus_neg_sl_sh(-__builtin_fabs(sum0), tab, sh);
+    const double sum = es_opaque(sum0);
+    if (!(__builtin_fabs(d1) < 512.0)) L1 = es_softplus_neg_generic(-__builtin_fabs(d1), tab);
+    if (!(__builtin_fabs(sum) < 512.0)) L2 = es_softplus_neg_generic(-__builtin_fabs(sum), tab);
     const double r1 = es_max_num(a, b) + L1;
     const double r2 = es_max_num(sum, 0.0) + L2;
     return r1 - r2;
+}
+
+ES_HD double es_polar_f_slg(double a, double b, const uint64_t* tab)
+{
+    return es_polar_f_slg_sh(a, b, tab, es_shift_reg());
 }
 
 #endif /* ES_SOFTPLUS_DEV_H */
