@@ -10,6 +10,14 @@
 
 #include "../../include/echoseal_hip.h"
 
+/* global memory by its address space: what the integer kernels (es_aead.hip, es_keyring.hip) read and write through */
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+typedef __attribute__((address_space(1))) const uint32_t g_cu32;
+typedef __attribute__((address_space(1))) const int32_t g_ci32;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+typedef __attribute__((address_space(1))) uint32_t g_u32;
+typedef __attribute__((address_space(1))) int32_t g_i32;
+
 struct es_frozen_mask { uint32_t w[32]; };            /* bit i set = index i frozen */
 
 struct es_band_tables {

@@ -14,13 +14,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(1))) const uint8_t g_cu8;
-typedef __attribute__((address_space(1))) const uint32_t g_cu32;
-typedef __attribute__((address_space(1))) const int32_t g_ci32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef __attribute__((address_space(1))) uint32_t g_u32;
-typedef __attribute__((address_space(1))) int32_t g_i32;
-
 // ring row, in 32-bit words (include/echoseal_hip.h): AEAD key | AES round keys | HMAC inner state | HMAC outer state | header PN | hop0
 constexpr int RW_AEAD = 0, RW_RK = 8, RW_IPAD = 52, RW_OPAD = 60, RW_HDR = 68, RW_HOP0 = 72, RW_WORDS = ES_KEYRING_BYTES / 4;
 static_assert(RW_WORDS == 76 && ES_KEYRING_BYTES % 16 == 0, "ring row layout");
@@ -152,12 +145,91 @@ __global__ __launch_bounds__(256) void es_schedule_keyed_kernel(const uint8_t* _
     }
 }
 
-#define ES_RAGGED 0
-#include "es_plan_body.inc"
-#undef ES_RAGGED
-#define ES_RAGGED 1          // the same kernel for records of unequal length
-#include "es_plan_body.inc"
-#undef ES_RAGGED
+// The candidate (peak slot, counter) pairs of _scan_band_multi_frame in try order, for key k and row `row` = item `pair` of the
+// launch, by one wave.  T: the row's sample count, against which a peak is judged to hold a frame or not.
+__device__ __forceinline__ void plan_row(long long pair, long long k, long long row, int T, const int32_t* __restrict__ peaks_p,
+        const int32_t* __restrict__ npeaks_p, const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p,
+        const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p, int C,
+        uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p, int32_t* __restrict__ looked_p)
+{
+    const int lane = threadIdx.x & 63;
+    g_ci32* peaks = (g_ci32*)peaks_p + row * ES_MAX_PEAKS;
+    g_cu8* hop = (g_cu8*)hop_p + k * (long long)C;
+    g_u8* slot_out = (g_u8*)slot_p + pair * ES_MAX_TRIES;
+    g_u32* ctr_out = (g_u32*)cctr_p + pair * ES_MAX_TRIES;
+    const int band = ((g_cu8*)rowband_p)[row];
+    int npk = ((g_ci32*)npeaks_p)[row] & 0xFFFF;
+    npk = npk < ES_PEAK_LIMIT ? npk : ES_PEAK_LIMIT;
+    const long long p0 = ((g_ci32*)base_p)[row];
+    int tried = 0, looked = 0;
+    #pragma unroll 1
+    for (int s = 0; s < npk && tried < ES_MAX_TRIES; ++s) {
+        const int start = peaks[s];
+        if (start < 0 || (long long)start + ES_FRAME_LEN > T) continue;               // only peaks that can hold a frame
+        const long long p = p0 + looked;
+        if (p < 0 || p >= P) break;                                                   // (a header table that does not cover the row: host error)
+        ++looked;
+        const bool hok = ((g_cu8*)hok_p)[k * P + p] != 0;
+        const int lo16 = ((g_ci32*)hlo_p)[k * P + p];
+        const int est = (int)((2LL * start + ES_FRAME_LEN) / (2 * ES_FRAME_LEN));     // round(start / 1215): 1215 is odd, no ties
+        bool wide = true;
+        if (!hok) {                                                                   // the +-3 window, gated by the hop alone
+            const int c = est - 3 + lane;
+            const bool v = lane < 7 && c >= 0 && c < C && hop[c] == band;
+            const unsigned long long m = __ballot(v);
+            if (m) {
+                const int pos = tried + lanes_below(m);
+                if (v && pos < ES_MAX_TRIES) { slot_out[pos] = (uint8_t)s; ctr_out[pos] = (uint32_t)c; }
+                tried += __popcll(m);
+                wide = false;
+            }
+        }
+        if (wide) {                                                                   // the +-200 window; with a header also gated by lo16
+            const int lo = est - 200 > 0 ? est - 200 : 0, hi = est + 200;
+            #pragma unroll 1
+            for (int c0 = lo; c0 <= hi && tried < ES_MAX_TRIES; c0 += 64) {
+                const int c = c0 + lane;
+                const bool v = c <= hi && c < C && hop[c] == band && (!hok || (c & 0xFFFF) == lo16);
+                const unsigned long long m = __ballot(v);
+                const int pos = tried + lanes_below(m);
+                if (v && pos < ES_MAX_TRIES) { slot_out[pos] = (uint8_t)s; ctr_out[pos] = (uint32_t)c; }
+                tried += __popcll(m);
+            }
+        }
+        tried = tried < ES_MAX_TRIES ? tried : ES_MAX_TRIES;
+    }
+    if (lane == 0) {
+        ((g_i32*)count_p)[pair] = tried;
+        if (looked_p) ((g_i32*)looked_p)[pair] = looked;
+    }
+}
+
+// one wave per (key, row), four waves per workgroup; every row T samples
+__global__ __launch_bounds__(256) void es_plan_kernel(const int32_t* __restrict__ peaks_p, const int32_t* __restrict__ npeaks_p,
+        const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p, long long rows, int T,
+        const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p,
+        long long N, int C, uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p,
+        int32_t* __restrict__ looked_p)
+{
+    const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+    if (pair >= N * rows) return;
+    const long long k = pair / rows, row = pair - k * rows;
+    plan_row(pair, k, row, T, peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p, looked_p);
+}
+
+// the same with row r of len_p[r] samples
+__global__ __launch_bounds__(256) void es_plan_ragged_kernel(const int32_t* __restrict__ peaks_p, const int32_t* __restrict__ npeaks_p,
+        const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p, long long rows, const int32_t* __restrict__ len_p,
+        const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p,
+        long long N, int C, uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p,
+        int32_t* __restrict__ looked_p)
+{
+    const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+    if (pair >= N * rows) return;
+    const long long k = pair / rows, row = pair - k * rows;
+    plan_row(pair, k, row, ((g_ci32*)len_p)[row], peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p,
+             looked_p);
+}
 
 }  // namespace
 

@@ -6,20 +6,66 @@
 //   band-pass with zero initial state carried through the frame (rtwm/embedder.py:117-136: two lfilter calls with the
 //   state handed over = one pass; es_bpf_batch, bit-exact SciPy order); then the peak rule of :137-141
 //   (peak = max|chips| + 1e-12; if peak > 3: chips *= 1/peak) and the cast to float32.
-// The symbol kernel is written once, in es_tx_body.inc, and compiled twice: with one header PN for the batch (es_tx_frames_batch) and
-// with the header PN of each frame's key read from the key ring (es_tx_frames_keyed_batch: rtwm/embedder.py:50, 105 per key).
+// The chips of a frame are written once, in tx_symbols_frame; two thin symbol kernels hand it the 16 header-PN bytes in LDS: one header
+// PN for the batch (es_tx_frames_batch), or that of each frame's key read from the key ring (es_tx_frames_keyed_batch:
+// rtwm/embedder.py:50, 105 per key).
 #include "es_internal.h"
 
 namespace {
 
 constexpr int ES_RING_HDR_PN = 272;                               // byte offset of the header PN in a key-ring row (include/echoseal_hip.h)
 
-#define ES_KEYED 0
-#include "es_tx_body.inc"
-#undef ES_KEYED
-#define ES_KEYED 1          // the same kernel with a header PN per frame, from the key ring
-#include "es_tx_body.inc"
-#undef ES_KEYED
+// the 1215 chips of frame f, by one workgroup; hdr_pn: the frame's 16 header-PN bytes, in LDS
+__device__ __forceinline__ void tx_symbols_frame(const uint8_t* __restrict__ code, const uint8_t* __restrict__ pn_rows,
+        const uint32_t* __restrict__ ctr, unsigned long long pre_bits, const uint8_t* hdr_pn, long long f, float* __restrict__ sym)
+{
+    const uint32_t lo16 = ctr[f] & 0xFFFFu;
+    const uint8_t* pn = pn_rows + f * ES_PN_BYTES;
+    for (int i = threadIdx.x; i < ES_FRAME_LEN; i += 256) {
+        float v;
+        if (i < ES_PRE_L) {
+            v = ((pre_bits >> (63 - i)) & 1ull) ? 1.0f : -1.0f;                           // bit i of the packed MLS, MSB first
+        } else if (i < ES_PRE_L + ES_HDR_L) {
+            const int k = i - ES_PRE_L;
+            const uint32_t hb = (lo16 >> (15 - (k >> 3))) & 1u;                           // 16 bits, each repeated 8 times
+            const uint32_t pb = (hdr_pn[k >> 3] >> (7 - (k & 7))) & 1u;
+            v = (hb ? 1.0f : -1.0f) * (pb ? 1.0f : -1.0f);
+        } else {
+            const int k = i - (ES_PRE_L + ES_HDR_L);
+            const uint32_t pb = (pn[i >> 3] >> (7 - (i & 7))) & 1u;                       // PN bit 191 + k
+            v = (code[f * ES_POLAR_N + k] ? 1.0f : -1.0f) * (pb ? 1.0f : -1.0f);
+        }
+        sym[f * ES_FRAME_LEN + i] = v;
+    }
+}
+
+// one header PN for the batch
+__global__ __launch_bounds__(256) void es_tx_symbols_kernel(const uint8_t* __restrict__ code, const uint8_t* __restrict__ pn_rows,
+        const uint32_t* __restrict__ ctr, unsigned long long pre_bits, const uint8_t* __restrict__ hdr_pn_g, long long B,
+        float* __restrict__ sym)
+{
+    __shared__ uint8_t hdr_pn[16];
+    if (threadIdx.x < 16) hdr_pn[threadIdx.x] = hdr_pn_g[threadIdx.x];
+    __syncthreads();
+    for (long long f = blockIdx.x; f < B; f += gridDim.x) tx_symbols_frame(code, pn_rows, ctr, pre_bits, hdr_pn, f, sym);
+}
+
+// frame f takes its header PN from ring row key[f], bytes 272..287; a key index outside [0, N) reads nothing of the ring and gives a
+// header PN of zero bytes
+__global__ __launch_bounds__(256) void es_tx_symbols_keyed_kernel(const uint8_t* __restrict__ code, const uint8_t* __restrict__ pn_rows,
+        const uint32_t* __restrict__ ctr, unsigned long long pre_bits, const uint8_t* __restrict__ ring, long long N,
+        const int32_t* __restrict__ key_p, long long B, float* __restrict__ sym)
+{
+    __shared__ uint8_t hdr_pn[16];
+    for (long long f = blockIdx.x; f < B; f += gridDim.x) {
+        const long long key = key_p[f];                                                   // block-uniform
+        const bool have = key >= 0 && key < N;
+        __syncthreads();                                                                  // the previous frame has read its header PN
+        if (threadIdx.x < 16) hdr_pn[threadIdx.x] = have ? ring[key * ES_KEYRING_BYTES + ES_RING_HDR_PN + threadIdx.x] : (uint8_t)0;
+        __syncthreads();
+        tx_symbols_frame(code, pn_rows, ctr, pre_bits, hdr_pn, f, sym);
+    }
+}
 
 // one wave per frame: peak over the float64 chips, optional rescale, cast
 __global__ __launch_bounds__(256) void es_tx_finish_kernel(const double* __restrict__ y, long long B, float* __restrict__ out)

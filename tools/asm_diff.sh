@@ -7,6 +7,8 @@
 # BY_SYMBOL=1: a file that differs as a whole is compared again symbol by symbol -- each function's lines, its kernel descriptor and its
 # metadata entry under its name, the rest of the file in place, the function numbers in local labels (.LBB3_7) masked -- and passes as
 # "same per symbol" if only the order in which the compiler emitted the functions changed (a host-side change can move an instantiation).
+# A file that still differs gets three lists: the symbols that are identical, those that differ (with the number of differing lines) and
+# those only one side has -- for a refactor that changes some kernels of a file and must leave the others alone.
 set -e
 old=$(realpath "$1"); new=$(realpath "$2"); shift 2
 out=${OUT:-$(mktemp -d)}; mkdir -p "$out/old" "$out/new"
@@ -48,6 +50,20 @@ for f in $srcs; do
   elif [ -n "$BY_SYMBOL" ] && by_symbol "$out/old/${f%.hip}.masked" > "$out/old/${f%.hip}.sorted" && by_symbol "$out/new/${f%.hip}.masked" > "$out/new/${f%.hip}.sorted" &&
        cmp -s "$out/old/${f%.hip}.sorted" "$out/new/${f%.hip}.sorted"; then
     echo "$f: same per symbol, functions emitted in another order ($(grep -c -- '-- Begin function' "$out/new/${f%.hip}.s") functions)"
+  elif [ -n "$BY_SYMBOL" ]; then
+    # the per-symbol verdict, from the .sorted files: which symbols both sides have line for line, which differ (lines that differ, both
+    # sides counted), which only one side has.  ~meta and ~tail are the file's own lines outside any function.
+    status=1
+    o=$out/old/${f%.hip}; n=$out/new/${f%.hip}
+    cut -f1 "$o.sorted" | uniq > "$o.syms"; cut -f1 "$n.sorted" | uniq > "$n.syms"
+    comm -12 "$o.syms" "$n.syms" > "$n.both"
+    diff "$o.sorted" "$n.sorted" | sed -n 's/^[<>] \([^\t]*\)\t.*/\1/p' | sort | uniq -c | awk '{ print $2 "\t" $1 }' | sort -t "$(printf '\t')" -k1,1 | join -t "$(printf '\t')" - "$n.both" > "$n.differing" || true
+    cut -f1 "$n.differing" | comm -13 - "$n.both" > "$n.identical"
+    echo "$f: DIFFERS per symbol"
+    echo "  identical ($(wc -l < "$n.identical")):"; sed 's/^$/(before the first function)/; s/^/    /' "$n.identical"
+    echo "  differing ($(wc -l < "$n.differing")):"; awk -F '\t' '{ print "    " $1 "  (" $2 " lines)" }' "$n.differing"
+    echo "  only in old ($(comm -23 "$o.syms" "$n.syms" | wc -l)):"; comm -23 "$o.syms" "$n.syms" | sed 's/^/    /'
+    echo "  only in new ($(comm -13 "$o.syms" "$n.syms" | wc -l)):"; comm -13 "$o.syms" "$n.syms" | sed 's/^/    /'
   else
     status=1
     echo "$f: DIFFERS in"
