@@ -32,6 +32,8 @@ ES_INFO_BYTES = 55
 ES_DTYPE_F32, ES_DTYPE_I16, ES_DTYPE_F64 = 0, 1, 2
 ES_RESAMPLE_DESC_WORDS, ES_RESAMPLE_TILE = 8, 1024     # es_resample_ragged_batch: int64 words per record, outputs per workgroup
 ES_STREAM_REC_WORDS = 5                                # es_mix_stream_batch / es_stream_commit_batch: int64 words per record of rec_host
+ES_MONITOR_REC_WORDS = 5                               # es_bpf_stream_batch / es_xcorr_stream_batch: (sid, len, col, move, base)
+ES_XC_SEG = 1216                                       # lags per segment of the correlation kernel (64 lanes x 19): a monitor's window grid
 
 # name -> (restype, argtypes); kept next to the header so a test can check both agree
 SIGNATURES = {
@@ -96,6 +98,12 @@ SIGNATURES = {
                                     c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "es_stream_commit_batch": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "es_bpf_stream_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "es_xcorr_stream_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                      c_void_p, c_void_p]),
+    "es_pick_at_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
     "es_plan_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,
                               c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "es_sync_ragged_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,

@@ -646,6 +646,86 @@ int es_stream_commit_batch(es_ctx* ctx, int64_t R, int64_t n_stride, const int64
                                          chip_cnt_dev}, (hipStream_t)stream);
 }
 
+namespace {
+/* The records of a monitor tick as the host laid them out, rec_host [R][ES_MONITOR_REC_WORDS] = (sid, len, col, move, base): refused here,
+ * before anything is enqueued, where the kernels could only clamp.  -> ES_OK; *any_move: some row is moved down first; *nseg: the most
+ * correlation segments a record's new lags touch (0: no record completes a lag). */
+int check_monitor_records(es_ctx* ctx, const int64_t* rec, int64_t R, int64_t n_stride, int64_t S, int H, bool* any_move, int* nseg)
+{
+    const int64_t SEG = (int64_t)XC_SEG;
+    std::vector<uint8_t> seen((size_t)S, 0);
+    *any_move = false; *nseg = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        const int64_t* w = rec + ES_MONITOR_REC_WORDS * r;
+        const int64_t sid = w[0], len = w[1], col = w[2], move = w[3], base = w[4];
+        if (sid < 0 || sid >= S) return fail(ctx, ES_EINVAL, "monitor records: a sid outside the table");
+        if (seen[(size_t)sid]) return fail(ctx, ES_EINVAL, "monitor records: a stream named twice in one launch");
+        seen[(size_t)sid] = 1;
+        if (len < 0 || len > n_stride) return fail(ctx, ES_EINVAL, "monitor records: a length outside 0 .. n_stride");
+        if (col < 0 || col > H || len > H - col) return fail(ctx, ES_EINVAL, "monitor records: the chunk does not fit its history row");
+        if (move < 0 || move % SEG || move > H - col) return fail(ctx, ES_EINVAL, "monitor records: move is not a multiple of 1216 inside the row");
+        if (base < 0 || base % SEG) return fail(ctx, ES_EINVAL, "monitor records: base is not a multiple of 1216");
+        if (move) *any_move = true;
+        const int64_t first = col > ES_PRE_L - 1 ? col - (ES_PRE_L - 1) : 0, end = col + len - (ES_PRE_L - 1);
+        if (end > first) {
+            const int64_t n = (end + SEG - 1) / SEG - first / SEG;
+            if (n > *nseg) *nseg = (int)n;
+        }
+    }
+    return ES_OK;
+}
+}  // namespace
+
+int es_bpf_stream_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t R, int64_t n_stride, const int64_t* sid_dev, const int64_t* len_dev,
+                        const int64_t* col_dev, const int64_t* move_dev, const int64_t* base_dev, const int64_t* rec_host, int64_t S, int H,
+                        const uint8_t* band_dev, double* z_dev, int64_t* pos_dev, double* y_hist_dev, double* corr_hist_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (R < 0 || n_stride < 0 || S < 0 || H < 0) return fail(ctx, ES_EINVAL, "es_bpf_stream_batch: negative size");
+    if (dtype != ES_DTYPE_F32 && dtype != ES_DTYPE_I16) return fail(ctx, ES_EINVAL, "es_bpf_stream_batch: dtype must be f32 or i16");
+    if (R == 0) return ES_OK;
+    if (R > (int64_t)1 << 27) return fail(ctx, ES_EINVAL, "es_bpf_stream_batch: more than 2^27 records");
+    if (!sid_dev || !len_dev || !col_dev || !move_dev || !base_dev || !rec_host || !band_dev || !z_dev || !pos_dev || !y_hist_dev || !corr_hist_dev ||
+        (!x_dev && n_stride > 0))
+        return fail(ctx, ES_EINVAL, "es_bpf_stream_batch: null pointer");
+    bool any_move; int nseg;
+    const int rc = check_monitor_records(ctx, rec_host, R, n_stride, S, H, &any_move, &nseg);
+    if (rc != ES_OK) return rc;
+    DeviceGuard g(ctx->device);
+    return es_launch_bpf_stream(ctx, {R, n_stride, sid_dev, len_dev, col_dev, move_dev, base_dev, S, H, band_dev, z_dev, pos_dev, y_hist_dev,
+                                      corr_hist_dev, any_move}, x_dev, dtype, (hipStream_t)stream);
+}
+
+int es_xcorr_stream_batch(es_ctx* ctx, const double* y_hist_dev, int64_t R, int64_t n_stride, const int64_t* sid_dev, const int64_t* len_dev,
+                          const int64_t* col_dev, const int64_t* rec_host, int64_t S, int H, const uint8_t* band_dev, double* corr_hist_dev,
+                          void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (R < 0 || n_stride < 0 || S < 0 || H < 0) return fail(ctx, ES_EINVAL, "es_xcorr_stream_batch: negative size");
+    if (R == 0) return ES_OK;
+    if (!y_hist_dev || !sid_dev || !len_dev || !col_dev || !rec_host || !band_dev || !corr_hist_dev)
+        return fail(ctx, ES_EINVAL, "es_xcorr_stream_batch: null pointer");
+    bool any_move; int nseg;
+    const int rc = check_monitor_records(ctx, rec_host, R, n_stride, S, H, &any_move, &nseg);
+    if (rc != ES_OK) return rc;
+    if (nseg == 0) return ES_OK;                       /* no chunk completes a lag */
+    DeviceGuard g(ctx->device);
+    return es_launch_xcorr_stream(ctx, {R, n_stride, sid_dev, len_dev, col_dev, nullptr, nullptr, S, H, band_dev, nullptr, nullptr,
+                                        const_cast<double*>(y_hist_dev), corr_hist_dev, false}, nseg, (hipStream_t)stream);
+}
+
+int es_pick_at_batch(es_ctx* ctx, const double* corr_dev, int64_t n_rows, int stride, int64_t B, const int32_t* row_dev, const int32_t* col_dev,
+                     const int32_t* nlag_dev, double* thr_dev, int32_t* peaks_dev, int32_t* npeaks_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (B < 0 || n_rows < 0 || stride < 0) return fail(ctx, ES_EINVAL, "es_pick_at_batch: negative size");
+    if (B == 0) return ES_OK;
+    if (n_rows < 1) return fail(ctx, ES_EINVAL, "es_pick_at_batch: no rows to read");
+    if (!corr_dev || !col_dev || !nlag_dev || !thr_dev || !peaks_dev || !npeaks_dev) return fail(ctx, ES_EINVAL, "es_pick_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_pick_at(ctx, corr_dev, n_rows, stride, B, row_dev, col_dev, nlag_dev, thr_dev, peaks_dev, npeaks_dev, (hipStream_t)stream);
+}
+
 int es_tx_frames_keyed_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
                              const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* ring_dev, int64_t N,
                              const int32_t* key_dev, int64_t B, double* y_ws_dev, float* frames_dev, void* stream)

@@ -173,6 +173,17 @@ int es_launch_xcorr_ragged(es_ctx* ctx, const double* y, int64_t B, int T, const
                            hipStream_t st);
 int es_launch_pick_ragged(es_ctx* ctx, const double* corr, int64_t B, int T, const int32_t* len, double* thr, int32_t* peaks,
                           int32_t* npeaks, hipStream_t st);
+/* a tick of a live monitor (es_bpf_stream_batch, es_xcorr_stream_batch; es_sync.hip): record r continues stream sid[r] of a table of S
+ * streams, history rows of H columns; move / base / z / pos / any_move are the band-pass call's alone */
+struct es_monitor_args {
+    int64_t R; int64_t n_stride; const int64_t* sid; const int64_t* len; const int64_t* col; const int64_t* move; const int64_t* base;
+    int64_t S; int H; const uint8_t* band; double* z; int64_t* pos; double* y_hist; double* corr_hist; bool any_move;
+};
+int es_launch_bpf_stream(es_ctx* ctx, const es_monitor_args& a, const void* x, int dtype, hipStream_t st);
+int es_launch_xcorr_stream(es_ctx* ctx, const es_monitor_args& a, int nseg, hipStream_t st);
+/* windows read in place: record i = nlag[i] lags from column col[i] of row row[i] (NULL = i) of corr [n_rows][stride] (es_sync.hip) */
+int es_launch_pick_at(es_ctx* ctx, const double* corr, int64_t n_rows, int stride, int64_t B, const int32_t* row, const int32_t* col,
+                      const int32_t* nlag, double* thr, int32_t* peaks, int32_t* npeaks, hipStream_t st);
 int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at,
                   const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s,
                   float* score, hipStream_t st);

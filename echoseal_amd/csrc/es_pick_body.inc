@@ -1,7 +1,17 @@
 // es_pick_body.inc -- the float64 threshold / peak kernel, included twice by es_sync.hip: ES_RAGGED 0 = es_pick_kernel<IN_LDS, NT> (rows
 // of n lags), ES_RAGGED 1 = es_pick_ragged_kernel<NT> (record `rec` has len[rec] - 62 lags, len clamped to [0, T], at the row stride
-// T - 62, read from global memory).  One text; the equal-length kernel is compiled from exactly the tokens it always was.
-#if ES_RAGGED
+// T - 62, read from global memory), ES_RAGGED 2 = es_pick_at_kernel<NT> (record `rec` is a window read in place: nlag[rec] lags from
+// column col[rec] of row row[rec] (NULL = rec) of n_rows rows of `stride` columns; col is clamped to [0, stride], nlag to what the row
+// holds from there, a row outside the array is a window without a lag).  One text; the equal-length kernel is compiled from exactly
+// the tokens it always was.
+#if ES_RAGGED == 2
+template <int NT>
+__global__ __launch_bounds__(NT) void es_pick_at_kernel(const double* __restrict__ corr, long long n_rows, int stride, long long B,
+        const int32_t* __restrict__ row, const int32_t* __restrict__ col, const int32_t* __restrict__ nlag, double* __restrict__ thr_out,
+        int32_t* __restrict__ peaks, int32_t* __restrict__ npeaks)
+{
+    constexpr bool IN_LDS = false;                    // windows of any length inside long rows: always read from global memory
+#elif ES_RAGGED
 template <int NT>
 __global__ __launch_bounds__(NT) void es_pick_ragged_kernel(const double* __restrict__ corr, long long B, int T,
         const int32_t* __restrict__ len, double* __restrict__ thr_out, int32_t* __restrict__ peaks, int32_t* __restrict__ npeaks)
@@ -26,15 +36,25 @@ __global__ __launch_bounds__(NT) void es_pick_kernel(const double* __restrict__ 
 
     for (long long rec = blockIdx.x; rec < B; rec += gridDim.x) {
 #if ES_RAGGED
+#if ES_RAGGED == 2
+        const long long rw = row ? (long long)row[rec] : rec;
+        int c0 = col[rec];
+        c0 = c0 < 0 ? 0 : (c0 > stride ? stride : c0);
+        int n = nlag[rec];                             // the window's own lag count
+        if (n > stride - c0) n = stride - c0;
+        if (rw < 0 || rw >= n_rows) n = 0;
+        const double* cg = corr + (rw < 0 || rw >= n_rows ? 0 : rw) * stride + c0;
+#else
         int Tr = len[rec];
         Tr = Tr < 0 ? 0 : (Tr > T ? T : Tr);
         const int n = Tr - (ES_PRE_L - 1);             // the record's own lag count
+        const double* cg = corr + rec * (T - (ES_PRE_L - 1));
+#endif
         if (n < 1) {                                   // shorter than the template: no lag, no peak (rtwm/detector.py:71-73); block-uniform
             if (threadIdx.x < ES_MAX_PEAKS) peaks[rec * ES_MAX_PEAKS + threadIdx.x] = -1;
             if (threadIdx.x == 0) { npeaks[rec] = 0; thr_out[rec] = 0.0; }
             continue;
         }
-        const double* cg = corr + rec * (T - (ES_PRE_L - 1));
 #else
         const double* cg = corr + rec * n;
 #endif

@@ -209,19 +209,21 @@ constexpr int BR_RECS = 4;                          // records per wave (one per
 // per 32 samples the recursion stood still until the previous tile's stores were acknowledged -- a third of the time on long records.
 // So a block is two waves: wave 1 loads tile k+1 into LDS and stores tile k-1 from LDS while wave 0 filters tile k (LDS to LDS); one
 // workgroup barrier per tile.
-template <bool I16>
-__global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict__ frames,
-        long long B, int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
-        double* __restrict__ y, float* __restrict__ y32)
+//
+// One body behind two kernels.  A lane row's record is T samples at frames[in_off ..] (element index), its output goes to yrow / y32row
+// (nullable), its band is bi; T is uniform over the block.  CONT = false (es_bpf_row2_kernel): the recursion starts from +0.0 and runs
+// whole tiles -- the zero padding of the last one is filtered too, harmless where nothing is read after the row's end.  CONT = true
+// (es_bpf_stream_kernel): it starts from the eight delay elements at zrow and stores them back as they stand after sample T - 1 exactly,
+// so the last tile stops at the record's own end; T == 0 leaves zrow as it is.
+template <bool I16, bool CONT>
+__device__ __forceinline__ void bpf_row2_body(double (&s_x)[2][BR_RECS][BR_TT], double (&s_y)[2][BR_RECS][BR_TT], const void* __restrict__ frames,
+        long long in_off, bool live, int T, int bi, const es_band_tables* __restrict__ tabs, double* __restrict__ yrow, float* __restrict__ y32row,
+        double* __restrict__ zrow)
 {
-    __shared__ double s_x[2][BR_RECS][BR_TT];
-    __shared__ double s_y[2][BR_RECS][BR_TT];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __builtin_amdgcn_s_setprio(3);
-    const long long rec0 = (long long)blockIdx.x * BR_RECS;
     const int row = lane >> 4, k = lane & 15;
-    const long long rec = rec0 + row;
-    const bool live = rec < B;
+    if (CONT && T <= 0) return;                                    // (block-uniform, before the first barrier)
     const int ntiles = (T + BR_TT - 1) / BR_TT;
     if (wv == 1) {
         // ---- the I/O wave: tile kt+1 in, tile kt-1 out, while the other wave filters tile kt
@@ -230,11 +232,11 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
             const int t = t0 + 2 * k;
             if (live) {
                 if (I16) {
-                    const int16_t* f = (const int16_t*)frames + rec * T;
+                    const int16_t* f = (const int16_t*)frames + in_off;
                     if (t < T) v0 = (float)f[t] * (1.0f / 32768.0f);          // PCM16 as soundfile.read hands it to the reference: exact in float32
                     if (t + 1 < T) v1 = (float)f[t + 1] * (1.0f / 32768.0f);
                 } else {
-                    const float* f = (const float*)frames + rec * T;
+                    const float* f = (const float*)frames + in_off;
                     if (t < T) v0 = f[t];
                     if (t + 1 < T) v1 = f[t + 1];
                 }
@@ -254,8 +256,8 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
                     const int t = (kt - 1) * BR_TT + 2 * k + h;
                     if (t < T) {
                         const double v = s_y[(kt - 1) & 1][row][2 * k + h];
-                        y[rec * T + t] = v;
-                        if (y32) y32[rec * T + t] = (float)v;
+                        yrow[t] = v;
+                        if (y32row) y32row[t] = (float)v;
                     }
                 }
             }
@@ -267,49 +269,122 @@ __global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict
                 const int t = (ntiles - 1) * BR_TT + 2 * k + h;
                 if (t < T) {
                     const double v = s_y[(ntiles - 1) & 1][row][2 * k + h];
-                    y[rec * T + t] = v;
-                    if (y32) y32[rec * T + t] = (float)v;
+                    yrow[t] = v;
+                    if (y32row) y32row[t] = (float)v;
                 }
             }
         }
         return;
     }
     // ---- the recursion wave
-    const int bi = live ? band[rec] : 0;
     const bool owner = k < 8;                         // holds z[k]
     const double b0 = tabs->ba[bi][0];
     const double bk = owner ? tabs->ba[bi][k + 1] : 0.0, ak = owner ? tabs->ba[bi][9 + k + 1] : 0.0;
-    double z = 0.0;
+    double z = (CONT && owner && live) ? zrow[k] : 0.0;
     uint32_t nb_lo = 0u, nb_hi = 0x80000000u;         // -0.0: what lane 7 keeps as its "neighbour" (written by the row_shl:1 moves in lanes 0..6 only)
+    // one sample of the recursion, the only place it is written: -> y (lane 0's is the output)
+    auto step = [&](double xn) -> double {
+        const double t = xn * bk;                                       // b[k+1] x
+        const double yn = z + b0 * xn;                                  // lane 0: y = z[0] + b[0] x
+        const double yb = __builtin_amdgcn_update_dpp(yn, yn, 0x150, 0xf, 0xf, false);      // row_newbcast:0
+        uint64_t zu; __builtin_memcpy(&zu, &z, 8);
+        nb_lo = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_lo, (int)(uint32_t)zu, 0x101, 0xf, 0xf, false);          // row_shl:1
+        nb_hi = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_hi, (int)(uint32_t)(zu >> 32), 0x101, 0xf, 0xf, false);
+        const uint64_t nu = ((uint64_t)nb_hi << 32) | nb_lo;
+        double z_nb; __builtin_memcpy(&z_nb, &nu, 8);
+        z = (z_nb + t) - yb * ak;                                       // z[k] = (z[k+1] + b[k+1] x) - a[k+1] y
+        return yn;
+    };
     __syncthreads();                                  // tile 0 is staged
     for (int kt = 0; kt < ntiles; ++kt) {
         if (owner) {
-            #pragma unroll                                          // all of the tile's LDS reads can be issued ahead of the recursion
-            for (int tb = 0; tb < BR_TT; tb += 8) {
-                double xs[8], ys[8];
-                #pragma unroll
-                for (int u = 0; u < 8; ++u) xs[u] = s_x[kt & 1][row][tb + u];
-                #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const double xn = xs[u];
-                    const double t = xn * bk;                                       // b[k+1] x
-                    const double yn = z + b0 * xn;                                  // lane 0: y = z[0] + b[0] x
-                    const double yb = __builtin_amdgcn_update_dpp(yn, yn, 0x150, 0xf, 0xf, false);      // row_newbcast:0
-                    uint64_t zu; __builtin_memcpy(&zu, &z, 8);
-                    nb_lo = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_lo, (int)(uint32_t)zu, 0x101, 0xf, 0xf, false);          // row_shl:1
-                    nb_hi = (uint32_t)__builtin_amdgcn_update_dpp((int)nb_hi, (int)(uint32_t)(zu >> 32), 0x101, 0xf, 0xf, false);
-                    const uint64_t nu = ((uint64_t)nb_hi << 32) | nb_lo;
-                    double z_nb; __builtin_memcpy(&z_nb, &nu, 8);
-                    z = (z_nb + t) - yb * ak;                                       // z[k] = (z[k+1] + b[k+1] x) - a[k+1] y
-                    ys[u] = yn;
+            if (CONT && T - kt * BR_TT < BR_TT) {
+                // the record's last, short tile: the state must stand as sample T - 1 leaves it, so the zero padding is not filtered
+                const int nt = T - kt * BR_TT;
+                #pragma unroll 1
+                for (int u = 0; u < nt; ++u) {
+                    const double yn = step(s_x[kt & 1][row][u]);
+                    if (k == 0) s_y[kt & 1][row][u] = yn;
                 }
-                if (k == 0) {
+            } else {
+                #pragma unroll                                          // all of the tile's LDS reads can be issued ahead of the recursion
+                for (int tb = 0; tb < BR_TT; tb += 8) {
+                    double xs[8], ys[8];
                     #pragma unroll
-                    for (int u = 0; u < 8; ++u) s_y[kt & 1][row][tb + u] = ys[u];
+                    for (int u = 0; u < 8; ++u) xs[u] = s_x[kt & 1][row][tb + u];
+                    #pragma unroll
+                    for (int u = 0; u < 8; ++u) ys[u] = step(xs[u]);
+                    if (k == 0) {
+                        #pragma unroll
+                        for (int u = 0; u < 8; ++u) s_y[kt & 1][row][tb + u] = ys[u];
+                    }
                 }
             }
         }
         __syncthreads();                                           // tile kt filtered, tile kt+1 staged
+    }
+    if (CONT && owner && live) zrow[k] = z;
+}
+
+template <bool I16>
+__global__ __launch_bounds__(128) void es_bpf_row2_kernel(const void* __restrict__ frames,
+        long long B, int T, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs,
+        double* __restrict__ y, float* __restrict__ y32)
+{
+    __shared__ double s_x[2][BR_RECS][BR_TT];
+    __shared__ double s_y[2][BR_RECS][BR_TT];
+    const long long rec = (long long)blockIdx.x * BR_RECS + ((threadIdx.x & 63) >> 4);
+    const bool live = rec < B;
+    bpf_row2_body<I16, false>(s_x, s_y, frames, rec * T, live, T, live ? band[rec] : 0, tabs, y + rec * T, y32 ? y32 + rec * T : nullptr, nullptr);
+}
+
+// A tick of live streams (es_bpf_stream_batch): record r = the chunk x[r][0 : len[r]] of stream sid[r], one block per record, its four
+// lane rows the stream's four history rows 4 sid + j (band band[4 sid + j]).  The chunk is appended at column col[r] of those rows of
+// y_hist [4 S][H]; the delay elements z [4 S][8] carry the recursion from tick to tick; pos [S][2] = (samples received, absolute index
+// of column 0).  sid, len and col are device data: a sid outside the table is a record of length 0, len is cut to what the chunk row
+// and the history row hold.
+template <bool I16>
+__global__ __launch_bounds__(128) void es_bpf_stream_kernel(const void* __restrict__ x, long long R, long long n_stride,
+        const int64_t* __restrict__ sid, const int64_t* __restrict__ len, const int64_t* __restrict__ col, const int64_t* __restrict__ base,
+        long long S, int H, const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs, double* __restrict__ z,
+        int64_t* __restrict__ pos, double* __restrict__ y_hist)
+{
+    __shared__ double s_x[2][BR_RECS][BR_TT];
+    __shared__ double s_y[2][BR_RECS][BR_TT];
+    const long long r = blockIdx.x;
+    const long long s = sid[r];
+    if (s < 0 || s >= S) return;                                   // (block-uniform)
+    long long c = col[r], n = len[r];
+    c = c < 0 ? 0 : (c > H ? H : c);
+    n = n < 0 ? 0 : (n > n_stride ? n_stride : n);
+    if (n > H - c) n = H - c;
+    if (threadIdx.x == 0) { pos[2 * s] = base[r] + c + n; pos[2 * s + 1] = base[r]; }
+    const long long row = 4 * s + ((threadIdx.x & 63) >> 4);
+    bpf_row2_body<I16, true>(s_x, s_y, x, r * n_stride, true, (int)n, band[row] & 3, tabs, y_hist + row * H + c, nullptr, z + row * 8);
+}
+
+// Moves the kept part of a stream's history rows down before a chunk that would not fit: columns [move, move + keep) of the four rows
+// 4 sid + j of y_hist and of corr_hist to [0, keep).  Source and destination overlap, so ONE block owns a row and walks it upwards a tile at
+// a time, the whole tile read before any of it is written: a tile's destination lies below everything still to be read.
+constexpr int MV_NT = 256, MV_PER = 8;
+__global__ __launch_bounds__(MV_NT) void es_hist_move_kernel(long long R, const int64_t* __restrict__ sid, const int64_t* __restrict__ col,
+        const int64_t* __restrict__ move, long long S, int H, double* y_hist, double* corr_hist)
+{
+    const long long r = blockIdx.x >> 3;
+    const long long s = sid[r];
+    if (r >= R || s < 0 || s >= S) return;
+    long long mv = move[r], keep = col[r];
+    mv = mv < 0 ? 0 : (mv > H ? H : mv);
+    keep = keep < 0 ? 0 : (keep > H - mv ? H - mv : keep);
+    if (mv == 0 || keep == 0) return;                              // (block-uniform)
+    double* rowp = ((blockIdx.x & 1) ? corr_hist : y_hist) + (4 * s + ((blockIdx.x >> 1) & 3)) * (long long)H;
+    for (long long t0 = 0; t0 < keep; t0 += MV_NT * MV_PER) {
+        double v[MV_PER];
+        #pragma unroll
+        for (int u = 0; u < MV_PER; ++u) { const long long i = t0 + u * MV_NT + threadIdx.x; v[u] = (i < keep) ? rowp[mv + i] : 0.0; }
+        __syncthreads();
+        #pragma unroll
+        for (int u = 0; u < MV_PER; ++u) { const long long i = t0 + u * MV_NT + threadIdx.x; if (i < keep) rowp[i] = v[u]; }
     }
 }
 
@@ -424,6 +499,37 @@ __global__ __launch_bounds__(64 * XC_WAVES) void es_xcorr_ragged_kernel(const do
         Tr = Tr < 0 ? 0 : (Tr > T ? T : Tr);
         if (lag0 >= Tr - (ES_PRE_L - 1)) continue;                         // wholly past the record's lags (wave-uniform): no work
         xcorr_segment(s_buf[wv], lane, y, T, Tr, rec, lag0, band, tabs, corr);
+    }
+}
+
+// The new lags of a tick of live streams (es_xcorr_stream_batch).  Record r appended len[r] samples at column col[r] of its stream's four
+// history rows; lag i of a row needs samples i .. i + 62, so the lags the chunk completes are [max(0, col - 62), col + len - 62).  They are
+// computed segment by segment on the row's own segment grid (columns are absolute indices minus a multiple of 1216, so chunk phase and
+// energy order are those of the absolute lag) from the first lag of the segment that holds the first new one: lags before it that are
+// written again get the values they had.  item = (record, row, j-th segment of at most nseg); a row without a new lag does no work.
+__global__ __launch_bounds__(64 * XC_WAVES) void es_xcorr_stream_kernel(const double* __restrict__ y_hist, long long R, long long n_stride,
+        const int64_t* __restrict__ sid, const int64_t* __restrict__ len, const int64_t* __restrict__ col, long long S, int H, int nseg,
+        const uint8_t* __restrict__ band, const es_band_tables* __restrict__ tabs, double* __restrict__ corr_hist)
+{
+    __shared__ double s_buf[XC_WAVES][XC_NS + 2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long n_items = R * 4 * nseg;
+    const long long stride = (long long)gridDim.x * XC_WAVES;
+    for (long long item = (long long)blockIdx.x * XC_WAVES + wv; item < n_items; item += stride) {
+        const long long q = item / nseg, r = q >> 2;
+        const long long s = sid[r];
+        if (s < 0 || s >= S) continue;                                     // (wave-uniform, like every test below)
+        long long c = col[r], n = len[r];
+        c = c < 0 ? 0 : (c > H ? H : c);
+        n = n < 0 ? 0 : (n > n_stride ? n_stride : n);
+        if (n > H - c) n = H - c;
+        const int have = __builtin_amdgcn_readfirstlane((int)(c + n));       // samples the row holds after the chunk
+        const int first = __builtin_amdgcn_readfirstlane(c > ES_PRE_L - 1 ? (int)c - (ES_PRE_L - 1) : 0);
+        const int lag0 = (first / XC_SEG + (int)(item % nseg)) * XC_SEG;
+        if (lag0 >= have - (ES_PRE_L - 1)) continue;                       // no new lag here
+        const long long row = 4 * s + (q & 3);
+        // the row's own base pointers with record 0: segment grid and chunk phase are the row's; H as the stride of both arrays
+        xcorr_segment(s_buf[wv], lane, y_hist + row * H, H, have, 0, lag0, band + row, tabs, corr_hist + row * H);
     }
 }
 
@@ -561,6 +667,9 @@ __device__ bool block_threshold_saturates(const double* v, int n, uint32_t* s_hi
 #define ES_RAGGED 1          // the same kernel for records of unequal length
 #include "es_pick_body.inc"
 #undef ES_RAGGED
+#define ES_RAGGED 2          // ... and for windows read in place inside longer rows (es_pick_at_batch)
+#include "es_pick_body.inc"
+#undef ES_RAGGED
 
 }  // namespace
 
@@ -621,4 +730,30 @@ int es_launch_pick_ragged(es_ctx* ctx, const double* corr, int64_t B, int T, con
     // rows of any length up to T - 62, read from global memory: the big block of es_launch_pick's long rows
     return es_launch(ctx, es_pick_ragged_kernel<1024>, es_grid(B, 1, ctx->num_cu * 16), 1024, 0, st, corr, (long long)B, T, len, thr,
                      peaks, npeaks);
+}
+
+int es_launch_bpf_stream(es_ctx* ctx, const es_monitor_args& a, const void* x, int dtype, hipStream_t st)
+{
+    // any row moved down first; then one block per record: the sixteen-lanes-per-row form (a stream's four bands are one block) serves every
+    // record count -- a tick has a record per pushed stream, far fewer than would fill the chip with four lanes per row
+    if (a.any_move) {
+        const int rc = es_launch(ctx, es_hist_move_kernel, (unsigned)(a.R * 8), MV_NT, 0, st, (long long)a.R, a.sid, a.col, a.move, (long long)a.S, a.H,
+                                 a.y_hist, a.corr_hist);
+        if (rc != ES_OK) return rc;
+    }
+    return es_launch(ctx, ES_BPF_BY_DTYPE(es_bpf_stream_kernel, dtype), (unsigned)a.R, 128, 0, st, x, (long long)a.R, (long long)a.n_stride, a.sid,
+                     a.len, a.col, a.base, (long long)a.S, a.H, a.band, ctx->d_tables, a.z, a.pos, a.y_hist);
+}
+
+int es_launch_xcorr_stream(es_ctx* ctx, const es_monitor_args& a, int nseg, hipStream_t st)
+{
+    return es_launch(ctx, es_xcorr_stream_kernel, es_grid(a.R * 4 * nseg, XC_WAVES, ctx->num_cu * 16), 64 * XC_WAVES, 0, st, (const double*)a.y_hist,
+                     (long long)a.R, (long long)a.n_stride, a.sid, a.len, a.col, (long long)a.S, a.H, nseg, a.band, ctx->d_tables, a.corr_hist);
+}
+
+int es_launch_pick_at(es_ctx* ctx, const double* corr, int64_t n_rows, int stride, int64_t B, const int32_t* row, const int32_t* col,
+                      const int32_t* nlag, double* thr, int32_t* peaks, int32_t* npeaks, hipStream_t st)
+{
+    return es_launch(ctx, es_pick_at_kernel<1024>, es_grid(B, 1, ctx->num_cu * 16), 1024, 0, st, corr, (long long)n_rows, stride, (long long)B,
+                     row, col, nlag, thr, peaks, npeaks);
 }

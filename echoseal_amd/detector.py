@@ -15,6 +15,7 @@ print() debugging is not reproduced.
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass
 
 import numpy as np
@@ -146,8 +147,10 @@ class WatermarkDetector:
                 scans[i] = sc
         return self._verify_scans(scans, [la.idx for la in launches], order)
 
-    def _verify_scans(self, scans: list, launches: list, order: list) -> list[bool]:
-        """Decode and walk the prepared scans of a verify_batch call (scans[i] None: clip i is shorter than the template)."""
+    def _verify_scans(self, scans: list, launches: list, order: list, walkers: list | None = None) -> list[bool]:
+        """Decode and walk the prepared scans of a verify_batch call (scans[i] None: clip i is shorter than the template).
+        walkers: the detector that walks clip i -- its traces and its session_nonce -- where that is not this one (a LiveMonitor's
+        private detector per stream, all of this detector's key: planning and decoding are stateless and stay here)."""
         # Decoding is stateless (the validator's verdict depends on blob and counter only; nonce bookkeeping happens on the host, in
         # _accept), so it is batched ahead of the walk; the WALK is clip by clip and band by band, in the reference's order with its
         # early returns.  When the walk needs a (clip, band) that is not decoded yet, that band and -- in walk order: the clip's
@@ -185,11 +188,22 @@ class WatermarkDetector:
             ok = False
             if scans[i] is not None:
                 for bi, (plan, hdr_log) in enumerate(plans[i]):
-                    if self._scan_replay(scans[i], bi, plan, hdr_log, need(i, bi) if plan else []):
+                    if (self if walkers is None else walkers[i])._scan_replay(scans[i], bi, plan, hdr_log, need(i, bi) if plan else []):
                         ok = True
                         break
             out.append(ok)
         return out
+
+    def open_streams(self, n: int, *, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False) -> "LiveMonitor":
+        """A monitor of n live streams at fs_target, all verified under this detector's key: LiveMonitor.push takes their next chunks
+        (at most chunk_max samples each, default half a second) and says, stream by stream, whether the last window_s seconds verify.
+        trace=True records each stream's tries and header decodes of its last push (LiveMonitor.traces)."""
+        from .monitor import check_geometry
+        window = int(round(float(window_s) * self.fs_target))
+        chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
+        check_geometry(window, chunk_max)                                   # refused before any engine exists
+        band_ids = [self._band_id(b) for b in self._band_order()]
+        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids), trace=trace)
 
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
     def _scan_prepare(self, signals, bands: list) -> list:
@@ -197,16 +211,20 @@ class WatermarkDetector:
         eng = self.engine
         launch = signals if isinstance(signals, Launch) else Launch(list(range(len(signals))), [sg.size for sg in signals], signals, None, self.fs_target)
         band_ids = np.array([self._band_id(b) for b in bands], np.uint8)
-        ss = sync_launch(eng, launch, band_ids)
+        return self._scans_of(sync_launch(eng, launch, band_ids), bands, band_ids)
+
+    def _scans_of(self, ss, bands: list, band_ids: np.ndarray) -> list:
+        """The scans of a SyncScan's clips: one header decode over every peak that can hold a frame, under this detector's key."""
+        eng = self.engine
         nb, rows_a = ss.nb, ss.rows
         src = None
         hdr = (np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0))
         if rows_a.size:
-            # frame j = sy.y[rows[j], starts[j] : starts[j] + 1215], read in place (no [P, 1215] copy)
-            src = _Frames(ss.sy.y, rows_a, ss.starts)
+            # frame j = sy.y[frame_rows[j], frame_cols[j] : frame_cols[j] + 1215], read in place (no [P, 1215] copy)
+            src = _Frames(ss.sy.y, ss.frame_rows, ss.frame_cols)
             okh, val, score = eng.header(ss.sy.y, self._dev(band_ids[rows_a % nb], np.uint8),
                                          self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8),
-                                         rows=self._dev(rows_a, np.int32), start=self._dev(ss.starts, np.int32))
+                                         rows=self._dev(src.rows, np.int32), start=self._dev(src.starts, np.int32))
             hdr = (okh.cpu().numpy().astype(bool), val.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64))
         return [_Scan(bands, src, rows_a - c * nb, np.flatnonzero((rows_a // nb) == c), ss.starts, hdr) for c in range(len(ss.sizes))]
 
@@ -468,3 +486,86 @@ class WatermarkDetector:
                 except InvalidTag:
                     pass
         return None, None
+
+
+class LiveMonitor:
+    """The monitored streams of a WatermarkDetector (WatermarkDetector.open_streams); stream ids are the slots of `table`.
+
+    Stream s behaves as a private WatermarkDetector(key, fs_target, list_size) that is called once per push, in push order, on the
+    stream's window [w0, n) -- while the stream is shorter than the window, exactly verify(everything received so far, fs_target) --
+    with its own session_nonce and, with trace=True, its own traces.  What differs is the work: the band-pass and the correlation are
+    continued from the previous push instead of started again, and nothing but the new chunk is uploaded.  Every push
+    walks its whole window, as verify would."""
+
+    def __init__(self, detector: WatermarkDetector, table, *, trace: bool = False) -> None:
+        self._det, self.table, self._trace = detector, table, bool(trace)
+        self._order = detector._band_order()
+        self._walkers: dict[int, WatermarkDetector] = {}
+
+    def __len__(self) -> int:
+        return int(np.count_nonzero(self.table.live))
+
+    def _walker(self, s: int) -> WatermarkDetector:
+        w = self._walkers.get(s)
+        if w is None:                                   # the detector's key, tables and engine, a session nonce and traces of its own
+            w = self._walkers[s] = copy.copy(self._det)
+            w.session_nonce, w._trace, w._hdr_trace = None, None, None
+        return w
+
+    def push(self, chunks, streams=None, *, fs: int | None = None) -> list[bool]:
+        """chunks[i], 1-D int16 or float32 at fs_target, continues stream streams[i] (None: one chunk per open stream, in order) ->
+        per chunk, whether the stream's window now verifies.  Streams not named are not touched.  Raises ValueError before any GPU
+        work for a chunk at another rate (fs=), a chunk that is not 1-D or longer than chunk_max, a stream named twice, outside the
+        table or closed."""
+        from .monitor import monitor_chunks, monitor_ids
+        from .scan import SyncScan
+        if fs is not None and int(fs) != self._det.fs_target:
+            raise ValueError(f"chunks at {fs} Hz: a monitor's streams arrive at fs_target = {self._det.fs_target} Hz (resample each "
+                             "stream before it is pushed; chunked resampling is not part of the monitor)")
+        if streams is None:
+            streams = np.flatnonzero(self.table.live)
+        ids = monitor_ids(self.table, streams)
+        arrs = monitor_chunks(chunks, self.table.chunk_max)
+        if ids.size != len(arrs):
+            raise ValueError("one chunk per stream is required")
+        if not ids.size:
+            return []
+        det = self._det
+        tick = det.engine.monitor_step(self.table, ids, arrs)
+        scans = det._scans_of(SyncScan.from_monitor(tick), self._order, self.table.bands)
+        walkers = [self._walker(int(s)) for s in ids]
+        for w in walkers:
+            w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
+        return det._verify_scans(scans, [list(range(len(scans)))], self._order, walkers)
+
+    def position(self, stream: int) -> int:
+        """Samples stream `stream` has received since it was opened."""
+        return int(self.table.n_host[int(stream)])
+
+    def window(self, stream: int) -> tuple[int, int]:
+        """(w0, n): the samples of the stream, counted from its opening, that its last push verified."""
+        from .monitor import window_start
+        n = self.position(stream)
+        return int(window_start(n, self.table.window)), n
+
+    def session_nonce(self, stream: int) -> bytes | None:
+        """The session nonce stream `stream` is locked to (None: nothing accepted yet)."""
+        w = self._walkers.get(int(stream))
+        return None if w is None else w.session_nonce
+
+    def traces(self, stream: int):
+        """(tries, header decodes) of the stream's last push, as WatermarkDetector._trace / _hdr_trace record them (trace=True)."""
+        w = self._walkers.get(int(stream))
+        return (None, None) if w is None else (w._trace, w._hdr_trace)
+
+    def add(self, n: int = 1) -> np.ndarray:
+        """n more fresh streams -> their ids; slots of closed streams are used first."""
+        return self._det.engine.add_monitor_streams(self.table, n)
+
+    def close(self, streams) -> None:
+        """Free the slots of `streams` (their state, history and session nonce are dropped); a push to a closed stream raises."""
+        from .monitor import monitor_ids
+        ids = monitor_ids(self.table, streams)
+        self._det.engine.close_monitor_streams(self.table, ids)
+        for s in ids:
+            self._walkers.pop(int(s), None)

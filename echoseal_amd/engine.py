@@ -5,6 +5,7 @@ buffers and to name the HIP stream; every computation is a hand-written HIP kern
 mirrors one stage of the reference detector:
 
     bpf / xcorr / pick / sync   rtwm/detector.py:59-99   (band-pass, NCC, threshold, NMS)
+    open_monitor / monitor_step the same three stages continued chunk by chunk for live streams (monitor.py)
     llr                         rtwm/detector.py:296-416 (_llr)
     scl                         rtwm/fastpolar.py:254-359 (PolarCode.decode, pre-validator)
     polar_encode                rtwm/fastpolar.py:237-252
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .monitor import MonitorChain, MonitorLayout, MonitorTable, MonitorTick, monitor_layout      # the live monitor's public names stay importable from here
 from .tables import pack_tables
 from .transmit import (EMBED_ROW_SAMPLES, EmbedClip, EmbedLayout, EmbedResult, StreamLayout, StreamTable, TxChain, _ptr, embed_launches, embed_layout,
                        stream_layout)      # the transmit chain's public names stay importable from here
@@ -136,7 +138,7 @@ class PlanResult:
     looked: torch.Tensor       # [N * rows] int32: fitting peaks looked at
 
 
-class RxEngine(TxChain):
+class RxEngine(TxChain, MonitorChain):
     def __init__(self, device: int | torch.device = 0, *, list_size_max: int = 32, fs: int = 48_000, code_k: int = 448):
         """code_k: information positions of the polar code (data bits + CRC-8).  448 is the reference's own code (rtwm/polar_fast.py:8-9);
         any other 9 <= K <= 1024 (PolarCode(1024, K), rtwm/fastpolar.py:209-234) makes an engine whose `scl` is the only FEC entry point

@@ -105,8 +105,38 @@ class SyncScan:
     sy: object           # the SyncResult as the kernels wrote it
     sizes: list          # samples of each clip
     nb: int              # sync rows per clip
-    rows: np.ndarray     # int64
-    starts: np.ndarray   # int64
+    rows: np.ndarray     # int64 clip * nb + band
+    starts: np.ndarray   # int64, relative to the clip's first sample
+    yrows: np.ndarray | None = None      # where the frames lie when not at sy.y[rows, starts] (a monitor tick: history rows ...
+    cols: np.ndarray | None = None       # ... and columns, start + the window's offset)
+
+    @property
+    def frame_rows(self) -> np.ndarray:
+        return self.rows if self.yrows is None else self.yrows
+
+    @property
+    def frame_cols(self) -> np.ndarray:
+        return self.starts if self.cols is None else self.cols
+
+    @classmethod
+    def from_monitor(cls, tick) -> "SyncScan":
+        """The scan of one monitor tick (engine.MonitorTick): every pushed stream is a clip, its window [w0, n) the clip's samples.
+        Peaks and starts are window-relative, as for a clip cut at w0; the frames are read in place at history column offset + start."""
+        rows, starts = fitting_peaks(tick.peaks, tick.npeaks, tick.length)
+        return cls(tick, [int(n) for n in tick.length[::tick.nb]], tick.nb, rows, starts, tick.rows[rows], tick.offset[rows] + starts)
+
+
+def fitting_peaks(peaks, npeaks, row_sizes):
+    """The peaks of a sync result that can hold a frame, in (row, peak) order: of the first PEAK_LIMIT peaks of each row those with
+    start + 1215 <= the row's samples (rtwm/detector.py:108, 112-113) -> (rows int64, starts int64)."""
+    npk = (npeaks.cpu().numpy() & 0xFFFF)
+    pk = peaks.cpu().numpy()
+    rows, starts = [], []
+    for r in range(pk.shape[0]):
+        for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
+            if st + FRAME_LEN <= row_sizes[r]:
+                rows.append(r); starts.append(int(st))
+    return np.array(rows, np.int64), np.array(starts, np.int64)
 
 
 def sync_launch(eng, launch: Launch, band_ids) -> SyncScan:
@@ -121,11 +151,5 @@ def sync_launch(eng, launch: Launch, band_ids) -> SyncScan:
     else:
         x = x[:, :M]                                                        # (device rows: made contiguous there where the stride is longer)
         sy = eng.sync_fast(x, bid) if M - (PRE_L - 1) <= eng.FAST_MAX_LAGS else eng.sync(x, bid, keep_corr=False)
-    npk = (sy.npeaks.cpu().numpy() & 0xFFFF)
-    pk = sy.peaks.cpu().numpy()
-    rows, starts = [], []
-    for r in range(len(sizes) * nb):
-        for st in pk[r, :min(int(npk[r]), pk.shape[1], PEAK_LIMIT)]:
-            if st + FRAME_LEN <= sizes[r // nb]:                            # rtwm/detector.py:112-113, against the clip's own length
-                rows.append(r); starts.append(int(st))
-    return SyncScan(sy, sizes, nb, np.array(rows, np.int64), np.array(starts, np.int64))
+    rows, starts = fitting_peaks(sy.peaks, sy.npeaks, np.repeat(np.asarray(sizes, np.int64), nb))      # against each clip's own length
+    return SyncScan(sy, sizes, nb, rows, starts)

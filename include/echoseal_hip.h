@@ -508,6 +508,57 @@ int es_stream_commit_batch(es_ctx* ctx, int64_t R, int64_t n_stride, const int64
                            float* tail_dev, int64_t* ctr_dev, int64_t* off_dev, const float* chips_dev, int64_t chips_total,
                            const int64_t* chip_base_dev, const int64_t* chip_cnt_dev, const int64_t* rec_host, void* stream);
 
+/* ---- the receive side of live streams: a monitor that verifies many streams chunk by chunk ---------------------------------------
+ * Definition.  A monitor table holds S stream slots; stream s has received n samples X since it was opened.  Per band,
+ * y = lfilter(b, a, X) from zero state at the opening, never restarted, and corr is the normalised correlation of that y, lag i
+ * absolute, 0 <= i < n - 62.  The table keeps the recent part of both, linear rows (not a ring: the pick and the peak-addressed calls
+ * read 1215 or more contiguous columns):
+ *   z_dev         [4 S][8] float64   the band-pass's eight delay elements of row 4 s + j as they stand after sample n - 1 (+0.0 when opened)
+ *   pos_dev       [S][2] int64       (n, base): samples received, absolute index of column 0 of the stream's rows; base % 1216 == 0
+ *   y_hist_dev    [4 S][H] float64   sample a of row 4 s + j at column a - base
+ *   corr_hist_dev [4 S][H] float64   lag a at column a - base
+ *   band_dev      [4 S] uint8        band of each row
+ * 1216 = 64 * 19 is the correlation kernel's segment and 19 its chunk: the order of a lag's energy sum follows the lag's index mod 19, so
+ * any window that starts at a multiple of 19 sees, bit for bit, the correlation values the stream already has.
+ *
+ * A tick is R records; record r = the chunk x[r][0 : len[r]] of stream sid[r], appended at column col[r] = n_old - base of its rows.
+ * rec_host [R][ES_MONITOR_REC_WORDS] int64 = (sid, len, col, move, base) as the host laid them out, checked before anything is enqueued:
+ * ES_EINVAL for a sid outside [0, S) or named twice, len outside 0 .. n_stride, a chunk that does not fit its row (col outside 0 .. H or
+ * col + len > H), a move that is not a multiple of 1216 with move + col <= H, a base that is not a multiple of 1216; nothing is written
+ * then.  The device arrays (int64 [R] each) must hold the same; what they hold instead is clamped (a sid outside the table: a record of
+ * length 0; len to the chunk row and to H - col; no read or write leaves x or the table).  Both calls only enqueue (capturable).
+ *
+ * es_bpf_stream_batch continues rtwm/detector.py:59-60 (y = lfilter(b, a, x)) across calls: the four rows of each record run SciPy's
+ * direct-form-II-transposed loop from z over the chunk, x ES_DTYPE_F32 or ES_DTYPE_I16 (read as x / 32768, as es_bpf_batch) in rows of
+ * n_stride, and z is stored as it stands after sample len - 1 exactly (len == 0 leaves it): y_hist equals es_bpf_batch over the whole
+ * stream, bit for bit, whatever the cuts.  Where move[r] > 0, columns [move, move + col) of the stream's rows of y_hist and corr_hist are
+ * first moved down to [0, col) -- the host does this when a chunk would not fit -- and base[r] is the base after that move.  pos is set to
+ * (base + col + len, base).  Rows of streams the records do not name are not touched. */
+#define ES_MONITOR_REC_WORDS 5
+int es_bpf_stream_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t R, int64_t n_stride, const int64_t* sid_dev, const int64_t* len_dev,
+                        const int64_t* col_dev, const int64_t* move_dev, const int64_t* base_dev, const int64_t* rec_host, int64_t S, int H,
+                        const uint8_t* band_dev, double* z_dev, int64_t* pos_dev, double* y_hist_dev, double* corr_hist_dev, void* stream);
+
+/* The lags the same records complete, enqueued behind es_bpf_stream_batch: continues rtwm/detector.py:76-79 (corr = correlate(y, tpl,
+ * 'valid') / (sqrt(conv(y^2, 1)) + 1e-12)).  Columns [max(0, col - 62), col + len - 62) of each record's four rows of corr_hist are
+ * written, computed as es_xcorr_batch computes them on the row's own 1216-lag segment grid, from the first lag of the segment that holds
+ * the first new one (lags written again keep their values): corr_hist equals es_xcorr_batch over the whole stream's y at every lag held.
+ * A chunk that completes no lag does no work.  Arguments and refusals as above. */
+int es_xcorr_stream_batch(es_ctx* ctx, const double* y_hist_dev, int64_t R, int64_t n_stride, const int64_t* sid_dev, const int64_t* len_dev,
+                          const int64_t* col_dev, const int64_t* rec_host, int64_t S, int H, const uint8_t* band_dev, double* corr_hist_dev,
+                          void* stream);
+
+/* es_pick_batch on windows read in place: continues rtwm/detector.py:83-99 (threshold, NMS +-607, top-5 fallback).  Record i is the
+ * nlag_dev[i] lags from column col_dev[i] of row row_dev[i] (int32 [B]; row_dev NULL = i) of corr_dev [n_rows][stride]; thr, the whole
+ * peaks row (window-relative) and npeaks with its bit-30 flag are those of es_pick_batch on that slice, bit for bit (the ragged pick's
+ * kernel: same saturation proof, order statistics, NMS and fallback).  nlag < 1: npeaks 0, thr 0.0 and a peaks row of -1, as
+ * es_sync_ragged_batch gives a record shorter than the template.  For a monitor the window after a push is [w0, n) with
+ * w0 = 1216 * ceil(max(0, n - W) / 1216): col = w0 - base, nlag = n - w0 - 62.  The three arrays are device data: col is clamped to
+ * [0, stride], nlag to stride - col, a row outside [0, n_rows) is a window without a lag.  Needs no tables beyond es_set_tables having
+ * been called, only enqueues. */
+int es_pick_at_batch(es_ctx* ctx, const double* corr_dev, int64_t n_rows, int stride, int64_t B, const int32_t* row_dev, const int32_t* col_dev,
+                     const int32_t* nlag_dev, double* thr_dev, int32_t* peaks_dev, int32_t* npeaks_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
