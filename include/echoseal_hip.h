@@ -116,7 +116,12 @@ int es_pick_batch(es_ctx* ctx, const double* corr_dev, int64_t B, int n_lags, do
  *                        near a decision, by the picker of es_sync_fused_batch (same results, flags
  *                        included); records the screen cannot settle are settled from float64
  *                        re-evaluations alone, and flags_dev [B] holds the reason code 1..5 (0 =
- *                        settled from the screen), for information.  No workspace.  T - 62 <= 4096. */
+ *                        settled from the screen), for information.  No workspace.  T - 62 <= 4096.
+ *                        The caller's screen must satisfy |corr32 - corr64| <= 3e-5 at every lag (corr64 =
+ *                        what es_xcorr_batch computes from y_dev); ANY such screen yields the float64
+ *                        result, and a non-finite or absurd value (|v| >= 1e30) only costs the record the
+ *                        float64 redo (code 1).  tests/test_gpu_sync_screen.py holds this with screens
+ *                        built to be the worst case for each decision. */
 int es_bpf2_batch(es_ctx* ctx, const void* frames_dev, int dtype, int64_t B, int T,
                   const uint8_t* band_dev, double* y_dev, float* y32_dev, void* stream);
 int es_xcorr32_batch(es_ctx* ctx, const float* y32_dev, int64_t B, int T, const uint8_t* band_dev,
