@@ -31,6 +31,9 @@ ES_PEAK_LIMIT = 25
 ES_INFO_BYTES = 55
 ES_DTYPE_F32, ES_DTYPE_I16, ES_DTYPE_F64 = 0, 1, 2
 ES_RESAMPLE_DESC_WORDS, ES_RESAMPLE_TILE = 8, 1024     # es_resample_ragged_batch: int64 words per record, outputs per workgroup
+# what es_resample_ragged_kernel holds in LDS per tile (window samples, table values; more is read through L2) and what it refuses: reduced
+# up, down or taps per phase above RATE_MAX, a polyphase table above TABLE_MAX values (utils.resample_limits keeps such clips on the host)
+ES_RESAMPLE_WIN_MAX, ES_RESAMPLE_FILT_MAX, ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TABLE_MAX = 4352, 3584, 1 << 20, 1 << 30
 ES_STREAM_REC_WORDS = 5                                # es_mix_stream_batch / es_stream_commit_batch: int64 words per record of rec_host
 ES_MONITOR_REC_WORDS = 5                               # es_bpf_stream_batch / es_xcorr_stream_batch: (sid, len, col, move, base)
 ES_XC_SEG = 1216                                       # lags per segment of the correlation kernel (64 lanes x 19): a monitor's window grid

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .utils import resampled_length
+from .utils import resample_limits, resampled_length
 
 PRE_L = 63               # chips of the sync template (utils.mseq_63)
 FRAME_LEN = 1215         # PRE_L + 128 header chips + 1024 code bits
@@ -78,14 +78,15 @@ def cut_launches(clips, fs_list, fs_target: int, nb: int, condition, budget: int
     Clips shorter than the template (rtwm/detector.py:71-73) are in none.  A call whose 1-D non-empty clips are all at fs_target takes
     the host path: signals as float32 or int16 (what the band-pass kernels read), launches float32 then int16.  A call with any such
     clip at another rate takes the device path: int16 / float32 / float64 clips stay raw, bucketed by their resampled
-    lengths, launches float32, float64, int16; 2-D, empty and oddly typed clips enter as host signals at fs_target.
+    lengths, launches float32, float64, int16; 2-D, empty and oddly typed clips, and a clip whose rate pair is outside what the
+    ragged kernel takes (utils.resample_limits: it would write nothing for it), enter as host signals at fs_target.
     condition(clip, rate) -> the clip at fs_target, on the host; asked only where rate != fs_target.  The budget holds for clips of
     one length too: an over-budget group of equally long clips is several launches, each on the equal-length sync path."""
     mixed = any(f != fs_target and np.ndim(c) == 1 and np.size(c) for c, f in zip(clips, fs_list))
     arrs, rates = [], []
     for c, f in zip(clips, fs_list):
         a = np.asarray(c)
-        if not (mixed and a.ndim == 1 and a.size and a.dtype in _DEVICE_SAMPLE_TYPES):
+        if not (mixed and a.ndim == 1 and a.size and a.dtype in _DEVICE_SAMPLE_TYPES and resample_limits(a.size, f, fs_target) is None):
             a = (np.asarray(condition(a, f)) if f != fs_target else a).reshape(-1)
             a, f = (a if a.dtype == np.int16 else a.astype(np.float32, copy=False)), fs_target
         arrs.append(a); rates.append(int(f))

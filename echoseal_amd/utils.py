@@ -122,6 +122,45 @@ def resample_plan(n_in: int, up: int, down: int, dtype):
     return h_tf, padlen // up, up, down, n_pre_remove, n_out, np.dtype(ctype)
 
 
+def resample_geometry(n_in: int, up: int, down: int):
+    """The integers of resample_plan without its filter: -> (up, down, taps per phase, first kept output, number of outputs) of the
+    reduced pair, or None when the rates are equal.  Closed form of resample_plan's padding loop (the zeros appended until upfirdn's
+    output is long enough), so that a rate pair can be judged before a filter of 20 * max(up, down) + 1 taps is designed."""
+    g = math.gcd(int(up), int(down))
+    up, down = int(up) // g, int(down) // g
+    if up == down == 1:
+        return None
+    n_out = -(-int(n_in) * up // down)
+    half_len = 10 * max(up, down)
+    n_pre_pad = down - half_len % down
+    y0 = (half_len + n_pre_pad) // down
+    len_h = 2 * half_len + 1 + n_pre_pad
+    # upfirdn returns ceil((n_in + c - 1) * up / down) outputs for c taps per phase: the smallest c that gives n_out + y0 of them
+    need = n_out + y0
+    c_min = -(-((need - 1) * down + 1) // up) - int(n_in) + 1
+    return up, down, max(-(-len_h // up), c_min), y0, n_out
+
+
+def resample_limits(n_in: int, fs_orig: int, fs_target: int) -> str | None:
+    """What keeps es_resample_ragged_batch from conditioning a clip of n_in samples at fs_orig to fs_target, in words, or None when
+    it can: the kernel steps through a tile in 32 bits and writes nothing for a record whose reduced up, down or taps per phase are
+    above ES_RESAMPLE_RATE_MAX or whose polyphase table has more than ES_RESAMPLE_TABLE_MAX values (include/echoseal_hip.h)."""
+    from ._native import ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TABLE_MAX
+    g = math.gcd(int(fs_orig), int(fs_target))
+    up, down = int(fs_target) // g, int(fs_orig) // g
+    if max(up, down) > ES_RESAMPLE_RATE_MAX:                                # (before the geometry: its integers are then of no use)
+        return f"up = {up}, down = {down}: above {ES_RESAMPLE_RATE_MAX}"
+    geo = resample_geometry(n_in, up, down)
+    if geo is None:
+        return None
+    hpp = geo[2]
+    if hpp > ES_RESAMPLE_RATE_MAX:
+        return f"{hpp} taps per phase: above {ES_RESAMPLE_RATE_MAX}"
+    if up * hpp > ES_RESAMPLE_TABLE_MAX:
+        return f"a polyphase table of {up} x {hpp} values: above {ES_RESAMPLE_TABLE_MAX}"
+    return None
+
+
 @dataclass
 class ConditionPlan:
     """Host side of es_resample_ragged_batch for clips of one sample type: desc int64 [R, 8] = (offset of the clip in the flat sample
@@ -136,7 +175,9 @@ class ConditionPlan:
 def condition_plan(lengths, fs_list, fs_target: int, dtype) -> ConditionPlan:
     """The descriptors that condition clips of `lengths` samples at rates `fs_list` (one rate, or one per clip) to fs_target in one launch.
     Clips lie back to back in the sample pool, in input order.  int16 samples are resampled as float32 (x / 32768, resample_to's input
-    after soundfile.read); filters are compared by their bytes, not by the rate pair, so two rate pairs with one table share it."""
+    after soundfile.read); filters are compared by their bytes, not by the rate pair, so two rate pairs with one table share it.
+    A clip whose reduced rate pair is outside the kernel's limits (resample_limits) is refused with a ValueError that names it, before
+    any filter is designed: the kernel would write nothing for it."""
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.int16), np.dtype(np.float32), np.dtype(np.float64)):
         raise ValueError("condition_plan: samples must be int16, float32 or float64")
@@ -145,6 +186,10 @@ def condition_plan(lengths, fs_list, fs_target: int, dtype) -> ConditionPlan:
     fs = [int(f) for f in fs_list] if isinstance(fs_list, (list, tuple, np.ndarray)) else [int(fs_list)] * len(n)
     if len(fs) != len(n) or any(v < 0 for v in n) or any(f < 1 for f in fs) or int(fs_target) < 1:
         raise ValueError("condition_plan: one positive rate per clip, no negative length")
+    for r, (n_in, f) in enumerate(zip(n, fs)):
+        why = resample_limits(n_in, f, int(fs_target))
+        if why is not None:
+            raise ValueError(f"condition_plan: clip {r} ({f} Hz -> {int(fs_target)} Hz) is outside what the device conditions: {why}")
     desc = np.zeros((len(n), 8), np.int64)
     pool: list[np.ndarray] = []
     seen: dict[bytes, int] = {}

@@ -324,10 +324,19 @@ int es_resample_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t B, int6
  * float64 record is computed in float64 and rounded once to float32 on store.  A record with up == down is copied (int16 converted),
  * bit patterns and signed zeros kept.  The descriptors are device data the host cannot refuse: n_out is clamped to out_stride, reads to
  * the record's own [offset, offset + n_in) inside the pool, and a record whose filter does not lie inside the filter pool (or with
- * up, down or taps per phase outside [1, 2^20]) writes nothing.  max_out >= every n_out sizes the grid (tiles of ES_RESAMPLE_TILE
+ * up, down or taps per phase outside [1, ES_RESAMPLE_RATE_MAX], or a table above ES_RESAMPLE_TABLE_MAX values) writes nothing.  max_out >= every n_out sizes the grid (tiles of ES_RESAMPLE_TILE
  * outputs; a larger n_out is cut to it).  Needs no tables, only enqueues (capturable); R == 0 or max_out == 0 launches nothing. */
 #define ES_RESAMPLE_DESC_WORDS 8
 #define ES_RESAMPLE_TILE    1024
+/* The kernel's own constants, stated here for the host (es_resample.hip keeps them as RS_WIN_MAX, RS_FILT_MAX, RS_RATE_MAX and a literal;
+ * tests/test_condition_host.py holds the two files equal).  A tile whose input window has at most WIN_MAX samples is staged in LDS, a
+ * polyphase table of at most FILT_MAX values too; larger ones are read through L2.  A record whose reduced up, down or taps per phase
+ * exceed RATE_MAX, or whose table has more than TABLE_MAX values, is the one the kernel writes nothing for: utils.condition_plan refuses
+ * it by name and scan.cut_launches conditions such a clip on the single-clip path instead. */
+#define ES_RESAMPLE_WIN_MAX   4352
+#define ES_RESAMPLE_FILT_MAX  3584
+#define ES_RESAMPLE_RATE_MAX  (1 << 20)
+#define ES_RESAMPLE_TABLE_MAX (1 << 30)
 int es_resample_ragged_batch(es_ctx* ctx, const void* pool_dev, int dtype, int64_t pool_n, const void* filt_dev, int64_t filt_n,
                              const int64_t* desc_dev, int64_t R, int rep, float* out_dev, int64_t out_stride, int64_t max_out,
                              void* stream);

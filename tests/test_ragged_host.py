@@ -148,3 +148,31 @@ def test_plan_reference_with_a_length_per_row_equals_scan_plan():
             nonempty += bool(want)
             seen_m.add(int(M))
     assert len(seen_m) == 9 and unfit >= 20 and nonempty >= 50, (seen_m, unfit, nonempty)
+
+
+def test_cut_launches_conditions_a_clip_outside_the_kernels_limits_on_the_host():
+    """A rate pair whose reduced up or down exceeds 2^20 makes the ragged kernel write nothing: such a clip goes down the host-signal
+    path -- condition(clip, rate), as 2-D and oddly typed clips do -- while its neighbours stay raw on the device path, so the batch
+    call still equals the per-clip calls."""
+    from echoseal_amd.scan import cut_launches
+    from echoseal_amd.utils import resample_limits
+    far = 1_048_583                                                         # coprime to 48 000 and above 2^20
+    clips = [np.zeros(3000, np.float32), np.ones(70_000, np.float32), np.zeros(2900, np.int16), np.ones(70_000, np.int16), np.zeros(4000, np.float32)]
+    rates = [44_100, far, 44_100, far, 48_000]
+    assert resample_limits(70_000, far, 48_000) is not None and resample_limits(3000, 44_100, 48_000) is None
+    asked = []
+
+    def condition(clip, rate):
+        asked.append((clip.dtype, clip.size, rate))
+        return np.full(3205, 0.5, np.float64)                               # what conditioning hands back: some signal at fs_target
+    launches = cut_launches(clips, rates, 48_000, 4, condition)
+    assert asked == [(np.float32, 70_000, far), (np.int16, 70_000, far)]     # only the two clips out of range, each once
+    assert [la.idx for la in launches] == [[1, 3, 0, 4], [2]] and [la.clips[0].dtype for la in launches] == [np.float32, np.int16]
+    f32 = launches[0]
+    assert f32.rates == [48_000, 48_000, 44_100, 48_000] and f32.sizes == [3205, 3205, 3266, 4000]
+    assert f32.clips[2] is clips[0] and f32.clips[3] is clips[4] and launches[1].clips[0] is clips[2]      # raw, as they came
+    assert all(c.dtype == np.float32 and c.size == 3205 and (c == 0.5).all() for c in f32.clips[:2])
+    # alone in its call it is conditioned on the host as well, and the call is still cut for the device path
+    asked.clear()
+    (one,) = cut_launches([clips[1]], [far], 48_000, 4, condition)
+    assert asked == [(np.float32, 70_000, far)] and one.rates == [48_000] and one.sizes == [3205]
