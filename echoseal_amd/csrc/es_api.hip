@@ -775,6 +775,43 @@ int es_resample_ragged_batch(es_ctx* ctx, const void* pool_dev, int dtype, int64
                                      (hipStream_t)stream);
 }
 
+int es_resample_stream_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t R, int64_t n_stride, const int64_t* sid_dev,
+                             const int64_t* len_dev, const int64_t* rec_host, int64_t S, const int64_t* rate_dev, const float* filt_dev,
+                             int64_t filt_n, float* tail_dev, int64_t* nin_dev, float* out_dev, int64_t out_stride, void* stream)
+{
+    if (!ctx) return ES_EINVAL;                        /* no tables involved, as es_resample_ragged_batch */
+    if (R < 0 || n_stride < 0 || S < 0 || filt_n < 0 || out_stride < 0) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: negative size");
+    if (dtype != ES_DTYPE_F32 && dtype != ES_DTYPE_I16) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: dtype must be f32 or i16");
+    if (R == 0) return ES_OK;
+    if (R > (int64_t)1 << 20 || n_stride > (int64_t)1 << 30 || out_stride > (int64_t)1 << 30)
+        return fail(ctx, ES_EINVAL, "es_resample_stream_batch: more than 2^20 records or rows of more than 2^30 samples");
+    if (!sid_dev || !len_dev || !rec_host || !rate_dev || !tail_dev || !nin_dev || (!x_dev && n_stride > 0) || (!out_dev && out_stride > 0) ||
+        (!filt_dev && filt_n > 0))
+        return fail(ctx, ES_EINVAL, "es_resample_stream_batch: null pointer");
+    std::vector<uint8_t> seen((size_t)S, 0);
+    int64_t max_out = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        const int64_t* w = rec_host + ES_RSTREAM_REC_WORDS * r;
+        const int64_t sid = w[0], len = w[1], n_old = w[2], f_old = w[3], cnt = w[4], up = w[5], down = w[6], y0 = w[7];
+        if (sid < 0 || sid >= S) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: a sid outside the table");
+        if (seen[(size_t)sid]) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: a stream named twice in one launch");
+        seen[(size_t)sid] = 1;
+        if (len < 0 || len > n_stride) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: a length outside 0 .. n_stride");
+        if (up < 1 || down < 1 || up > ES_RESAMPLE_RATE_MAX || down > ES_RESAMPLE_RATE_MAX || y0 < 0 || y0 > ES_RSTREAM_Y0_MAX)
+            return fail(ctx, ES_EINVAL, "es_resample_stream_batch: rate words outside their range");
+        if (n_old < 0 || n_old > ((int64_t)1 << 62) / up - len)
+            return fail(ctx, ES_EINVAL, "es_resample_stream_batch: a stream position whose n * up leaves 62 bits");
+        const int64_t f0 = up == down ? n_old : es_rs_finalized(n_old, up, down, y0);
+        const int64_t f1 = up == down ? n_old + len : es_rs_finalized(n_old + len, up, down, y0);
+        if (f_old != f0 || cnt != f1 - f0) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: counts that disagree with the rate words");
+        if (cnt > out_stride) return fail(ctx, ES_EINVAL, "es_resample_stream_batch: more outputs than an output row holds");
+        if (cnt > max_out) max_out = cnt;
+    }
+    DeviceGuard g(ctx->device);
+    return es_launch_resample_stream(ctx, {x_dev, dtype, R, n_stride, sid_dev, len_dev, S, rate_dev, filt_dev, filt_n, tail_dev, nin_dev, out_dev,
+                                           out_stride, max_out}, (hipStream_t)stream);
+}
+
 int es_set_option(es_ctx* ctx, const char* name, int value)
 {
     if (!ctx || !name) return ES_EINVAL;

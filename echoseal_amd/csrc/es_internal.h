@@ -226,6 +226,21 @@ struct es_resample_ragged_args {
     float* out; int64_t out_stride; int64_t max_out;
 };
 int es_launch_resample_ragged(es_ctx* ctx, const es_resample_ragged_args& a, hipStream_t st);
+/* chunks of live streams at their own rates: record r continues stream sid[r] of a table of S (rate [S][5], tail [S][256], nin [S]);
+ * max_out: the most outputs a record finalizes, from the host records (es_resample_stream_batch; es_resample.hip) */
+struct es_resample_stream_args {
+    const void* x; int dtype; int64_t R; int64_t n_stride; const int64_t* sid; const int64_t* len; int64_t S; const int64_t* rate;
+    const float* filt; int64_t filt_n; float* tail; int64_t* nin; float* out; int64_t out_stride; int64_t max_out;
+};
+int es_launch_resample_stream(es_ctx* ctx, const es_resample_stream_args& a, hipStream_t st);
+/* F(n): the outputs of resample_poly(X[:n], up, down) that no later sample changes -- those whose newest input sample has arrived
+ * (DESIGN 4.16); n * up < 2^62 is the caller's to hold */
+__host__ __device__ static inline long long es_rs_finalized(long long n, long long up, long long down, long long y0)
+{
+    if (n <= 0) return 0;
+    const long long f = (n * up - 1) / down - y0 + 1;
+    return f > 0 ? f : 0;
+}
 int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* band_key32, const uint32_t* ctr_dev,
                        uint32_t ctr0, int64_t n, uint8_t* pn_rows, uint8_t* band, hipStream_t st);
 int es_launch_aead_seal(es_ctx* ctx, const uint8_t* key32, const uint8_t* nonces, const uint8_t* plain, int64_t n, uint8_t* blobs,

@@ -4,6 +4,7 @@ Host orchestration (band order, counter candidates, AEAD validation, anti-replay
 Python as in the reference; every numeric stage runs on the GPU through echoseal_amd.engine:
 
     resample_to             -> es_resample_ragged_batch            (rtwm/utils.py:58-66; clips of a batch call at other rates)
+                               es_resample_stream_batch            (the same for live streams at other rates, chunk by chunk)
     _scan_band_multi_frame  -> es_bpf / es_xcorr / es_pick        (rtwm/detector.py:59-99)
     _decode_header          -> es_header_batch, es_header_at_batch at the peaks of a scan (rtwm/detector.py:452-515)
     _llr                    -> es_llr_batch, es_llr_at_batch at the peaks of a scan       (rtwm/detector.py:296-416)
@@ -194,16 +195,20 @@ class WatermarkDetector:
             out.append(ok)
         return out
 
-    def open_streams(self, n: int, *, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False) -> "LiveMonitor":
-        """A monitor of n live streams at fs_target, all verified under this detector's key: LiveMonitor.push takes their next chunks
-        (at most chunk_max samples each, default half a second) and says, stream by stream, whether the last window_s seconds verify.
-        trace=True records each stream's tries and header decodes of its last push (LiveMonitor.traces)."""
-        from .monitor import check_geometry
+    def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False) -> "LiveMonitor":
+        """A monitor of n live streams, all verified under this detector's key: LiveMonitor.push takes their next chunks and says, stream
+        by stream, whether the last window_s seconds verify.  fs: the rate the streams arrive at, one or one per stream (None:
+        fs_target); a stream at another rate is conditioned on the device chunk by chunk, to the samples of
+        resample_poly(whole stream) that no later sample changes (finite samples only).  window_s and chunk_max (default
+        half a second) count time and samples at fs_target: a chunk may finalize at most chunk_max conditioned samples.  trace=True
+        records each stream's tries and header decodes of its last push (LiveMonitor.traces)."""
+        from .monitor import check_geometry, stream_rates
         window = int(round(float(window_s) * self.fs_target))
         chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
         check_geometry(window, chunk_max)                                   # refused before any engine exists
+        stream_rates(int(n), fs, self.fs_target)                             # ... and so is a rate that cannot be served
         band_ids = [self._band_id(b) for b in self._band_order()]
-        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids), trace=trace)
+        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids, fs=fs), trace=trace)
 
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
     def _scan_prepare(self, signals, bands: list) -> list:
@@ -495,7 +500,8 @@ class LiveMonitor:
     stream's window [w0, n) -- while the stream is shorter than the window, exactly verify(everything received so far, fs_target) --
     with its own session_nonce and, with trace=True, its own traces.  What differs is the work: the band-pass and the correlation are
     continued from the previous push instead of started again, and nothing but the new chunk is uploaded.  Every push
-    walks its whole window, as verify would."""
+    walks its whole window, as verify would.  A stream opened at another rate is conditioned on the device first; "the stream" above is
+    then its conditioned stream, resample_poly(everything received)[:F(n)]."""
 
     def __init__(self, detector: WatermarkDetector, table, *, trace: bool = False) -> None:
         self._det, self.table, self._trace = detector, table, bool(trace)
@@ -513,21 +519,28 @@ class LiveMonitor:
         return w
 
     def push(self, chunks, streams=None, *, fs: int | None = None) -> list[bool]:
-        """chunks[i], 1-D int16 or float32 at fs_target, continues stream streams[i] (None: one chunk per open stream, in order) ->
-        per chunk, whether the stream's window now verifies.  Streams not named are not touched.  Raises ValueError before any GPU
-        work for a chunk at another rate (fs=), a chunk that is not 1-D or longer than chunk_max, a stream named twice, outside the
-        table or closed."""
-        from .monitor import monitor_chunks, monitor_ids
+        """chunks[i], 1-D int16 or float32 at the rate its stream was opened with, continues stream streams[i] (None: one chunk per open
+        stream, in order) -> per chunk, whether the stream's window now verifies.  Streams not named are not touched.  fs= is a
+        check, not a conversion: every named stream must have been opened at that rate.  Raises ValueError before any GPU work for
+        that, a chunk that is not 1-D, longer than chunk_max or (at another rate) finalizing more than chunk_max samples, a stream
+        named twice, outside the table or closed."""
+        from .monitor import monitor_chunks, monitor_conditioned, monitor_ids
         from .scan import SyncScan
-        if fs is not None and int(fs) != self._det.fs_target:
-            raise ValueError(f"chunks at {fs} Hz: a monitor's streams arrive at fs_target = {self._det.fs_target} Hz (resample each "
-                             "stream before it is pushed; chunked resampling is not part of the monitor)")
+        tab, target, chunks = self.table, self._det.fs_target, list(chunks)
+        if fs is not None and tab.rs is None and int(fs) != target:
+            raise ValueError(f"chunks at {fs} Hz: this monitor's streams arrive at fs_target = {target} Hz (open a stream with fs={fs} "
+                             "to have it conditioned on the device; push(fs=) only checks the rate)")
         if streams is None:
-            streams = np.flatnonzero(self.table.live)
-        ids = monitor_ids(self.table, streams)
-        arrs = monitor_chunks(chunks, self.table.chunk_max)
-        if ids.size != len(arrs):
+            streams = np.flatnonzero(tab.live)
+        ids = monitor_ids(tab, streams)
+        if fs is not None and tab.rs is not None and (tab.rs.fs[ids] != int(fs)).any():
+            bad = int(ids[tab.rs.fs[ids] != int(fs)][0])
+            raise ValueError(f"chunks at {fs} Hz: stream {bad} was opened at {int(tab.rs.fs[bad])} Hz (fs_target = {target} Hz); push(fs=) "
+                             "only checks the rate, a stream's rate is fixed when it is opened")
+        if len(chunks) != ids.size:
             raise ValueError("one chunk per stream is required")
+        arrs = monitor_chunks(chunks, tab.chunk_max, None if tab.rs is None else tab.rs.fs[ids] == target)
+        monitor_conditioned(tab, ids, arrs)                                 # a chunk that finalizes more than chunk_max: refused here
         if not ids.size:
             return []
         det = self._det
@@ -539,8 +552,17 @@ class LiveMonitor:
         return det._verify_scans(scans, [list(range(len(scans)))], self._order, walkers)
 
     def position(self, stream: int) -> int:
-        """Samples stream `stream` has received since it was opened."""
+        """Samples at fs_target stream `stream` has been verified over since it was opened: the samples received, for a stream at
+        another rate the conditioned samples that are final."""
         return int(self.table.n_host[int(stream)])
+
+    def received(self, stream: int) -> int:
+        """Samples stream `stream` has received since it was opened, at its own rate."""
+        return int(self.table.n_in_host[int(stream)])
+
+    def rate(self, stream: int) -> int:
+        """The rate stream `stream` was opened at."""
+        return int(self.table.fs[int(stream)]) or int(self._det.fs_target)
 
     def window(self, stream: int) -> tuple[int, int]:
         """(w0, n): the samples of the stream, counted from its opening, that its last push verified."""
@@ -558,9 +580,10 @@ class LiveMonitor:
         w = self._walkers.get(int(stream))
         return (None, None) if w is None else (w._trace, w._hdr_trace)
 
-    def add(self, n: int = 1) -> np.ndarray:
-        """n more fresh streams -> their ids; slots of closed streams are used first."""
-        return self._det.engine.add_monitor_streams(self.table, n)
+    def add(self, n: int = 1, fs=None) -> np.ndarray:
+        """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
+        fs_target)."""
+        return self._det.engine.add_monitor_streams(self.table, n, fs)
 
     def close(self, streams) -> None:
         """Free the slots of `streams` (their state, history and session nonce are dropped); a push to a closed stream raises."""

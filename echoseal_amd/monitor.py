@@ -10,6 +10,10 @@ starts at a multiple of 19 sees exactly the correlation values the stream alread
 `monitor_layout` (where a tick's chunks go, and when rows are moved down) and the argument checks are host functions that need no
 engine; `MonitorChain` is the part of RxEngine that owns the table and launches a tick (es_bpf_stream_batch -> es_xcorr_stream_batch ->
 es_pick_at_batch).
+
+Streams at other rates: a slot has a rate of its own, fixed when it is opened; its chunks are conditioned on the device
+(es_resample_stream_batch) to the finalized prefix of resample_poly over the whole stream, and everything above holds with that
+conditioned stream in place of X.  `ResamplerTable` is that state (rates, filters, tails, samples received), usable on its own.
 """
 from __future__ import annotations
 
@@ -50,6 +54,88 @@ def check_geometry(window: int, chunk_max: int, hist: int | None = None) -> int:
     if 4 * hist >= 2 ** 31:
         raise ValueError("history rows of 2^29 columns or more are not supported")
     return hist
+
+
+@dataclass
+class ResamplerTable:
+    """The resampling state of S live streams (RxEngine.open_resampler; a MonitorTable with rates holds one as `rs`).  Stream s arrives at
+    fs[s] and is conditioned to fs_target: rate_host[s] = (up, down, offset of its filter in the pool, taps per phase, y0), the words
+    es_resample_stream_batch reads; a stream at fs_target has (1, 1, 0, 0, 0) and is copied.  In a monitor the chunks of streams at
+    fs_target go straight to the band-pass, never through the resampling kernels: there the device `tail` and `nin` are kept for the
+    other-rate slots only (an at-rate slot's stay +0.0 and 0; n_in_host counts for every slot).  A table of RxEngine.open_resampler
+    keeps them for every stream."""
+    fs_target: int
+    fs: np.ndarray             # [S] int64 rate of each stream
+    rate_host: np.ndarray      # [S, 5] int64
+    filters: np.ndarray        # float32 pool, one copy per distinct rate
+    n_in_host: np.ndarray      # [S] int64 samples received at the stream's own rate (host mirror of nin)
+    offsets: dict              # rate -> (up, down, filter offset, hpp, y0)
+    rate: object = None        # [S, 5] int64 device
+    filt: object = None        # float32 device
+    tail: object = None        # [S, 256] float32 device: the last 256 samples received, newest last (the kernel reads the newest 255)
+    nin: object = None         # [S] int64 device
+
+    @property
+    def n(self) -> int:
+        return int(self.fs.size)
+
+
+def stream_rates(n_streams: int, fs, fs_target: int) -> np.ndarray:
+    """`fs` (None: every stream at fs_target; one rate; or one per stream) as int64 [n_streams], each rate checked by
+    utils.stream_geometry (integers only, no filter is designed).  A ValueError names what is refused; nothing is changed."""
+    S, fs_target = int(n_streams), int(fs_target)
+    if fs is None:
+        return np.full(S, fs_target, np.int64)
+    if np.ndim(fs) == 0:
+        fs = [fs] * S
+    rates = [int(f) for f in fs]
+    if len(rates) != S:
+        raise ValueError(f"fs names {len(rates)} rates for {S} streams: give one rate, or one per stream")
+    from .utils import stream_geometry
+    for f in sorted(set(rates)):
+        stream_geometry(f, fs_target)
+    return np.asarray(rates, np.int64).reshape(S)
+
+
+def resampler_extend(rt: ResamplerTable, fs) -> None:
+    """Append streams at rates `fs` to the host half of rt: a rate not seen before adds its filter to the pool (designed once)."""
+    from .utils import stream_resample_plan
+    rows = []
+    for f in (int(v) for v in fs):
+        if f not in rt.offsets:
+            pl = stream_resample_plan(f, rt.fs_target)                      # refuses by name
+            rt.offsets[f] = (pl.up, pl.down, int(rt.filters.size) if pl.hpp else 0, pl.hpp, pl.y0)
+            rt.filters = np.concatenate((rt.filters, pl.h_tf))
+        rows.append(rt.offsets[f])
+    rt.rate_host = np.concatenate((rt.rate_host, np.asarray(rows, np.int64).reshape(-1, nat.ES_RSTREAM_RATE_WORDS)))
+    rt.fs = np.concatenate((rt.fs, np.asarray(list(fs), np.int64).reshape(-1)))
+    rt.n_in_host = np.concatenate((rt.n_in_host, np.zeros(len(rows), np.int64)))
+
+
+def resampler_host(fs_list, fs_target: int) -> ResamplerTable:
+    """The host half of a resampler table for streams at rates fs_list, checked; RxEngine.open_resampler adds the device arrays."""
+    fs_target = int(fs_target)
+    if fs_target < 1:
+        raise ValueError("fs_target must be positive")
+    rt = ResamplerTable(fs_target, np.zeros(0, np.int64), np.zeros((0, nat.ES_RSTREAM_RATE_WORDS), np.int64), np.zeros(0, np.float32),
+                        np.zeros(0, np.int64), {})
+    resampler_extend(rt, np.asarray(fs_list, np.int64).reshape(-1))
+    return rt
+
+
+def resample_counts(rt: ResamplerTable, ids: np.ndarray, lengths: np.ndarray):
+    """-> (F(n_old), outputs finalized) int64 per chunk of `lengths` samples pushed to streams `ids`, from the host mirror alone.  A
+    position at which n * up would pass 2^62 is refused."""
+    from .utils import finalized, stream_position_limit
+    f_old, cnt = np.zeros(ids.size, np.int64), np.zeros(ids.size, np.int64)
+    for i, (s, ln) in enumerate(zip(ids.tolist(), lengths.tolist())):
+        up, down, _, _, y0 = (int(v) for v in rt.rate_host[s])
+        n_old = int(rt.n_in_host[s])
+        if n_old + ln > stream_position_limit(up):
+            raise ValueError(f"stream {s} at {int(rt.fs[s])} Hz: position {n_old + ln} times up = {up} passes 2^62")
+        f_old[i] = finalized(n_old, up, down, y0) if up != down else n_old
+        cnt[i] = (finalized(n_old + ln, up, down, y0) if up != down else n_old + ln) - f_old[i]
+    return f_old, cnt
 
 
 @dataclass
@@ -100,14 +186,28 @@ class MonitorTable:
     pos: object = None         # [S, 2] int64 device: (n, base)
     y_hist: object = None      # [4 S, H] float64 device
     corr_hist: object = None   # [4 S, H] float64 device
+    fs_target: int = 0         # the rate the streams are conditioned to (0: not stated -- every stream arrives at it)
+    rs: ResamplerTable | None = None        # rates, filters, tails and samples received of streams at other rates (None: all at fs_target)
+
+    @property
+    def fs(self) -> np.ndarray:
+        """[S] int64 rate of each stream (fs_target where none was given)."""
+        return np.full(self.n, self.fs_target, np.int64) if self.rs is None else self.rs.fs
+
+    @property
+    def n_in_host(self) -> np.ndarray:
+        """[S] int64 samples received at the stream's own rate (n_host is the conditioned position)."""
+        return self.n_host if self.rs is None else self.rs.n_in_host
 
     @property
     def n(self) -> int:
         return int(self.live.size)
 
 
-def host_table(n_streams: int, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3)) -> MonitorTable:
-    """The host half of a monitor table, checked; RxEngine.open_monitor adds the device arrays."""
+def host_table(n_streams: int, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), *, fs=None,
+               fs_target: int | None = None) -> MonitorTable:
+    """The host half of a monitor table, checked; RxEngine.open_monitor adds the device arrays.  fs: the rate of every stream, or one per
+    stream (None: all at fs_target, which then need not be stated)."""
     hist = check_geometry(window, chunk_max, hist)
     S = int(n_streams)
     if S < 0:
@@ -115,7 +215,15 @@ def host_table(n_streams: int, window: int, chunk_max: int, hist: int | None = N
     b = np.asarray(bands, dtype=np.int64).reshape(-1)
     if b.size != nat.ES_NBANDS or sorted(b.tolist()) != list(range(nat.ES_NBANDS)):
         raise ValueError("bands: the four band indices, each once")
-    return MonitorTable(int(window), int(chunk_max), hist, b.astype(np.uint8), np.zeros(S, np.int64), np.zeros(S, np.int64), np.ones(S, bool))
+    t = MonitorTable(int(window), int(chunk_max), hist, b.astype(np.uint8), np.zeros(S, np.int64), np.zeros(S, np.int64), np.ones(S, bool),
+                     fs_target=int(fs_target or 0))
+    if fs is not None:
+        if not fs_target:
+            raise ValueError("fs needs fs_target, the rate the streams are conditioned to")
+        rates = stream_rates(S, fs, fs_target)
+        if (rates != t.fs_target).any():
+            t.rs = resampler_host(rates, fs_target)
+    return t
 
 
 def monitor_ids(table: MonitorTable, sid) -> np.ndarray:
@@ -130,18 +238,38 @@ def monitor_ids(table: MonitorTable, sid) -> np.ndarray:
     return ids
 
 
-def monitor_chunks(chunks, chunk_max: int) -> list:
-    """The chunks of a tick as 1-D int16 or float32 host arrays (other sample types are converted to float32, as verify() does)."""
+def monitor_chunks(chunks, chunk_max: int, at_rate=None) -> list:
+    """The chunks of a tick as 1-D int16 or float32 host arrays (other sample types are converted to float32, as verify() does).
+    chunk_max counts samples at fs_target (None: any length): at_rate[i] False marks a chunk at another rate, whose finalized outputs
+    monitor_conditioned holds to it instead."""
     out = []
-    for c in chunks:
+    for i, c in enumerate(chunks):
         a = np.asarray(c.cpu().numpy() if hasattr(c, "cpu") else c)
         if a.ndim != 1:
             raise ValueError(f"a chunk of {a.ndim} dimensions: chunks are 1-D sample arrays, one channel per stream")
-        if a.size > chunk_max:
+        if chunk_max is not None and a.size > chunk_max and (at_rate is None or at_rate[i]):
             raise ValueError(f"a chunk of {a.size} samples is longer than chunk_max = {chunk_max}: push it in pieces, or open the monitor "
                              "with a larger chunk_max")
         out.append(np.ascontiguousarray(a if a.dtype == np.int16 else a.astype(np.float32, copy=False)))
     return out
+
+
+def monitor_conditioned(table: MonitorTable, ids: np.ndarray, arrs: list):
+    """-> (lengths at fs_target, other-rate mask, F(n_old)) int64 / bool / int64 per chunk: a chunk at fs_target counts as it is, one at
+    another rate as the outputs it finalizes, refused where they exceed chunk_max.  Host mirror only."""
+    lengths = np.array([a.size for a in arrs], np.int64)
+    other = np.zeros(ids.size, bool) if table.rs is None else table.rs.rate_host[ids, 0] != table.rs.rate_host[ids, 1]
+    f_old = np.zeros(ids.size, np.int64)
+    if other.any():
+        f_old[other], cnt = resample_counts(table.rs, ids[other], lengths[other])
+        if cnt.size and cnt.max() > table.chunk_max:
+            i = int(np.flatnonzero(other)[int(cnt.argmax())])
+            raise ValueError(f"a chunk of {arrs[i].size} samples at {int(table.rs.fs[ids[i]])} Hz finalizes {int(cnt.max())} samples at "
+                             f"{table.fs_target} Hz, more than chunk_max = {table.chunk_max}: push it in pieces, or open the monitor with "
+                             "a larger chunk_max")
+        lengths = lengths.copy()
+        lengths[other] = cnt
+    return lengths, other, f_old
 
 
 @dataclass
@@ -163,12 +291,90 @@ class MonitorChain:
     """The monitor methods of RxEngine (a mixin without state of its own).  From the engine it uses _ctx, _lib, device, _stream and
     _peak_out."""
 
-    def open_monitor(self, n_streams: int, *, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3)) -> MonitorTable:
-        """A table of n_streams fresh streams at the engine's rate: windows of `window` samples (>= 2 * 1216), chunks of at most
-        chunk_max samples, history rows of `hist` columns (default and minimum window + 1216 + chunk_max), row j of every stream on
-        band bands[j].  Everything is allocated here; monitor_step only enqueues."""
+    # ---- chunked resampling on its own (DESIGN 4.16)
+    def _resampler_device(self, rt: ResamplerTable) -> None:
+        """(Re)build the device half of rt from its host half, keeping the tails and counts of the streams it already has."""
         import torch
-        t = host_table(n_streams, window, chunk_max, hist, bands)
+        dev, S = self.device, rt.n
+        rt.rate = torch.from_numpy(np.ascontiguousarray(rt.rate_host)).to(dev)
+        rt.filt = torch.from_numpy(rt.filters if rt.filters.size else np.zeros(1, np.float32)).to(dev)
+        old = 0 if rt.tail is None else int(rt.tail.shape[0])
+        tail = torch.zeros((S, nat.ES_RSTREAM_TAIL), dtype=torch.float32, device=dev)
+        nin = torch.zeros(S, dtype=torch.int64, device=dev)
+        if old:
+            tail[:old], nin[:old] = rt.tail, rt.nin
+        rt.tail, rt.nin = tail, nin
+
+    def open_resampler(self, fs_list, fs_target: int) -> ResamplerTable:
+        """A table of fresh streams at rates fs_list, conditioned to fs_target chunk by chunk (any target, not only the engine's)."""
+        rt = resampler_host(fs_list, fs_target)
+        self._resampler_device(rt)
+        return rt
+
+    def _resample_enqueue(self, rt: ResamplerTable, ids, lengths, f_old, counts, x_ptr: int, dtype: int, n_stride: int, sid_ptr: int, len_ptr: int,
+                          out_ptr: int, out_stride: int) -> None:
+        """One es_resample_stream_batch over records that already lie on the device; the host mirror moves on."""
+        rec = np.ascontiguousarray(np.concatenate((np.stack((ids, lengths, rt.n_in_host[ids], f_old, counts), axis=1), rt.rate_host[ids][:, [0, 1, 4]]),
+                                                  axis=1).astype(np.int64))                                        # [R, 8], as the C ABI checks it
+        nat.check(self._ctx, self._lib.es_resample_stream_batch(self._ctx, x_ptr, dtype, ids.size, n_stride, sid_ptr, len_ptr, rec.ctypes.data, rt.n,
+                                                                rt.rate.data_ptr(), rt.filt.data_ptr(), int(rt.filters.size), rt.tail.data_ptr(),
+                                                                rt.nin.data_ptr(), out_ptr, out_stride, self._stream()), "es_resample_stream_batch")
+        rt.n_in_host[ids] += lengths
+
+    def resample_step(self, table: ResamplerTable, sid, chunks, *, out=None):
+        """chunks[i] (1-D int16 or float32, any length) continues stream sid[i] -> (float32 rows [R, stride] on the device, counts int64 [R]):
+        row i holds the counts[i] samples the chunk finalizes, r[F(n_old) : F(n_new)] of r = resample_poly(whole stream, up, down) -- bit
+        for bit, possibly none; the rest of a row is not written (out: the rows the kernels write into, float32 [>= R, >= max count],
+        float32 chunks first; what is returned is those rows in input order).  One upload, one launch per sample type present."""
+        import torch
+        ids = np.asarray(sid, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= table.n):
+            raise ValueError(f"stream id outside [0, {table.n})")
+        if np.unique(ids).size != ids.size:
+            raise ValueError("a stream is named twice in one step: give each stream one chunk per step (concatenate its chunks)")
+        arrs = monitor_chunks(chunks, None)
+        if ids.size != len(arrs):
+            raise ValueError("one stream id per chunk is required")
+        R = ids.size
+        lengths = np.array([a.size for a in arrs], np.int64)
+        f_old, counts = resample_counts(table, ids, lengths)
+        if out is None:
+            out = torch.empty((R, max(4, (int(counts.max()) + 3) // 4 * 4) if R else 4), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < R or (R and out.shape[1] < counts.max()):
+            raise ValueError("out: contiguous float32 rows, one per chunk, as long as the most outputs a chunk finalizes")
+        ostride = int(out.shape[1])
+        if R == 0:
+            return out[:0], counts
+        order = np.argsort([a.dtype == np.int16 for a in arrs], kind="stable")
+        k32 = int(sum(a.dtype != np.int16 for a in arrs))
+        stride = max(4, (int(lengths.max()) + 3) // 4 * 4)
+        buf = np.zeros(k32 * stride * 4 + (R - k32) * stride * 2, np.uint8)
+        x32 = buf[:k32 * stride * 4].view(np.float32).reshape(k32, stride)
+        x16 = buf[k32 * stride * 4:].view(np.int16).reshape(R - k32, stride)
+        for k, i in enumerate(order):
+            (x32 if k < k32 else x16)[k if k < k32 else k - k32, :arrs[i].size] = arrs[i]
+        xd = torch.from_numpy(buf).to(self.device, non_blocking=True)
+        rec_d = torch.from_numpy(np.ascontiguousarray(np.stack((ids[order], lengths[order])))).to(self.device, non_blocking=True)      # [2, R]
+        for a, b, dt, byte0 in ((0, k32, nat.ES_DTYPE_F32, 0), (k32, R, nat.ES_DTYPE_I16, k32 * stride * 4)):
+            if b > a:
+                sel = order[a:b]
+                self._resample_enqueue(table, ids[sel], lengths[sel], f_old[sel], counts[sel], xd.data_ptr() + byte0, dt, stride,
+                                       rec_d[0].data_ptr() + 8 * a, rec_d[1].data_ptr() + 8 * a, out.data_ptr() + 4 * a * ostride, ostride)
+        xd.record_stream(torch.cuda.current_stream(self.device))
+        if (order == np.arange(R)).all():
+            return out[:R], counts
+        inv = np.empty(R, np.int64)
+        inv[order] = np.arange(R)                                           # rows lie in launch order: back to input order, unwritten columns with them
+        return out[torch.from_numpy(inv).to(self.device)], counts
+
+    def open_monitor(self, n_streams: int, *, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), fs=None) -> MonitorTable:
+        """A table of n_streams fresh streams: windows of `window` samples (>= 2 * 1216), chunks of at most chunk_max samples, history
+        rows of `hist` columns (default and minimum window + 1216 + chunk_max), row j of every stream on band bands[j]; fs: the rate
+        the streams arrive at, one or one per stream (None: the engine's).  Everything is allocated here; monitor_step only enqueues."""
+        import torch
+        t = host_table(n_streams, window, chunk_max, hist, bands, fs=fs, fs_target=self.fs)
+        if t.rs is not None:
+            self._resampler_device(t.rs)
         S, dev = t.n, self.device
         t.band = torch.from_numpy(np.tile(t.bands, S)).to(dev)
         t.z = torch.zeros((4 * S, 8), dtype=torch.float64, device=dev)
@@ -177,10 +383,17 @@ class MonitorChain:
         t.corr_hist = torch.zeros((4 * S, t.hist), dtype=torch.float64, device=dev)
         return t
 
-    def add_monitor_streams(self, table: MonitorTable, n: int) -> np.ndarray:
-        """n more fresh streams: closed slots are used first, lowest first, then the table grows (an allocation).  -> their ids."""
+    def add_monitor_streams(self, table: MonitorTable, n: int, fs=None) -> np.ndarray:
+        """n more fresh streams: closed slots are used first, lowest first, then the table grows (an allocation).  fs: their rate, one or
+        one per stream (None: the engine's).  -> their ids."""
         import torch
         n, S = int(n), table.n
+        target = table.fs_target or int(self.fs)
+        rates = stream_rates(n, fs, target)                                # a rate that cannot be served: refused by name before anything changes
+        table.fs_target = target
+        if table.rs is None and (rates != target).any():
+            table.rs = resampler_host(np.full(S, target, np.int64), target)
+            table.rs.n_in_host[:] = table.n_host                            # at-rate streams: received = conditioned
         ids = np.concatenate((np.flatnonzero(~table.live)[:n], np.arange(S, S + n, dtype=np.int64)))[:n]
         grow = int(np.count_nonzero(ids >= S))
         if grow:
@@ -191,6 +404,16 @@ class MonitorChain:
             table.n_host, table.base_host = (np.concatenate((a, np.zeros(grow, np.int64))) for a in (table.n_host, table.base_host))
             table.live = np.concatenate((table.live, np.zeros(grow, bool)))
         table.live[ids] = True
+        if table.rs is not None:
+            rt = table.rs
+            reuse = ids < rt.n
+            resampler_extend(rt, rates[~reuse])                              # (ids beyond the table are ascending: rates[~reuse] in their order)
+            for s_, f in zip(ids[reuse].tolist(), rates[reuse].tolist()):
+                if f not in rt.offsets:
+                    resampler_extend(rt, [f])                               # designs the filter; the row it appended is dropped again
+                    rt.fs, rt.rate_host, rt.n_in_host = rt.fs[:-1], rt.rate_host[:-1], rt.n_in_host[:-1]
+                rt.fs[s_], rt.rate_host[s_], rt.n_in_host[s_] = f, rt.offsets[f], 0
+            self._resampler_device(rt)
         return ids
 
     def close_monitor_streams(self, table: MonitorTable, sid) -> None:
@@ -204,57 +427,90 @@ class MonitorChain:
             table.y_hist[rows] = 0.0
             table.corr_hist[rows] = 0.0
             table.pos[torch.from_numpy(ids).to(self.device)] = 0
+            if table.rs is not None:
+                table.rs.tail[torch.from_numpy(ids).to(self.device)] = 0.0
+                table.rs.nin[torch.from_numpy(ids).to(self.device)] = 0
         table.n_host[ids], table.base_host[ids], table.live[ids] = 0, 0, False
+        if table.rs is not None:
+            table.rs.n_in_host[ids] = 0
 
     def monitor_step(self, table: MonitorTable, sid, chunks) -> MonitorTick:
         """One tick: chunks[i] (1-D int16 or float32, 0 .. chunk_max samples) continues stream sid[i]; streams not named are not
         touched.  One upload of the chunks and one launch sequence -- band-pass continued from the stored delay elements (one launch
         per sample type present), the lags the chunks complete, threshold and peaks of every pushed row's window -- whatever the
         number of streams.  Per pushed (stream, band) row, thr / peaks / npeaks are bit for bit those of pick(xcorr(.)) on the
-        contiguous slice y[w0 : n] of the whole stream's band-pass output."""
+        contiguous slice y[w0 : n] of the whole stream's band-pass output.  A stream at another rate is first conditioned
+        on the device, in the same upload (es_resample_stream_batch, one launch per sample type present among them); the samples its
+        chunk finalizes (at most chunk_max, possibly none) are its chunk in all of the above, a third band-pass group in float32."""
         import torch
-        ids = monitor_ids(table, sid)
-        arrs = monitor_chunks(chunks, table.chunk_max)
+        ids, chunks = monitor_ids(table, sid), list(chunks)
+        other_s = None if table.rs is None else table.rs.rate_host[:, 0] != table.rs.rate_host[:, 1]
+        arrs = monitor_chunks(chunks, table.chunk_max, None if other_s is None or ids.size != len(chunks) else ~other_s[ids])
         if ids.size != len(arrs):
             raise ValueError("one stream id per chunk is required")
         R = ids.size
-        lengths = np.array([a.size for a in arrs], np.int64)
+        raw = np.array([a.size for a in arrs], np.int64)
+        lengths, other, f_old = monitor_conditioned(table, ids, arrs)      # at fs_target: what the band-pass appends
         lay = monitor_layout(table.n_host[ids], table.base_host[ids], lengths, table.window, table.hist)
         q_rows = (4 * ids[:, None] + np.arange(4)).reshape(-1)
         offset, length = np.repeat(lay.w0 - lay.base, 4), np.repeat(lay.n - lay.w0, 4)
         thr, peaks, npeaks, _ = self._peak_out(4 * R, flags=False)
         if R == 0:
             return MonitorTick(table.y_hist, thr, peaks, npeaks, ids, q_rows, offset, length)
-        # float32 chunks first, then int16: ONE host buffer, one upload, a launch per sample type over its slice of the records
-        order = np.argsort([a.dtype == np.int16 for a in arrs], kind="stable")
-        k32 = int(sum(a.dtype != np.int16 for a in arrs))
-        stride = max(4, (int(lengths.max()) + 3) // 4 * 4)
+        # ONE host buffer, one upload: float32 chunks first (streams at the table's rate, then the others), then int16 likewise; the
+        # records in launch order: at-rate float32, at-rate int16, other-rate float32, other-rate int16
+        i16 = np.array([a.dtype == np.int16 for a in arrs], bool)
+        order = np.argsort(2 * other + i16, kind="stable")
+        nA, nB, nC = (int(np.count_nonzero(m)) for m in (~other & ~i16, ~other & i16, other & ~i16))
+        nD, k32 = R - nA - nB - nC, nA + nC
+        stride = max(4, (int(raw.max()) + 3) // 4 * 4)
         buf = np.zeros(k32 * stride * 4 + (R - k32) * stride * 2, np.uint8)
         x32 = buf[:k32 * stride * 4].view(np.float32).reshape(k32, stride)
         x16 = buf[k32 * stride * 4:].view(np.int16).reshape(R - k32, stride)
-        for k, i in enumerate(order):
-            (x32 if k < k32 else x16)[k if k < k32 else k - k32, :arrs[i].size] = arrs[i]
+        rows32 = np.concatenate((order[:nA], order[nA + nB: nA + nB + nC]))                                         # records of x32's rows
+        rows16 = np.concatenate((order[nA: nA + nB], order[nA + nB + nC:]))
+        for k, i in enumerate(rows32):
+            x32[k, :arrs[i].size] = arrs[i]
+        for k, i in enumerate(rows16):
+            x16[k, :arrs[i].size] = arrs[i]
         xd = torch.from_numpy(buf).to(self.device, non_blocking=True)
         rec = np.ascontiguousarray(np.stack((ids, lengths, lay.col, lay.move, lay.base), axis=1)[order])          # [R, 5], as the C ABI checks it
-        rec_d = torch.from_numpy(np.ascontiguousarray(rec.T)).to(self.device, non_blocking=True)                    # [5, R]
+        rec_d = torch.from_numpy(np.ascontiguousarray(np.concatenate((rec.T, raw[order][None])))).to(self.device, non_blocking=True)    # [6, R]: + the chunks' own lengths
         pk = np.stack((q_rows, offset, length - (PRE_L - 1))).astype(np.int32)                                      # [3, 4 R], input order
         pk_d = torch.from_numpy(pk).to(self.device, non_blocking=True)
         S, H, st = table.n, table.hist, self._stream()
-        for a, b, dt, byte0 in ((0, k32, nat.ES_DTYPE_F32, 0), (k32, R, nat.ES_DTYPE_I16, k32 * stride * 4)):
+        byte16 = k32 * stride * 4
+        nE, ostride, cond = nC + nD, 4, None
+        if nE:                                                              # condition the other-rate chunks: row e of `cond` = record nA + nB + e
+            ostride = max(4, (int(lengths[other].max()) + 3) // 4 * 4)
+            cond = torch.empty((nE, ostride), dtype=torch.float32, device=self.device)
+            for a, b, dt, x_ptr in ((nA + nB, nA + nB + nC, nat.ES_DTYPE_F32, xd.data_ptr() + 4 * nA * stride),
+                                    (nA + nB + nC, R, nat.ES_DTYPE_I16, xd.data_ptr() + byte16 + 2 * nB * stride)):
+                if b > a:
+                    sel = order[a:b]
+                    self._resample_enqueue(table.rs, ids[sel], raw[sel], f_old[sel], lengths[sel], x_ptr, dt, stride, rec_d[0].data_ptr() + 8 * a,
+                                           rec_d[5].data_ptr() + 8 * a, cond.data_ptr() + 4 * (a - nA - nB) * ostride, ostride)
+        for a, b, dt, x_ptr, n_stride in ((0, nA, nat.ES_DTYPE_F32, xd.data_ptr(), stride), (nA, nA + nB, nat.ES_DTYPE_I16, xd.data_ptr() + byte16, stride),
+                                          (nA + nB, R, nat.ES_DTYPE_F32, cond.data_ptr() if nE else 0, ostride)):
             if b > a:
                 cols = [rec_d[w].data_ptr() + 8 * a for w in range(5)]
-                nat.check(self._ctx, self._lib.es_bpf_stream_batch(self._ctx, xd.data_ptr() + byte0, dt, b - a, stride, *cols, rec[a:].ctypes.data, S, H,
+                nat.check(self._ctx, self._lib.es_bpf_stream_batch(self._ctx, x_ptr, dt, b - a, n_stride, *cols, rec[a:].ctypes.data, S, H,
                                                                    table.band.data_ptr(), table.z.data_ptr(), table.pos.data_ptr(),
                                                                    table.y_hist.data_ptr(), table.corr_hist.data_ptr(), st), "es_bpf_stream_batch")
-        nat.check(self._ctx, self._lib.es_xcorr_stream_batch(self._ctx, table.y_hist.data_ptr(), R, stride, rec_d[0].data_ptr(), rec_d[1].data_ptr(),
-                                                             rec_d[2].data_ptr(), rec.ctypes.data, S, H, table.band.data_ptr(),
+        nat.check(self._ctx, self._lib.es_xcorr_stream_batch(self._ctx, table.y_hist.data_ptr(), R, max(stride, ostride), rec_d[0].data_ptr(),
+                                                             rec_d[1].data_ptr(), rec_d[2].data_ptr(), rec.ctypes.data, S, H, table.band.data_ptr(),
                                                              table.corr_hist.data_ptr(), st), "es_xcorr_stream_batch")
         nat.check(self._ctx, self._lib.es_pick_at_batch(self._ctx, table.corr_hist.data_ptr(), 4 * S, H, 4 * R, pk_d[0].data_ptr(), pk_d[1].data_ptr(),
                                                         pk_d[2].data_ptr(), thr.data_ptr(), peaks.data_ptr(), npeaks.data_ptr(), st), "es_pick_at_batch")
         xd.record_stream(torch.cuda.current_stream(self.device))
+        if cond is not None:
+            cond.record_stream(torch.cuda.current_stream(self.device))
         table.n_host[ids], table.base_host[ids] = lay.n, lay.base
+        if table.rs is not None:
+            table.rs.n_in_host[ids[~other]] += raw[~other]                  # (the other-rate streams' were moved on by _resample_enqueue)
         return MonitorTick(table.y_hist, thr, peaks, npeaks, ids, q_rows, offset, length)
 
 
-__all__ = ["SEG", "MIN_WINDOW", "MonitorChain", "MonitorLayout", "MonitorTable", "MonitorTick", "check_geometry", "history_columns", "host_table",
-           "monitor_chunks", "monitor_ids", "monitor_layout", "window_start"]
+__all__ = ["SEG", "MIN_WINDOW", "MonitorChain", "MonitorLayout", "MonitorTable", "MonitorTick", "ResamplerTable", "check_geometry",
+           "history_columns", "host_table", "monitor_chunks", "monitor_conditioned", "monitor_ids", "monitor_layout", "resample_counts",
+           "resampler_host", "stream_rates", "window_start"]

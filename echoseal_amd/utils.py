@@ -162,6 +162,74 @@ def resample_limits(n_in: int, fs_orig: int, fs_target: int) -> str | None:
 
 
 @dataclass
+class StreamResamplePlan:
+    """What a live stream at another rate is conditioned with (stream_resample_plan): the reduced pair, resample_geometry's first kept
+    output y0 (a property of the pair alone), the canonical taps per phase hpp = ceil((2 half_len + 1 + n_pre_pad) / up) -- no post padding,
+    which only appends zero taps -- and the float32 polyphase table in resample_plan's transposed, flipped layout [up * hpp].  Equal
+    rates: up = down = 1, y0 = hpp = 0 and an empty table (the stream is copied)."""
+    up: int
+    down: int
+    y0: int
+    hpp: int
+    h_tf: np.ndarray
+
+
+STREAM_TAPS_MAX = 256                                                       # ES_RSTREAM_TAIL: a stream's tail row holds the 255 samples before its chunk
+
+
+def stream_geometry(fs_in: int, fs_target: int):
+    """The integers of stream_resample_plan without its filter: -> (up, down, y0, hpp, n_pre_pad) of the reduced pair; equal rates:
+    (1, 1, 0, 0, 0).  Refused with a ValueError that names the rate: what resample_limits refuses, and a pair that needs more than 256
+    taps per phase (the tail row serves 255 samples before the chunk; 384 kHz -> 48 kHz needs 169)."""
+    fs_in, fs_target = int(fs_in), int(fs_target)
+    if fs_in < 1 or fs_target < 1:
+        raise ValueError(f"a stream at {fs_in} Hz -> {fs_target} Hz: rates are positive")
+    why = resample_limits(0, fs_in, fs_target)
+    if why is not None:
+        raise ValueError(f"a stream at {fs_in} Hz -> {fs_target} Hz is outside what the device conditions: {why}")
+    g = math.gcd(fs_in, fs_target)
+    up, down = fs_target // g, fs_in // g
+    if up == down:
+        return 1, 1, 0, 0, 0
+    half_len = 10 * max(up, down)
+    n_pre_pad = down - half_len % down
+    hpp = -(-(2 * half_len + 1 + n_pre_pad) // up)
+    if hpp > STREAM_TAPS_MAX:
+        raise ValueError(f"a stream at {fs_in} Hz -> {fs_target} Hz needs {hpp} taps per phase: more than the {STREAM_TAPS_MAX} a live "
+                         "stream's tail serves (condition such a feed before it is pushed)")
+    return up, down, (half_len + n_pre_pad) // down, hpp, n_pre_pad
+
+
+def stream_resample_plan(fs_in: int, fs_target: int) -> StreamResamplePlan:
+    """The plan that conditions a live stream at fs_in to fs_target chunk by chunk; refusals are stream_geometry's."""
+    from scipy.signal import firwin
+    up, down, y0, hpp, n_pre_pad = stream_geometry(fs_in, fs_target)
+    if up == down:
+        return StreamResamplePlan(1, 1, 0, 0, np.zeros(0, np.float32))
+    half_len = 10 * max(up, down)
+    h = firwin(2 * half_len + 1, 1.0 / max(up, down), window=("kaiser", 5.0)).astype(np.float32)        # as resample_plan for float32
+    h *= up
+    hf = np.zeros(up * hpp, np.float32)
+    hf[n_pre_pad: n_pre_pad + h.size] = h
+    return StreamResamplePlan(up, down, y0, hpp, np.ascontiguousarray(hf.reshape(-1, up).T[:, ::-1].ravel()))
+
+
+def finalized(n, up: int, down: int, y0: int):
+    """F(n) = max(0, (n up - 1) // down - y0 + 1): how many leading outputs of resample_poly(X[:n], up, down) no later sample changes --
+    output k is final once its newest input sample, ((y0 + k) down) // up, has arrived.  n: a scalar (-> int) or an array (-> int64;
+    n * up must stay below 2^63)."""
+    up, down, y0 = int(up), int(down), int(y0)
+    if np.ndim(n) == 0:
+        return max(0, (int(n) * up - 1) // down - y0 + 1)
+    return np.maximum((np.asarray(n, dtype=np.int64) * up - 1) // down - y0 + 1, 0)
+
+
+def stream_position_limit(up: int) -> int:
+    """The most samples a stream with this `up` may have received: n * up stays below 2^62 (the kernels' 64-bit arithmetic)."""
+    return ((1 << 62) - 1) // int(up)
+
+
+@dataclass
 class ConditionPlan:
     """Host side of es_resample_ragged_batch for clips of one sample type: desc int64 [R, 8] = (offset of the clip in the flat sample
     pool, n_in, up, down, offset of its filter in `filters`, taps per phase, first kept output, n_out) -- words 2, 3 and 5..7 and the

@@ -341,6 +341,39 @@ int es_resample_ragged_batch(es_ctx* ctx, const void* pool_dev, int dtype, int64
                              const int64_t* desc_dev, int64_t R, int rep, float* out_dev, int64_t out_stride, int64_t max_out,
                              void* stream);
 
+/* The same conditioning for live streams that arrive chunk by chunk at rates of their own: what a monitor runs in front of
+ * es_bpf_stream_batch.  Continues resample_to (rtwm/utils.py:58-66 = scipy.signal.resample_poly) across calls.
+ * Definition.  Stream s has a rate pair reduced to (up, down), fixed when its slot is opened, and has received n samples X (float32, or
+ * int16 read as x / 32768).  With half_len = 10 max(up, down), n_pre_pad = down - half_len % down and y0 = (half_len + n_pre_pad) / down,
+ *   F(n) = max(0, (n up - 1) / down - y0 + 1),  F(0) = 0
+ * is the number of leading outputs of resample_poly(X[:n], up, down) that no later sample changes: output k is final once its newest input
+ * sample, ((y0 + k) down) / up, has arrived.  The stream's conditioned stream is r = resample_poly(X, up, down)[:F(n)], float32; a call
+ * that takes a stream from n_old to n_old + len samples writes r[F(n_old) : F(n_old + len)], bit for bit (accumulator from +0, products in
+ * ascending input index, multiply and add rounded separately), possibly no sample at all.  Finite samples only: an Inf or NaN that meets
+ * a zero tap makes SciPy's own value depend on the clip's length.
+ *   rate_dev [S][ES_RSTREAM_RATE_WORDS] int64   (up, down, offset of the filter in the filter pool, taps per phase hpp, y0); up == down:
+ *                                               a stream at the target rate, copied
+ *   filt_dev [filt_n] float32                   polyphase tables in utils.resample_plan's transposed, flipped layout, without post padding:
+ *                                               hpp = ceil((2 half_len + 1 + n_pre_pad) / up) <= ES_RSTREAM_TAIL
+ *   tail_dev [S][ES_RSTREAM_TAIL] float32       the last samples received, newest last (+0.0 in a fresh slot); the kernel reads the last 255
+ *   nin_dev  [S] int64                          samples received (0 in a fresh slot)
+ * Record r = the chunk x_dev[r][0 : len[r]] (rows of n_stride, ES_DTYPE_F32 or ES_DTYPE_I16) of stream sid[r]; its outputs go to
+ * out_dev[r][0 : count] (float32, rows of out_stride), the rest of the row is not written.  Then, by a second kernel behind the first,
+ * tail := the last of (tail ++ chunk as float32) and nin += len.  rec_host [R][ES_RSTREAM_REC_WORDS] int64 = (sid, len, n_old, F(n_old),
+ * count, up, down, y0) as the host laid the tick out, checked before anything is enqueued: ES_EINVAL for a sid outside [0, S) or named
+ * twice, len outside 0 .. n_stride, up or down outside [1, ES_RESAMPLE_RATE_MAX], a position with (n_old + len) up >= 2^62, F(n_old) or
+ * count that disagree with the rate words, a count above out_stride; nothing is written then.  The device arrays must hold the same; what
+ * they hold instead is clamped (a sid outside the table or rate words no filter in the pool fits: no output; len to the chunk row, the
+ * count to the output row; no read or write leaves x, the table or out).  The kernels take n_old from nin_dev, so a captured call
+ * continues its streams on every replay.  Needs no tables, only enqueues (capturable); R == 0 launches nothing. */
+#define ES_RSTREAM_REC_WORDS  8
+#define ES_RSTREAM_RATE_WORDS 5
+#define ES_RSTREAM_TAIL       256
+#define ES_RSTREAM_Y0_MAX     (1 << 24)
+int es_resample_stream_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t R, int64_t n_stride, const int64_t* sid_dev,
+                             const int64_t* len_dev, const int64_t* rec_host, int64_t S, const int64_t* rate_dev, const float* filt_dev,
+                             int64_t filt_n, float* tail_dev, int64_t* nin_dev, float* out_dev, int64_t out_stride, void* stream);
+
 /* Diagnostic: out[i] = log1p(exp(t[i])) for t[i] <= 0 exactly as the list decoder's f / penalty evaluate it on the device
  * (np.logaddexp / np.log1p(np.exp(.)) of rtwm/fastpolar.py:18-23, 32-40 through the C library's exp and log1p) -- lets a
  * test compare the device arithmetic with the host C library bit for bit.  t_dev, out_dev float64 [n].                   */

@@ -10,6 +10,13 @@ Medians with min and max; the verdicts of both are compared.  The sync stage alo
 timed too: that is where the two paths differ, the candidate walk behind it is the same code.
 
     python tools/monitor_tick.py --ticks 10 --out profiles/monitor_tick.json --tag <commit>
+
+--fs RATE: the streams arrive at RATE instead.  The same marked streams are converted to RATE on the host once; the monitor is
+opened with fs=RATE and pushed chunk_s of them per tick, the yardstick is a second monitor at 48 kHz on the same engine that is pushed the
+pre-conditioned chunks r[F(n_old) : F(n_new)] -- the path that existed before, with the resampling done elsewhere.  LiveMonitor.push and
+monitor_step of both are timed as above and the verdicts compared.
+
+    python tools/monitor_tick.py --fs 44100 --ticks 10 --out profiles/monitor_tick_rates.json --tag <commit>
 """
 import argparse
 import json
@@ -43,6 +50,61 @@ def stats(ev, wall):
     return {"median_ms": statistics.median(ev), "min_ms": min(ev), "max_ms": max(ev), "wall_median_ms": statistics.median(wall), "ticks": len(ev)}
 
 
+def main_rates(args) -> None:
+    """Streams at args.fs against an at-rate monitor fed the conditioned chunks."""
+    from scipy.signal import resample_poly
+    from echoseal_amd.utils import finalized, stream_resample_plan
+    eng = RxEngine(0, fs=FS)
+    stream = torch.cuda.current_stream(eng.device)
+    pl = stream_resample_plan(args.fs, FS)
+    S, chunk, chunk_t = args.streams, int(args.chunk_s * args.fs), int(args.chunk_s * FS)
+    fill = -(-int(args.window_s * FS) // chunk_t) + 1
+    ticks = fill + 2 * (args.warmup + args.ticks)
+    rng = np.random.default_rng(1)
+    host = (0.05 * rng.standard_normal((S, ticks * chunk_t + 4800))).astype(np.float32)
+    marked = eng.embed(KEY, host, seed=7).audio.cpu().numpy()
+    xs = [resample_poly(x.astype(np.float64), pl.down, pl.up).astype(np.float32)[:ticks * chunk] for x in marked]      # at args.fs
+    rs = [resample_poly(x, pl.up, pl.down) for x in xs]                                                                # what the device finalizes
+    F = lambda n: finalized(n, pl.up, pl.down, pl.y0)
+    cmax = F(chunk) + pl.y0 + 2
+    det = WatermarkDetector(KEY, fs_target=FS, list_size=args.list_size, engine=eng)
+    mon = det.open_streams(S, fs=args.fs, window_s=args.window_s, chunk_max=cmax)
+    ref_det = WatermarkDetector(KEY, fs_target=FS, list_size=args.list_size, engine=eng)
+    ref = ref_det.open_streams(S, window_s=args.window_s, chunk_max=cmax)
+    at = 0
+    raw = lambda: [x[at: at + chunk] for x in xs]
+    cond = lambda: [r[F(at): F(at + chunk)] for r in rs]
+    for _ in range(fill):
+        mon.push(raw()); ref.push(cond())
+        at += chunk
+    ev = {k: ([], []) for k in ("push", "push_at_rate", "step", "step_at_rate")}
+    same = True
+    for t in range(args.warmup + args.ticks):
+        got, e, w = timed(lambda: mon.push(raw()), stream)
+        want, e2, w2 = timed(lambda: ref.push(cond()), stream)
+        at += chunk
+        same = same and got == want
+        if t >= args.warmup:
+            ev["push"][0].append(e); ev["push"][1].append(w); ev["push_at_rate"][0].append(e2); ev["push_at_rate"][1].append(w2)
+    ids = np.arange(S)
+    for t in range(args.warmup + args.ticks):
+        a, e, w = timed(lambda: eng.monitor_step(mon.table, ids, raw()), stream)
+        b, e2, w2 = timed(lambda: eng.monitor_step(ref.table, ids, cond()), stream)
+        at += chunk
+        same = same and torch.equal(a.peaks, b.peaks) and torch.equal(a.npeaks, b.npeaks) and torch.equal(a.thr.view(torch.int64), b.thr.view(torch.int64))
+        if t >= args.warmup:
+            ev["step"][0].append(e); ev["step"][1].append(w); ev["step_at_rate"][0].append(e2); ev["step_at_rate"][1].append(w2)
+    row = {"streams": S, "fs": args.fs, "window_s": args.window_s, "chunk_s": args.chunk_s, "list_size": args.list_size,
+           "monitor_push": stats(*ev["push"]), "monitor_push_at_rate": stats(*ev["push_at_rate"]), "monitor_step": stats(*ev["step"]),
+           "monitor_step_at_rate": stats(*ev["step_at_rate"]), "same_results": bool(same), "device": torch.cuda.get_device_name(eng.device),
+           "tag": args.tag}
+    print(json.dumps(row), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(row) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=64)
@@ -53,7 +115,10 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--fs", type=int, default=None, help="rate the streams arrive at (default: 48 000, the monitor's own)")
     args = ap.parse_args()
+    if args.fs is not None and args.fs != FS:
+        return main_rates(args)
     eng = RxEngine(0, fs=FS)
     stream = torch.cuda.current_stream(eng.device)
     S, chunk, window = args.streams, int(args.chunk_s * FS), int(args.window_s * FS)
