@@ -37,6 +37,7 @@ ES_RESAMPLE_WIN_MAX, ES_RESAMPLE_FILT_MAX, ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TAB
 ES_STREAM_REC_WORDS = 5                                # es_mix_stream_batch / es_stream_commit_batch: int64 words per record of rec_host
 ES_MONITOR_REC_WORDS = 5                               # es_bpf_stream_batch / es_xcorr_stream_batch: (sid, len, col, move, base)
 ES_RSTREAM_REC_WORDS, ES_RSTREAM_RATE_WORDS, ES_RSTREAM_TAIL = 8, 5, 256     # es_resample_stream_batch: host record, rate words, tail row
+ES_MEMO_EMPTY = 0xFFFFFFFFFFFFFFFF                     # both words of an empty memo entry (es_memo_probe_batch / es_memo_insert_batch)
 ES_XC_SEG = 1216                                       # lags per segment of the correlation kernel (64 lanes x 19): a monitor's window grid
 
 # name -> (restype, argtypes); kept next to the header so a test can check both agree
@@ -116,6 +117,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "es_plan_ragged_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                      c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "es_memo_probe_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "es_memo_insert_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -1012,4 +1012,36 @@ int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* n
                                  N, C, cand_slot_dev, cand_ctr_dev, count_dev, looked_dev, (hipStream_t)stream);
 }
 
+// what both memo calls refuse: a table that is not a power of two of entries, a count the uint32 claim words cannot index
+static int memo_refusal(es_ctx* ctx, const char* who, int64_t slots, int64_t n)
+{
+    const char* why = (slots < 1 || (slots & (slots - 1)) != 0) ? ": slots must be a power of two, at least 1"
+                      : (n < 0 || n >= (((int64_t)1 << 32) - 1)) ? ": n must be in [0, 2^32 - 1)" : nullptr;
+    if (!why) return ES_OK;
+    ctx->err = std::string(who) + why;
+    return ES_EINVAL;
+}
+
+int es_memo_probe_batch(es_ctx* ctx, const uint64_t* table_dev, int64_t slots, const uint64_t* k0_dev, const uint64_t* k1_dev, int64_t n,
+                        uint8_t* hit_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (memo_refusal(ctx, "es_memo_probe_batch", slots, n) != ES_OK) return ES_EINVAL;
+    if (n == 0) return ES_OK;
+    if (!table_dev || !k0_dev || !k1_dev || !hit_dev) return fail(ctx, ES_EINVAL, "es_memo_probe_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_memo_probe(ctx, table_dev, slots, k0_dev, k1_dev, n, hit_dev, (hipStream_t)stream);
+}
+
+int es_memo_insert_batch(es_ctx* ctx, uint64_t* table_dev, uint32_t* claim_dev, int64_t slots, const uint64_t* k0_dev, const uint64_t* k1_dev,
+                         int64_t n, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (memo_refusal(ctx, "es_memo_insert_batch", slots, n) != ES_OK) return ES_EINVAL;
+    if (n == 0) return ES_OK;
+    if (!table_dev || !claim_dev || !k0_dev || !k1_dev) return fail(ctx, ES_EINVAL, "es_memo_insert_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_memo_insert(ctx, table_dev, claim_dev, slots, k0_dev, k1_dev, n, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -270,5 +270,18 @@ int es_launch_plan_ragged(es_ctx* ctx, const int32_t* peaks, const int32_t* npea
                           int64_t N, int C, uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
+/* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the
+ * splitmix64 finaliser over k0 * 0x9E3779B97F4A7C15 + k1, as include/echoseal_hip.h states it (host twin: echoseal_amd/memo.py slot) */
+__host__ __device__ static inline unsigned long long es_memo_mix(unsigned long long k0, unsigned long long k1)
+{
+    unsigned long long z = k0 * 0x9E3779B97F4A7C15ull + k1;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+int es_launch_memo_probe(es_ctx* ctx, const uint64_t* table, int64_t slots, const uint64_t* k0, const uint64_t* k1, int64_t n, uint8_t* hit,
+                         hipStream_t st);
+int es_launch_memo_insert(es_ctx* ctx, uint64_t* table, uint32_t* claim, int64_t slots, const uint64_t* k0, const uint64_t* k1, int64_t n,
+                          hipStream_t st);
 
 #endif

@@ -23,6 +23,7 @@ import numpy as np
 
 from ._native import NativeError
 from .crypto import SecureChannel
+from .monitor import LiveTable
 from .polar_fast import N_DEFAULT
 from .primitives import InvalidTag
 from .scan import FRAME_LEN, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, Launch, cut_launches, ragged_buckets, sync_launch  # noqa: F401 (re-exported)
@@ -493,7 +494,7 @@ class WatermarkDetector:
         return None, None
 
 
-class LiveMonitor:
+class LiveMonitor(LiveTable):
     """The monitored streams of a WatermarkDetector (WatermarkDetector.open_streams); stream ids are the slots of `table`.
 
     Stream s behaves as a private WatermarkDetector(key, fs_target, list_size) that is called once per push, in push order, on the
@@ -508,8 +509,9 @@ class LiveMonitor:
         self._order = detector._band_order()
         self._walkers: dict[int, WatermarkDetector] = {}
 
-    def __len__(self) -> int:
-        return int(np.count_nonzero(self.table.live))
+    @property
+    def fs_target(self) -> int:
+        return self._det.fs_target
 
     def _walker(self, s: int) -> WatermarkDetector:
         w = self._walkers.get(s)
@@ -524,23 +526,9 @@ class LiveMonitor:
         check, not a conversion: every named stream must have been opened at that rate.  Raises ValueError before any GPU work for
         that, a chunk that is not 1-D, longer than chunk_max or (at another rate) finalizing more than chunk_max samples, a stream
         named twice, outside the table or closed."""
-        from .monitor import monitor_chunks, monitor_conditioned, monitor_ids
+        from .monitor import push_arguments
         from .scan import SyncScan
-        tab, target, chunks = self.table, self._det.fs_target, list(chunks)
-        if fs is not None and tab.rs is None and int(fs) != target:
-            raise ValueError(f"chunks at {fs} Hz: this monitor's streams arrive at fs_target = {target} Hz (open a stream with fs={fs} "
-                             "to have it conditioned on the device; push(fs=) only checks the rate)")
-        if streams is None:
-            streams = np.flatnonzero(tab.live)
-        ids = monitor_ids(tab, streams)
-        if fs is not None and tab.rs is not None and (tab.rs.fs[ids] != int(fs)).any():
-            bad = int(ids[tab.rs.fs[ids] != int(fs)][0])
-            raise ValueError(f"chunks at {fs} Hz: stream {bad} was opened at {int(tab.rs.fs[bad])} Hz (fs_target = {target} Hz); push(fs=) "
-                             "only checks the rate, a stream's rate is fixed when it is opened")
-        if len(chunks) != ids.size:
-            raise ValueError("one chunk per stream is required")
-        arrs = monitor_chunks(chunks, tab.chunk_max, None if tab.rs is None else tab.rs.fs[ids] == target)
-        monitor_conditioned(tab, ids, arrs)                                 # a chunk that finalizes more than chunk_max: refused here
+        ids, arrs, _ = push_arguments(self.table, self.fs_target, chunks, streams, fs)
         if not ids.size:
             return []
         det = self._det
@@ -550,25 +538,6 @@ class LiveMonitor:
         for w in walkers:
             w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
         return det._verify_scans(scans, [list(range(len(scans)))], self._order, walkers)
-
-    def position(self, stream: int) -> int:
-        """Samples at fs_target stream `stream` has been verified over since it was opened: the samples received, for a stream at
-        another rate the conditioned samples that are final."""
-        return int(self.table.n_host[int(stream)])
-
-    def received(self, stream: int) -> int:
-        """Samples stream `stream` has received since it was opened, at its own rate."""
-        return int(self.table.n_in_host[int(stream)])
-
-    def rate(self, stream: int) -> int:
-        """The rate stream `stream` was opened at."""
-        return int(self.table.fs[int(stream)]) or int(self._det.fs_target)
-
-    def window(self, stream: int) -> tuple[int, int]:
-        """(w0, n): the samples of the stream, counted from its opening, that its last push verified."""
-        from .monitor import window_start
-        n = self.position(stream)
-        return int(window_start(n, self.table.window)), n
 
     def session_nonce(self, stream: int) -> bytes | None:
         """The session nonce stream `stream` is locked to (None: nothing accepted yet)."""

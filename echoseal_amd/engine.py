@@ -138,6 +138,15 @@ class PlanResult:
     looked: torch.Tensor       # [N * rows] int32: fitting peaks looked at
 
 
+@dataclass
+class Memo:
+    """A verdict memo on the device (RxEngine.open_memo; layout and rules: include/echoseal_hip.h, host model: memo.MemoModel).  The
+    uint64 words are held in int64 tensors, bit for bit."""
+    table: torch.Tensor        # [slots, 2] int64: the records themselves, -1 / -1 (all ones) where empty
+    claim: torch.Tensor        # [slots] int32: es_memo_insert_batch's claim words, -1 (0xFFFFFFFF) between calls
+    slots: int
+
+
 class RxEngine(TxChain, MonitorChain):
     def __init__(self, device: int | torch.device = 0, *, list_size_max: int = 32, fs: int = 48_000, code_k: int = 448):
         """code_k: information positions of the polar code (data bits + CRC-8).  448 is the reference's own code (rtwm/polar_fast.py:8-9);
@@ -661,6 +670,36 @@ class RxEngine(TxChain, MonitorChain):
                                                      _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(res.slot), _ptr(res.ctr),
                                                      _ptr(res.count), _ptr(res.looked), self._stream()), "es_plan_batch")
         return res
+
+    # ------------------------------------------------------------------ the verdict memo (es_memo.hip)
+    def open_memo(self, slots: int) -> Memo:
+        """An empty memo of `slots` entries (a power of two): 16 bytes of table and 4 of claim word per entry."""
+        from .memo import check_slots
+        slots = check_slots(slots)
+        return Memo(torch.full((slots, 2), -1, dtype=torch.int64, device=self.device), torch.full((slots,), -1, dtype=torch.int32, device=self.device), slots)
+
+    def _memo_words(self, k0, k1):
+        """Packed records as int64 device tensors: uint64 host arrays (memo.pack) are reinterpreted, device tensors are taken as they are."""
+        w = [t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.uint64).view(np.int64)) for t in (k0, k1)]
+        w = [self._dev(t, torch.int64).reshape(-1) for t in w]
+        if w[0].numel() != w[1].numel():
+            raise ValueError("memo records: one k0 and one k1 word per record")
+        return w[0], w[1], w[0].numel()
+
+    def memo_probe(self, memo: Memo, k0, k1) -> torch.Tensor:
+        """-> uint8 [n]: record i is in the memo (es_memo_probe_batch)."""
+        k0, k1, n = self._memo_words(k0, k1)
+        hit = torch.empty(n, dtype=torch.uint8, device=self.device)
+        nat.check(self._ctx, self._lib.es_memo_probe_batch(self._ctx, _ptr(memo.table), memo.slots, _ptr(k0), _ptr(k1), n, _ptr(hit), self._stream()),
+                  "es_memo_probe_batch")
+        return hit
+
+    def memo_insert(self, memo: Memo, k0, k1) -> None:
+        """Store the records of one call (es_memo_insert_batch): per entry the record of the lowest index wins, a record whose k0 is all
+        ones is ignored."""
+        k0, k1, n = self._memo_words(k0, k1)
+        nat.check(self._ctx, self._lib.es_memo_insert_batch(self._ctx, _ptr(memo.table), _ptr(memo.claim), memo.slots, _ptr(k0), _ptr(k1), n,
+                                                            self._stream()), "es_memo_insert_batch")
 
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)
     def _ctr_dev(self, ctrs) -> torch.Tensor:

@@ -15,6 +15,10 @@ and everything keyed runs for all keys at once from a key ring on the device:
 
 Each key starts with session_nonce = None, so a key matches iff some candidate of its walk validates (AEAD opens, "ESAL", counter
 equal), and the first such candidate in the reference's walk order is the reported one.  Nonce state across calls is out of scope.
+
+Live streams (WatermarkIdentifier.open_streams -> LiveIdentifier): the same walk over a monitor tick's scan instead of a
+sync call's, frames read in place in the monitor's history, and a memo on the device (memo.py, es_memo_probe_batch /
+es_memo_insert_batch) of candidates already known to fail, so that a push decodes only what no earlier push has decoded.
 """
 from __future__ import annotations
 
@@ -22,8 +26,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import memo
 from ._native import ES_MAX_PEAKS, ES_MAX_TRIES, NativeError
 from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
+from .monitor import LiveTable
 from .scan import cut_launches, sync_launch
 from .utils import BAND_PLAN
 
@@ -76,6 +82,19 @@ def plan_reference(peaks, npeaks: int, M: int, band: int, hdr_ok, hdr_lo16, hop)
     return plan, looked
 
 
+@dataclass
+class _LiveWalk:
+    """What WatermarkIdentifier._walk needs of a monitor tick beyond its SyncScan; one entry per scan row where not said otherwise."""
+    rows: np.ndarray            # int64 history row 4 s + j
+    offset: np.ndarray          # int64 column of the window's first sample
+    w0: np.ndarray              # int64 absolute index of the window's first sample
+    epoch: np.ndarray           # int64 epoch of the row's stream slot
+    hop: object                 # uint8 [N, C] device: the hop table of the window
+    memo: object                # engine.Memo, or None: every candidate is decoded
+    stats: dict                 # planned / decoded / skipped candidates, summed over the walk
+    trace: bool                 # record traces (the live identifier's own switch, not its WatermarkIdentifier's)
+
+
 class WatermarkIdentifier:
     """identify(audio, fs_in) -> one entry per key: a KeyMatch, or None where WatermarkDetector(key).verify would return False.
     With `.trace = True` a call returns (matches, traces), traces[i] = (the `_trace`, the `_hdr_trace`) a fresh detector of key i
@@ -119,17 +138,51 @@ class WatermarkIdentifier:
                     self._group(part, [out[i] for i in part.idx], [traces[i] for i in part.idx])
         return (out, traces) if self.trace else out
 
+    def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
+                     memo_slots: int | None = None) -> "LiveIdentifier":
+        """A monitor of n live streams that says, per push and stream, which of this identifier's keys marks the stream's last window_s
+        seconds (LiveIdentifier.push).  fs, window_s, chunk_max and trace are those of WatermarkDetector.open_streams.  memo_slots:
+        entries of the verdict memo, a power of two; 0: no memo, every push decodes its whole window; None:
+        memo.default_slots -- the next power of two above 2 x keys x 4 n x 400, between 2^10 and 2^25 entries of 20 bytes each (16 keys
+        and 64 streams: 2^22 entries, 80 MiB; never more than 640 MiB)."""
+        from .monitor import check_geometry, stream_rates
+        window = int(round(float(window_s) * self.fs_target))
+        chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
+        check_geometry(window, chunk_max)                                   # refused before any engine exists
+        stream_rates(int(n), fs, self.fs_target)                             # ... and so is a rate that cannot be served
+        slots = memo.default_slots(len(self.keys), int(n)) if memo_slots is None else int(memo_slots)
+        LiveIdentifier.check_memo(slots, len(self.keys), window)            # ... and a window or key list the memo's records cannot name
+        return LiveIdentifier(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=tuple(range(NB)), fs=fs),
+                              trace=trace, memo_slots=slots)
+
     # ------------------------------------------------------------------ one group of clips that share their launches
     def _group(self, launch, out, traces) -> None:
+        self._walk(sync_launch(self.engine, launch, range(NB)), out, traces)      # conditioning + sync once, whatever the number of keys
+
+    def _keyring(self):
+        if self._ring is None or self._ring.ring.device != self.engine.device:
+            self._ring = self.engine.keyring(self.keys)
+        return self._ring
+
+    def _hop_table(self, C: int):
+        """uint8 [N, C] on the device: band of (key, counter) for the counters 0 .. C - 1."""
+        import torch
+        eng, N = self.engine, len(self.keys)
+        kk = torch.arange(N, dtype=torch.int32, device=eng.device).repeat_interleave(C)
+        cc = torch.arange(C, dtype=torch.int64, device=eng.device).repeat(N)
+        return eng.schedule_keyed(self._keyring(), kk, cc, want_pn=False)[1].reshape(N, C)
+
+    def _walk(self, scan, out, traces, live: "_LiveWalk | None" = None) -> None:
+        """Everything after the sync, for the clips of one SyncScan: header decode per (key, fitting peak), hop table, plan, rank loop,
+        final check.  live: the scan is a monitor tick's (SyncScan.from_monitor) -- frames are read in place in the history rows, row
+        lengths are the windows', and candidates the memo knows to fail are not decoded again."""
         import torch
         eng = self.engine
         dev = eng.device
-        N, g = len(self.keys), len(launch.idx)
+        N, g = len(self.keys), len(scan.sizes)
+        tracing = self.trace if live is None else live.trace
         R = g * NB                                                          # sync rows: row = clip * 4 + band index
-        if self._ring is None or self._ring.ring.device != dev:
-            self._ring = eng.keyring(self.keys)
-        ring = self._ring
-        scan = sync_launch(eng, launch, range(NB))                           # conditioning + sync once, whatever the number of keys
+        ring = self._keyring()
         sy, y, rows_a, starts = scan.sy, scan.sy.y, scan.rows, scan.starts   # the P fitting peaks, in (row, peak) order
         if not rows_a.size:                                                 # no peak can hold a frame: nothing to try for any key
             return
@@ -141,20 +194,17 @@ class WatermarkIdentifier:
         # one header decode over (key, fitting peak), key-major, each key with its own header PN
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
         okh, val, score = eng.header(y, t(np.tile(rows_a % NB, N), np.uint8), ring.hdr_pn.repeat_interleave(P, dim=0),
-                                     rows=t(np.tile(rows_a, N), np.int32), start=t(np.tile(starts, N), np.int32))
+                                     rows=t(np.tile(scan.frame_rows, N), np.int32), start=t(np.tile(scan.frame_cols, N), np.int32))
         # hop table: band of (key, counter) for every counter a window can reach
-        C = -(-M // FRAME_LEN) + WIDE_DELTA + 1
-        kk = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(C)
-        cc = torch.arange(C, dtype=torch.int64, device=dev).repeat(N)
-        _, hop = eng.schedule_keyed(ring, kk, cc, want_pn=False)
+        hop = self._hop_table(-(-M // FRAME_LEN) + WIDE_DELTA + 1) if live is None else live.hop
         rowband = np.tile(np.arange(NB, dtype=np.uint8), g)
-        plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M if int(sizes.min()) == M else M_rows, okh.reshape(N, P), val.reshape(N, P),
-                        hop.reshape(N, C))
+        plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M if live is None and int(sizes.min()) == M else M_rows, okh.reshape(N, P),
+                        val.reshape(N, P), hop)
         count = plan.count.cpu().numpy().astype(np.int64).reshape(N, R)
         hop0 = ring.hop0.cpu().numpy().astype(np.int64)
         order = np.array([[h] + [b for b in range(NB) if b != h] for h in range(NB)], np.int64)[hop0]      # [N, 4]: rtwm/detector.py:46-52
         pk_h = sy.peaks.cpu().numpy()
-        if self.trace:
+        if tracing:
             looked = plan.looked.cpu().numpy().reshape(N, R)
             hdr_h = (okh.cpu().numpy().reshape(N, P), val.cpu().numpy().reshape(N, P), score.cpu().numpy().astype(np.float64).reshape(N, P))
             fit = (pk_h >= 0) & (pk_h + FRAME_LEN <= M_rows[:, None]) & (np.arange(ES_MAX_PEAKS)[None, :] < np.minimum(sy.npeaks.cpu().numpy() & 0xFFFF, PEAK_LIMIT)[:, None])
@@ -183,41 +233,59 @@ class WatermarkIdentifier:
                 flat = t((ks[pair_of] * R + rs[pair_of]) * ES_MAX_TRIES + pos, np.int64)
                 ctr_d = plan.ctr.reshape(-1)[flat]
                 slot_d = plan.slot.reshape(-1)[flat].to(torch.int64)
-                row_d = t(rs[pair_of], np.int64)
+                row_h = rs[pair_of]
+                row_d = t(row_h, np.int64)
                 start_d = sy.peaks.reshape(-1)[row_d * ES_MAX_PEAKS + slot_d]
                 key_d = t(ks[pair_of], np.int32)
-                row_d = row_d.to(torch.int32)
-                ok_all = np.empty((total, 4), np.int8)
+                ctr_h = ctr_d.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+                start_h = start_d.cpu().numpy().astype(np.int64)
+                if live is None:                                            # frames at sy.y[row, start] ...
+                    yrow_d, col_d = row_d.to(torch.int32), start_d
+                else:                                                       # ... or in place in the history: row 4 s + j, column offset + start
+                    yrow_d, col_d = t(live.rows[row_h], np.int32), t(live.offset[row_h] + start_h, np.int32)
+                todo = np.arange(total)
+                if live is not None:
+                    live.stats["planned"] += total
+                    if live.memo is not None:                               # candidates already known to fail are not decoded again
+                        k0, k1 = memo.pack(ks[pair_of], live.rows[row_h], live.epoch[row_h], live.w0[row_h] + start_h, ctr_h)
+                        k0_d, k1_d = t(k0.view(np.int64), np.int64), t(k1.view(np.int64), np.int64)
+                        todo = np.flatnonzero(eng.memo_probe(live.memo, k0_d, k1_d).cpu().numpy() == 0)
+                    live.stats["decoded"] += int(todo.size)
+                    live.stats["skipped"] += total - int(todo.size)
+                ok_all = np.zeros((total, 4), np.int8)                      # (a candidate that is not decoded is a known failure)
                 blobs: dict[int, np.ndarray] = {}
-                for a in range(0, total, cap):
-                    b = min(total, a + cap)
-                    n = b - a
-                    pn, bands = eng.schedule_keyed(ring, key_d[a:b], ctr_d[a:b])
-                    l0 = eng.llr(y, bands, pn, variant=0, rows=row_d[a:b], start=start_d[a:b])
-                    l1 = eng.llr(y, bands, pn, variant=1, rows=row_d[a:b], start=start_d[a:b])
+                for a in range(0, todo.size, cap):
+                    sel = todo[a:a + cap]
+                    n = sel.size
+                    sel_d = t(sel, np.int64)
+                    at = {"rows": yrow_d[sel_d], "start": col_d[sel_d]}
+                    pn, bands = eng.schedule_keyed(ring, key_d[sel_d], ctr_d[sel_d])
+                    l0 = eng.llr(y, bands, pn, variant=0, **at)
+                    l1 = eng.llr(y, bands, pn, variant=1, **at)
                     res = eng.scl(torch.cat((l0, -l0, l1, -l1), dim=0), list_size=L, skip_if_hard_ok=False)
-                    payload, ok, _which = eng.select(res, ring=ring, key_idx=key_d[a:b].repeat(4), ctrs=ctr_d[a:b].repeat(4))
+                    payload, ok, _which = eng.select(res, ring=ring, key_idx=key_d[sel_d].repeat(4), ctrs=ctr_d[sel_d].repeat(4))
                     okc = ok.cpu().numpy().reshape(4, n).T
                     if (okc == -2).any():
                         raise NativeError("es_scl_batch: some candidate records were not decoded (no free scratch-slab slot)")
-                    ok_all[a:b] = okc
+                    ok_all[sel] = okc
                     hit = np.flatnonzero((okc == 1).any(axis=1))
                     if hit.size:
                         v = np.argmax(okc[hit] == 1, axis=1)                # the first of +llr0, -llr0, +llr1, -llr1 that validates
                         got = payload[t(v * n + hit, np.int64)].cpu().numpy()
                         for i, vv, row in zip(hit, v, got):
-                            blobs[a + int(i)] = (int(vv), row)
+                            blobs[int(sel[i])] = (int(vv), row)
+                if live is not None and live.memo is not None and todo.size:
+                    # what was decoded and failed in all four variants is remembered: ONE insert per rank, the rest masked out
+                    eng.memo_insert(live.memo, np.where((ok_all[todo] == 0).all(axis=1), k0[todo], memo.EMPTY), k1[todo])
                 hits = np.flatnonzero((ok_all == 1).any(axis=1))
                 if hits.size:
                     pairs, where = np.unique(pair_of[hits], return_index=True)      # hits ascend: the first hit of each pair
                     first[pairs] = hits[where]
-                ctr_h = ctr_d.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
-                start_h = start_d.cpu().numpy().astype(np.int64)
                 for p in np.flatnonzero(first >= 0):
                     i = int(first[p])
                     vv, blob = blobs[i]
                     found.append((int(ks[p]), int(cs[p]), int(ctr_h[i]), int(order[ks[p], rank]), int(start_h[i]), vv, blob))
-            if self.trace:
+            if tracing:
                 off = np.cumsum(cnt) - cnt
                 slot_h = slot_d.cpu().numpy() if total else None
                 for p in range(ks.size):
@@ -241,4 +309,100 @@ class WatermarkIdentifier:
                 out[f[1]][f[0]] = KeyMatch(f[0], f[2], f[3], f[4], f[5], f[6].tobytes(), pt.tobytes())
 
 
-__all__ = ["KeyMatch", "WatermarkIdentifier", "plan_reference", "ctr_estimate"]
+class LiveIdentifier(LiveTable):
+    """The monitored streams of a WatermarkIdentifier (WatermarkIdentifier.open_streams); stream ids are the slots of `table`.
+
+    After a push, entry k of stream s is what WatermarkIdentifier.identify gives for key k on the stream's window [w0, n): while
+    w0 == 0 exactly identify(everything received so far, fs_target), afterwards the identifier's walk over the scan of the contiguous
+    slice y_whole[:, w0 : n] of the whole stream's band-pass -- same boolean, same tries in the same order, same accepted blob, with
+    KeyMatch.start relative to the window.  Every push is stateless per key, as identify is.  A stream opened at another rate is
+    conditioned on the device first, as for LiveMonitor.
+
+    What differs is the work.  The band-pass and the correlation are continued from push to push by the monitor table,
+    and a candidate (key, band row, absolute position, counter) that failed once is remembered in a memo on the device: its verdict
+    depends on nothing else, and the history it read is bit-identical from push to push, so a tick decodes only candidates it has never
+    decoded.  `stats` counts the candidates of the last push: planned = decoded + skipped."""
+
+    def __init__(self, identifier: WatermarkIdentifier, table, *, trace: bool = False, memo_slots: int = 0) -> None:
+        self._id, self.table, self._trace = identifier, table, bool(trace)
+        self.check_memo(memo_slots, len(identifier.keys), table.window)
+        self.memo_slots = int(memo_slots)
+        self._memo = None                                                   # engine.Memo, opened by the first push that needs it
+        self._hop = None                                                    # the window's hop table, built by the first push
+        self._epoch = np.zeros(table.n, np.int64)                           # times each stream slot has been closed, mod 2^16
+        self.stats = {"planned": 0, "decoded": 0, "skipped": 0}
+
+    @staticmethod
+    def check_memo(slots: int, n_keys: int, window: int) -> None:
+        """Refuse what the memo's records cannot name: they hold 20 bits of key index and 16 of counter."""
+        if not slots:
+            return
+        memo.check_slots(slots)
+        if n_keys > memo.MAX_KEYS:
+            raise ValueError(f"{n_keys} keys: a live identifier with a memo takes at most {memo.MAX_KEYS} keys (memo_slots=0 takes any number)")
+        C = -(-int(window) // FRAME_LEN) + WIDE_DELTA + 1
+        if C > memo.MAX_COUNTERS:
+            raise ValueError(f"window of {int(window)} samples: its candidates reach counter ceil(window / 1215) + 200 = {C - 1}, the memo's records "
+                             f"hold counters below {memo.MAX_COUNTERS} (use a shorter window_s, or memo_slots=0)")
+
+    @property
+    def fs_target(self) -> int:
+        return self._id.fs_target
+
+    def push(self, chunks, streams=None, *, fs: int | None = None):
+        """chunks[i], 1-D int16 or float32 at the rate its stream was opened with, continues stream streams[i] (None: one chunk per open
+        stream, in order) -> per chunk a list of len(keys) entries, a KeyMatch or None; with trace=True (matches, traces) as
+        identify_batch returns them.  Streams not named are not touched.  Raises ValueError before any GPU work for what
+        LiveMonitor.push refuses, and for a stream that would pass 2^48 samples while the memo is on."""
+        from .monitor import push_arguments
+        from .scan import SyncScan
+        tab, N = self.table, len(self._id.keys)
+        ids, arrs, lengths = push_arguments(tab, self.fs_target, chunks, streams, fs)
+        if self.memo_slots and ids.size and (tab.n_host[ids] + lengths).max() > memo.MAX_POSITION:
+            bad = int(ids[int((tab.n_host[ids] + lengths).argmax())])
+            raise ValueError(f"stream {bad} would pass 2^48 samples: the memo's records hold absolute positions below that (close the stream "
+                             "and open it again, or use memo_slots=0)")
+        out = [[None] * N for _ in ids]
+        traces = [[([], []) for _ in range(N)] for _ in ids]
+        self.stats = {"planned": 0, "decoded": 0, "skipped": 0}
+        if ids.size and N:
+            eng = self._id.engine
+            if self.memo_slots and self._memo is None:
+                self._memo = eng.open_memo(self.memo_slots)
+            if self._hop is None:                                           # depends on the keys and the window alone
+                self._hop = self._id._hop_table(-(-tab.window // FRAME_LEN) + WIDE_DELTA + 1)
+            tick = eng.monitor_step(tab, ids, arrs)
+            per_call = max(1, PAIR_BUDGET // (N * NB))                      # cut as identify_batch cuts its clips
+            for a in range(0, ids.size, per_call):
+                part = tick.part(a, a + per_call)
+                s_rows = np.repeat(part.sid, NB)                            # the stream of each scan row
+                live = _LiveWalk(part.rows, part.offset, tab.base_host[s_rows] + part.offset, self._epoch[s_rows], self._hop, self._memo, self.stats,
+                                 self._trace)
+                self._id._walk(SyncScan.from_monitor(part), out[a:a + per_call], traces[a:a + per_call], live)
+        elif ids.size:
+            self._id.engine.monitor_step(tab, ids, arrs)                    # no key: the streams still move on
+        return (out, traces) if self._trace else out
+
+    def forget(self) -> None:
+        """Empty the memo: the next push of every stream decodes its whole window again."""
+        if self._memo is not None:
+            self._memo.table.fill_(-1)
+
+    def add(self, n: int = 1, fs=None) -> np.ndarray:
+        """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
+        fs_target)."""
+        ids = self._id.engine.add_monitor_streams(self.table, n, fs)
+        self._epoch = np.concatenate((self._epoch, np.zeros(self.table.n - self._epoch.size, np.int64)))
+        return ids
+
+    def close(self, streams) -> None:
+        """Free the slots of `streams` (their state and history are dropped); a push to a closed stream raises.  The slot's epoch moves
+        on, so whoever opens it next never meets this stream's verdicts; when an epoch wraps the whole memo is emptied."""
+        from .monitor import monitor_ids
+        ids = monitor_ids(self.table, streams)
+        self._id.engine.close_monitor_streams(self.table, ids)
+        if memo.bump_epochs(self._epoch, ids):
+            self.forget()
+
+
+__all__ = ["KeyMatch", "LiveIdentifier", "WatermarkIdentifier", "plan_reference", "ctr_estimate"]

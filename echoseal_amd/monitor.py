@@ -272,6 +272,56 @@ def monitor_conditioned(table: MonitorTable, ids: np.ndarray, arrs: list):
     return lengths, other, f_old
 
 
+def push_arguments(table: MonitorTable, target: int, chunks, streams=None, fs=None):
+    """The arguments of a push of live streams (LiveMonitor.push, LiveIdentifier.push), checked without an engine -> (ids int64, chunks as
+    1-D int16 / float32 host arrays, their lengths at fs_target).  streams None: one chunk per open stream, in order.  fs= is a check,
+    not a conversion: every named stream must have been opened at that rate.  A ValueError names what is refused: that, a chunk that is
+    not 1-D, longer than chunk_max or (at another rate) finalizing more than chunk_max samples, a stream named twice, outside the table
+    or closed."""
+    chunks = list(chunks)
+    if fs is not None and table.rs is None and int(fs) != target:
+        raise ValueError(f"chunks at {fs} Hz: this monitor's streams arrive at fs_target = {target} Hz (open a stream with fs={fs} "
+                         "to have it conditioned on the device; push(fs=) only checks the rate)")
+    if streams is None:
+        streams = np.flatnonzero(table.live)
+    ids = monitor_ids(table, streams)
+    if fs is not None and table.rs is not None and (table.rs.fs[ids] != int(fs)).any():
+        bad = int(ids[table.rs.fs[ids] != int(fs)][0])
+        raise ValueError(f"chunks at {fs} Hz: stream {bad} was opened at {int(table.rs.fs[bad])} Hz (fs_target = {target} Hz); push(fs=) "
+                         "only checks the rate, a stream's rate is fixed when it is opened")
+    if len(chunks) != ids.size:
+        raise ValueError("one chunk per stream is required")
+    arrs = monitor_chunks(chunks, table.chunk_max, None if table.rs is None else table.rs.fs[ids] == target)
+    lengths, _, _ = monitor_conditioned(table, ids, arrs)                   # a chunk that finalizes more than chunk_max: refused here
+    return ids, arrs, lengths
+
+
+class LiveTable:
+    """What LiveMonitor and LiveIdentifier say about their streams: both hold a MonitorTable as `table` and the rate the streams are
+    conditioned to as `fs_target`; stream ids are the table's slots."""
+
+    def __len__(self) -> int:
+        return int(np.count_nonzero(self.table.live))
+
+    def position(self, stream: int) -> int:
+        """Samples at fs_target stream `stream` has been verified over since it was opened: the samples received, for a stream at
+        another rate the conditioned samples that are final."""
+        return int(self.table.n_host[int(stream)])
+
+    def received(self, stream: int) -> int:
+        """Samples stream `stream` has received since it was opened, at its own rate."""
+        return int(self.table.n_in_host[int(stream)])
+
+    def rate(self, stream: int) -> int:
+        """The rate stream `stream` was opened at."""
+        return int(self.table.fs[int(stream)]) or int(self.fs_target)
+
+    def window(self, stream: int) -> tuple[int, int]:
+        """(w0, n): the samples of the stream, counted from its opening, that its last push looked at."""
+        n = self.position(stream)
+        return int(window_start(n, self.table.window)), n
+
+
 @dataclass
 class MonitorTick:
     """What one tick found (RxEngine.monitor_step).  Record q = 4 i + j is band row j of the i-th pushed stream; its window is
@@ -285,6 +335,11 @@ class MonitorTick:
     offset: np.ndarray         # [4 R] int64 column of the window's first sample: w0 - base
     length: np.ndarray         # [4 R] int64 samples of the window: n - w0
     nb: int = nat.ES_NBANDS
+
+    def part(self, a: int, b: int) -> "MonitorTick":
+        """The records of pushed streams a .. b - 1 as a tick of their own."""
+        q = slice(self.nb * a, self.nb * b)
+        return MonitorTick(self.y, self.thr[q], self.peaks[q], self.npeaks[q], self.sid[a:b], self.rows[q], self.offset[q], self.length[q], self.nb)
 
 
 class MonitorChain:
@@ -511,6 +566,6 @@ class MonitorChain:
         return MonitorTick(table.y_hist, thr, peaks, npeaks, ids, q_rows, offset, length)
 
 
-__all__ = ["SEG", "MIN_WINDOW", "MonitorChain", "MonitorLayout", "MonitorTable", "MonitorTick", "ResamplerTable", "check_geometry",
-           "history_columns", "host_table", "monitor_chunks", "monitor_conditioned", "monitor_ids", "monitor_layout", "resample_counts",
-           "resampler_host", "stream_rates", "window_start"]
+__all__ = ["SEG", "MIN_WINDOW", "LiveTable", "MonitorChain", "MonitorLayout", "MonitorTable", "MonitorTick", "ResamplerTable", "check_geometry",
+           "history_columns", "host_table", "monitor_chunks", "monitor_conditioned", "monitor_ids", "monitor_layout", "push_arguments",
+           "resample_counts", "resampler_host", "stream_rates", "window_start"]

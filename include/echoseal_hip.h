@@ -606,6 +606,34 @@ int es_xcorr_stream_batch(es_ctx* ctx, const double* y_hist_dev, int64_t R, int6
 int es_pick_at_batch(es_ctx* ctx, const double* corr_dev, int64_t n_rows, int stride, int64_t B, const int32_t* row_dev, const int32_t* col_dev,
                      const int32_t* nlag_dev, double* thr_dev, int32_t* peaks_dev, int32_t* npeaks_dev, void* stream);
 
+/* ---- the verdict memo of live identification: which (key, row, position, counter) candidates are already known to fail ----------
+ * A candidate's verdict (the four list decodes of rtwm/detector.py:161-190 and their validation) depends on the key, the band row, the
+ * 1215 band-passed samples at an absolute position and the counter alone, and a monitor's band-passed history is bit-identical from
+ * push to push: a candidate that failed once fails for as long as its stream lives.  The memo remembers such candidates, exactly.
+ *
+ * table_dev [slots][2] uint64, 16-byte aligned, slots a power of two; an entry is the record (k0, k1) itself, ES_MEMO_EMPTY in both
+ * words when empty.  The caller packs the records (echoseal_amd/memo.py pack):
+ *     k0 = key index (bits 0..19) | history row 4 s + j (bits 20..43) | epoch of stream slot s (bits 44..59); bits 60..63 zero
+ *     k1 = absolute start w0 + peak (bits 0..47) | counter (bits 48..63)
+ * so no record equals the empty entry.  Record (k0, k1) lives at
+ *     slot = mix(k0 * 0x9E3779B97F4A7C15 + k1) & (slots - 1),   mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                                                                        z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31
+ * (the splitmix64 finaliser, arithmetic mod 2^64) or nowhere: direct-mapped, no probe sequence.  A miss only costs a decode.
+ *
+ * es_memo_probe_batch: hit_dev[i] = (table[slot_i] == (k0_dev[i], k1_dev[i])), both words; reads only.
+ * es_memo_insert_batch: among the records of the call that map to one slot, the one with the lowest index replaces whatever the slot
+ * held and the others are dropped; a record whose k0 is ES_MEMO_EMPTY is ignored (how a caller masks records out).  The table after
+ * the call is a function of the table before it and the records.  Two kernels, no wait of any kind: an atomic min of the record
+ * index on claim_dev [slots] uint32, which must rest at 0xFFFFFFFF, then the record whose index the claim word holds writes both
+ * words and puts 0xFFFFFFFF back.  claim_dev is all 0xFFFFFFFF again when the call has run.
+ * ES_EINVAL, before anything is enqueued and with nothing written: slots < 1 or not a power of two, n < 0 or n >= 2^32 - 1, a null
+ * pointer with n > 0.  n == 0 enqueues nothing.  Both need no tables and only enqueue (capturable). */
+#define ES_MEMO_EMPTY 0xFFFFFFFFFFFFFFFFull
+int es_memo_probe_batch(es_ctx* ctx, const uint64_t* table_dev, int64_t slots, const uint64_t* k0_dev, const uint64_t* k1_dev, int64_t n,
+                        uint8_t* hit_dev, void* stream);
+int es_memo_insert_batch(es_ctx* ctx, uint64_t* table_dev, uint32_t* claim_dev, int64_t slots, const uint64_t* k0_dev, const uint64_t* k1_dev,
+                         int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
