@@ -1012,6 +1012,41 @@ int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* n
                                  N, C, cand_slot_dev, cand_ctr_dev, count_dev, looked_dev, (hipStream_t)stream);
 }
 
+int es_plan_at_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev, const int32_t* hdr_base_dev,
+                     int64_t rows, const int32_t* len_dev, int T_max, const uint8_t* hdr_ok_dev, const int32_t* hdr_lo16_dev, int64_t P,
+                     const uint8_t* hop_dev, int64_t N, int C, const int64_t* pos0_dev, const uint32_t* ctr0_dev, const int32_t* hop_row_dev,
+                     const uint32_t* hop_base_dev, int HR, uint8_t* cand_slot_dev, uint32_t* cand_ctr_dev, int32_t* count_dev,
+                     int32_t* looked_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (rows < 0 || N < 0 || P < 0 || T_max < 0) return fail(ctx, ES_EINVAL, "es_plan_at_batch: negative size");
+    if (rows == 0 || N == 0) return ES_OK;
+    if (rows * N > ((int64_t)1 << 31)) return fail(ctx, ES_EINVAL, "es_plan_at_batch: more than 2^31 (key, row) pairs in one call");
+    if (HR < 1) return fail(ctx, ES_EINVAL, "es_plan_at_batch: no hop row");
+    // a hop row starts 200 counters before the estimate at the row's first sample and must reach 200 past the one at its last frame
+    if (C < (T_max + ES_FRAME_LEN - 1) / ES_FRAME_LEN + 402) return fail(ctx, ES_EINVAL, "es_plan_at_batch: hop rows narrower than ceil(T_max / 1215) + 402 counters");
+    if (!peaks_dev || !npeaks_dev || !rowband_dev || !hdr_base_dev || !len_dev || !hop_dev || !pos0_dev || !ctr0_dev || !hop_row_dev ||
+        !hop_base_dev || !cand_slot_dev || !cand_ctr_dev || !count_dev || (P > 0 && (!hdr_ok_dev || !hdr_lo16_dev)))
+        return fail(ctx, ES_EINVAL, "es_plan_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_plan_at(ctx, peaks_dev, npeaks_dev, rowband_dev, hdr_base_dev, rows, len_dev, hdr_ok_dev, hdr_lo16_dev, P, hop_dev, N, C,
+                             pos0_dev, ctr0_dev, hop_row_dev, hop_base_dev, HR, cand_slot_dev, cand_ctr_dev, count_dev, looked_dev,
+                             (hipStream_t)stream);
+}
+
+int es_hop_window_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const uint32_t* hop_base_dev, int64_t HR, int64_t C, uint8_t* hop_dev,
+                        void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (N < 0 || HR < 0 || C < 0) return fail(ctx, ES_EINVAL, "es_hop_window_batch: negative count");
+    if (N == 0 || HR == 0 || C == 0) return ES_OK;
+    if (HR > ((int64_t)1 << 31) || C > ((int64_t)1 << 31) || N > ((int64_t)1 << 31) || N * HR > ((int64_t)1 << 40) / C)
+        return fail(ctx, ES_EINVAL, "es_hop_window_batch: more than 2^40 (key, hop row, column) entries in one call");
+    if (!ring_dev || !hop_base_dev || !hop_dev) return fail(ctx, ES_EINVAL, "es_hop_window_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_hop_window(ctx, ring_dev, N, hop_base_dev, HR, C, hop_dev, (hipStream_t)stream);
+}
+
 // what both memo calls refuse: a table that is not a power of two of entries, a count the uint32 claim words cannot index
 static int memo_refusal(es_ctx* ctx, const char* who, int64_t slots, int64_t n)
 {

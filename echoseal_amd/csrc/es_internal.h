@@ -14,6 +14,7 @@
 typedef __attribute__((address_space(1))) const uint8_t g_cu8;
 typedef __attribute__((address_space(1))) const uint32_t g_cu32;
 typedef __attribute__((address_space(1))) const int32_t g_ci32;
+typedef __attribute__((address_space(1))) const long long g_ci64;
 typedef __attribute__((address_space(1))) uint8_t g_u8;
 typedef __attribute__((address_space(1))) uint32_t g_u32;
 typedef __attribute__((address_space(1))) int32_t g_i32;
@@ -268,6 +269,12 @@ int es_launch_plan(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, con
 int es_launch_plan_ragged(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base,
                           int64_t rows, const int32_t* len, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop,
                           int64_t N, int C, uint8_t* cand_slot, uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
+int es_launch_plan_at(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base, int64_t rows,
+                      const int32_t* len, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
+                      const int64_t* pos0, const uint32_t* ctr0, const int32_t* hop_row, const uint32_t* hop_base, int HR, uint8_t* cand_slot,
+                      uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
+int es_launch_hop_window(es_ctx* ctx, const uint8_t* ring, int64_t N, const uint32_t* hop_base, int64_t HR, int64_t C, uint8_t* hop,
+                         hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

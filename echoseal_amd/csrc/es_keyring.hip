@@ -2,7 +2,8 @@
 // device), the key / PN / hop schedule of (key, counter) records, and the counter-candidate planning of the detector's scan for
 // every (key, clip, band).  Replaces, per key, SecureChannel.__init__ (rtwm/crypto.py:19-30: HKDF-SHA256), StreamPRNG.__init__
 // (rtwm/utils.py:86-88: BLAKE2s), the host-side expansion of es_sched.hip, and _scan_band_multi_frame's candidate loop
-// (rtwm/detector.py:105-142).
+// (rtwm/detector.py:105-142) -- also for rows that lie somewhere in a stream marked from any counter (es_plan_at_kernel: line 117 with the
+// row's absolute position and the stream's counter origin), over hop windows filled here (es_hop_window_kernel: rtwm/utils.py:27-36).
 //
 // Integer work throughout.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
@@ -98,6 +99,20 @@ __global__ __launch_bounds__(256) void es_keyring_derive_kernel(const uint8_t* _
     }
 }
 
+// b = band index of counter ctr under the hop key of ring row `row`: HMAC-SHA256(master, ctr_be32)[0] % 4 from the row's pad states.
+// The one statement of it, for es_schedule_keyed_kernel and es_hop_window_kernel.  A macro and not a device function: the compiler
+// orders the sums of the two compressions by where their operands are defined in the function it simplifies first, and through any
+// wrapper function, however thin, es_schedule_keyed_kernel came out with a dozen instructions in another order (tools/asm_diff.sh).
+#define ES_HOP_BAND(b, row, ctr)                                                                                                      \
+    do {                                                                                                                              \
+        uint32_t ip[8], op[8], w[16], tag[8];                                                                                         \
+        _Pragma("unroll")                                                                                                             \
+        for (int t = 0; t < 8; ++t) { ip[t] = (row)[RW_IPAD + t]; op[t] = (row)[RW_OPAD + t]; }                                       \
+        w[0] = (ctr);                                                                 /* message = ctr_be32 */                        \
+        hmac256_short(ip, op, w, 1, tag);                                                                                             \
+        (b) = (tag[0] >> 24) & 3u;                                                    /* tag[0] % 4 */                                \
+    } while (0)
+
 // es_schedule_kernel (es_sched.hip) with the key material of record i read from ring row key[i]
 __global__ __launch_bounds__(256) void es_schedule_keyed_kernel(const uint8_t* __restrict__ ring_p, long long N,
         const int32_t* __restrict__ key_p, const uint32_t* __restrict__ ctr_p, long long n, const uint8_t* __restrict__ sbox_g,
@@ -132,29 +147,44 @@ __global__ __launch_bounds__(256) void es_schedule_keyed_kernel(const uint8_t* _
         }
         if (band_p) {
             uint32_t b = 0;
-            if (have) {
-                uint32_t ip[8], op[8], w[16], tag[8];
-                #pragma unroll
-                for (int t = 0; t < 8; ++t) { ip[t] = row[RW_IPAD + t]; op[t] = row[RW_OPAD + t]; }
-                w[0] = ctr;                                                           // message = ctr_be32
-                hmac256_short(ip, op, w, 1, tag);
-                b = (tag[0] >> 24) & 3u;                                              // tag[0] % 4
-            }
+            if (have) ES_HOP_BAND(b, row, ctr);
             ((g_u8*)band_p)[i] = (uint8_t)b;
         }
     }
 }
 
+// The hop windows of es_plan_at_batch: one lane per (key k, hop row h, column col) of the [N][HR][C] table, counter = base[h] + col.
+// A counter past 2^32 - 1 does not exist and gets 0xFF, which matches no band.
+__global__ __launch_bounds__(256) void es_hop_window_kernel(const uint8_t* __restrict__ ring_p, long long N, const uint32_t* __restrict__ base_p,
+        long long HR, long long C, uint8_t* __restrict__ hop_p)
+{
+    const long long n = N * HR * C, stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const long long kh = i / C, col = i - kh * C, k = kh / HR, h = kh - k * HR;
+        const unsigned long long ctr = (unsigned long long)((g_cu32*)base_p)[h] + (unsigned long long)col;
+        g_cu32* row = (g_cu32*)(ring_p + k * ES_KEYRING_BYTES);
+        uint32_t b = 0xFFu;
+        if (ctr <= 0xFFFFFFFFull) ES_HOP_BAND(b, row, (uint32_t)ctr);
+        ((g_u8*)hop_p)[i] = (uint8_t)b;
+    }
+}
+
 // The candidate (peak slot, counter) pairs of _scan_band_multi_frame in try order, for key k and row `row` = item `pair` of the
 // launch, by one wave.  T: the row's sample count, against which a peak is judged to hold a frame or not.
+// AT (es_plan_at_kernel): the row's first sample is absolute sample pos0 of a stream whose frame k carries counter ctr0 + k, so counters
+// are 64-bit here and end at 2^32 - 1, and column 0 of the hop row read is counter hbase.  Without AT the hop row is the key's and starts
+// at counter 0; pos0, ctr0, hbase and hrow are not read.
+template <bool AT>
 __device__ __forceinline__ void plan_row(long long pair, long long k, long long row, int T, const int32_t* __restrict__ peaks_p,
         const int32_t* __restrict__ npeaks_p, const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p,
         const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p, int C,
-        uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p, int32_t* __restrict__ looked_p)
+        uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p, int32_t* __restrict__ count_p, int32_t* __restrict__ looked_p,
+        long long pos0 = 0, long long ctr0 = 0, long long hbase = 0, long long hrow = 0)
 {
+    using ctr_t = typename std::conditional<AT, long long, int>::type;
     const int lane = threadIdx.x & 63;
     g_ci32* peaks = (g_ci32*)peaks_p + row * ES_MAX_PEAKS;
-    g_cu8* hop = (g_cu8*)hop_p + k * (long long)C;
+    g_cu8* hop = (g_cu8*)hop_p + (AT ? hrow : k) * (long long)C;
     g_u8* slot_out = (g_u8*)slot_p + pair * ES_MAX_TRIES;
     g_u32* ctr_out = (g_u32*)cctr_p + pair * ES_MAX_TRIES;
     const int band = ((g_cu8*)rowband_p)[row];
@@ -171,11 +201,15 @@ __device__ __forceinline__ void plan_row(long long pair, long long k, long long 
         ++looked;
         const bool hok = ((g_cu8*)hok_p)[k * P + p] != 0;
         const int lo16 = ((g_ci32*)hlo_p)[k * P + p];
-        const int est = (int)((2LL * start + ES_FRAME_LEN) / (2 * ES_FRAME_LEN));     // round(start / 1215): 1215 is odd, no ties
+        ctr_t est;
+        if constexpr (AT) est = ctr0 + (2 * (pos0 + start) + ES_FRAME_LEN) / (2 * ES_FRAME_LEN);     // the frame the absolute sample lies in
+        else est = (int)((2LL * start + ES_FRAME_LEN) / (2 * ES_FRAME_LEN));          // round(start / 1215): 1215 is odd, no ties
         bool wide = true;
         if (!hok) {                                                                   // the +-3 window, gated by the hop alone
-            const int c = est - 3 + lane;
-            const bool v = lane < 7 && c >= 0 && c < C && hop[c] == band;
+            const ctr_t c = est - 3 + lane;
+            bool v;                                                                   // (every hop read is guarded by the hop row's width)
+            if constexpr (AT) v = lane < 7 && c >= 0 && c <= 0xFFFFFFFFLL && c - hbase >= 0 && c - hbase < C && hop[c - hbase] == band;
+            else v = lane < 7 && c >= 0 && c < C && hop[c] == band;
             const unsigned long long m = __ballot(v);
             if (m) {
                 const int pos = tried + lanes_below(m);
@@ -185,11 +219,14 @@ __device__ __forceinline__ void plan_row(long long pair, long long k, long long 
             }
         }
         if (wide) {                                                                   // the +-200 window; with a header also gated by lo16
-            const int lo = est - 200 > 0 ? est - 200 : 0, hi = est + 200;
+            const ctr_t lo = est - 200 > 0 ? est - 200 : 0, hi = est + 200;
             #pragma unroll 1
-            for (int c0 = lo; c0 <= hi && tried < ES_MAX_TRIES; c0 += 64) {
-                const int c = c0 + lane;
-                const bool v = c <= hi && c < C && hop[c] == band && (!hok || (c & 0xFFFF) == lo16);
+            for (ctr_t c0 = lo; c0 <= hi && tried < ES_MAX_TRIES; c0 += 64) {
+                const ctr_t c = c0 + lane;
+                bool v;
+                if constexpr (AT) v = c <= hi && c <= 0xFFFFFFFFLL && c - hbase >= 0 && c - hbase < C && hop[c - hbase] == band &&
+                                      (!hok || (int)(c & 0xFFFF) == lo16);
+                else v = c <= hi && c < C && hop[c] == band && (!hok || (c & 0xFFFF) == lo16);
                 const unsigned long long m = __ballot(v);
                 const int pos = tried + lanes_below(m);
                 if (v && pos < ES_MAX_TRIES) { slot_out[pos] = (uint8_t)s; ctr_out[pos] = (uint32_t)c; }
@@ -214,7 +251,7 @@ __global__ __launch_bounds__(256) void es_plan_kernel(const int32_t* __restrict_
     const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
     if (pair >= N * rows) return;
     const long long k = pair / rows, row = pair - k * rows;
-    plan_row(pair, k, row, T, peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p, looked_p);
+    plan_row<false>(pair, k, row, T, peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p, looked_p);
 }
 
 // the same with row r of len_p[r] samples
@@ -227,8 +264,33 @@ __global__ __launch_bounds__(256) void es_plan_ragged_kernel(const int32_t* __re
     const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
     if (pair >= N * rows) return;
     const long long k = pair / rows, row = pair - k * rows;
-    plan_row(pair, k, row, ((g_ci32*)len_p)[row], peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p,
+    plan_row<false>(pair, k, row, ((g_ci32*)len_p)[row], peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p,
              looked_p);
+}
+
+// es_plan_ragged_kernel for rows that lie somewhere in a stream: row r starts at absolute sample pos0[r] of a stream whose counters
+// start at ctr0[r], and the pair (k, r) reads hop row hrow[r] of key k's HR hop rows, whose column 0 is counter hbase[hrow[r]].
+// A hop row index outside [0, HR) plans nothing.
+__global__ __launch_bounds__(256) void es_plan_at_kernel(const int32_t* __restrict__ peaks_p, const int32_t* __restrict__ npeaks_p,
+        const uint8_t* __restrict__ rowband_p, const int32_t* __restrict__ base_p, long long rows, const int32_t* __restrict__ len_p,
+        const uint8_t* __restrict__ hok_p, const int32_t* __restrict__ hlo_p, long long P, const uint8_t* __restrict__ hop_p,
+        long long N, int C, const long long* __restrict__ pos0_p, const uint32_t* __restrict__ ctr0_p, const int32_t* __restrict__ hrow_p,
+        const uint32_t* __restrict__ hbase_p, int HR, uint8_t* __restrict__ slot_p, uint32_t* __restrict__ cctr_p,
+        int32_t* __restrict__ count_p, int32_t* __restrict__ looked_p)
+{
+    const long long pair = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+    if (pair >= N * rows) return;
+    const long long k = pair / rows, row = pair - k * rows;
+    const int h = ((g_ci32*)hrow_p)[row];
+    if (h < 0 || h >= HR) {
+        if ((threadIdx.x & 63) == 0) {
+            ((g_i32*)count_p)[pair] = 0;
+            if (looked_p) ((g_i32*)looked_p)[pair] = 0;
+        }
+        return;
+    }
+    plan_row<true>(pair, k, row, ((g_ci32*)len_p)[row], peaks_p, npeaks_p, rowband_p, base_p, hok_p, hlo_p, P, hop_p, C, slot_p, cctr_p, count_p,
+                   looked_p, ((g_ci64*)pos0_p)[row], (long long)((g_cu32*)ctr0_p)[row], (long long)((g_cu32*)hbase_p)[h], k * HR + h);
 }
 
 }  // namespace
@@ -264,4 +326,22 @@ int es_launch_plan_ragged(es_ctx* ctx, const int32_t* peaks, const int32_t* npea
     const long long pairs = (long long)N * rows;                                      // one wave each, four waves per block
     return es_launch(ctx, es_plan_ragged_kernel, (unsigned)((pairs + 3) / 4), 256, 0, st, peaks, npeaks, rowband, hdr_base,
                      (long long)rows, len, hdr_ok, hdr_lo16, (long long)P, hop, (long long)N, C, cand_slot, cand_ctr, count, looked);
+}
+
+int es_launch_plan_at(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, const uint8_t* rowband, const int32_t* hdr_base, int64_t rows,
+                      const int32_t* len, const uint8_t* hdr_ok, const int32_t* hdr_lo16, int64_t P, const uint8_t* hop, int64_t N, int C,
+                      const int64_t* pos0, const uint32_t* ctr0, const int32_t* hop_row, const uint32_t* hop_base, int HR, uint8_t* cand_slot,
+                      uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st)
+{
+    const long long pairs = (long long)N * rows;                                      // one wave each, four waves per block
+    return es_launch(ctx, es_plan_at_kernel, (unsigned)((pairs + 3) / 4), 256, 0, st, peaks, npeaks, rowband, hdr_base, (long long)rows, len,
+                     hdr_ok, hdr_lo16, (long long)P, hop, (long long)N, C, (const long long*)pos0, ctr0, hop_row, hop_base, HR, cand_slot,
+                     cand_ctr, count, looked);
+}
+
+int es_launch_hop_window(es_ctx* ctx, const uint8_t* ring, int64_t N, const uint32_t* hop_base, int64_t HR, int64_t C, uint8_t* hop,
+                         hipStream_t st)
+{
+    return es_launch(ctx, es_hop_window_kernel, es_grid((long long)N * HR * C, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, hop_base,
+                     (long long)HR, (long long)C, hop);
 }

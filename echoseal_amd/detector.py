@@ -26,7 +26,8 @@ from .crypto import SecureChannel
 from .monitor import LiveTable
 from .polar_fast import N_DEFAULT
 from .primitives import InvalidTag
-from .scan import FRAME_LEN, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, Launch, cut_launches, ragged_buckets, sync_launch  # noqa: F401 (re-exported)
+from .scan import (CTR_END, FRAME_LEN, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, Launch, check_counter_reach, counter_estimate,  # noqa: F401 (re-exported)
+                   counter_origins, cut_launches, ragged_buckets, sync_launch)
 from .tables import matched_filter_taps
 from .utils import BAND_PLAN, BandHop, butter_bandpass, choose_band, mseq_63, resample_to, resampled_length  # noqa: F401 (re-exported)
 
@@ -59,6 +60,18 @@ class _Scan:
     sel: np.ndarray             # their places in src and hdr
     starts: np.ndarray          # of the whole launch, like src and hdr
     hdr: tuple                  # header decodes under the detector's key: (ok, low 16 counter bits, score)
+    ctr0: int | None = None     # counter origin of the clip or stream; None: estimates are relative to the scan, as the reference's
+    pos0: int = 0               # absolute sample of the scan's first sample in its stream (a monitor window's w0; 0 for a clip)
+
+
+def clip_origins(ctr0, clips, fs_list, fs_target: int) -> list:
+    """The counter origins of a batch call's clips (scan.counter_origins), each checked against its clip's length at fs_target
+    (scan.check_counter_reach).  Host arithmetic only."""
+    origins = counter_origins(ctr0, len(clips))
+    for c, f, o in zip(clips, fs_list, origins):
+        if o is not None:
+            check_counter_reach(o, resampled_length(int(np.size(c)), int(f), fs_target))
+    return origins
 
 
 class WatermarkDetector:
@@ -129,23 +142,28 @@ class WatermarkDetector:
         hop0 = self._hop.band(0)
         return [hop0] + [b for b in BAND_PLAN if b != hop0]                 # rtwm/detector.py:46-52
 
-    def verify(self, audio: np.ndarray, fs_in: int) -> bool:
-        return self.verify_batch([audio], fs_in)[0]
+    def verify(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None) -> bool:
+        return self.verify_batch([audio], fs_in, None if ctr0 is None else [ctr0])[0]
 
-    def verify_batch(self, clips, fs_in) -> list[bool]:
+    def verify_batch(self, clips, fs_in, ctr0=None) -> list[bool]:
         """verify() for several recordings ("full batched verify()"): the result, the order of tries
         and the evolution of `session_nonce` are those of calling the reference's verify() on the clips one after the other
         (rtwm/detector.py:44-53, 105-152); what is batched is the GPU work.  Clips of one sample type share launches whatever their
         lengths (ragged_buckets: sorted by length, rows x longest clip <= RAGGED_ROW_SAMPLES per launch).  Per launch: ONE sync launch
         sequence over (clips x 4 bands) records, ONE header decode over every peak that can hold a frame and ONE demodulate +
         list-decode + validate batch over the (peak, counter) candidates of all clips and bands; the host then walks clip by clip,
-        in input order, and band by band in the reference's order with its early returns."""
+        in input order, and band by band in the reference's order with its early returns.
+        ctr0: the counter origin of every clip, or one per clip with None entries allowed: the clip's first sample is
+        where the frame of counter ctr0 starts, so a peak at `start` is looked for around ctr0 + round(start / 1215).  None (the
+        default): the reference's estimate round(start / 1215), which finds frames of counters up to about the clip's length + 200."""
         fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        origins = clip_origins(ctr0, clips, fs_list, self.fs_target)       # refused by name before any engine exists
         order = self._band_order()
         launches = cut_launches(clips, fs_list, self.fs_target, len(order), self._conditioned)
         scans: list = [None] * len(clips)
         for la in launches:
             for i, sc in zip(la.idx, self._scan_prepare(la, order)):
+                sc.ctr0 = origins[i]
                 scans[i] = sc
         return self._verify_scans(scans, [la.idx for la in launches], order)
 
@@ -196,20 +214,27 @@ class WatermarkDetector:
             out.append(ok)
         return out
 
-    def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False) -> "LiveMonitor":
+    def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
+                     ctr0=None) -> "LiveMonitor":
         """A monitor of n live streams, all verified under this detector's key: LiveMonitor.push takes their next chunks and says, stream
         by stream, whether the last window_s seconds verify.  fs: the rate the streams arrive at, one or one per stream (None:
         fs_target); a stream at another rate is conditioned on the device chunk by chunk, to the samples of
         resample_poly(whole stream) that no later sample changes (finite samples only).  window_s and chunk_max (default
         half a second) count time and samples at fs_target: a chunk may finalize at most chunk_max conditioned samples.  trace=True
-        records each stream's tries and header decodes of its last push (LiveMonitor.traces)."""
-        from .monitor import check_geometry, stream_rates
+        records each stream's tries and header decodes of its last push (LiveMonitor.traces).  ctr0: the counter origin of every
+        stream, or one per stream with None entries allowed -- what the issuer opened the stream with (WatermarkIssuer.open_streams):
+        frame k of the stream carries counter ctr0 + k, and a push looks for a peak's counter around that of its absolute position
+        (DESIGN 4.18).  None: estimates relative to the window, which follow a stream marked from counter 0 for its first seconds."""
+        from .monitor import check_geometry, origin_words, stream_rates
         window = int(round(float(window_s) * self.fs_target))
         chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
         check_geometry(window, chunk_max)                                   # refused before any engine exists
         stream_rates(int(n), fs, self.fs_target)                             # ... and so is a rate that cannot be served
+        origin_words(ctr0, int(n))                                          # ... and an origin that is no counter
         band_ids = [self._band_id(b) for b in self._band_order()]
-        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids, fs=fs), trace=trace)
+        origin = {} if ctr0 is None else {"ctr0": ctr0}                     # (no origin: the call as it always was)
+        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids, fs=fs, **origin),
+                           trace=trace)
 
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
     def _scan_prepare(self, signals, bands: list) -> list:
@@ -246,20 +271,21 @@ class WatermarkDetector:
             if tried >= MAX_TRIES:
                 break
             start = int(scan.starts[j])
-            ctr_est = int(round(start / FRAME_LEN))
+            # rtwm/detector.py:117, or with an origin the counter of the frame at the peak's absolute position
+            ctr_est = int(round(start / FRAME_LEN)) if scan.ctr0 is None else counter_estimate(start, scan.pos0, scan.ctr0)
             hdr_ok, ctr_lo16, score = bool(scan.hdr[0][j]), int(scan.hdr[1][j]), float(scan.hdr[2][j])
             hdr_log.append((float(hdr_ok), float(ctr_lo16), score))
             cands: list[int] = []
-            if hdr_ok:                                                      # rtwm/detector.py:122-127
-                for ctr in range(max(0, ctr_est - WIDE_DELTA), ctr_est + WIDE_DELTA + 1):
+            if hdr_ok:                                                      # rtwm/detector.py:122-127 (counters end at 2^32 - 1)
+                for ctr in range(max(0, ctr_est - WIDE_DELTA), min(ctr_est + WIDE_DELTA + 1, CTR_END)):
                     if (ctr & 0xFFFF) == ctr_lo16 and self._hop.band(ctr) == band:
                         cands.append(ctr)
             else:                                                           # :131-140
-                for ctr in range(max(0, ctr_est - TIGHT_DELTA), ctr_est + TIGHT_DELTA + 1):
+                for ctr in range(max(0, ctr_est - TIGHT_DELTA), min(ctr_est + TIGHT_DELTA + 1, CTR_END)):
                     if self._hop.band(ctr) == band:
                         cands.append(ctr)
                 if not cands:
-                    for ctr in range(max(0, ctr_est - WIDE_DELTA), ctr_est + WIDE_DELTA + 1):
+                    for ctr in range(max(0, ctr_est - WIDE_DELTA), min(ctr_est + WIDE_DELTA + 1, CTR_END)):
                         if self._hop.band(ctr) == band:
                             cands.append(ctr)
             for ctr in cands[:MAX_TRIES - tried]:
@@ -534,6 +560,9 @@ class LiveMonitor(LiveTable):
         det = self._det
         tick = det.engine.monitor_step(self.table, ids, arrs)
         scans = det._scans_of(SyncScan.from_monitor(tick), self._order, self.table.bands)
+        for i, s in enumerate(ids.tolist()):                                # a stream with an origin: estimates from absolute positions
+            if self.table.origin_host[s] >= 0:
+                scans[i].ctr0, scans[i].pos0 = int(self.table.origin_host[s]), int(self.table.base_host[s] + tick.offset[tick.nb * i])
         walkers = [self._walker(int(s)) for s in ids]
         for w in walkers:
             w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
@@ -549,10 +578,12 @@ class LiveMonitor(LiveTable):
         w = self._walkers.get(int(stream))
         return (None, None) if w is None else (w._trace, w._hdr_trace)
 
-    def add(self, n: int = 1, fs=None) -> np.ndarray:
+    def add(self, n: int = 1, fs=None, ctr0=None) -> np.ndarray:
         """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
-        fs_target)."""
-        return self._det.engine.add_monitor_streams(self.table, n, fs)
+        fs_target); ctr0: their counter origins, one or one per stream (None: no origin)."""
+        from .monitor import origin_words
+        origin_words(ctr0, int(n))                                          # refused by name before the engine is asked
+        return self._det.engine.add_monitor_streams(self.table, n, fs, **({} if ctr0 is None else {"ctr0": ctr0}))
 
     def close(self, streams) -> None:
         """Free the slots of `streams` (their state, history and session nonce are dropped); a push to a closed stream raises."""

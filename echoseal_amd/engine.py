@@ -632,19 +632,38 @@ class RxEngine(TxChain, MonitorChain):
                                                                  _ptr(ok), _ptr(plain), self._stream()), "es_aead_check_keyed_batch")
         return (ok, plain) if want_plain else ok
 
+    def hop_window(self, ring: KeyRing, hop_base, C: int) -> torch.Tensor:
+        """Hop rows filled on the device (es_hop_window_batch): -> uint8 [N, HR, C], entry (k, h, col) = band of counter hop_base[h] + col
+        under key k of the ring, 0xFF where that counter lies past 2^32 - 1.  hop_base: HR counters in [0, 2^32) (host values or a
+        tensor); nothing but them is uploaded."""
+        base = self._ctr_dev(hop_base).reshape(-1)
+        HR, C = base.numel(), int(C)
+        if C < 0:
+            raise ValueError("C: a column count")
+        hop = torch.empty((ring.n, HR, C), dtype=torch.uint8, device=self.device)
+        nat.check(self._ctx, self._lib.es_hop_window_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(base), HR, C, _ptr(hop), self._stream()),
+                  "es_hop_window_batch")
+        return hop
+
     def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
-             hop: torch.Tensor) -> PlanResult:
+             hop: torch.Tensor, *, pos0=None, ctr0=None, hop_row=None, hop_base=None) -> PlanResult:
         """Counter candidates of every (key, row) in try order (es_plan_batch; the rules of _scan_band_multi_frame,
         rtwm/detector.py:105-142).  peaks int32 [rows, 32] / npeaks int32 [rows] of a sync call over records of T samples -- an int, or
         for the rows of a sync_ragged call their sample counts, an integer tensor / array [rows] (es_plan_ragged_batch) --, rowband
         uint8 [rows] their bands, hdr_base int32 [rows] = index of the row's first fitting peak among the P fitting peaks of all
-        rows, hdr_ok uint8 / hdr_lo16 int32 [N, P] header results per (key, fitting peak), hop uint8 [N, C] band of (key, counter)."""
+        rows, hdr_ok uint8 / hdr_lo16 int32 [N, P] header results per (key, fitting peak), hop uint8 [N, C] band of (key, counter).
+        With any of pos0 / ctr0 / hop_row / hop_base (es_plan_at_batch): row r starts at absolute sample pos0[r] (default 0) of a
+        stream whose counters start at ctr0[r] (default 0), hop is uint8 [N, HR, C] (hop_window), the row reads hop row hop_row[r]
+        (default 0), whose column 0 is counter hop_base[hop_row[r]] (default 0); T may be an int or per row."""
         rows = peaks.shape[0]
         if peaks.dim() != 2 or peaks.shape[1] != nat.ES_MAX_PEAKS or peaks.dtype != torch.int32 or npeaks.dtype != torch.int32 or npeaks.numel() != rows:
             raise ValueError("peaks / npeaks: the int32 [rows, 32] / [rows] outputs of a sync call")
-        if hop.dim() != 2 or hop.dtype != torch.uint8:
-            raise ValueError("hop must be uint8 [N, C]")
-        N, C = hop.shape
+        at = not (pos0 is None and ctr0 is None and hop_row is None and hop_base is None)
+        if at and hop.dim() == 2:
+            hop = hop[:, None, :]
+        if hop.dim() != (3 if at else 2) or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [N, HR, C]" if at else "hop must be uint8 [N, C]")
+        N, C = hop.shape[0], hop.shape[-1]
         if hdr_ok.dtype != torch.uint8 or hdr_lo16.dtype != torch.int32 or hdr_ok.shape != hdr_lo16.shape or hdr_ok.dim() != 2 or hdr_ok.shape[0] != N:
             raise ValueError("hdr_ok uint8 / hdr_lo16 int32 must be [N, P]")
         P = hdr_ok.shape[1]
@@ -658,6 +677,27 @@ class RxEngine(TxChain, MonitorChain):
         res = PlanResult(torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.uint8, device=self.device),
                          torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.int32, device=self.device),
                          torch.empty(pairs, dtype=torch.int32, device=self.device), torch.empty(pairs, dtype=torch.int32, device=self.device))
+        if at:
+            HR = hop.shape[1]
+            def per_row(v, n, what, counter=False):                 # one value, or one per row / hop row; None: zeros
+                v = np.zeros(n, np.int64) if v is None else v
+                t = (self._ctr_dev(v) if counter else self._dev(v, torch.int64)).reshape(-1)
+                if t.numel() == 1 and n != 1:
+                    t = t.expand(n)
+                if t.numel() != n:
+                    raise ValueError(f"{what}: one entry, or {n}")
+                return t.contiguous()
+            pos0_d, ctr0_d = per_row(pos0, rows, "pos0"), per_row(ctr0, rows, "ctr0", True)
+            hrow_d, hbase_d = per_row(hop_row, rows, "hop_row").to(torch.int32), per_row(hop_base, HR, "hop_base", True)
+            if torch.is_tensor(T) or isinstance(T, np.ndarray):
+                t_max, lens = (int(T.max()) if rows else 0), self._lens(T, rows)
+            else:
+                t_max, lens = int(T), torch.full((rows,), int(T), dtype=torch.int32, device=self.device)
+            nat.check(self._ctx, self._lib.es_plan_at_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows, _ptr(lens),
+                                                            t_max, _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(pos0_d), _ptr(ctr0_d),
+                                                            _ptr(hrow_d), _ptr(hbase_d), HR, _ptr(res.slot), _ptr(res.ctr), _ptr(res.count),
+                                                            _ptr(res.looked), self._stream()), "es_plan_at_batch")
+            return res
         if torch.is_tensor(T) or isinstance(T, np.ndarray):
             t_max = int(T.max()) if rows else 0                     # (the bound on the hop table's width)
             lens = self._lens(T, rows)

@@ -28,9 +28,9 @@ import numpy as np
 
 from . import memo
 from ._native import ES_MAX_PEAKS, ES_MAX_TRIES, NativeError
-from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector
+from .detector import FRAME_LEN, MAX_TRIES, PEAK_LIMIT, TIGHT_DELTA, WIDE_DELTA, WatermarkDetector, clip_origins
 from .monitor import LiveTable
-from .scan import cut_launches, sync_launch
+from .scan import CTR_END, counter_estimate, cut_launches, sync_launch
 from .utils import BAND_PLAN
 
 assert MAX_TRIES == ES_MAX_TRIES
@@ -54,11 +54,15 @@ def ctr_estimate(start: int) -> int:
     return (2 * int(start) + FRAME_LEN) // (2 * FRAME_LEN)
 
 
-def plan_reference(peaks, npeaks: int, M: int, band: int, hdr_ok, hdr_lo16, hop):
-    """Host twin of es_plan_batch for one (key, row): the rules of WatermarkDetector._scan_plan (rtwm/detector.py:105-142) restated
-    on the kernel's inputs.  peaks: the row's ES_MAX_PEAKS sync peaks, npeaks: its raw count word, M: samples per record, band: the
-    row's band index, hdr_ok / hdr_lo16: header results of the row's fitting peaks in order, hop[ctr]: band index of the key's
-    counters.  -> (plan [(peak slot, ctr)] in try order, fitting peaks looked at)."""
+def plan_reference(peaks, npeaks: int, M: int, band: int, hdr_ok, hdr_lo16, hop, pos0: int = 0, ctr0: int = 0, hop_base: int = 0):
+    """Host twin of es_plan_batch / es_plan_at_batch for one (key, row): the rules of WatermarkDetector._scan_plan
+    (rtwm/detector.py:105-142) restated on the kernel's inputs.  peaks: the row's ES_MAX_PEAKS sync peaks, npeaks: its raw count word,
+    M: samples per record, band: the row's band index, hdr_ok / hdr_lo16: header results of the row's fitting peaks in order,
+    hop[ctr - hop_base]: band index of the key's counters (a counter outside the table is skipped, as the kernels skip it); pos0: the
+    absolute sample of the row's first sample, ctr0: the counter origin of its stream (both 0: the reference's estimate).
+    -> (plan [(peak slot, ctr)] in try order, fitting peaks looked at)."""
+    pos0, ctr0, hop_base, C = int(pos0), int(ctr0), int(hop_base), len(hop)
+    hops = lambda c: 0 <= c - hop_base < C and hop[c - hop_base] == band
     plan: list[tuple[int, int]] = []
     looked = 0
     n = min(int(npeaks) & 0xFFFF, ES_MAX_PEAKS, PEAK_LIMIT)
@@ -70,14 +74,14 @@ def plan_reference(peaks, npeaks: int, M: int, band: int, hdr_ok, hdr_lo16, hop)
             break
         j = looked
         looked += 1
-        est = ctr_estimate(start)
-        wide = range(max(0, est - WIDE_DELTA), est + WIDE_DELTA + 1)
+        est = counter_estimate(start, pos0, ctr0)
+        wide = range(max(0, est - WIDE_DELTA), min(est + WIDE_DELTA + 1, CTR_END))      # counters end at 2^32 - 1
         if hdr_ok[j]:
-            cands = [c for c in wide if (c & 0xFFFF) == int(hdr_lo16[j]) and hop[c] == band]
+            cands = [c for c in wide if (c & 0xFFFF) == int(hdr_lo16[j]) and hops(c)]
         else:
-            cands = [c for c in range(max(0, est - TIGHT_DELTA), est + TIGHT_DELTA + 1) if hop[c] == band]
+            cands = [c for c in range(max(0, est - TIGHT_DELTA), min(est + TIGHT_DELTA + 1, CTR_END)) if hops(c)]
             if not cands:
-                cands = [c for c in wide if hop[c] == band]
+                cands = [c for c in wide if hops(c)]
         plan += [(slot, c) for c in cands[:MAX_TRIES - len(plan)]]
     return plan, looked
 
@@ -89,7 +93,10 @@ class _LiveWalk:
     offset: np.ndarray          # int64 column of the window's first sample
     w0: np.ndarray              # int64 absolute index of the window's first sample
     epoch: np.ndarray           # int64 epoch of the row's stream slot
-    hop: object                 # uint8 [N, C] device: the hop table of the window
+    hop: object                 # uint8 [N, C] device: the hop table of the window, counters from 0 (streams without an origin)
+    origin: np.ndarray          # int64 per pushed stream: its counter origin, -1 for none
+    hop_at: object              # () -> uint8 [N, 1, hop_at_width] device: the same table as a hop row of es_plan_at_batch
+    hop_at_width: int           # ceil(W / 1215) + 402: what es_plan_at_batch asks of a hop row for windows of W samples
     memo: object                # engine.Memo, or None: every candidate is decoded
     stats: dict                 # planned / decoded / skipped candidates, summed over the walk
     trace: bool                 # record traces (the live identifier's own switch, not its WatermarkIdentifier's)
@@ -118,46 +125,52 @@ class WatermarkIdentifier:
     def _pair_cap(self) -> int:
         return self._det._pair_cap()
 
-    def identify(self, audio, fs_in: int):
-        res = self.identify_batch([audio], fs_in)
+    def identify(self, audio, fs_in: int, ctr0: int | None = None):
+        res = self.identify_batch([audio], fs_in, None if ctr0 is None else [ctr0])
         return (res[0][0], res[1][0]) if self.trace else res[0]
 
-    def identify_batch(self, clips, fs_in):
+    def identify_batch(self, clips, fs_in, ctr0=None):
         """identify() for several recordings -> one list of per-key entries per clip (with .trace: (those, per clip the per-key
-        traces)).  Clips of one sample type share their launches whatever their lengths (scan.cut_launches)."""
+        traces)).  Clips of one sample type share their launches whatever their lengths (scan.cut_launches).  ctr0: the counter origin
+        of every clip, or one per clip with None entries allowed, as for WatermarkDetector.verify_batch."""
         N = len(self.keys)
         clips = list(clips)
+        fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        origins = clip_origins(ctr0, clips, fs_list, self.fs_target)       # refused by name before any engine exists
         out = [[None] * N for _ in clips]
         traces = [[([], []) for _ in range(N)] for _ in clips]
         if N:
-            fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
             per_call = max(1, PAIR_BUDGET // (N * NB))
             for la in cut_launches(clips, fs_list, self.fs_target, NB, self._det._conditioned):      # (clips shorter than the template are in none)
                 for at in range(0, len(la.idx), per_call):
                     part = la.part(at, at + per_call)
-                    self._group(part, [out[i] for i in part.idx], [traces[i] for i in part.idx])
+                    self._group(part, [out[i] for i in part.idx], [traces[i] for i in part.idx], [origins[i] for i in part.idx])
         return (out, traces) if self.trace else out
 
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
-                     memo_slots: int | None = None) -> "LiveIdentifier":
+                     memo_slots: int | None = None, ctr0=None) -> "LiveIdentifier":
         """A monitor of n live streams that says, per push and stream, which of this identifier's keys marks the stream's last window_s
         seconds (LiveIdentifier.push).  fs, window_s, chunk_max and trace are those of WatermarkDetector.open_streams.  memo_slots:
         entries of the verdict memo, a power of two; 0: no memo, every push decodes its whole window; None:
         memo.default_slots -- the next power of two above 2 x keys x 4 n x 400, between 2^10 and 2^25 entries of 20 bytes each (16 keys
-        and 64 streams: 2^22 entries, 80 MiB; never more than 640 MiB)."""
-        from .monitor import check_geometry, stream_rates
+        and 64 streams: 2^22 entries, 80 MiB; never more than 640 MiB).  ctr0: the counter origin of every stream, or one per stream
+        with None entries allowed, as for WatermarkDetector.open_streams."""
+        from .monitor import check_geometry, origin_words, stream_rates
         window = int(round(float(window_s) * self.fs_target))
         chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
         check_geometry(window, chunk_max)                                   # refused before any engine exists
         stream_rates(int(n), fs, self.fs_target)                             # ... and so is a rate that cannot be served
+        relative = bool((origin_words(ctr0, int(n)) < 0).any())             # ... and an origin that is no counter
         slots = memo.default_slots(len(self.keys), int(n)) if memo_slots is None else int(memo_slots)
-        LiveIdentifier.check_memo(slots, len(self.keys), window)            # ... and a window or key list the memo's records cannot name
-        return LiveIdentifier(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=tuple(range(NB)), fs=fs),
+        LiveIdentifier.check_memo(slots, len(self.keys), window, relative)  # ... and a window or key list the memo's records cannot name
+        origin = {} if ctr0 is None else {"ctr0": ctr0}                     # (no origin: the call as it always was)
+        return LiveIdentifier(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=tuple(range(NB)), fs=fs, **origin),
                               trace=trace, memo_slots=slots)
 
     # ------------------------------------------------------------------ one group of clips that share their launches
-    def _group(self, launch, out, traces) -> None:
-        self._walk(sync_launch(self.engine, launch, range(NB)), out, traces)      # conditioning + sync once, whatever the number of keys
+    def _group(self, launch, out, traces, origins=None) -> None:
+        # conditioning + sync once, whatever the number of keys
+        self._walk(sync_launch(self.engine, launch, range(NB)), out, traces, origins=origins)
 
     def _keyring(self):
         if self._ring is None or self._ring.ring.device != self.engine.device:
@@ -172,10 +185,11 @@ class WatermarkIdentifier:
         cc = torch.arange(C, dtype=torch.int64, device=eng.device).repeat(N)
         return eng.schedule_keyed(self._keyring(), kk, cc, want_pn=False)[1].reshape(N, C)
 
-    def _walk(self, scan, out, traces, live: "_LiveWalk | None" = None) -> None:
+    def _walk(self, scan, out, traces, live: "_LiveWalk | None" = None, origins=None) -> None:
         """Everything after the sync, for the clips of one SyncScan: header decode per (key, fitting peak), hop table, plan, rank loop,
         final check.  live: the scan is a monitor tick's (SyncScan.from_monitor) -- frames are read in place in the history rows, row
-        lengths are the windows', and candidates the memo knows to fail are not decoded again."""
+        lengths are the windows', and candidates the memo knows to fail are not decoded again.  origins: per clip its counter origin
+        or None (a tick's are live.origin): with any, the plan is es_plan_at_batch's over one hop row per distinct window base."""
         import torch
         eng = self.engine
         dev = eng.device
@@ -196,10 +210,31 @@ class WatermarkIdentifier:
         okh, val, score = eng.header(y, t(np.tile(rows_a % NB, N), np.uint8), ring.hdr_pn.repeat_interleave(P, dim=0),
                                      rows=t(np.tile(scan.frame_rows, N), np.int32), start=t(np.tile(scan.frame_cols, N), np.int32))
         # hop table: band of (key, counter) for every counter a window can reach
-        hop = self._hop_table(-(-M // FRAME_LEN) + WIDE_DELTA + 1) if live is None else live.hop
         rowband = np.tile(np.arange(NB, dtype=np.uint8), g)
-        plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M if live is None and int(sizes.min()) == M else M_rows, okh.reshape(N, P),
-                        val.reshape(N, P), hop)
+        if live is not None:
+            origin = live.origin
+        else:
+            origin = np.full(g, -1, np.int64) if origins is None else np.array([-1 if o is None else o for o in origins], np.int64)
+        absolute = origin >= 0                                              # per clip
+        if not absolute.any():
+            hop = self._hop_table(-(-M // FRAME_LEN) + WIDE_DELTA + 1) if live is None else live.hop
+            plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M if live is None and int(sizes.min()) == M else M_rows, okh.reshape(N, P),
+                            val.reshape(N, P), hop)
+        else:
+            # a clip with an origin starts at sample pos0 (a window's w0; 0 for a clip) of a stream marked from that
+            # counter; one without keeps estimates relative to its first sample, which is origin 0 at pos0 0.  One hop row per
+            # distinct base, filled on the device; the row of base 0 is the hop table of clips without origins.
+            C = -(-M // FRAME_LEN) + 2 * WIDE_DELTA + 2 if live is None else live.hop_at_width
+            pos0 = np.where(absolute, 0 if live is None else live.w0[::NB], 0).astype(np.int64)
+            ctr0 = np.where(absolute, origin, 0)
+            row_base = np.maximum(0, ctr0 + (2 * pos0 + FRAME_LEN) // (2 * FRAME_LEN) - WIDE_DELTA)
+            bases, hop_row = np.unique(row_base, return_inverse=True)
+            if live is not None and bases[0] == 0:                          # counters from 0: the window's own table, built once
+                hop = torch.cat((live.hop_at(), eng.hop_window(ring, bases[1:], C)), dim=1)
+            else:
+                hop = eng.hop_window(ring, bases, C)
+            plan = eng.plan(sy.peaks, sy.npeaks, rowband, base, M_rows, okh.reshape(N, P), val.reshape(N, P), hop, pos0=np.repeat(pos0, NB),
+                            ctr0=np.repeat(ctr0, NB), hop_row=np.repeat(hop_row.reshape(-1), NB), hop_base=bases)
         count = plan.count.cpu().numpy().astype(np.int64).reshape(N, R)
         hop0 = ring.hop0.cpu().numpy().astype(np.int64)
         order = np.array([[h] + [b for b in range(NB) if b != h] for h in range(NB)], np.int64)[hop0]      # [N, 4]: rtwm/detector.py:46-52
@@ -247,7 +282,13 @@ class WatermarkIdentifier:
                 if live is not None:
                     live.stats["planned"] += total
                     if live.memo is not None:                               # candidates already known to fail are not decoded again
-                        k0, k1 = memo.pack(ks[pair_of], live.rows[row_h], live.epoch[row_h], live.w0[row_h] + start_h, ctr_h)
+                        a_h = live.w0[row_h] + start_h                      # absolute start
+                        org = origin[row_h // NB]                           # a stream with an origin: counter relative to its peak's estimate
+                        field = np.where(org >= 0, ctr_h - (org + (2 * a_h + FRAME_LEN) // (2 * FRAME_LEN)) + WIDE_DELTA, ctr_h)
+                        k0, k1 = np.empty(total, np.uint64), np.empty(total, np.uint64)
+                        for sel_, pack_ in ((org < 0, memo.pack), (org >= 0, memo.pack_abs)):
+                            if sel_.any():
+                                k0[sel_], k1[sel_] = pack_(ks[pair_of][sel_], live.rows[row_h][sel_], live.epoch[row_h][sel_], a_h[sel_], field[sel_])
                         k0_d, k1_d = t(k0.view(np.int64), np.int64), t(k1.view(np.int64), np.int64)
                         todo = np.flatnonzero(eng.memo_probe(live.memo, k0_d, k1_d).cpu().numpy() == 0)
                     live.stats["decoded"] += int(todo.size)
@@ -325,25 +366,27 @@ class LiveIdentifier(LiveTable):
 
     def __init__(self, identifier: WatermarkIdentifier, table, *, trace: bool = False, memo_slots: int = 0) -> None:
         self._id, self.table, self._trace = identifier, table, bool(trace)
-        self.check_memo(memo_slots, len(identifier.keys), table.window)
+        self.check_memo(memo_slots, len(identifier.keys), table.window, bool((table.origin_host < 0).any()))
         self.memo_slots = int(memo_slots)
         self._memo = None                                                   # engine.Memo, opened by the first push that needs it
         self._hop = None                                                    # the window's hop table, built by the first push
+        self._hop_at = None                                                 # the same as a hop row of es_plan_at_batch, built when first needed
         self._epoch = np.zeros(table.n, np.int64)                           # times each stream slot has been closed, mod 2^16
         self.stats = {"planned": 0, "decoded": 0, "skipped": 0}
 
     @staticmethod
-    def check_memo(slots: int, n_keys: int, window: int) -> None:
-        """Refuse what the memo's records cannot name: they hold 20 bits of key index and 16 of counter."""
+    def check_memo(slots: int, n_keys: int, window: int, relative: bool = True) -> None:
+        """Refuse what the memo's records cannot name: they hold 20 bits of key index and 16 of counter.  relative: some stream has
+        no counter origin -- its records hold the counter itself; one with an origin holds 0 .. 400 whatever the window."""
         if not slots:
             return
         memo.check_slots(slots)
         if n_keys > memo.MAX_KEYS:
             raise ValueError(f"{n_keys} keys: a live identifier with a memo takes at most {memo.MAX_KEYS} keys (memo_slots=0 takes any number)")
         C = -(-int(window) // FRAME_LEN) + WIDE_DELTA + 1
-        if C > memo.MAX_COUNTERS:
+        if relative and C > memo.MAX_COUNTERS:
             raise ValueError(f"window of {int(window)} samples: its candidates reach counter ceil(window / 1215) + 200 = {C - 1}, the memo's records "
-                             f"hold counters below {memo.MAX_COUNTERS} (use a shorter window_s, or memo_slots=0)")
+                             f"hold counters below {memo.MAX_COUNTERS} (use a shorter window_s, memo_slots=0, or give every stream its counter origin ctr0)")
 
     @property
     def fs_target(self) -> int:
@@ -353,7 +396,8 @@ class LiveIdentifier(LiveTable):
         """chunks[i], 1-D int16 or float32 at the rate its stream was opened with, continues stream streams[i] (None: one chunk per open
         stream, in order) -> per chunk a list of len(keys) entries, a KeyMatch or None; with trace=True (matches, traces) as
         identify_batch returns them.  Streams not named are not touched.  Raises ValueError before any GPU work for what
-        LiveMonitor.push refuses, and for a stream that would pass 2^48 samples while the memo is on."""
+        LiveMonitor.push refuses, and for a stream that would pass 2^48 samples while the memo is on.  A stream with a counter origin
+        (origin(stream)) is planned from absolute positions: pos0 = w0 and its origin; its hop row is rebuilt on the device each push."""
         from .monitor import push_arguments
         from .scan import SyncScan
         tab, N = self.table, len(self._id.keys)
@@ -369,29 +413,39 @@ class LiveIdentifier(LiveTable):
             eng = self._id.engine
             if self.memo_slots and self._memo is None:
                 self._memo = eng.open_memo(self.memo_slots)
-            if self._hop is None:                                           # depends on the keys and the window alone
+            if self._hop is None and (tab.origin_host[ids] < 0).any():      # depends on the keys and the window alone (streams without an origin)
                 self._hop = self._id._hop_table(-(-tab.window // FRAME_LEN) + WIDE_DELTA + 1)
             tick = eng.monitor_step(tab, ids, arrs)
             per_call = max(1, PAIR_BUDGET // (N * NB))                      # cut as identify_batch cuts its clips
             for a in range(0, ids.size, per_call):
                 part = tick.part(a, a + per_call)
                 s_rows = np.repeat(part.sid, NB)                            # the stream of each scan row
-                live = _LiveWalk(part.rows, part.offset, tab.base_host[s_rows] + part.offset, self._epoch[s_rows], self._hop, self._memo, self.stats,
-                                 self._trace)
+                live = _LiveWalk(part.rows, part.offset, tab.base_host[s_rows] + part.offset, self._epoch[s_rows], self._hop, tab.origin_host[part.sid],
+                                 self._hop_row0, -(-tab.window // FRAME_LEN) + 2 * WIDE_DELTA + 2, self._memo, self.stats, self._trace)
                 self._id._walk(SyncScan.from_monitor(part), out[a:a + per_call], traces[a:a + per_call], live)
         elif ids.size:
             self._id.engine.monitor_step(tab, ids, arrs)                    # no key: the streams still move on
         return (out, traces) if self._trace else out
+
+    def _hop_row0(self):
+        """The window's hop table (counters from 0) at the width es_plan_at_batch asks for, as its hop row: depends on the keys and the
+        window alone, built by the first push that mixes streams with and without an origin."""
+        if self._hop_at is None:
+            self._hop_at = self._id.engine.hop_window(self._id._keyring(), [0], -(-self.table.window // FRAME_LEN) + 2 * WIDE_DELTA + 2)
+        return self._hop_at
 
     def forget(self) -> None:
         """Empty the memo: the next push of every stream decodes its whole window again."""
         if self._memo is not None:
             self._memo.table.fill_(-1)
 
-    def add(self, n: int = 1, fs=None) -> np.ndarray:
+    def add(self, n: int = 1, fs=None, ctr0=None) -> np.ndarray:
         """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
-        fs_target)."""
-        ids = self._id.engine.add_monitor_streams(self.table, n, fs)
+        fs_target); ctr0: their counter origins, one or one per stream (None: no origin -- refused where the memo's records cannot
+        hold the window's counters)."""
+        from .monitor import origin_words
+        self.check_memo(self.memo_slots, len(self._id.keys), self.table.window, bool((origin_words(ctr0, int(n)) < 0).any()))
+        ids = self._id.engine.add_monitor_streams(self.table, n, fs, **({} if ctr0 is None else {"ctr0": ctr0}))
         self._epoch = np.concatenate((self._epoch, np.zeros(self.table.n - self._epoch.size, np.int64)))
         return ids
 

@@ -34,6 +34,20 @@ def pack(key_idx, row, epoch, start, ctr):
     return k | (r << _U(KEY_BITS)) | (e << _U(KEY_BITS + ROW_BITS)), s | (c << _U(START_BITS))
 
 
+DELTA_MAX = 400                             # a candidate lies within +-200 counters of its peak's estimate
+
+
+def pack_abs(key_idx, row, epoch, start, delta):
+    """pack() for the candidates of a stream with a counter origin: the 16-bit counter field holds
+    delta = ctr - ctr_est(start) + 200, with ctr_est(start) = origin + round(start / 1215) of the record's absolute start -- 0 .. 400 by
+    the planner's rules.  The origin is a function of (stream slot, epoch), both in the record, so the record still names one candidate
+    whatever the size of its counter.  A delta outside 0 .. 400 is a ValueError."""
+    d = np.asarray(delta, dtype=np.int64).reshape(-1)
+    if d.size and (d.min() < 0 or d.max() > DELTA_MAX):
+        raise ValueError(f"memo record: counter delta outside [0, {DELTA_MAX}] (a candidate more than 200 counters from its peak's estimate)")
+    return pack(key_idx, row, epoch, start, d)
+
+
 def unpack(k0, k1):
     """-> (key index, history row, epoch, absolute start, counter) int64 arrays of packed records."""
     k0, k1 = np.asarray(k0, _U), np.asarray(k1, _U)
@@ -104,4 +118,4 @@ def bump_epochs(epoch: np.ndarray, ids) -> bool:
     return bool(ids.size and (epoch[ids] == 0).any())
 
 
-__all__ = ["EMPTY", "MAX_KEYS", "MAX_COUNTERS", "MAX_POSITION", "MemoModel", "bump_epochs", "check_slots", "default_slots", "pack", "slot", "unpack"]
+__all__ = ["EMPTY", "MAX_KEYS", "MAX_COUNTERS", "MAX_POSITION", "MemoModel", "bump_epochs", "check_slots", "default_slots", "pack", "pack_abs", "slot", "unpack"]

@@ -188,6 +188,7 @@ class MonitorTable:
     corr_hist: object = None   # [4 S, H] float64 device
     fs_target: int = 0         # the rate the streams are conditioned to (0: not stated -- every stream arrives at it)
     rs: ResamplerTable | None = None        # rates, filters, tails and samples received of streams at other rates (None: all at fs_target)
+    origin_host: np.ndarray | None = None   # [S] int64 counter origin of each stream; -1: none, counters relative to the window
 
     @property
     def fs(self) -> np.ndarray:
@@ -204,19 +205,27 @@ class MonitorTable:
         return int(self.live.size)
 
 
+def origin_words(ctr0, n: int) -> np.ndarray:
+    """Counter origins (scan.counter_origins: None, one, or one per stream; checked) as the table holds them: int64 [n], -1 for None."""
+    from .scan import counter_origins
+    return np.array([-1 if v is None else v for v in counter_origins(ctr0, n, "stream")], np.int64).reshape(int(n))
+
+
 def host_table(n_streams: int, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), *, fs=None,
-               fs_target: int | None = None) -> MonitorTable:
+               fs_target: int | None = None, ctr0=None) -> MonitorTable:
     """The host half of a monitor table, checked; RxEngine.open_monitor adds the device arrays.  fs: the rate of every stream, or one per
-    stream (None: all at fs_target, which then need not be stated)."""
+    stream (None: all at fs_target, which then need not be stated).  ctr0: the counter origin of every stream, or one per stream (None, or
+    a None entry: no origin)."""
     hist = check_geometry(window, chunk_max, hist)
     S = int(n_streams)
     if S < 0:
         raise ValueError("negative number of streams")
+    origins = origin_words(ctr0, S)
     b = np.asarray(bands, dtype=np.int64).reshape(-1)
     if b.size != nat.ES_NBANDS or sorted(b.tolist()) != list(range(nat.ES_NBANDS)):
         raise ValueError("bands: the four band indices, each once")
     t = MonitorTable(int(window), int(chunk_max), hist, b.astype(np.uint8), np.zeros(S, np.int64), np.zeros(S, np.int64), np.ones(S, bool),
-                     fs_target=int(fs_target or 0))
+                     fs_target=int(fs_target or 0), origin_host=origins)
     if fs is not None:
         if not fs_target:
             raise ValueError("fs needs fs_target, the rate the streams are conditioned to")
@@ -277,7 +286,7 @@ def push_arguments(table: MonitorTable, target: int, chunks, streams=None, fs=No
     1-D int16 / float32 host arrays, their lengths at fs_target).  streams None: one chunk per open stream, in order.  fs= is a check,
     not a conversion: every named stream must have been opened at that rate.  A ValueError names what is refused: that, a chunk that is
     not 1-D, longer than chunk_max or (at another rate) finalizing more than chunk_max samples, a stream named twice, outside the table
-    or closed."""
+    or closed, and a stream with a counter origin whose samples would reach the end of the counter range."""
     chunks = list(chunks)
     if fs is not None and table.rs is None and int(fs) != target:
         raise ValueError(f"chunks at {fs} Hz: this monitor's streams arrive at fs_target = {target} Hz (open a stream with fs={fs} "
@@ -293,6 +302,10 @@ def push_arguments(table: MonitorTable, target: int, chunks, streams=None, fs=No
         raise ValueError("one chunk per stream is required")
     arrs = monitor_chunks(chunks, table.chunk_max, None if table.rs is None else table.rs.fs[ids] == target)
     lengths, _, _ = monitor_conditioned(table, ids, arrs)                   # a chunk that finalizes more than chunk_max: refused here
+    from .scan import check_counter_reach
+    for s, n in zip(ids.tolist(), (table.n_host[ids] + lengths).tolist()):
+        if table.origin_host[s] >= 0:
+            check_counter_reach(int(table.origin_host[s]), n, "stream")
     return ids, arrs, lengths
 
 
@@ -315,6 +328,12 @@ class LiveTable:
     def rate(self, stream: int) -> int:
         """The rate stream `stream` was opened at."""
         return int(self.table.fs[int(stream)]) or int(self.fs_target)
+
+    def origin(self, stream: int) -> int | None:
+        """The counter origin stream `stream` was opened with: its frame k carries counter origin + k (None: no origin, counters are
+        estimated relative to the window)."""
+        o = int(self.table.origin_host[int(stream)])
+        return None if o < 0 else o
 
     def window(self, stream: int) -> tuple[int, int]:
         """(w0, n): the samples of the stream, counted from its opening, that its last push looked at."""
@@ -422,12 +441,14 @@ class MonitorChain:
         inv[order] = np.arange(R)                                           # rows lie in launch order: back to input order, unwritten columns with them
         return out[torch.from_numpy(inv).to(self.device)], counts
 
-    def open_monitor(self, n_streams: int, *, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), fs=None) -> MonitorTable:
+    def open_monitor(self, n_streams: int, *, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), fs=None,
+                     ctr0=None) -> MonitorTable:
         """A table of n_streams fresh streams: windows of `window` samples (>= 2 * 1216), chunks of at most chunk_max samples, history
         rows of `hist` columns (default and minimum window + 1216 + chunk_max), row j of every stream on band bands[j]; fs: the rate
-        the streams arrive at, one or one per stream (None: the engine's).  Everything is allocated here; monitor_step only enqueues."""
+        the streams arrive at, one or one per stream (None: the engine's); ctr0: their counter origins, one or one per stream (None: no
+        origin; a host record, read by whoever plans the streams' candidates).  Everything is allocated here; monitor_step only enqueues."""
         import torch
-        t = host_table(n_streams, window, chunk_max, hist, bands, fs=fs, fs_target=self.fs)
+        t = host_table(n_streams, window, chunk_max, hist, bands, fs=fs, fs_target=self.fs, ctr0=ctr0)
         if t.rs is not None:
             self._resampler_device(t.rs)
         S, dev = t.n, self.device
@@ -438,13 +459,14 @@ class MonitorChain:
         t.corr_hist = torch.zeros((4 * S, t.hist), dtype=torch.float64, device=dev)
         return t
 
-    def add_monitor_streams(self, table: MonitorTable, n: int, fs=None) -> np.ndarray:
+    def add_monitor_streams(self, table: MonitorTable, n: int, fs=None, ctr0=None) -> np.ndarray:
         """n more fresh streams: closed slots are used first, lowest first, then the table grows (an allocation).  fs: their rate, one or
-        one per stream (None: the engine's).  -> their ids."""
+        one per stream (None: the engine's); ctr0: their counter origins, one or one per stream (None: no origin).  -> their ids."""
         import torch
         n, S = int(n), table.n
         target = table.fs_target or int(self.fs)
         rates = stream_rates(n, fs, target)                                # a rate that cannot be served: refused by name before anything changes
+        origins = origin_words(ctr0, n)                                    # ... and so is an origin that is no counter
         table.fs_target = target
         if table.rs is None and (rates != target).any():
             table.rs = resampler_host(np.full(S, target, np.int64), target)
@@ -458,7 +480,9 @@ class MonitorChain:
             table.band = torch.from_numpy(np.tile(table.bands, S + grow)).to(self.device)
             table.n_host, table.base_host = (np.concatenate((a, np.zeros(grow, np.int64))) for a in (table.n_host, table.base_host))
             table.live = np.concatenate((table.live, np.zeros(grow, bool)))
+            table.origin_host = np.concatenate((table.origin_host, np.full(grow, -1, np.int64)))
         table.live[ids] = True
+        table.origin_host[ids] = origins
         if table.rs is not None:
             rt = table.rs
             reuse = ids < rt.n
@@ -485,7 +509,7 @@ class MonitorChain:
             if table.rs is not None:
                 table.rs.tail[torch.from_numpy(ids).to(self.device)] = 0.0
                 table.rs.nin[torch.from_numpy(ids).to(self.device)] = 0
-        table.n_host[ids], table.base_host[ids], table.live[ids] = 0, 0, False
+        table.n_host[ids], table.base_host[ids], table.live[ids], table.origin_host[ids] = 0, 0, False, -1
         if table.rs is not None:
             table.rs.n_in_host[ids] = 0
 

@@ -15,6 +15,47 @@ PRE_L = 63               # chips of the sync template (utils.mseq_63)
 FRAME_LEN = 1215         # PRE_L + 128 header chips + 1024 code bits
 PEAK_LIMIT = 25          # rtwm/detector.py:108
 
+WIDE_DELTA = 200         # rtwm/detector.py:118: the widest counter window around a peak's estimate
+CTR_END = 1 << 32        # frame counters are 32-bit words: the header carries their low 16 bits, the payload all of them
+
+
+def counter_estimate(start: int, pos0: int = 0, ctr0: int = 0) -> int:
+    """The counter of the frame a peak lies on: the peak at `start` of a window whose first sample is absolute sample pos0
+    of a stream marked from counter ctr0 -> ctr0 + round((pos0 + start) / 1215), in integers (1215 is odd: no ties).  At pos0 = ctr0 = 0
+    it is rtwm/detector.py:117, round(start / 1215)."""
+    return int(ctr0) + (2 * (int(pos0) + int(start)) + FRAME_LEN) // (2 * FRAME_LEN)
+
+
+def counter_origins(ctr0, n: int, what: str = "clip") -> list:
+    """`ctr0` (None; one origin; or one per clip / stream, entries may be None) as a list of n entries, each None or an int in [0, 2^32).
+    A ValueError names what is refused: a negative origin, one of 2^32 or more, one that is not an integer, a wrong count."""
+    n = int(n)
+    if ctr0 is None or isinstance(ctr0, (int, np.integer)) or np.ndim(ctr0) == 0:
+        vals = [ctr0] * n
+    else:
+        vals = list(ctr0)
+        if len(vals) != n:
+            raise ValueError(f"ctr0 names {len(vals)} counter origins for {n} {what}s: give one origin, or one per {what}")
+    out = []
+    for v in vals:
+        if v is not None:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"ctr0 = {v!r}: a counter origin is an integer in [0, 2^32) (or None: counters relative to the {what})")
+            v = int(v)
+            if not 0 <= v < CTR_END:
+                raise ValueError(f"ctr0 = {v}: a counter origin is an integer in [0, 2^32) (counters that wrap are out of scope)")
+        out.append(v)
+    return out
+
+
+def check_counter_reach(origin, samples: int, what: str = "clip") -> None:
+    """Refuse an origin from which `samples` samples reach the end of the counter range: origin + ceil(samples / 1215) + 201 must not
+    pass 2^32 - 1 (the widest candidate window of the last frame stays inside the counters that exist)."""
+    if origin is not None and int(origin) + -(-int(samples) // FRAME_LEN) + WIDE_DELTA + 1 > CTR_END - 1:
+        raise ValueError(f"ctr0 = {int(origin)}: a {what} of {int(samples)} samples would reach counter ctr0 + ceil(samples / 1215) + 201 > 2^32 - 1 "
+                         "(counters that wrap past 2^32 are out of scope)")
+
+
 # Padded samples (sync rows x longest clip) of one launch over clips of unequal length.  A memory bound, not a tuned value: a padded row
 # sample costs 20 bytes on the device (float32 in, float64 y, float64 corr), so 2^26 of them are 1.3 GB.
 RAGGED_ROW_SAMPLES = 1 << 26

@@ -488,6 +488,32 @@ int es_plan_ragged_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* n
                          const int32_t* hdr_lo16_dev, int64_t P, const uint8_t* hop_dev, int64_t N, int C, uint8_t* cand_slot_dev,
                          uint32_t* cand_ctr_dev, int32_t* count_dev, int32_t* looked_dev, void* stream);
 
+/* es_plan_ragged_batch for rows that lie somewhere in a marked stream (a monitor's window, a clip cut out of a session): row r starts at
+ * absolute stream sample pos0_dev[r] (int64 [rows], 0 <= pos0 < 2^62; 0 for a clip) of a stream whose frame k carries counter
+ * ctr0_dev[r] + k (uint32 [rows]).  Line 117 of the reference (rtwm/detector.py: ctr_est = int(round(start / FRAME_LEN))) becomes
+ *     ctr_est = ctr0 + (2 * (pos0 + start) + 1215) / 2430                      in 64-bit integers;
+ * everything else of rtwm/detector.py:105-142 is es_plan_batch's: the low-16 header gate, the +-3 then +-200 windows, max(0, .), the hop
+ * gate, ES_PEAK_LIMIT peaks, ES_MAX_TRIES tries, the try order.  A counter above 2^32 - 1 is never a candidate.
+ * hop_dev [N][HR][C] uint8: HR hop rows per key, column 0 of row h is counter hop_base_dev[h] (uint32 [HR]) -- es_hop_window_batch; the pair
+ * (k, r) reads hop_dev[(k * HR + hop_row_dev[r]) * C + (ctr - hop_base_dev[hop_row_dev[r]])] (hop_row_dev int32 [rows]), every read guarded
+ * by 0 <= column < C: a counter outside the hop row is skipped.  A hop_row outside [0, HR) plans nothing for the row (count 0, looked 0).
+ * Host contract: hop_base = max(0, ctr0 + (2 * pos0 + 1215) / 2430 - 200) for every row that reads the hop row; with
+ * C >= ceil(T_max / 1215) + 402 (else ES_EINVAL, as HR < 1) the row then covers every counter the rules reach from a row of at most T_max
+ * samples.  With pos0 = ctr0 = 0, one hop row and base 0 the outputs are es_plan_ragged_batch's.  A refused call enqueues nothing;
+ * rows * N == 0 is ES_OK.  Outputs as es_plan_batch.  Needs no tables, only enqueues.                                              */
+int es_plan_at_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeaks_dev, const uint8_t* rowband_dev, const int32_t* hdr_base_dev,
+                     int64_t rows, const int32_t* len_dev, int T_max, const uint8_t* hdr_ok_dev, const int32_t* hdr_lo16_dev, int64_t P,
+                     const uint8_t* hop_dev, int64_t N, int C, const int64_t* pos0_dev, const uint32_t* ctr0_dev, const int32_t* hop_row_dev,
+                     const uint32_t* hop_base_dev, int HR, uint8_t* cand_slot_dev, uint32_t* cand_ctr_dev, int32_t* count_dev,
+                     int32_t* looked_dev, void* stream);
+
+/* The hop rows of es_plan_at_batch, filled on the device: hop_dev[(k * HR + h) * C + col] = band of counter hop_base_dev[h] + col under
+ * key k, one lane per entry -- choose_band (rtwm/utils.py:27-36) from the ring's HMAC pad states, as es_schedule_keyed_batch with
+ * pn_rows_dev == NULL, without a list of (key, counter) records to upload.  A counter past 2^32 - 1 gets 0xFF, which matches no band.
+ * hop_base_dev [HR] uint32.  N * HR * C == 0 is ES_OK; a negative count or a null pointer with work to do is ES_EINVAL.  Only enqueues. */
+int es_hop_window_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const uint32_t* hop_base_dev, int64_t HR, int64_t C, uint8_t* hop_dev,
+                        void* stream);
+
 /* ---- the transmit side for many keys: clips of unequal length, each marked under its own key, in one launch sequence ----------
  * es_aead_seal_batch with the ChaCha20 key of ring row key_dev[i] (read as es_aead_check_keyed_batch reads it) in place of key32_host:
  * SecureChannel.seal (rtwm/crypto.py:33-37) per (key, blob), what WatermarkEmbedder._build_payload puts into a frame

@@ -10,6 +10,9 @@ engine's stream and is synchronised before the next starts: a figure is what a c
 candidates decoded per tick (each is four list decodes), and whether all three gave the same answers.
 
     python tools/live_identify_tick.py --ticks 30 --out profiles/live_identify_tick.json --tag <commit>
+
+--ctr0 C: the streams of (a) and (b) are opened with counter origins C, C + 1000, C + 2000, ... -- planned from absolute
+positions, their hop rows rebuilt on the device each push -- and (c) is given the counter of the frame each window starts in.
 """
 import argparse
 import json
@@ -52,6 +55,7 @@ def main() -> None:
     ap.add_argument("--list-size", type=int, default=8)
     ap.add_argument("--ticks", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ctr0", type=int, default=None, help="open the streams with counter origins ctr0, ctr0 + 1000, ...")
     ap.add_argument("--out", default=None)
     ap.add_argument("--tag", default="")
     args = ap.parse_args()
@@ -63,13 +67,15 @@ def main() -> None:
     xs = (0.1 * rng.standard_normal((S, fill * fill_chunk + (args.warmup + args.ticks) * chunk))).astype(np.float32)
     keys = [rng.bytes(32) for _ in range(args.keys)]
     ident = WatermarkIdentifier(keys, fs_target=FS, list_size=args.list_size, engine=eng)
-    with_memo = ident.open_streams(S, window_s=args.window_s, chunk_max=fill_chunk)
-    without = ident.open_streams(S, window_s=args.window_s, chunk_max=fill_chunk, memo_slots=0)
+    origin = {} if args.ctr0 is None else {"ctr0": [args.ctr0 + 1000 * s for s in range(S)]}
+    with_memo = ident.open_streams(S, window_s=args.window_s, chunk_max=fill_chunk, **origin)
+    without = ident.open_streams(S, window_s=args.window_s, chunk_max=fill_chunk, memo_slots=0, **origin)
     at = 0
     for _ in range(fill):
         with_memo.push([x[at: at + fill_chunk] for x in xs]); without.push([x[at: at + fill_chunk] for x in xs])
         at += fill_chunk
     ev = {k: ([], [], []) for k in ("memo", "no_memo", "identify_batch")}
+    skipped = []
     same = True
     for t in range(args.warmup + args.ticks):
         chunks = [x[at: at + chunk] for x in xs]
@@ -77,8 +83,13 @@ def main() -> None:
         b, eb, wb = timed(lambda: without.push(chunks), stream)
         at += chunk
         w0, n = with_memo.window(0)
-        c, ec, wc = timed(lambda: ident.identify_batch([x[w0:n] for x in xs], FS), stream)
-        same = same and a == b == c
+        # a window cut at w0 = 1216 k of a stream marked from C starts k samples into the frame of counter C + k: the clip call has no
+        # pos0, so with origins (c) is timed but walks slightly other candidates than the pushes, and only (a) == (b) is compared
+        clip_origin = {} if args.ctr0 is None else {"ctr0": [args.ctr0 + 1000 * s + (2 * w0 + 1215) // 2430 for s in range(S)]}
+        c, ec, wc = timed(lambda: ident.identify_batch([x[w0:n] for x in xs], FS, **clip_origin), stream)
+        same = same and a == b and (args.ctr0 is not None or b == c)
+        if t >= args.warmup:
+            skipped.append(with_memo.stats["skipped"])
         if t >= args.warmup:
             for k, e, w, d in (("memo", ea, wa, with_memo.stats["decoded"]), ("no_memo", eb, wb, without.stats["decoded"]),
                                ("identify_batch", ec, wc, without.stats["planned"])):      # (c) decodes what (b) decodes: the same walk
@@ -86,7 +97,7 @@ def main() -> None:
     row = {"streams": S, "keys": args.keys, "window_s": args.window_s, "chunk_s": args.chunk_s, "list_size": args.list_size,
            "memo_slots": with_memo.memo_slots, "push_memo": stats(*ev["memo"]), "push_no_memo": stats(*ev["no_memo"]),
            "identify_batch": stats(*ev["identify_batch"]), "planned_per_tick_median": statistics.median(ev["identify_batch"][2]),
-           "same_answers": bool(same), "device": torch.cuda.get_device_name(eng.device), "tag": args.tag}
+           "skipped_per_tick_median": statistics.median(skipped), "ctr0": args.ctr0, "same_answers": bool(same), "device": torch.cuda.get_device_name(eng.device), "tag": args.tag}
     print(json.dumps(row), flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
