@@ -100,8 +100,8 @@ def test_sealer_reproduces_crafted_blobs(engine, vectors):
 
 
 # -------------------------------------------------------------------------------------------------------- grid-stride loops
-def _mixed_block(rng, vs, n=PERIOD):
-    """n rows under KEY: the crafted vectors, then sealed rows with per-row counters, some sealed with a wrong magic or
+def _mixed_block(rng, vs, n=PERIOD, key=KEY):
+    """n rows under `key`: its crafted vectors vs, then sealed rows with per-row counters, some sealed with a wrong magic or
     checked against a wrong counter, some with one flipped bit.  -> (blobs, clean blobs, plaintexts, ctrs)."""
     k = len(vs)
     ctr = rng.integers(0, M32, n).astype(np.int64)
@@ -112,7 +112,7 @@ def _mixed_block(rng, vs, n=PERIOD):
     plain[:, 8:] = rng.integers(0, 256, (n, 19), dtype=np.uint8)
     nonces = rng.integers(0, 256, (n, 12), dtype=np.uint8)
     clean = np.empty((n, 55), np.uint8)
-    clean[k:] = seal_rows(KEY, nonces[k:], plain[k:])
+    clean[k:] = seal_rows(key, nonces[k:], plain[k:])
     for i, v in enumerate(vs):
         clean[i] = np.frombuffer(v.blob, np.uint8); plain[i] = np.frombuffer(v.plain, np.uint8); ctr[i] = v.ctr
     blobs = clean.copy()

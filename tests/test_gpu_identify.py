@@ -70,27 +70,31 @@ def _pad_states(key):
     return ip, op
 
 
-def test_ring_rows_equal_host_derivation(engine):
-    from echoseal_amd import _native as nat
+def check_ring_row(row, key, k):
+    """One key-ring row (uint8 [ES_KEYRING_BYTES], host) against the host derivation of `key`, field by field; k names the row."""
     from echoseal_amd.crypto import SecureChannel
     from echoseal_amd.primitives import _aes128_round_keys
     from echoseal_amd.utils import band_index
+    sec = SecureChannel(key)
+    assert row[0:32].tobytes() == sec._aead._key, k
+    rk = row[32:208].view(np.uint32)
+    assert np.array_equal(rk[:4], np.frombuffer(sec._prng.sub_key, ">u4")), k
+    assert np.array_equal(rk, np.frombuffer(_aes128_round_keys(sec._prng.sub_key).tobytes(), ">u4")), k
+    ip, op = _pad_states(key)
+    assert row[208:240].view(np.uint32).tolist() == ip and row[240:272].view(np.uint32).tolist() == op, k
+    assert row[272:288].tobytes() == np.packbits(sec.pn_bits(0, 128)).tobytes(), k
+    assert row[288] == band_index(key, 0) and not row[289:].any(), k
+
+
+def test_ring_rows_equal_host_derivation(engine):
+    from echoseal_amd import _native as nat
     assert _compress(_IV, b"abc\x80" + bytes(59) + b"\x18") == [int.from_bytes(hashlib.sha256(b"abc").digest()[4 * i:4 * i + 4], "big") for i in range(8)]
     keys = _keys()
     kr = engine.keyring(keys)
     ring = kr.ring.cpu().numpy()
     assert ring.shape == (N_KEYS, nat.ES_KEYRING_BYTES) and kr.n == N_KEYS
     for k, key in enumerate(keys):
-        sec = SecureChannel(key)
-        row = ring[k]
-        assert row[0:32].tobytes() == sec._aead._key, k
-        rk = row[32:208].view(np.uint32)
-        assert np.array_equal(rk[:4], np.frombuffer(sec._prng.sub_key, ">u4")), k
-        assert np.array_equal(rk, np.frombuffer(_aes128_round_keys(sec._prng.sub_key).tobytes(), ">u4")), k
-        ip, op = _pad_states(key)
-        assert row[208:240].view(np.uint32).tolist() == ip and row[240:272].view(np.uint32).tolist() == op, k
-        assert row[272:288].tobytes() == np.packbits(sec.pn_bits(0, 128)).tobytes(), k
-        assert row[288] == band_index(key, 0) and not row[289:].any(), k
+        check_ring_row(ring[k], key, k)
     assert np.array_equal(kr.hop0.cpu().numpy(), ring[:, 288]) and np.array_equal(kr.hdr_pn.cpu().numpy(), ring[:, 272:288])
     with pytest.raises(ValueError):
         engine.keyring([bytes(31)])
