@@ -1047,6 +1047,54 @@ int es_hop_window_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const u
     return es_launch_hop_window(ctx, ring_dev, N, hop_base_dev, HR, C, hop_dev, (hipStream_t)stream);
 }
 
+// What both acquisition calls refuse and when they have nothing to do: -> ES_EINVAL, ES_OK with *work = false, or ES_OK with *work = true
+// and the exact grid of one wave per (record, tile of 64 high halves) within 2^31 - 1 blocks.
+static int acquire_span(es_ctx* ctx, const char* who, int64_t P, int64_t ctr_lo, int64_t ctr_hi, bool* work)
+{
+    *work = false;
+    const char* why = P < 0 ? ": negative count"
+                      : (ctr_lo < 0 || ctr_hi > ((int64_t)1 << 32) || ctr_lo > ctr_hi) ? ": the span must lie in [0, 2^32] with ctr_lo <= ctr_hi" : nullptr;
+    if (!why) {
+        const int64_t H = ((ctr_hi + 65535) >> 16) - (ctr_lo >> 16), TW = ((H + 31) / 32 + 1) / 2;
+        if (P == 0 || H == 0) return ES_OK;
+        if (P > (((int64_t)1 << 33) - 4) / TW) why = ": more than 2^31 - 1 blocks of four (record, 64 high halves) tiles in one call";
+    }
+    if (why) {
+        ctx->err = std::string(who) + why;
+        return ES_EINVAL;
+    }
+    *work = true;
+    return ES_OK;
+}
+
+int es_acquire_mask_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* ok_dev, const int32_t* lo16_dev,
+                          const uint8_t* band_dev, int64_t P, int64_t ctr_lo, int64_t ctr_hi, uint32_t* mask_dev, int32_t* count_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (N < 0) return fail(ctx, ES_EINVAL, "es_acquire_mask_batch: negative count");
+    bool work;
+    if (acquire_span(ctx, "es_acquire_mask_batch", P, ctr_lo, ctr_hi, &work) != ES_OK) return ES_EINVAL;
+    if (!work) return ES_OK;
+    if (N < 1) return fail(ctx, ES_EINVAL, "es_acquire_mask_batch: records but an empty key ring");
+    if (!ring_dev || !key_dev || !ok_dev || !lo16_dev || !band_dev || !mask_dev || !count_dev)
+        return fail(ctx, ES_EINVAL, "es_acquire_mask_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_acquire_mask(ctx, ring_dev, N, key_dev, ok_dev, lo16_dev, band_dev, P, ctr_lo, ctr_hi, mask_dev, count_dev, (hipStream_t)stream);
+}
+
+int es_acquire_list_batch(es_ctx* ctx, const uint32_t* mask_dev, const int32_t* lo16_dev, int64_t P, int64_t ctr_lo, int64_t ctr_hi,
+                          const int64_t* base_dev, int64_t total, int32_t* cand_rec_dev, uint32_t* cand_ctr_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (total < 0) return fail(ctx, ES_EINVAL, "es_acquire_list_batch: negative count");
+    bool work;
+    if (acquire_span(ctx, "es_acquire_list_batch", P, ctr_lo, ctr_hi, &work) != ES_OK) return ES_EINVAL;
+    if (!work || total == 0) return ES_OK;
+    if (!mask_dev || !lo16_dev || !base_dev || !cand_rec_dev || !cand_ctr_dev) return fail(ctx, ES_EINVAL, "es_acquire_list_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_acquire_list(ctx, mask_dev, lo16_dev, P, ctr_lo, ctr_hi, base_dev, total, cand_rec_dev, cand_ctr_dev, (hipStream_t)stream);
+}
+
 // what both memo calls refuse: a table that is not a power of two of entries, a count the uint32 claim words cannot index
 static int memo_refusal(es_ctx* ctx, const char* who, int64_t slots, int64_t n)
 {

@@ -275,6 +275,11 @@ int es_launch_plan_at(es_ctx* ctx, const int32_t* peaks, const int32_t* npeaks, 
                       uint32_t* cand_ctr, int32_t* count, int32_t* looked, hipStream_t st);
 int es_launch_hop_window(es_ctx* ctx, const uint8_t* ring, int64_t N, const uint32_t* hop_base, int64_t HR, int64_t C, uint8_t* hop,
                          hipStream_t st);
+/* acquisition (es_keyring.hip): the span is checked by the entry points, 0 <= ctr_lo <= ctr_hi <= 2^32, and so is the grid */
+int es_launch_acquire_mask(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* ok, const int32_t* lo16,
+                           const uint8_t* band, int64_t P, int64_t ctr_lo, int64_t ctr_hi, uint32_t* mask, int32_t* count, hipStream_t st);
+int es_launch_acquire_list(es_ctx* ctx, const uint32_t* mask, const int32_t* lo16, int64_t P, int64_t ctr_lo, int64_t ctr_hi, const int64_t* base,
+                           int64_t total, int32_t* cand_rec, uint32_t* cand_ctr, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

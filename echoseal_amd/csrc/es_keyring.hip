@@ -4,6 +4,8 @@
 // (rtwm/utils.py:86-88: BLAKE2s), the host-side expansion of es_sched.hip, and _scan_band_multi_frame's candidate loop
 // (rtwm/detector.py:105-142) -- also for rows that lie somewhere in a stream marked from any counter (es_plan_at_kernel: line 117 with the
 // row's absolute position and the stream's counter origin), over hop windows filled here (es_hop_window_kernel: rtwm/utils.py:27-36).
+// Where nobody knows the origin, the low-16 gate of lines 122-127 is taken over a span of the whole counter range instead of an estimate's
+// window (es_acquire_mask_kernel, es_acquire_count_kernel, es_acquire_list_kernel).
 //
 // Integer work throughout.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
@@ -293,6 +295,79 @@ __global__ __launch_bounds__(256) void es_plan_at_kernel(const int32_t* __restri
                    looked_p, ((g_ci64*)pos0_p)[row], (long long)((g_cu32*)ctr0_p)[row], (long long)((g_cu32*)hbase_p)[h], k * HR + h);
 }
 
+// ---- acquisition: every counter of a 32-bit span a decoded header may belong to (es_acquire_mask_batch, es_acquire_list_batch) ----
+// A record p is one (key, fitting peak) with its header decode; its candidates are the counters (h << 16) | lo16[p] of the span that hop to
+// the band the peak was found in.  Row p of the mask has one bit per high half h, bit h - h0 of [W] words; a wave covers one tile of 64 high
+// halves (two words) of one record, TW = ceil(W / 2) tiles per record, four waves per workgroup.
+
+// One lane per (record, h): the HMAC of its counter where the record is live and the counter lies in [ctr_lo, ctr_hi).  Both words of the
+// tile are written whatever they hold.
+__global__ __launch_bounds__(256) void es_acquire_mask_kernel(const uint8_t* __restrict__ ring_p, long long N, const int32_t* __restrict__ key_p,
+        const uint8_t* __restrict__ ok_p, const int32_t* __restrict__ lo16_p, const uint8_t* __restrict__ band_p, long long P, long long ctr_lo,
+        long long ctr_hi, long long h0, int H, int W, int TW, uint32_t* __restrict__ mask_p)
+{
+    const long long g = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);         // wave-uniform
+    if (g >= P * TW) return;
+    const long long p = g / TW;
+    const int tile = (int)(g - p * TW), lane = threadIdx.x & 63, j = tile * 64 + lane;
+    const long long key = ((g_ci32*)key_p)[p];
+    const int lo16 = ((g_ci32*)lo16_p)[p];
+    const bool live = ((g_cu8*)ok_p)[p] != 0 && key >= 0 && key < N && lo16 >= 0 && lo16 <= 0xFFFF;
+    const long long c = ((h0 + j) << 16) | (long long)(lo16 & 0xFFFF);
+    bool v = live && j < H && c >= ctr_lo && c < ctr_hi;                                        // (ctr_hi <= 2^32: c is a 32-bit counter)
+    if (v) {
+        g_cu32* row = (g_cu32*)(ring_p + key * ES_KEYRING_BYTES);
+        uint32_t b = 0;
+        ES_HOP_BAND(b, row, (uint32_t)c);
+        v = b == ((g_cu8*)band_p)[p];
+    }
+    const unsigned long long m = __ballot(v);
+    g_u32* out = (g_u32*)mask_p + p * W;
+    if (lane == 0) out[2 * tile] = (uint32_t)m;                                                 // (2 * tile < W by TW = ceil(W / 2))
+    if (lane == 32 && 2 * tile + 1 < W) out[2 * tile + 1] = (uint32_t)(m >> 32);
+}
+
+// count[p] = set bits of mask row p: one wave per record over the words the launch before wrote (integer sums: the same in any order)
+__global__ __launch_bounds__(256) void es_acquire_count_kernel(const uint32_t* __restrict__ mask_p, long long P, int W, int32_t* __restrict__ count_p)
+{
+    const long long p = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);         // wave-uniform
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    g_cu32* row = (g_cu32*)mask_p + p * W;
+    uint32_t n = 0;
+    #pragma unroll 1
+    for (int w = lane; w < W; w += 64) n += (uint32_t)__popc(row[w]);
+    n = es_wave_incl_scan_u32(n);
+    if (lane == 63) ((g_i32*)count_p)[p] = (int32_t)n;
+}
+
+// The set bits of every record with base[p] >= 0 as (record, counter) entries base[p] + i, i ascending with h.  A wave owns one tile: its
+// offset in the record's list is the popcount of the row's words before the tile, which it sums itself (no wave waits for another); inside
+// the tile the order comes from the ballot.  An entry at or past `total` is not written.
+__global__ __launch_bounds__(256) void es_acquire_list_kernel(const uint32_t* __restrict__ mask_p, const int32_t* __restrict__ lo16_p, long long P,
+        long long h0, int W, int TW, const long long* __restrict__ base_p, long long total, int32_t* __restrict__ rec_p, uint32_t* __restrict__ ctr_p)
+{
+    const long long g = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);         // wave-uniform
+    if (g >= P * TW) return;
+    const long long p = g / TW;
+    const int tile = (int)(g - p * TW), lane = threadIdx.x & 63;
+    const long long base = ((g_ci64*)base_p)[p];
+    if (base < 0) return;
+    g_cu32* row = (g_cu32*)mask_p + p * W;
+    uint32_t before = 0;
+    #pragma unroll 1
+    for (int w = lane; w < 2 * tile; w += 64) before += (uint32_t)__popc(row[w]);
+    before = (uint32_t)es_wave_read_lane((int)es_wave_incl_scan_u32(before), 63);
+    const int wi = 2 * tile + (lane >> 5);
+    const bool v = wi < W && ((row[wi < W ? wi : 0] >> (lane & 31)) & 1u) != 0;
+    const unsigned long long m = __ballot(v);
+    const long long at = base + before + lanes_below(m);
+    if (v && at < total) {
+        ((g_i32*)rec_p)[at] = (int32_t)p;
+        ((g_u32*)ctr_p)[at] = (uint32_t)(((h0 + tile * 64 + lane) << 16) | (long long)(((g_ci32*)lo16_p)[p] & 0xFFFF));
+    }
+}
+
 }  // namespace
 
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
@@ -344,4 +419,23 @@ int es_launch_hop_window(es_ctx* ctx, const uint8_t* ring, int64_t N, const uint
 {
     return es_launch(ctx, es_hop_window_kernel, es_grid((long long)N * HR * C, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, hop_base,
                      (long long)HR, (long long)C, hop);
+}
+
+// the exact grids of the acquisition kernels (one wave per tile of 64 high halves, four waves per block): no cap, the entry points refuse a
+// call whose grid would pass 2^31 - 1 blocks
+int es_launch_acquire_mask(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint8_t* ok, const int32_t* lo16,
+                           const uint8_t* band, int64_t P, int64_t ctr_lo, int64_t ctr_hi, uint32_t* mask, int32_t* count, hipStream_t st)
+{
+    const long long h0 = ctr_lo >> 16, H = ((ctr_hi + 65535) >> 16) - h0, W = (H + 31) / 32, TW = (W + 1) / 2;
+    if (const int rc = es_launch(ctx, es_acquire_mask_kernel, (unsigned)((P * TW + 3) / 4), 256, 0, st, ring, (long long)N, key, ok, lo16, band,
+                                 (long long)P, (long long)ctr_lo, (long long)ctr_hi, h0, (int)H, (int)W, (int)TW, mask)) return rc;
+    return es_launch(ctx, es_acquire_count_kernel, (unsigned)((P + 3) / 4), 256, 0, st, (const uint32_t*)mask, (long long)P, (int)W, count);
+}
+
+int es_launch_acquire_list(es_ctx* ctx, const uint32_t* mask, const int32_t* lo16, int64_t P, int64_t ctr_lo, int64_t ctr_hi, const int64_t* base,
+                           int64_t total, int32_t* cand_rec, uint32_t* cand_ctr, hipStream_t st)
+{
+    const long long h0 = ctr_lo >> 16, H = ((ctr_hi + 65535) >> 16) - h0, W = (H + 31) / 32, TW = (W + 1) / 2;
+    return es_launch(ctx, es_acquire_list_kernel, (unsigned)((P * TW + 3) / 4), 256, 0, st, mask, lo16, (long long)P, h0, (int)W, (int)TW,
+                     (const long long*)base, (long long)total, cand_rec, cand_ctr);
 }

@@ -22,6 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._native import NativeError
+from .acquire import FULL_SPAN, Acquired, check_max_records, check_span, origin_of, record_order
 from .crypto import SecureChannel
 from .monitor import LiveTable
 from .polar_fast import N_DEFAULT
@@ -91,6 +92,7 @@ class WatermarkDetector:
         if self._hdr_pn_sy.size != HDR_L:
             raise RuntimeError(f"Header PN length {self._hdr_pn_sy.size} != expected {HDR_L}")
         self._engine = engine
+        self._ring = None                                   # (engine, one-row key ring of this detector's key): acquire
         self._trace: list[tuple[int, int, int]] | None = None   # set to [] to record (band_lo, peak, ctr) tries
         self._hdr_trace: list[tuple[float, float, float]] | None = None   # set to [] to record every header decode of a scan
 
@@ -213,6 +215,88 @@ class WatermarkDetector:
                         break
             out.append(ok)
         return out
+
+    # ------------------------------------------------------------------ acquisition
+    def acquire(self, audio: np.ndarray, fs_in: int, *, span=FULL_SPAN, max_records: int = 8) -> Acquired | None:
+        return self.acquire_batch([audio], fs_in, span=span, max_records=max_records)[0]
+
+    def acquire_batch(self, clips, fs_in, *, span=FULL_SPAN, max_records: int = 8) -> list:
+        """Find a frame of this detector's key in each clip without knowing the clip's counter origin, and with it the origin: -> per
+        clip None, or an Acquired whose ctr0 makes verify(clip, fs_in, ctr0=ctr0) the ordinary verify.  Where verify looks for a peak's
+        counter around an estimate, this looks at every counter of `span` (default: all 2^32) that carries the low 16 bits the peak's
+        header decoded to and hops to the band the peak was found in -- about a quarter of 65 536 per header over the full span.  The
+        front is verify_batch's (cut_launches, one sync and one header decode per launch, mixed rates and int16 included); per launch
+        ONE es_acquire_mask_batch and ONE es_acquire_list_batch enumerate the candidates of all its clips' records (at most max_records
+        per clip, acquire.record_order); the walk is clip by clip in input order, record by record, counters ascending, and stops at the
+        first candidate _accept takes -- with its session-nonce bookkeeping, and each try appended to _trace.  An empty span: all None,
+        no GPU work.  ValueError before any engine exists: a span outside [0, 2^32] or reversed, max_records < 1."""
+        span, max_records = check_span(span), check_max_records(max_records)
+        fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        out: list = [None] * len(clips)
+        if span[0] == span[1]:
+            return out
+        order = self._band_order()
+        plans: dict[int, tuple] = {}
+        for la in cut_launches(clips, fs_list, self.fs_target, len(order), self._conditioned):
+            scans = self._scan_prepare(la, order)
+            for i, plan in zip(la.idx, self._acquire_plan(scans, [0] * len(scans), span, max_records)):
+                plans[i] = plan
+        for i in sorted(plans):
+            out[i] = self._acquire_walk(*plans[i], self)
+        return out
+
+    def _key_ring(self):
+        """This detector's key as a ring of one row, derived once per engine."""
+        eng = self.engine
+        if self._ring is None or self._ring[0] is not eng:
+            self._ring = (eng, eng.keyring([self._band_key]))
+        return self._ring[1]
+
+    def _acquire_plan(self, scans: list, pos0: list, span, max_records: int) -> list:
+        """The candidates of every scan of one launch, by one mask and one list launch over all their records
+        -> per scan (scan, pos0, [header index j of each searched record], [its counters, ascending])."""
+        recs = [record_order(sc.hdr[0][sc.sel], sc.hdr[1][sc.sel], sc.rows[sc.sel], sc.starts[sc.sel], p0, max_records) if sc.sel.size else []
+                for sc, p0 in zip(scans, pos0)]
+        recs = [[int(sc.sel[k]) for k in r] for sc, r in zip(scans, recs)]     # places in the launch's header decode
+        flat = [(c, j) for c, r in enumerate(recs) for j in r]
+        ctrs: list = [np.zeros(0, np.int64)] * len(flat)
+        if flat:
+            eng = self.engine
+            lo16 = np.array([scans[c].hdr[1][j] for c, j in flat], np.int32)
+            band = np.array([self._band_id(scans[c].bands[int(scans[c].rows[j])]) for c, j in flat], np.uint8)
+            mask, count = eng.acquire_mask(self._key_ring(), np.zeros(len(flat), np.int32), np.ones(len(flat), np.uint8), lo16, band, span)
+            count = count.cpu().numpy().astype(np.int64)
+            base, total = np.cumsum(count) - count, int(count.sum())            # walk order: clip by clip, record by record
+            if total:
+                _, cc = eng.acquire_list(mask, lo16, span, base, total)
+                cc = cc.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+                ctrs = [cc[b:b + n] for b, n in zip(base.tolist(), count.tolist())]
+        out, at = [], 0
+        for sc, p0, r in zip(scans, pos0, recs):
+            out.append((sc, p0, r, ctrs[at:at + len(r)]))
+            at += len(r)
+        return out
+
+    def _acquire_walk(self, scan, pos0: int, recs: list, ctrs: list, walker) -> Acquired | None:
+        """Decode one clip's candidates in try order, in chunks of _pair_cap(), and walk them with `walker` (its _trace, its
+        session_nonce) up to the first it accepts."""
+        tries = [(j, int(c)) for j, cs in zip(recs, ctrs) for c in cs]
+        cap, tried = self._pair_cap(), 0
+        for k in range(0, len(tries), cap):
+            part = tries[k:k + cap]
+            for (j, ctr), blobs in zip(part, self._decode_pairs(scan.src, [j for j, _ in part], [c for _, c in part])):
+                band, start = scan.bands[int(scan.rows[j])], int(scan.starts[j])
+                tried += 1
+                if walker._trace is not None:
+                    walker._trace.append((int(band[0]), start, ctr))
+                if walker._accept(blobs, ctr):
+                    blob = next(b for b in blobs if b is not None)
+                    try:
+                        plain = self.sec.open(blob)
+                    except Exception:
+                        plain = self._decrypt_blob_fallback(blob)[0] or blob
+                    return Acquired(origin_of(ctr, start, pos0), ctr, start, (int(band[0]), int(band[1])), blob, plain, len(recs), tried)
+        return None
 
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
                      ctr0=None) -> "LiveMonitor":
@@ -567,6 +651,50 @@ class LiveMonitor(LiveTable):
         for w in walkers:
             w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
         return det._verify_scans(scans, [list(range(len(scans)))], self._order, walkers)
+
+    def acquire_streams(self, streams) -> np.ndarray:
+        """The streams an acquire call names, checked on the host: None = every open stream without an origin; a named stream must be
+        open, named once and without an origin."""
+        from .monitor import monitor_ids
+        if streams is None:
+            return np.flatnonzero(self.table.live & (self.table.origin_host < 0))
+        ids = monitor_ids(self.table, streams)
+        for s in ids.tolist():
+            if self.table.origin_host[s] >= 0:
+                raise ValueError(f"stream {s} already has a counter origin ({int(self.table.origin_host[s])}): there is nothing to acquire")
+        return ids
+
+    def acquire(self, streams=None, *, span=FULL_SPAN, max_records: int = 8) -> list:
+        """WatermarkDetector.acquire on the current window of each named stream (None: every open stream without an origin), with no new
+        samples: -> per stream None or an Acquired.  The window's absolute position is known, so a found frame gives the stream's counter
+        origin, ctr0 = ctr - round((w0 + start) / 1215): it is stored (origin(s) answers it) and later pushes plan from absolute positions
+        as for a stream opened with it -- unless the samples received so far would reach the end of the counter range from
+        it (scan.check_counter_reach), in which case the result is returned and the stream stays without an origin.  Each stream is
+        walked by its own walker: the session nonce is the stream's, and with trace=True traces(s) then holds the tries of this call.
+        ValueError before any GPU work: a span outside [0, 2^32] or reversed, max_records < 1, a stream that is closed, named twice,
+        outside the table or has an origin already.  An empty span: all None, no GPU work."""
+        span, max_records = check_span(span), check_max_records(max_records)
+        ids = self.acquire_streams(streams)
+        if not ids.size or span[0] == span[1]:
+            return [None] * int(ids.size)
+        from .scan import SyncScan
+        det, tab = self._det, self.table
+        tick = det.engine.monitor_step(tab, ids, [np.zeros(0, np.float32)] * int(ids.size))         # no samples: the windows as they stand
+        scans = det._scans_of(SyncScan.from_monitor(tick), self._order, tab.bands)
+        pos0 = [int(tab.base_host[s] + tick.offset[tick.nb * i]) for i, s in enumerate(ids.tolist())]    # as push computes it
+        out = []
+        for s, plan in zip(ids.tolist(), det._acquire_plan(scans, pos0, span, max_records)):
+            w = self._walker(s)
+            w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
+            acq = det._acquire_walk(*plan, w)
+            if acq is not None:
+                try:
+                    check_counter_reach(acq.ctr0, int(tab.n_host[s]), "stream")
+                    tab.origin_host[s] = acq.ctr0
+                except ValueError:
+                    pass
+            out.append(acq)
+        return out
 
     def session_nonce(self, stream: int) -> bytes | None:
         """The session nonce stream `stream` is locked to (None: nothing accepted yet)."""

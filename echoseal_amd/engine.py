@@ -645,6 +645,42 @@ class RxEngine(TxChain, MonitorChain):
                   "es_hop_window_batch")
         return hop
 
+    def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):
+        """Which counters of `span` each header record may belong to (es_acquire_mask_batch; acquire.mask_model is the host twin).
+        Record p = (ring row key_idx[p] int32, ok[p] uint8, lo16[p] int32, band[p] uint8), as one header call gives them
+        -> (mask int32 [P, W] holding the uint32 words, count int32 [P]); bit h - h0 of row p: (h << 16) | lo16[p] is a candidate."""
+        from .acquire import span_words
+        lo, hi = span
+        _, _, W = span_words(span)
+        kd, okd = self._dev(key_idx, torch.int32).reshape(-1), self._dev(ok, torch.uint8).reshape(-1)
+        lod, bd = self._dev(lo16, torch.int32).reshape(-1), self._dev(band, torch.uint8).reshape(-1)
+        P = kd.numel()
+        if not (okd.numel() == lod.numel() == bd.numel() == P):
+            raise ValueError("key_idx, ok, lo16, band: one entry per record")
+        mask = torch.empty((P, W), dtype=torch.int32, device=self.device)
+        count = torch.empty(P, dtype=torch.int32, device=self.device)
+        nat.check(self._ctx, self._lib.es_acquire_mask_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(okd), _ptr(lod), _ptr(bd), P,
+                                                             int(lo), int(hi), _ptr(mask), _ptr(count), self._stream()), "es_acquire_mask_batch")
+        return mask, count
+
+    def acquire_list(self, mask: torch.Tensor, lo16, span, base, total: int):
+        """The set bits of acquire_mask's rows as a flat list (es_acquire_list_batch): record p with base[p] >= 0 fills entries base[p] ..
+        of -> (cand_rec int32 [total], cand_ctr int32 [total] holding the uint32 counters), its counters ascending; base[p] < 0 skips
+        the record.  base (int64 [P]) and total are the host's choice, made from acquire_mask's counts."""
+        lo, hi = span
+        P, total = mask.shape[0], int(total)
+        from .acquire import span_words
+        if mask.dim() != 2 or mask.dtype != torch.int32 or mask.shape[1] != span_words(span)[2]:
+            raise ValueError("mask: the int32 [P, W] output of acquire_mask over the same span")
+        mask, lod, based = mask.contiguous(), self._dev(lo16, torch.int32).reshape(-1), self._dev(base, torch.int64).reshape(-1)
+        if lod.numel() != P or based.numel() != P or total < 0:
+            raise ValueError("lo16, base: one entry per record; total: an entry count")
+        rec = torch.empty(total, dtype=torch.int32, device=self.device)
+        ctr = torch.empty(total, dtype=torch.int32, device=self.device)
+        nat.check(self._ctx, self._lib.es_acquire_list_batch(self._ctx, _ptr(mask), _ptr(lod), P, int(lo), int(hi), _ptr(based), total, _ptr(rec),
+                                                             _ptr(ctr), self._stream()), "es_acquire_list_batch")
+        return rec, ctr
+
     def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
              hop: torch.Tensor, *, pos0=None, ctr0=None, hop_row=None, hop_base=None) -> PlanResult:
         """Counter candidates of every (key, row) in try order (es_plan_batch; the rules of _scan_band_multi_frame,

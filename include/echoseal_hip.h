@@ -514,6 +514,35 @@ int es_plan_at_batch(es_ctx* ctx, const int32_t* peaks_dev, const int32_t* npeak
 int es_hop_window_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const uint32_t* hop_base_dev, int64_t HR, int64_t C, uint8_t* hop_dev,
                         void* stream);
 
+/* ---- acquisition: the counters a decoded header may belong to, over a span of the whole 32-bit range -------------------------------
+ * Extends rtwm/detector.py:117-127 (ctr_est = int(round(start / FRAME_LEN)); the low-16 gate over ctr_est +- 200): where the caller does
+ * not know where in its stream a clip or a window lies, the estimate says nothing, and what is left of lines 122-127 is the header's low
+ * half and the hop (rtwm/utils.py:27-36) -- over every counter there is.  A record p is one (key, fitting peak) pair with its header decode,
+ * as one es_header_at_batch gives it: ring row key_dev[p] (int32), ok_dev[p] (uint8), lo16_dev[p] (int32) and band_dev[p] (uint8), the band
+ * of the sync row the peak was found in.  The span [ctr_lo, ctr_hi) is given in 64-bit integers, 0 <= ctr_lo <= ctr_hi <= 2^32; with
+ *     h0 = ctr_lo >> 16,   h1 = (ctr_hi + 65535) >> 16,   H = h1 - h0,   W = ceil(H / 32)
+ * es_acquire_mask_batch writes mask_dev [P][W] uint32: bit (h - h0) & 31 of word (h - h0) >> 5 of row p is set exactly when ok_dev[p] != 0,
+ * 0 <= key_dev[p] < N, 0 <= lo16_dev[p] <= 65535, c = (h << 16) | lo16_dev[p] lies in [ctr_lo, ctr_hi) and the band of counter c under
+ * ring row key_dev[p] (HMAC-SHA256 from the row's pad states, as es_hop_window_batch) equals band_dev[p].  One lane per (record, h); every
+ * word of every row is written, zeros included; count_dev [P] int32 = the set bits of each row, summed by a second launch over the finished
+ * rows (no atomics: the same on every run).  A record that is not ok, or whose key or low half is out of range, reads nothing of the ring.
+ * ES_EINVAL, with nothing enqueued and nothing written: a negative count, a span outside [0, 2^32] or reversed, N < 1 or a null pointer
+ * with work to do, more than 2^31 - 1 workgroups (four (record, 64 high halves) tiles each: the grid is exact, P * H is small in every real
+ * call).  P == 0 or H == 0: ES_OK, nothing enqueued.  Needs no tables, only enqueues.                                                   */
+int es_acquire_mask_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const int32_t* key_dev, const uint8_t* ok_dev, const int32_t* lo16_dev,
+                          const uint8_t* band_dev, int64_t P, int64_t ctr_lo, int64_t ctr_hi, uint32_t* mask_dev, int32_t* count_dev, void* stream);
+
+/* The set bits of es_acquire_mask_batch's rows as a flat candidate list, in an order the host chooses after reading the P counts: for every
+ * record p with base_dev[p] >= 0 (int64 [P]) the i-th set bit of row p, h ascending, becomes
+ *     cand_rec_dev[base_dev[p] + i] = p (int32),   cand_ctr_dev[base_dev[p] + i] = (h << 16) | (lo16_dev[p] & 0xFFFF) (uint32).
+ * A record with base_dev[p] < 0 is skipped.  Nothing outside the named ranges is written, and no entry at or past `total`, the entries of
+ * the two output arrays (the host's ranges, base[p] + count[p] <= total, are disjoint by its own choice).  One wave per (record, 64 high
+ * halves): the order inside comes from the wave's ballot, the offset from the popcounts of the row's words before it, which the wave sums
+ * itself -- no workgroup waits for another, no atomic decides an order.  mask_dev, the span and P as in the mask call.  Refusals as
+ * es_acquire_mask_batch (and total < 0); P == 0, H == 0 or total == 0: ES_OK, nothing enqueued.  Needs no tables, only enqueues.          */
+int es_acquire_list_batch(es_ctx* ctx, const uint32_t* mask_dev, const int32_t* lo16_dev, int64_t P, int64_t ctr_lo, int64_t ctr_hi,
+                          const int64_t* base_dev, int64_t total, int32_t* cand_rec_dev, uint32_t* cand_ctr_dev, void* stream);
+
 /* ---- the transmit side for many keys: clips of unequal length, each marked under its own key, in one launch sequence ----------
  * es_aead_seal_batch with the ChaCha20 key of ring row key_dev[i] (read as es_aead_check_keyed_batch reads it) in place of key32_host:
  * SecureChannel.seal (rtwm/crypto.py:33-37) per (key, blob), what WatermarkEmbedder._build_payload puts into a frame
