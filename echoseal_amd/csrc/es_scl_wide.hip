@@ -21,7 +21,8 @@
 // The sort is a bitonic network over the 2L candidates on (metric, candidate index) -- a strict total order, so
 // the result is Python's stable list.sort -- with two candidates per lane IN REGISTERS: partner lanes exchange
 // through DPP / ds_swizzle / ds_bpermute, only the stages whose partner sits in another wave (3 of 45 at L = 256)
-// go through LDS and a workgroup barrier.
+// go through LDS and a workgroup barrier.  Lists that fit one wave run the network's all-ascending form (wide_sort): its masks are constants and
+// the first stage of a merge phase meets the mirrored lane, a DPP operand up to groups of 16 lanes.
 //
 // Barriers.  A path may read a slot that another wave wrote, but only one it inherited at a sort (whose barriers
 // order the write before the read); and a lane only ever writes its OWN slot.  What remains is write-after-read:
@@ -93,8 +94,17 @@ constexpr int wide_low_row(int DL, int d) { int r = 0; for (int k = DL; k < d; +
 struct WidePtr16 { uint64_t lo, hi; };
 template <int L> using wide_ptr_t = std::conditional_t<(L > 256), WidePtr16, uint64_t>;
 
-__device__ __forceinline__ uint64_t p8_set(uint64_t w, int k, int v) { const int sh = 8 * k; return (w & ~(255ULL << sh)) | ((uint64_t)(uint32_t)v << sh); }
-__device__ __forceinline__ int p8_get(uint64_t w, int k) { return (int)((w >> (8 * k)) & 255ULL); }
+// (bytes of the proper 32-bit half: the half is selected first and the shifts are 32-bit -- a 64-bit shift by a run-time count, which the depth
+// is in the slab loop and the partial-sum fold, issues at the float64 rate.  The depth is wave-uniform: the masks are scalar.  With a
+// compile-time depth this folds to one byte extract / insert.)
+__device__ __forceinline__ uint64_t p8_set(uint64_t w, int k, int v)
+{
+    const int sh = 8 * (k & 3);
+    const uint32_t m = 255u << sh, x = (uint32_t)v << sh, mlo = k < 4 ? m : 0u, mhi = k < 4 ? 0u : m;
+    const uint32_t lo = ((uint32_t)w & ~mlo) | (x & mlo), hi = ((uint32_t)(w >> 32) & ~mhi) | (x & mhi);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ int p8_get(uint64_t w, int k) { return (int)(((k < 4 ? (uint32_t)w : (uint32_t)(w >> 32)) >> (8 * (k & 3))) & 255u); }
 __device__ __forceinline__ WidePtr16 p8_set(WidePtr16 w, int k, int v)
 {
     const int sh = 16 * (k & 3);
@@ -209,7 +219,59 @@ __device__ __forceinline__ void ce_inlane(uint32_t& lo0, uint32_t& hi0, uint32_t
     lo0 = nlo0; hi0 = nhi0; ix0 = nix0;
 }
 
+// The first stage of a merge phase in the all-ascending network of lists up to 64 paths: element e meets e ^ (k - 1), which is the OTHER
+// element of the mirrored lane -- a DPP operand for groups of 2, 4, 8 and 16 lanes (quad_perm:[1,0,3,2], quad_perm:[3,2,1,0],
+// row_half_mirror, row_mirror).  Both of a lane's elements are the smaller (or both the larger) ones of their pairs: tmask = lanes that take
+// the minima.  As ES_CE_DPP, twice, the lane's own two elements in swapped roles: mine 0 against the partner's 1, mine 1 against the
+// partner's 0; the results go to fresh registers (the second compare reads what the first one would have overwritten).
+#define ES_CE_DPP_X(CTRL, lo0, hi0, ix0, lo1, hi1, ix1, tmask)                                                               \
+    do { uint32_t t_, a_, b_, c_, d_, e_, f_;                                                                                \
+        asm volatile("s_nop 1\n\t"                                                                                           \
+                     "v_sub_co_u32_dpp %6, vcc, %12, %9 " CTRL " row_mask:0xf bank_mask:0xf\n\t"                             \
+                     "v_subb_co_u32_dpp %6, vcc, %10, %7, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                       \
+                     "v_subb_co_u32_dpp %6, vcc, %11, %8, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                       \
+                     "s_xor_b64 vcc, vcc, %13\n\t"                                                                           \
+                     "v_cndmask_b32_dpp %2, %12, %9, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                            \
+                     "v_cndmask_b32_dpp %0, %10, %7, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                            \
+                     "v_cndmask_b32_dpp %1, %11, %8, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                            \
+                     "v_sub_co_u32_dpp %6, vcc, %9, %12 " CTRL " row_mask:0xf bank_mask:0xf\n\t"                             \
+                     "v_subb_co_u32_dpp %6, vcc, %7, %10, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                       \
+                     "v_subb_co_u32_dpp %6, vcc, %8, %11, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                       \
+                     "s_xor_b64 vcc, vcc, %13\n\t"                                                                           \
+                     "v_cndmask_b32_dpp %5, %9, %12, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                            \
+                     "v_cndmask_b32_dpp %3, %7, %10, vcc " CTRL " row_mask:0xf bank_mask:0xf\n\t"                            \
+                     "v_cndmask_b32_dpp %4, %8, %11, vcc " CTRL " row_mask:0xf bank_mask:0xf"                                 \
+                     : "=&v"(a_), "=&v"(b_), "=&v"(c_), "=&v"(d_), "=&v"(e_), "=&v"(f_), "=&v"(t_)                           \
+                     : "v"(lo0), "v"(hi0), "v"(ix0), "v"(lo1), "v"(hi1), "v"(ix1), "s"(tmask) : "vcc", "scc");               \
+        lo0 = a_; hi0 = b_; ix0 = c_; lo1 = d_; hi1 = e_; ix1 = f_;                                                          \
+    } while (0)
+// Lanes of a wave whose index has bit d clear (d a power of two below 64, a constant after unrolling; 0: every lane), as a mask formed
+// WHERE IT IS USED: handed plain constants the compiler hoists the masks out of the bit loop into scalar registers, of which the kernel
+// has none to spare -- they came back through v_readlane / v_writelane, two vector instructions per stage.  A scalar move is free.
+#define ES_WIDE_MASK32(C) ([]() { uint32_t h_; asm volatile("s_mov_b32 %0, " #C : "=s"(h_)); return h_; }())
+__device__ __forceinline__ unsigned long long wide_lanes_clear(int d)
+{
+    uint32_t lo, hi;
+    switch (d) {
+        case 0:  lo = hi = ES_WIDE_MASK32(0xFFFFFFFF); break;
+        case 1:  lo = hi = ES_WIDE_MASK32(0x55555555); break;
+        case 2:  lo = hi = ES_WIDE_MASK32(0x33333333); break;
+        case 4:  lo = hi = ES_WIDE_MASK32(0x0F0F0F0F); break;
+        case 8:  lo = hi = ES_WIDE_MASK32(0x00FF00FF); break;
+        case 16: lo = hi = ES_WIDE_MASK32(0x0000FFFF); break;
+        default: lo = ES_WIDE_MASK32(0xFFFFFFFF); hi = ES_WIDE_MASK32(0); break;
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+// lane l <-> lane l ^ 31 / l ^ 63 (the mirrored lane of a group of 32 / 64)
+__device__ __forceinline__ int wmirror_b32(int v, int D) { return D == 31 ? __builtin_amdgcn_ds_swizzle(v, 0x7C1F) : __shfl_xor(v, 63); }
+
 // Bitonic network over 2L (key, index) pairs, element e = 2 * lane + b held as (k0, i0) / (k1, i1); ascending on exit.
+// Lists of up to 64 paths (one wave) run its all-ascending form: a merge phase of k elements starts by meeting element e with e ^ (k - 1)
+// -- the two runs it merges both ascend -- and goes on with the half-cleaners e ^ j, j = k / 4 .. 1.  Every stage's "take the minimum" mask
+// is then a constant of the lane index (no compare, no ballot), and the first stage's partner, the mirrored lane, is a DPP operand where
+// the stage at the same distance of the alternating form (lane ^ 4, lane ^ 16) fetched three words per element through ds_swizzle.
+// Both are sorting networks and (metric, index) is a strict total order (dead lanes' fillers are identical): the result is the same.
 // (LF < L: independent networks over aligned groups of LF lanes -- one per frame; pl = lane index within the frame)
 template <int L, int LF>
 __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, uint32_t& i1, const int p, const int pl, WideLds<L, (LF > 64 ? 2 : 1)>& W, int& buf)
@@ -217,6 +279,42 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
     constexpr int NBUF = wide_pub_bufs(L, LF > 64 ? 2 : 1);     // 1: one buffer, a barrier before each write to it (see WidePub)
     uint64_t u0, u1; __builtin_memcpy(&u0, &k0, 8); __builtin_memcpy(&u1, &k1, 8);
     uint32_t lo0 = (uint32_t)u0, hi0 = (uint32_t)(u0 >> 32), lo1 = (uint32_t)u1, hi1 = (uint32_t)(u1 >> 32);
+    if constexpr (LF <= 64) {
+    #pragma unroll
+    for (int k = 2; k <= 2 * LF; k <<= 1) {
+        if (k > 2) {                                             // element e <-> e ^ (k - 1): lane p ^ dm, the other element
+            const int dm = (k >> 1) - 1;
+            const unsigned long long tm = wide_lanes_clear(k >> 2);
+            if (dm == 1) ES_CE_DPP_X("quad_perm:[1,0,3,2]", lo0, hi0, i0, lo1, hi1, i1, tm);
+            else if (dm == 3) ES_CE_DPP_X("quad_perm:[3,2,1,0]", lo0, hi0, i0, lo1, hi1, i1, tm);
+            else if (dm == 7) ES_CE_DPP_X("row_half_mirror", lo0, hi0, i0, lo1, hi1, i1, tm);
+            else if (dm == 15) ES_CE_DPP_X("row_mirror", lo0, hi0, i0, lo1, hi1, i1, tm);
+            else {
+                const uint32_t a0 = (uint32_t)wmirror_b32((int)lo1, dm), b0 = (uint32_t)wmirror_b32((int)hi1, dm), c0 = (uint32_t)wmirror_b32((int)i1, dm);
+                const uint32_t a1 = (uint32_t)wmirror_b32((int)lo0, dm), b1 = (uint32_t)wmirror_b32((int)hi0, dm), c1 = (uint32_t)wmirror_b32((int)i0, dm);
+                ce_pair(lo0, hi0, i0, a0, b0, c0, tm);
+                ce_pair(lo1, hi1, i1, a1, b1, c1, tm);
+            }
+        }
+        #pragma unroll
+        for (int j = (k == 2) ? 1 : (k >> 2); j >= 1; j >>= 1) {
+            if (j == 1) ce_inlane(lo0, hi0, i0, lo1, hi1, i1, wide_lanes_clear(0));
+            else {
+                const int dl = j >> 1;                           // partner lane p ^ dl, same b
+                const unsigned long long tm = wide_lanes_clear(dl);
+                if (dl == 1) { ES_CE_DPP("quad_perm:[1,0,3,2]", lo0, hi0, i0, tm); ES_CE_DPP("quad_perm:[1,0,3,2]", lo1, hi1, i1, tm); }
+                else if (dl == 2) { ES_CE_DPP("quad_perm:[2,3,0,1]", lo0, hi0, i0, tm); ES_CE_DPP("quad_perm:[2,3,0,1]", lo1, hi1, i1, tm); }
+                else if (dl == 8) { ES_CE_DPP("row_ror:8", lo0, hi0, i0, tm); ES_CE_DPP("row_ror:8", lo1, hi1, i1, tm); }
+                else {
+                    const uint32_t a0 = (uint32_t)wxor_b32((int)lo0, dl), b0 = (uint32_t)wxor_b32((int)hi0, dl), c0 = (uint32_t)wxor_b32((int)i0, dl);
+                    const uint32_t a1 = (uint32_t)wxor_b32((int)lo1, dl), b1 = (uint32_t)wxor_b32((int)hi1, dl), c1 = (uint32_t)wxor_b32((int)i1, dl);
+                    ce_pair(lo0, hi0, i0, a0, b0, c0, tm);
+                    ce_pair(lo1, hi1, i1, a1, b1, c1, tm);
+                }
+            }
+        }
+    }
+    } else {
     #pragma unroll
     for (int k = 2; k <= 2 * LF; k <<= 1) {
         const bool asc = ((2 * pl) & k) == 0;                    // k == 2 LF: always ascending
@@ -258,9 +356,15 @@ __device__ __forceinline__ void wide_sort(double& k0, uint32_t& i0, double& k1, 
             }
         }
     }
+    }
     u0 = ((uint64_t)hi0 << 32) | lo0; u1 = ((uint64_t)hi1 << 32) | lo1;
     __builtin_memcpy(&k0, &u0, 8); __builtin_memcpy(&k1, &u1, 8);
 }
+
+// v, as a value formed where this is called.  The loops that zero a settled frame's candidate rows start at it: handed the lane index itself
+// the compiler strides them by eight, hoists the eight start offsets lane + 64 k out of the frame loop and carries them -- in registers or
+// spilled -- through the whole list loop.
+__device__ __forceinline__ int wide_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
 // hard decision -> butterfly -> data bits -> CRC of one frame by one wave (fastpolar.py:260-268); returns the CRC verdict to every lane
 template <bool GK>
@@ -431,10 +535,11 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     const int ok = hard_decision_wave<GK>(a, ff, lane, hd_words, hd_bytes, a.data_pos);
                     if (ok) {                                  // settled: its candidate rows read as zeros
                         if (lane == 0) a.ncand[ff] = 0;
+                        const int ln = wide_opaque(lane);
                         #pragma unroll 1
-                        for (int k = lane; k < a.lsz * NIB; k += 64) a.cand_info[(long long)ff * a.lsz * NIB + k] = 0;
+                        for (int k = ln; k < a.lsz * NIB; k += 64) a.cand_info[(long long)ff * a.lsz * NIB + k] = 0;
                         #pragma unroll 1
-                        for (int k = lane; k < a.lsz; k += 64) { a.cand_metric[(long long)ff * a.lsz + k] = 0.0; a.cand_ok[(long long)ff * a.lsz + k] = 0; }
+                        for (int k = ln; k < a.lsz; k += 64) { a.cand_metric[(long long)ff * a.lsz + k] = 0.0; a.cand_ok[(long long)ff * a.lsz + k] = 0; }
                     } else { if (lane == 0) drawn[n] = ff; ++n; }
                 }
                 wave_fence_lds();
@@ -477,10 +582,11 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 const int ok = hard_decision_wave<GK>(a, ff, lane, hd_words, hd_bytes, a.data_pos);
                 if (ok && a.skip_if_hard_ok) {                 // no list for this record: its candidate rows read as zeros
                     if (lane == 0) a.ncand[ff] = 0;
+                    const int ln = wide_opaque(lane);
                     #pragma unroll 1
-                    for (int k = lane; k < a.lsz * NIB; k += 64) a.cand_info[ff * a.lsz * NIB + k] = 0;
+                    for (int k = ln; k < a.lsz * NIB; k += 64) a.cand_info[ff * a.lsz * NIB + k] = 0;
                     #pragma unroll 1
-                    for (int k = lane; k < a.lsz; k += 64) { a.cand_metric[ff * a.lsz + k] = 0.0; a.cand_ok[ff * a.lsz + k] = 0; }
+                    for (int k = ln; k < a.lsz; k += 64) { a.cand_metric[ff * a.lsz + k] = 0.0; a.cand_ok[ff * a.lsz + k] = 0; }
                 } else active_mask |= 1ULL << fi;
             }
         } else {
@@ -519,9 +625,23 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
         bool dirty = false;               // shared slots may still be being read by a wave that is behind (group-uniform)
         group_sync();
 
-        for (int i = 0; i < N; ++i) {
+        // One leaf.  The even and the odd leaf of a pair are two instances of this text (ODD a compile-time constant): only the even one
+        // walks the tree (an odd leaf's top is depth 10, a g of what its sibling left in LDS), evaluates a softplus and fetches the
+        // softplus pair through the sort; the odd one takes its penalty from lp_odd and folds the partial sums upward.
+        auto leaf = [&](auto odd_c, const int i) {
+            constexpr bool ODD = decltype(odd_c)::value;
             const bool frozen = (a.frozen.w[i >> 5] >> (i & 31)) & 1u;
-            if (i == 0) {
+            // An even leaf's penalty softplus log1p(exp(-|lam|)), right behind the f that forms lam: the straight-line form over the
+            // ES_EXP_SHIFT pair that f has just set up; out of range (|lam| >= 512) the generic form, a cold path behind one ballot.
+            double lp_even = 0.0;
+            auto leaf_softplus = [&](double x, double sh) {
+                int bad = 0;
+                const double al_ = __builtin_fabs(x);
+                double v = es_leaf_softplus_sl_sh(al_, tab, &bad, sh);
+                if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) { if (bad) v = es_softplus_neg_generic(-al_, tab); }
+                return v;
+            };
+            if (!ODD && i == 0) {
                 // First chain: the paths of a frame are still copies of its path 0, so each node is computed once, the frame's
                 // lanes sharing its elements, into that path's slot (a barrier per depth here: lanes read what other lanes wrote).
                 #pragma unroll 1
@@ -539,9 +659,17 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     }
                     group_sync();
                 }
-                lam = es_polar_f_sp(W.low[lrow(9)][fp0], W.low[lrow(9) + 1][fp0], tab, &sp_diff, &sp_sum);
+                {                                                         // (generic softplus as a cold path, as at depth 10 below)
+                    const double xa = W.low[lrow(9)][fp0], xb = W.low[lrow(9) + 1][fp0];
+                    int bad = 0;
+                    const double sh = es_shift_reg();
+                    lam = es_polar_f_sl_sp_sh(xa, xb, tab, &sp_diff, &sp_sum, &bad, sh);
+                    if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) lam = es_polar_f_sp(xa, xb, tab, &sp_diff, &sp_sum);
+                    lp_even = leaf_softplus(lam, sh);
+                }
                 dirty = true;
             } else {
+                if constexpr (!ODD) {
                 const int top = NLEV - __builtin_ctz((unsigned)i);
                 if (top <= 9 && dirty) { group_sync(); dirty = false; }         // this step writes slots
                 // --- depths top..DL-1: slab to slab, the lane walks the node
@@ -767,15 +895,18 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 if (top <= DL && !have_dl) low_level(integral_constant<int, DL>{}, std::true_type{});
                 if constexpr (DL < 8) { if (top <= 8) low_level(integral_constant<int, 8>{}, std::false_type{}); }
                 if (top <= 9) low_level(integral_constant<int, 9>{}, std::false_type{});
+                }
                 // --- depth 10: LDS -> register
                 {
                     const int ps = p8_get(pb_, 5);
                     const double xa = W.low[lrow(9)][ps], xb = W.low[lrow(9) + 1][ps];
-                    if (i & 1) lam = es_polar_g(xa, xb, (b0 >> 1) & 1u);
+                    if constexpr (ODD) lam = es_polar_g(xa, xb, (b0 >> 1) & 1u);
                     else {                                                // (generic softplus as a cold path, as at depth 9)
                         int bad = 0;
-                        lam = es_polar_f_sl_sp(xa, xb, tab, &sp_diff, &sp_sum, &bad);
+                        const double sh = es_shift_reg();
+                        lam = es_polar_f_sl_sp_sh(xa, xb, tab, &sp_diff, &sp_sum, &bad, sh);
                         if (__builtin_amdgcn_ballot_w64(bad != 0) != 0ULL) lam = es_polar_f_sp(xa, xb, tab, &sp_diff, &sp_sum);
+                        lp_even = leaf_softplus(lam, sh);
                     }
                 }
                 dirty = true;
@@ -783,21 +914,17 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
 
             // --- decision
             const double al = __builtin_fabs(lam);
-            double lp;
-            if (i & 1) lp = lp_odd;                                  // set when the even sibling was decided
-            else lp = es_softplus_neg(-al, tab);
+            const double lp = ODD ? lp_odd : lp_even;               // lp_odd: set when the even sibling was decided
             const uint32_t pref = (lam >= 0.0) ? 1u : 0u;
             uint32_t bit = 0;
             if (frozen) {                                             // fastpolar.py:281-286
-                double pen = lp;
-                if (pref != 0u) pen = lp + al;
-                metric = metric + pen;
-                lp_odd = sp_sum;                                      // sibling g = b + a when this bit is 0
+                metric = metric + es_leaf_penalty(lp, al, pref, 0u);
+                if constexpr (!ODD) lp_odd = sp_sum;                  // sibling g = b + a when this bit is 0
             } else {                                                  // fastpolar.py:288-330
                 const bool live = pl < cnt;
                 const int nc = 2 * cnt;
-                double k0 = live ? metric + ((pref != 0u) ? lp + al : lp) : __builtin_inf();
-                double k1 = live ? metric + ((pref != 1u) ? lp + al : lp) : __builtin_inf();
+                double k0 = live ? metric + es_leaf_penalty(lp, al, pref, 0u) : __builtin_inf();
+                double k1 = live ? metric + es_leaf_penalty(lp, al, pref, 1u) : __builtin_inf();
                 uint32_t i0 = live ? (uint32_t)(2 * pl) : 0xFFFFu, i1 = live ? (uint32_t)(2 * pl + 1) : 0xFFFFu;   // candidate index within the frame
                 const bool wstart = (info_idx & 31) == 0;
                 const int keep = nc < a.lsz ? nc : a.lsz;          // a.lsz <= LF: lists of any size run on the next power of two's kernel
@@ -822,7 +949,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     anc = (uint32_t)(t >> 48);
                     b0 = fetch32(parent, b0);
                     hist = (fetch32(parent, wstart ? 0u : hist) << 1) | bit;
-                    if (!(i & 1)) {
+                    if constexpr (!ODD) {
                         const uint64_t sd = fetch64(parent, __builtin_bit_cast(uint64_t, sp_diff)), ss = fetch64(parent, __builtin_bit_cast(uint64_t, sp_sum));
                         lp_odd = __builtin_bit_cast(double, bit ? sd : ss);
                     }
@@ -835,7 +962,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 else W.pub.xpb[xb][p] = pb_ | ((uint64_t)(wstart ? (uint32_t)pl : anc) << 48);
                 W.pub.xb0[xb][p] = b0;
                 W.pub.xhist[xb][p] = wstart ? 0u : hist;
-                if (!(i & 1)) { W.pub.xsp[xb][0][p] = sp_diff; W.pub.xsp[xb][1][p] = sp_sum; }
+                if constexpr (!ODD) { W.pub.xsp[xb][0][p] = sp_diff; W.pub.xsp[xb][1][p] = sp_sum; }
                 int buf = 0;
                 wide_sort<L, LF>(k0, i0, k1, i1, p, pl, W, buf);
                 if constexpr (!WAVE && NBUF == 1) __syncthreads();         // one buffer: every wave has read the last cross-wave stage
@@ -855,7 +982,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                 }
                 b0 = W.pub.xb0[xb][parent];
                 hist = (W.pub.xhist[xb][parent] << 1) | bit;
-                if (!(i & 1)) lp_odd = W.pub.xsp[xb][bit ? 0 : 1][parent];
+                if constexpr (!ODD) lp_odd = W.pub.xsp[xb][bit ? 0 : 1][parent];
                 }
                 if ((info_idx & 31) == 31) { TBW[(info_idx >> 5) * L + p] = hist; TBA[(info_idx >> 5) * L + p] = (uint16_t)anc; }
                 cnt = keep;
@@ -864,7 +991,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
             }
 
             // --- partial sums: fold upward while the node is a right child (fastpolar.py:156-183); each lane its own path
-            const int t = __builtin_ctz(~(unsigned)i);
+            const int t = ODD ? __builtin_ctz(~(unsigned)i) : 0;   // (an even leaf is a left child: its bit becomes the 1-bit block)
             if (t < NLEV) {
                 uint32_t cw = bit;
                 const int t5 = t < 5 ? t : 5;
@@ -898,7 +1025,8 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     pb_ = p8_set(pb_, NLEV - t - 1, p);
                 }
             }
-        }
+        };
+        for (int i = 0; i < N; i += 2) { leaf(std::false_type{}, i); leaf(std::true_type{}, i + 1); }
 
         // ---------------- final ordering (fastpolar.py:335), trace-back, CRC -- per frame
         group_sync();

@@ -189,4 +189,17 @@ ES_HD double es_polar_f_slg(double a, double b, const uint64_t* tab)
     return es_polar_f_slg_sh(a, b, tab, es_shift_reg());
 }
 
+/* The leaf penalty's softplus log1p(exp(-al)), al = |leaf LLR|, on the straight-line form: the value es_metric_penalty (es_math.h) starts
+ * from, bit for bit, while al < 512.  Outside that range (NaN included) *bad is set (or-ed in) and the result is unspecified: the caller
+ * evaluates es_softplus_neg_generic(-al) instead, on a cold path after ONE test for all its lanes, as the f levels of depths 9 and 10 do --
+ * no branch follows the evaluation.  tests/test_leaf_penalty_dev.py compares the three steps with es_metric_penalty on the host. */
+ES_HD double es_leaf_softplus_sl_sh(double al, const uint64_t* tab, int* bad, double sh)
+{
+    *bad |= !(al < 512.0);
+    return es_softplus_neg_sl_sh(-al, tab, sh);
+}
+
+/* ... and the penalty of deciding `bit` at a leaf whose LLR has magnitude al and preferred bit pref, from that softplus (fastpolar.py:32-40) */
+ES_HD double es_leaf_penalty(double lp, double al, uint32_t pref, uint32_t bit) { return (bit != pref) ? lp + al : lp; }
+
 #endif /* ES_SOFTPLUS_DEV_H */
