@@ -7,14 +7,31 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
+import sys
 
 import torch  # noqa: F401  -- must be imported BEFORE the HIP library so that both share torch's HIP runtime
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libechoseal_hip.so")
-if os.environ.get("ES_LIB_VARIANT"):           # development: an A/B build made by tools/build_variant.sh (same ABI check, same loud failure when missing)
-    LIB_PATH = os.path.join(_HERE, f"libechoseal_hip_{os.environ['ES_LIB_VARIANT']}.so")
+
+
+class NativeError(RuntimeError):
+    pass
+
+
+def variant_path(variant):
+    """The library ES_LIB_VARIANT names: an A/B build made by tools/build_variant.sh or a mutant of tools/mutant_audit.py (same ABI check,
+    same loud failure when missing).  The name goes into a file name, so it is letters, digits and underscores or it is refused."""
+    if not variant:
+        return os.path.join(_HERE, "libechoseal_hip.so")
+    if not re.fullmatch(r"[A-Za-z0-9_]+", variant):
+        raise NativeError(f"ES_LIB_VARIANT={variant!r} is not a variant name ([A-Za-z0-9_]+)")
+    return os.path.join(_HERE, f"libechoseal_hip_{variant}.so")
+
+
+LIB_VARIANT = os.environ.get("ES_LIB_VARIANT", "")
+LIB_PATH = variant_path(LIB_VARIANT)
 
 ES_ABI_VERSION = 2          # include/echoseal_hip.h; load() refuses a library built from another one
 ES_FRAME_LEN = 1215
@@ -131,10 +148,6 @@ SIGNATURES = {
 _lib = None
 
 
-class NativeError(RuntimeError):
-    pass
-
-
 def load() -> ctypes.CDLL:
     """Load the HIP library (once).  Raises if it has not been built -- never falls back."""
     global _lib
@@ -157,6 +170,8 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args
+    if LIB_VARIANT:                      # said once: load() returns the cached library from here on
+        print(f"echoseal_amd: loaded variant library {os.path.basename(LIB_PATH)} (ES_LIB_VARIANT={LIB_VARIANT})", file=sys.stderr)
     _lib = lib
     return lib
 

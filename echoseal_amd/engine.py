@@ -165,12 +165,22 @@ class RxEngine(TxChain, MonitorChain):
         self.list_size_max = int(list_size_max)
         self.fs = fs
         self.code_k = int(code_k)
-        ba, tpl, taps, ntaps, frozen = pack_tables(fs, self.code_k)
+        self.set_tables(*pack_tables(fs, self.code_k))
+        self.info_bytes = int(self._lib.es_info_bytes(self._ctx))
+
+    def tables(self):
+        """The host arrays last installed: (ba [4, 18] float64, tpl, taps [4, ES_MAX_TAPS] float32, ntaps int32 [4], frozen)."""
+        return self._tables
+
+    def set_tables(self, ba, tpl, taps, ntaps, frozen) -> None:
+        """Install band-pass coefficients, sync templates, matched filters and the frozen set (es_set_tables): what __init__ does with
+        pack_tables(fs, code_k).  Arrays in pack_tables' shapes and types; work enqueued under the previous tables is waited for.  For
+        tests and experiments that need tables the band plan never produces, such as a one-tap matched filter."""
+        torch.cuda.synchronize(self.device)
         self._tables = (ba, tpl, taps, ntaps, frozen)       # keep host arrays alive
         nat.check(self._ctx, self._lib.es_set_tables(
             self._ctx, ba.ctypes.data, tpl.ctypes.data, taps.ctypes.data, ntaps.ctypes.data,
             frozen.ctypes.data), "es_set_tables")
-        self.info_bytes = int(self._lib.es_info_bytes(self._ctx))
 
     def set_option(self, name: str, value: int) -> None:
         """Tuning knobs of the native library (results never depend on them); see include/echoseal_hip.h."""

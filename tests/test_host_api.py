@@ -38,6 +38,29 @@ def test_loader_refuses_another_abi_version(tmp_path, monkeypatch):
         nat.load()
 
 
+def test_variant_names_are_checked_and_the_loaded_variant_is_named_once(monkeypatch, capsys):
+    """ES_LIB_VARIANT goes into a file name: anything but [A-Za-z0-9_]+ is refused, and a variant that loads says so on stderr, once."""
+    import echoseal_amd._native as nat
+    here = os.path.dirname(nat.__file__)
+    assert nat.variant_path("") == os.path.join(here, "libechoseal_hip.so")
+    assert nat.variant_path("pick_cap") == os.path.join(here, "libechoseal_hip_pick_cap.so")
+    for bad in ("../x", "a/b", "a.b", "a-b", "a b", "x;y", "é"):
+        with pytest.raises(nat.NativeError, match="ES_LIB_VARIANT"):
+            nat.variant_path(bad)
+    stock = nat.variant_path("")
+    monkeypatch.setattr(nat, "LIB_PATH", stock)           # the stock library under a variant's name: what load() says is under test
+    monkeypatch.setattr(nat, "LIB_VARIANT", "some_variant")
+    monkeypatch.setattr(nat, "_lib", None)
+    nat.load()
+    nat.load()
+    err = capsys.readouterr().err
+    assert err.count("\n") == 1 and "some_variant" in err and "variant library" in err
+    monkeypatch.setattr(nat, "LIB_VARIANT", "")
+    monkeypatch.setattr(nat, "_lib", None)
+    nat.load()
+    assert capsys.readouterr().err == ""                   # the stock library is loaded without a word
+
+
 def test_product_never_imports_oracle():
     """Only tests/ (the sweeps under tests/fuzz/ included), __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/:
     neither the package nor the measurement tools under tools/ do."""
