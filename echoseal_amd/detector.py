@@ -17,6 +17,7 @@ print() debugging is not reproduced.
 from __future__ import annotations
 
 import copy
+import itertools
 from dataclasses import dataclass
 
 import numpy as np
@@ -27,8 +28,9 @@ from .crypto import SecureChannel
 from .monitor import LiveTable
 from .polar_fast import N_DEFAULT
 from .primitives import InvalidTag
-from .scan import (CTR_END, FRAME_LEN, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, Launch, check_counter_reach, counter_estimate,  # noqa: F401 (re-exported)
-                   counter_origins, cut_launches, ragged_buckets, sync_launch)
+from .scan import (CTR_END, FRAME_LEN, MAX_TRIES, PEAK_LIMIT, PRE_L, RAGGED_ROW_SAMPLES, TIGHT_DELTA, WIDE_DELTA, Launch,  # noqa: F401 (re-exported)
+                   SyncScan, check_counter_reach, counter_estimate, counter_origins, cut_launches, dev, plan_tries, ragged_buckets, rate_list,
+                   sync_launch)
 from .tables import matched_filter_taps
 from .utils import BAND_PLAN, BandHop, butter_bandpass, choose_band, mseq_63, resample_to, resampled_length  # noqa: F401 (re-exported)
 
@@ -37,19 +39,35 @@ HDR_BITS = 16
 HDR_REPEAT = 8
 HDR_L = 128
 assert PRE_L == len(PRE_BITS) and FRAME_LEN == PRE_L + HDR_L + N_DEFAULT
-TIGHT_DELTA = 3
-WIDE_DELTA = 200
 EPS = 1e-12
 
-MAX_TRIES = 400          # rtwm/detector.py:107
 
+def decode_four(eng, y, rows, cols, pn, bands, list_size: int):
+    """The four decodes the reference tries per candidate (+llr0, -llr0, +llr1, -llr1; rtwm/detector.py:161-190) for n candidates at
+    once, candidate i the frame at y[rows[i], cols[i]:] with PN row pn[i] on band bands[i] (device tensors): two demodulations read in
+    place, one list decode -> the SclResult of the 4 n rows, row v * n + i = variant v of candidate i.  Scheduling and selection are the callers'."""
+    import torch
+    if list_size > eng.list_size_max:
+        raise NotImplementedError(f"list_size={list_size}: the HIP decoder supports list sizes up to {eng.list_size_max}")
+    l0 = eng.llr(y, bands, pn, variant=0, rows=rows, start=cols)
+    l1 = eng.llr(y, bands, pn, variant=1, rows=rows, start=cols)
+    return eng.scl(torch.cat((l0, -l0, l1, -l1), dim=0), list_size=list_size, skip_if_hard_ok=False)
+
+
+def check_decoded(ok: np.ndarray) -> np.ndarray:
+    """The host copy of a selection's verdicts, refused where the list decoder skipped a record (-2)."""
+    if (ok == -2).any():
+        raise NativeError("es_scl_batch: some candidate records were not decoded (no free scratch-slab slot)")
+    return ok
+
+
+@dataclass(eq=False)
 class _Frames:
     """Where the frames of a scan lie, without copying them: frame j = y[rows[j], starts[j] : starts[j] + 1215] of the band-passed
     records y (device, float64), read in place by es_header_at_batch / es_llr_at_batch.  rows, starts: host int arrays."""
-    __slots__ = ("y", "rows", "starts")
-
-    def __init__(self, y, rows: np.ndarray, starts: np.ndarray) -> None:
-        self.y, self.rows, self.starts = y, rows, starts
+    y: object
+    rows: np.ndarray
+    starts: np.ndarray
 
 
 @dataclass
@@ -116,10 +134,6 @@ class WatermarkDetector:
     def _band_id(self, band) -> int:
         return BAND_PLAN.index((int(band[0]), int(band[1])))
 
-    def _dev(self, arr: np.ndarray, dtype):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(arr, dtype=dtype)).to(self.engine.device)
-
     # ------------------------------------------------------------------ API
     def verify_wav(self, path: str) -> bool:
         """verify() for a WAV file (f-4 ingest): PCM16 samples stay int16 up to the band-pass kernel (x / 32768 there: the
@@ -158,7 +172,7 @@ class WatermarkDetector:
         ctr0: the counter origin of every clip, or one per clip with None entries allowed: the clip's first sample is
         where the frame of counter ctr0 starts, so a peak at `start` is looked for around ctr0 + round(start / 1215).  None (the
         default): the reference's estimate round(start / 1215), which finds frames of counters up to about the clip's length + 200."""
-        fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        fs_list = rate_list(fs_in, len(clips))
         origins = clip_origins(ctr0, clips, fs_list, self.fs_target)       # refused by name before any engine exists
         order = self._band_order()
         launches = cut_launches(clips, fs_list, self.fs_target, len(order), self._conditioned)
@@ -197,24 +211,15 @@ class WatermarkDetector:
                         break
                     batch.append((j, r)); n += m
                 flat = [(j, p) for (j, r) in batch for p in plans[j][r][0]]
-                res = self._decode_pairs_grouped([(scans[j].src, p[0], p[2]) for j, p in flat]) if flat else []
-                at = 0
+                res = iter(self._decode_pairs_grouped([(scans[j].src, p[0], p[2]) for j, p in flat]) if flat else [])
                 for (j, r) in batch:
-                    m = len(plans[j][r][0])
-                    cache[(j, r)] = res[at:at + m]
-                    at += m
+                    cache[(j, r)] = list(itertools.islice(res, len(plans[j][r][0])))
             return cache[(i, bi)]
 
-        out = []
-        for i in range(len(scans)):
-            ok = False
-            if scans[i] is not None:
-                for bi, (plan, hdr_log) in enumerate(plans[i]):
-                    if (self if walkers is None else walkers[i])._scan_replay(scans[i], bi, plan, hdr_log, need(i, bi) if plan else []):
-                        ok = True
-                        break
-            out.append(ok)
-        return out
+        def walk(i: int) -> bool:                                           # (any() stops at the first band that verifies: the early return)
+            w = self if walkers is None else walkers[i]
+            return any(w._scan_replay(scans[i], bi, plan, hdr_log, need(i, bi) if plan else []) for bi, (plan, hdr_log) in enumerate(plans[i]))
+        return [scans[i] is not None and walk(i) for i in range(len(scans))]
 
     # ------------------------------------------------------------------ acquisition
     def acquire(self, audio: np.ndarray, fs_in: int, *, span=FULL_SPAN, max_records: int = 8) -> Acquired | None:
@@ -231,7 +236,7 @@ class WatermarkDetector:
         first candidate _accept takes -- with its session-nonce bookkeeping, and each try appended to _trace.  An empty span: all None,
         no GPU work.  ValueError before any engine exists: a span outside [0, 2^32] or reversed, max_records < 1."""
         span, max_records = check_span(span), check_max_records(max_records)
-        fs_list = list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * len(clips)
+        fs_list = rate_list(fs_in, len(clips))
         out: list = [None] * len(clips)
         if span[0] == span[1]:
             return out
@@ -271,11 +276,8 @@ class WatermarkDetector:
                 _, cc = eng.acquire_list(mask, lo16, span, base, total)
                 cc = cc.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
                 ctrs = [cc[b:b + n] for b, n in zip(base.tolist(), count.tolist())]
-        out, at = [], 0
-        for sc, p0, r in zip(scans, pos0, recs):
-            out.append((sc, p0, r, ctrs[at:at + len(r)]))
-            at += len(r)
-        return out
+        ctrs = iter(ctrs)
+        return [(sc, p0, r, [next(ctrs) for _ in r]) for sc, p0, r in zip(scans, pos0, recs)]
 
     def _acquire_walk(self, scan, pos0: int, recs: list, ctrs: list, walker) -> Acquired | None:
         """Decode one clip's candidates in try order, in chunks of _pair_cap(), and walk them with `walker` (its _trace, its
@@ -309,16 +311,10 @@ class WatermarkDetector:
         stream, or one per stream with None entries allowed -- what the issuer opened the stream with (WatermarkIssuer.open_streams):
         frame k of the stream carries counter ctr0 + k, and a push looks for a peak's counter around that of its absolute position
         (DESIGN 4.18).  None: estimates relative to the window, which follow a stream marked from counter 0 for its first seconds."""
-        from .monitor import check_geometry, origin_words, stream_rates
-        window = int(round(float(window_s) * self.fs_target))
-        chunk_max = self.fs_target // 2 if chunk_max is None else int(chunk_max)
-        check_geometry(window, chunk_max)                                   # refused before any engine exists
-        stream_rates(int(n), fs, self.fs_target)                             # ... and so is a rate that cannot be served
-        origin_words(ctr0, int(n))                                          # ... and an origin that is no counter
+        from .monitor import open_arguments
         band_ids = [self._band_id(b) for b in self._band_order()]
-        origin = {} if ctr0 is None else {"ctr0": ctr0}                     # (no origin: the call as it always was)
-        return LiveMonitor(self, self.engine.open_monitor(int(n), window=window, chunk_max=chunk_max, bands=band_ids, fs=fs, **origin),
-                           trace=trace)
+        how = open_arguments(n, self.fs_target, bands=band_ids, fs=fs, window_s=window_s, chunk_max=chunk_max, ctr0=ctr0)      # refuses before any engine exists
+        return LiveMonitor(self, self.engine.open_monitor(int(n), **how), trace=trace)
 
     # one scan = what _scan_band_multi_frame needs for every band of one clip, produced in batched launches
     def _scan_prepare(self, signals, bands: list) -> list:
@@ -337,9 +333,8 @@ class WatermarkDetector:
         if rows_a.size:
             # frame j = sy.y[frame_rows[j], frame_cols[j] : frame_cols[j] + 1215], read in place (no [P, 1215] copy)
             src = _Frames(ss.sy.y, ss.frame_rows, ss.frame_cols)
-            okh, val, score = eng.header(ss.sy.y, self._dev(band_ids[rows_a % nb], np.uint8),
-                                         self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8),
-                                         rows=self._dev(src.rows, np.int32), start=self._dev(src.starts, np.int32))
+            okh, val, score = eng.header(ss.sy.y, dev(eng, band_ids[rows_a % nb], np.uint8), dev(eng, np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8),
+                                         rows=dev(eng, src.rows, np.int32), start=dev(eng, src.starts, np.int32))
             hdr = (okh.cpu().numpy().astype(bool), val.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64))
         return [_Scan(bands, src, rows_a - c * nb, np.flatnonzero((rows_a // nb) == c), ss.starts, hdr) for c in range(len(ss.sizes))]
 
@@ -347,35 +342,13 @@ class WatermarkDetector:
         """The candidate (peak, counter) pairs of one band in the reference's try order (rtwm/detector.py:105-140):
         -> (plan [(peak slot j, start, ctr, header-log index)], header log of the peaks looked at)."""
         band = scan.bands[bi]
-        sel = [int(j) for j in scan.sel if scan.rows[j] == bi]             # this band's peaks, in peak order
-        plan: list[tuple[int, int, int, int]] = []
-        hdr_log = []
-        tried = 0
-        for j in sel:
-            if tried >= MAX_TRIES:
-                break
-            start = int(scan.starts[j])
-            # rtwm/detector.py:117, or with an origin the counter of the frame at the peak's absolute position (DESIGN 4.18)
-            ctr_est = int(round(start / FRAME_LEN)) if scan.ctr0 is None else counter_estimate(start, scan.pos0, scan.ctr0)
-            hdr_ok, ctr_lo16, score = bool(scan.hdr[0][j]), int(scan.hdr[1][j]), float(scan.hdr[2][j])
-            hdr_log.append((float(hdr_ok), float(ctr_lo16), score))
-            cands: list[int] = []
-            if hdr_ok:                                                      # rtwm/detector.py:122-127 (counters end at 2^32 - 1)
-                for ctr in range(max(0, ctr_est - WIDE_DELTA), min(ctr_est + WIDE_DELTA + 1, CTR_END)):
-                    if (ctr & 0xFFFF) == ctr_lo16 and self._hop.band(ctr) == band:
-                        cands.append(ctr)
-            else:                                                           # :131-140
-                for ctr in range(max(0, ctr_est - TIGHT_DELTA), min(ctr_est + TIGHT_DELTA + 1, CTR_END)):
-                    if self._hop.band(ctr) == band:
-                        cands.append(ctr)
-                if not cands:
-                    for ctr in range(max(0, ctr_est - WIDE_DELTA), min(ctr_est + WIDE_DELTA + 1, CTR_END)):
-                        if self._hop.band(ctr) == band:
-                            cands.append(ctr)
-            for ctr in cands[:MAX_TRIES - tried]:
-                plan.append((j, start, ctr, len(hdr_log) - 1))              # (.., index of this peak's header decode in hdr_log)
-            tried += len(cands[:MAX_TRIES - tried])
-        return plan, hdr_log
+        sel = np.asarray(scan.sel, np.int64)[np.asarray(scan.rows)[scan.sel] == bi]     # this band's peaks, in peak order
+        idx, starts, ok, lo16, score = [sel.tolist()] + [np.asarray(a)[sel].tolist() for a in (scan.starts, *scan.hdr)]
+        # estimates: rtwm/detector.py:117, or with an origin the counter of the frame at the peak's absolute position (DESIGN 4.18)
+        at = (0, 0) if scan.ctr0 is None else (scan.pos0, scan.ctr0)
+        tries, looked = plan_tries(starts, ok, lo16, lambda ctr: self._hop.band(ctr) == band, *at)
+        hdr_log = [(float(bool(a)), float(int(b)), float(c)) for a, b, c in zip(ok[:looked], lo16[:looked], score[:looked])]
+        return [(idx[h], starts[h], ctr, h) for h, cs in tries for ctr in cs], hdr_log    # (.., index of the peak's header decode in hdr_log)
 
     def _scan_replay(self, scan, bi: int, plan, hdr_log, results) -> bool:
         """Walk one band's decoded candidates as the reference does (early return, traces, nonce bookkeeping in _accept)."""
@@ -394,11 +367,7 @@ class WatermarkDetector:
     def _scan_decide(self, scan, bi: int) -> bool:
         """The per-band loop of _scan_band_multi_frame (rtwm/detector.py:105-152) over prepared peaks / headers."""
         plan, hdr_log = self._scan_plan(scan, bi)
-        if not plan:
-            if self._hdr_trace is not None:
-                self._hdr_trace.extend(hdr_log)
-            return False
-        results = self._decode_pairs(scan.src, [p[0] for p in plan], [p[2] for p in plan])
+        results = self._decode_pairs(scan.src, [p[0] for p in plan], [p[2] for p in plan]) if plan else []
         return self._scan_replay(scan, bi, plan, hdr_log, results)
 
     def verify_raw_frame(self, signal: np.ndarray) -> bool:
@@ -422,8 +391,8 @@ class WatermarkDetector:
 
     # ------------------------------------------------------------------ sync (GPU)
     def _bandpass(self, signal: np.ndarray, band) -> np.ndarray:
-        x = self._dev(np.asarray(signal).astype(np.float32, copy=False).reshape(1, -1), np.float32)
-        b = self._dev(np.array([self._band_id(band)]), np.uint8)
+        x = dev(self.engine, np.asarray(signal).astype(np.float32, copy=False).reshape(1, -1), np.float32)
+        b = dev(self.engine, np.array([self._band_id(band)]), np.uint8)
         return self.engine.bpf(x, b)[0].cpu().numpy()
 
     def _sync(self, signal: np.ndarray, band):
@@ -431,8 +400,8 @@ class WatermarkDetector:
         sig = np.asarray(signal).astype(np.float32, copy=False).reshape(-1)
         if sig.size < PRE_L:                               # rtwm/detector.py:71-73
             return None
-        x = self._dev(sig.reshape(1, -1), np.float32)
-        b = self._dev(np.array([self._band_id(band)]), np.uint8)
+        x = dev(self.engine, sig.reshape(1, -1), np.float32)
+        b = dev(self.engine, np.array([self._band_id(band)]), np.uint8)
         sy = self.engine.sync(x, b, keep_corr=False)
         n = int(sy.npeaks[0].item()) & 0xFFFF
         peaks = [int(p) for p in sy.peaks[0, : min(n, sy.peaks.shape[1])].cpu().numpy()]
@@ -462,18 +431,18 @@ class WatermarkDetector:
         if frame.size == 0:
             return np.zeros(N_DEFAULT, dtype=np.float32)
         band = self._hop.band(frame_id)
-        y = self._dev(frame.reshape(1, -1), np.float64)
-        out = self.engine.llr(y, self._dev(np.array([self._band_id(band)]), np.uint8),
-                              self._dev(self._pn_rows([frame_id]), np.uint8), variant=int(pn_variant))
+        y = dev(self.engine, frame.reshape(1, -1), np.float64)
+        out = self.engine.llr(y, dev(self.engine, np.array([self._band_id(band)]), np.uint8),
+                              dev(self.engine, self._pn_rows([frame_id]), np.uint8), variant=int(pn_variant))
         return out[0].cpu().numpy()
 
     def _decode_header(self, frame: np.ndarray, band) -> tuple[bool, int, float]:
         frame = np.asarray(frame, dtype=np.float64).reshape(-1)
         if frame.size < PRE_L + HDR_L:                     # rtwm/detector.py:461-462
             return False, 0, 0.0
-        y = self._dev(frame.reshape(1, -1), np.float64)
-        ok, val, score = self.engine.header(y, self._dev(np.array([self._band_id(band)]), np.uint8),
-                                            self._dev(np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8))
+        y = dev(self.engine, frame.reshape(1, -1), np.float64)
+        ok, val, score = self.engine.header(y, dev(self.engine, np.array([self._band_id(band)]), np.uint8),
+                                            dev(self.engine, np.packbits(self.sec.pn_bits(0, HDR_L)).reshape(1, -1), np.uint8))
         return bool(ok[0].item()), int(val[0].item()), float(score[0].item())
 
     def _validator(self, frame_ctr: int):
@@ -491,21 +460,16 @@ class WatermarkDetector:
         ctrs = list(ctrs)
         if not ctrs:
             return []
-        y = self._dev(np.asarray(frame, dtype=np.float64).reshape(1, -1), np.float64)
+        y = dev(self.engine, np.asarray(frame, dtype=np.float64).reshape(1, -1), np.float64)
         return self._decode_pairs(_Frames(y, np.zeros(1, np.int64), np.zeros(1, np.int64)), [0] * len(ctrs), ctrs)
 
     def _decode_pairs_grouped(self, triples) -> list[list[bytes | None]]:
         """_decode_pairs for (frames, frame index, ctr) triples that may come from several clips (each group of equally long clips
         has its own _Frames): consecutive triples of one _Frames go through one call."""
         out: list = []
-        k = 0
-        while k < len(triples):
-            fr = triples[k][0]
-            m = k
-            while m < len(triples) and triples[m][0] is fr:
-                m += 1
-            out += self._decode_pairs(fr, [t[1] for t in triples[k:m]], [t[2] for t in triples[k:m]])
-            k = m
+        for _, run in itertools.groupby(triples, key=lambda t: id(t[0])):
+            run = list(run)
+            out += self._decode_pairs(run[0][0], [t[1] for t in run], [t[2] for t in run])
         return out
 
     def _pair_cap(self) -> int:
@@ -516,12 +480,7 @@ class WatermarkDetector:
     def _decode_pairs(self, frames, rows, ctrs) -> list[list[bytes | None]]:
         """Chunked front of _decode_pairs_chunk, so that a long candidate list never asks for gigabytes at once."""
         cap = self._pair_cap()
-        if len(ctrs) <= cap:
-            return self._decode_pairs_chunk(frames, rows, ctrs)
-        out: list = []
-        for k in range(0, len(ctrs), cap):
-            out += self._decode_pairs_chunk(frames, rows[k:k + cap], ctrs[k:k + cap])
-        return out
+        return [r for k in range(0, max(1, len(ctrs)), cap) for r in self._decode_pairs_chunk(frames, rows[k:k + cap], ctrs[k:k + cap])]
 
     def _decode_pairs_chunk(self, frames, rows, ctrs) -> list[list[bytes | None]]:
         """The same for (frame, counter) pairs: frames = _Frames, pair i = (frame rows[i] of it, ctrs[i]).
@@ -531,25 +490,18 @@ class WatermarkDetector:
         from .engine import select_payload
         import torch
         eng = self.engine
-        L = self._list_size
-        if L > eng.list_size_max:
-            raise NotImplementedError(f"list_size={L}: the HIP decoder supports list sizes up to {eng.list_size_max}")
         B = len(ctrs)
         j = np.asarray(rows, np.int64)
-        at = {"rows": self._dev(frames.rows[j], np.int32), "start": self._dev(frames.starts[j], np.int32)}
         # PN rows and band indices of the candidate counters straight from the device schedule (es_schedule_batch)
+        at = dev(eng, frames.rows[j], np.int32), dev(eng, frames.starts[j], np.int32)
         pn, bands = eng.schedule(self.sec._prng.sub_key, self._band_key, ctrs=torch.tensor(ctrs, dtype=torch.int64))
-        l0 = eng.llr(frames.y, bands, pn, variant=0, **at)
-        l1 = eng.llr(frames.y, bands, pn, variant=1, **at)
-        res = eng.scl(torch.cat((l0, -l0, l1, -l1), dim=0), list_size=L, skip_if_hard_ok=False)
+        res = decode_four(eng, frames.y, *at, pn, bands, self._list_size)
         key = getattr(self._aead, "_key", None)
         if key is not None:
             # validator + candidate selection on the GPU (es_select_batch): same rules as select_payload with
             # self._validator(ctr), without a Python callback per candidate
             payload, ok, _which = eng.select(res, key32=key, ctrs=torch.tensor(ctrs * 4, dtype=torch.int64))
-            payload = payload.cpu().numpy(); ok = ok.cpu().numpy()
-            if (ok == -2).any():
-                raise NativeError("es_scl_batch: some candidate records were not decoded (no free scratch-slab slot)")
+            payload = payload.cpu().numpy(); ok = check_decoded(ok.cpu().numpy())
             return [[payload[v * B + i].tobytes() if ok[v * B + i] == 1 else None for v in range(4)] for i in range(B)]
         out = []
         for i, ctr in enumerate(ctrs):
@@ -623,12 +575,27 @@ class LiveMonitor(LiveTable):
     def fs_target(self) -> int:
         return self._det.fs_target
 
-    def _walker(self, s: int) -> WatermarkDetector:
-        w = self._walkers.get(s)
-        if w is None:                                   # the detector's key, tables and engine, a session nonce and traces of its own
-            w = self._walkers[s] = copy.copy(self._det)
-            w.session_nonce, w._trace, w._hdr_trace = None, None, None
-        return w
+    @property
+    def engine(self):
+        return self._det.engine
+
+    def _fresh_walkers(self, ids) -> list:
+        """The walkers of streams `ids` -- the detector's key, tables and engine, a session nonce and traces of their own --, the traces
+        emptied for the call at hand."""
+        walkers = []
+        for s in map(int, ids):
+            w = self._walkers.get(s)
+            if w is None:
+                w = self._walkers[s] = copy.copy(self._det)
+                w.session_nonce = None
+            w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
+            walkers.append(w)
+        return walkers
+
+    def _window_scans(self, ids, chunks):
+        """One tick over streams `ids` -> (the scans of their windows under the detector's key, each window's absolute first sample)."""
+        tick = self.engine.monitor_step(self.table, ids, chunks)
+        return self._det._scans_of(SyncScan.from_monitor(tick), self._order, self.table.bands), (self.table.base_host[ids] + tick.offset[::tick.nb]).tolist()
 
     def push(self, chunks, streams=None, *, fs: int | None = None) -> list[bool]:
         """chunks[i], 1-D int16 or float32 at the rate its stream was opened with, continues stream streams[i] (None: one chunk per open
@@ -637,20 +604,14 @@ class LiveMonitor(LiveTable):
         that, a chunk that is not 1-D, longer than chunk_max or (at another rate) finalizing more than chunk_max samples, a stream
         named twice, outside the table or closed."""
         from .monitor import push_arguments
-        from .scan import SyncScan
         ids, arrs, _ = push_arguments(self.table, self.fs_target, chunks, streams, fs)
         if not ids.size:
             return []
-        det = self._det
-        tick = det.engine.monitor_step(self.table, ids, arrs)
-        scans = det._scans_of(SyncScan.from_monitor(tick), self._order, self.table.bands)
-        for i, s in enumerate(ids.tolist()):                                # a stream with an origin: estimates from absolute positions
+        scans, pos0 = self._window_scans(ids, arrs)
+        for sc, s, p0 in zip(scans, ids.tolist(), pos0):                    # a stream with an origin: estimates from absolute positions
             if self.table.origin_host[s] >= 0:
-                scans[i].ctr0, scans[i].pos0 = int(self.table.origin_host[s]), int(self.table.base_host[s] + tick.offset[tick.nb * i])
-        walkers = [self._walker(int(s)) for s in ids]
-        for w in walkers:
-            w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
-        return det._verify_scans(scans, [list(range(len(scans)))], self._order, walkers)
+                sc.ctr0, sc.pos0 = int(self.table.origin_host[s]), p0
+        return self._det._verify_scans(scans, [list(range(len(scans)))], self._order, self._fresh_walkers(ids))
 
     def acquire_streams(self, streams) -> np.ndarray:
         """The streams an acquire call names, checked on the host: None = every open stream without an origin; a named stream must be
@@ -677,15 +638,11 @@ class LiveMonitor(LiveTable):
         ids = self.acquire_streams(streams)
         if not ids.size or span[0] == span[1]:
             return [None] * int(ids.size)
-        from .scan import SyncScan
         det, tab = self._det, self.table
-        tick = det.engine.monitor_step(tab, ids, [np.zeros(0, np.float32)] * int(ids.size))         # no samples: the windows as they stand
-        scans = det._scans_of(SyncScan.from_monitor(tick), self._order, tab.bands)
-        pos0 = [int(tab.base_host[s] + tick.offset[tick.nb * i]) for i, s in enumerate(ids.tolist())]    # as push computes it
+        scans, pos0 = self._window_scans(ids, [np.zeros(0, np.float32)] * int(ids.size))       # no samples: the windows as they stand
+        plans = det._acquire_plan(scans, pos0, span, max_records)
         out = []
-        for s, plan in zip(ids.tolist(), det._acquire_plan(scans, pos0, span, max_records)):
-            w = self._walker(s)
-            w._trace, w._hdr_trace = ([], []) if self._trace else (None, None)
+        for s, plan, w in zip(ids.tolist(), plans, self._fresh_walkers(ids)):
             acq = det._acquire_walk(*plan, w)
             if acq is not None:
                 try:
@@ -706,17 +663,6 @@ class LiveMonitor(LiveTable):
         w = self._walkers.get(int(stream))
         return (None, None) if w is None else (w._trace, w._hdr_trace)
 
-    def add(self, n: int = 1, fs=None, ctr0=None) -> np.ndarray:
-        """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
-        fs_target); ctr0: their counter origins, one or one per stream (None: no origin)."""
-        from .monitor import origin_words
-        origin_words(ctr0, int(n))                                          # refused by name before the engine is asked
-        return self._det.engine.add_monitor_streams(self.table, n, fs, **({} if ctr0 is None else {"ctr0": ctr0}))
-
-    def close(self, streams) -> None:
-        """Free the slots of `streams` (their state, history and session nonce are dropped); a push to a closed stream raises."""
-        from .monitor import monitor_ids
-        ids = monitor_ids(self.table, streams)
-        self._det.engine.close_monitor_streams(self.table, ids)
-        for s in ids:
+    def _slots_changed(self, ids, closed: bool) -> None:
+        for s in ids if closed else ():                                     # a closed stream's session nonce and traces go with it
             self._walkers.pop(int(s), None)

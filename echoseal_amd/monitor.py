@@ -211,6 +211,21 @@ def origin_words(ctr0, n: int) -> np.ndarray:
     return np.array([-1 if v is None else v for v in counter_origins(ctr0, n, "stream")], np.int64).reshape(int(n))
 
 
+def origin_keywords(ctr0) -> dict:           # ctr0 as the keyword of open_monitor / add_monitor_streams; no origin: the call as it always was
+    return {} if ctr0 is None else {"ctr0": ctr0}
+
+
+def open_arguments(n: int, fs_target: int, *, bands, fs=None, window_s: float = 5.0, chunk_max: int | None = None, ctr0=None) -> dict:
+    """What both open_streams do before an engine is touched: window_s and chunk_max (default half a second) in samples at fs_target,
+    then by name a geometry that cannot work, a rate that cannot be served, an origin that is no counter -> RxEngine.open_monitor's keywords."""
+    window = int(round(float(window_s) * fs_target))
+    chunk_max = fs_target // 2 if chunk_max is None else int(chunk_max)
+    check_geometry(window, chunk_max)
+    stream_rates(int(n), fs, fs_target)
+    origin_words(ctr0, int(n))
+    return dict(window=window, chunk_max=chunk_max, bands=bands, fs=fs, **origin_keywords(ctr0))
+
+
 def host_table(n_streams: int, window: int, chunk_max: int, hist: int | None = None, bands=(0, 1, 2, 3), *, fs=None,
                fs_target: int | None = None, ctr0=None) -> MonitorTable:
     """The host half of a monitor table, checked; RxEngine.open_monitor adds the device arrays.  fs: the rate of every stream, or one per
@@ -311,10 +326,29 @@ def push_arguments(table: MonitorTable, target: int, chunks, streams=None, fs=No
 
 class LiveTable:
     """What LiveMonitor and LiveIdentifier say about their streams: both hold a MonitorTable as `table` and the rate the streams are
-    conditioned to as `fs_target`; stream ids are the table's slots."""
+    conditioned to as `fs_target`; stream ids are the table's slots.  Both also name their `engine`, and hear of slots that were
+    opened or closed through `_slots_changed`."""
 
     def __len__(self) -> int:
         return int(np.count_nonzero(self.table.live))
+
+    def add(self, n: int = 1, fs=None, ctr0=None) -> np.ndarray:
+        """n more fresh streams -> their ids; slots of closed streams are used first.  fs: their rate, one or one per stream (None:
+        fs_target); ctr0: their counter origins, one or one per stream (None: no origin)."""
+        origin_words(ctr0, int(n))                                          # refused by name before the engine is asked
+        ids = self.engine.add_monitor_streams(self.table, n, fs, **origin_keywords(ctr0))
+        self._slots_changed(ids, closed=False)
+        return ids
+
+    def close(self, streams) -> None:
+        """Free the slots of `streams` (state, history and what the owner kept per stream are dropped); a push to a closed stream raises."""
+        ids = monitor_ids(self.table, streams)
+        self.engine.close_monitor_streams(self.table, ids)
+        self._slots_changed(ids, closed=True)
+
+    def _slots_changed(self, ids: np.ndarray, closed: bool) -> None:
+        """Slots `ids` were just opened as fresh streams, or closed."""
+
 
     def position(self, stream: int) -> int:
         """Samples at fs_target stream `stream` has been verified over since it was opened: the samples received, for a stream at

@@ -1,7 +1,8 @@
 """The scan front end of WatermarkDetector and WatermarkIdentifier: from a list of clips with their rates to sync results with the
 peaks that can hold a frame.  Host code only: the clips of a call are cut into launches (cut_launches), a launch's samples reach the
 device in one place (Launch.rows) and one sync call finds its peaks (sync_launch).  Nothing here is keyed: header decodes and everything
-after them belong to the callers.
+after them belong to the callers, who share the host statement of the reference's try order (plan_tries) and the widths of the hop
+tables it reads.
 """
 from __future__ import annotations
 
@@ -15,7 +16,9 @@ PRE_L = 63               # chips of the sync template (utils.mseq_63)
 FRAME_LEN = 1215         # PRE_L + 128 header chips + 1024 code bits
 PEAK_LIMIT = 25          # rtwm/detector.py:108
 
-WIDE_DELTA = 200         # rtwm/detector.py:118: the widest counter window around a peak's estimate
+MAX_TRIES = 400          # rtwm/detector.py:107
+TIGHT_DELTA = 3          # rtwm/detector.py:131: the counter window around a peak's estimate when its header failed ...
+WIDE_DELTA = 200         # rtwm/detector.py:118: ... and the widest one
 CTR_END = 1 << 32        # frame counters are 32-bit words: the header carries their low 16 bits, the payload all of them
 
 
@@ -24,6 +27,41 @@ def counter_estimate(start: int, pos0: int = 0, ctr0: int = 0) -> int:
     of a stream marked from counter ctr0 -> ctr0 + round((pos0 + start) / 1215), in integers (1215 is odd: no ties).  At pos0 = ctr0 = 0
     it is rtwm/detector.py:117, round(start / 1215)."""
     return int(ctr0) + (2 * (int(pos0) + int(start)) + FRAME_LEN) // (2 * FRAME_LEN)
+
+
+def plan_tries(starts, hdr_ok, hdr_lo16, hops, pos0: int = 0, ctr0: int = 0):
+    """The reference's try order for one band row (rtwm/detector.py:105-142), stated once on the host.  starts: the row's peaks that can
+    hold a frame, in peak order; hdr_ok / hdr_lo16: their header results; hops(c): counter c hops to the row's band; pos0 / ctr0: as
+    for counter_estimate.  Counters stay inside [0, 2^32); MAX_TRIES tries end the row, between peaks or inside one.
+    -> ([(peak index, its counters)] in try order, peaks looked at)."""
+    tries, left = [], MAX_TRIES
+    for j, start in enumerate(starts):
+        if left <= 0:
+            break
+        est = counter_estimate(start, pos0, ctr0)
+        wide = range(max(0, est - WIDE_DELTA), min(est + WIDE_DELTA + 1, CTR_END))      # counters end at 2^32 - 1
+        if hdr_ok[j]:                                                       # rtwm/detector.py:122-127
+            lo16 = int(hdr_lo16[j])
+            cands = [c for c in wide if (c & 0xFFFF) == lo16 and hops(c)]
+        else:                                                               # :131-140
+            cands = [c for c in range(max(0, est - TIGHT_DELTA), min(est + TIGHT_DELTA + 1, CTR_END)) if hops(c)]
+            if not cands:
+                cands = [c for c in wide if hops(c)]
+        tries.append((j, cands[:left]))
+        left -= len(cands)
+    return tries, len(tries)
+
+
+def hop_width(samples: int) -> int:         # counters from 0 that the tries of a record of `samples` samples reach: the hop table of es_plan_batch
+    return -(-int(samples) // FRAME_LEN) + WIDE_DELTA + 1
+
+
+def hop_at_width(samples: int) -> int:      # the same from 200 below any window base's estimate: what es_plan_at_batch asks of a hop row
+    return -(-int(samples) // FRAME_LEN) + 2 * WIDE_DELTA + 2
+
+
+def rate_list(fs_in, n: int) -> list:        # `fs_in` of a batch call, one rate or one per clip, as a list of n
+    return list(fs_in) if isinstance(fs_in, (list, tuple)) else [fs_in] * n
 
 
 def counter_origins(ctr0, n: int, what: str = "clip") -> list:
@@ -51,7 +89,7 @@ def counter_origins(ctr0, n: int, what: str = "clip") -> list:
 def check_counter_reach(origin, samples: int, what: str = "clip") -> None:
     """Refuse an origin from which `samples` samples reach the end of the counter range: origin + ceil(samples / 1215) + 201 must not
     pass 2^32 - 1 (the widest candidate window of the last frame stays inside the counters that exist)."""
-    if origin is not None and int(origin) + -(-int(samples) // FRAME_LEN) + WIDE_DELTA + 1 > CTR_END - 1:
+    if origin is not None and int(origin) + hop_width(samples) > CTR_END - 1:
         raise ValueError(f"ctr0 = {int(origin)}: a {what} of {int(samples)} samples would reach counter ctr0 + ceil(samples / 1215) + 201 > 2^32 - 1 "
                          "(counters that wrap past 2^32 are out of scope)")
 
@@ -79,7 +117,8 @@ def ragged_buckets(lengths, rows_per_clip: int, budget: int) -> list[list[int]]:
     return out
 
 
-def _dev(eng, arr: np.ndarray, dtype):
+def dev(eng, arr: np.ndarray, dtype):
+    """A host array on the engine's device, contiguous and of `dtype`: the one upload helper of the receive side."""
     import torch
     return torch.from_numpy(np.ascontiguousarray(arr, dtype=dtype)).to(eng.device)
 
@@ -111,7 +150,7 @@ class Launch:
             host = np.zeros((len(self.clips), M), self.clips[0].dtype)
             for c, sg in enumerate(self.clips):
                 host[c, :sg.size] = sg
-        return _dev(eng, np.repeat(host, nb, axis=0), host.dtype), self.sizes
+        return dev(eng, np.repeat(host, nb, axis=0), host.dtype), self.sizes
 
 
 def cut_launches(clips, fs_list, fs_target: int, nb: int, condition, budget: int = RAGGED_ROW_SAMPLES) -> list[Launch]:
@@ -186,7 +225,7 @@ def sync_launch(eng, launch: Launch, band_ids) -> SyncScan:
     import torch
     nb = len(band_ids)
     x, sizes = launch.rows(eng, nb)
-    bid = _dev(eng, np.tile(np.asarray(band_ids, np.uint8), len(sizes)), np.uint8)
+    bid = dev(eng, np.tile(np.asarray(band_ids, np.uint8), len(sizes)), np.uint8)
     M = max(sizes)
     if min(sizes) < M:
         sy = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=False)

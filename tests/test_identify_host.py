@@ -49,7 +49,7 @@ def test_identifier_surface_needs_no_gpu():
 def test_counter_estimate_is_round():
     """(2 * start + 1215) // 2430 == round(start / 1215) for every start below 2^24 (and a spread above): 1215 is odd, so the
     quotient never lies on a tie and Python's round-half-even never comes into play."""
-    from echoseal_amd.identify import ctr_estimate
+    from echoseal_amd.scan import counter_estimate as ctr_estimate
     start = np.arange(1 << 24, dtype=np.int64)
     assert np.array_equal((2 * start + 1215) // 2430, np.rint(start / 1215).astype(np.int64))
     rng = np.random.default_rng(0)
