@@ -6,7 +6,8 @@ library per entry (echoseal_amd/libechoseal_hip_<id>.so, loaded through ES_LIB_V
 unmutated code already proves in range, and feeds no subscript, pointer, trip count, barrier, launch geometry or LDS size, removes no
 guard of a memory access and touches no atomic's address -- so the mutant can neither fault nor hang nor run longer than the original.
 `equivalent` (at most three entries) is the written argument that no input changes any output; such an entry is built and run but is
-allowed to survive.  tests/test_mutants_listed.py holds the table to the sources and to the suite.
+allowed to survive.  tests/test_mutants_listed.py holds the table to the sources and to the suite.  SCL_MUTANTS, further down, is a second
+table of the same kind for the list decoders.
 
 An entry in a header or body file counts for every translation unit that includes it (kernel_units in test_mutants_listed.py).
 
@@ -208,4 +209,99 @@ MUTANTS = [
            "Flips the sign g gives its first operand: an LLR value, in every list decoder, with no index derived from it."),
 ]
 
-BY_ID = {m.id: m for m in MUTANTS}
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The list decoders: the fine-grained decisions of es_scl.hip, es_scl_multi.hip, es_scl_wide.hip (es_scl_wide_large.hip
+# compiles the same kernel) and of the arithmetic they share, es_math.h and es_softplus_dev.h.  The same tuple and the same rules, with one
+# more: the decoders spin on slots and barriers, so no entry feeds a subscript, a slab, LDS or slot address (p8_get / p8_set, ptr_get, fp0,
+# myr, holder, parent, src, any W.sel / TBW / TBA / CB index), cnt, keep, nc, a trip count, the slot claim or release, a barrier or fence,
+# launch geometry, the ki & 127 table index, a DPP or swizzle control or an asm block; a tie rule is reversed (`<` -> `>`: still a strict
+# total order, the ranks stay a permutation), never made non-strict.  At most four entries are declared equivalent.
+# tests/test_mutants_listed.py holds the table to these rules.  `tools/mutant_audit.py --table scl` builds and runs it.
+_SL = "tests/test_softplus_sl_gpu.py"
+_SEDGE = "tests/test_gpu_scl_decision_edges.py"
+SCL_K = SCL + (_PARITY + "::test_scl_other_codes_vs_oracle",)                      # the run-time-K arms of the lane-per-path decoder
+SCL_HDR = SCL + (_PARITY + "::test_device_softplus_bits", _SL + "::test_device_f_edge_operands_bits")
+SCL_RANGE = SCL_HDR + (_PARITY + "::test_scl_softplus_fallback_ranges",)
+# with the tests written for the survivors of the first run (tests/test_gpu_scl_decision_edges.py)
+SCL_ZERO = SCL + (_SEDGE + "::test_zero_llrs_decide_the_hard_crc",)
+SCL_K0 = SCL_HDR + (_SEDGE + "::test_log1p_k_boundary_inside_the_tree",)
+SCL_CORNER_FIRST = SCL_HDR + (_SEDGE + "::test_log1p_corner_first_word_inside_the_tree",)
+SCL_CORNER_LAST = SCL_HDR + (_SEDGE + "::test_log1p_corner_last_word_inside_the_tree",)
+
+_RANK = ("Reverses the order of equal metrics in a rank: `<` and `>` on distinct indices are both strict total orders, so the ranks stay a "
+         "permutation of the same range and every guarded store under `rank < keep` or into the rows below cnt writes the same set of slots.")
+_HARD = "A comparison inside a value computation: one bit of the hard decision's word, which is only folded, gathered into bytes and stored."
+_PEN = "Chooses which of two softplus values already computed for this path becomes a penalty: a float64 that is only added, compared and stored."
+_CRC = "A comparison inside a value computation: the stored CRC verdict of one candidate row, from bytes already read."
+_HOK = ("Flips the wave-uniform CRC verdict of the hard decision: it is stored, and with skip_if_hard_ok it chooses between the two paths "
+        "(zeroed rows or the list) that the unmutated kernel takes for other frames of the same launch.")
+_RNG = ("Moves the bound of the range flag of the straight-line softplus: operands in [512, 1024) then keep the straight-line value, which is "
+        "arithmetic and one table read under the untouched ki & 127 mask, in place of the generic one.")
+_DEAD = ("lp_odd is read at an odd leaf alone, and holds what the decision of its even sibling stored.  The frozen arm stores it only where an "
+         "even leaf is decided leaf by leaf and is frozen: every other frozen even leaf opens an all-frozen aligned block of two or more "
+         "leaves (the rate-0 arm, which takes the odd leaf's term from L2last), so that is leaf 0, or an even leaf whose odd sibling "
+         "carries information.  No Polar(1024, K) frozen set has either, K = 9 .. 1024: leaf 0 always carries information and a frozen "
+         "even leaf always has a frozen odd sibling (tests/test_mutants_listed.py::test_no_code_has_a_frozen_even_leaf_before_an_information_leaf "
+         "enumerates them), and these two kernels run the K = 448 code only.  The value the line stores is never read.")
+_SEL = "A threshold on the high word of a float64 that selects among values all of which the straight-line softplus has already computed."
+
+SCL_MUTANTS = [
+    # ---- es_scl.hip: one wave per frame
+    Mutant("s1_bit_tie", "es_scl.hip", "(mk == mc && k < cc_)", "(mk == mc && k > cc_)", SCL, _RANK),
+    Mutant("s1_final_tie", "es_scl.hip", "(mk == metric && k < path)", "(mk == metric && k > path)", SCL, _RANK),
+    Mutant("s1_hard_zero", "es_scl.hip", "__ballot(v > 0.0)", "__ballot(v >= 0.0)", SCL_ZERO, _HARD),
+    Mutant("s1_odd_penalty_info", "es_scl.hip", "(q & 1) ? sp_diff : sp_sum", "(q & 1) ? sp_sum : sp_diff", SCL, _PEN),
+    Mutant("s1_odd_penalty_frozen", "es_scl.hip", "lp_odd = sp_sum;", "lp_odd = sp_diff;", SCL, _PEN, equivalent=_DEAD),
+    Mutant("s1_cand_crc", "es_scl.hip", "crc8_bytes(W.outb[path], ES_INFO_BYTES) == W.outb[path][ES_INFO_BYTES];",
+           "(crc8_bytes(W.outb[path], ES_INFO_BYTES) & 0x7fu) == (W.outb[path][ES_INFO_BYTES] & 0x7fu);", SCL, _CRC),
+    Mutant("s1_hard_crc", "es_scl.hip", "== W.outb[0][ES_INFO_BYTES]);", "!= W.outb[0][ES_INFO_BYTES]);", SCL, _HOK),
+    Mutant("s1_rate0_penalty", "es_scl.hip", "double pen = (P >= 2 && (q & 1)) ? L2last : lp;", "double pen = (P >= 2 && (q & 1)) ? lp : L2last;", SCL,
+           _PEN),
+    # ---- es_scl_multi.hip: several frames per wave
+    Mutant("sm_bit_tie", "es_scl_multi.hip", "(mk == mc && k < cc_)", "(mk == mc && k > cc_)", SCL, _RANK),
+    Mutant("sm_final_tie", "es_scl_multi.hip", "(mk == metric && k < pl)", "(mk == metric && k > pl)", SCL, _RANK),
+    Mutant("sm_hard_zero", "es_scl_multi.hip", "__ballot(v > 0.0)", "__ballot(v >= 0.0)", SCL_ZERO, _HARD),
+    Mutant("sm_odd_penalty_info", "es_scl_multi.hip", "(q & 1) ? sp_diff : sp_sum", "(q & 1) ? sp_sum : sp_diff", SCL, _PEN),
+    Mutant("sm_odd_penalty_frozen", "es_scl_multi.hip", "lp_odd = sp_sum;", "lp_odd = sp_diff;", SCL, _PEN, equivalent=_DEAD),
+    Mutant("sm_cand_crc", "es_scl_multi.hip", "crc8_bytes(W.outb[path], ES_INFO_BYTES) == W.outb[path][ES_INFO_BYTES];",
+           "(crc8_bytes(W.outb[path], ES_INFO_BYTES) & 0x7fu) == (W.outb[path][ES_INFO_BYTES] & 0x7fu);", SCL, _CRC),
+    Mutant("sm_hard_crc", "es_scl_multi.hip", "== W.outb[0][ES_INFO_BYTES]);", "!= W.outb[0][ES_INFO_BYTES]);", SCL, _HOK),
+    Mutant("sm_rate0_penalty", "es_scl_multi.hip", "double pen = (q & 1) ? L2last : lp;", "double pen = (q & 1) ? lp : L2last;", SCL, _PEN),
+    # ---- es_scl_wide.hip: one lane per path (es_scl_wide_large.hip compiles it for two more capacities)
+    Mutant("sw_final_tie", "es_scl_wide.hip", "(mk == metric && k < pl)", "(mk == metric && k > pl)", SCL, _RANK),
+    Mutant("sw_hard_zero", "es_scl_wide.hip", "__ballot(v > 0.0)", "__ballot(v >= 0.0)", SCL_ZERO, _HARD),
+    Mutant("sw_odd_penalty_wave", "es_scl_wide.hip", "bit ? sd : ss", "bit ? ss : sd", SCL, _PEN),
+    Mutant("sw_odd_penalty_block", "es_scl_wide.hip", "xsp[xb][bit ? 0 : 1]", "xsp[xb][bit ? 1 : 0]", SCL,
+           "Chooses which of the two softplus rows this step published, both written for every lane under the same barrier, becomes a "
+           "penalty: the subscript stays one of the constants 0 and 1 that the unmutated line uses.",),
+    Mutant("sw_odd_penalty_frozen", "es_scl_wide.hip", "lp_odd = sp_sum;", "lp_odd = sp_diff;", SCL, _PEN),
+    Mutant("sw_cand_crc", "es_scl_wide.hip", "(wd[MWIN_W - 1] & 0xffu)", "(wd[MWIN_W - 1] & 0x7fu)", SCL, _CRC),
+    Mutant("sw_hard_crc", "es_scl_wide.hip", "== hbytes[ES_INFO_BYTES]);", "!= hbytes[ES_INFO_BYTES]);", SCL, _HOK),
+    Mutant("sw_cand_crc_k", "es_scl_wide.hip", "(uint8_t)(reg == ((((lo << 8) | hi) >> (8 - rem)) & 0xffu));",
+           "(uint8_t)(reg == ((((lo << 8) | hi) >> (8 - rem)) & 0x7fu));", SCL_K, _CRC),
+    Mutant("sw_hard_crc_k", "es_scl_wide.hip", "ok = (reg == (", "ok = (reg != (", SCL_K, _HOK),
+    Mutant("sw_window_start", "es_scl_wide.hip", "const bool wstart = (info_idx & 31) == 0;", "const bool wstart = (info_idx & 31) == 1;", SCL,
+           "Moves the step at which a trace-back window's history word and ancestor are reset: both are stored values, the ancestor is "
+           "a lane index below LF and is masked by LF - 1 where the final trace-back reads it."),
+    Mutant("sw_odd_leaf_g_bit", "es_scl_wide.hip", "(b0 >> 1) & 1u", "(b0 >> 2) & 1u", SCL,
+           "Takes another bit of the path's partial-sum word as the sign g gives its first operand: an LLR value with no index derived from it."),
+    Mutant("sw_fold", "es_scl_wide.hip", "cw = (left ^ cw) | (cw << S);", "cw = (left & cw) | (cw << S);", SCL,
+           "Changes the bits of a partial-sum word, which are only stored, folded again and used as the signs of g; the words' positions are untouched."),
+    # ---- es_softplus_dev.h: the straight-line softplus and f of the lane-per-path decoder
+    Mutant("sd_leaf_range", "es_softplus_dev.h", "*bad |= !(al < 512.0);", "*bad |= !(al < 1024.0);", SCL_RANGE, _RNG),
+    Mutant("sd_f_range", "es_softplus_dev.h", "(__builtin_fabs(d1) < 512.0) & (__builtin_fabs(sum) < 512.0)",
+           "(__builtin_fabs(d1) < 1024.0) & (__builtin_fabs(sum) < 1024.0)", SCL_RANGE, _RNG),
+    Mutant("sd_slg_range", "es_softplus_dev.h", "if (!(__builtin_fabs(d1) < 512.0)) L1 =", "if (!(__builtin_fabs(d1) < 1024.0)) L1 =", SCL_RANGE, _RNG),
+    Mutant("sd_tiny29", "es_softplus_dev.h", "hy < 0x3e200000", "hy < 0x3e100000", SCL_HDR, _SEL),
+    Mutant("sd_k0", "es_softplus_dev.h", "hy < 0x3FDA827A", "hy < 0x3FDA827B", SCL_K0, _SEL),
+    Mutant("sd_corner", "es_softplus_dev.h", "hu0 > 0x3FFFFFFCu", "hu0 > 0x3FFFFFFDu", SCL_CORNER_FIRST, _SEL),
+    # ---- es_math.h: the softplus of the other two decoders and of every cold path
+    Mutant("em_tiny29", "es_math.h", "hy < 0x3e200000", "hy < 0x3e100000", SCL_HDR, _SEL),
+    Mutant("em_k0", "es_math.h", "hy < 0x3FDA827A", "hy < 0x3FDA827B", SCL_K0, _SEL),
+    Mutant("em_corner", "es_math.h", "(hu0 - 0x3FFFFFFDu) < 3u", "(hu0 - 0x3FFFFFFDu) < 2u", SCL_CORNER_LAST, _SEL),
+    Mutant("em_fast_range", "es_math.h", "*ok = (__builtin_fabs(t) < 512.0);", "*ok = (__builtin_fabs(t) < 1024.0);", SCL_RANGE, _RNG),
+    Mutant("em_lp1", "es_math.h", "#define ES_LP1 6.666666666666735130e-01", "#define ES_LP1 6.666666666666736130e-01", SCL_HDR,
+           "Moves log1p's first polynomial coefficient to the next double (0x1.5555555555593p-1 -> ...94p-1): a float64 that is only multiplied and added."),
+]
+
+BY_ID = {m.id: m for m in MUTANTS + SCL_MUTANTS}

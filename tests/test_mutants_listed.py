@@ -145,3 +145,79 @@ def test_the_saturation_margin_cannot_move_a_threshold():
     for m in (2.5, 2.0, 1.5, 1.0, 0.5, 0.0):
         assert wrong(m) == [], m
     assert wrong(-30.0)                                                      # the enumeration can find one: a large margin of the wrong sign
+
+
+# ---------------------------------------------------------------------------------------------------------------- the list decoders
+SCL_FILES = ("es_scl.hip", "es_scl_multi.hip", "es_scl_wide.hip", "es_math.h", "es_softplus_dev.h")
+# what computes or is a subscript, a slab, LDS or slot address, a trip count or a barrier in the list decoders: no entry's text may name one
+SCL_INDEX_NAMES = ("p8_get", "p8_set", "ptr_get", "ptr_set", "fp0", "myr", "holder", "parent", "src", "W.sel", "TBW", "TBA", "CB[", "cnt", "keep",
+                   "nc", "info_idx +", "++info_idx", "dirty", "group_sync", "__syncthreads", "wave_fence", "ki & 127", "ES_EXP_TAB_LDS_ADDR",
+                   "dpp", "swizzle", "bpermute", "asm", "<<<", "atomic", "slot", "cursor")
+
+
+def asm_spans(text):
+    """[start, end) of every `asm(` ... `)` or `asm volatile(` ... `)` block of a source text, parentheses balanced."""
+    spans = []
+    for m in re.finditer(r"\basm\s*(?:volatile\s*)?\(", text):
+        depth, i = 1, m.end()
+        while depth and i < len(text):
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        spans.append((m.start(), i))
+    return spans
+
+
+def names_an_index(text, names=SCL_INDEX_NAMES):
+    """The index helpers, counts and barriers that a mutant's text names; a plain word counts only as a whole identifier."""
+    return [n for n in names if (re.search(r"(?<![A-Za-z0-9_])" + re.escape(n) + r"(?![A-Za-z0-9_])", text) if re.fullmatch(r"\w+", n) else n in text)]
+
+
+def test_the_list_decoder_table_fits_the_sources_and_the_suite():
+    found = problems(M.SCL_MUTANTS)
+    assert not found, "\n".join(found)
+    assert not {m.id for m in M.SCL_MUTANTS} & {m.id for m in M.MUTANTS}
+    assert len(M.BY_ID) == len(M.MUTANTS) + len(M.SCL_MUTANTS) and all(M.BY_ID[m.id] is m for m in M.MUTANTS + M.SCL_MUTANTS)
+
+
+def test_the_list_decoder_table_covers_every_file():
+    assert 28 <= len(M.SCL_MUTANTS) <= 40
+    per_file = {f: sum(m.file == f for m in M.SCL_MUTANTS) for f in SCL_FILES}
+    assert all(n >= 4 for n in per_file.values()), per_file
+    assert sum(per_file.values()) == len(M.SCL_MUTANTS), sorted({m.file for m in M.SCL_MUTANTS} - set(SCL_FILES))
+    equivalent = [m.id for m in M.SCL_MUTANTS if m.equivalent is not None]
+    assert len(equivalent) <= 4, equivalent
+
+
+def test_no_list_decoder_entry_touches_an_asm_block_or_an_index():
+    for m in M.SCL_MUTANTS:
+        text = open(os.path.join(CSRC, m.file)).read()
+        at = text.index(m.old)
+        inside = [s for s in asm_spans(text) if s[0] < at + len(m.old) and at < s[1]]
+        assert not inside, f"{m.id}: `old` lies inside an asm block"
+        assert not asm_spans(m.new) and "asm" not in m.new, f"{m.id}: `new` holds an asm block"
+        named = names_an_index(m.old) + names_an_index(m.new)
+        assert not named, f"{m.id}: names {named}"
+    # the two checks find what they look for
+    src = 'x = a; asm volatile("v_mov_b64 %0, %1" : "=v"(x) : "s"(K)); y = b;'
+    (lo, hi), = asm_spans(src)
+    assert src[lo:hi].startswith("asm volatile(") and src[hi:] == "; y = b;"
+    assert names_an_index("W.sel[fp0 + rank] = c") == ["fp0", "W.sel"] and names_an_index("rank < keep") == ["keep"]
+    assert names_an_index("(mk == mc && k < cc_)") == [] and names_an_index("nc_") == [] and names_an_index("const int nc = 2 * cnt;") == ["cnt", "nc"]
+
+
+def test_no_code_has_a_frozen_even_leaf_before_an_information_leaf():
+    """Why `lp_odd = sp_sum` -> `sp_diff` in the frozen arm of es_scl.hip and es_scl_multi.hip is declared equivalent: the line's value is
+    read only after a frozen even leaf that is decided leaf by leaf, which is leaf 0 or an even leaf whose odd sibling carries information
+    (any other frozen even leaf opens a rate-0 block).  The oracle's frozen sets, which tests/test_oracle_polar.py pins to the reference
+    and the device tables are compared with, have neither for any K the engine accepts."""
+    from oracle import oracle as O
+    O.build()
+    for K in range(9, 1025):
+        with O.code_k(K):
+            frozen, _ = O.polar_tables()
+        assert int(frozen.sum()) == 1024 - K and not frozen[0], K
+        assert not (frozen[0::2] & ~frozen[1::2]).any(), K
+    for name in ("es_scl.hip", "es_scl_multi.hip"):                          # the block arm is taken at every even leaf but leaf 0
+        text = open(os.path.join(CSRC, name)).read()
+        assert re.search(r"if \(\(i & 1\) == 0 && (P >= 2 && )?i != 0\) \{", text), name
+    assert "launch_scl<64>" not in open(os.path.join(CSRC, "es_scl.hip")).read()       # P = 64 / L >= 2 in es_scl.hip

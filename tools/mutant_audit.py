@@ -4,6 +4,8 @@
   tools/mutant_audit.py build [ids...]   no GPU: one library per entry of tests/mutants.py, echoseal_amd/libechoseal_hip_<id>.so
   tools/mutant_audit.py run [ids...]     on the GPU: each entry's killers against its library, results into profiles/mutants.json
 
+Without ids both take a whole table: `--table dsp` (the default) is MUTANTS, `--table scl` SCL_MUTANTS, the list decoders.
+
 build copies echoseal_amd/csrc to a scratch directory per entry, applies the entry's substitution there (it must apply exactly once),
 compiles only the translation units that include the changed file, with the Makefile's flags and per-file flags, and links them with
 the stock objects.  Compiles and links share one pool of 16 jobs.  No mutated source is kept.
@@ -16,7 +18,8 @@ other status, a status 1 without a failed test (errors in fixtures or at collect
 `HSA_STATUS_ERROR` in the child's output, stops the whole run there: nothing further is started, the records
 so far are in the file, and the run is continued (`--resume FILE`, with the remaining ids) only after the cause has been read from what
 it left.  Nothing is ever tried twice.  After the last entry, a survivor that is not declared equivalent gets one more run against the
-whole `-m gpu` suite, under the suite's own unmutated time (measured when the first survivor needs it) with the same margin.
+whole `-m gpu` suite, under the suite's own unmutated time (measured when the first survivor needs it) with the same margin;
+`--suite-max N` gives that run to the first N such survivors only, in table order, and records the others "suite_status": "not run".
 Before the first child starts, run refuses an entry whose library has not been built.
 """
 import argparse
@@ -42,11 +45,14 @@ BASELINE_LIMIT = 600                       # the unmutated killers of one set; t
 SUITE_LIMIT = 1100
 
 
-def chosen(ids):
+TABLES = {"dsp": lambda: M.MUTANTS, "scl": lambda: M.SCL_MUTANTS}
+
+
+def chosen(ids, table="dsp"):
     unknown = [i for i in ids if i not in M.BY_ID]
     if unknown:
         sys.exit(f"no such entry in tests/mutants.py: {unknown}")
-    return [M.BY_ID[i] for i in ids] if ids else list(M.MUTANTS)
+    return [M.BY_ID[i] for i in ids] if ids else list(TABLES[table]())
 
 
 # ---------------------------------------------------------------------------------------------------------------- build
@@ -102,7 +108,7 @@ def build_one(m, pool, hipcc, arch, flags, per_file, srcs):
 
 
 def cmd_build(args):
-    todo = chosen(args.ids)
+    todo = chosen(args.ids, args.table)
     subprocess.run(["make", "-s", f"-j{JOBS}", "-C", CSRC], check=True)                      # the stock objects and library
     hipcc, arch, flags, per_file, srcs = makefile()
     # one pool of JOBS jobs for every compile and every link; an entry's driver thread copies the sources and waits for its jobs
@@ -134,7 +140,7 @@ class Stop(Exception):
 
 
 def cmd_run(args):
-    todo = chosen(args.ids)
+    todo = chosen(args.ids, args.table)
     records = []
     if args.resume:
         records = json.load(open(args.resume))
@@ -187,9 +193,17 @@ def cmd_run(args):
             print(f"{rec['status']:9s} {sec:6.1f} s  {m.id}  {failed or ''}", flush=True)
             checked(m.id, status, out, (0, 1), failed)
         # survivors of their own killers, the declared equivalents apart: does any test of the whole suite notice them?
+        suite_runs = 0
         for m in todo:
             rec = next(r for r in records if r["id"] == m.id)
-            if rec["status"] != "survived" or rec["equivalent"] or "suite_status" in rec:
+            if rec["status"] != "survived" or rec["equivalent"]:
+                continue
+            suite_runs += 1                                                    # --suite-max counts survivors in table order, a resumed file's included
+            if rec.get("suite_status", "not run") != "not run":
+                continue
+            if args.suite_max is not None and suite_runs > args.suite_max:
+                rec["suite_status"] = "not run"
+                save()
                 continue
             if base["suite_seconds"] is None:
                 s_status, s_sec, s_failed, s_out = child(SUITE_LIMIT, None, ["tests"])
@@ -223,6 +237,12 @@ def main():
     b.add_argument("ids", nargs="*")
     r = sub.add_parser("run")
     r.add_argument("ids", nargs="*")
+    for p in (b, r):
+        p.add_argument("--table", choices=sorted(TABLES), default="dsp",
+                       help="the table taken when no ids are given: dsp = MUTANTS, scl = SCL_MUTANTS, the list decoders (DESIGN 2.3)")
+    r.add_argument("--suite-max", type=int, default=None, metavar="N",
+                   help="only the first N survivors that are not declared equivalent, in table order, get the whole-suite run; "
+                        "the others are recorded \"suite_status\": \"not run\" (default: all of them)")
     r.add_argument("--out", default=os.path.join(ROOT, "profiles", "mutants.json"))
     r.add_argument("--resume", help="the file of a run that stopped or covered other ids: its records are kept, its baseline times reused")
     args = ap.parse_args()
