@@ -114,7 +114,8 @@ MUTANTS = [
     Mutant("plan_pm3_width", "es_keyring.hip", "else v = lane < 7 && c >= 0 && c < C", "else v = lane < 6 && c >= 0 && c < C", PLAN,
            "Drops one lane from the narrow window: fewer candidates, the same guards, the output position still under the untouched "
            "pos < ES_MAX_TRIES."),
-    Mutant("plan_wide_lo", "es_keyring.hip", "est - 200 > 0 ? est - 200 : 0,", "est - 199 > 0 ? est - 199 : 0,", PLAN,
+    Mutant("plan_wide_lo", "es_keyring.hip", "est - 200 > 0 ? est - 200 : 0,", "est - 199 > 0 ? est - 199 : 0,",
+           PLAN + ("tests/test_gpu_search_traces.py::test_identifier_follows_the_reference_under_every_key",),
            "Moves the wide window's first counter by one; its 400 to 402 counters take the same seven trips of 64, every hop read "
            "stays guarded by c < C and every store by the untouched pos < ES_MAX_TRIES."),
     Mutant("plan_wide_hi", "es_keyring.hip", "hi = est + 200;", "hi = est + 201;", PLAN,
