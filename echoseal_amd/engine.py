@@ -15,9 +15,7 @@ sync + LLR (variant 0, known start/counter) + SCL-L.
 """
 from __future__ import annotations
 
-import os
 import sys
-import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -28,38 +26,6 @@ from .monitor import MonitorChain, MonitorLayout, MonitorTable, MonitorTick, mon
 from .tables import pack_tables
 from .transmit import (EMBED_ROW_SAMPLES, EmbedClip, EmbedLayout, EmbedResult, StreamLayout, StreamTable, TxChain, _ptr, embed_launches, embed_layout,
                        stream_layout)      # the transmit chain's public names stay importable from here
-
-# The streaming pipelines run on up to eight HIP streams.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues
-# (default 4) and streams that share a queue serialise, silently.  The variable belongs to the process's environment: this module reads
-# it and never sets it; DecodePipeline warns when more streams are alive than the budget it names.
-_HWQ_ENV_AT_IMPORT = os.environ.get("GPU_MAX_HW_QUEUES")      # None: the runtime's default
-_LIVE_STREAMS = [0]                                            # streams made through pipeline_streams and not yet given back (a plain count:
-                                                               # weak references to torch.cuda.Stream objects crash the interpreter's final GC)
-
-
-def hw_queue_budget() -> int:
-    """Hardware queues the process's HIP streams are spread over, as far as this module can tell: GPU_MAX_HW_QUEUES as it stood
-    when the module was imported, else the runtime's default of 4."""
-    try:
-        return max(1, int(_HWQ_ENV_AT_IMPORT)) if _HWQ_ENV_AT_IMPORT is not None else 4
-    except ValueError:
-        return 4
-
-
-def pipeline_streams(device, n: int, priority: int = 0) -> list:
-    """n new HIP streams, counted against the hardware-queue budget (DecodePipeline makes its own through this; a process that builds
-    several pipelines makes the streams once and hands them to each: DecodePipeline(streams=...))."""
-    out = [torch.cuda.Stream(device, priority=priority) for _ in range(n)]
-    _LIVE_STREAMS[0] += n
-    if _LIVE_STREAMS[0] > hw_queue_budget():
-        import gc
-        gc.collect()                                # (pipelines that are garbage but not yet collected still count their streams)
-    if _LIVE_STREAMS[0] > hw_queue_budget():
-        warnings.warn(f"DecodePipeline: {_LIVE_STREAMS[0]} pipeline streams are alive but the HIP runtime has {hw_queue_budget()} hardware queues "
-                      f"(GPU_MAX_HW_QUEUES{'=' + _HWQ_ENV_AT_IMPORT if _HWQ_ENV_AT_IMPORT else ' not set'}): streams that share a "
-                      "queue serialise.  Hand existing streams to further pipelines (streams=...).", RuntimeWarning, stacklevel=3)
-    return out
-
 
 _FRAME_DTYPES = {torch.int16: nat.ES_DTYPE_I16, torch.float32: nat.ES_DTYPE_F32}     # what the band-pass reads
 _RESAMPLE_DTYPES = {torch.int16: (nat.ES_DTYPE_I16, np.int16), torch.float32: (nat.ES_DTYPE_F32, np.float32),
@@ -292,6 +258,32 @@ class RxEngine(TxChain, MonitorChain):
                                                           _ptr(y32), _ptr(thr), _ptr(peaks), _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()),
                       "es_front_batch")
         return y, thr, peaks, npeaks, flags, out
+
+    def front_steps(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | str | None = None,
+                    out: torch.Tensor | None = None, events=None, side: torch.cuda.Stream | None = None):
+        """The same sequence as three library calls on the current stream, -> what `front` returns: the one place it is written out
+        (decode_batch and every DecodePipeline arrangement run it).  events: two timing events, recorded before and after the sync.
+        out: the rows the demodulator writes.  side: a stream the demodulator runs on beside the sync -- both only need y --, forked
+        after the band-pass and joined before returning (the current stream itself: no fork, the demodulator still ahead of the sync)."""
+        y, y32 = self.bpf2(frames, band)
+        peak = isinstance(start, str)
+        beside = side is not None and not peak
+        if beside:
+            cur = torch.cuda.current_stream(self.device)
+            if side != cur:
+                side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                llr = self.llr(y, band, pn_rows, start=start, variant=0, out=out)
+        if events is not None:
+            events[0].record()
+        thr, peaks, npeaks, flags = self.sync_fused(y, y32, band)        # correlation screen + exact picking, one kernel
+        if events is not None:
+            events[1].record()
+        if not beside:                  # (start="peak": at the first detected peak, read in place from the peaks, so behind the sync)
+            llr = self.llr(y, band, pn_rows, start=start, peaks=peaks if peak else None, variant=0, out=out)
+        elif side != cur:
+            cur.wait_stream(side)
+        return y, thr, peaks, npeaks, flags, llr
 
     def reserve(self, B_max: int, T_max: int) -> None:
         """Size the context's workspaces once (es_reserve): afterwards the sync entry points only enqueue."""
@@ -868,324 +860,25 @@ class RxEngine(TxChain, MonitorChain):
             _peak_start(start)
         elif getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(self.device)
-        fast = (not keep_corr) and frames.shape[1] - 62 <= self.FAST_MAX_LAGS
-        if fast:      # float32 correlation screen + exact float64 fix-ups (identical thr / peaks)
-            y, y32 = self.bpf2(frames, band)
+        if (not keep_corr) and frames.shape[1] - 62 <= self.FAST_MAX_LAGS:
+            corr = None      # float32 correlation screen + exact float64 fix-ups (identical thr / peaks)
+            y, thr, peaks, npeaks, _flags, llr = self.front_steps(frames, band, pn_rows, start=start, side=None if peak else self._side)
         else:
             y = self.bpf(frames, band)
-        if not peak:
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):      # the demodulator only needs y: it runs beside sync
-                llr = self.llr(y, band, pn_rows, start=start, variant=0)
-        if fast:
-            corr = None
-            thr, peaks, npeaks, _flags = self.sync_fused(y, y32, band)
-        else:
+            if not peak:
+                self._side.wait_stream(main)
+                with torch.cuda.stream(self._side):      # the demodulator only needs y: it runs beside sync
+                    llr = self.llr(y, band, pn_rows, start=start, variant=0)
             corr = self.xcorr(y, band)
             thr, peaks, npeaks = self.pick(corr)
-        if peak:
-            llr = self.llr(y, band, pn_rows, start="peak", peaks=peaks, variant=0)
-        else:
-            main.wait_stream(self._side)             # join before SCL, which wants the chip to itself
-            llr.record_stream(main)
+            if peak:
+                llr = self.llr(y, band, pn_rows, start="peak", peaks=peaks, variant=0)
+            else:
+                main.wait_stream(self._side)             # join before SCL, which wants the chip to itself
+        if not peak:
+            llr.record_stream(main)                          # (allocated on the side stream, read on the caller's from here on)
         scl = self.scl(llr, list_size=list_size, skip_if_hard_ok=True)
         return SyncResult(y, corr if keep_corr else None, thr, peaks, npeaks), llr, scl
-
-
-class DecodePipeline:
-    """Streaming form of `RxEngine.decode_batch`: several batches in flight.  Batches are independent; per batch the kernels'
-    inputs and results are those of decode_batch in every arrangement.  Three arrangements:
-
-      * group=G (the throughput arrangement, bench.py's headline): the front ends (band-pass, fused sync, demodulator) of G
-        consecutive batches run on `lanes` high-priority HIP streams and fill one LLR buffer; ONE list-decoder launch -- one
-        lane per path, 64/L frames per wave, the mapping with the fewest instructions per frame -- decodes the group on one
-        of `scl_streams` further streams.  A batch's list-decoder rows are a slice of its group's result
-        (`GroupTicket.result()`), complete when the group's launch is; `synchronize()` / `wait` decode an incomplete group.
-      * lanes=K: K independent whole-chain lanes, each one HIP stream with its own context that runs band-pass .. list decoder
-        of its batches (k, k+K, ...) in order; rows of a batch within a few milliseconds of its submission.
-      * neither (round 1): the front end on one stream (LLR on a side stream), the list decoder on one of `scl_streams`
-        further streams, at most `depth` batches in flight.
-
-    Results are complete after `wait(result)` / `synchronize()`.  Beyond hw_queue_budget() live HIP streams, streams share
-    hardware queues and serialise: pass `streams=` (lanes: a list; grouped: (front-end streams, list-decoder streams)) to build a further pipeline on
-    existing ones; more live pipeline streams than hardware queues raises a RuntimeWarning (hw_queue_budget)."""
-
-    def __init__(self, eng: "RxEngine", *, list_size: int = 8, scl_streams: int = 2, depth: int | None = None, lanes: int = 0,
-                 side_stream: bool = True, group: int = 0, streams=None):
-        self.eng = eng
-        self.list_size = int(list_size)
-        dev = eng.device
-        self._own_streams = 0                         # streams this pipeline made itself (given back to the budget when it is collected)
-        self._build(eng, dev, scl_streams, depth, lanes, side_stream, group, streams)
-
-    def _mk(self, device, n: int, priority: int = 0) -> list:
-        self._own_streams += n
-        return pipeline_streams(device, n, priority)
-
-    def __del__(self):  # pragma: no cover
-        try:
-            _LIVE_STREAMS[0] -= self._own_streams
-        except Exception:
-            pass
-
-    def _build(self, eng, dev, scl_streams, depth, lanes, side_stream, group, streams) -> None:
-        # `group` > 0: the throughput arrangement -- the front ends (band-pass .. demodulator) of `group` consecutive batches
-        # run on `lanes` front streams and write their LLR rows into ONE buffer, and ONE list-decoder launch (on one of
-        # `scl_streams` streams, own context, one lane per path: es_set_option "scl_lanes" = 1) decodes the whole group:
-        # that mapping needs tens of thousands of frames per launch to fill the chip, which a 1 024-frame batch cannot give it.
-        # Per batch the kernels' inputs and results are those of decode_batch; a batch's list-decoder rows are complete when
-        # its group's launch is (GroupTicket.result() / wait / synchronize flush an incomplete group).
-        self.group = max(0, int(group))
-        if self.group:
-            self.lanes = max(1, int(lanes) or 4)
-            nb = max(1, int(scl_streams))
-            # the short front-end kernels get dispatch priority: they must slip in whenever list-decoder waves leave
-            # `streams` = (front-end streams, list-decoder streams) to run on instead of new ones
-            self.lane_streams = list(streams[0])[:self.lanes] if streams is not None else self._mk(dev, self.lanes, priority=-1)
-            if len(self.lane_streams) != self.lanes:
-                raise ValueError("streams: one front-end stream per lane")
-            self.lane_engs = [eng] + [RxEngine(dev, list_size_max=0) for _ in range(self.lanes - 1)]     # front-end contexts: no list-decoder scratch
-            self.backs = list(streams[1])[:nb] if streams is not None else self._mk(dev, nb)
-            if len(self.backs) != nb:
-                raise ValueError("streams: one list-decoder stream per scl_streams")
-            self.scl_engs = [RxEngine(dev, list_size_max=max(8, self.list_size)) for _ in range(nb)]
-            for e in self.scl_engs:                   # kernel by launch size: a full group runs one lane per path, a lone batch one frame per wave
-                e.set_option("scl_multi", -1); e.set_option("scl_lanes", 0); e.set_option("scl_lane_slab", 1)
-            self.front = self.side = None
-            self._ring: list = [None] * (nb + 1)      # the most recent groups: a new group's front ends wait for the decoder of the group nb + 1 before it
-            self._open = None
-            self._k = self._g = 0
-            self._flush_lanes = 0                     # (tests: 1 = one lane per path whatever the group's size)
-            return
-        # `lanes` > 0: the other arrangement -- K independent lanes, each one HIP stream (= one hardware queue) with its
-        # own context that runs the WHOLE chain of its batches (k, k+K, ...) in order; no cross-stream events at all.
-        self.lanes = max(0, int(lanes))
-        if self.lanes:
-            # (lane 0 on the caller's own stream was measured slower: 1.29 M against 1.43 M frames/s at 7 lanes)
-            # `streams`: HIP streams to run the lanes on instead of new ones -- a process that builds several pipelines should hand
-            # the same streams to each: beyond hw_queue_budget() live streams, streams share hardware queues and serialise
-            self.lane_streams = list(streams)[:self.lanes] if streams is not None else self._mk(dev, self.lanes)
-            if len(self.lane_streams) != self.lanes:
-                raise ValueError("streams: one per lane")
-            self.lane_engs = [eng] + [RxEngine(dev, list_size_max=max(8, self.list_size)) for _ in range(self.lanes - 1)]
-            self.scl_engs = self.lane_engs
-            self.backs = self.lane_streams
-            self.front = self.side = None
-            self._k = 0
-            return
-        # the short front-end kernels get dispatch priority over the long-running list decoders
-        self.front = self._mk(dev, 1, priority=-1)[0]
-        self.side = self._mk(dev, 1, priority=-1)[0] if side_stream else self.front   # one hardware queue less without it
-        self.backs = self._mk(dev, max(1, int(scl_streams)))
-        self.scl_engs = [eng] + [RxEngine(dev, list_size_max=max(8, self.list_size)) for _ in self.backs[1:]]
-        # Batches in flight = list-decoder streams: the front end of batch k waits for batch k-2 to leave, so it
-        # runs while only ONE list decoder is resident (two of them fill every SIMD's register file and would
-        # starve the short front-end kernels of wave slots), and its own list decoder then starts beside the
-        # one still running.
-        self.depth = len(self.backs) if depth is None else max(1, int(depth))
-        self._inflight: list = []            # `done` events of the most recent batches
-        self._k = 0
-
-    def submit(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *,
-               start: torch.Tensor | None = None, xcorr_events=None, select: bool = False, inputs_ready: bool = False):
-        """Enqueue one batch.  inputs_ready (grouped arrangement): skip the wait on the caller's stream -- for INPUTS known to be
-        complete on the device (10 us of host time per batch; it covers the inputs only: the group's own buffers are ordered by the pipeline).  start: frame starts [B] (None = 0; "peak" = the first detected peak of each record, read in place by the demodulator);
-        select (lanes only): also run the candidate selection (es_select_batch, validator None) on the lane's stream --
-        the result is attached to the returned SclResult as `.selected = (payload, ok, which)`."""
-        eng = self.eng
-        if frames.shape[1] - 62 > eng.FAST_MAX_LAGS:
-            raise ValueError("DecodePipeline serves frame-sized records (use RxEngine.decode_batch for long captures)")
-        if self.group:
-            return self._submit_grouped(frames, band, pn_rows, start, xcorr_events, select, inputs_ready)
-        if self.lanes:
-            j = self._k % self.lanes
-            self._k += 1
-            st, e = self.lane_streams[j], self.lane_engs[j]
-            st.wait_stream(torch.cuda.current_stream(eng.device))
-            with torch.cuda.stream(st):
-                y, y32 = e.bpf2(frames, band)
-                if xcorr_events is not None:
-                    xcorr_events[0].record()
-                thr, peaks, npeaks, flags = e.sync_fused(y, y32, band)        # correlation screen + exact picking, one kernel
-                if xcorr_events is not None:
-                    xcorr_events[1].record()
-                # "peak": demodulate at the first detected peak, read in place from the peaks (no kernel in between)
-                llr = e.llr(y, band, pn_rows, start=start, peaks=peaks if isinstance(start, str) else None, variant=0)
-                scl = e.scl(llr, list_size=self.list_size, skip_if_hard_ok=True)
-                if select:
-                    scl.selected = e.select(scl)
-                done = torch.cuda.Event()
-                done.record()
-            for t in (frames, band, pn_rows):
-                t.record_stream(st)
-            return SyncResult(y, None, thr, peaks, npeaks, flags=flags), llr, scl, done
-        self.front.wait_stream(torch.cuda.current_stream(eng.device))   # inputs were produced on the caller's stream
-        if len(self._inflight) >= self.depth:                           # at most `depth` batches in flight
-            self.front.wait_event(self._inflight.pop(0))
-        peak = isinstance(start, str)                                   # "peak": the demodulator follows sync on the front stream
-        with torch.cuda.stream(self.front):
-            y, y32 = eng.bpf2(frames, band)
-            if not peak:
-                if self.side is not self.front:
-                    self.side.wait_stream(self.front)
-                with torch.cuda.stream(self.side):
-                    llr = eng.llr(y, band, pn_rows, start=start, variant=0)
-            if xcorr_events is not None:
-                xcorr_events[0].record()
-            thr, peaks, npeaks, flags = eng.sync_fused(y, y32, band)
-            if xcorr_events is not None:
-                xcorr_events[1].record()
-            if peak:
-                llr = eng.llr(y, band, pn_rows, start=start, peaks=peaks, variant=0)
-            elif self.side is not self.front:
-                self.front.wait_stream(self.side)
-            ready = torch.cuda.Event()
-            ready.record()
-        j = self._k % len(self.backs)
-        self._k += 1
-        back = self.backs[j]
-        back.wait_event(ready)
-        llr.record_stream(back)
-        with torch.cuda.stream(back):
-            scl = self.scl_engs[j].scl(llr, list_size=self.list_size, skip_if_hard_ok=True)
-            done = torch.cuda.Event()
-            done.record()
-        self._inflight.append(done)
-        return SyncResult(y, None, thr, peaks, npeaks, flags=flags), llr, scl, done
-
-    # ---- grouped arrangement
-    def _submit_grouped(self, frames, band, pn_rows, start, xcorr_events, select, inputs_ready=False):
-        B = frames.shape[0]
-        g = self._open
-        if g is not None and (g.B != B or g.select != bool(select)):
-            self._flush(g); g = None
-        if g is None:
-            r = self._g % len(self._ring)
-            g = _Group(self, B, bool(select), self._ring[r], self.eng.device)
-            self._ring[r] = g                         # (only its `done` event is looked at again: the throttle of the group opened R groups later)
-            self._open = g
-            self._g += 1
-        j = self._k % self.lanes
-        self._k += 1
-        st, e = self.lane_streams[j], self.lane_engs[j]
-        if not inputs_ready:                                                  # (inputs_ready: the caller vouches that frames / band / pn_rows are complete on the device)
-            st.wait_stream(torch.cuda.current_stream(self.eng.device))
-        if g.throttle is not None:
-            st.wait_event(g.throttle)                                         # at most len(ring) groups in flight on the GPU
-        if g.llr is None:
-            g.allocate(st)                                                    # on THIS lane's stream: the block's earlier life is ordered before its writes
-        if j not in g.lanes_used:
-            g.lanes_used.add(j)
-            if st is not g.alloc_stream:
-                st.wait_event(g.alloc_ev)                                     # (a recycled block may still be in use by work queued on the allocating stream)
-                g.llr.record_stream(st)
-        slot = g.count
-        rows = g.llr[slot * B:(slot + 1) * B]
-        with torch.cuda.stream(st):
-            if xcorr_events is None:                                          # the three launches through one library call
-                y, thr, peaks, npeaks, flags, _ = e.front(frames, band, pn_rows, start=start, out=rows)
-            else:
-                y, y32 = e.bpf2(frames, band)
-                if xcorr_events is not None:
-                    xcorr_events[0].record()
-                thr, peaks, npeaks, flags = e.sync_fused(y, y32, band)
-                if xcorr_events is not None:
-                    xcorr_events[1].record()
-                e.llr(y, band, pn_rows, start=start, peaks=peaks if isinstance(start, str) else None, variant=0, out=rows)
-            ready = torch.cuda.Event()
-            ready.record()
-        for t in (frames, band, pn_rows):
-            t.record_stream(st)
-        g.ready.append(ready)
-        g.count += 1
-        ticket = GroupTicket(g, slot)
-        if g.count == g.capacity:
-            self._flush(g)
-        return SyncResult(y, None, thr, peaks, npeaks, flags=flags), rows, ticket, ticket
-
-    def _flush(self, g) -> None:
-        if g.done is not None:
-            return
-        j = g.index % len(self.backs)
-        back, e = self.backs[j], self.scl_engs[j]
-        for ev in g.ready:
-            back.wait_event(ev)
-        lp = 1
-        while lp < self.list_size:
-            lp <<= 1
-        # one lane per path once the group gives every SIMD a wave (launches of several groups overlap); a lone batch: the library's choice
-        e.set_option("scl_lanes", 1 if (g.count * g.B * lp >= 64 * 1024 or self._flush_lanes == 1) else 0)
-        g.llr.record_stream(back)
-        with torch.cuda.stream(back):
-            g.scl = e.scl(g.llr[:g.count * g.B], list_size=self.list_size, skip_if_hard_ok=True)
-            if g.select:
-                g.selected = e.select(g.scl)
-            g.done = torch.cuda.Event()
-            g.done.record()
-        if self._open is g:
-            self._open = None
-
-    @staticmethod
-    def wait(result) -> None:
-        result[3].synchronize()
-
-    def synchronize(self) -> None:
-        if self.group:
-            if self._open is not None:
-                self._flush(self._open)
-            for st in self.lane_streams:
-                st.synchronize()
-        if self.front is not None:
-            self.front.synchronize(); self.side.synchronize()
-        for b in self.backs:
-            b.synchronize()
-
-
-class _Group:
-    """Batches that share one list-decoder launch (DecodePipeline, grouped arrangement)."""
-
-    def __init__(self, pipe: DecodePipeline, B: int, select: bool, prev, device):
-        self.pipe, self.B, self.select = pipe, B, select
-        self.index = pipe._g
-        self.capacity = pipe.group
-        self.device = device
-        # a buffer of its own (the rows handed out to the caller stay valid as long as the caller keeps them), allocated by the first
-        # submit on that batch's lane stream (`allocate`); the caching allocator is told about every other stream that touches it
-        self.llr = self.alloc_stream = self.alloc_ev = None
-        self.throttle = prev.done if prev is not None else None
-        self.lanes_used: set = set()
-        self.ready: list = []
-        self.count = 0
-        self.scl = self.selected = self.done = None
-
-    def allocate(self, stream) -> None:
-        with torch.cuda.stream(stream):
-            self.llr = torch.empty((self.capacity * self.B, 1024), dtype=torch.float32, device=self.device)
-            self.alloc_ev = torch.cuda.Event()
-            self.alloc_ev.record()
-        self.alloc_stream = stream
-
-
-class GroupTicket:
-    """A batch's place in its group: `result()` -> SclResult rows of this batch (flushes / waits as needed)."""
-
-    def __init__(self, g: _Group, slot: int):
-        self.g, self.slot = g, slot
-
-    def synchronize(self) -> None:
-        self.g.pipe._flush(self.g)
-        self.g.done.synchronize()
-
-    def result(self) -> SclResult:
-        self.synchronize()
-        lo, hi = self.slot * self.g.B, (self.slot + 1) * self.g.B
-        s = self.g.scl
-        if not getattr(self.g, "checked", False):
-            s.check(); self.g.checked = True                  # (the launch is complete: one small reduction per group)
-        res = SclResult(s.hard_info[lo:hi], s.hard_ok[lo:hi], s.cand_info[lo:hi], s.cand_metric[lo:hi], s.cand_ok[lo:hi], s.ncand[lo:hi])
-        if self.g.selected is not None:
-            res.selected = tuple(t[lo:hi] for t in self.g.selected)
-        return res
 
 
 def select_payload(scl: SclResult, row: int = 0, validator=None):
@@ -1224,3 +917,10 @@ def select_payload(scl: SclResult, row: int = 0, validator=None):
     if best_crc is not None:
         return best_crc[1], False
     return best_any[1], False
+
+
+def __getattr__(name: str):      # the pipeline's public names stay importable from here (on first use: pipeline.py imports this module, so not at import)
+    if name in ("DecodePipeline", "GroupTicket", "hw_queue_budget", "pipeline_streams"):
+        from . import pipeline
+        return getattr(pipeline, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,7 +1,7 @@
 """Does the interpreter exit cleanly after using the engine in various ways?  python tools/exit_probe.py  (each mode in a child process; prints its exit code)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODES = ["front", "front_noweak", "front_sel", "front_keep", "engine", "lanes", "grouped"]
+MODES = ["front", "front_sel", "front_keep", "engine", "lanes", "grouped"]
 if len(sys.argv) > 2 and sys.argv[1] == "--child":
     sys.path.insert(0, ROOT)
     import numpy as np, torch
@@ -13,11 +13,6 @@ if len(sys.argv) > 2 and sys.argv[1] == "--child":
     if mode == "streams":
         st = pipeline_streams(eng.device, 4)
     if mode.startswith("front"):
-        import echoseal_amd.engine as E
-        if mode == "front_noweak":
-            class _S(set):
-                def add(self, x): pass
-            E._LIVE_STREAMS = _S()
         from echoseal_amd import workloads as WL
         frames, band, pn, _ = WL.c2_frames(range(256))
         f, b, p = (torch.from_numpy(x).to(eng.device) for x in (frames, band, pn))
