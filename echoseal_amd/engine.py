@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 from .monitor import MonitorChain, MonitorLayout, MonitorTable, MonitorTick, monitor_layout      # the live monitor's public names stay importable from here
 from .tables import pack_tables
-from .transmit import (EMBED_ROW_SAMPLES, EmbedClip, EmbedLayout, EmbedResult, StreamLayout, StreamTable, TxChain, _ptr, embed_launches, embed_layout,
+from .transmit import (EMBED_ROW_SAMPLES, EmbedClip, EmbedLayout, EmbedResult, StreamLayout, StreamTable, TxChain, embed_launches, embed_layout,
                        stream_layout)      # the transmit chain's public names stay importable from here
 
 _FRAME_DTYPES = {torch.int16: nat.ES_DTYPE_I16, torch.float32: nat.ES_DTYPE_F32}     # what the band-pass reads
@@ -144,13 +144,11 @@ class RxEngine(TxChain, MonitorChain):
         tests and experiments that need tables the band plan never produces, such as a one-tap matched filter."""
         torch.cuda.synchronize(self.device)
         self._tables = (ba, tpl, taps, ntaps, frozen)       # keep host arrays alive
-        nat.check(self._ctx, self._lib.es_set_tables(
-            self._ctx, ba.ctypes.data, tpl.ctypes.data, taps.ctypes.data, ntaps.ctypes.data,
-            frozen.ctypes.data), "es_set_tables")
+        self._call("es_set_tables", ba.ctypes.data, tpl.ctypes.data, taps.ctypes.data, ntaps.ctypes.data, frozen.ctypes.data)
 
     def set_option(self, name: str, value: int) -> None:
         """Tuning knobs of the native library (results never depend on them); see include/echoseal_hip.h."""
-        nat.check(self._ctx, self._lib.es_set_option(self._ctx, name.encode(), int(value)), "es_set_option")
+        self._call("es_set_option", name.encode(), int(value))
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -167,6 +165,20 @@ class RxEngine(TxChain, MonitorChain):
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _call(self, name: str, *args) -> None:
+        """The one place the C ABI is called (include/echoseal_hip.h): entry point `name`, looked up on _lib at every call (tests replace
+        _lib), with the context first, every tensor as its data_ptr() and everything else as it is -- None (a NULL pointer), sizes, addresses
+        already formed, floats, bytes --, and the current stream last exactly when the name ends in _batch: the header's own rule, held by
+        tests/test_binding_call.py.  Nothing is checked here.  A return code raises nat.check's NativeError.
+        A tensor is an object whose type is torch.Tensor itself: one of a subclass (an nn.Parameter) is handed through unconverted and
+        ctypes refuses it -- no caller passes one; hand its .data instead."""
+        args = [a.data_ptr() if type(a) is torch.Tensor else a for a in args]
+        if name.endswith("_batch"):
+            args.append(self._stream())
+        rc = getattr(self._lib, name)(self._ctx, *args)
+        if rc:
+            nat.check(self._ctx, rc, name)
 
     def _dev(self, x, dtype) -> torch.Tensor:
         t = torch.as_tensor(x)
@@ -201,8 +213,7 @@ class RxEngine(TxChain, MonitorChain):
     def bpf(self, frames: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
         frames, dt, B, T = self._frames(frames)
         y = torch.empty((B, T), dtype=torch.float64, device=self.device)
-        nat.check(self._ctx, self._lib.es_bpf_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(y),
-                                                    self._stream()), "es_bpf_batch")
+        self._call("es_bpf_batch", frames, dt, B, T, band, y)
         return y
 
     def bpf2(self, frames: torch.Tensor, band: torch.Tensor):
@@ -210,24 +221,20 @@ class RxEngine(TxChain, MonitorChain):
         frames, dt, B, T = self._frames(frames)
         y = torch.empty((B, T), dtype=torch.float64, device=self.device)
         y32 = torch.empty((B, T), dtype=torch.float32, device=self.device)
-        nat.check(self._ctx, self._lib.es_bpf2_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(y), _ptr(y32),
-                                                     self._stream()), "es_bpf2_batch")
+        self._call("es_bpf2_batch", frames, dt, B, T, band, y, y32)
         return y, y32
 
     def xcorr32(self, y32: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
         B, T = y32.shape
         corr = torch.empty((B, T - 62), dtype=torch.float32, device=self.device)
-        nat.check(self._ctx, self._lib.es_xcorr32_batch(self._ctx, _ptr(y32), B, T, _ptr(band), _ptr(corr),
-                                                        self._stream()), "es_xcorr32_batch")
+        self._call("es_xcorr32_batch", y32, B, T, band, corr)
         return corr
 
     def pick_exact(self, corr32: torch.Tensor, y: torch.Tensor, band: torch.Tensor):
         """thr / peaks / npeaks identical to pick(xcorr(y)); also returns the per-record flags (reason codes 1..5, 0 = settled from the screen)."""
         B, T = y.shape
         thr, peaks, npeaks, flags = self._peak_out(B)
-        nat.check(self._ctx, self._lib.es_pick_exact_batch(self._ctx, _ptr(corr32), _ptr(y), B, T, _ptr(band), _ptr(thr),
-                                                           _ptr(peaks), _ptr(npeaks), _ptr(flags), self._stream()),
-                  "es_pick_exact_batch")
+        self._call("es_pick_exact_batch", corr32, y, B, T, band, thr, peaks, npeaks, flags)
         return thr, peaks, npeaks, flags
 
     def sync_fused(self, y: torch.Tensor, y32: torch.Tensor, band: torch.Tensor):
@@ -235,8 +242,7 @@ class RxEngine(TxChain, MonitorChain):
         -> (thr, peaks, npeaks, flags), identical to pick(xcorr(y))."""
         B, T = y.shape
         thr, peaks, npeaks, flags = self._peak_out(B)
-        nat.check(self._ctx, self._lib.es_sync_fused_batch(self._ctx, _ptr(y32), _ptr(y), B, T, _ptr(band), _ptr(thr), _ptr(peaks),
-                                                           _ptr(npeaks), _ptr(flags), self._stream()), "es_sync_fused_batch")
+        self._call("es_sync_fused_batch", y32, y, B, T, band, thr, peaks, npeaks, flags)
         return thr, peaks, npeaks, flags
 
     def front(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | str | None = None,
@@ -250,13 +256,9 @@ class RxEngine(TxChain, MonitorChain):
         out = self._llr_out(out, B)
         if isinstance(start, str):
             _peak_start(start)
-            nat.check(self._ctx, self._lib.es_front_peak_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(pn_rows), _ptr(y), _ptr(y32),
-                                                               _ptr(thr), _ptr(peaks), _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()),
-                      "es_front_peak_batch")
+            self._call("es_front_peak_batch", frames, dt, B, T, band, pn_rows, y, y32, thr, peaks, npeaks, flags, out)
         else:
-            nat.check(self._ctx, self._lib.es_front_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(band), _ptr(pn_rows), _ptr(start), _ptr(y),
-                                                          _ptr(y32), _ptr(thr), _ptr(peaks), _ptr(npeaks), _ptr(flags), _ptr(out), self._stream()),
-                      "es_front_batch")
+            self._call("es_front_batch", frames, dt, B, T, band, pn_rows, start, y, y32, thr, peaks, npeaks, flags, out)
         return y, thr, peaks, npeaks, flags, out
 
     def front_steps(self, frames: torch.Tensor, band: torch.Tensor, pn_rows: torch.Tensor, *, start: torch.Tensor | str | None = None,
@@ -287,7 +289,7 @@ class RxEngine(TxChain, MonitorChain):
 
     def reserve(self, B_max: int, T_max: int) -> None:
         """Size the context's workspaces once (es_reserve): afterwards the sync entry points only enqueue."""
-        nat.check(self._ctx, self._lib.es_reserve(self._ctx, int(B_max), int(T_max)), "es_reserve")
+        self._call("es_reserve", int(B_max), int(T_max))
 
     FAST_MAX_LAGS = 4096
 
@@ -308,15 +310,13 @@ class RxEngine(TxChain, MonitorChain):
     def xcorr(self, y: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
         B, T = y.shape
         corr = torch.empty((B, T - 62), dtype=torch.float64, device=self.device)
-        nat.check(self._ctx, self._lib.es_xcorr_batch(self._ctx, _ptr(y), B, T, _ptr(band), _ptr(corr),
-                                                      self._stream()), "es_xcorr_batch")
+        self._call("es_xcorr_batch", y, B, T, band, corr)
         return corr
 
     def pick(self, corr: torch.Tensor):
         B, n = corr.shape
         thr, peaks, npeaks, _ = self._peak_out(B, flags=False)
-        nat.check(self._ctx, self._lib.es_pick_batch(self._ctx, _ptr(corr), B, n, _ptr(thr), _ptr(peaks),
-                                                     _ptr(npeaks), self._stream()), "es_pick_batch")
+        self._call("es_pick_batch", corr, B, n, thr, peaks, npeaks)
         return thr, peaks, npeaks
 
     def sync(self, frames: torch.Tensor, band: torch.Tensor, *, keep_corr: bool = True) -> SyncResult:
@@ -342,8 +342,7 @@ class RxEngine(TxChain, MonitorChain):
         y = torch.empty((B, T), dtype=torch.float64, device=self.device)
         corr = torch.empty((B, max(T - 62, 0)), dtype=torch.float64, device=self.device) if keep_corr else None
         thr, peaks, npeaks, _ = self._peak_out(B, flags=False)
-        nat.check(self._ctx, self._lib.es_sync_ragged_batch(self._ctx, _ptr(frames), dt, B, T, _ptr(lens), _ptr(band), _ptr(y), _ptr(corr),
-                                                            _ptr(thr), _ptr(peaks), _ptr(npeaks), self._stream()), "es_sync_ragged_batch")
+        self._call("es_sync_ragged_batch", frames, dt, B, T, lens, band, y, corr, thr, peaks, npeaks)
         return SyncResult(y, corr, thr, peaks, npeaks)
 
     # ------------------------------------------------------------------ soft demod
@@ -385,13 +384,9 @@ class RxEngine(TxChain, MonitorChain):
         best_s = torch.empty(B, dtype=torch.int32, device=self.device) if want_diag else None
         score = torch.empty((B, 2), dtype=torch.float32, device=self.device) if want_diag else None
         if at:
-            nat.check(self._ctx, self._lib.es_llr_at_batch(self._ctx, _ptr(y), y.shape[0], T, B, _ptr(rows), _ptr(st), stride, _ptr(band),
-                                                           _ptr(pn_rows), int(variant), _ptr(out), _ptr(best_s), _ptr(score),
-                                                           self._stream()), "es_llr_at_batch")
+            self._call("es_llr_at_batch", y, y.shape[0], T, B, rows, st, stride, band, pn_rows, int(variant), out, best_s, score)
         else:
-            nat.check(self._ctx, self._lib.es_llr_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(pn_rows),
-                                                        int(variant), _ptr(out), _ptr(best_s), _ptr(score),
-                                                        self._stream()), "es_llr_batch")
+            self._call("es_llr_batch", y, B, T, start, band, pn_rows, int(variant), out, best_s, score)
         return (out, best_s, score) if want_diag else out
 
     def header(self, y: torch.Tensor, band: torch.Tensor, hdr_pn: torch.Tensor, *, start: torch.Tensor | str | None = None,
@@ -413,13 +408,9 @@ class RxEngine(TxChain, MonitorChain):
         score = torch.empty(B, dtype=torch.float32, device=self.device)
         best_s = torch.empty(B, dtype=torch.int32, device=self.device) if want_diag else None
         if at:
-            nat.check(self._ctx, self._lib.es_header_at_batch(self._ctx, _ptr(y), y.shape[0], T, B, _ptr(rows), _ptr(st), stride, _ptr(band),
-                                                              _ptr(hdr_pn), _ptr(ok), _ptr(val), _ptr(score), _ptr(best_s), self._stream()),
-                      "es_header_at_batch")
+            self._call("es_header_at_batch", y, y.shape[0], T, B, rows, st, stride, band, hdr_pn, ok, val, score, best_s)
         else:
-            nat.check(self._ctx, self._lib.es_header_batch(self._ctx, _ptr(y), B, T, _ptr(start), _ptr(band), _ptr(hdr_pn),
-                                                           _ptr(ok), _ptr(val), _ptr(score), _ptr(best_s), self._stream()),
-                      "es_header_batch")
+            self._call("es_header_batch", y, B, T, start, band, hdr_pn, ok, val, score, best_s)
         return (ok, val, score, best_s) if want_diag else (ok, val, score)
 
     # ------------------------------------------------------------------ FEC
@@ -439,17 +430,15 @@ class RxEngine(TxChain, MonitorChain):
             torch.empty((B, self.info_bytes), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev),
             torch.empty((B, L, self.info_bytes), dtype=torch.uint8, device=dev), torch.empty((B, L), dtype=torch.float64, device=dev),
             torch.empty((B, L), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))   # every row is written by the kernel
-        nat.check(self._ctx, self._lib.es_scl_batch(
-            self._ctx, _ptr(llr), dt, B, L, int(bool(skip_if_hard_ok)), _ptr(res.hard_info), _ptr(res.hard_ok),
-            _ptr(res.cand_info), _ptr(res.cand_metric), _ptr(res.cand_ok), _ptr(res.ncand), self._stream()),
-            "es_scl_batch")
+        self._call("es_scl_batch", llr, dt, B, L, int(bool(skip_if_hard_ok)), res.hard_info, res.hard_ok, res.cand_info, res.cand_metric, res.cand_ok,
+                   res.ncand)
         return res
 
     def softplus(self, t: torch.Tensor) -> torch.Tensor:
         """Diagnostic: log1p(exp(t)) for t <= 0 as the list decoder evaluates it on the device (float64 in, float64 out)."""
         t = t.contiguous()
         out = torch.empty_like(t)
-        nat.check(self._ctx, self._lib.es_softplus_batch(self._ctx, _ptr(t), t.numel(), _ptr(out), self._stream()), "es_softplus_batch")
+        self._call("es_softplus_batch", t, t.numel(), out)
         return out
 
     def polar_f(self, a: torch.Tensor, b: torch.Tensor):
@@ -458,16 +447,14 @@ class RxEngine(TxChain, MonitorChain):
         a = a.contiguous(); b = b.contiguous()
         out = torch.empty((3, a.numel()), dtype=torch.float64, device=a.device)
         bad = torch.empty(a.numel(), dtype=torch.int32, device=a.device)
-        nat.check(self._ctx, self._lib.es_polar_f_batch(self._ctx, _ptr(a), _ptr(b), a.numel(), _ptr(out), _ptr(bad), self._stream()),
-                  "es_polar_f_batch")
+        self._call("es_polar_f_batch", a, b, a.numel(), out, bad)
         return out, bad
 
     def polar_encode(self, info: torch.Tensor) -> torch.Tensor:
         info = info.contiguous()
         B = info.shape[0]
         code = torch.empty((B, 1024), dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_polar_encode_batch(self._ctx, _ptr(info), B, _ptr(code), self._stream()),
-                  "es_polar_encode_batch")
+        self._call("es_polar_encode_batch", info, B, code)
         return code
 
     # ------------------------------------------------------------------ input conditioning
@@ -490,9 +477,8 @@ class RxEngine(TxChain, MonitorChain):
         xd = self._dev(x, tdt)
         hd = torch.from_numpy(h_tf).to(self.device)
         out = torch.empty((x.shape[0], n_out), dtype=tdt, device=self.device)
-        nat.check(self._ctx, self._lib.es_resample_batch(self._ctx, _ptr(xd), nat.ES_DTYPE_F32 if tdt == torch.float32 else nat.ES_DTYPE_F64,
-                                                         x.shape[0], x.shape[1], _ptr(hd), hpp, up, down, y0, n_out, _ptr(out),
-                                                         self._stream()), "es_resample_batch")
+        self._call("es_resample_batch", xd, nat.ES_DTYPE_F32 if tdt == torch.float32 else nat.ES_DTYPE_F64, x.shape[0], x.shape[1], hd, hpp, up, down, y0,
+                   n_out, out)
         return out[0] if one_d else out
 
     def condition_upload(self, lengths, fs_list, fs_target: int, dtype) -> "DevicePlan":
@@ -542,8 +528,7 @@ class RxEngine(TxChain, MonitorChain):
             pool = torch.cat(ts)                                            # device clips: gathered on the device
         else:
             pool = torch.cat([t.cpu() for t in ts]).to(self.device, non_blocking=True)      # ONE upload, unpadded
-        nat.check(self._ctx, self._lib.es_resample_ragged_batch(self._ctx, _ptr(pool), dt, pool.numel(), _ptr(filt), filt.numel(), _ptr(desc), R,
-                                                                rep, _ptr(out), stride, longest, self._stream()), "es_resample_ragged_batch")
+        self._call("es_resample_ragged_batch", pool, dt, pool.numel(), filt, filt.numel(), desc, R, rep, out, stride, longest)
         return out, lens
 
     # ------------------------------------------------------------------ key / PN / hop schedule
@@ -561,9 +546,7 @@ class RxEngine(TxChain, MonitorChain):
             cd = None
         pn = torch.empty((n, 152), dtype=torch.uint8, device=self.device)
         band = torch.empty(n, dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_schedule_batch(self._ctx, bytes(aes_key16), bytes(band_key32), _ptr(cd),
-                                                         int(ctr0) & 0xFFFFFFFF, n, _ptr(pn), _ptr(band), self._stream()),
-                  "es_schedule_batch")
+        self._call("es_schedule_batch", bytes(aes_key16), bytes(band_key32), cd, int(ctr0) & 0xFFFFFFFF, n, pn, band)
         return pn, band
 
     # ------------------------------------------------------------------ many keys at once (es_keyring.hip)
@@ -583,7 +566,7 @@ class RxEngine(TxChain, MonitorChain):
             raise ValueError("keys must be 32 bytes each")
         N = mk.shape[0]
         ring = torch.empty((N, nat.ES_KEYRING_BYTES), dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_keyring_derive_batch(self._ctx, _ptr(mk), N, _ptr(ring), self._stream()), "es_keyring_derive_batch")
+        self._call("es_keyring_derive_batch", mk, N, ring)
         return KeyRing(ring, N)
 
     @staticmethod
@@ -613,8 +596,7 @@ class RxEngine(TxChain, MonitorChain):
         band = torch.empty(n, dtype=torch.uint8, device=self.device) if want_band else None
         if n and ring.n == 0:
             raise ValueError("records but an empty key ring")
-        nat.check(self._ctx, self._lib.es_schedule_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(cd), n, _ptr(pn), _ptr(band),
-                                                               self._stream()), "es_schedule_keyed_batch")
+        self._call("es_schedule_keyed_batch", ring.ring, ring.n, kd, cd, n, pn, band)
         return pn, band
 
     def aead_check_keyed(self, ring: KeyRing, key_idx, blobs: torch.Tensor, ctrs, *, want_plain: bool = False):
@@ -630,8 +612,7 @@ class RxEngine(TxChain, MonitorChain):
         kd = self._key_dev(ring, key_idx, ctrs.numel())
         ok = torch.empty(blobs.shape[:-1], dtype=torch.uint8, device=self.device)
         plain = torch.empty(blobs.shape[:-1] + (27,), dtype=torch.uint8, device=self.device) if want_plain else None
-        nat.check(self._ctx, self._lib.es_aead_check_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(blobs), n, group, _ptr(ctrs),
-                                                                 _ptr(ok), _ptr(plain), self._stream()), "es_aead_check_keyed_batch")
+        self._call("es_aead_check_keyed_batch", ring.ring, ring.n, kd, blobs, n, group, ctrs, ok, plain)
         return (ok, plain) if want_plain else ok
 
     def hop_window(self, ring: KeyRing, hop_base, C: int) -> torch.Tensor:
@@ -643,8 +624,7 @@ class RxEngine(TxChain, MonitorChain):
         if C < 0:
             raise ValueError("C: a column count")
         hop = torch.empty((ring.n, HR, C), dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_hop_window_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(base), HR, C, _ptr(hop), self._stream()),
-                  "es_hop_window_batch")
+        self._call("es_hop_window_batch", ring.ring, ring.n, base, HR, C, hop)
         return hop
 
     def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):
@@ -661,8 +641,7 @@ class RxEngine(TxChain, MonitorChain):
             raise ValueError("key_idx, ok, lo16, band: one entry per record")
         mask = torch.empty((P, W), dtype=torch.int32, device=self.device)
         count = torch.empty(P, dtype=torch.int32, device=self.device)
-        nat.check(self._ctx, self._lib.es_acquire_mask_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(okd), _ptr(lod), _ptr(bd), P,
-                                                             int(lo), int(hi), _ptr(mask), _ptr(count), self._stream()), "es_acquire_mask_batch")
+        self._call("es_acquire_mask_batch", ring.ring, ring.n, kd, okd, lod, bd, P, int(lo), int(hi), mask, count)
         return mask, count
 
     def acquire_list(self, mask: torch.Tensor, lo16, span, base, total: int):
@@ -679,8 +658,7 @@ class RxEngine(TxChain, MonitorChain):
             raise ValueError("lo16, base: one entry per record; total: an entry count")
         rec = torch.empty(total, dtype=torch.int32, device=self.device)
         ctr = torch.empty(total, dtype=torch.int32, device=self.device)
-        nat.check(self._ctx, self._lib.es_acquire_list_batch(self._ctx, _ptr(mask), _ptr(lod), P, int(lo), int(hi), _ptr(based), total, _ptr(rec),
-                                                             _ptr(ctr), self._stream()), "es_acquire_list_batch")
+        self._call("es_acquire_list_batch", mask, lod, P, int(lo), int(hi), based, total, rec, ctr)
         return rec, ctr
 
     def plan(self, peaks: torch.Tensor, npeaks: torch.Tensor, rowband, hdr_base, T, hdr_ok: torch.Tensor, hdr_lo16: torch.Tensor,
@@ -715,6 +693,9 @@ class RxEngine(TxChain, MonitorChain):
         res = PlanResult(torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.uint8, device=self.device),
                          torch.empty((pairs, nat.ES_MAX_TRIES), dtype=torch.int32, device=self.device),
                          torch.empty(pairs, dtype=torch.int32, device=self.device), torch.empty(pairs, dtype=torch.int32, device=self.device))
+        row_args = (peaks, npeaks, rowband, hdr_base, rows)         # the three argument groups every arm passes, in the header's order
+        key_args = (hdr_ok, hdr_lo16, P, hop, N, C)
+        out = (res.slot, res.ctr, res.count, res.looked)
         if at:
             HR = hop.shape[1]
             def per_row(v, n, what, counter=False):                 # one value, or one per row / hop row; None: zeros
@@ -727,26 +708,17 @@ class RxEngine(TxChain, MonitorChain):
                 return t.contiguous()
             pos0_d, ctr0_d = per_row(pos0, rows, "pos0"), per_row(ctr0, rows, "ctr0", True)
             hrow_d, hbase_d = per_row(hop_row, rows, "hop_row").to(torch.int32), per_row(hop_base, HR, "hop_base", True)
-            if torch.is_tensor(T) or isinstance(T, np.ndarray):
-                t_max, lens = (int(T.max()) if rows else 0), self._lens(T, rows)
-            else:
-                t_max, lens = int(T), torch.full((rows,), int(T), dtype=torch.int32, device=self.device)
-            nat.check(self._ctx, self._lib.es_plan_at_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows, _ptr(lens),
-                                                            t_max, _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(pos0_d), _ptr(ctr0_d),
-                                                            _ptr(hrow_d), _ptr(hbase_d), HR, _ptr(res.slot), _ptr(res.ctr), _ptr(res.count),
-                                                            _ptr(res.looked), self._stream()), "es_plan_at_batch")
-            return res
-        if torch.is_tensor(T) or isinstance(T, np.ndarray):
-            t_max = int(T.max()) if rows else 0                     # (the bound on the hop table's width)
-            lens = self._lens(T, rows)
-            nat.check(self._ctx, self._lib.es_plan_ragged_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows,
-                                                                _ptr(lens), t_max, _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C,
-                                                                _ptr(res.slot), _ptr(res.ctr), _ptr(res.count), _ptr(res.looked),
-                                                                self._stream()), "es_plan_ragged_batch")
-            return res
-        nat.check(self._ctx, self._lib.es_plan_batch(self._ctx, _ptr(peaks), _ptr(npeaks), _ptr(rowband), _ptr(hdr_base), rows, int(T),
-                                                     _ptr(hdr_ok), _ptr(hdr_lo16), P, _ptr(hop), N, C, _ptr(res.slot), _ptr(res.ctr),
-                                                     _ptr(res.count), _ptr(res.looked), self._stream()), "es_plan_batch")
+        ragged = torch.is_tensor(T) or isinstance(T, np.ndarray)
+        if ragged:
+            t_max, lens = (int(T.max()) if rows else 0), self._lens(T, rows)      # (t_max: the bound on the hop table's width)
+        elif at:
+            t_max, lens = int(T), torch.full((rows,), int(T), dtype=torch.int32, device=self.device)
+        if at:
+            self._call("es_plan_at_batch", *row_args, lens, t_max, *key_args, pos0_d, ctr0_d, hrow_d, hbase_d, HR, *out)
+        elif ragged:
+            self._call("es_plan_ragged_batch", *row_args, lens, t_max, *key_args, *out)
+        else:
+            self._call("es_plan_batch", *row_args, int(T), *key_args, *out)
         return res
 
     # ------------------------------------------------------------------ the verdict memo (es_memo.hip)
@@ -768,16 +740,14 @@ class RxEngine(TxChain, MonitorChain):
         """-> uint8 [n]: record i is in the memo (es_memo_probe_batch)."""
         k0, k1, n = self._memo_words(k0, k1)
         hit = torch.empty(n, dtype=torch.uint8, device=self.device)
-        nat.check(self._ctx, self._lib.es_memo_probe_batch(self._ctx, _ptr(memo.table), memo.slots, _ptr(k0), _ptr(k1), n, _ptr(hit), self._stream()),
-                  "es_memo_probe_batch")
+        self._call("es_memo_probe_batch", memo.table, memo.slots, k0, k1, n, hit)
         return hit
 
     def memo_insert(self, memo: Memo, k0, k1) -> None:
         """Store the records of one call (es_memo_insert_batch): per entry the record of the lowest index wins, a record whose k0 is all
         ones is ignored."""
         k0, k1, n = self._memo_words(k0, k1)
-        nat.check(self._ctx, self._lib.es_memo_insert_batch(self._ctx, _ptr(memo.table), _ptr(memo.claim), memo.slots, _ptr(k0), _ptr(k1), n,
-                                                            self._stream()), "es_memo_insert_batch")
+        self._call("es_memo_insert_batch", memo.table, memo.claim, memo.slots, k0, k1, n)
 
     # ------------------------------------------------------------------ after the list decoder (SURVEY 8 f-2)
     def _ctr_dev(self, ctrs) -> torch.Tensor:
@@ -800,8 +770,7 @@ class RxEngine(TxChain, MonitorChain):
             raise ValueError("one expected counter per blob row (or per frame for [B,L,55]) is required")
         ok = torch.empty(blobs.shape[:-1], dtype=torch.uint8, device=self.device)
         plain = torch.empty(blobs.shape[:-1] + (27,), dtype=torch.uint8, device=self.device) if want_plain else None
-        nat.check(self._ctx, self._lib.es_aead_check_batch(self._ctx, bytes(key32), _ptr(blobs), n, group, _ptr(ctrs), _ptr(ok),
-                                                           _ptr(plain), self._stream()), "es_aead_check_batch")
+        self._call("es_aead_check_batch", bytes(key32), blobs, n, group, ctrs, ok, plain)
         return (ok, plain) if want_plain else ok
 
     def select(self, scl: SclResult, *, key32: bytes | None = None, ctrs: torch.Tensor | None = None, ring: KeyRing | None = None,
@@ -814,35 +783,27 @@ class RxEngine(TxChain, MonitorChain):
         if ring is not None:
             if key32 is not None or key_idx is None or ctrs is None:
                 raise ValueError("ring= goes with key_idx= and ctrs=, and without key32=")
-            ctrs = self._ctr_dev(ctrs)
-            if ctrs.numel() != B:
-                raise ValueError("one expected counter per record is required with a key")
-            kd = self._key_dev(ring, key_idx, B)
-            payload = torch.empty((B, 55), dtype=torch.uint8, device=self.device)
-            ok = torch.empty(B, dtype=torch.int8, device=self.device)
-            which = torch.empty(B, dtype=torch.int32, device=self.device)
-            nat.check(self._ctx, self._lib.es_select_keyed_batch(
-                self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(ctrs), B, L, _ptr(scl.hard_info), _ptr(scl.hard_ok), _ptr(scl.cand_info),
-                _ptr(scl.cand_metric), _ptr(scl.cand_ok), _ptr(scl.ncand), _ptr(payload), _ptr(ok), _ptr(which), self._stream()),
-                "es_select_keyed_batch")
-            return payload, ok, which
-        if key_idx is not None:
+        elif key_idx is not None:
             raise ValueError("key_idx= goes with ring=")
-        if key32 is not None:
+        elif key32 is not None:
             if len(key32) != 32:
                 raise ValueError("AEAD key must be 32 bytes")
             if ctrs is None:
                 raise ValueError("one expected counter per record is required with a key")
+        keyed = ring is not None or key32 is not None
+        if keyed:
             ctrs = self._ctr_dev(ctrs)
             if ctrs.numel() != B:
                 raise ValueError("one expected counter per record is required with a key")
+        kd = self._key_dev(ring, key_idx, B) if ring is not None else None
         payload = torch.empty((B, 55), dtype=torch.uint8, device=self.device)
         ok = torch.empty(B, dtype=torch.int8, device=self.device)
         which = torch.empty(B, dtype=torch.int32, device=self.device)
-        nat.check(self._ctx, self._lib.es_select_batch(
-            self._ctx, None if key32 is None else bytes(key32), _ptr(ctrs) if key32 is not None else None, B, L,
-            _ptr(scl.hard_info), _ptr(scl.hard_ok), _ptr(scl.cand_info), _ptr(scl.cand_metric), _ptr(scl.cand_ok),
-            _ptr(scl.ncand), _ptr(payload), _ptr(ok), _ptr(which), self._stream()), "es_select_batch")
+        lists = (B, L, scl.hard_info, scl.hard_ok, scl.cand_info, scl.cand_metric, scl.cand_ok, scl.ncand, payload, ok, which)
+        if ring is not None:
+            self._call("es_select_keyed_batch", ring.ring, ring.n, kd, ctrs, *lists)
+        else:
+            self._call("es_select_batch", bytes(key32) if keyed else None, ctrs if keyed else None, *lists)
         return payload, ok, which
 
     # ------------------------------------------------------------------ metric unit

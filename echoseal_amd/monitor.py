@@ -296,6 +296,22 @@ def monitor_conditioned(table: MonitorTable, ids: np.ndarray, arrs: list):
     return lengths, other, f_old
 
 
+def pack_chunks(arrs: list, order):
+    """The staging buffer of one upload -> (buf uint8, stride, k32): the float32 chunks of `arrs` in the order `order` visits them, then the
+    int16 chunks in the order `order` visits them, each a zero-filled row of stride = max(4, the longest chunk rounded up to 4) samples; the
+    k32 float32 rows are the first k32 * stride * 4 bytes.  A pure host function."""
+    rows = [i for i in order if arrs[i].dtype != np.int16]
+    k32 = len(rows)
+    rows += [i for i in order if arrs[i].dtype == np.int16]
+    stride = max(4, (max((a.size for a in arrs), default=0) + 3) // 4 * 4)
+    buf = np.zeros(k32 * stride * 4 + (len(rows) - k32) * stride * 2, np.uint8)
+    x32 = buf[:k32 * stride * 4].view(np.float32).reshape(k32, stride)
+    x16 = buf[k32 * stride * 4:].view(np.int16).reshape(len(rows) - k32, stride)
+    for k, i in enumerate(rows):
+        (x32[k] if k < k32 else x16[k - k32])[:arrs[i].size] = arrs[i]
+    return buf, stride, k32
+
+
 def push_arguments(table: MonitorTable, target: int, chunks, streams=None, fs=None):
     """The arguments of a push of live streams (LiveMonitor.push, LiveIdentifier.push), checked without an engine -> (ids int64, chunks as
     1-D int16 / float32 host arrays, their lengths at fs_target).  streams None: one chunk per open stream, in order.  fs= is a check,
@@ -396,8 +412,7 @@ class MonitorTick:
 
 
 class MonitorChain:
-    """The monitor methods of RxEngine (a mixin without state of its own).  From the engine it uses _ctx, _lib, device, _stream and
-    _peak_out."""
+    """The monitor methods of RxEngine (a mixin without state of its own).  From the engine it uses _call, device and _peak_out."""
 
     # ---- chunked resampling on its own (DESIGN 4.16)
     def _resampler_device(self, rt: ResamplerTable) -> None:
@@ -424,9 +439,8 @@ class MonitorChain:
         """One es_resample_stream_batch over records that already lie on the device; the host mirror moves on."""
         rec = np.ascontiguousarray(np.concatenate((np.stack((ids, lengths, rt.n_in_host[ids], f_old, counts), axis=1), rt.rate_host[ids][:, [0, 1, 4]]),
                                                   axis=1).astype(np.int64))                                        # [R, 8], as the C ABI checks it
-        nat.check(self._ctx, self._lib.es_resample_stream_batch(self._ctx, x_ptr, dtype, ids.size, n_stride, sid_ptr, len_ptr, rec.ctypes.data, rt.n,
-                                                                rt.rate.data_ptr(), rt.filt.data_ptr(), int(rt.filters.size), rt.tail.data_ptr(),
-                                                                rt.nin.data_ptr(), out_ptr, out_stride, self._stream()), "es_resample_stream_batch")
+        self._call("es_resample_stream_batch", x_ptr, dtype, ids.size, n_stride, sid_ptr, len_ptr, rec.ctypes.data, rt.n, rt.rate, rt.filt,
+                   int(rt.filters.size), rt.tail, rt.nin, out_ptr, out_stride)
         rt.n_in_host[ids] += lengths
 
     def resample_step(self, table: ResamplerTable, sid, chunks, *, out=None):
@@ -454,13 +468,7 @@ class MonitorChain:
         if R == 0:
             return out[:0], counts
         order = np.argsort([a.dtype == np.int16 for a in arrs], kind="stable")
-        k32 = int(sum(a.dtype != np.int16 for a in arrs))
-        stride = max(4, (int(lengths.max()) + 3) // 4 * 4)
-        buf = np.zeros(k32 * stride * 4 + (R - k32) * stride * 2, np.uint8)
-        x32 = buf[:k32 * stride * 4].view(np.float32).reshape(k32, stride)
-        x16 = buf[k32 * stride * 4:].view(np.int16).reshape(R - k32, stride)
-        for k, i in enumerate(order):
-            (x32 if k < k32 else x16)[k if k < k32 else k - k32, :arrs[i].size] = arrs[i]
+        buf, stride, k32 = pack_chunks(arrs, order)
         xd = torch.from_numpy(buf).to(self.device, non_blocking=True)
         rec_d = torch.from_numpy(np.ascontiguousarray(np.stack((ids[order], lengths[order])))).to(self.device, non_blocking=True)      # [2, R]
         for a, b, dt, byte0 in ((0, k32, nat.ES_DTYPE_F32, 0), (k32, R, nat.ES_DTYPE_I16, k32 * stride * 4)):
@@ -575,23 +583,14 @@ class MonitorChain:
         i16 = np.array([a.dtype == np.int16 for a in arrs], bool)
         order = np.argsort(2 * other + i16, kind="stable")
         nA, nB, nC = (int(np.count_nonzero(m)) for m in (~other & ~i16, ~other & i16, other & ~i16))
-        nD, k32 = R - nA - nB - nC, nA + nC
-        stride = max(4, (int(raw.max()) + 3) // 4 * 4)
-        buf = np.zeros(k32 * stride * 4 + (R - k32) * stride * 2, np.uint8)
-        x32 = buf[:k32 * stride * 4].view(np.float32).reshape(k32, stride)
-        x16 = buf[k32 * stride * 4:].view(np.int16).reshape(R - k32, stride)
-        rows32 = np.concatenate((order[:nA], order[nA + nB: nA + nB + nC]))                                         # records of x32's rows
-        rows16 = np.concatenate((order[nA: nA + nB], order[nA + nB + nC:]))
-        for k, i in enumerate(rows32):
-            x32[k, :arrs[i].size] = arrs[i]
-        for k, i in enumerate(rows16):
-            x16[k, :arrs[i].size] = arrs[i]
+        nD = R - nA - nB - nC
+        buf, stride, k32 = pack_chunks(arrs, order)                         # k32 = nA + nC
         xd = torch.from_numpy(buf).to(self.device, non_blocking=True)
         rec = np.ascontiguousarray(np.stack((ids, lengths, lay.col, lay.move, lay.base), axis=1)[order])          # [R, 5], as the C ABI checks it
         rec_d = torch.from_numpy(np.ascontiguousarray(np.concatenate((rec.T, raw[order][None])))).to(self.device, non_blocking=True)    # [6, R]: + the chunks' own lengths
         pk = np.stack((q_rows, offset, length - (PRE_L - 1))).astype(np.int32)                                      # [3, 4 R], input order
         pk_d = torch.from_numpy(pk).to(self.device, non_blocking=True)
-        S, H, st = table.n, table.hist, self._stream()
+        S, H = table.n, table.hist
         byte16 = k32 * stride * 4
         nE, ostride, cond = nC + nD, 4, None
         if nE:                                                              # condition the other-rate chunks: row e of `cond` = record nA + nB + e
@@ -607,14 +606,11 @@ class MonitorChain:
                                           (nA + nB, R, nat.ES_DTYPE_F32, cond.data_ptr() if nE else 0, ostride)):
             if b > a:
                 cols = [rec_d[w].data_ptr() + 8 * a for w in range(5)]
-                nat.check(self._ctx, self._lib.es_bpf_stream_batch(self._ctx, x_ptr, dt, b - a, n_stride, *cols, rec[a:].ctypes.data, S, H,
-                                                                   table.band.data_ptr(), table.z.data_ptr(), table.pos.data_ptr(),
-                                                                   table.y_hist.data_ptr(), table.corr_hist.data_ptr(), st), "es_bpf_stream_batch")
-        nat.check(self._ctx, self._lib.es_xcorr_stream_batch(self._ctx, table.y_hist.data_ptr(), R, max(stride, ostride), rec_d[0].data_ptr(),
-                                                             rec_d[1].data_ptr(), rec_d[2].data_ptr(), rec.ctypes.data, S, H, table.band.data_ptr(),
-                                                             table.corr_hist.data_ptr(), st), "es_xcorr_stream_batch")
-        nat.check(self._ctx, self._lib.es_pick_at_batch(self._ctx, table.corr_hist.data_ptr(), 4 * S, H, 4 * R, pk_d[0].data_ptr(), pk_d[1].data_ptr(),
-                                                        pk_d[2].data_ptr(), thr.data_ptr(), peaks.data_ptr(), npeaks.data_ptr(), st), "es_pick_at_batch")
+                self._call("es_bpf_stream_batch", x_ptr, dt, b - a, n_stride, *cols, rec[a:].ctypes.data, S, H, table.band, table.z, table.pos,
+                           table.y_hist, table.corr_hist)
+        self._call("es_xcorr_stream_batch", table.y_hist, R, max(stride, ostride), rec_d[0], rec_d[1], rec_d[2], rec.ctypes.data, S, H, table.band,
+                   table.corr_hist)
+        self._call("es_pick_at_batch", table.corr_hist, 4 * S, H, 4 * R, pk_d[0], pk_d[1], pk_d[2], thr, peaks, npeaks)
         xd.record_stream(torch.cuda.current_stream(self.device))
         if cond is not None:
             cond.record_stream(torch.cuda.current_stream(self.device))
@@ -625,5 +621,5 @@ class MonitorChain:
 
 
 __all__ = ["SEG", "MIN_WINDOW", "LiveTable", "MonitorChain", "MonitorLayout", "MonitorTable", "MonitorTick", "ResamplerTable", "check_geometry",
-           "history_columns", "host_table", "monitor_chunks", "monitor_conditioned", "monitor_ids", "monitor_layout", "push_arguments",
+           "history_columns", "host_table", "monitor_chunks", "monitor_conditioned", "monitor_ids", "monitor_layout", "pack_chunks", "push_arguments",
            "resample_counts", "resampler_host", "stream_rates", "window_start"]

@@ -22,10 +22,6 @@ from .scan import ragged_buckets
 from .utils import db_to_lin, mseq_63
 
 
-def _ptr(t: torch.Tensor | None) -> int | None:
-    return None if t is None else t.data_ptr()
-
-
 @dataclass
 class EmbedResult:
     audio: torch.Tensor        # [R,n] float32 watermarked recordings ([n] for 1-D input)
@@ -201,8 +197,8 @@ def _clip_results(rows: torch.Tensor, scale, idx, lengths: np.ndarray, block: in
 
 
 class TxChain:
-    """The transmit methods of RxEngine (a mixin: it has no state of its own).  From the engine it uses _ctx, _lib, device, _stream,
-    _dev, _ctr_dev, _key_dev, _key_host, keyring, polar_encode, schedule and schedule_keyed."""
+    """The transmit methods of RxEngine (a mixin: it has no state of its own).  From the engine it uses _call, device, _dev, _ctr_dev,
+    _key_dev, _key_host, keyring, polar_encode, schedule and schedule_keyed."""
 
     # ------------------------------------------------------------------ device steps the entry points share
     def _seal_args(self, nonces, plain):
@@ -276,7 +272,7 @@ class TxChain:
         if len(key32) != 32:
             raise ValueError("AEAD key must be 32 bytes")
         nonces, plain, n, blobs = self._seal_args(nonces, plain)
-        nat.check(self._ctx, self._lib.es_aead_seal_batch(self._ctx, bytes(key32), _ptr(nonces), _ptr(plain), n, _ptr(blobs), self._stream()), "es_aead_seal_batch")
+        self._call("es_aead_seal_batch", bytes(key32), nonces, plain, n, blobs)
         return blobs
 
     def seal_keyed(self, ring, key_idx, nonces: torch.Tensor, plain: torch.Tensor) -> torch.Tensor:
@@ -286,8 +282,7 @@ class TxChain:
         kd = self._key_dev(ring, key_idx, n)
         if n and ring.n == 0:
             raise ValueError("records but an empty key ring")
-        nat.check(self._ctx, self._lib.es_aead_seal_keyed_batch(self._ctx, _ptr(ring.ring), ring.n, _ptr(kd), _ptr(nonces), _ptr(plain), n, _ptr(blobs),
-                                                                self._stream()), "es_aead_seal_keyed_batch")
+        self._call("es_aead_seal_keyed_batch", ring.ring, ring.n, kd, nonces, plain, n, blobs)
         return blobs
 
     def make_frames(self, sec, band_key32: bytes, ctrs, payloads: torch.Tensor) -> torch.Tensor:
@@ -298,8 +293,7 @@ class TxChain:
         code = self.polar_encode(payloads)
         pn, band = self.schedule(sec._prng.sub_key, band_key32, cd.to(torch.int64) & 0xFFFFFFFF)
         hdr16 = np.packbits(sec.pn_bits(0, 128)).tobytes()
-        nat.check(self._ctx, self._lib.es_tx_frames_batch(self._ctx, _ptr(code), _ptr(pn), _ptr(band), _ptr(cd), pre8, hdr16, B,
-                                                          _ptr(y_ws), _ptr(frames), self._stream()), "es_tx_frames_batch")
+        self._call("es_tx_frames_batch", code, pn, band, cd, pre8, hdr16, B, y_ws, frames)
         return frames
 
     def make_frames_keyed(self, ring, key_idx, ctrs, payloads: torch.Tensor) -> torch.Tensor:
@@ -312,8 +306,7 @@ class TxChain:
             raise ValueError("records but an empty key ring")
         code = self.polar_encode(payloads)
         pn, band = self.schedule_keyed(ring, kd, cd.to(torch.int64) & 0xFFFFFFFF)
-        nat.check(self._ctx, self._lib.es_tx_frames_keyed_batch(self._ctx, _ptr(code), _ptr(pn), _ptr(band), _ptr(cd), pre8, _ptr(ring.ring), ring.n,
-                                                                _ptr(kd), B, _ptr(y_ws), _ptr(frames), self._stream()), "es_tx_frames_keyed_batch")
+        self._call("es_tx_frames_keyed_batch", code, pn, band, cd, pre8, ring.ring, ring.n, kd, B, y_ws, frames)
         return frames
 
     def synthetic_frames(self, key32: bytes, ctr0: int, n: int, *, seed: int = 20260101):
@@ -365,8 +358,7 @@ class TxChain:
             if chip_off.numel() != R:
                 raise ValueError("chip_off: one offset per recording")
         out, block, scale = self._mix_out(x, out, block, want_scale)
-        nat.check(self._ctx, self._lib.es_mix_batch(self._ctx, _ptr(x), R, n, block, _ptr(chips), chips.shape[1], _ptr(chip_off), db_to_lin(target_rel_db),
-                                                    db_to_lin(floor_rel_dbfs), _ptr(out), _ptr(scale), self._stream()), "es_mix_batch")
+        self._call("es_mix_batch", x, R, n, block, chips, chips.shape[1], chip_off, db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), out, scale)
         return (out, scale) if want_scale else out
 
     def mix_ragged(self, x: torch.Tensor, lens, chips: torch.Tensor, chip_base, chip_cnt, *, block: int = 1024, target_rel_db: float = -10.0,
@@ -384,8 +376,8 @@ class TxChain:
         if lens.numel() != R or chip_base.numel() != R or chip_cnt.numel() != R:
             raise ValueError("lens, chip_base, chip_cnt: one entry per recording")
         out, block, scale = self._mix_out(x, out, block, want_scale)
-        nat.check(self._ctx, self._lib.es_mix_ragged_batch(self._ctx, _ptr(x), R, n, _ptr(lens), block, _ptr(chips), chips.numel(), _ptr(chip_base), _ptr(chip_cnt),
-                                                           db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs), _ptr(out), _ptr(scale), self._stream()), "es_mix_ragged_batch")
+        self._call("es_mix_ragged_batch", x, R, n, lens, block, chips, chips.numel(), chip_base, chip_cnt, db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs),
+                   out, scale)
         return (out, scale) if want_scale else out
 
     # ------------------------------------------------------------------ the entry points: recordings of one key, clips of many, live streams
@@ -580,13 +572,11 @@ class TxChain:
                 blobs = self._launch_blobs(table.ring, kf_d, ctr_d, lay.ctr, payloads, idx, lay.nf, seed, (table.nonce8, fr[2]))      # (the stream's own nonce)
                 frames = self.make_frames_keyed(table.ring, kf_d, ctr_d, blobs)
             scale = self._mix_out(x, x, block, want_scale)[2]
-            tick = (n, stride, _ptr(rec_d[2]))
-            pool = (_ptr(frames), F * nat.ES_FRAME_LEN, _ptr(rec_d[3]), _ptr(rec_d[4]), rec.ctypes.data)
-            nat.check(self._ctx, self._lib.es_mix_stream_batch(self._ctx, _ptr(x), *tick, block, _ptr(rec_d[0]), table.n, _ptr(table.tail),
-                                                               _ptr(table.off), *pool, db_to_lin(target_rel_db), db_to_lin(floor_rel_dbfs),
-                                                               _ptr(x), _ptr(scale), self._stream()), "es_mix_stream_batch")
-            nat.check(self._ctx, self._lib.es_stream_commit_batch(self._ctx, *tick, _ptr(rec_d[0]), table.n, _ptr(table.tail), _ptr(table.ctr),
-                                                                  _ptr(table.off), *pool, self._stream()), "es_stream_commit_batch")
+            tick = (n, stride, rec_d[2])
+            pool = (frames, F * nat.ES_FRAME_LEN, rec_d[3], rec_d[4], rec.ctypes.data)
+            self._call("es_mix_stream_batch", x, *tick, block, rec_d[0], table.n, table.tail, table.off, *pool, db_to_lin(target_rel_db),
+                       db_to_lin(floor_rel_dbfs), x, scale)
+            self._call("es_stream_commit_batch", *tick, rec_d[0], table.n, table.tail, table.ctr, table.off, *pool)
             table.ctr_host[rows], table.off_host[rows] = lay.ctr_next, lay.off_next
             _clip_results(x, scale, idx, lengths, block, lay.ctr_next, lay.off_next, out)
         return out
