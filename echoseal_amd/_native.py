@@ -2,6 +2,8 @@
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  The hot path only ever runs on the HIP kernels.
+
+The header is the one statement of the ABI: SIGNATURES and every ES_* constant of this module are read from it at import (bind_header).
 """
 from __future__ import annotations
 
@@ -11,9 +13,10 @@ import re
 import sys
 
 import torch  # noqa: F401  -- must be imported BEFORE the HIP library so that both share torch's HIP runtime
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_void_p
+from ctypes import c_char_p, c_double, c_int, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_hip.h")
 
 
 class NativeError(RuntimeError):
@@ -33,117 +36,61 @@ def variant_path(variant):
 LIB_VARIANT = os.environ.get("ES_LIB_VARIANT", "")
 LIB_PATH = variant_path(LIB_VARIANT)
 
-ES_ABI_VERSION = 2          # include/echoseal_hip.h; load() refuses a library built from another one
-ES_FRAME_LEN = 1215
-ES_PRE_L = 63
-ES_NBANDS = 4
-ES_MAX_TAPS = 576
-ES_MAX_TAPS_FAST = 160
-ES_MAX_PEAKS = 32
-ES_MAX_LIST = 1024
-ES_PN_BYTES = 152
-ES_KEYRING_BYTES = 304
-ES_MAX_TRIES = 400
-ES_PEAK_LIMIT = 25
-ES_INFO_BYTES = 55
-ES_DTYPE_F32, ES_DTYPE_I16, ES_DTYPE_F64 = 0, 1, 2
-ES_RESAMPLE_DESC_WORDS, ES_RESAMPLE_TILE = 8, 1024     # es_resample_ragged_batch: int64 words per record, outputs per workgroup
-# what es_resample_ragged_kernel holds in LDS per tile (window samples, table values; more is read through L2) and what it refuses: reduced
-# up, down or taps per phase above RATE_MAX, a polyphase table above TABLE_MAX values (utils.resample_limits keeps such clips on the host)
-ES_RESAMPLE_WIN_MAX, ES_RESAMPLE_FILT_MAX, ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TABLE_MAX = 4352, 3584, 1 << 20, 1 << 30
-ES_STREAM_REC_WORDS = 5                                # es_mix_stream_batch / es_stream_commit_batch: int64 words per record of rec_host
-ES_MONITOR_REC_WORDS = 5                               # es_bpf_stream_batch / es_xcorr_stream_batch: (sid, len, col, move, base)
-ES_RSTREAM_REC_WORDS, ES_RSTREAM_RATE_WORDS, ES_RSTREAM_TAIL = 8, 5, 256     # es_resample_stream_batch: host record, rate words, tail row
-ES_MEMO_EMPTY = 0xFFFFFFFFFFFFFFFF                     # both words of an empty memo entry (es_memo_probe_batch / es_memo_insert_batch)
-ES_XC_SEG = 1216                                       # lags per segment of the correlation kernel (64 lanes x 19): a monitor's window grid
+# The binding rule.  A parameter: a pointer is c_void_p -- except `const char*` and a `const uint8_t* <name>_host` (bytes objects: c_char_p);
+# a scalar is one of the four below.  A return type is one of _RESTYPES.  Anything else is refused by name.
+_SCALARS = {"int": c_int, "int64_t": c_int64, "uint32_t": c_uint32, "double": c_double}
+_RESTYPES = {"int": c_int, "void": None, "es_ctx*": c_void_p, "const char*": c_char_p}
+_INT = r"(?:0[xX][0-9a-fA-F]+|[0-9]+)[uUlL]*"
 
-# name -> (restype, argtypes); kept next to the header so a test can check both agree
-SIGNATURES = {
-    "es_create": (c_void_p, [c_int, c_int]),
-    "es_destroy": (None, [c_void_p]),
-    "es_last_error": (c_char_p, [c_void_p]),
-    "es_abi_version": (c_int, []),
-    "es_info_bytes": (c_int, [c_void_p]),
-    "es_set_tables": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_bpf_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "es_bpf2_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_xcorr32_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "es_pick_exact_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p]),
-    "es_sync_fused_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p]),
-    "es_front_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_reserve": (c_int, [c_void_p, c_int64, c_int]),
-    "es_xcorr_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "es_pick_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_sync_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_llr_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                             c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_header_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_llr_at_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_header_at_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_front_peak_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_scl_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_polar_encode_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_schedule_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_void_p, ctypes.c_uint32, c_int64, c_void_p, c_void_p, c_void_p]),
-    "es_tx_frames_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_char_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "es_mix_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
-    "es_resample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
-    "es_resample_ragged_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64,
-                                         c_void_p]),
-    "es_resample_stream_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                         c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "es_set_option": (c_int, [c_void_p, c_char_p, c_int]),
-    "es_softplus_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_polar_f_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "es_aead_check_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_aead_seal_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_select_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_keyring_derive_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_schedule_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "es_aead_check_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_void_p]),
-    "es_select_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_aead_seal_keyed_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_tx_frames_keyed_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_char_p, c_void_p, c_int64, c_void_p, c_int64,
-                                         c_void_p, c_void_p, c_void_p]),
-    "es_mix_ragged_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_double,
-                                    c_double, c_void_p, c_void_p, c_void_p]),
-    "es_mix_stream_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                    c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
-    "es_stream_commit_batch": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_bpf_stream_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_xcorr_stream_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
-                                      c_void_p, c_void_p]),
-    "es_pick_at_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p]),
-    "es_plan_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,
-                              c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_sync_ragged_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_plan_ragged_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
-                                     c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "es_plan_at_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
-                                 c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p]),
-    "es_hop_window_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "es_acquire_mask_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
-                                      c_void_p, c_void_p]),
-    "es_acquire_list_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "es_memo_probe_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "es_memo_insert_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
-}
+
+def _ctype(name, ctype, param):
+    if ctype in _SCALARS:
+        return _SCALARS[ctype]
+    if re.fullmatch(r"(?:const )?\w+\*", ctype):
+        return c_char_p if ctype == "const char*" or (ctype == "const uint8_t*" and param.endswith("_host")) else c_void_p
+    raise NativeError(f"{name}: parameter `{ctype} {param}` has a type outside the binding rule (_native.bind_header)")
+
+
+def _define(name, value):
+    """An integer literal (decimal or hex, u / l suffixes, a sign, parentheses) or `a << b` of two of them."""
+    v = value.strip()
+    while v.startswith("(") and v.endswith(")"):
+        v = v[1:-1].strip()
+    m = re.fullmatch(rf"(-?{_INT})(?:\s*<<\s*({_INT}))?", v)
+    if not m:
+        raise NativeError(f"#define {name} {value.strip()}: not an integer literal or `a << b` (_native.bind_header)")
+    a, b = (int(g.rstrip("uUlL"), 0) if g else 0 for g in m.groups())
+    return a << b
+
+
+def bind_header(text):
+    """(declarations, signatures, constants) of a header in the style of include/echoseal_hip.h: name -> [(C type, parameter name)],
+    name -> (restype, argtypes), ES_* name -> int.  Nothing is skipped: a type or a value outside the rule raises NativeError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {name: _define(name, value) for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ES_\w+)[ \t]+(.*?)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    declarations, signatures = {}, {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\b(es_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RESTYPES:
+            raise NativeError(f"{name}: return type `{ret}` is outside the binding rule (_native.bind_header)")
+        decl = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = re.fullmatch(r"(.*?)(\w+)", " ".join(p.split()))
+            if not m or not m.group(1).strip():
+                raise NativeError(f"{name}: cannot read the parameter `{p.strip()}` (_native.bind_header)")
+            decl.append((re.sub(r"\s*\*", "*", m.group(1).strip()), m.group(2)))
+        declarations[name] = decl
+        signatures[name] = (_RESTYPES[ret], [_ctype(name, t, n) for t, n in decl])
+    return declarations, signatures, constants
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        DECLARATIONS, SIGNATURES, CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{HEADER_PATH}: the C ABI's header is what this module binds from ({e})") from None
+globals().update(CONSTANTS)              # ES_ABI_VERSION (load() refuses a library built from another one), ES_FRAME_LEN, ES_DTYPE_F32 ...
 
 _lib = None
 
@@ -163,8 +110,8 @@ def load() -> ctypes.CDLL:
         got = int(lib.es_abi_version())
     except AttributeError:
         got = None
-    if got != ES_ABI_VERSION:
-        raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {ES_ABI_VERSION} "
+    if got != CONSTANTS["ES_ABI_VERSION"]:
+        raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree

@@ -106,10 +106,13 @@ es_ctx* es_create(int device, int list_size_max)
     hipDeviceProp_t prop;
     if (!g.ok || hipGetDeviceProperties(&prop, device) != hipSuccess) { g_create_err = "hipGetDeviceProperties failed"; delete ctx; return nullptr; }
     ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    es_host_sbox(ctx->h_sbox);
     if (hipMalloc(&ctx->d_tables, sizeof(es_band_tables)) != hipSuccess ||
         hipMalloc(&ctx->d_data_pos, sizeof(uint16_t) * ES_POLAR_N) != hipSuccess ||
         hipMalloc(&ctx->d_exp_tab, sizeof(kExpTab)) != hipSuccess ||
-        hipMemcpy(ctx->d_exp_tab, kExpTab, sizeof(kExpTab), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(ctx->d_exp_tab, kExpTab, sizeof(kExpTab), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&ctx->d_sbox, sizeof ctx->h_sbox) != hipSuccess ||
+        hipMemcpy(ctx->d_sbox, ctx->h_sbox, sizeof ctx->h_sbox, hipMemcpyHostToDevice) != hipSuccess) {
         g_create_err = "device allocation failed in es_create";
         es_destroy(ctx);
         return nullptr;
@@ -168,7 +171,6 @@ void es_destroy(es_ctx* ctx)
     if (ctx->d_wide_scratch) (void)hipFree(ctx->d_wide_scratch);
     if (ctx->d_wide_slot_bits) (void)hipFree(ctx->d_wide_slot_bits);
     if (ctx->d_sbox) (void)hipFree(ctx->d_sbox);
-    if (ctx->d_hdr_pn) (void)hipFree(ctx->d_hdr_pn);
     if (ctx->d_cursors) (void)hipFree(ctx->d_cursors);
     delete ctx;
 }

@@ -51,8 +51,8 @@ struct es_ctx {
     void*   d_wide_scratch = nullptr; size_t wide_scratch_bytes = 0; long long wide_lanes = 0;   /* lane-per-path list decoder (es_scl_wide.hip): list sizes 64..1024, and shorter lists with scl_lanes = 1; its slab in lanes */
     bool    wide_enabled = false;
     unsigned* d_wide_slot_bits = nullptr; int wide_slot_words = 0;   /* its slab slot bitmap (>= 128 words: a slot per one-wave block of the slab, 3 072 / 4 096 on 256 CUs) */
-    uint8_t* d_sbox = nullptr;        /* AES S-box (es_schedule_batch) */
-    uint8_t* d_hdr_pn = nullptr;      /* packed header PN (es_tx_frames_batch) */
+    uint8_t* d_sbox = nullptr;        /* AES S-box (es_schedule_batch and the key-ring entry points), filled by es_create ... */
+    uint8_t h_sbox[256] = {};         /* ... from this host copy, which es_launch_schedule expands its round keys with */
     /* Who is using a scratch slab (es_slab_enter).  Domain 0 = d_scl_scratch (es_scl.hip, es_scl_multi.hip),
        domain 1 = d_wide_scratch (es_scl_wide.hip).  `shape`: how the launch cuts the slab into slots; launches of one shareable shape on
        several streams share the slab through its slot bitmap, anything else is ordered behind the outstanding launches. */
@@ -121,6 +121,7 @@ __device__ __forceinline__ int es_wave_read_lane(int v, int src) { return __buil
  * of 64 lanes x XC_R consecutive lags (19 is odd: a lane stride of 19 words is free of LDS bank conflicts), a block is XC_WAVES waves. */
 constexpr int XC_R = 19;
 constexpr int XC_SEG = 64 * XC_R;                  /* lags per wave */
+static_assert(XC_SEG == ES_XC_SEG, "include/echoseal_hip.h states the correlation segment for the host");
 constexpr int XC_WAVES = 4;
 
 /* kernels exist for power-of-two list sizes; a context created for list_size_max serves every size up to the next one */
@@ -215,7 +216,7 @@ struct es_stream_commit_args {
     const float* chips; int64_t chips_total; const int64_t* chip_base; const int64_t* chip_cnt;
 };
 int es_launch_stream_commit(es_ctx* ctx, const es_stream_commit_args& a, hipStream_t st);
-/* es_launch_tx_frames with the header PN of frame f read from ring row key[f] (es_tx.hip): no host memory, only enqueues */
+/* es_launch_tx_frames with the header PN of frame f read from ring row key[f] (es_tx.hip) */
 int es_launch_tx_frames_keyed(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows, const uint8_t* band, const uint32_t* ctr,
                               unsigned long long pre_bits, const uint8_t* ring, int64_t N, const int32_t* key, int64_t B, double* y_ws,
                               float* frames, hipStream_t st);
@@ -252,7 +253,7 @@ int es_launch_select(es_ctx* ctx, const uint8_t* key32, const uint32_t* ctr, int
                      const uint8_t* hard_ok, const uint8_t* cand_info, const double* cand_metric, const uint8_t* cand_ok,
                      const int32_t* ncand, uint8_t* payload, int8_t* ok, int32_t* which, hipStream_t st);
 /* many keys at once (es_keyring.hip, es_aead.hip): ring rows of ES_KEYRING_BYTES, key = ring row of each record */
-int es_ensure_sbox(es_ctx* ctx);                                 /* ctx->d_sbox, created on first use (es_sched.hip) */
+void es_host_sbox(uint8_t sb[256]);                              /* the AES S-box, computed (es_sched.hip): es_create fills h_sbox / d_sbox with it */
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st);
 int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t n,
                              uint8_t* pn_rows, uint8_t* band, hipStream_t st);

@@ -372,7 +372,6 @@ __global__ __launch_bounds__(256) void es_acquire_list_kernel(const uint32_t* __
 
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
 {
-    if (const int rc = es_ensure_sbox(ctx)) return rc;
     return es_launch(ctx, es_keyring_derive_kernel, es_grid(N, 256, ctx->num_cu * 8), 256, 0, st, master32, (long long)N,
                      (const uint8_t*)ctx->d_sbox, ring);
 }
@@ -380,7 +379,6 @@ int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, ui
 int es_launch_schedule_keyed(es_ctx* ctx, const uint8_t* ring, int64_t N, const int32_t* key, const uint32_t* ctr, int64_t n,
                              uint8_t* pn_rows, uint8_t* band, hipStream_t st)
 {
-    if (const int rc = es_ensure_sbox(ctx)) return rc;
     return es_launch(ctx, es_schedule_keyed_kernel, es_grid(n, 256, ctx->num_cu * 8), 256, 0, st, ring, (long long)N, key, ctr,
                      (long long)n, (const uint8_t*)ctx->d_sbox, pn_rows, band);
 }

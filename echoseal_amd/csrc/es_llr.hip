@@ -239,17 +239,6 @@ struct LlrWaveLds {
     uint32_t pnw[32];                                                         // payload PN bits, first = MSB of word 0
 };
 
-#ifdef ES_LLR_STAMPS
-// Diagnostic build: cycles per phase, summed over the records of a launch.  The stamps are atomics, i.e. vector-memory operations: the first
-// interval that waits on vmcnt (the sample loads) also waits for them, so "load" reads several times too large (the load phase alone, with
-// the arithmetic compiled out, is 0.13 ms of the kernel's 1.2 ms per 65 536 records); the other phases compare with each other.
-__device__ unsigned long long g_llr_dbg[16];
-#define LLR_STAMP(k) do { __builtin_amdgcn_s_waitcnt(0xC07F); const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-        if (lane == 0) atomicAdd(&g_llr_dbg[k], _t - t_last); t_last = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define LLR_STAMP(k) do { } while (0)
-#endif
-
 // Record addressing.  AT = false (es_llr_batch / es_header_batch): record i is row i of y, its frame starts at start[i] (NULL = 0).
 // AT = true (the *_at entry points): record i is row r = row[i] (NULL = i) from s = max(start[i * start_stride], 0) (NULL = 0); a row
 // outside [0, n_rows) reads as a start at T, i.e. an empty frame, and nothing of y is read for it.  Band, PN rows and every output are
@@ -294,9 +283,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
     rec_addr<AT>(rec, B, T, start, row, n_rows, start_stride, st_next, ro_next);
     int bi_next = (rec < B) ? band[rec] : 0;
     for (; rec < B; rec += stride) {
-#ifdef ES_LLR_STAMPS
-        unsigned long long t_last = __builtin_amdgcn_s_memtime();
-#endif
         float* out = llr + rec * NPAY;
         const int st0 = st_next;
         const long long roff = ro_next;
@@ -316,7 +302,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
         const double* fr = (AT ? y + roff : y + rec * T) + st0;
         const int prefix = mem < PAYLOAD_START ? mem : PAYLOAD_START; // :327
         const int nfull = prefix + npl;
-        LLR_STAMP(8);
         {
             // All the record's samples are requested before the first one is used: unconditional loads from clamped addresses, no
             // control flow between a load and its use (a bounds test per element made the compiler wait for every load where it was
@@ -351,7 +336,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             W.pnw[lane] = (uint32_t)(v >> (8 - sh));
         }
         fence();
-        LLR_STAMP(0);
         auto pn_sym = [&](int i) { return ((W.pnw[i >> 5] >> (31 - (i & 31))) & 1u) ? 1.0f : -1.0f; };
 
         // ---- geometry (:335-363)
@@ -401,7 +385,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             }
         }
         fence();
-        LLR_STAMP(1);
 
         // ---- shift search (:366-379): score(s) = mean(|win[base+s+i] * pn[i]|, i >= guard).  pn[i] is +-1, so |win * pn| ==
         // |win| exactly: the scores are NumPy pairwise sums over sliding windows of |win|.  (The sums themselves cannot slide:
@@ -438,7 +421,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             for (int j = j0; j < j1; ++j) { run += (double)__builtin_fabsf(W.win[j]); put(j + 1, run); }
         }
         fence();
-        LLR_STAMP(2);
         const bool finite_all = total < 1.0e37;                      // float32 sums cannot overflow below this
         double a1 = -1.0, a2 = -1.0;                                 // two largest exact-sum scores (with multiplicity)
         for (int u = lane; u < nshift; u += 64) {
@@ -467,7 +449,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             ncand += __popcll(mb);
         }
         fence();
-        LLR_STAMP(3);
         float best = -1.0f, second = -1.0f; int best_s = 0;
         for (int ci = 0; ci < ncand; ++ci) {                         // ascending shift: the first maximum wins (strict > in the reference)
             const int s = W.b.sh.cand[ci];
@@ -477,7 +458,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             else if (score > second) second = score;
         }
 
-        LLR_STAMP(4);
         // ---- despread at the chosen shift (:382-385)
         const int a0 = base + best_s;
         fence();
@@ -490,11 +470,9 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
         const float* tail = W.a.d + toff;
         const float medv = wave_median_hist_f32(W.b.hist, nt, lane, [&](int i) { return tail[i]; });
         const float madv = wave_median_hist_f32(W.b.hist, nt, lane, [&](int i) { return __builtin_fabsf(tail[i] - medv); });
-        LLR_STAMP(5);
         PwPlan tp; pw_plan_build(tp, nt);
         const float mu = wave_pairwise_sum(tp, lane, [&](int i) { return tail[i]; }) / (float)nt;
         const float var = wave_pairwise_sum(tp, lane, [&](int i) { const float c = tail[i] - mu; return c * c; }) / (float)nt;
-        LLR_STAMP(6);
         const double mad = (double)madv + 1e-12;
         const double sigma_mad = 1.4826 * mad;
         const double sigma_std = (double)__builtin_sqrtf(var) + 1e-12;
@@ -518,7 +496,6 @@ __global__ __launch_bounds__(64 * LW_WAVES, 3) void es_llr_wave_kernel(const dou
             if (score_out) { score_out[2 * rec] = best; score_out[2 * rec + 1] = second; }
         }
         fence();
-        LLR_STAMP(7);
     }
 }
 
@@ -658,20 +635,8 @@ int es_launch_llr(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t*
                   const uint8_t* band, const uint8_t* pn, int variant, float* llr, int32_t* best_s,
                   float* score, hipStream_t st)
 {
-    const int rc = es_launch(ctx, ES_BY_TAPS_AT(es_llr_wave_kernel, ctx, at), es_grid(B, LW_WAVES, ctx->num_cu * 64 / LW_WAVES), 64 * LW_WAVES, 0, st,
-                             y, (long long)B, T, start, band, pn, variant, ctx->d_tables, llr, best_s, score, at.row, (long long)at.n_rows, at.start_stride);
-#ifdef ES_LLR_STAMPS
-    {   // diagnostic build only: share of the phases, summed over the records of this launch
-        unsigned long long h[16]; static const unsigned long long z[16] = {0};
-        (void)hipDeviceSynchronize(); (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_llr_dbg), sizeof h); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_llr_dbg), z, sizeof z);
-        const char* nm[9] = {"load", "matched filter", "prefix sums", "scores+candidates", "exact candidate sums", "despread+medians", "mean/var", "scale+store", "meta"};
-        unsigned long long tot = 0; for (int k = 0; k < 9; ++k) tot += h[k];
-        fprintf(stderr, "[llr stamps B=%lld]", (long long)B);
-        for (int k = 0; k < 9; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * h[k] / (tot ? tot : 1));
-        fprintf(stderr, "\n");
-    }
-#endif
-    return rc;
+    return es_launch(ctx, ES_BY_TAPS_AT(es_llr_wave_kernel, ctx, at), es_grid(B, LW_WAVES, ctx->num_cu * 64 / LW_WAVES), 64 * LW_WAVES, 0, st,
+                     y, (long long)B, T, start, band, pn, variant, ctx->d_tables, llr, best_s, score, at.row, (long long)at.n_rows, at.start_stride);
 }
 
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,

@@ -57,16 +57,6 @@ __global__ __launch_bounds__(256) void es_schedule_kernel(SchedKeys k, const uin
 // ---- host side: S-box, key expansion, HMAC pad states (FIPS 197 / FIPS 180-4 / RFC 2104) ----------------------
 uint8_t h_xt(uint8_t x) { return (uint8_t)((x << 1) ^ ((x >> 7) * 0x1b)); }
 uint8_t h_gmul(uint8_t a, uint8_t b) { uint8_t p = 0; while (b) { if (b & 1) p ^= a; a = h_xt(a); b >>= 1; } return p; }
-void host_sbox(uint8_t sb[256])
-{
-    for (int x = 0; x < 256; ++x) {
-        uint8_t inv = 0;
-        if (x) for (int yv = 1; yv < 256; ++yv) if (h_gmul((uint8_t)x, (uint8_t)yv) == 1) { inv = (uint8_t)yv; break; }
-        uint8_t s = inv, r = inv;
-        for (int i = 0; i < 4; ++i) { r = (uint8_t)((r << 1) | (r >> 7)); s ^= r; }
-        sb[x] = (uint8_t)(s ^ 0x63);
-    }
-}
 uint32_t h_ror(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 void host_sha256_compress(uint32_t st[8], const uint8_t blk[64])
 {
@@ -93,24 +83,22 @@ void host_sha256_compress(uint32_t st[8], const uint8_t blk[64])
 
 }  // namespace
 
-// the AES S-box on the device, created on first use (es_schedule_batch and the key-ring entry points)
-int es_ensure_sbox(es_ctx* ctx)
+// the AES S-box (FIPS 197 5.1.1: the inverse in GF(2^8), then the affine map), computed once per context by es_create
+void es_host_sbox(uint8_t sb[256])
 {
-    if (!ctx->d_sbox) {
-        uint8_t sb[256];
-        host_sbox(sb);
-        ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_sbox, 256));
-        ES_HIP_CHECK(ctx, hipMemcpy(ctx->d_sbox, sb, 256, hipMemcpyHostToDevice));
+    for (int x = 0; x < 256; ++x) {
+        uint8_t inv = 0;
+        if (x) for (int yv = 1; yv < 256; ++yv) if (h_gmul((uint8_t)x, (uint8_t)yv) == 1) { inv = (uint8_t)yv; break; }
+        uint8_t s = inv, r = inv;
+        for (int i = 0; i < 4; ++i) { r = (uint8_t)((r << 1) | (r >> 7)); s ^= r; }
+        sb[x] = (uint8_t)(s ^ 0x63);
     }
-    return ES_OK;
 }
 
 int es_launch_schedule(es_ctx* ctx, const uint8_t* aes_key16, const uint8_t* band_key32, const uint32_t* ctr_dev,
                        uint32_t ctr0, int64_t n, uint8_t* pn_rows, uint8_t* band, hipStream_t st)
 {
-    uint8_t sb[256];
-    host_sbox(sb);
-    if (const int rc = es_ensure_sbox(ctx)) return rc;
+    const uint8_t* sb = ctx->h_sbox;
     SchedKeys k;
     uint8_t rk[176];
     std::memcpy(rk, aes_key16, 16);

@@ -7,9 +7,10 @@
 //   state handed over = one pass; es_bpf_batch, bit-exact SciPy order); then the peak rule of :137-141
 //   (peak = max|chips| + 1e-12; if peak > 3: chips *= 1/peak) and the cast to float32.
 // The chips of a frame are written once, in tx_symbols_frame; two thin symbol kernels hand it the 16 header-PN bytes in LDS: one header
-// PN for the batch (es_tx_frames_batch), or that of each frame's key read from the key ring (es_tx_frames_keyed_batch:
+// PN for the batch, passed by value (es_tx_frames_batch), or that of each frame's key read from the key ring (es_tx_frames_keyed_batch:
 // rtwm/embedder.py:50, 105 per key).
 #include "es_internal.h"
+#include <cstring>
 
 namespace {
 
@@ -39,13 +40,15 @@ __device__ __forceinline__ void tx_symbols_frame(const uint8_t* __restrict__ cod
     }
 }
 
-// one header PN for the batch
+struct HdrPn { uint32_t w[4]; };                                  // the 16 packed header-PN bytes in memory order, by value
+
+// one header PN for the batch, a kernel argument like pre_bits
 __global__ __launch_bounds__(256) void es_tx_symbols_kernel(const uint8_t* __restrict__ code, const uint8_t* __restrict__ pn_rows,
-        const uint32_t* __restrict__ ctr, unsigned long long pre_bits, const uint8_t* __restrict__ hdr_pn_g, long long B,
-        float* __restrict__ sym)
+        const uint32_t* __restrict__ ctr, unsigned long long pre_bits, HdrPn hdr_pn_v, long long B, float* __restrict__ sym)
 {
     __shared__ uint8_t hdr_pn[16];
-    if (threadIdx.x < 16) hdr_pn[threadIdx.x] = hdr_pn_g[threadIdx.x];
+    if (threadIdx.x < 16)                                             // byte t = bits 8 (t & 3) .. of word t >> 2, read from the argument segment: no private copy
+        hdr_pn[threadIdx.x] = (uint8_t)(hdr_pn_v.w[threadIdx.x >> 2] >> (8 * (threadIdx.x & 3)));
     __syncthreads();
     for (long long f = blockIdx.x; f < B; f += gridDim.x) tx_symbols_frame(code, pn_rows, ctr, pre_bits, hdr_pn, f, sym);
 }
@@ -94,11 +97,11 @@ __global__ __launch_bounds__(256) void es_tx_finish_kernel(const double* __restr
 int es_launch_tx_frames(es_ctx* ctx, const uint8_t* code, const uint8_t* pn_rows, const uint8_t* band, const uint32_t* ctr,
                         unsigned long long pre_bits, const uint8_t* hdr_pn16, int64_t B, double* y_ws, float* frames, hipStream_t st)
 {
-    if (!ctx->d_hdr_pn) ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_hdr_pn, 16));
-    ES_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_hdr_pn, hdr_pn16, 16, hipMemcpyHostToDevice, st));
+    HdrPn hdr_pn;
+    std::memcpy(hdr_pn.w, hdr_pn16, 16);
     const long long cap = (long long)ctx->num_cu * 16;
-    int rc = es_launch(ctx, es_tx_symbols_kernel, es_grid(B, 1, cap), 256, 0, st, code, pn_rows, ctr, pre_bits,
-                       ctx->d_hdr_pn, (long long)B, frames);
+    int rc = es_launch(ctx, es_tx_symbols_kernel, es_grid(B, 1, cap), 256, 0, st, code, pn_rows, ctr, pre_bits, hdr_pn, (long long)B,
+                       frames);
     if (rc != ES_OK) return rc;
     rc = es_launch_bpf(ctx, frames, ES_DTYPE_F32, B, ES_FRAME_LEN, band, y_ws, nullptr, st);
     if (rc != ES_OK) return rc;

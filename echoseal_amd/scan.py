@@ -10,13 +10,14 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _native as nat
 from .utils import resample_limits, resampled_length
 
-PRE_L = 63               # chips of the sync template (utils.mseq_63)
-FRAME_LEN = 1215         # PRE_L + 128 header chips + 1024 code bits
-PEAK_LIMIT = 25          # rtwm/detector.py:108
+PRE_L = nat.ES_PRE_L              # 63 chips of the sync template (utils.mseq_63)
+FRAME_LEN = nat.ES_FRAME_LEN      # 1215 = PRE_L + 128 header chips + 1024 code bits
+PEAK_LIMIT = nat.ES_PEAK_LIMIT    # 25, rtwm/detector.py:108
 
-MAX_TRIES = 400          # rtwm/detector.py:107
+MAX_TRIES = nat.ES_MAX_TRIES      # 400, rtwm/detector.py:107
 TIGHT_DELTA = 3          # rtwm/detector.py:131: the counter window around a peak's estimate when its header failed ...
 WIDE_DELTA = 200         # rtwm/detector.py:118: ... and the widest one
 CTR_END = 1 << 32        # frame counters are 32-bit words: the header carries their low 16 bits, the payload all of them

@@ -15,10 +15,11 @@ from functools import lru_cache
 import numpy as np
 from scipy.signal import lfilter
 
+from ._native import ES_MAX_TAPS
 from .reliability import Q_NMAX_1024
 from .utils import BAND_PLAN, butter_bandpass, mseq_63
 
-MAX_TAPS = 576          # ES_MAX_TAPS: row stride of the tap table (the kernels' small-footprint instantiation serves up to 160)
+MAX_TAPS = ES_MAX_TAPS  # 576: row stride of the tap table (the kernels' small-footprint instantiation serves up to 160)
 
 
 @lru_cache(maxsize=None)

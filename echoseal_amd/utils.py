@@ -17,6 +17,7 @@ from typing import Tuple
 import numpy as np
 from scipy.signal import butter, resample_poly
 
+from ._native import ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TABLE_MAX, ES_RSTREAM_TAIL
 from .primitives import aes128_encrypt_blocks
 
 BAND_PLAN: list[Tuple[int, int]] = [
@@ -145,7 +146,6 @@ def resample_limits(n_in: int, fs_orig: int, fs_target: int) -> str | None:
     """What keeps es_resample_ragged_batch from conditioning a clip of n_in samples at fs_orig to fs_target, in words, or None when
     it can: the kernel steps through a tile in 32 bits and writes nothing for a record whose reduced up, down or taps per phase are
     above ES_RESAMPLE_RATE_MAX or whose polyphase table has more than ES_RESAMPLE_TABLE_MAX values (include/echoseal_hip.h)."""
-    from ._native import ES_RESAMPLE_RATE_MAX, ES_RESAMPLE_TABLE_MAX
     g = math.gcd(int(fs_orig), int(fs_target))
     up, down = int(fs_target) // g, int(fs_orig) // g
     if max(up, down) > ES_RESAMPLE_RATE_MAX:                                # (before the geometry: its integers are then of no use)
@@ -174,7 +174,7 @@ class StreamResamplePlan:
     h_tf: np.ndarray
 
 
-STREAM_TAPS_MAX = 256                                                       # ES_RSTREAM_TAIL: a stream's tail row holds the 255 samples before its chunk
+STREAM_TAPS_MAX = ES_RSTREAM_TAIL                                           # 256: a stream's tail row holds the 255 samples before its chunk
 
 
 def stream_geometry(fs_in: int, fs_target: int):

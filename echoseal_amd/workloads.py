@@ -18,8 +18,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._native import ES_FRAME_LEN
+
 KEY = b"\xAA" * 32
-FRAME_LEN = 1215
+FRAME_LEN = ES_FRAME_LEN     # 1215
 C3_WINDOW = 2048
 C3_SNR_DB = -15.0
 

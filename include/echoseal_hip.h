@@ -14,6 +14,9 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls only enqueue
  *     work; they never synchronise the device, so they may be captured into a hipGraph.
  *   - one es_ctx per host thread / Python object; a context is not re-entrant.
+ *   - echoseal_amd/_native.py reads its ctypes signatures and every ES_* constant from this file (bind_header): parameters are pointers,
+ *     int, int64_t, uint32_t or double; a `const uint8_t* <name>_host` is passed a bytes object; an ES_* #define is an integer literal
+ *     or `a << b`.  Anything else is refused at import (tests/test_abi_binding.py).
  */
 #ifndef ECHOSEAL_HIP_H
 #define ECHOSEAL_HIP_H
@@ -279,7 +282,9 @@ int es_schedule_batch(es_ctx* ctx, const uint8_t* aes_key16_host, const uint8_t*
  * state; if max|chips| + 1e-12 > 3 the frame is scaled by its reciprocal; float32 out.
  * code_dev [B][1024] {0,1} (es_polar_encode_batch), pn_rows_dev [B][152] and band_dev [B] (es_schedule_batch or the
  * broadcast schedule), ctr_dev [B] uint32; preamble8_host = np.packbits(mseq_63()) (8 bytes, last bit unused),
- * hdr_pn16_host = np.packbits(pn_bits(0, 128)); y_ws_dev = float64 workspace [B][1215]; frames_dev float32 [B][1215]. */
+ * hdr_pn16_host = np.packbits(pn_bits(0, 128)); y_ws_dev = float64 workspace [B][1215]; frames_dev float32 [B][1215].
+ * Both host arrays are read during the call and travel by value as kernel arguments: the call only enqueues and can be captured into a
+ * graph, and calls under different keys on different streams share nothing. */
 int es_tx_frames_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
                        const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* hdr_pn16_host, int64_t B,
                        double* y_ws_dev, float* frames_dev, void* stream);
@@ -556,8 +561,8 @@ int es_aead_seal_keyed_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, co
  * pn_bits(0, 128) of the frame's key) is the 16 bytes at offset 272 of ring row key_dev[f]; pn_rows_dev and band_dev come from
  * es_schedule_keyed_batch over the same (key, counter) records.  Band-pass and peak rule are those of es_tx_frames_batch.  key_dev [B]
  * int32; a key index outside [0, N) gives a header PN of zero bytes and reads nothing of the ring; N == 0 with B > 0 is ES_EINVAL.
- * Unlike es_tx_frames_batch it copies nothing from host memory (preamble8_host is read during the call and travels by value):
- * it only enqueues and can be captured into a graph.                                                                              */
+ * Like es_tx_frames_batch it only enqueues and can be captured into a graph (preamble8_host is read during the call and travels by
+ * value).                                                                                                                          */
 int es_tx_frames_keyed_batch(es_ctx* ctx, const uint8_t* code_dev, const uint8_t* pn_rows_dev, const uint8_t* band_dev,
                              const uint32_t* ctr_dev, const uint8_t* preamble8_host, const uint8_t* ring_dev, int64_t N,
                              const int32_t* key_dev, int64_t B, double* y_ws_dev, float* frames_dev, void* stream);
@@ -637,6 +642,7 @@ int es_stream_commit_batch(es_ctx* ctx, int64_t R, int64_t n_stride, const int64
  * first moved down to [0, col) -- the host does this when a chunk would not fit -- and base[r] is the base after that move.  pos is set to
  * (base + col + len, base).  Rows of streams the records do not name are not touched. */
 #define ES_MONITOR_REC_WORDS 5
+#define ES_XC_SEG 1216   /* lags per segment of the correlation kernel (64 lanes x 19): a monitor's window grid */
 int es_bpf_stream_batch(es_ctx* ctx, const void* x_dev, int dtype, int64_t R, int64_t n_stride, const int64_t* sid_dev, const int64_t* len_dev,
                         const int64_t* col_dev, const int64_t* move_dev, const int64_t* base_dev, const int64_t* rec_host, int64_t S, int H,
                         const uint8_t* band_dev, double* z_dev, int64_t* pos_dev, double* y_hist_dev, double* corr_hist_dev, void* stream);

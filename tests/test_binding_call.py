@@ -87,16 +87,14 @@ def test_success_does_not_ask_for_an_error(monkeypatch):
 
 def test_header_stream_last_exactly_for_batch_names():
     """The rule _call rests on: a declaration ends in `void* stream` if and only if its name ends in `_batch`; SIGNATURES agrees."""
-    hdr = open(os.path.join(ROOT, "include", "echoseal_hip.h")).read()
-    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
-    decl = {name: [p.strip() for p in params.split(",")] for name, params in re.findall(r"\b(es_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)}
+    decl = nat.DECLARATIONS
     assert set(decl) == set(nat.SIGNATURES) and len(decl) == 56, set(decl) ^ set(nat.SIGNATURES)
     for name, params in decl.items():
-        takes = re.fullmatch(r"void\s*\*\s*stream", params[-1]) is not None
-        assert takes == name.endswith("_batch"), (name, params[-1])
-        assert not any(re.search(r"\bstream$", p) for p in params[:-1]), name
+        takes = bool(params) and params[-1] == ("void*", "stream")
+        assert takes == name.endswith("_batch"), (name, params[-1:])
+        assert not any(p == "stream" for _, p in params[:-1]), name
         argtypes = nat.SIGNATURES[name][1]
-        assert len(argtypes) == (0 if params == ["void"] else len(params)), name
+        assert len(argtypes) == len(params), name
         if takes:
             assert argtypes[-1] is nat.c_void_p and argtypes[0] is nat.c_void_p, name
 

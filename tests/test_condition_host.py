@@ -24,15 +24,13 @@ LENGTHS = [1, 2, 3, 20, 21, 22, 63, 64, 200]
 def test_entry_points_declared_bound_and_exported():
     import echoseal_amd._native as nat
     text = open(HEADER).read()
-    assert re.search(r"#define\s+ES_ABI_VERSION\s+2\b", text) and nat.ES_ABI_VERSION == 2        # additive: the version stays
+    assert nat.CONSTANTS["ES_ABI_VERSION"] == nat.ES_ABI_VERSION == 2                             # additive: the version stays
     assert os.path.exists(LIB), "build the HIP library first (__graft_entry__.build())"
     lib = ctypes.CDLL(LIB)
     nm = _tool("llvm-nm") or _tool("nm")
     syms = set(subprocess.run([nm, "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout.split()) if nm else None
     for name, nargs in ENTRY_POINTS.items():
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-        assert decl, name
-        assert len([a for a in decl.group(1).split(",") if a.strip()]) == nargs, name
+        assert len(nat.DECLARATIONS[name]) == nargs, name
         res, args = nat.SIGNATURES[name]
         assert res is ctypes.c_int and len(args) == nargs, name
         assert hasattr(lib, name), name
@@ -43,8 +41,7 @@ def test_entry_points_declared_bound_and_exported():
     assert args[2] is ctypes.c_int and args[8] is ctypes.c_int and all(args[k] is ctypes.c_int64 for k in (3, 5, 7, 10, 11))
     # descriptor width and tile length: header, binder and engine agree
     from echoseal_amd import engine as E
-    words = int(re.search(r"#define\s+ES_RESAMPLE_DESC_WORDS\s+(\d+)", text).group(1))
-    tile = int(re.search(r"#define\s+ES_RESAMPLE_TILE\s+(\d+)", text).group(1))
+    words, tile = nat.CONSTANTS["ES_RESAMPLE_DESC_WORDS"], nat.CONSTANTS["ES_RESAMPLE_TILE"]
     assert words == nat.ES_RESAMPLE_DESC_WORDS == 8 and tile == nat.ES_RESAMPLE_TILE == E.RESAMPLE_TILE
     assert callable(E.RxEngine.resample_ragged)
 
@@ -171,11 +168,9 @@ def test_kernel_constants_equal_header_binder_and_the_tests_mirror():
     import echoseal_amd._native as nat
     import resample_arms as A
     kernel = open(os.path.join(ROOT, "echoseal_amd", "csrc", "es_resample.hip")).read()
-    header = open(HEADER).read()
     value = lambda s: eval(s, {"__builtins__": {}})                          # "4352", "1 << 20"
     k = {n: value(re.search(r"constexpr\s+int\s+RS_" + n + r"\s*=\s*([0-9<\s]+);", kernel).group(1)) for n in ("WIN_MAX", "FILT_MAX", "RATE_MAX")}
-    h = {n: value(re.search(r"#define\s+ES_RESAMPLE_" + n + r"\s+\(?([0-9<\s]+?)\)?\s*\n", header).group(1))
-         for n in ("WIN_MAX", "FILT_MAX", "RATE_MAX", "TABLE_MAX", "TILE")}
+    h = {n: nat.CONSTANTS["ES_RESAMPLE_" + n] for n in ("WIN_MAX", "FILT_MAX", "RATE_MAX", "TABLE_MAX", "TILE")}
     assert k == {"WIN_MAX": A.WIN_MAX, "FILT_MAX": A.FILT_MAX, "RATE_MAX": A.RATE_MAX} == {n: h[n] for n in k} == {"WIN_MAX": 4352, "FILT_MAX": 3584, "RATE_MAX": 1 << 20}
     assert (nat.ES_RESAMPLE_WIN_MAX, nat.ES_RESAMPLE_FILT_MAX, nat.ES_RESAMPLE_RATE_MAX, nat.ES_RESAMPLE_TABLE_MAX) == (h["WIN_MAX"], h["FILT_MAX"], h["RATE_MAX"], h["TABLE_MAX"])
     assert h["TILE"] == A.TILE == nat.ES_RESAMPLE_TILE and re.search(r"constexpr\s+int\s+RS_TILE\s*=\s*ES_RESAMPLE_TILE\s*;", kernel)

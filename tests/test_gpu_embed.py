@@ -268,3 +268,93 @@ def test_front_end_context_and_graph_capture(engine):
         torch.cuda.synchronize()
         assert torch.equal(out, ref), block
     front.close()
+
+
+# ------------------------------------------------------------------ the frame generator only enqueues
+KEY_A, KEY_B = bytes(range(32)), bytes(range(100, 132))
+
+
+def frame_inputs(engine, seed):
+    """Four frames' device inputs: counters around a low-16 wrap, sealed-payload bytes (any 55 bytes make a frame)."""
+    rng = np.random.default_rng(seed)
+    ctr = torch.tensor([65534, 65535, 65536, 7], dtype=torch.int64, device=engine.device)
+    return ctr, dev(engine, rng.integers(0, 256, (4, 55), dtype=np.uint8))
+
+
+def test_make_frames_of_two_keys_on_two_streams_do_not_share_a_header_pn(engine):
+    """The header PN travels by value with each launch: key A's frames on a stream that is still busy and key B's on another, with no
+    host synchronisation in between, are each what the same call gives alone."""
+    from echoseal_amd.crypto import SecureChannel
+    from echoseal_amd.engine import RxEngine
+    front = RxEngine(engine.device, list_size_max=0)
+    sec_a, sec_b = SecureChannel(KEY_A), SecureChannel(KEY_B)
+    (ctr_a, pay_a), (ctr_b, pay_b) = frame_inputs(engine, 1), frame_inputs(engine, 2)
+    alone_a = front.make_frames(sec_a, KEY_A, ctr_a, pay_a)
+    alone_b = front.make_frames(sec_b, KEY_B, ctr_b, pay_b)
+    busy = torch.zeros(1 << 26, dtype=torch.float32, device=engine.device)
+    torch.cuda.synchronize()
+    assert not torch.equal(alone_a[:, 63:191], alone_b[:, 63:191])          # the two header PNs differ, so a mix-up would show
+    s1, s2 = torch.cuda.Stream(engine.device), torch.cuda.Stream(engine.device)
+    with torch.cuda.stream(s1):
+        for _ in range(32):                                                 # a few milliseconds of other work in front of key A's launches
+            busy.add_(1.0)
+        got_a = front.make_frames(sec_a, KEY_A, ctr_a, pay_a)
+    with torch.cuda.stream(s2):
+        got_b = front.make_frames(sec_b, KEY_B, ctr_b, pay_b)
+    torch.cuda.synchronize()
+    assert torch.equal(got_a, alone_a) and torch.equal(got_b, alone_b)
+    assert bool((busy == 32.0).all())
+    front.close()
+
+
+def graph_chain(graph):
+    """-> (node types in no particular order, is the graph one chain: every node but one root has exactly one predecessor, every node
+    but one leaf exactly one successor).  Asked of the HIP runtime the library is linked to."""
+    import ctypes
+    import echoseal_amd._native as nat
+    hip, g, n = nat.load(), ctypes.c_void_p(graph.raw_cuda_graph()), ctypes.c_size_t(0)
+    assert hip.hipGraphGetNodes(g, None, ctypes.byref(n)) == 0
+    nodes = (ctypes.c_void_p * n.value)()
+    assert hip.hipGraphGetNodes(g, nodes, ctypes.byref(n)) == 0
+    ne = ctypes.c_size_t(0)
+    assert hip.hipGraphGetEdges(g, None, None, ctypes.byref(ne)) == 0
+    src, dst = (ctypes.c_void_p * ne.value)(), (ctypes.c_void_p * ne.value)()
+    assert hip.hipGraphGetEdges(g, src, dst, ctypes.byref(ne)) == 0
+    types = []
+    for node in nodes:
+        t = ctypes.c_int(-1)
+        assert hip.hipGraphNodeGetType(ctypes.c_void_p(node), ctypes.byref(t)) == 0
+        types.append(t.value)
+    chain = ne.value == n.value - 1 and len(set(src)) == ne.value and len(set(dst)) == ne.value
+    return types, chain
+
+
+def test_a_fresh_context_captures_its_first_schedule_and_frames_as_one_chain(engine):
+    """Everything a context owns is made by es_create: the first es_schedule_keyed_batch of a context, es_schedule_batch and
+    es_tx_frames_batch record into a stream capture as kernel launches on the capture stream alone, and the replays give the eager bits."""
+    from echoseal_amd.crypto import SecureChannel
+    from echoseal_amd.engine import RxEngine
+    sec = SecureChannel(KEY_A)
+    ring = engine.keyring([KEY_A, KEY_B])                                   # derived by another context: the fresh one below has run nothing
+    key_idx = torch.tensor([0, 1, 1, 0], dtype=torch.int32, device=engine.device)
+    ctr, pay = frame_inputs(engine, 3)
+    want_pn, want_band = engine.schedule_keyed(ring, key_idx, ctr)
+    want = engine.make_frames(sec, KEY_A, ctr, pay)
+    torch.cuda.synchronize()
+    front = RxEngine(engine.device, list_size_max=0)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph(keep_graph=True)
+    with torch.cuda.graph(graph):
+        pn, band = front.schedule_keyed(ring, key_idx, ctr)
+        frames = front.make_frames(sec, KEY_A, ctr, pay)
+    types, chain = graph_chain(graph)
+    assert len(types) >= 5 and set(types) == {0}, types                     # hipGraphNodeTypeKernel: no copy from host memory, no host node
+    assert chain, "the capture forked: a side stream or an unordered node"
+    for _ in range(2):
+        for t in (pn, band, frames):
+            t.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(pn, want_pn) and torch.equal(band, want_band) and torch.equal(frames, want)
+    del graph
+    front.close()

@@ -2,7 +2,6 @@
 every refusal of WatermarkIdentifier.open_streams / LiveIdentifier.push -- none of which may need an engine."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,23 +11,16 @@ HEADER = os.path.join(ROOT, "include", "echoseal_hip.h")
 KEYS = [bytes([k]) * 32 for k in (1, 2, 3)]
 
 
-def _decl_args(text, name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, name
-    return [a.strip() for a in m.group(1).split(",") if a.strip()]
-
-
 def test_header_declares_and_native_binds_the_memo_entry_points():
     import echoseal_amd._native as nat
-    text = open(HEADER).read()
-    assert re.search(r"#define\s+ES_ABI_VERSION\s+2\b", text) and nat.ES_ABI_VERSION == 2
-    assert int(re.search(r"#define\s+ES_MEMO_EMPTY\s+(0x[0-9A-Fa-f]+)", text).group(1), 16) == nat.ES_MEMO_EMPTY == 2 ** 64 - 1
+    assert nat.CONSTANTS["ES_ABI_VERSION"] == nat.ES_ABI_VERSION == 2
+    assert nat.CONSTANTS["ES_MEMO_EMPTY"] == nat.ES_MEMO_EMPTY == 2 ** 64 - 1
     for name, n in (("es_memo_probe_batch", 8), ("es_memo_insert_batch", 8)):
         res, args = nat.SIGNATURES[name]
-        decl = _decl_args(text, name)
+        decl = nat.DECLARATIONS[name]
         assert res is ctypes.c_int and len(args) == n == len(decl), name
-        for a, d in zip(args, decl):                                        # the two int64 (slots, n) sit where the header puts them
-            assert (a is ctypes.c_int64) == d.startswith("int64_t"), (name, d)
+        for a, (ctype, _) in zip(args, decl):                               # the two int64 (slots, n) sit where the header puts them
+            assert (a is ctypes.c_int64) == (ctype == "int64_t"), (name, ctype)
     lib = ctypes.CDLL(nat.LIB_PATH)                                          # loads without a GPU
     assert hasattr(lib, "es_memo_probe_batch") and hasattr(lib, "es_memo_insert_batch")
     assert lib.es_abi_version() == 2

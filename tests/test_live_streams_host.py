@@ -3,7 +3,6 @@ WatermarkEmbedder.process (rtwm/embedder.py:44-62: make a frame whenever the chi
 boundary (header, binder, exported symbol)."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -136,16 +135,14 @@ def test_shared_host_steps_of_the_embeds(monkeypatch):
 def test_entry_points_declared_bound_and_exported():
     import echoseal_amd._native as nat
     text = open(HEADER).read()
-    assert re.search(r"#define\s+ES_ABI_VERSION\s+2\b", text) and nat.ES_ABI_VERSION == 2        # additive: the version stays
-    assert re.search(r"#define\s+ES_STREAM_REC_WORDS\s+5\b", text) and nat.ES_STREAM_REC_WORDS == 5
+    assert nat.CONSTANTS["ES_ABI_VERSION"] == nat.ES_ABI_VERSION == 2                             # additive: the version stays
+    assert nat.CONSTANTS["ES_STREAM_REC_WORDS"] == nat.ES_STREAM_REC_WORDS == 5
     assert os.path.exists(LIB), "build the HIP library first (__graft_entry__.build())"
     lib = ctypes.CDLL(LIB)
     nm = _tool("llvm-nm") or _tool("nm")
     syms = set(subprocess.run([nm, "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout.split()) if nm else None
     for name, nargs in ENTRY_POINTS.items():
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-        assert decl, name
-        assert len([a for a in decl.group(1).split(",") if a.strip()]) == nargs, name
+        assert len(nat.DECLARATIONS[name]) == nargs, name
         res, args = nat.SIGNATURES[name]
         assert res is ctypes.c_int and len(args) == nargs, name
         assert hasattr(lib, name), name

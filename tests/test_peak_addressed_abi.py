@@ -26,25 +26,18 @@ EXISTING = {
 FIELDS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
-def _decl_args(text, name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip()])
-
-
 def test_header_declares_the_new_functions_under_abi_2():
-    text = open(HEADER).read()
-    assert re.search(r"#define\s+ES_ABI_VERSION\s+2\b", text)
+    import echoseal_amd._native as nat
+    assert os.path.samefile(nat.HEADER_PATH, HEADER) and nat.CONSTANTS["ES_ABI_VERSION"] == 2
     for name, n in NEW.items():
-        assert _decl_args(text, name) == n, name
+        assert len(nat.DECLARATIONS[name]) == n, name
 
 
 def test_native_binds_the_new_functions():
     import echoseal_amd._native as nat
-    text = open(HEADER).read()
     for name, n in NEW.items():
         res, args = nat.SIGNATURES[name]
-        assert res is ctypes.c_int and len(args) == n == _decl_args(text, name), name
+        assert res is ctypes.c_int and len(args) == n == len(nat.DECLARATIONS[name]), name
     assert nat.ES_ABI_VERSION == 2
 
 
