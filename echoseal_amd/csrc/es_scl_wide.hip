@@ -688,6 +688,48 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                     auto g1 = [&](float lo, float hi, uint32_t u) { return es_polar_g((double)lo, (double)hi, u); };      // depth-1 element from llr[e], llr[e + 512]
                     if (i == 512) {
                         auto ld = [&](int j, float (&q)[4]) { q[0] = llr32[j]; q[1] = llr32[j + 512]; q[2] = llr32[j + 256]; q[3] = llr32[j + 768]; };
+                        if constexpr (WAVE && LF >= 8) {
+                        // The channel LLRs belong to the frame and the two signs are one bit each: element j of depth 2 takes one of FOUR values,
+                        // whatever the path.  The frame's LF lanes evaluate them once between them: in a round of LF / 4 elements lane pl evaluates
+                        // element pl >> 2 for sign combination pl & 3 (both bits lane constants: no bit extraction in the evaluation), and every path
+                        // then takes each element of the round from the lane that holds its combination (ds_bpermute, registers only: nothing is
+                        // stored but the results, and no fence is needed).  1024 / LF evaluations a lane instead of 256: 128 at L = 8, 16 at L = 64.
+                        // Same g1 and f on the same operands, so the same bits: only the lane that evaluates them differs.  All 64 lanes are active
+                        // here (dead paths and mirrored frames decode along), so every source lane of the exchange holds a value.
+                        // (Measured against a 4 x 256 table in dead rows of the slab with a gather behind a fence: the table gave 0.3-1.3 % on
+                        // the headline step, the exchange 1.7-2.7 %)
+                        {
+                            constexpr int ST = LF / 4;                              // elements per round: lane pl evaluates element pl >> 2 of the round
+                            const int plo = wide_opaque(pl), c = plo & 3;               // my sign combination: bit 0 for (j, j + 512), bit 1 for (j + 256, j + 768)
+                            const uint32_t ua = (uint32_t)c & 1u, ub = (uint32_t)c >> 1;
+                            const int jl = plo >> 2;
+                            const int fb = (p - plo) << 2;                          // ds_bpermute address of the frame's lane 0
+                            // every path takes element j0 + t of a round from the lane of its frame that evaluated combination (t, my two bits)
+                            auto hand_out = [&](double v, int j0, uint32_t ba, uint32_t bb) {
+                                const int lo = (int)(uint32_t)__double_as_longlong(v), hi = (int)(uint32_t)((uint64_t)__double_as_longlong(v) >> 32);
+                                #pragma unroll
+                                for (int t = 0; t < ST; ++t) {
+                                    const int src = fb + (int)((((ba >> t) & 1u) | (((bb >> t) & 1u) << 1) | (uint32_t)(4 * t)) << 2);
+                                    const uint32_t xl = (uint32_t)__builtin_amdgcn_ds_bpermute(src, lo), xh = (uint32_t)__builtin_amdgcn_ds_bpermute(src, hi);
+                                    dst2[(long long)(j0 + t) * L] = __longlong_as_double((long long)(((uint64_t)xh << 32) | xl));
+                                }
+                            };
+                            float q0[4], q1[4];                                     // two operand sets in rotation (renamed, not copied)
+                            ld(jl, q0); ld(jl + ST, q1);
+                            uint32_t wa = 0, wb = 0;                                // my partial-sum bits of elements j .. and j + 256 .., a word per 32 elements
+                            #pragma unroll 1
+                            for (int j = 0; j < 256; j += 2 * ST) {                 // two rounds per pass
+                                if ((j & 31) == 0) { wa = beta_ld((512 + j) >> 5, bs1); wb = beta_ld((512 + j + 256) >> 5, bs1); }
+                                const double v0 = es_polar_f_slg(g1(q0[0], q0[1], ua), g1(q0[2], q0[3], ub), tab);
+                                ld((j + 2 * ST + jl) & 255, q0);                    // (past the end: any element)
+                                hand_out(v0, j, wa, wb);
+                                const double v1 = es_polar_f_slg(g1(q1[0], q1[1], ua), g1(q1[2], q1[3], ub), tab);
+                                ld((j + 3 * ST + jl) & 255, q1);
+                                hand_out(v1, j + ST, wa >> ST, wb >> ST);
+                                wa >>= (2 * ST) & 31; wb >>= (2 * ST) & 31;          // (LF = 64: a pass is a whole word, reloaded above)
+                            }
+                        }
+                        } else {
                         float q[4], qn[4];
                         ld(0, q);
                         #pragma unroll 1
@@ -701,6 +743,7 @@ __global__ __launch_bounds__(L, wide_wps(L)) void es_scl_wide_kernel(WideArgs a)
                                 #pragma unroll
                                 for (int k = 0; k < 4; ++k) q[k] = qn[k];
                             }
+                        }
                         }
                     } else {
                         const int bs2 = p8_get(pb_, 1);                             // slot of my 256-bit block

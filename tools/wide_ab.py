@@ -1,5 +1,5 @@
 """A/B of builds of the one-lane-per-path list decoder: python tools/wide_ab.py NAME [NAME ...]  (libechoseal_hip_NAME.so; '' = the product library).
-Each build runs in its own process: SCL-L on random LLRs (B = 65 536 and 24 576 at L = 8; 8 192 at L = 32; 1 024 at L = 256), best of 3, plus a digest
+Each build runs in its own process: SCL-L on random LLRs (B = 65 536 and 24 576 at L = 8; 8 192 at L = 32; 4 096 at L = 64; 1 024 at L = 256), best of 3, plus a digest
 of the outputs so that builds can be checked to agree bit for bit (the digest of the product build is the reference)."""
 import hashlib, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +18,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     base = torch.from_numpy(x).to(eng.device)
     base[::7] = torch.round(base[::7])                                   # some tie-heavy rows
     eng.set_option("scl_multi", 1); eng.set_option("scl_lanes", 1)
-    for L, B in ((8, 65536), (8, 24576), (32, 8192), (256, 1024)):
+    for L, B in ((8, 65536), (8, 24576), (32, 8192), (64, 4096), (256, 1024)):
         llr = base.repeat(-(-B // 4096), 1)[:B].contiguous()
         r = eng.scl(llr, list_size=L, skip_if_hard_ok=False); torch.cuda.synchronize()
         best = 1e9
