@@ -92,6 +92,18 @@ except OSError as e:
     raise NativeError(f"{HEADER_PATH}: the C ABI's header is what this module binds from ({e})") from None
 globals().update(CONSTANTS)              # ES_ABI_VERSION (load() refuses a library built from another one), ES_FRAME_LEN, ES_DTYPE_F32 ...
 
+# The companion header of the presence test, bound by the same rule into tables of its own: the three above stay the statement
+# of include/echoseal_hip.h alone.  load() sets these argtypes too, and RxEngine._call finds the names on the library like any other.
+PRESENCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_presence.h")
+try:
+    with open(PRESENCE_HEADER_PATH) as _f:
+        PRESENCE_DECLARATIONS, PRESENCE_SIGNATURES, PRESENCE_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{PRESENCE_HEADER_PATH}: the presence calls are bound from this header ({e})") from None
+if set(PRESENCE_SIGNATURES) & set(SIGNATURES) or set(PRESENCE_CONSTANTS) & set(CONSTANTS):
+    raise NativeError(f"{PRESENCE_HEADER_PATH} declares a name include/echoseal_hip.h already has")
+globals().update(PRESENCE_CONSTANTS)     # ES_HOP_TILE, ES_HOP_ORIGINS
+
 _lib = None
 
 
@@ -113,7 +125,7 @@ def load() -> ctypes.CDLL:
     if got != CONSTANTS["ES_ABI_VERSION"]:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

@@ -1049,6 +1049,48 @@ int es_hop_window_batch(es_ctx* ctx, const uint8_t* ring_dev, int64_t N, const u
     return es_launch_hop_window(ctx, ring_dev, N, hop_base_dev, HR, C, hop_dev, (hipStream_t)stream);
 }
 
+// ---- presence (include/echoseal_presence.h) ----
+// what both presence calls refuse of the correlation rows
+static const char* presence_rows(int64_t rows, int64_t stride, int64_t B)
+{
+    return (rows < 0 || stride < 0 || B < 0) ? ": negative count"
+           : stride > 0x7FFFFFFFll ? ": stride above 2^31 - 1"
+           : (B > ((int64_t)1 << 40) || rows / 4 < B) ? ": rows < 4 B" : nullptr;
+}
+
+int es_phase_fold_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64_t stride, const int32_t* nlag_dev, int64_t B,
+                        double* fold_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_rows(rows, stride, B)) return fail(ctx, ES_EINVAL, (std::string("es_phase_fold_batch") + why).c_str());
+    if (B == 0) return ES_OK;
+    if (B > 0x7FFFFFFFll / 5) return fail(ctx, ES_EINVAL, "es_phase_fold_batch: more than 2^31 - 1 blocks of five per clip in one call");
+    if (!nlag_dev || !fold_dev || (!corr_dev && stride >= ES_FRAME_LEN)) return fail(ctx, ES_EINVAL, "es_phase_fold_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_phase_fold(ctx, corr_dev, stride, nlag_dev, B, fold_dev, (hipStream_t)stream);
+}
+
+int es_hop_score_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64_t stride, const int32_t* nlag_dev, int64_t B,
+                       const int32_t* phase_dev, int P, const uint8_t* hop_dev, int64_t K, int64_t Ccols, int64_t n_origins,
+                       double* score_dev, int64_t* origin_dev, int32_t* rank_dev, void* scratch_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_rows(rows, stride, B)) return fail(ctx, ES_EINVAL, (std::string("es_hop_score_batch") + why).c_str());
+    if (K < 0 || Ccols < 0 || n_origins < 0) return fail(ctx, ES_EINVAL, "es_hop_score_batch: negative count");
+    if (P < 1 || P > ES_FRAME_LEN) return fail(ctx, ES_EINVAL, "es_hop_score_batch: P must be in 1 .. 1215");
+    const int64_t Jmax = stride / ES_FRAME_LEN, NB = n_origins / ES_HOP_ORIGINS + (n_origins % ES_HOP_ORIGINS != 0);
+    if (Ccols < n_origins + Jmax - 1) return fail(ctx, ES_EINVAL, "es_hop_score_batch: Ccols < n_origins + Jmax - 1 (Jmax = stride / 1215)");
+    if (B == 0 || K == 0) return ES_OK;
+    if (K > 0x7FFFFFFFll / B || (NB > 0 && B * K > 0x7FFFFFFFll / NB))
+        return fail(ctx, ES_EINVAL, "es_hop_score_batch: more than 2^31 - 1 blocks of (clip, key, 256 origins) in one call");
+    const bool scored = NB > 0 && Jmax > 0;                                 // otherwise no block reads rows, phases or hop bytes
+    if (!nlag_dev || !score_dev || !origin_dev || !rank_dev || (NB > 0 && (!scratch_dev || !phase_dev)) || (scored && (!corr_dev || !hop_dev)))
+        return fail(ctx, ES_EINVAL, "es_hop_score_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_hop_score(ctx, corr_dev, stride, nlag_dev, B, phase_dev, P, hop_dev, K, Ccols, n_origins, score_dev, origin_dev, rank_dev,
+                               scratch_dev, (hipStream_t)stream);
+}
+
 // What both acquisition calls refuse and when they have nothing to do: -> ES_EINVAL, ES_OK with *work = false, or ES_OK with *work = true
 // and the exact grid of one wave per (record, tile of 64 high halves) within 2^31 - 1 blocks.
 static int acquire_span(es_ctx* ctx, const char* who, int64_t P, int64_t ctr_lo, int64_t ctr_hi, bool* work)

@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "../../include/echoseal_hip.h"
+#include "../../include/echoseal_presence.h"
 
 /* global memory by its address space: what the integer kernels (es_aead.hip, es_keyring.hip) read and write through */
 typedef __attribute__((address_space(1))) const uint8_t g_cu8;
@@ -281,6 +282,11 @@ int es_launch_acquire_mask(es_ctx* ctx, const uint8_t* ring, int64_t N, const in
                            const uint8_t* band, int64_t P, int64_t ctr_lo, int64_t ctr_hi, uint32_t* mask, int32_t* count, hipStream_t st);
 int es_launch_acquire_list(es_ctx* ctx, const uint32_t* mask, const int32_t* lo16, int64_t P, int64_t ctr_lo, int64_t ctr_hi, const int64_t* base,
                            int64_t total, int32_t* cand_rec, uint32_t* cand_ctr, hipStream_t st);
+/* presence (es_keyring.hip; include/echoseal_presence.h): counts, the hop table's width and both grids are checked by the entry points */
+int es_launch_phase_fold(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, double* fold, hipStream_t st);
+int es_launch_hop_score(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, const int32_t* phase, int P,
+                        const uint8_t* hop, int64_t K, int64_t Ccols, int64_t n_origins, double* score, int64_t* origin, int32_t* rank,
+                        void* scratch, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

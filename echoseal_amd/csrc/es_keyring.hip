@@ -7,7 +7,11 @@
 // Where nobody knows the origin, the low-16 gate of lines 122-127 is taken over a span of the whole counter range instead of an estimate's
 // window (es_acquire_mask_kernel, es_acquire_count_kernel, es_acquire_list_kernel).
 //
-// Integer work throughout.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
+// Last, the presence test, which reads the same hop rows: the keyless fold of a clip's correlation rows over the 1215-sample frame grid and
+// the score of every (key, counter origin, phase) against them (es_phase_fold_kernel, es_hop_score_kernel) -- the only float64
+// work in this file, every sum in one lane from its first slot to its last.
+//
+// Integer work otherwise.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
 // counter window across the lanes, order kept by ballot + count of lower lanes.  Global memory is reached through
 // address_space(1) pointers only.
@@ -368,6 +372,121 @@ __global__ __launch_bounds__(256) void es_acquire_list_kernel(const uint32_t* __
     }
 }
 
+// ---- presence: the preamble peaks of a clip against a key's hop sequence (include/echoseal_presence.h; host twin: echoseal_amd/presence.py) ----
+// Clip b owns rows 4 b .. 4 b + 3 of corr [rows][stride], row 4 b + band the correlation row of BAND_PLAN index `band`, lags [0, nlag[b]);
+// J = nlag / 1215 whole slots.  Every sum is float64, added slot by slot from +0.0 in ascending slot order by ONE lane (no FMA: the unit
+// is built with -ffp-contract=off), so a plain host loop gives the same bits.  No column at or past nlag is read.
+constexpr int HS_TILE = ES_HOP_TILE, HS_ORIGINS = ES_HOP_ORIGINS;
+static_assert(HS_ORIGINS == 256 && HS_TILE * 4 == HS_ORIGINS, "one lane loads one (slot, band) value of a tile");
+
+__device__ __forceinline__ long long clip_nlag(const int32_t* __restrict__ nlag_p, long long b, long long stride)
+{
+    const long long n = ((g_ci32*)nlag_p)[b];
+    return n < 0 ? 0 : (n > stride ? stride : n);
+}
+
+// fold[b][phi] = sum over slots j of the largest of the four band rows at lag phi + 1215 j: one lane per (clip, phase), five blocks per clip
+__global__ __launch_bounds__(256) void es_phase_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        double* __restrict__ fold_p)
+{
+    const long long b = blockIdx.x / 5;
+    const int phi = (int)(blockIdx.x - b * 5) * 256 + (int)threadIdx.x;
+    if (phi >= ES_FRAME_LEN) return;
+    const long long J = clip_nlag(nlag_p, b, stride) / ES_FRAME_LEN;
+    const double* row = corr_p + 4 * b * stride + phi;
+    double acc = 0.0;
+    #pragma unroll 1
+    for (long long j = 0; j < J; ++j) {
+        const double* v = row + j * ES_FRAME_LEN;
+        double m = v[0];
+        #pragma unroll
+        for (int band = 1; band < 4; ++band) {
+            const double c = v[band * stride];
+            m = c > m ? c : m;
+        }
+        acc = acc + m;
+    }
+    fold_p[b * ES_FRAME_LEN + phi] = acc;
+}
+
+// what a lane, a block or a (clip, key) pair has found so far: `a` is replaced by `b` where b is scored and a is not, or b's score is
+// larger, or equal at a lower origin (an origin is owned by one lane, which keeps its earliest list entry itself)
+struct hs_best { double score; long long origin; int rank; };
+__device__ __forceinline__ bool hs_better(const hs_best& b, const hs_best& a)
+{
+    return b.origin >= 0 && (a.origin < 0 || b.score > a.score || (b.score == a.score && b.origin < a.origin));
+}
+
+// One block per (clip b, key k, chunk of 256 origins), one lane per origin.  Per list entry the [J][4] values of its phase pass through
+// LDS in tiles of HS_TILE slots; the lane adds vals[j][hop[k][origin + j]] slot by slot, so neighbouring lanes read neighbouring hop bytes.
+// An origin whose window holds a byte above 3 (0xFF: a counter that does not exist) is not scored.  The block's best goes to slot
+// (b K + k) NB + chunk of the scratch arrays.
+__global__ __launch_bounds__(256) void es_hop_score_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        const int32_t* __restrict__ phase_p, int P, const uint8_t* __restrict__ hop_p, long long K, long long Ccols, long long n_origins,
+        long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    __shared__ double vals[HS_TILE * 4];
+    __shared__ hs_best red[HS_ORIGINS];
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * HS_ORIGINS + tid;
+    const bool live = origin < n_origins;
+    const long long J = clip_nlag(nlag_p, b, stride) / ES_FRAME_LEN;
+    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + (live ? origin : 0);                         // columns origin .. origin + J - 1 < Ccols (the entry point's check)
+    const double* rows = corr_p + 4 * b * stride;
+    hs_best best = {-__builtin_inf(), -1, -1};
+    #pragma unroll 1
+    for (int p = 0; p < P; ++p) {
+        const int phi = ((g_ci32*)phase_p)[b * P + p];
+        if (phi < 0 || phi >= ES_FRAME_LEN || J == 0) continue;                           // (block-uniform) an entry that is no phase is not scored
+        double acc = 0.0;
+        bool ok = live;
+        #pragma unroll 1
+        for (long long j0 = 0; j0 < J; j0 += HS_TILE) {
+            const int nt = (int)(J - j0 < HS_TILE ? J - j0 : HS_TILE);
+            __syncthreads();                                                              // the tile before has been read
+            if ((tid >> 2) < nt) vals[tid] = rows[(tid & 3) * stride + phi + (j0 + (tid >> 2)) * ES_FRAME_LEN];
+            __syncthreads();
+            if (live) {
+                #pragma unroll 1
+                for (int j = 0; j < nt; ++j) {
+                    const unsigned h = hop[j0 + j];
+                    ok = ok && h < 4u;
+                    acc = acc + vals[4 * j + (int)(h & 3u)];
+                }
+            }
+        }
+        const double s = acc / (double)J;
+        if (ok && (best.origin < 0 || s > best.score)) { best.score = s; best.origin = origin; best.rank = p; }
+    }
+    red[tid] = best;
+    __syncthreads();
+    #pragma unroll 1
+    for (int w = HS_ORIGINS / 2; w > 0; w >>= 1) {                                         // a maximum under a total order: any shape gives the same winner
+        if (tid < w && hs_better(red[tid + w], red[tid])) red[tid] = red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sc_score[blockIdx.x] = red[0].score; sc_origin[blockIdx.x] = red[0].origin; sc_rank[blockIdx.x] = red[0].rank;
+    }
+}
+
+// the best of the NB chunks of each (clip, key), chunks ascending (ties keep the lower origin): one lane per pair
+__global__ __launch_bounds__(256) void es_hop_best_kernel(const double* __restrict__ sc_score, const long long* __restrict__ sc_origin,
+        const long long* __restrict__ sc_rank, long long pairs, long long NB, double* __restrict__ score_p, long long* __restrict__ origin_p,
+        int32_t* __restrict__ rank_p)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pairs) return;
+    hs_best best = {-__builtin_inf(), -1, -1};
+    #pragma unroll 1
+    for (long long c = 0; c < NB; ++c) {
+        const hs_best cand = {sc_score[i * NB + c], sc_origin[i * NB + c], (int)sc_rank[i * NB + c]};
+        if (hs_better(cand, best)) best = cand;
+    }
+    score_p[i] = best.score; origin_p[i] = best.origin; rank_p[i] = best.rank;
+}
+
 }  // namespace
 
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
@@ -436,4 +555,25 @@ int es_launch_acquire_list(es_ctx* ctx, const uint32_t* mask, const int32_t* lo1
     const long long h0 = ctr_lo >> 16, H = ((ctr_hi + 65535) >> 16) - h0, W = (H + 31) / 32, TW = (W + 1) / 2;
     return es_launch(ctx, es_acquire_list_kernel, (unsigned)((P * TW + 3) / 4), 256, 0, st, mask, lo16, (long long)P, h0, (int)W, (int)TW,
                      (const long long*)base, (long long)total, cand_rec, cand_ctr);
+}
+
+// the exact grids of the presence kernels: the entry points refuse a call whose grid would pass 2^31 - 1 blocks
+int es_launch_phase_fold(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, double* fold, hipStream_t st)
+{
+    return es_launch(ctx, es_phase_fold_kernel, (unsigned)(B * 5), 256, 0, st, corr, (long long)stride, nlag, fold);
+}
+
+int es_launch_hop_score(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, const int32_t* phase, int P,
+                        const uint8_t* hop, int64_t K, int64_t Ccols, int64_t n_origins, double* score, int64_t* origin, int32_t* rank,
+                        void* scratch, hipStream_t st)
+{
+    const long long NB = (n_origins + ES_HOP_ORIGINS - 1) / ES_HOP_ORIGINS, pairs = (long long)B * K, slots = pairs * NB;
+    double* sc_score = (double*)scratch;
+    long long* sc_origin = (long long*)scratch + slots;
+    long long* sc_rank = (long long*)scratch + 2 * slots;
+    if (slots > 0)
+        if (const int rc = es_launch(ctx, es_hop_score_kernel, (unsigned)slots, 256, 0, st, corr, (long long)stride, nlag, phase, P, hop, (long long)K,
+                                     (long long)Ccols, (long long)n_origins, NB, sc_score, sc_origin, sc_rank)) return rc;
+    return es_launch(ctx, es_hop_best_kernel, (unsigned)((pairs + 255) / 256), 256, 0, st, (const double*)sc_score, (const long long*)sc_origin,
+                     (const long long*)sc_rank, pairs, NB, score, (long long*)origin, rank);
 }

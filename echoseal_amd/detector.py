@@ -111,6 +111,8 @@ class WatermarkDetector:
             raise RuntimeError(f"Header PN length {self._hdr_pn_sy.size} != expected {HDR_L}")
         self._engine = engine
         self._ring = None                                   # (engine, one-row key ring of this detector's key): acquire
+        self._decoy_ring = None                             # (engine, decoys, ring of this key and that many decoy keys): presence
+        self._presence_rows: list | None = None             # set to [] to record (clip indices, correlation rows, lags) of every presence launch
         self._trace: list[tuple[int, int, int]] | None = None   # set to [] to record (band_lo, peak, ctr) tries
         self._hdr_trace: list[tuple[float, float, float]] | None = None   # set to [] to record every header decode of a scan
 
@@ -299,6 +301,69 @@ class WatermarkDetector:
                         plain = self._decrypt_blob_fallback(blob)[0] or blob
                     return Acquired(origin_of(ctr, start, pos0), ctr, start, (int(band[0]), int(band[1])), blob, plain, len(recs), tried)
         return None
+
+    # ------------------------------------------------------------------ presence
+    def presence(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = 8, decoys: int = 32):
+        return self.presence_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys)[0]
+
+    def presence_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32) -> list:
+        """Tell whether each clip carries this key's mark, without demodulating anything: -> per clip a presence.Presence, or None for a
+        clip without one whole 1215-sample slot.  The 63-chip preamble of every frame survives the channel where the payload does not
+        (DESIGN 4.23), and it peaks in the band the HMAC-keyed hop sequence names: the score of a key is the mean, over the clip's
+        frame slots on one 1215-sample grid, of the correlation rows the key hops through from some counter of `span`, maximised over
+        the span and over the `phases` grid phases of largest keyless fold.  The same search runs under `decoys` public decoy keys
+        (presence.decoy_keys); detected = the own score is strictly above every decoy's.  No threshold is tuned anywhere; the verdict
+        is statistical, not authenticated.  ctr0 = c (one value, or one per clip with None entries allowed) is shorthand for
+        span = (c, c + 2).  phases = 1215 searches every phase.
+        The front is verify_batch's (cut_launches, four rows per clip in BAND_PLAN order, mixed rates, int16 and unequal lengths
+        included) with the correlation rows kept; per launch ONE fold, ONE hop window over the ring [key] + decoys and ONE score call.
+        session_nonce and the traces are not touched.  ValueError before any engine exists: a span outside [0, 2^32], reversed or
+        reaching past 2^32 from its last origin, phases outside 1 .. 1215, decoys < 0, a bad ctr0."""
+        from . import presence as pr
+        import torch
+        fs_list = rate_list(fs_in, len(clips))
+        P, R = pr.check_phases(phases), pr.check_decoys(decoys)
+        spans = pr.clip_spans(ctr0, span, len(clips))
+        for c, f, s in zip(clips, fs_list, spans):                          # refused by name before any engine exists
+            pr.check_reach(s, resampled_length(int(np.size(c)), int(f), self.fs_target))
+        out: list = [None] * len(clips)
+        band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
+        nb = band_ids.size
+        for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
+            ids = [i for i, s in enumerate(spans) if s == (lo, hi)]
+            for la in cut_launches([clips[i] for i in ids], [fs_list[i] for i in ids], self.fs_target, nb, self._conditioned):
+                eng = self.engine
+                x, sizes = la.rows(eng, nb)
+                bid = dev(eng, np.tile(band_ids, len(sizes)), np.uint8)
+                M = max(sizes)
+                if min(sizes) < M:
+                    corr = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=True).corr
+                else:
+                    corr = eng.xcorr(eng.bpf(x[:, :M], bid), bid)
+                nlag = np.array(sizes, np.int64) - (PRE_L - 1)
+                J = nlag // FRAME_LEN
+                if not J.max():
+                    continue
+                fold = eng.phase_fold(corr, nlag).cpu().numpy()
+                plists = [pr.pick_phases(f, P) for f in fold]
+                ring = self._presence_ring(R)
+                jmax = corr.shape[1] // FRAME_LEN                            # the slots the score call sizes the hop table for
+                hop = eng.hop_window(ring, [min(lo, CTR_END - 1)], max(hi - lo + jmax - 1, 0))
+                score, origin, rank = (t.cpu().numpy() for t in eng.hop_score(corr, nlag, np.array(plists, np.int32), hop, hi - lo))
+                if self._presence_rows is not None:
+                    self._presence_rows.append(([ids[i] for i in la.idx], corr.cpu().numpy(), nlag))
+                for k, i in enumerate(la.idx):
+                    if J[k]:
+                        out[ids[i]] = pr.verdict(score[k], origin[k], rank[k], lo, plists[k], int(J[k]))
+        return out
+
+    def _presence_ring(self, decoys: int):
+        """The ring [this detector's key] + the first `decoys` public decoy keys, derived once per engine and count."""
+        from .presence import decoy_keys
+        eng = self.engine
+        if self._decoy_ring is None or self._decoy_ring[0] is not eng or self._decoy_ring[1] != decoys:
+            self._decoy_ring = (eng, decoys, eng.keyring([self._band_key] + decoy_keys(decoys)))
+        return self._decoy_ring[2]
 
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
                      ctr0=None) -> "LiveMonitor":

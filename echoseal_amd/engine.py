@@ -627,6 +627,51 @@ class RxEngine(TxChain, MonitorChain):
         self._call("es_hop_window_batch", ring.ring, ring.n, base, HR, C, hop)
         return hop
 
+    # ------------------------------------------------------------------ presence (include/echoseal_presence.h)
+    def _presence_rows(self, corr: torch.Tensor, nlag):
+        """The correlation rows of a presence call, checked: -> (corr, rows, stride, nlag int32 [B] on the device, B)."""
+        if corr.dim() != 2 or corr.dtype != torch.float64 or not corr.is_contiguous() or corr.device != self.device:
+            raise ValueError("corr must be a contiguous float64 [rows, stride] tensor on the engine's device")
+        nlag = self._dev(nlag, torch.int32).reshape(-1)
+        if 4 * nlag.numel() > corr.shape[0]:
+            raise ValueError("corr: four rows per clip, row 4 * clip + band")
+        return corr, corr.shape[0], corr.shape[1], nlag, nlag.numel()
+
+    def phase_fold(self, corr: torch.Tensor, nlag) -> torch.Tensor:
+        """The keyless fold of a presence test (es_phase_fold_batch; presence.fold_model is the host twin): corr float64 [rows, stride],
+        row 4 * clip + band the correlation row of BAND_PLAN band `band`, nlag [B] the lags of each clip (clamped to [0, stride]; columns
+        past them are never read) -> fold float64 [B, 1215], fold[b, phi] = sum over the clip's whole slots j of the largest of its four
+        rows at lag phi + 1215 j."""
+        corr, rows, stride, nlag, B = self._presence_rows(corr, nlag)
+        fold = torch.empty((B, nat.ES_FRAME_LEN), dtype=torch.float64, device=self.device)
+        self._call("es_phase_fold_batch", corr, rows, stride, nlag, B, fold)
+        return fold
+
+    def hop_score(self, corr: torch.Tensor, nlag, phases, hop: torch.Tensor, n_origins: int):
+        """The keyed score of a presence test (es_hop_score_batch; presence.score_model is the host twin).  corr, nlag as for phase_fold;
+        phases int [B, P], 1 <= P <= 1215: each clip's phase list; hop uint8 [K, Ccols] (or hop_window's [K, 1, Ccols]): column i = the
+        band of counter lo + i under key row k, Ccols >= n_origins + stride // 1215 - 1; origins 0 .. n_origins - 1 are searched
+        -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K]): per (clip, key) the largest mean of the rows the key hops
+        through, the origin (counter - lo) and the list entry it was found at; (-inf, -1, -1) where nothing was scored."""
+        corr, rows, stride, nlag, B = self._presence_rows(corr, nlag)
+        phases = self._dev(phases, torch.int32)
+        if phases.dim() != 2 or phases.shape[0] != B:
+            raise ValueError("phases: int [B, P], one list per clip")
+        if hop.dim() == 3 and hop.shape[1] == 1:
+            hop = hop[:, 0, :]
+        if hop.dim() != 2 or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [K, Ccols]")
+        hop = hop.contiguous()
+        K, n_origins = hop.shape[0], int(n_origins)
+        score = torch.empty((B, K), dtype=torch.float64, device=self.device)
+        origin = torch.empty((B, K), dtype=torch.int64, device=self.device)
+        rank = torch.empty((B, K), dtype=torch.int32, device=self.device)
+        chunks = -(-max(n_origins, 0) // nat.ES_HOP_ORIGINS)
+        scratch = torch.empty(3 * B * K * chunks, dtype=torch.int64, device=self.device)      # the workgroups' bests: 24 bytes each
+        self._call("es_hop_score_batch", corr, rows, stride, nlag, B, phases, phases.shape[1], hop, K, hop.shape[1], n_origins, score, origin, rank,
+                   scratch if scratch.numel() else None)
+        return score, origin, rank
+
     def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):
         """Which counters of `span` each header record may belong to (es_acquire_mask_batch; acquire.mask_model is the host twin).
         Record p = (ring row key_idx[p] int32, ok[p] uint8, lo16[p] int32, band[p] uint8), as one header call gives them

@@ -1,0 +1,189 @@
+"""CPU: the host side of the presence test -- the twin (echoseal_amd/presence.py) against loops written out here, the phase
+pick with planted ties, every argument check, the decoy keys, the companion header's place in the binding, and the twin's verdicts on
+clips A and B rebuilt with the CPU oracle."""
+import hashlib
+import math
+
+import numpy as np
+import pytest
+
+import echoseal_amd._native as nat
+import presence_cases as PC
+from echoseal_amd import presence as pr
+from echoseal_amd.detector import WatermarkDetector
+from echoseal_amd.utils import band_index
+
+
+def _rows(seed, B, nlags, stride, negative=False):
+    rng = np.random.default_rng(seed)
+    corr = rng.uniform(-1.0, 1.0, (4 * B, stride))
+    if negative:
+        corr = -np.abs(corr) - 0.25
+    for b, n in enumerate(nlags):
+        corr[4 * b:4 * b + 4, n:] = np.nan                                  # what must never be read
+    return corr
+
+
+def _fold_loop(corr, nlag):
+    out = np.zeros((len(nlag), 1215))
+    for b, n in enumerate(nlag):
+        for phi in range(1215):
+            s = 0.0
+            for j in range(n // 1215):
+                s = s + max(float(corr[4 * b + band, phi + 1215 * j]) for band in range(4))
+            out[b, phi] = s
+    return out
+
+
+def _score_loop(corr, nlag, phases, hop, n_origins):
+    B, K = len(nlag), hop.shape[0]
+    score, origin, rank = np.full((B, K), -math.inf), np.full((B, K), -1, np.int64), np.full((B, K), -1, np.int32)
+    for b in range(B):
+        J = nlag[b] // 1215
+        for k in range(K):
+            best = None
+            for c in range(n_origins if J else 0):
+                if any(hop[k, c + j] > 3 for j in range(J)):
+                    continue
+                for p, phi in enumerate(phases[b]):
+                    s = 0.0
+                    for j in range(J):
+                        s = s + float(corr[4 * b + hop[k, c + j], phi + 1215 * j])
+                    s = s / J
+                    if best is None or s > best[0]:                         # origins ascend, list entries ascend: ties keep the first
+                        best = (s, c, p)
+            if best is not None:
+                score[b, k], origin[b, k], rank[b, k] = best
+    return score, origin, rank
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def test_fold_model_is_the_written_out_loop():
+    nlag = [1214, 1215, 2 * 1215 + 7, 3 * 1215]
+    corr = _rows(1, 4, nlag, 3 * 1215 + 9)
+    got = pr.fold_model(corr, nlag)
+    assert _same_bits(got, _fold_loop(corr, nlag)) and not got[0].any() and np.isfinite(got).all()
+    neg = _rows(2, 1, [2 * 1215], 2 * 1215, negative=True)
+    assert _same_bits(pr.fold_model(neg, [2 * 1215]), _fold_loop(neg, [2 * 1215])) and (pr.fold_model(neg, [2 * 1215]) < -0.4).all()
+    full = _rows(6, 2, [3 * 1215 + 9] * 2, 3 * 1215 + 9)
+    assert _same_bits(pr.fold_model(full, [10 ** 9, -5]), _fold_loop(full, [3 * 1215 + 9, 0]))                           # clamped to [0, stride]
+
+
+def test_score_model_is_the_written_out_loop():
+    rng = np.random.default_rng(3)
+    nlag = [3 * 1215 + 100, 1215, 700]
+    corr = _rows(4, 3, nlag, 3 * 1215 + 100)
+    hop = rng.integers(0, 4, (3, 40 + 3 - 1)).astype(np.uint8)
+    hop[1, 17] = 0xFF                                                       # excludes origins 15 .. 17 of three slots, 17 of one
+    phases = [[5, 1214, 0, 5], [1214, 7, 7, 3], [1, 2, 3, 4]]
+    got = pr.score_model(corr, nlag, phases, hop, 40)
+    want = _score_loop(corr, nlag, phases, hop, 40)
+    assert _same_bits(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
+    assert got[1].dtype == np.int64 and got[2].dtype == np.int32
+    assert (got[1][:2] >= 0).all() and np.isneginf(got[0][2]).all() and (got[1][2] == -1).all() and (got[2][2] == -1).all()      # J == 0
+    assert got[1][0, 1] not in (15, 16, 17)
+    none = pr.score_model(corr, nlag, phases, hop, 0)
+    assert np.isneginf(none[0]).all() and (none[1] == -1).all() and (none[2] == -1).all()
+
+
+def test_score_model_ties_lowest_origin_then_earliest_entry():
+    corr = _rows(5, 1, [2 * 1215], 2 * 1215, negative=True)                # all scores negative: the best does not start at 0
+    hop = np.array([[0, 1, 0, 1, 0, 1, 2]], np.uint8)                       # origins 0, 2, 4 and 1, 3 have identical windows
+    score, origin, rank = pr.score_model(corr, [2 * 1215], [[9, 9, 9]], hop, 6)
+    want = _score_loop(corr, [2 * 1215], [[9, 9, 9]], hop, 6)
+    assert score[0, 0] < 0 and origin[0, 0] in (0, 1, 5) and rank[0, 0] == 0
+    assert _same_bits(score, want[0]) and np.array_equal(origin, want[1]) and np.array_equal(rank, want[2])
+
+
+def test_pick_phases_planted_ties():
+    f = np.linspace(0.0, 1.0, 1215)
+    f[[7, 300, 1214]] = 5.0
+    f[[3, 900]] = 4.0
+    assert pr.pick_phases(f, 6) == [7, 300, 1214, 3, 900, 1213]
+    assert pr.pick_phases(np.zeros(1215), 4) == [0, 1, 2, 3]
+    assert pr.pick_phases(-f, 1) == [0] and sorted(pr.pick_phases(f, 1215)) == list(range(1215))
+    with pytest.raises(ValueError):
+        pr.pick_phases(f[:100], 3)
+
+
+def test_decoy_keys_known_answers():
+    keys = pr.decoy_keys(3)
+    assert keys == [hashlib.sha256(b"EchoSeal:decoy:v1:" + bytes([0, 0, 0, i])).digest() for i in range(3)]
+    assert keys[0].hex() == hashlib.sha256(b"EchoSeal:decoy:v1:\x00\x00\x00\x00").hexdigest() and len(set(pr.decoy_keys(33))) == 33
+    assert pr.decoy_keys(0) == [] and pr.decoy_keys(33)[:3] == keys
+    hop = pr.hop_model(keys, 2 ** 32 - 2, 4)
+    assert hop[:, 2:].tolist() == [[0xFF, 0xFF]] * 3 and hop[1, :2].tolist() == [band_index(keys[1], 2 ** 32 - 2), band_index(keys[1], 2 ** 32 - 1)]
+
+
+@pytest.mark.parametrize("kw, word", [
+    (dict(span=(-1, 5)), "outside"), (dict(span=(5, 2 ** 32 + 1)), "outside"), (dict(span=(9, 3)), "reversed"), (dict(span=7), "pair"),
+    (dict(span=(0.0, 4)), "integers"), (dict(span=(2 ** 32 - 10, 2 ** 32)), "wrap"), (dict(phases=0), "phases"), (dict(phases=1216), "phases"),
+    (dict(phases=2.0), "phases"), (dict(phases=True), "phases"), (dict(decoys=-1), "decoys"), (dict(decoys=1.5), "decoys"),
+    (dict(ctr0=-3), "ctr0"), (dict(ctr0=2 ** 32), "ctr0"), (dict(ctr0=[1, 2]), "ctr0"), (dict(ctr0=2 ** 32 - 1), "outside"),
+])
+def test_every_refusal_comes_before_any_engine(kw, word, monkeypatch):
+    det = WatermarkDetector(PC.KEY)
+    monkeypatch.setattr(WatermarkDetector, "engine", property(lambda self: pytest.fail("an engine was asked for")))
+    clip = np.zeros(3 * 1215 + 62, np.float32)                              # J = 3: span (2^32 - 10, 2^32) reaches counter 2^32 + 1
+    with pytest.raises(ValueError) as e:
+        det.presence(clip, 48_000, kw.pop("ctr0", None), **kw)
+    assert word in str(e.value), str(e.value)
+
+
+def test_the_reach_check_is_exact():
+    assert pr.slots(62) == 0 and pr.slots(1276) == 0 and pr.slots(1277) == 1 and pr.slots(3 * 1215 + 62) == 3
+    assert pr.check_reach((2 ** 32 - 10, 2 ** 32 - 2), 3 * 1215 + 62) == (2 ** 32 - 10, 2 ** 32 - 2)        # hi + J - 1 == 2^32
+    with pytest.raises(ValueError):
+        pr.check_reach((2 ** 32 - 10, 2 ** 32 - 1), 3 * 1215 + 62)
+    assert pr.check_reach((2 ** 32, 2 ** 32), 10 ** 6) == (2 ** 32, 2 ** 32)                                  # an empty span reaches nothing
+    assert pr.clip_spans([None, 7], (0, 64), 2) == [(0, 64), (7, 9)] and pr.clip_spans(5, (0, 64), 2) == [(5, 7)] * 2
+
+
+def test_the_companion_header_is_bound_beside_the_abi():
+    assert len(nat.DECLARATIONS) == len(nat.SIGNATURES) == 56 and nat.ES_ABI_VERSION == 2
+    assert set(nat.PRESENCE_DECLARATIONS) == set(nat.PRESENCE_SIGNATURES) == {"es_phase_fold_batch", "es_hop_score_batch"}
+    assert not set(nat.PRESENCE_DECLARATIONS) & set(nat.DECLARATIONS) and not set(nat.PRESENCE_CONSTANTS) & set(nat.CONSTANTS)
+    assert nat.PRESENCE_CONSTANTS == {"ES_HOP_TILE": 64, "ES_HOP_ORIGINS": 256} and nat.ES_HOP_TILE == 64 and nat.ES_HOP_ORIGINS == 256
+    from test_abi_binding import POINTERS, SCALARS
+    for name, params in nat.PRESENCE_DECLARATIONS.items():
+        assert {t for t, _ in params} <= SCALARS | POINTERS, name
+        assert params[0] == ("es_ctx*", "ctx") and params[-1] == ("void*", "stream") and name.endswith("_batch"), name
+        assert not any(p == "stream" for _, p in params[:-1]) and len(nat.PRESENCE_SIGNATURES[name][1]) == len(params)
+        for (ctype, _), arg in zip(params, nat.PRESENCE_SIGNATURES[name][1]):
+            assert (arg is nat.c_int64) == (ctype == "int64_t") and (arg is nat.c_int) == (ctype == "int"), (name, ctype)
+    src = open(nat.HEADER_PATH).read()
+    assert "es_hop_score_batch" not in src and "es_phase_fold_batch" not in src          # include/echoseal_hip.h is as it was
+
+
+@pytest.fixture(scope="module")
+def rows(oracle):
+    return {(kind, name): PC.oracle_rows(oracle, PC.cached(kind, name)) for kind in ("marked", "unmarked") for name in PC.CLIPS}
+
+
+@pytest.mark.parametrize("name", list(PC.CLIPS))
+def test_the_twin_finds_the_marked_clips(rows, name):
+    corr, nlag = rows["marked", name]
+    p = pr.presence_model(corr, nlag, PC.KEY, span=PC.SPAN, phases=8, decoys=32)
+    assert p.detected and (p.ctr, p.phase) == PC.FOUND and p.ctr0 == 1 and p.frames == 78 and p.phases[0] == 438 and len(p.phases) == 8
+    assert p.null.shape == (32,) and p.null.dtype == np.float64 and p.score > p.null.max()
+    print(f"clip {name}: own {p.score:.4f}, decoy max {p.null.max():.4f}, median {np.median(p.null):.4f}")
+    assert pr.presence_model(corr, nlag, PC.KEY, span=PC.SPAN, decoys=0).detected is False         # no decoy, no verdict
+    by_origin = pr.presence_model(corr, nlag, PC.KEY, span=(1, 3))                                  # ctr0 = 1's span
+    assert by_origin.detected and (by_origin.ctr, by_origin.phase) == PC.FOUND and by_origin.score == p.score
+
+
+@pytest.mark.parametrize("name", list(PC.CLIPS))
+def test_the_twin_refuses_another_key_and_the_unmarked_host(rows, name):
+    corr, nlag = rows["marked", name]
+    other = pr.presence_model(corr, nlag, PC.OTHER_KEY, span=PC.SPAN, phases=8, decoys=32)
+    assert not other.detected and other.phases[0] == 438                   # the grid is public: the key is what is missing
+    corr, nlag = rows["unmarked", name]
+    assert not pr.presence_model(corr, nlag, PC.KEY, span=PC.SPAN, phases=8, decoys=32).detected
+
+
+def test_a_clip_without_a_whole_slot_has_no_result():
+    assert pr.presence_model(np.zeros((4, 1214)), 1214, PC.KEY, span=PC.SPAN) is None
