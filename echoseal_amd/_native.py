@@ -104,6 +104,17 @@ if set(PRESENCE_SIGNATURES) & set(SIGNATURES) or set(PRESENCE_CONSTANTS) & set(C
     raise NativeError(f"{PRESENCE_HEADER_PATH} declares a name include/echoseal_hip.h already has")
 globals().update(PRESENCE_CONSTANTS)     # ES_HOP_TILE, ES_HOP_ORIGINS
 
+# The companion header of the drift-following presence test, bound the same way into three more tables.
+WARP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_warp.h")
+try:
+    with open(WARP_HEADER_PATH) as _f:
+        WARP_DECLARATIONS, WARP_SIGNATURES, WARP_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{WARP_HEADER_PATH}: the warp calls are bound from this header ({e})") from None
+if set(WARP_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES)) or set(WARP_CONSTANTS) & (set(CONSTANTS) | set(PRESENCE_CONSTANTS)):
+    raise NativeError(f"{WARP_HEADER_PATH} declares a name another header already has")
+globals().update(WARP_CONSTANTS)         # ES_WARP_HB
+
 _lib = None
 
 
@@ -125,7 +136,7 @@ def load() -> ctypes.CDLL:
     if got != CONSTANTS["ES_ABI_VERSION"]:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
-    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

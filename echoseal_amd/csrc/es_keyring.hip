@@ -8,8 +8,9 @@
 // window (es_acquire_mask_kernel, es_acquire_count_kernel, es_acquire_list_kernel).
 //
 // Last, the presence test, which reads the same hop rows: the keyless fold of a clip's correlation rows over the 1215-sample frame grid and
-// the score of every (key, counter origin, phase) against them (es_phase_fold_kernel, es_hop_score_kernel) -- the only float64
-// work in this file, every sum in one lane from its first slot to its last.
+// the score of every (key, counter origin, phase) against them (es_phase_fold_kernel, es_hop_score_kernel), and both again
+// on a grid that follows clock drift, a table of per-slot offsets (es_warp_fold_kernel, es_warp_score_kernel) -- the only
+// float64 work in this file, every sum in one lane from its first slot to its last.
 //
 // Integer work otherwise.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
@@ -385,6 +386,18 @@ __device__ __forceinline__ long long clip_nlag(const int32_t* __restrict__ nlag_
     return n < 0 ? 0 : (n > stride ? stride : n);
 }
 
+// the largest of the four band rows at one lag: band 0 first, a later band only where strictly larger
+__device__ __forceinline__ double band_max(const double* __restrict__ v, long long stride)
+{
+    double m = v[0];
+    #pragma unroll
+    for (int band = 1; band < 4; ++band) {
+        const double c = v[band * stride];
+        m = c > m ? c : m;
+    }
+    return m;
+}
+
 // fold[b][phi] = sum over slots j of the largest of the four band rows at lag phi + 1215 j: one lane per (clip, phase), five blocks per clip
 __global__ __launch_bounds__(256) void es_phase_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
         double* __restrict__ fold_p)
@@ -396,16 +409,8 @@ __global__ __launch_bounds__(256) void es_phase_fold_kernel(const double* __rest
     const double* row = corr_p + 4 * b * stride + phi;
     double acc = 0.0;
     #pragma unroll 1
-    for (long long j = 0; j < J; ++j) {
-        const double* v = row + j * ES_FRAME_LEN;
-        double m = v[0];
-        #pragma unroll
-        for (int band = 1; band < 4; ++band) {
-            const double c = v[band * stride];
-            m = c > m ? c : m;
-        }
-        acc = acc + m;
-    }
+    for (long long j = 0; j < J; ++j)
+        acc = acc + band_max(row + j * ES_FRAME_LEN, stride);
     fold_p[b * ES_FRAME_LEN + phi] = acc;
 }
 
@@ -415,6 +420,22 @@ struct hs_best { double score; long long origin; int rank; };
 __device__ __forceinline__ bool hs_better(const hs_best& b, const hs_best& a)
 {
     return b.origin >= 0 && (a.origin < 0 || b.score > a.score || (b.score == a.score && b.origin < a.origin));
+}
+
+// the best of a block's 256 lanes, to slot blockIdx.x of the scratch arrays: the end of both score kernels
+__device__ __forceinline__ void hs_block_best(hs_best* red, const hs_best& best, int tid, double* __restrict__ sc_score,
+        long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    red[tid] = best;
+    __syncthreads();
+    #pragma unroll 1
+    for (int w = HS_ORIGINS / 2; w > 0; w >>= 1) {                                         // a maximum under a total order: any shape gives the same winner
+        if (tid < w && hs_better(red[tid + w], red[tid])) red[tid] = red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sc_score[blockIdx.x] = red[0].score; sc_origin[blockIdx.x] = red[0].origin; sc_rank[blockIdx.x] = red[0].rank;
+    }
 }
 
 // One block per (clip b, key k, chunk of 256 origins), one lane per origin.  Per list entry the [J][4] values of its phase pass through
@@ -459,16 +480,7 @@ __global__ __launch_bounds__(256) void es_hop_score_kernel(const double* __restr
         const double s = acc / (double)J;
         if (ok && (best.origin < 0 || s > best.score)) { best.score = s; best.origin = origin; best.rank = p; }
     }
-    red[tid] = best;
-    __syncthreads();
-    #pragma unroll 1
-    for (int w = HS_ORIGINS / 2; w > 0; w >>= 1) {                                         // a maximum under a total order: any shape gives the same winner
-        if (tid < w && hs_better(red[tid + w], red[tid])) red[tid] = red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        sc_score[blockIdx.x] = red[0].score; sc_origin[blockIdx.x] = red[0].origin; sc_rank[blockIdx.x] = red[0].rank;
-    }
+    hs_block_best(red, best, tid, sc_score, sc_origin, sc_rank);
 }
 
 // the best of the NB chunks of each (clip, key), chunks ascending (ties keep the lower origin): one lane per pair
@@ -485,6 +497,124 @@ __global__ __launch_bounds__(256) void es_hop_best_kernel(const double* __restri
         if (hs_better(cand, best)) best = cand;
     }
     score_p[i] = best.score; origin_p[i] = best.origin; rank_p[i] = best.rank;
+}
+
+// ---- presence along a table of per-slot offsets (include/echoseal_warp.h) ----
+// Slot j of row d of clip b starts at lag 1215 j + warp[b][d][j].  A row is usable where d < nwarp[b] and every one of its J slots lies
+// whole inside [0, nlag): both kernels judge each slot from the table before they read it, so no table can make them read past a row.
+constexpr int WS_HB = ES_WARP_HB;
+
+// J of clip b: nslot[b] clamped to [0, min(Jw, nlag / 1215)]
+__device__ __forceinline__ long long warp_slots(const es_warp_tab& tab, long long b, long long n)
+{
+    const long long most = n / ES_FRAME_LEN < tab.Jw ? n / ES_FRAME_LEN : tab.Jw, J = ((g_ci32*)tab.nslot)[b];
+    return J < 0 ? 0 : (J > most ? most : J);
+}
+
+// the first lag of slot j under offset w, or -1 where the slot does not lie whole inside [0, n)
+__device__ __forceinline__ long long warp_lag(long long j, int w, long long n)
+{
+    const long long c = j * ES_FRAME_LEN + w;
+    return (c >= 0 && c + (ES_FRAME_LEN - 1) < n) ? c : -1;
+}
+
+// fold[b][d][phi] = sum over slots j of band_max at lag phi + 1215 j + warp[b][d][j], -inf for an unusable row: one lane per (clip, row,
+// phase), five blocks per (clip, row); the row's offsets pass through LDS 256 slots at a time, already turned into first lags
+__global__ __launch_bounds__(256) void es_warp_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        es_warp_tab tab, double* __restrict__ fold_p)
+{
+    __shared__ long long lag[256];
+    const int tid = threadIdx.x;
+    const long long bd = blockIdx.x / 5, b = bd / tab.D, d = bd - b * tab.D;
+    const int phi = (int)(blockIdx.x - bd * 5) * 256 + tid;
+    const long long n = clip_nlag(nlag_p, b, stride), J = warp_slots(tab, b, n);
+    g_ci32* wrow = (g_ci32*)tab.warp + bd * tab.Jw;
+    const double* row = corr_p + 4 * b * stride + phi;
+    bool usable = d < ((g_ci32*)tab.nwarp)[b];                                            // block-uniform, like everything the loop branches on
+    double acc = 0.0;
+    #pragma unroll 1
+    for (long long j0 = 0; usable && j0 < J; j0 += 256) {
+        const int nt = (int)(J - j0 < 256 ? J - j0 : 256);
+        __syncthreads();                                                                  // the tile before has been read
+        if (tid < nt) lag[tid] = warp_lag(j0 + tid, wrow[j0 + tid], n);
+        usable = __syncthreads_and(tid >= nt || lag[tid] >= 0) != 0;
+        if (usable && phi < ES_FRAME_LEN) {
+            #pragma unroll 1
+            for (int j = 0; j < nt; ++j)
+                acc = acc + band_max(row + lag[j], stride);
+        }
+    }
+    if (phi < ES_FRAME_LEN) fold_p[bd * ES_FRAME_LEN + phi] = usable ? acc : -__builtin_inf();
+}
+
+// es_hop_score_kernel along the table, the list taken HB entries at a time.  A lane's hop window is the same for every entry, so the slot
+// tile is the outer loop and the block of entries the inner one: per tile the block's [HS_TILE][4][HB] values pass through LDS (the HB
+// values of one (slot, band) side by side), a hop byte is read once per block, and acc[e] still takes its terms in ascending slot order.
+// An entry is dropped where it names no usable row or no phase: e_bad is raised by whichever lane finds a slot of its row outside the
+// clip, and that slot is not read.  HB = 1 is the loop of es_hop_score_kernel itself.
+template <int HB>
+__global__ __launch_bounds__(256) void es_warp_score_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        es_warp_tab tab, const int32_t* __restrict__ hyp_p, int H, const uint8_t* __restrict__ hop_p, long long K, long long Ccols,
+        long long n_origins, long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    __shared__ __attribute__((aligned(16))) double vals[HS_TILE * 4 * HB];
+    __shared__ hs_best red[HS_ORIGINS];
+    __shared__ int e_row[HB], e_phi[HB], e_bad[HB];
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * HS_ORIGINS + tid;
+    const bool live = origin < n_origins;
+    const long long n = clip_nlag(nlag_p, b, stride), J = warp_slots(tab, b, n);
+    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + (live ? origin : 0);                         // columns origin .. origin + J - 1 < Ccols: J <= Jw
+    const double* rows = corr_p + 4 * b * stride;
+    hs_best best = {-__builtin_inf(), -1, -1};
+    #pragma unroll 1
+    for (int h0 = 0; h0 < H && J > 0; h0 += HB) {
+        __syncthreads();                                                                  // the block before has been judged
+        if (tid < HB) {
+            int d = -1, phi = -1;
+            if (h0 + tid < H) { d = ((g_ci32*)hyp_p)[(b * H + h0 + tid) * 2]; phi = ((g_ci32*)hyp_p)[(b * H + h0 + tid) * 2 + 1]; }
+            const bool named = d >= 0 && d < tab.D && d < ((g_ci32*)tab.nwarp)[b] && phi >= 0 && phi < ES_FRAME_LEN;
+            e_row[tid] = named ? d : -1; e_phi[tid] = phi; e_bad[tid] = !named;
+        }
+        __syncthreads();
+        double acc[HB];
+        #pragma unroll
+        for (int e = 0; e < HB; ++e) acc[e] = 0.0;
+        bool ok = live;
+        #pragma unroll 1
+        for (long long j0 = 0; j0 < J; j0 += HS_TILE) {
+            const int nt = (int)(J - j0 < HS_TILE ? J - j0 : HS_TILE);
+            __syncthreads();                                                              // the tile before has been read
+            if ((tid >> 2) < nt) {
+                const long long j = j0 + (tid >> 2);
+                #pragma unroll
+                for (int e = 0; e < HB; ++e) {
+                    const int d = e_row[e];
+                    const long long c = d < 0 ? -1 : warp_lag(j, ((g_ci32*)tab.warp)[(b * tab.D + d) * tab.Jw + j], n);
+                    if (c >= 0) vals[tid * HB + e] = rows[(tid & 3) * stride + c + e_phi[e]];
+                    else if (d >= 0) e_bad[e] = 1;
+                }
+            }
+            __syncthreads();
+            if (live) {
+                #pragma unroll 1
+                for (int j = 0; j < nt; ++j) {
+                    const unsigned h = hop[j0 + j];
+                    ok = ok && h < 4u;
+                    const double* v = vals + (4 * j + (int)(h & 3u)) * HB;
+                    #pragma unroll
+                    for (int e = 0; e < HB; ++e) acc[e] = acc[e] + v[e];
+                }
+            }
+        }
+        #pragma unroll
+        for (int e = 0; e < HB; ++e) {                                                    // entries ascending: of equal scores the earliest stays
+            const double s = acc[e] / (double)J;
+            if (ok && !e_bad[e] && (best.origin < 0 || s > best.score)) { best.score = s; best.origin = origin; best.rank = h0 + e; }
+        }
+    }
+    hs_block_best(red, best, tid, sc_score, sc_origin, sc_rank);
 }
 
 }  // namespace
@@ -563,17 +693,45 @@ int es_launch_phase_fold(es_ctx* ctx, const double* corr, int64_t stride, const 
     return es_launch(ctx, es_phase_fold_kernel, (unsigned)(B * 5), 256, 0, st, corr, (long long)stride, nlag, fold);
 }
 
+// the caller's scratch as the three arrays of the blocks' bests, one slot per (clip, key, chunk), and the launch that reduces them
+struct hs_scratch {
+    long long NB, pairs, slots;
+    double* score; long long* origin; long long* rank;
+    hs_scratch(void* scratch, int64_t B, int64_t K, int64_t n_origins)
+        : NB((n_origins + ES_HOP_ORIGINS - 1) / ES_HOP_ORIGINS), pairs((long long)B * K), slots(pairs * NB), score((double*)scratch),
+          origin((long long*)scratch + slots), rank((long long*)scratch + 2 * slots) {}
+};
+static int es_launch_hop_best(es_ctx* ctx, const hs_scratch& sc, double* score, int64_t* origin, int32_t* rank, hipStream_t st)
+{
+    return es_launch(ctx, es_hop_best_kernel, (unsigned)((sc.pairs + 255) / 256), 256, 0, st, (const double*)sc.score, (const long long*)sc.origin,
+                     (const long long*)sc.rank, sc.pairs, sc.NB, score, (long long*)origin, rank);
+}
+
 int es_launch_hop_score(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, const int32_t* phase, int P,
                         const uint8_t* hop, int64_t K, int64_t Ccols, int64_t n_origins, double* score, int64_t* origin, int32_t* rank,
                         void* scratch, hipStream_t st)
 {
-    const long long NB = (n_origins + ES_HOP_ORIGINS - 1) / ES_HOP_ORIGINS, pairs = (long long)B * K, slots = pairs * NB;
-    double* sc_score = (double*)scratch;
-    long long* sc_origin = (long long*)scratch + slots;
-    long long* sc_rank = (long long*)scratch + 2 * slots;
-    if (slots > 0)
-        if (const int rc = es_launch(ctx, es_hop_score_kernel, (unsigned)slots, 256, 0, st, corr, (long long)stride, nlag, phase, P, hop, (long long)K,
-                                     (long long)Ccols, (long long)n_origins, NB, sc_score, sc_origin, sc_rank)) return rc;
-    return es_launch(ctx, es_hop_best_kernel, (unsigned)((pairs + 255) / 256), 256, 0, st, (const double*)sc_score, (const long long*)sc_origin,
-                     (const long long*)sc_rank, pairs, NB, score, (long long*)origin, rank);
+    const hs_scratch sc(scratch, B, K, n_origins);
+    if (sc.slots > 0)
+        if (const int rc = es_launch(ctx, es_hop_score_kernel, (unsigned)sc.slots, 256, 0, st, corr, (long long)stride, nlag, phase, P, hop, (long long)K,
+                                     (long long)Ccols, (long long)n_origins, sc.NB, sc.score, sc.origin, sc.rank)) return rc;
+    return es_launch_hop_best(ctx, sc, score, origin, rank, st);
+}
+
+// the same along a table of per-slot offsets (include/echoseal_warp.h): exact grids again, checked by the entry points
+int es_launch_warp_fold(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, const es_warp_tab& tab, double* fold,
+                        hipStream_t st)
+{
+    return es_launch(ctx, es_warp_fold_kernel, (unsigned)(B * tab.D * 5), 256, 0, st, corr, (long long)stride, nlag, tab, fold);
+}
+
+int es_launch_warp_score(es_ctx* ctx, const double* corr, int64_t stride, const int32_t* nlag, int64_t B, const es_warp_tab& tab,
+                         const int32_t* hyp, int64_t H, const uint8_t* hop, int64_t K, int64_t Ccols, int64_t n_origins, double* score,
+                         int64_t* origin, int32_t* rank, void* scratch, hipStream_t st)
+{
+    const hs_scratch sc(scratch, B, K, n_origins);
+    if (sc.slots > 0)
+        if (const int rc = es_launch(ctx, es_warp_score_kernel<WS_HB>, (unsigned)sc.slots, 256, 0, st, corr, (long long)stride, nlag, tab, hyp, (int)H,
+                                     hop, (long long)K, (long long)Ccols, (long long)n_origins, sc.NB, sc.score, sc.origin, sc.rank)) return rc;
+    return es_launch_hop_best(ctx, sc, score, origin, rank, st);
 }

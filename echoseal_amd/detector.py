@@ -303,10 +303,12 @@ class WatermarkDetector:
         return None
 
     # ------------------------------------------------------------------ presence
-    def presence(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = 8, decoys: int = 32):
-        return self.presence_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys)[0]
+    def presence(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = 8, decoys: int = 32,
+                 drift_ppm=0.0):
+        return self.presence_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys,
+                                   drift_ppm=drift_ppm)[0]
 
-    def presence_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32) -> list:
+    def presence_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> list:
         """Tell whether each clip carries this key's mark, without demodulating anything: -> per clip a presence.Presence, or None for a
         clip without one whole 1215-sample slot.  The 63-chip preamble of every frame survives the channel where the payload does not
         (DESIGN 4.23), and it peaks in the band the HMAC-keyed hop sequence names: the score of a key is the mean, over the clip's
@@ -315,17 +317,27 @@ class WatermarkDetector:
         (presence.decoy_keys); detected = the own score is strictly above every decoy's.  No threshold is tuned anywhere; the verdict
         is statistical, not authenticated.  ctr0 = c (one value, or one per clip with None entries allowed) is shorthand for
         span = (c, c + 2).  phases = 1215 searches every phase.
+        drift_ppm > 0: the clip may have been captured on another sample clock than it was played on, up to drift_ppm
+        parts per million fast or slow.  The grid then stretches: every total skew of -E .. E samples across the clip is tried
+        (presence.skew_table), `phases` counts the (skew, phase) pairs of largest fold, and Presence.skew / drift_ppm / hypotheses say
+        what was found; per launch ONE warp fold, ONE download and pick, ONE hop window and ONE warp score (es_warp_fold_batch,
+        es_warp_score_batch).  All keys search the same pairs, so the verdict and its 1 / (decoys + 1) bound stand.  drift_ppm = 0 is
+        the rigid grid: the calls and the bits of before.
         The front is verify_batch's (cut_launches, four rows per clip in BAND_PLAN order, mixed rates, int16 and unequal lengths
         included) with the correlation rows kept; per launch ONE fold, ONE hop window over the ring [key] + decoys and ONE score call.
         session_nonce and the traces are not touched.  ValueError before any engine exists: a span outside [0, 2^32], reversed or
-        reaching past 2^32 from its last origin, phases outside 1 .. 1215, decoys < 0, a bad ctr0."""
+        reaching past 2^32 from its last origin, phases outside 1 .. 1215, decoys < 0, a bad ctr0, a drift_ppm that is negative, not
+        finite or no number, or that skews some clip by a whole frame or leaves it no slot."""
         from . import presence as pr
         import torch
         fs_list = rate_list(fs_in, len(clips))
-        P, R = pr.check_phases(phases), pr.check_decoys(decoys)
+        P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
         spans = pr.clip_spans(ctr0, span, len(clips))
         for c, f, s in zip(clips, fs_list, spans):                          # refused by name before any engine exists
-            pr.check_reach(s, resampled_length(int(np.size(c)), int(f), self.fs_target))
+            samples = resampled_length(int(np.size(c)), int(f), self.fs_target)
+            pr.check_reach(s, samples)
+            if drift > 0:
+                pr.skew_table(samples - (PRE_L - 1), drift)
         out: list = [None] * len(clips)
         band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
         nb = band_ids.size
@@ -341,6 +353,9 @@ class WatermarkDetector:
                 else:
                     corr = eng.xcorr(eng.bpf(x[:, :M], bid), bid)
                 nlag = np.array(sizes, np.int64) - (PRE_L - 1)
+                if drift > 0:
+                    self._presence_drift(eng, corr, nlag, drift, P, R, lo, hi, [ids[i] for i in la.idx], out)
+                    continue
                 J = nlag // FRAME_LEN
                 if not J.max():
                     continue
@@ -356,6 +371,31 @@ class WatermarkDetector:
                     if J[k]:
                         out[ids[i]] = pr.verdict(score[k], origin[k], rank[k], lo, plists[k], int(J[k]))
         return out
+
+    def _presence_drift(self, eng, corr, nlag, drift: float, P: int, R: int, lo: int, hi: int, ids: list, out: list) -> None:
+        """One launch of presence_batch with a drift search: the skew tables of the clips packed [B][Dmax][Jmax] (zeros past a clip's
+        own rows and slots: nwarp and nslot say where they end), the fold along every row, each clip's (row, phase) list, and the score."""
+        from . import presence as pr
+        tabs = [pr.skew_table(n, drift) for n in nlag.tolist()]
+        J = np.array([t[1] for t in tabs], np.int32)
+        if J.max():
+            nwarp = np.array([len(t[0]) for t in tabs], np.int32)
+            warp = np.zeros((len(tabs), int(nwarp.max()), int(J.max())), np.int32)
+            for k, (_, j, w) in enumerate(tabs):
+                warp[k, :w.shape[0], :j] = w
+            warp, nwarp_d, nslot_d = dev(eng, warp, np.int32), dev(eng, nwarp, np.int32), dev(eng, J, np.int32)
+            fold = eng.warp_fold(corr, nlag, warp, nwarp_d, nslot_d).cpu().numpy()
+            hyps = [pr.pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
+            hyp = np.full((len(tabs), P, 2), -1, np.int32)                  # a list is P entries long; a shorter one ends in entries that name nothing
+            for k, h in enumerate(hyps):
+                hyp[k, :len(h)] = h
+            hop = eng.hop_window(self._presence_ring(R), [min(lo, CTR_END - 1)], max(hi - lo + int(J.max()) - 1, 0))
+            score, origin, rank = (t.cpu().numpy() for t in eng.warp_score(corr, nlag, warp, nwarp_d, nslot_d, hyp, hop, hi - lo))
+            for k, i in enumerate(ids):
+                if J[k]:
+                    out[i] = pr.drift_verdict(score[k], origin[k], rank[k], lo, hyps[k], tabs[k][0], int(J[k]))
+            if self._presence_rows is not None:
+                self._presence_rows.append((ids, corr.cpu().numpy(), nlag))
 
     def _presence_ring(self, decoys: int):
         """The ring [this detector's key] + the first `decoys` public decoy keys, derived once per engine and count."""

@@ -637,6 +637,22 @@ class RxEngine(TxChain, MonitorChain):
             raise ValueError("corr: four rows per clip, row 4 * clip + band")
         return corr, corr.shape[0], corr.shape[1], nlag, nlag.numel()
 
+    def _score_io(self, hop: torch.Tensor, B: int, n_origins):
+        """The hop rows of a score call, checked, and what the call writes: -> (hop uint8 [K, Ccols], K, n_origins, score, origin, rank,
+        scratch)."""
+        if hop.dim() == 3 and hop.shape[1] == 1:
+            hop = hop[:, 0, :]
+        if hop.dim() != 2 or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [K, Ccols]")
+        hop = hop.contiguous()
+        K, n_origins = hop.shape[0], int(n_origins)
+        score = torch.empty((B, K), dtype=torch.float64, device=self.device)
+        origin = torch.empty((B, K), dtype=torch.int64, device=self.device)
+        rank = torch.empty((B, K), dtype=torch.int32, device=self.device)
+        chunks = -(-max(n_origins, 0) // nat.ES_HOP_ORIGINS)
+        scratch = torch.empty(3 * B * K * chunks, dtype=torch.int64, device=self.device)      # the workgroups' bests: 24 bytes each
+        return hop, K, n_origins, score, origin, rank, scratch
+
     def phase_fold(self, corr: torch.Tensor, nlag) -> torch.Tensor:
         """The keyless fold of a presence test (es_phase_fold_batch; presence.fold_model is the host twin): corr float64 [rows, stride],
         row 4 * clip + band the correlation row of BAND_PLAN band `band`, nlag [B] the lags of each clip (clamped to [0, stride]; columns
@@ -657,19 +673,44 @@ class RxEngine(TxChain, MonitorChain):
         phases = self._dev(phases, torch.int32)
         if phases.dim() != 2 or phases.shape[0] != B:
             raise ValueError("phases: int [B, P], one list per clip")
-        if hop.dim() == 3 and hop.shape[1] == 1:
-            hop = hop[:, 0, :]
-        if hop.dim() != 2 or hop.dtype != torch.uint8:
-            raise ValueError("hop must be uint8 [K, Ccols]")
-        hop = hop.contiguous()
-        K, n_origins = hop.shape[0], int(n_origins)
-        score = torch.empty((B, K), dtype=torch.float64, device=self.device)
-        origin = torch.empty((B, K), dtype=torch.int64, device=self.device)
-        rank = torch.empty((B, K), dtype=torch.int32, device=self.device)
-        chunks = -(-max(n_origins, 0) // nat.ES_HOP_ORIGINS)
-        scratch = torch.empty(3 * B * K * chunks, dtype=torch.int64, device=self.device)      # the workgroups' bests: 24 bytes each
+        hop, K, n_origins, score, origin, rank, scratch = self._score_io(hop, B, n_origins)
         self._call("es_hop_score_batch", corr, rows, stride, nlag, B, phases, phases.shape[1], hop, K, hop.shape[1], n_origins, score, origin, rank,
                    scratch if scratch.numel() else None)
+        return score, origin, rank
+
+    # ------------------------------------------------------------------ presence under clock drift (include/echoseal_warp.h)
+    def _warp_table(self, warp, nwarp, nslot, B: int):
+        """The table of per-slot offsets of a warp call, checked: -> (warp int32 [B, D, Jw], nwarp int32 [B], nslot int32 [B], D, Jw)."""
+        warp = self._dev(warp, torch.int32)
+        nwarp, nslot = self._dev(nwarp, torch.int32).reshape(-1), self._dev(nslot, torch.int32).reshape(-1)
+        if warp.dim() != 3 or warp.shape[0] != B or nwarp.numel() != B or nslot.numel() != B:
+            raise ValueError("warp: int [B, D, Jw] with nwarp [B] rows and nslot [B] slots per clip")
+        return warp, nwarp, nslot, warp.shape[1], warp.shape[2]
+
+    def warp_fold(self, corr: torch.Tensor, nlag, warp, nwarp, nslot) -> torch.Tensor:
+        """phase_fold along a table of per-slot offsets (es_warp_fold_batch; presence.warp_fold_model is the host twin).  corr, nlag as
+        for phase_fold; warp int [B, D, Jw]: slot j of row d of clip b starts warp[b, d, j] samples after 1215 j; nwarp [B] the rows
+        and nslot [B] the slots of each clip (clamped to [0, min(Jw, nlag // 1215)]) -> fold float64 [B, D, 1215]; a row at or past
+        nwarp, or one with a slot that does not lie whole inside the clip's lags, is all -inf and is never read."""
+        corr, rows, stride, nlag, B = self._presence_rows(corr, nlag)
+        warp, nwarp, nslot, D, Jw = self._warp_table(warp, nwarp, nslot, B)
+        fold = torch.empty((B, D, nat.ES_FRAME_LEN), dtype=torch.float64, device=self.device)
+        self._call("es_warp_fold_batch", corr, rows, stride, nlag, B, warp if warp.numel() else None, nwarp, nslot, D, Jw, fold)
+        return fold
+
+    def warp_score(self, corr: torch.Tensor, nlag, warp, nwarp, nslot, hyp, hop: torch.Tensor, n_origins: int):
+        """hop_score along a table of per-slot offsets (es_warp_score_batch; presence.warp_score_model is the host twin).  corr, nlag,
+        warp, nwarp, nslot as for warp_fold; hyp int [B, H, 2], H >= 1: entry h of clip b is (row d, phase phi); hop uint8 [K, Ccols]
+        (or hop_window's [K, 1, Ccols]) with Ccols >= n_origins + Jw - 1 -> (score float64 [B, K], origin int64 [B, K], rank int32
+        [B, K]) as hop_score gives them, rank the list entry; an entry that names no usable row or no phase is not scored."""
+        corr, rows, stride, nlag, B = self._presence_rows(corr, nlag)
+        warp, nwarp, nslot, D, Jw = self._warp_table(warp, nwarp, nslot, B)
+        hyp = self._dev(hyp, torch.int32)
+        if hyp.dim() != 3 or hyp.shape[0] != B or hyp.shape[2] != 2:
+            raise ValueError("hyp: int [B, H, 2], a list of (row, phase) per clip")
+        hop, K, n_origins, score, origin, rank, scratch = self._score_io(hop, B, n_origins)
+        self._call("es_warp_score_batch", corr, rows, stride, nlag, B, warp if warp.numel() else None, nwarp, nslot, D, Jw, hyp, hyp.shape[1],
+                   hop, K, hop.shape[1], n_origins, score, origin, rank, scratch if scratch.numel() else None)
         return score, origin, rank
 
     def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):

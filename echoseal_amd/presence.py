@@ -6,11 +6,18 @@ anything here.
 The rows: clip b owns rows 4 b .. 4 b + 3 of `corr`, row 4 b + band the float64 correlation row (es_xcorr_batch) of BAND_PLAN band `band`,
 lags [0, nlag[b]); J = nlag // 1215 whole slots.  Every sum is float64, added term by term in ascending slot order from 0.0 -- the loops
 below add one slot at a time to every independent sum at once, which is that order for each of them; np.sum is never used.
+
+Drift: a recording played by one device and captured by another has no rigid grid.  skew_table lists, for a largest clock
+offset of drift_ppm, every total skew e of -E .. E samples across the clip as a row of per-slot offsets; warp_fold_model /
+pick_hypotheses / warp_score_model are the fold, the pick and the score along those rows (es_warp_fold_batch, es_warp_score_batch;
+include/echoseal_warp.h), and presence_model(..., drift_ppm=...) the whole search.
 """
 from __future__ import annotations
 
 import hashlib
+import math
 from dataclasses import dataclass
+from fractions import Fraction
 
 import numpy as np
 
@@ -29,8 +36,12 @@ class Presence:
     origins and the phase list; null: the same under each public decoy key, in decoy order; detected: score > max(null), strictly, with
     at least one decoy -- under exchangeability of the keys a false alarm has probability at most 1 / (len(null) + 1).  ctr: the counter
     of the first whole frame of the best origin, phase its first sample, ctr0 = acquire.origin_of(ctr, phase) the counter origin to verify
-    or acquire with; all three -1 where nothing was scored (an empty span).  frames: whole 1215-sample slots of the clip (J); phases:
-    the phase list that was searched, best keyless fold first."""
+    or acquire with; all three -1 where nothing was scored (an empty span).  frames: the 1215-sample slots that were summed (J); phases:
+    the phase list that was searched, best keyless fold first.
+    With a drift search (drift_ppm > 0 asked for): skew, the total offset in samples across the clip of the grid the best score was found
+    on (the last slot starts `skew` samples later than on the rigid grid; 0 where nothing was scored); drift_ppm, the clock offset that
+    corresponds to, 10^6 skew / (1215 frames); hypotheses, the (skew, phase) pairs that were searched, best keyless fold first (phases
+    is their second column).  Without one: 0, 0.0 and None."""
     detected: bool
     score: float
     null: np.ndarray
@@ -39,6 +50,9 @@ class Presence:
     ctr0: int
     frames: int
     phases: list
+    skew: int = 0
+    drift_ppm: float = 0.0
+    hypotheses: list | None = None
 
 
 def decoy_keys(n: int) -> list[bytes]:
@@ -167,6 +181,122 @@ def score_model(corr, nlag, phases, hop, n_origins: int):
     return score, origin, rank
 
 
+def check_drift(drift_ppm) -> float:
+    """drift_ppm of a presence call: a finite number, 0 or more (0: the rigid grid)."""
+    if isinstance(drift_ppm, (bool, np.bool_)) or not isinstance(drift_ppm, (int, float, np.integer, np.floating)):
+        raise ValueError(f"drift_ppm = {drift_ppm!r}: a number of parts per million")
+    if not math.isfinite(drift_ppm) or drift_ppm < 0:
+        raise ValueError(f"drift_ppm = {drift_ppm!r}: the largest clock offset searched in either direction, finite and 0 or more")
+    return float(drift_ppm)
+
+
+def skew_table(nlag: int, drift_ppm) -> tuple[list[int], int, np.ndarray]:
+    """The grids a drift search tries on a clip of nlag lags -> (skews, J, warp).  E = ceil(drift_ppm nlag / 10^6) exactly;
+    J = (nlag - E) // 1215 slots; skews = [0, -1, 1, -2, 2 .. -E, E], row 0 the rigid grid; warp int32 [2 E + 1, J],
+    warp[d][j] = floor((2 j e + J) / (2 J)) for e = skews[d]: j e / J rounded half up, so e is the total skew across the clip.  Every
+    column phi + 1215 j + warp[d][j], phi <= 1214, lies in [0, nlag).  Integers only.  ValueError: a bad drift_ppm (check_drift),
+    E > 1214, or no slot left (J == 0) where the rigid grid had one."""
+    drift, nlag = check_drift(drift_ppm), max(int(nlag), 0)
+    E = math.ceil(Fraction(drift) * nlag / 10 ** 6)
+    if E > FRAME_LEN - 1:
+        raise ValueError(f"drift_ppm = {drift_ppm!r}: {E} samples of skew across {nlag} lags, more than {FRAME_LEN - 1} (a whole frame)")
+    J = (nlag - E) // FRAME_LEN
+    if J == 0 and nlag // FRAME_LEN:
+        raise ValueError(f"drift_ppm = {drift_ppm!r}: {E} samples of skew leave no whole slot in {nlag} lags")
+    skews = [0] + [s * e for e in range(1, E + 1) for s in (-1, 1)]
+    j = np.arange(J, dtype=np.int64)
+    warp = np.stack([(2 * j * e + J) // (2 * J) if J else j for e in skews]).astype(np.int32)       # // floors, for negative e too
+    return skews, J, warp
+
+
+def _table(warp, nwarp, nslot, nlag):
+    """The table of a warp call as the kernels see it: -> (warp int64 [B, D, Jw], nwarp [B], J [B] clamped to [0, min(Jw, nlag // 1215)])."""
+    warp = np.asarray(warp, np.int64)
+    if warp.ndim != 3 or warp.shape[0] != nlag.size:
+        raise ValueError("warp: int [B, D, Jw], a table per clip")
+    nwarp, nslot = (np.asarray(a, np.int64).reshape(-1) for a in (nwarp, nslot))
+    if nwarp.size != nlag.size or nslot.size != nlag.size:
+        raise ValueError("nwarp, nslot: one value per clip")
+    return warp, nwarp, np.clip(nslot, 0, np.minimum(warp.shape[2], nlag // FRAME_LEN))
+
+
+def _usable(w, d: int, nw: int, J: int, n: int) -> bool:
+    """Row d of a clip's table w [D, Jw]: d < nwarp, and each of its J slots whole inside [0, n)."""
+    if not 0 <= d < min(nw, w.shape[0]):
+        return False
+    first = FRAME_LEN * np.arange(J, dtype=np.int64) + w[d, :J]
+    return bool((first >= 0).all() and (first + (FRAME_LEN - 1) < n).all())
+
+
+def warp_fold_model(corr, nlag, warp, nwarp, nslot) -> np.ndarray:
+    """es_warp_fold_batch in NumPy -> fold float64 [B, D, 1215]; an unusable row is -inf."""
+    corr, nlag = _rows(corr, nlag)
+    warp, nwarp, nslot = _table(warp, nwarp, nslot, nlag)
+    fold = np.full((nlag.size, warp.shape[1], FRAME_LEN), -np.inf, np.float64)
+    phi = np.arange(FRAME_LEN)
+    for b, (n, J) in enumerate(zip(nlag.tolist(), nslot.tolist())):
+        for d in range(warp.shape[1]):
+            if not _usable(warp[b], d, int(nwarp[b]), J, n):
+                continue
+            acc = np.zeros(FRAME_LEN, np.float64)
+            for j in range(J):
+                v = corr[NBANDS * b:NBANDS * b + NBANDS][:, FRAME_LEN * j + int(warp[b, d, j]) + phi]
+                m = v[0].copy()
+                for band in range(1, NBANDS):                               # a later band only where strictly larger
+                    np.copyto(m, v[band], where=v[band] > m)
+                acc = acc + m
+            fold[b, d] = acc
+    return fold
+
+
+def pick_hypotheses(fold_rows, phases: int) -> list[tuple[int, int]]:
+    """The min(phases, D 1215) pairs (row d, phase phi) of largest fold over the usable rows of one clip's fold [D, 1215] (an unusable
+    row is all -inf), largest first; of equal values the lower row first, then the lower phase."""
+    f = np.asarray(fold_rows, np.float64)
+    if f.ndim != 2 or f.shape[1] != FRAME_LEN:
+        raise ValueError(f"a clip's fold is [D, {FRAME_LEN}]")
+    pairs = [(d, phi) for d in range(f.shape[0]) if not np.isneginf(f[d]).all() for phi in range(FRAME_LEN)]
+    pairs.sort(key=lambda p: (-f[p], p))
+    return pairs[:min(check_phases(phases), f.shape[0] * FRAME_LEN)]
+
+
+def warp_score_model(corr, nlag, warp, nwarp, nslot, hyp, hop, n_origins: int):
+    """es_warp_score_batch in NumPy: hyp int [B, H, 2], entry h of clip b = (d, phi)
+    -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K])."""
+    corr, nlag = _rows(corr, nlag)
+    warp, nwarp, nslot = _table(warp, nwarp, nslot, nlag)
+    hyp = np.asarray(hyp, np.int64).reshape(nlag.size, -1, 2)
+    hop = np.asarray(hop, np.uint8)
+    K, n_origins = hop.shape[0], int(n_origins)
+    score = np.full((nlag.size, K), -np.inf, np.float64)
+    origin = np.full((nlag.size, K), -1, np.int64)
+    rank = np.full((nlag.size, K), -1, np.int32)
+    for b, (n, J) in enumerate(zip(nlag.tolist(), nslot.tolist())):
+        if J == 0 or n_origins == 0:
+            continue
+        if hop.shape[1] < n_origins + J - 1:
+            raise ValueError("hop: fewer than n_origins + J - 1 columns")
+        rows = corr[NBANDS * b:NBANDS * b + NBANDS]
+        good = [bool(0 <= phi < FRAME_LEN) and _usable(warp[b], d, int(nwarp[b]), J, n) for d, phi in hyp[b].tolist()]
+        for k in range(K):
+            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]: slot j of every origin's window
+            scored = np.flatnonzero((win < NBANDS).all(axis=0))
+            if not scored.size:
+                continue
+            win = (win & 3).astype(np.int64)
+            for h, (d, phi) in enumerate(hyp[b].tolist()):
+                if not good[h]:
+                    continue
+                acc = np.zeros(n_origins, np.float64)
+                for j in range(J):
+                    acc = acc + rows[win[j], phi + FRAME_LEN * j + int(warp[b, d, j])]
+                s = (acc / np.float64(J))[scored]
+                i = int(np.argmax(s))                                                    # the first of equal values: the lowest origin
+                if origin[b, k] < 0 or s[i] > score[b, k] or (s[i] == score[b, k] and scored[i] < origin[b, k]):
+                    score[b, k], origin[b, k], rank[b, k] = s[i], scored[i], h
+    return score, origin, rank
+
+
 def verdict(score_row, origin_row, rank_row, lo: int, phases: list, frames: int) -> Presence:
     """The Presence of one clip from its row of the score call: key row 0 is the detector's key, rows 1 .. R the decoys."""
     own, null = float(score_row[0]), np.array(score_row[1:], np.float64)
@@ -176,12 +306,31 @@ def verdict(score_row, origin_row, rank_row, lo: int, phases: list, frames: int)
     return Presence(bool(null.size and own > null.max()), own, null, ctr, phase, origin_of(ctr, phase) if found else -1, int(frames), list(phases))
 
 
-def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int = 8, decoys: int = 32) -> Presence | None:
+def drift_verdict(score_row, origin_row, rank_row, lo: int, hyps: list, skews: list, frames: int) -> Presence:
+    """The Presence of one clip from its row of the warp score call: hyps its (row, phase) list, skews the skew of each table row."""
+    p = verdict(score_row, origin_row, rank_row, lo, [phi for _, phi in hyps], frames)
+    p.skew = int(skews[hyps[int(rank_row[0])][0]]) if p.ctr >= 0 else 0
+    p.drift_ppm = 1e6 * p.skew / (FRAME_LEN * int(frames))
+    p.hypotheses = [(int(skews[d]), int(phi)) for d, phi in hyps]
+    return p
+
+
+def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> Presence | None:
     """WatermarkDetector.presence from one clip's four correlation rows (BAND_PLAN order), on the host: the fold, the phase list, the hop
-    rows of `key` and the decoys, the score and the verdict.  None where the clip has no whole slot."""
+    rows of `key` and the decoys, the score and the verdict.  None where the clip has no whole slot.  drift_ppm > 0: the same along every
+    row of skew_table(nlag, drift_ppm), the list being the (row, phase) pairs of largest fold."""
     corr4 = np.asarray(corr4, np.float64)
     nlag = min(max(int(nlag), 0), corr4.shape[1])
     lo, hi = check_reach(span, nlag + PRE_L - 1)
+    if check_drift(drift_ppm) > 0:
+        skews, J, warp = skew_table(nlag, drift_ppm)
+        if J == 0:
+            return None
+        tab = (warp[None], [len(skews)], [J])
+        hyps = pick_hypotheses(warp_fold_model(corr4, [nlag], *tab)[0], phases)
+        hop = hop_model([bytes(key)] + decoy_keys(decoys), lo, max(hi - lo + J - 1, 0))
+        score, origin, rank = warp_score_model(corr4, [nlag], *tab, [hyps], hop, hi - lo)
+        return drift_verdict(score[0], origin[0], rank[0], lo, hyps, skews, J)
     J = nlag // FRAME_LEN
     if J == 0:
         return None
@@ -191,5 +340,6 @@ def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int 
     return verdict(score[0], origin[0], rank[0], lo, plist, J)
 
 
-__all__ = ["DECOY_LABEL", "Presence", "check_decoys", "check_phases", "check_reach", "clip_spans", "decoy_keys", "fold_model", "hop_model",
-           "pick_phases", "presence_model", "score_model", "slots", "verdict"]
+__all__ = ["DECOY_LABEL", "Presence", "check_decoys", "check_drift", "check_phases", "check_reach", "clip_spans", "decoy_keys", "drift_verdict",
+           "fold_model", "hop_model", "pick_hypotheses", "pick_phases", "presence_model", "score_model", "skew_table", "slots", "verdict",
+           "warp_fold_model", "warp_score_model"]
