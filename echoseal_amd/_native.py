@@ -115,6 +115,18 @@ if set(WARP_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES)) or set(WA
     raise NativeError(f"{WARP_HEADER_PATH} declares a name another header already has")
 globals().update(WARP_CONSTANTS)         # ES_WARP_HB
 
+# The companion header of the presence test over records anywhere in a table of rows, bound the same way into three more tables.
+LIVE_PRESENCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_live_presence.h")
+try:
+    with open(LIVE_PRESENCE_HEADER_PATH) as _f:
+        LIVE_PRESENCE_DECLARATIONS, LIVE_PRESENCE_SIGNATURES, LIVE_PRESENCE_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{LIVE_PRESENCE_HEADER_PATH}: the live presence calls are bound from this header ({e})") from None
+if (set(LIVE_PRESENCE_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set(WARP_SIGNATURES))
+        or set(LIVE_PRESENCE_CONSTANTS) & (set(CONSTANTS) | set(PRESENCE_CONSTANTS) | set(WARP_CONSTANTS))):
+    raise NativeError(f"{LIVE_PRESENCE_HEADER_PATH} declares a name another header already has")
+globals().update(LIVE_PRESENCE_CONSTANTS)
+
 _lib = None
 
 
@@ -136,7 +148,7 @@ def load() -> ctypes.CDLL:
     if got != CONSTANTS["ES_ABI_VERSION"]:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
-    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

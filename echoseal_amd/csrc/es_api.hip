@@ -1132,6 +1132,59 @@ int es_warp_score_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64
                                 n_origins, score_dev, origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
 }
 
+// ---- presence over records anywhere in a table of rows (include/echoseal_live_presence.h) ----
+// what both _at calls refuse of the table: no "four rows per record" here, records name their rows and may share them
+static const char* presence_table(int64_t rows, int64_t stride, int64_t B)
+{
+    return (rows < 0 || stride < 0 || B < 0) ? ": negative count"
+           : (stride > 0x7FFFFFFFll || rows > 0x7FFFFFFFll) ? ": rows or stride above 2^31 - 1"
+           : B > ((int64_t)1 << 40) ? ": more than 2^40 records" : nullptr;
+}
+
+int es_warp_fold_at_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64_t stride, const int64_t* row_dev, const int64_t* col_dev,
+                          const int32_t* nlag_dev, int64_t B, const int32_t* warp_dev, const int32_t* nwarp_dev, const int32_t* nslot_dev,
+                          int64_t D, int64_t Jw, double* fold_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_table(rows, stride, B)) return fail(ctx, ES_EINVAL, (std::string("es_warp_fold_at_batch") + why).c_str());
+    if (D < 0 || Jw < 0) return fail(ctx, ES_EINVAL, "es_warp_fold_at_batch: negative count");
+    if (B == 0 || D == 0) return ES_OK;
+    if (D > 0x7FFFFFFFll / 5 || B > 0x7FFFFFFFll / 5 / D)
+        return fail(ctx, ES_EINVAL, "es_warp_fold_at_batch: more than 2^31 - 1 blocks of five per (record, row) in one call");
+    const bool read = Jw > 0 && rows > 0 && stride >= ES_FRAME_LEN;         // otherwise J == 0 everywhere: neither rows nor offsets are read
+    if (!row_dev || !col_dev || !nlag_dev || !nwarp_dev || !nslot_dev || !fold_dev || (read && (!corr_dev || !warp_dev)))
+        return fail(ctx, ES_EINVAL, "es_warp_fold_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_warp_fold_at(ctx, corr_dev, rows, stride, row_dev, col_dev, nlag_dev, B, es_warp_tab{warp_dev, nwarp_dev, nslot_dev, D, Jw},
+                                  fold_dev, (hipStream_t)stream);
+}
+
+int es_warp_score_at_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64_t stride, const int64_t* row_dev, const int64_t* col_dev,
+                           const int32_t* nlag_dev, int64_t B, const int32_t* warp_dev, const int32_t* nwarp_dev, const int32_t* nslot_dev,
+                           int64_t D, int64_t Jw, const int32_t* hyp_dev, int64_t H, const uint8_t* hop_dev, int64_t K, int64_t HR,
+                           int64_t Ccols, const int32_t* hop_row_dev, int64_t n_origins, double* score_dev, int64_t* origin_dev,
+                           int32_t* rank_dev, void* scratch_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_table(rows, stride, B)) return fail(ctx, ES_EINVAL, (std::string("es_warp_score_at_batch") + why).c_str());
+    if (D < 0 || Jw < 0 || K < 0 || Ccols < 0 || n_origins < 0) return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: negative count");
+    if (H < 1 || H > 0x7FFFFFFFll || D > 0x7FFFFFFFll) return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: H must be in 1 .. 2^31 - 1, D below 2^31");
+    if (HR < 1 || HR > 0x7FFFFFFFll) return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: HR must be in 1 .. 2^31 - 1");
+    const int64_t NB = n_origins / ES_HOP_ORIGINS + (n_origins % ES_HOP_ORIGINS != 0);
+    if (Ccols < n_origins + Jw - 1) return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: Ccols < n_origins + Jw - 1");
+    if (B == 0 || K == 0) return ES_OK;
+    if (K > 0x7FFFFFFFll / B || (NB > 0 && B * K > 0x7FFFFFFFll / NB))
+        return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: more than 2^31 - 1 blocks of (record, key, 256 origins) in one call");
+    const bool scored = NB > 0 && Jw > 0 && rows > 0 && stride >= ES_FRAME_LEN; // otherwise J == 0 everywhere: no block reads rows, entries or hop bytes
+    if (!score_dev || !origin_dev || !rank_dev ||
+        (NB > 0 && (!scratch_dev || !row_dev || !col_dev || !nlag_dev || !nslot_dev || !hop_row_dev)) ||
+        (scored && (!corr_dev || !nwarp_dev || !hyp_dev || !hop_dev || (D > 0 && !warp_dev))))
+        return fail(ctx, ES_EINVAL, "es_warp_score_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_warp_score_at(ctx, corr_dev, rows, stride, row_dev, col_dev, nlag_dev, B, es_warp_tab{warp_dev, nwarp_dev, nslot_dev, D, Jw}, hyp_dev,
+                                   H, hop_dev, K, HR, Ccols, hop_row_dev, n_origins, score_dev, origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
+}
+
 // What both acquisition calls refuse and when they have nothing to do: -> ES_EINVAL, ES_OK with *work = false, or ES_OK with *work = true
 // and the exact grid of one wave per (record, tile of 64 high halves) within 2^31 - 1 blocks.
 static int acquire_span(es_ctx* ctx, const char* who, int64_t P, int64_t ctr_lo, int64_t ctr_hi, bool* work)

@@ -9,8 +9,9 @@
 //
 // Last, the presence test, which reads the same hop rows: the keyless fold of a clip's correlation rows over the 1215-sample frame grid and
 // the score of every (key, counter origin, phase) against them (es_phase_fold_kernel, es_hop_score_kernel), and both again
-// on a grid that follows clock drift, a table of per-slot offsets (es_warp_fold_kernel, es_warp_score_kernel) -- the only
-// float64 work in this file, every sum in one lane from its first slot to its last.
+// on a grid that follows clock drift, a table of per-slot offsets (es_warp_fold_kernel, es_warp_score_kernel), and those two
+// over records that lie anywhere in a table of rows, such as the windows of live streams in a monitor's history (es_warp_fold_at_kernel,
+// es_warp_score_at_kernel) -- the only float64 work in this file, every sum in one lane from its first slot to its last.
 //
 // Integer work otherwise.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
@@ -398,6 +399,19 @@ __device__ __forceinline__ double band_max(const double* __restrict__ v, long lo
     return m;
 }
 
+// the same for a record whose four band rows lie anywhere: o[band] = the element offset of the row of BAND_PLAN band `band` from v
+struct band_rows { long long o[4]; };
+__device__ __forceinline__ double band_max(const double* __restrict__ v, const band_rows& r)
+{
+    double m = v[r.o[0]];
+    #pragma unroll
+    for (int band = 1; band < 4; ++band) {
+        const double c = v[r.o[band]];
+        m = c > m ? c : m;
+    }
+    return m;
+}
+
 // fold[b][phi] = sum over slots j of the largest of the four band rows at lag phi + 1215 j: one lane per (clip, phase), five blocks per clip
 __global__ __launch_bounds__(256) void es_phase_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
         double* __restrict__ fold_p)
@@ -518,18 +532,20 @@ __device__ __forceinline__ long long warp_lag(long long j, int w, long long n)
     return (c >= 0 && c + (ES_FRAME_LEN - 1) < n) ? c : -1;
 }
 
-// fold[b][d][phi] = sum over slots j of band_max at lag phi + 1215 j + warp[b][d][j], -inf for an unusable row: one lane per (clip, row,
-// phase), five blocks per (clip, row); the row's offsets pass through LDS 256 slots at a time, already turned into first lags
-__global__ __launch_bounds__(256) void es_warp_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
-        es_warp_tab tab, double* __restrict__ fold_p)
+// fold[b][d][phi] = sum over slots j of band_max at lag phi + 1215 j + warp[b][d][j], -inf for an unusable row: one lane per (record, row,
+// phase), five blocks per (record, row) = item bd of the launch; the row's offsets pass through LDS 256 slots at a time, already turned into
+// first lags.  The one body of es_warp_fold_kernel and es_warp_fold_at_kernel: corr_p + lag0 + phi is lag 0 of phase phi, r says where the four
+// band rows lie from there (ROWS: a clip's stride, its rows being 4 b .. 4 b + 3, or the band_rows of a record anywhere), n is the record's
+// lag count -- nothing but lags [0, n) of those rows is read.
+template <typename ROWS>
+__device__ __forceinline__ void warp_fold_body(const double* __restrict__ corr_p, long long lag0, const ROWS& r, long long n, long long b, long long d,
+        long long bd, int phi, const es_warp_tab& tab, double* __restrict__ fold_p)
 {
     __shared__ long long lag[256];
     const int tid = threadIdx.x;
-    const long long bd = blockIdx.x / 5, b = bd / tab.D, d = bd - b * tab.D;
-    const int phi = (int)(blockIdx.x - bd * 5) * 256 + tid;
-    const long long n = clip_nlag(nlag_p, b, stride), J = warp_slots(tab, b, n);
+    const long long J = warp_slots(tab, b, n);
     g_ci32* wrow = (g_ci32*)tab.warp + bd * tab.Jw;
-    const double* row = corr_p + 4 * b * stride + phi;
+    const double* row = corr_p + lag0 + phi;
     bool usable = d < ((g_ci32*)tab.nwarp)[b];                                            // block-uniform, like everything the loop branches on
     double acc = 0.0;
     #pragma unroll 1
@@ -541,10 +557,48 @@ __global__ __launch_bounds__(256) void es_warp_fold_kernel(const double* __restr
         if (usable && phi < ES_FRAME_LEN) {
             #pragma unroll 1
             for (int j = 0; j < nt; ++j)
-                acc = acc + band_max(row + lag[j], stride);
+                acc = acc + band_max(row + lag[j], r);
         }
     }
     if (phi < ES_FRAME_LEN) fold_p[bd * ES_FRAME_LEN + phi] = usable ? acc : -__builtin_inf();
+}
+
+__global__ __launch_bounds__(256) void es_warp_fold_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        es_warp_tab tab, double* __restrict__ fold_p)
+{
+    const long long bd = blockIdx.x / 5, b = bd / tab.D, d = bd - b * tab.D;
+    const int phi = (int)(blockIdx.x - bd * 5) * 256 + (int)threadIdx.x;
+    warp_fold_body(corr_p, 4 * b * stride, stride, clip_nlag(nlag_p, b, stride), b, d, bd, phi, tab, fold_p);
+}
+
+// Record b of an _at call (include/echoseal_live_presence.h): its four rows are row[b][0 .. 3] of corr [rows][stride], its lag 0 column col[b].
+// -> its lag count, nlag[b] clamped to [0, stride - col], and r.o[band] = row[b][band] * stride + col; 0 and zeros for a record that is not
+// addressable (a row outside [0, rows) or a column outside [0, stride]).  Decided here, from the three arrays alone, before any row is read.
+struct es_at_rec { const long long* row; const long long* col; const int32_t* nlag; long long rows, stride; };
+__device__ __forceinline__ long long at_record(const es_at_rec& at, long long b, band_rows& r)
+{
+    const long long col = ((g_ci64*)at.col)[b];
+    bool ok = col >= 0 && col <= at.stride;
+    long long q[4];
+    #pragma unroll
+    for (int band = 0; band < 4; ++band) {
+        q[band] = ((g_ci64*)at.row)[4 * b + band];
+        ok = ok && q[band] >= 0 && q[band] < at.rows;
+    }
+    #pragma unroll
+    for (int band = 0; band < 4; ++band) r.o[band] = ok ? q[band] * at.stride + col : 0;   // (rows * stride < 2^62: the entry point's check)
+    const long long n = ((g_ci32*)at.nlag)[b], most = ok ? at.stride - col : 0;
+    return n < 0 ? 0 : (n > most ? most : n);
+}
+
+// es_warp_fold_kernel over records that lie anywhere in the table of rows
+__global__ __launch_bounds__(256) void es_warp_fold_at_kernel(const double* __restrict__ corr_p, es_at_rec at, es_warp_tab tab, double* __restrict__ fold_p)
+{
+    const long long bd = blockIdx.x / 5, b = bd / tab.D, d = bd - b * tab.D;
+    const int phi = (int)(blockIdx.x - bd * 5) * 256 + (int)threadIdx.x;
+    band_rows r;
+    const long long n = at_record(at, b, r);
+    warp_fold_body(corr_p, 0, r, n, b, d, bd, phi, tab, fold_p);
 }
 
 // es_hop_score_kernel along the table, the list taken HB entries at a time.  A lane's hop window is the same for every entry, so the slot
@@ -552,21 +606,18 @@ __global__ __launch_bounds__(256) void es_warp_fold_kernel(const double* __restr
 // values of one (slot, band) side by side), a hop byte is read once per block, and acc[e] still takes its terms in ascending slot order.
 // An entry is dropped where it names no usable row or no phase: e_bad is raised by whichever lane finds a slot of its row outside the
 // clip, and that slot is not read.  HB = 1 is the loop of es_hop_score_kernel itself.
-template <int HB>
-__global__ __launch_bounds__(256) void es_warp_score_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
-        es_warp_tab tab, const int32_t* __restrict__ hyp_p, int H, const uint8_t* __restrict__ hop_p, long long K, long long Ccols,
-        long long n_origins, long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+// The one body of es_warp_score_kernel and es_warp_score_at_kernel.  The staging lane tid & 3 owns one band.  Without AT `rows` stands on
+// row 4 b of a clip and the lane's row is (tid & 3) * stride further; with AT `rows` stands on lag 0 of the lane's own row, wherever the
+// record has it, and stride is not read.  n and J are the record's lags and slots, hop the lane's window (column 0 = its origin).
+template <int HB, bool AT>
+__device__ __forceinline__ void warp_score_body(const double* __restrict__ rows, long long stride, long long n, long long J, g_cu8* hop, bool live, long long origin,
+        long long b, const es_warp_tab& tab, const int32_t* __restrict__ hyp_p, int H, double* __restrict__ sc_score, long long* __restrict__ sc_origin,
+        long long* __restrict__ sc_rank)
 {
     __shared__ __attribute__((aligned(16))) double vals[HS_TILE * 4 * HB];
     __shared__ hs_best red[HS_ORIGINS];
     __shared__ int e_row[HB], e_phi[HB], e_bad[HB];
     const int tid = threadIdx.x;
-    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
-    const long long origin = chunk * HS_ORIGINS + tid;
-    const bool live = origin < n_origins;
-    const long long n = clip_nlag(nlag_p, b, stride), J = warp_slots(tab, b, n);
-    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + (live ? origin : 0);                         // columns origin .. origin + J - 1 < Ccols: J <= Jw
-    const double* rows = corr_p + 4 * b * stride;
     hs_best best = {-__builtin_inf(), -1, -1};
     #pragma unroll 1
     for (int h0 = 0; h0 < H && J > 0; h0 += HB) {
@@ -592,7 +643,7 @@ __global__ __launch_bounds__(256) void es_warp_score_kernel(const double* __rest
                 for (int e = 0; e < HB; ++e) {
                     const int d = e_row[e];
                     const long long c = d < 0 ? -1 : warp_lag(j, ((g_ci32*)tab.warp)[(b * tab.D + d) * tab.Jw + j], n);
-                    if (c >= 0) vals[tid * HB + e] = rows[(tid & 3) * stride + c + e_phi[e]];
+                    if (c >= 0) vals[tid * HB + e] = AT ? rows[c + e_phi[e]] : rows[(tid & 3) * stride + c + e_phi[e]];
                     else if (d >= 0) e_bad[e] = 1;
                 }
             }
@@ -615,6 +666,44 @@ __global__ __launch_bounds__(256) void es_warp_score_kernel(const double* __rest
         }
     }
     hs_block_best(red, best, tid, sc_score, sc_origin, sc_rank);
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void es_warp_score_kernel(const double* __restrict__ corr_p, long long stride, const int32_t* __restrict__ nlag_p,
+        es_warp_tab tab, const int32_t* __restrict__ hyp_p, int H, const uint8_t* __restrict__ hop_p, long long K, long long Ccols,
+        long long n_origins, long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * HS_ORIGINS + tid;
+    const bool live = origin < n_origins;
+    const long long n = clip_nlag(nlag_p, b, stride), J = warp_slots(tab, b, n);
+    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + (live ? origin : 0);                         // columns origin .. origin + J - 1 < Ccols: J <= Jw
+    warp_score_body<HB, false>(corr_p + 4 * b * stride, stride, n, J, hop, live, origin, b, tab, hyp_p, H, sc_score, sc_origin, sc_rank);
+}
+
+// es_warp_score_kernel over records that lie anywhere in the table of rows; the pair (b, k) reads hop row hop_row[b] of key k's HR hop rows.
+// A hop row index outside [0, HR) leaves the record no slot: nothing of it is read, nothing is scored.
+template <int HB>
+__global__ __launch_bounds__(256) void es_warp_score_at_kernel(const double* __restrict__ corr_p, es_at_rec at, es_warp_tab tab,
+        const int32_t* __restrict__ hyp_p, int H, const uint8_t* __restrict__ hop_p, long long K, long long HR, long long Ccols,
+        const int32_t* __restrict__ hop_row_p, long long n_origins, long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin,
+        long long* __restrict__ sc_rank)
+{
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * HS_ORIGINS + tid;
+    const bool live = origin < n_origins;
+    band_rows r;
+    const long long n = at_record(at, b, r);
+    long long mine = r.o[0];                                                              // the staging lane tid & 3 owns one band: one row base per lane
+    #pragma unroll
+    for (int band = 1; band < 4; ++band) mine = (tid & 3) == band ? r.o[band] : mine;
+    const long long hr = ((g_ci32*)hop_row_p)[b];
+    const bool hashop = hr >= 0 && hr < HR;
+    const long long J = hashop ? warp_slots(tab, b, n) : 0;
+    g_cu8* hop = (g_cu8*)hop_p + (k * HR + (hashop ? hr : 0)) * Ccols + (live ? origin : 0); // columns origin .. origin + J - 1 < Ccols: J <= Jw
+    warp_score_body<HB, true>(corr_p + mine, 0, n, J, hop, live, origin, b, tab, hyp_p, H, sc_score, sc_origin, sc_rank);
 }
 
 }  // namespace
@@ -733,5 +822,26 @@ int es_launch_warp_score(es_ctx* ctx, const double* corr, int64_t stride, const 
     if (sc.slots > 0)
         if (const int rc = es_launch(ctx, es_warp_score_kernel<WS_HB>, (unsigned)sc.slots, 256, 0, st, corr, (long long)stride, nlag, tab, hyp, (int)H,
                                      hop, (long long)K, (long long)Ccols, (long long)n_origins, sc.NB, sc.score, sc.origin, sc.rank)) return rc;
+    return es_launch_hop_best(ctx, sc, score, origin, rank, st);
+}
+
+// the same over records that lie anywhere in a table of rows (include/echoseal_live_presence.h): exact grids, checked by the entry points
+int es_launch_warp_fold_at(es_ctx* ctx, const double* corr, int64_t rows, int64_t stride, const int64_t* row, const int64_t* col, const int32_t* nlag,
+                           int64_t B, const es_warp_tab& tab, double* fold, hipStream_t st)
+{
+    return es_launch(ctx, es_warp_fold_at_kernel, (unsigned)(B * tab.D * 5), 256, 0, st, corr,
+                     es_at_rec{(const long long*)row, (const long long*)col, nlag, (long long)rows, (long long)stride}, tab, fold);
+}
+
+int es_launch_warp_score_at(es_ctx* ctx, const double* corr, int64_t rows, int64_t stride, const int64_t* row, const int64_t* col, const int32_t* nlag,
+                            int64_t B, const es_warp_tab& tab, const int32_t* hyp, int64_t H, const uint8_t* hop, int64_t K, int64_t HR, int64_t Ccols,
+                            const int32_t* hop_row, int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st)
+{
+    const hs_scratch sc(scratch, B, K, n_origins);
+    if (sc.slots > 0)
+        if (const int rc = es_launch(ctx, es_warp_score_at_kernel<WS_HB>, (unsigned)sc.slots, 256, 0, st, corr,
+                                     es_at_rec{(const long long*)row, (const long long*)col, nlag, (long long)rows, (long long)stride}, tab, hyp, (int)H,
+                                     hop, (long long)K, (long long)HR, (long long)Ccols, hop_row, (long long)n_origins, sc.NB, sc.score, sc.origin,
+                                     sc.rank)) return rc;
     return es_launch_hop_best(ctx, sc, score, origin, rank, st);
 }

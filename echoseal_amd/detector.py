@@ -328,8 +328,15 @@ class WatermarkDetector:
         session_nonce and the traces are not touched.  ValueError before any engine exists: a span outside [0, 2^32], reversed or
         reaching past 2^32 from its last origin, phases outside 1 .. 1215, decoys < 0, a bad ctr0, a drift_ppm that is negative, not
         finite or no number, or that skews some clip by a whole frame or leaves it no slot."""
+        return [None if r is None else r[0] for r in self._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, None)]
+
+    def _presence_clips(self, clips, fs_in, ctr0, span, phases, decoys, drift_ppm, keys) -> list:
+        """presence_batch under each of `keys` (None: this detector's key alone) -> per clip None or one Presence per key.  The checks,
+        the front and the launches are the same whatever the keys: the fold and the hypothesis list are keyless, so one front and one
+        score call over the ring keys + decoys serve them all (presence.search)."""
         from . import presence as pr
         import torch
+        clips = list(clips)
         fs_list = rate_list(fs_in, len(clips))
         P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
         spans = pr.clip_spans(ctr0, span, len(clips))
@@ -339,6 +346,7 @@ class WatermarkDetector:
             if drift > 0:
                 pr.skew_table(samples - (PRE_L - 1), drift)
         out: list = [None] * len(clips)
+        n_own = 1 if keys is None else len(keys)
         band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
         nb = band_ids.size
         for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
@@ -353,56 +361,21 @@ class WatermarkDetector:
                 else:
                     corr = eng.xcorr(eng.bpf(x[:, :M], bid), bid)
                 nlag = np.array(sizes, np.int64) - (PRE_L - 1)
-                if drift > 0:
-                    self._presence_drift(eng, corr, nlag, drift, P, R, lo, hi, [ids[i] for i in la.idx], out)
-                    continue
-                J = nlag // FRAME_LEN
-                if not J.max():
-                    continue
-                fold = eng.phase_fold(corr, nlag).cpu().numpy()
-                plists = [pr.pick_phases(f, P) for f in fold]
-                ring = self._presence_ring(R)
-                jmax = corr.shape[1] // FRAME_LEN                            # the slots the score call sizes the hop table for
-                hop = eng.hop_window(ring, [min(lo, CTR_END - 1)], max(hi - lo + jmax - 1, 0))
-                score, origin, rank = (t.cpu().numpy() for t in eng.hop_score(corr, nlag, np.array(plists, np.int32), hop, hi - lo))
-                if self._presence_rows is not None:
+                res = pr.search(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P) if n_own else [None] * len(sizes)
+                if self._presence_rows is not None and any(r is not None for r in res):
                     self._presence_rows.append(([ids[i] for i in la.idx], corr.cpu().numpy(), nlag))
                 for k, i in enumerate(la.idx):
-                    if J[k]:
-                        out[ids[i]] = pr.verdict(score[k], origin[k], rank[k], lo, plists[k], int(J[k]))
+                    out[ids[i]] = res[k]
         return out
 
-    def _presence_drift(self, eng, corr, nlag, drift: float, P: int, R: int, lo: int, hi: int, ids: list, out: list) -> None:
-        """One launch of presence_batch with a drift search: the skew tables of the clips packed [B][Dmax][Jmax] (zeros past a clip's
-        own rows and slots: nwarp and nslot say where they end), the fold along every row, each clip's (row, phase) list, and the score."""
-        from . import presence as pr
-        tabs = [pr.skew_table(n, drift) for n in nlag.tolist()]
-        J = np.array([t[1] for t in tabs], np.int32)
-        if J.max():
-            nwarp = np.array([len(t[0]) for t in tabs], np.int32)
-            warp = np.zeros((len(tabs), int(nwarp.max()), int(J.max())), np.int32)
-            for k, (_, j, w) in enumerate(tabs):
-                warp[k, :w.shape[0], :j] = w
-            warp, nwarp_d, nslot_d = dev(eng, warp, np.int32), dev(eng, nwarp, np.int32), dev(eng, J, np.int32)
-            fold = eng.warp_fold(corr, nlag, warp, nwarp_d, nslot_d).cpu().numpy()
-            hyps = [pr.pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
-            hyp = np.full((len(tabs), P, 2), -1, np.int32)                  # a list is P entries long; a shorter one ends in entries that name nothing
-            for k, h in enumerate(hyps):
-                hyp[k, :len(h)] = h
-            hop = eng.hop_window(self._presence_ring(R), [min(lo, CTR_END - 1)], max(hi - lo + int(J.max()) - 1, 0))
-            score, origin, rank = (t.cpu().numpy() for t in eng.warp_score(corr, nlag, warp, nwarp_d, nslot_d, hyp, hop, hi - lo))
-            for k, i in enumerate(ids):
-                if J[k]:
-                    out[i] = pr.drift_verdict(score[k], origin[k], rank[k], lo, hyps[k], tabs[k][0], int(J[k]))
-            if self._presence_rows is not None:
-                self._presence_rows.append((ids, corr.cpu().numpy(), nlag))
-
-    def _presence_ring(self, decoys: int):
-        """The ring [this detector's key] + the first `decoys` public decoy keys, derived once per engine and count."""
+    def _presence_ring(self, decoys: int, keys=None):
+        """The ring [own keys] + the first `decoys` public decoy keys (keys None: this detector's key alone), derived once per engine,
+        count and key list."""
         from .presence import decoy_keys
         eng = self.engine
-        if self._decoy_ring is None or self._decoy_ring[0] is not eng or self._decoy_ring[1] != decoys:
-            self._decoy_ring = (eng, decoys, eng.keyring([self._band_key] + decoy_keys(decoys)))
+        own = (self._band_key,) if keys is None else tuple(bytes(k) for k in keys)
+        if self._decoy_ring is None or self._decoy_ring[0] is not eng or self._decoy_ring[1] != (decoys, own):
+            self._decoy_ring = (eng, (decoys, own), eng.keyring(list(own) + decoy_keys(decoys)))
         return self._decoy_ring[2]
 
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
@@ -757,6 +730,21 @@ class LiveMonitor(LiveTable):
                     pass
             out.append(acq)
         return out
+
+    def presence(self, streams=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> list:
+        """WatermarkDetector.presence on the current window [w0, n) of each named stream (None: every open stream), with no new samples:
+        -> per stream a presence.Presence, or None for a window without one whole 1215-sample slot.  The window's correlation rows are
+        the table's own: nothing but a few small tables is uploaded, no band-pass and no correlation runs again.  A stream
+        with a counter origin searches the two counters its window's first frame can carry (presence.live_span); one without searches
+        `span`, read as absolute counters of the window's first frame.  Presence.ctr is the counter of the window's first whole frame,
+        phase its first sample relative to the window, ctr0 = acquire.origin_of(ctr, phase, w0).  drift_ppm as for
+        WatermarkDetector.presence, over the window.
+        Per call ONE fold launch over all named streams, ONE download and pick, ONE hop window over the ring [key] + decoys with a hop
+        row per distinct span base, and ONE score launch per group of equal span width (streams with an origin, streams without).
+        The verdict is statistical, not authenticated: it never sets a stream's origin, and the table, the session nonces
+        and the traces are not touched.  ValueError before any GPU work: a bad span, phases, decoys or drift_ppm, a span that reaches
+        past 2^32 from its last origin, a stream that is closed, named twice or outside the table."""
+        return [None if r is None else r[0] for r in self._presence(self._det, None, streams, span, phases, decoys, drift_ppm)]
 
     def session_nonce(self, stream: int) -> bytes | None:
         """The session nonce stream `stream` is locked to (None: nothing accepted yet)."""

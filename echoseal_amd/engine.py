@@ -713,6 +713,56 @@ class RxEngine(TxChain, MonitorChain):
                    hop, K, hop.shape[1], n_origins, score, origin, rank, scratch if scratch.numel() else None)
         return score, origin, rank
 
+    # ------------------------------------------------------------------ presence of records anywhere in a table of rows (DESIGN 4.25;
+    # include/echoseal_live_presence.h)
+    def _presence_records(self, corr: torch.Tensor, rows4, col, nlag):
+        """The table of rows and the records of an _at call, checked: -> (corr, rows, stride, rows4 int64 [B, 4], col int64 [B], nlag int32
+        [B], B).  What the arrays hold is the kernels' to judge: a record that names a row or a column outside the table has no lags."""
+        if corr.dim() != 2 or corr.dtype != torch.float64 or not corr.is_contiguous() or corr.device != self.device:
+            raise ValueError("corr must be a contiguous float64 [rows, stride] tensor on the engine's device")
+        rows4 = self._dev(rows4, torch.int64)
+        col, nlag = self._dev(col, torch.int64).reshape(-1), self._dev(nlag, torch.int32).reshape(-1)
+        B = nlag.numel()
+        if rows4.dim() != 2 or tuple(rows4.shape) != (B, 4) or col.numel() != B:
+            raise ValueError("rows4: int [B, 4], the row of each band of each record; col, nlag: one value per record")
+        return corr, corr.shape[0], corr.shape[1], rows4, col, nlag, B
+
+    def warp_fold_at(self, corr: torch.Tensor, rows4, col, nlag, warp, nwarp, nslot) -> torch.Tensor:
+        """warp_fold over records that lie anywhere in a table of rows (es_warp_fold_at_batch; presence.window_rows + warp_fold_model is the
+        host twin).  corr float64 [rows, stride]; rows4 int [B, 4]: rows4[b, band] the row that holds BAND_PLAN band `band` of record b;
+        col [B] the column of its lag 0; nlag [B] its lags (clamped to [0, stride - col]; a record with a row or a column outside the table
+        has none).  Nothing outside columns [col, col + nlag) of a record's own rows is read; records may share rows and overlap.  warp,
+        nwarp, nslot as for warp_fold -> fold float64 [B, D, 1215]."""
+        corr, rows, stride, rows4, col, nlag, B = self._presence_records(corr, rows4, col, nlag)
+        warp, nwarp, nslot, D, Jw = self._warp_table(warp, nwarp, nslot, B)
+        fold = torch.empty((B, D, nat.ES_FRAME_LEN), dtype=torch.float64, device=self.device)
+        self._call("es_warp_fold_at_batch", corr, rows, stride, rows4, col, nlag, B, warp if warp.numel() else None, nwarp, nslot, D, Jw, fold)
+        return fold
+
+    def warp_score_at(self, corr: torch.Tensor, rows4, col, nlag, warp, nwarp, nslot, hyp, hop: torch.Tensor, hop_row, n_origins: int):
+        """warp_score over records that lie anywhere in a table of rows (es_warp_score_at_batch; presence.window_rows + warp_score_model on
+        the record's hop row is the host twin).  corr, rows4, col, nlag as for warp_fold_at; warp, nwarp, nslot, hyp as for warp_score; hop
+        uint8 [K, HR, Ccols] as hop_window gives it ([K, Ccols]: one hop row), Ccols >= n_origins + Jw - 1; hop_row int [B]: record b
+        reads hop row hop_row[b] of every key, one outside [0, HR) scores nothing -> (score float64 [B, K], origin int64 [B, K], rank
+        int32 [B, K])."""
+        corr, rows, stride, rows4, col, nlag, B = self._presence_records(corr, rows4, col, nlag)
+        warp, nwarp, nslot, D, Jw = self._warp_table(warp, nwarp, nslot, B)
+        hyp = self._dev(hyp, torch.int32)
+        if hyp.dim() != 3 or hyp.shape[0] != B or hyp.shape[2] != 2:
+            raise ValueError("hyp: int [B, H, 2], a list of (row, phase) per record")
+        if hop.dim() == 2:
+            hop = hop[:, None, :]
+        if hop.dim() != 3 or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [K, HR, Ccols]")
+        HR, Ccols = hop.shape[1], hop.shape[2]
+        hop_row = self._dev(hop_row, torch.int32).reshape(-1)
+        if hop_row.numel() != B:
+            raise ValueError("hop_row: one hop row index per record")
+        hop, K, n_origins, score, origin, rank, scratch = self._score_io(hop.reshape(hop.shape[0], HR * Ccols), B, n_origins)
+        self._call("es_warp_score_at_batch", corr, rows, stride, rows4, col, nlag, B, warp if warp.numel() else None, nwarp, nslot, D, Jw, hyp,
+                   hyp.shape[1], hop, K, HR, Ccols, hop_row, n_origins, score, origin, rank, scratch if scratch.numel() else None)
+        return score, origin, rank
+
     def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):
         """Which counters of `span` each header record may belong to (es_acquire_mask_batch; acquire.mask_model is the host twin).
         Record p = (ring row key_idx[p] int32, ok[p] uint8, lo16[p] int32, band[p] uint8), as one header call gives them

@@ -146,6 +146,20 @@ class WatermarkIdentifier:
                                origins=[origins[i] for i in part.idx])
         return (out, traces) if self.trace else out
 
+    def presence(self, audio, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0):
+        return self.presence_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys,
+                                   drift_ppm=drift_ppm)[0]
+
+    def presence_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> list:
+        """WatermarkDetector.presence_batch under every key at once -> per clip None (no whole 1215-sample slot) or a list with one
+        presence.Presence per key: entry k is field for field what WatermarkDetector(keys[k]).presence_batch gives for the clip.  The
+        fold and the hypothesis list are keyless, so the front and the launches are the single detector's, with the ring keys + decoys
+        in place of [key] + decoys: entry k has score = key row k and null = the decoy rows.
+        Each entry keeps its own bound of 1 / (decoys + 1) on a false alarm.  The chance that SOME key of the N is flagged on unmarked
+        audio is bounded by N / (decoys + 1), not 1 / (decoys + 1): ask for decoys accordingly.  Arguments and ValueErrors are
+        WatermarkDetector.presence_batch's."""
+        return self._det._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, self.keys)
+
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
                      memo_slots: int | None = None, ctr0=None) -> "LiveIdentifier":
         """A monitor of n live streams that says, per push and stream, which of this identifier's keys marks the stream's last window_s
@@ -440,6 +454,16 @@ class LiveIdentifier(LiveTable):
         elif ids.size:
             self.engine.monitor_step(tab, ids, arrs)                        # no key: the streams still move on
         return (out, traces) if self._trace else out
+
+    def presence(self, streams=None, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> list:
+        """LiveMonitor.presence under every key at once -> per stream None (no whole slot in its window) or a list with one
+        presence.Presence per key: entry k is field for field what a LiveMonitor of key k gives on the same table.  The ring is
+        keys + decoys, entry k has score = key row k and null = the decoy rows; one fold launch and one score launch per group of
+        equal span width cover all streams and all keys.  With N keys the chance that SOME key is flagged on unmarked
+        audio is bounded by N / (decoys + 1), not 1 / (decoys + 1): ask for decoys accordingly.  Nothing is pushed, and neither the
+        table, the memo, the stats nor any origin is touched: the verdict is statistical and never sets a stream's origin.
+        ValueError before any GPU work, as for LiveMonitor.presence."""
+        return self._presence(self._id._det, self._id.keys, streams, span, phases, decoys, drift_ppm)
 
     def _hop_row0(self):
         """The window's hop table (counters from 0) at the width es_plan_at_batch asks for, as its hop row: depends on the keys and the

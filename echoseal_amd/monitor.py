@@ -365,6 +365,38 @@ class LiveTable:
     def _slots_changed(self, ids: np.ndarray, closed: bool) -> None:
         """Slots `ids` were just opened as fresh streams, or closed."""
 
+    def _presence(self, det, keys, streams, span, phases, decoys, drift_ppm) -> list:
+        """The presence test on the current window [w0, n) of each named stream (None: every open stream), read in
+        place in the table's correlation history, under each of `keys` (None: the key of `det` alone) -> per stream None (no whole
+        slot) or one Presence per key.  det: the WatermarkDetector whose engine and decoy ring are used.  Everything is checked on the
+        host before any GPU work; the table is only read."""
+        from . import presence as pr
+        from .acquire import check_span
+        tab = self.table
+        P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
+        span = check_span(span)
+        ids = np.flatnonzero(tab.live) if streams is None else monitor_ids(tab, streams)
+        n, base = tab.n_host[ids], tab.base_host[ids]
+        w0 = window_start(n, tab.window)
+        nlag = n - (PRE_L - 1) - w0                                         # the window's lags: column w0 - base onwards of the stream's rows
+        spans = []
+        for s, nl, w in zip(ids.tolist(), nlag.tolist(), w0.tolist()):
+            J = max(nl, 0) // nat.ES_FRAME_LEN
+            if J and drift > 0:
+                pr.skew_table(nl, drift)                                    # a skew of a whole frame, or no slot left: refused by name
+            o = int(tab.origin_host[s])
+            spans.append(pr.live_span(o, w, J) if o >= 0 else pr.check_reach(span, nl + PRE_L - 1))
+        out: list = [None] * int(ids.size)
+        some = np.flatnonzero(nlag >= nat.ES_FRAME_LEN)
+        n_own = 1 if keys is None else len(keys)
+        if some.size and n_own:
+            rows4 = np.array([pr.table_rows(tab.bands, s) for s in ids[some].tolist()], np.int64)
+            res = pr.search(det.engine, det._presence_ring(R, keys), n_own, tab.corr_hist, nlag[some], [spans[i] for i in some.tolist()], drift, P,
+                            at=(rows4, (w0 - base)[some]), pos0=w0[some])
+            for i, r in zip(some.tolist(), res):
+                out[i] = r
+        return out
+
 
     def position(self, stream: int) -> int:
         """Samples at fs_target stream `stream` has been verified over since it was opened: the samples received, for a stream at

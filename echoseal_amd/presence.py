@@ -11,6 +11,11 @@ Drift: a recording played by one device and captured by another ha
 offset of drift_ppm, every total skew e of -E .. E samples across the clip as a row of per-slot offsets; warp_fold_model /
 pick_hypotheses / warp_score_model are the fold, the pick and the score along those rows (es_warp_fold_batch, es_warp_score_batch;
 include/echoseal_warp.h), and presence_model(..., drift_ppm=...) the whole search.
+
+Live windows: a record may lie anywhere in a table of rows, such as a stream's window in a monitor table's correlation
+history.  window_rows cuts the block es_warp_fold_at_batch / es_warp_score_at_batch may read (include/echoseal_live_presence.h), so the
+models above are their twins too; live_span is the counter span of a stream with an origin, live_model the whole call for one stream.
+Last, `search`: the launches and verdicts behind every public presence call, the one function here that is handed an engine.
 """
 from __future__ import annotations
 
@@ -340,6 +345,144 @@ def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int 
     return verdict(score[0], origin[0], rank[0], lo, plist, J)
 
 
+# ---- records anywhere in a table of rows: the windows of live streams (include/echoseal_live_presence.h) ----
+def window_rows(corr, rows4, col, nlag) -> np.ndarray:
+    """The record of an _at call as a clip: float64 [4, n], row `band` = corr[rows4[band], col : col + n], n = nlag clamped to
+    [0, stride - col] -- and n = 0 where the record is not addressable (a row outside [0, rows) or col outside [0, stride]).  The
+    models above run on it unchanged: es_warp_fold_at_batch / es_warp_score_at_batch read exactly this block."""
+    corr = np.asarray(corr, np.float64)
+    if corr.ndim != 2:
+        raise ValueError("corr: float64 [rows, stride]")
+    rows4 = [int(r) for r in np.asarray(rows4, np.int64).reshape(-1)]
+    if len(rows4) != NBANDS:
+        raise ValueError("rows4: the row of each of the four bands")
+    col, stride = int(col), corr.shape[1]
+    ok = 0 <= col <= stride and all(0 <= r < corr.shape[0] for r in rows4)
+    n = min(max(int(nlag), 0), stride - col) if ok else 0
+    return np.stack([corr[r, col:col + n] for r in rows4]) if n else np.zeros((NBANDS, 0), np.float64)
+
+
+def live_span(origin: int, w0: int, J: int) -> tuple[int, int]:
+    """The counters the first whole frame of a window may carry, for a stream whose frame k carries counter origin + k and whose window
+    starts at absolute sample w0: slot 0 at phase phi <= 1214 carries origin + round((w0 + phi) / 1215) (the rounding of es_plan_at_batch
+    and acquire.origin_of), which is e or e + 1 for e = origin + (2 w0 + 1215) // 2430 -> (e, e + 2), hi lowered so that the window of
+    the last origin, hi - 1 + J - 1, is a counter (hi + J - 1 <= 2^32; never below lo)."""
+    e = min(int(origin) + (2 * int(w0) + FRAME_LEN) // (2 * FRAME_LEN), CTR_END)
+    return e, max(e, min(e + 2, CTR_END - max(int(J), 1) + 1))
+
+
+def table_rows(bands, stream: int) -> list[int]:
+    """rows4 of stream `stream` of a monitor table whose row 4 s + j holds band bands[j]: entry `band` = 4 s + j with bands[j] == band."""
+    place = {int(b): j for j, b in enumerate(np.asarray(bands).reshape(-1).tolist())}
+    if sorted(place) != list(range(NBANDS)):
+        raise ValueError("bands: the four band indices, each once")
+    return [NBANDS * int(stream) + place[band] for band in range(NBANDS)]
+
+
+def live_model(hist, stream: int, bands, base: int, w0: int, n: int, key: bytes, *, origin: int | None = None, span=(0, 4096), phases: int = 8,
+               decoys: int = 32, drift_ppm=0.0) -> Presence | None:
+    """LiveMonitor.presence for one stream, on the host, from the monitor table's correlation history `hist` [4 S, H] (column 0 = absolute
+    lag `base`): the window [w0, n) has lags [0, n - 62 - w0) from column w0 - base of the stream's four rows; the span is live_span
+    for a stream with a counter origin, else `span` read as absolute counters of the window's first frame; then presence_model.  The
+    result's ctr0 is acquire.origin_of(ctr, phase, w0): ctr is the counter of the window's first whole frame, phase is relative to the
+    window.  None where the window has no whole slot."""
+    nlag = int(n) - (PRE_L - 1) - int(w0)
+    J = max(nlag, 0) // FRAME_LEN
+    if J == 0:
+        return None
+    block = window_rows(hist, table_rows(bands, stream), int(w0) - int(base), nlag)
+    sp = check_reach(span, nlag + PRE_L - 1) if origin is None or int(origin) < 0 else live_span(origin, w0, J)
+    p = presence_model(block, nlag, key, span=sp, phases=phases, decoys=decoys, drift_ppm=drift_ppm)
+    if p is not None and p.ctr >= 0:
+        p.ctr0 = origin_of(p.ctr, p.phase, int(w0))
+    return p
+
+
+def _verdicts(n_own: int, score_row, origin_row, rank_row, make) -> list:
+    """One Presence per own key from a record's row of a score call over the ring [own keys] + decoys: entry k ranks key row k against
+    the decoy rows.  make(score, origin, rank) is verdict / drift_verdict with the record's own arguments bound."""
+    pick = lambda a, k: np.concatenate((a[k:k + 1], a[n_own:]))
+    return [make(pick(score_row, k), pick(origin_row, k), pick(rank_row, k)) for k in range(n_own)]
+
+
+def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=None, pos0=None) -> list:
+    """The launches and verdicts of every presence call (WatermarkDetector.presence_batch, WatermarkIdentifier.presence_batch,
+    LiveMonitor.presence, LiveIdentifier.presence) -> per record None (no whole slot) or a list of n_own Presence, one per own key.
+    ring: the device key ring [the n_own own keys] + decoys.  corr, nlag: the records' rows; spans: (lo, hi) per record.
+    at None: clips, record b = rows 4 b .. 4 b + 3 from column 0, all of ONE span -- the rigid grid (drift 0) through phase_fold /
+    hop_score, a drift search through warp_fold / warp_score, as presence_batch always called them.
+    at = (rows4 [B, 4], col [B]): records anywhere in the table `corr`, each with its own span -- ONE warp_fold_at over all of them (drift 0:
+    a one-row table of zeros), ONE download and pick, ONE hop_window with a hop row per distinct span base, and ONE warp_score_at per
+    group of equal span width.  pos0 [B]: the absolute first sample of each record, for the verdict's ctr0 (None: 0)."""
+    nlag = np.asarray(nlag, np.int64).reshape(-1)
+    B = nlag.size
+    out: list = [None] * B
+    spans = [(int(lo), int(hi)) for lo, hi in spans]
+    rigid = not drift > 0
+    tabs = None if rigid else [skew_table(n, drift) for n in nlag.tolist()]
+    J = np.maximum(nlag, 0) // FRAME_LEN if rigid else np.array([t[1] for t in tabs], np.int64)
+    if not B or not J.max():
+        return out
+    dev = lambda a, dt: _torch().from_numpy(np.ascontiguousarray(a, dt)).to(eng.device)
+    table = None
+    if rigid and at is None:
+        fold = eng.phase_fold(corr, nlag).cpu().numpy()
+        lists = [pick_phases(f, P) for f in fold]
+        jw = corr.shape[1] // FRAME_LEN                                     # the slots hop_score sizes the hop table for
+    else:
+        nwarp = np.ones(B, np.int32) if rigid else np.array([len(t[0]) for t in tabs], np.int32)
+        warp = np.zeros((B, int(nwarp.max()), int(J.max())), np.int32)      # zeros past a record's own rows and slots: nwarp and nslot say where they end
+        for k, t in enumerate(tabs or ()):
+            warp[k, :t[2].shape[0], :t[1]] = t[2]
+        table = (dev(warp, np.int32), dev(nwarp, np.int32), dev(J, np.int32))
+        fold = (eng.warp_fold(corr, nlag, *table) if at is None else eng.warp_fold_at(corr, at[0], at[1], nlag, *table)).cpu().numpy()
+        lists = [pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
+        jw = int(J.max())
+    bases = sorted({min(lo, CTR_END - 1) for lo, _ in spans})               # one hop row per distinct span base
+    hop = eng.hop_window(ring, bases, max(max(hi - lo for lo, hi in spans) + jw - 1, 0))
+    for width in sorted({hi - lo for lo, hi in spans}):
+        ids = [b for b, (lo, hi) in enumerate(spans) if hi - lo == width]
+        if at is None:
+            if len(ids) != B or len(bases) != 1:
+                raise ValueError("clips of one launch share one span")
+            if rigid:
+                res = eng.hop_score(corr, nlag, np.array(lists, np.int32), hop, width)
+            else:
+                hyp = np.full((B, P, 2), -1, np.int32)                      # a list is P entries long; a shorter one ends in entries that name nothing
+                for k, h in enumerate(lists):
+                    hyp[k, :len(h)] = h
+                res = eng.warp_score(corr, nlag, *table, hyp, hop, width)
+        else:
+            hyp = np.full((len(ids), P, 2), -1, np.int32)
+            for k, b in enumerate(ids):
+                hyp[k, :len(lists[b])] = lists[b]
+            sel = dev(ids, np.int64)
+            rows4, col = dev(at[0], np.int64).reshape(B, NBANDS), dev(at[1], np.int64).reshape(B)
+            hop_row = np.array([bases.index(min(spans[b][0], CTR_END - 1)) for b in ids], np.int32)
+            res = eng.warp_score_at(corr, rows4[sel], col[sel], nlag[ids], table[0][sel], table[1][sel], table[2][sel], hyp, hop, hop_row, width)
+        score, origin, rank = (t.cpu().numpy() for t in res)
+        for k, b in enumerate(ids):
+            if not J[b]:
+                continue
+            lo = spans[b][0]
+            if rigid:
+                phis = lists[b] if at is None else [phi for _, phi in lists[b]]
+                make = lambda s, o, r: verdict(s, o, r, lo, phis, int(J[b]))
+            else:
+                make = lambda s, o, r: drift_verdict(s, o, r, lo, lists[b], tabs[b][0], int(J[b]))
+            out[b] = _verdicts(n_own, score[k], origin[k], rank[k], make)
+            if pos0 is not None:
+                for p in out[b]:
+                    if p.ctr >= 0:
+                        p.ctr0 = origin_of(p.ctr, p.phase, int(pos0[b]))
+    return out
+
+
+def _torch():
+    import torch
+    return torch
+
+
 __all__ = ["DECOY_LABEL", "Presence", "check_decoys", "check_drift", "check_phases", "check_reach", "clip_spans", "decoy_keys", "drift_verdict",
-           "fold_model", "hop_model", "pick_hypotheses", "pick_phases", "presence_model", "score_model", "skew_table", "slots", "verdict",
-           "warp_fold_model", "warp_score_model"]
+           "fold_model", "hop_model", "live_model", "live_span", "pick_hypotheses", "pick_phases", "presence_model", "score_model", "search", "skew_table", "slots",
+           "table_rows", "verdict", "warp_fold_model", "warp_score_model", "window_rows"]
