@@ -127,6 +127,18 @@ if (set(LIVE_PRESENCE_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) 
     raise NativeError(f"{LIVE_PRESENCE_HEADER_PATH} declares a name another header already has")
 globals().update(LIVE_PRESENCE_CONSTANTS)
 
+# The companion header of the hypothesis list picked on the device, bound the same way into three more tables.
+PICK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_pick.h")
+try:
+    with open(PICK_HEADER_PATH) as _f:
+        PICK_DECLARATIONS, PICK_SIGNATURES, PICK_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{PICK_HEADER_PATH}: the device pick is bound from this header ({e})") from None
+if (set(PICK_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set(WARP_SIGNATURES) | set(LIVE_PRESENCE_SIGNATURES))
+        or set(PICK_CONSTANTS) & (set(CONSTANTS) | set(PRESENCE_CONSTANTS) | set(WARP_CONSTANTS) | set(LIVE_PRESENCE_CONSTANTS))):
+    raise NativeError(f"{PICK_HEADER_PATH} declares a name another header already has")
+globals().update(PICK_CONSTANTS)         # ES_PICK_MAX_H
+
 _lib = None
 
 
@@ -148,7 +160,7 @@ def load() -> ctypes.CDLL:
     if got != CONSTANTS["ES_ABI_VERSION"]:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
-    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES, **PICK_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

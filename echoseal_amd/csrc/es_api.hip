@@ -1185,6 +1185,21 @@ int es_warp_score_at_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, in
                                    H, hop_dev, K, HR, Ccols, hop_row_dev, n_origins, score_dev, origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
 }
 
+// ---- the hypothesis list picked on the device (include/echoseal_pick.h) ----
+int es_fold_pick_batch(es_ctx* ctx, const double* fold_dev, int64_t B, int64_t D, const int32_t* nwarp_dev, int64_t H, int32_t* hyp_dev,
+                       double* val_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (B < 0 || D < 0) return fail(ctx, ES_EINVAL, "es_fold_pick_batch: negative count");
+    if (H < 1 || H > ES_PICK_MAX_H) return fail(ctx, ES_EINVAL, "es_fold_pick_batch: H must be in 1 .. ES_PICK_MAX_H");
+    if (B > 0x7FFFFFFFll) return fail(ctx, ES_EINVAL, "es_fold_pick_batch: more than 2^31 - 1 records (a workgroup each) in one call");
+    if (D > 0x7FFFFFFFll / ES_FRAME_LEN) return fail(ctx, ES_EINVAL, "es_fold_pick_batch: 1215 D above 2^31 - 1");
+    if (B == 0 || D == 0) return ES_OK;
+    if (!fold_dev || !hyp_dev) return fail(ctx, ES_EINVAL, "es_fold_pick_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_fold_pick(ctx, fold_dev, B, D, nwarp_dev, H, hyp_dev, val_dev, (hipStream_t)stream);
+}
+
 // What both acquisition calls refuse and when they have nothing to do: -> ES_EINVAL, ES_OK with *work = false, or ES_OK with *work = true
 // and the exact grid of one wave per (record, tile of 64 high halves) within 2^31 - 1 blocks.
 static int acquire_span(es_ctx* ctx, const char* who, int64_t P, int64_t ctr_lo, int64_t ctr_hi, bool* work)

@@ -12,6 +12,7 @@
 #include "../../include/echoseal_presence.h"
 #include "../../include/echoseal_warp.h"
 #include "../../include/echoseal_live_presence.h"
+#include "../../include/echoseal_pick.h"
 
 /* global memory by its address space: what the integer kernels (es_aead.hip, es_keyring.hip) read and write through */
 typedef __attribute__((address_space(1))) const uint8_t g_cu8;
@@ -302,6 +303,8 @@ int es_launch_warp_fold_at(es_ctx* ctx, const double* corr, int64_t rows, int64_
 int es_launch_warp_score_at(es_ctx* ctx, const double* corr, int64_t rows, int64_t stride, const int64_t* row, const int64_t* col, const int32_t* nlag,
                             int64_t B, const es_warp_tab& tab, const int32_t* hyp, int64_t H, const uint8_t* hop, int64_t K, int64_t HR, int64_t Ccols,
                             const int32_t* hop_row, int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st);
+/* the hypothesis list picked on the device (es_keyring.hip; include/echoseal_pick.h): a workgroup per record, B checked by the entry point */
+int es_launch_fold_pick(es_ctx* ctx, const double* fold, int64_t B, int64_t D, const int32_t* nwarp, int64_t H, int32_t* hyp, double* val, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

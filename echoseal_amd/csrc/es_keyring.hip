@@ -11,7 +11,8 @@
 // the score of every (key, counter origin, phase) against them (es_phase_fold_kernel, es_hop_score_kernel), and both again
 // on a grid that follows clock drift, a table of per-slot offsets (es_warp_fold_kernel, es_warp_score_kernel), and those two
 // over records that lie anywhere in a table of rows, such as the windows of live streams in a monitor's history (es_warp_fold_at_kernel,
-// es_warp_score_at_kernel) -- the only float64 work in this file, every sum in one lane from its first slot to its last.
+// es_warp_score_at_kernel) -- the only float64 work in this file, every sum in one lane from its first slot to its last --
+// and the pick of the hypothesis list from a fold (es_fold_pick_kernel), which compares float64 values as integers.
 //
 // Integer work otherwise.  Ring and schedule: one lane per key / per record, the S-box in LDS, round keys and hash states in
 // registers (every index a constant after unrolling: no private memory).  Plan: one wave per (key, row), peaks serially, the
@@ -706,6 +707,87 @@ __global__ __launch_bounds__(256) void es_warp_score_at_kernel(const double* __r
     warp_score_body<HB, true>(corr_p + mine, 0, n, J, hop, live, origin, b, tab, hyp_p, H, sc_score, sc_origin, sc_rank);
 }
 
+// ---- the hypothesis list of a presence test picked on the device (include/echoseal_pick.h) ----
+// Per record the H candidates of largest fold value, equal values by the lower row and then the lower phase.
+//
+// One workgroup of four waves per record.  A value becomes a 96-bit key (hi, lo): hi the order-preserving integer image of the value
+// (f64_key of es_wave.h after -0.0 has become +0.0; 0 for what is no candidate, -inf and every NaN -- no candidate's image is 0), lo the
+// complement of its index d 1215 + phi, so that of equal values the lower index has the larger key.  The keys of a record are distinct,
+// and entry h is the largest key strictly below entry h - 1's: H rounds of a maximum under a total order, which any reduction shape
+// gives alike -- lanes stride over the record's nwarp 1215 values (coalesced 8-byte reads), the wave reduces through cross-lane moves,
+// the four waves through four LDS slots that every lane then reads, so each lane knows the winner and no second barrier is needed
+// (the slots alternate between two sets from round to round).  The first round without a candidate ends the list; the rest is filled.
+constexpr int FP_BLOCK = 256, FP_WAVES = FP_BLOCK / 64;
+
+struct fp_key { uint64_t hi; uint32_t lo; };
+
+__device__ __forceinline__ bool fp_above(const fp_key& a, const fp_key& b) { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
+
+// the image of a candidate's value, 0 for -inf and NaN
+__device__ __forceinline__ uint64_t fp_image(double v)
+{
+    uint64_t b; __builtin_memcpy(&b, &v, 8);
+    const uint64_t mag = b & 0x7fffffffffffffffULL;
+    if (mag > 0x7ff0000000000000ULL || b == 0xfff0000000000000ULL) return 0;
+    double x = v;
+    if (mag == 0) x = 0.0;                                                                // -0.0 == +0.0
+    return f64_key(x);
+}
+
+template <int S>
+__device__ __forceinline__ fp_key fp_max_xor(const fp_key& k, int lane)
+{
+    fp_key o;
+    const uint32_t l = (uint32_t)xor_lanes_b32<S>((int)(uint32_t)k.hi, lane), h = (uint32_t)xor_lanes_b32<S>((int)(uint32_t)(k.hi >> 32), lane);
+    o.hi = ((uint64_t)h << 32) | l;
+    o.lo = (uint32_t)xor_lanes_b32<S>((int)k.lo, lane);
+    return fp_above(o, k) ? o : k;
+}
+
+__global__ __launch_bounds__(FP_BLOCK) void es_fold_pick_kernel(const double* __restrict__ fold_p, long long D, const int32_t* __restrict__ nwarp_p, int H,
+        int32_t* __restrict__ hyp_p, double* __restrict__ val_p)
+{
+    __shared__ fp_key red[2][FP_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long b = blockIdx.x;
+    long long nw = nwarp_p ? (long long)((g_ci32*)nwarp_p)[b] : D;
+    nw = nw < 0 ? 0 : (nw > D ? D : nw);
+    const unsigned n = (unsigned)(nw * ES_FRAME_LEN);                                     // 1215 D < 2^31: the entry point's check
+    const double* f = fold_p + b * D * ES_FRAME_LEN;                                      // values [0, n) of it are read, nothing else
+    fp_key prev = {~0ull, ~0u};                                                           // above every key: no image is all ones
+    int h = 0;
+    #pragma unroll 1
+    for (; h < H; ++h) {
+        fp_key best = {0, 0};
+        #pragma unroll 4
+        for (unsigned i = tid; i < n; i += FP_BLOCK) {
+            const fp_key k = {fp_image(f[i]), ~i};
+            if (k.hi != 0 && fp_above(prev, k) && fp_above(k, best)) best = k;
+        }
+        best = fp_max_xor<1>(best, lane); best = fp_max_xor<2>(best, lane); best = fp_max_xor<4>(best, lane);
+        best = fp_max_xor<8>(best, lane); best = fp_max_xor<16>(best, lane); best = fp_max_xor<32>(best, lane);
+        if (lane == 0) red[h & 1][wave] = best;
+        __syncthreads();
+        best = red[h & 1][0];
+        #pragma unroll
+        for (int w = 1; w < FP_WAVES; ++w)
+            if (fp_above(red[h & 1][w], best)) best = red[h & 1][w];
+        if (best.hi == 0) break;                                                          // (block-uniform) the record has no further candidate
+        if (tid == 0) {
+            const unsigned i = ~best.lo;
+            hyp_p[(b * H + h) * 2] = (int32_t)(i / ES_FRAME_LEN);
+            hyp_p[(b * H + h) * 2 + 1] = (int32_t)(i % ES_FRAME_LEN);
+            if (val_p) val_p[b * H + h] = f[i];
+        }
+        prev = best;
+    }
+    for (int e = h + tid; e < H; e += FP_BLOCK) {                                         // entries that name nothing
+        hyp_p[(b * H + e) * 2] = -1;
+        hyp_p[(b * H + e) * 2 + 1] = -1;
+        if (val_p) val_p[b * H + e] = -__builtin_inf();
+    }
+}
+
 }  // namespace
 
 int es_launch_keyring_derive(es_ctx* ctx, const uint8_t* master32, int64_t N, uint8_t* ring, hipStream_t st)
@@ -844,4 +926,10 @@ int es_launch_warp_score_at(es_ctx* ctx, const double* corr, int64_t rows, int64
                                      hop, (long long)K, (long long)HR, (long long)Ccols, hop_row, (long long)n_origins, sc.NB, sc.score, sc.origin,
                                      sc.rank)) return rc;
     return es_launch_hop_best(ctx, sc, score, origin, rank, st);
+}
+
+// the exact grid, a workgroup per record: the entry point refuses B > 2^31 - 1
+int es_launch_fold_pick(es_ctx* ctx, const double* fold, int64_t B, int64_t D, const int32_t* nwarp, int64_t H, int32_t* hyp, double* val, hipStream_t st)
+{
+    return es_launch(ctx, es_fold_pick_kernel, (unsigned)B, FP_BLOCK, 0, st, fold, (long long)D, nwarp, (int)H, hyp, val);
 }

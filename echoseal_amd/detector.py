@@ -330,21 +330,53 @@ class WatermarkDetector:
         finite or no number, or that skews some clip by a whole frame or leaves it no slot."""
         return [None if r is None else r[0] for r in self._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, None)]
 
-    def _presence_clips(self, clips, fs_in, ctr0, span, phases, decoys, drift_ppm, keys) -> list:
+    # ------------------------------------------------------------------ the presence timeline (DESIGN 4.26)
+    def presence_map(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), window: int = 40, step: int = 20,
+                     confirm: int = 2, phases: int = 8, decoys: int = 32, drift_ppm=0.0):
+        return self.presence_map_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, window=window, step=step, confirm=confirm,
+                                       phases=phases, decoys=decoys, drift_ppm=drift_ppm)[0]
+
+    def presence_map_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2, phases: int = 8,
+                           decoys: int = 32, drift_ppm=0.0) -> list:
+        """Which parts of each clip carry this key's mark, and where it was cut: -> per clip a presence.PresenceMap, or None for a clip
+        without one whole 1215-sample slot.  The presence test (presence_batch) runs on windows of `window` slots every `step` slots
+        (presence.map_windows; about 1 s every 0.5 s by default), each on its own frame grid, so a cut between two windows does not
+        blur either.  A clip of at most `window` slots is one window: the map's single entry is presence() on the clip, field for field.
+        span = (lo, hi) names the counters the clip's slot 0 may carry; the window that starts s slots in searches (lo + s, hi + s),
+        lowered at 2^32 (presence.window_span), so a cut that removes up to hi - lo frames stays inside the search, and an insertion
+        of up to lo.  ctr0 = c is shorthand for span = (c, c + 2), which follows no cut.  A detected window gives the grid anchor
+        t = col + phase - 1215 ctr; adjacent detected windows whose anchors agree (presence.consistent: within 1 sample, plus what
+        drift_ppm allows between them) form a stretch, one of at least `confirm` windows is confirmed, and successive confirmed
+        stretches are joined by a Splice that says how many samples are missing between their grids.  A lone detected window is the
+        1 / (decoys + 1) event the rule allows per window and confirms nothing; every verdict stays statistical.
+        drift_ppm > 0 gives each window the drift search of DESIGN 4.24 over its own length.
+        The front is presence_batch's; then per launch the windows of all its clips go through presence.search_map: per group of windows
+        ONE fold, ONE device pick (es_fold_pick_batch), ONE hop window and ONE score per span width, never a launch per window.
+        ValueError before any engine exists: what presence_batch refuses of span, ctr0, decoys and drift_ppm (the drift judged on a
+        window), window, step or confirm that are no integers, step < 1, step > window, confirm < 1, phases outside 1 .. 64."""
+        return [None if r is None else r[0] for r in self._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, None,
+                                                                          grid=(window, step, confirm))]
+
+    def _presence_clips(self, clips, fs_in, ctr0, span, phases, decoys, drift_ppm, keys, grid=None) -> list:
         """presence_batch under each of `keys` (None: this detector's key alone) -> per clip None or one Presence per key.  The checks,
         the front and the launches are the same whatever the keys: the fold and the hypothesis list are keyless, so one front and one
-        score call over the ring keys + decoys serve them all (presence.search)."""
+        score call over the ring keys + decoys serve them all (presence.search).  grid = (window, step, confirm): presence_map_batch
+        instead, one PresenceMap per key, the same front with presence.search_map behind it."""
         from . import presence as pr
         import torch
         clips = list(clips)
         fs_list = rate_list(fs_in, len(clips))
         P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
+        if grid is not None:
+            grid = pr.check_map(*grid, P)[:3]
         spans = pr.clip_spans(ctr0, span, len(clips))
         for c, f, s in zip(clips, fs_list, spans):                          # refused by name before any engine exists
             samples = resampled_length(int(np.size(c)), int(f), self.fs_target)
-            pr.check_reach(s, samples)
+            if grid is None:
+                pr.check_reach(s, samples)
             if drift > 0:
-                pr.skew_table(samples - (PRE_L - 1), drift)
+                for n in {samples - (PRE_L - 1)} if grid is None else {w[2] for w in pr.map_windows(samples - (PRE_L - 1), *grid[:2])}:
+                    pr.skew_table(n, drift)
         out: list = [None] * len(clips)
         n_own = 1 if keys is None else len(keys)
         band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
@@ -361,7 +393,12 @@ class WatermarkDetector:
                 else:
                     corr = eng.xcorr(eng.bpf(x[:, :M], bid), bid)
                 nlag = np.array(sizes, np.int64) - (PRE_L - 1)
-                res = pr.search(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P) if n_own else [None] * len(sizes)
+                if not n_own:
+                    res = [None] * len(sizes)
+                elif grid is None:
+                    res = pr.search(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P)
+                else:
+                    res = pr.search_map(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P, *grid)
                 if self._presence_rows is not None and any(r is not None for r in res):
                     self._presence_rows.append(([ids[i] for i in la.idx], corr.cpu().numpy(), nlag))
                 for k, i in enumerate(la.idx):

@@ -763,6 +763,34 @@ class RxEngine(TxChain, MonitorChain):
                    hyp.shape[1], hop, K, HR, Ccols, hop_row, n_origins, score, origin, rank, scratch if scratch.numel() else None)
         return score, origin, rank
 
+    # ------------------------------------------------------------------ the hypothesis list on the device (include/echoseal_pick.h)
+    def fold_pick(self, fold: torch.Tensor, nwarp=None, H: int = 8, *, want_val: bool = True):
+        """The hypothesis list of each record of a fold, picked on the device (es_fold_pick_batch; presence.pick_model is the host twin).
+        fold float64 [B, D, 1215] as warp_fold / warp_fold_at give it ([B, 1215], phase_fold's: D = 1); nwarp [B] the rows of each
+        record (None: D; clamped to [0, D]; rows past them are never read); 1 <= H <= ES_PICK_MAX_H -> (hyp int32 [B, H, 2], val float64
+        [B, H]): entry h the (row, phase) of h-th largest value, equal values by the lower row, then the lower phase; -inf and NaN are
+        never picked; (-1, -1) and -inf from the first entry past a record's last candidate -- the form warp_score / warp_score_at take
+        for "an entry that names nothing".  want_val=False: val is None and is not written.  B * D == 0 enqueues nothing: every list is
+        empty, and the outputs are filled here."""
+        if fold.dim() == 2:
+            fold = fold[:, None, :]
+        if fold.dim() != 3 or fold.shape[2] != nat.ES_FRAME_LEN or fold.dtype != torch.float64 or not fold.is_contiguous() or fold.device != self.device:
+            raise ValueError("fold must be a contiguous float64 [B, D, 1215] tensor on the engine's device")
+        B, D, H = fold.shape[0], fold.shape[1], int(H)
+        if not 1 <= H <= nat.ES_PICK_MAX_H:
+            raise ValueError(f"H = {H}: a list of 1 .. {nat.ES_PICK_MAX_H} entries")
+        if nwarp is not None:
+            nwarp = self._dev(nwarp, torch.int32).reshape(-1)
+            if nwarp.numel() != B:
+                raise ValueError("nwarp: one row count per record")
+        if B * D == 0:
+            return (torch.full((B, H, 2), -1, dtype=torch.int32, device=self.device),
+                    torch.full((B, H), float("-inf"), dtype=torch.float64, device=self.device) if want_val else None)
+        hyp = torch.empty((B, H, 2), dtype=torch.int32, device=self.device)
+        val = torch.empty((B, H), dtype=torch.float64, device=self.device) if want_val else None
+        self._call("es_fold_pick_batch", fold, B, D, nwarp, H, hyp, val)
+        return hyp, val
+
     def acquire_mask(self, ring: KeyRing, key_idx, ok, lo16, band, span):
         """Which counters of `span` each header record may belong to (es_acquire_mask_batch; acquire.mask_model is the host twin).
         Record p = (ring row key_idx[p] int32, ok[p] uint8, lo16[p] int32, band[p] uint8), as one header call gives them

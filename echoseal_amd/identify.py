@@ -160,6 +160,20 @@ class WatermarkIdentifier:
         WatermarkDetector.presence_batch's."""
         return self._det._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, self.keys)
 
+    def presence_map(self, audio, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2,
+                     phases: int = 8, decoys: int = 32, drift_ppm=0.0):
+        return self.presence_map_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, window=window, step=step, confirm=confirm,
+                                       phases=phases, decoys=decoys, drift_ppm=drift_ppm)[0]
+
+    def presence_map_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2, phases: int = 8,
+                           decoys: int = 32, drift_ppm=0.0) -> list:
+        """WatermarkDetector.presence_map_batch under every key at once -> per clip None (no whole 1215-sample slot) or a list with one
+        presence.PresenceMap per key: entry k is field for field what WatermarkDetector(keys[k]).presence_map_batch gives for the clip.
+        The windows' folds and lists are keyless, so one front, one fold and one pick serve every key, and one score call covers the
+        ring keys + decoys; each key is ranked against the decoys alone, so for N keys the chance that some key's window is detected
+        falsely is at most N / (decoys + 1).  Arguments and ValueErrors are WatermarkDetector.presence_map_batch's."""
+        return self._det._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, self.keys, grid=(window, step, confirm))
+
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
                      memo_slots: int | None = None, ctr0=None) -> "LiveIdentifier":
         """A monitor of n live streams that says, per push and stream, which of this identifier's keys marks the stream's last window_s

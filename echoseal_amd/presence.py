@@ -15,7 +15,12 @@ include/echoseal_warp.h), and presence_model(..., drift_ppm=...) the whole searc
 Live windows: a record may lie anywhere in a table of rows, such as a stream's window in a monitor table's correlation
 history.  window_rows cuts the block es_warp_fold_at_batch / es_warp_score_at_batch may read (include/echoseal_live_presence.h), so the
 models above are their twins too; live_span is the counter span of a stream with an origin, live_model the whole call for one stream.
-Last, `search`: the launches and verdicts behind every public presence call, the one function here that is handed an engine.
+`search`: the launches and verdicts behind every public presence call; it and search_map are the functions here that are handed an engine.
+
+The timeline: which parts of a clip carry the mark, and where it was cut.  pick_model is the twin of the device's pick
+(es_fold_pick_batch; include/echoseal_pick.h); map_windows cuts a clip into overlapping windows, each a record of the _at calls with its own
+span; stretches joins the detected windows that lie on one frame grid and names the splices between confirmed stretches; map_model is the
+whole call on the host, search_map its launches.
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ from .utils import band_index
 NBANDS = 4
 DECOY_LABEL = b"EchoSeal:decoy:v1:"
 NO_BAND = 0xFF                   # es_hop_window_batch's byte for a counter past 2^32 - 1
+PICK_MAX_H = 64                  # ES_PICK_MAX_H of include/echoseal_pick.h: the longest list es_fold_pick_batch picks
 
 
 @dataclass
@@ -405,7 +411,7 @@ def _verdicts(n_own: int, score_row, origin_row, rank_row, make) -> list:
     return [make(pick(score_row, k), pick(origin_row, k), pick(rank_row, k)) for k in range(n_own)]
 
 
-def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=None, pos0=None) -> list:
+def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=None, pos0=None, device_pick: bool = False) -> list:
     """The launches and verdicts of every presence call (WatermarkDetector.presence_batch, WatermarkIdentifier.presence_batch,
     LiveMonitor.presence, LiveIdentifier.presence) -> per record None (no whole slot) or a list of n_own Presence, one per own key.
     ring: the device key ring [the n_own own keys] + decoys.  corr, nlag: the records' rows; spans: (lo, hi) per record.
@@ -413,13 +419,21 @@ def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=No
     hop_score, a drift search through warp_fold / warp_score, as presence_batch always called them.
     at = (rows4 [B, 4], col [B]): records anywhere in the table `corr`, each with its own span -- ONE warp_fold_at over all of them (drift 0:
     a one-row table of zeros), ONE download and pick, ONE hop_window with a hop row per distinct span base, and ONE warp_score_at per
-    group of equal span width.  pos0 [B]: the absolute first sample of each record, for the verdict's ctr0 (None: 0)."""
+    group of equal span width.  pos0 [B]: the absolute first sample of each record, for the verdict's ctr0 (None: 0).
+    device_pick (the at= route only, P <= ES_PICK_MAX_H): the fold stays on the device, ONE fold_pick replaces the download
+    and the host's pick, its lists go into warp_score_at as they are, and only they are downloaded, for the verdicts' phase lists -- the
+    same verdicts, field for field.  False: the launches and bits every call had before."""
+    if device_pick and at is None:
+        raise ValueError("device_pick: the route of records anywhere in a table (at=)")
+    if device_pick and P > PICK_MAX_H:
+        raise ValueError(f"phases = {P}: the device picks lists of at most {PICK_MAX_H} entries")
     nlag = np.asarray(nlag, np.int64).reshape(-1)
     B = nlag.size
     out: list = [None] * B
     spans = [(int(lo), int(hi)) for lo, hi in spans]
     rigid = not drift > 0
-    tabs = None if rigid else [skew_table(n, drift) for n in nlag.tolist()]
+    made = {} if rigid else {n: skew_table(n, drift) for n in set(nlag.tolist())}       # records of one length share a table
+    tabs = None if rigid else [made[n] for n in nlag.tolist()]
     J = np.maximum(nlag, 0) // FRAME_LEN if rigid else np.array([t[1] for t in tabs], np.int64)
     if not B or not J.max():
         return out
@@ -435,8 +449,13 @@ def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=No
         for k, t in enumerate(tabs or ()):
             warp[k, :t[2].shape[0], :t[1]] = t[2]
         table = (dev(warp, np.int32), dev(nwarp, np.int32), dev(J, np.int32))
-        fold = (eng.warp_fold(corr, nlag, *table) if at is None else eng.warp_fold_at(corr, at[0], at[1], nlag, *table)).cpu().numpy()
-        lists = [pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
+        fold = eng.warp_fold(corr, nlag, *table) if at is None else eng.warp_fold_at(corr, at[0], at[1], nlag, *table)
+        if device_pick:
+            hyp_dev = eng.fold_pick(fold, table[1], P, want_val=False)[0]
+            lists = [[(d, phi) for d, phi in h if d >= 0] for h in hyp_dev.cpu().numpy().tolist()]
+        else:
+            fold = fold.cpu().numpy()
+            lists = [pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
         jw = int(J.max())
     bases = sorted({min(lo, CTR_END - 1) for lo, _ in spans})               # one hop row per distinct span base
     hop = eng.hop_window(ring, bases, max(max(hi - lo for lo, hi in spans) + jw - 1, 0))
@@ -453,10 +472,13 @@ def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=No
                     hyp[k, :len(h)] = h
                 res = eng.warp_score(corr, nlag, *table, hyp, hop, width)
         else:
-            hyp = np.full((len(ids), P, 2), -1, np.int32)
-            for k, b in enumerate(ids):
-                hyp[k, :len(lists[b])] = lists[b]
             sel = dev(ids, np.int64)
+            if device_pick:
+                hyp = hyp_dev[sel]
+            else:
+                hyp = np.full((len(ids), P, 2), -1, np.int32)
+                for k, b in enumerate(ids):
+                    hyp[k, :len(lists[b])] = lists[b]
             rows4, col = dev(at[0], np.int64).reshape(B, NBANDS), dev(at[1], np.int64).reshape(B)
             hop_row = np.array([bases.index(min(spans[b][0], CTR_END - 1)) for b in ids], np.int32)
             res = eng.warp_score_at(corr, rows4[sel], col[sel], nlag[ids], table[0][sel], table[1][sel], table[2][sel], hyp, hop, hop_row, width)
@@ -478,11 +500,218 @@ def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=No
     return out
 
 
+# ---- the hypothesis list as the device picks it (include/echoseal_pick.h) ----
+def pick_model(fold, nwarp=None, H: int = 8):
+    """es_fold_pick_batch in NumPy: fold float64 [B, D, 1215], nwarp [B] (None: D; clamped to [0, D]) -> (hyp int32 [B, H, 2], val
+    float64 [B, H]).  The candidates of record b are the values of its first nwarp[b] rows that are neither -inf nor NaN; entry h is
+    the (row, phase) of the h-th largest, equal values (-0.0 == +0.0) by the lower row, then the lower phase; val the value as the fold
+    holds it; (-1, -1) and -inf past the last candidate."""
+    fold = np.asarray(fold, np.float64)
+    if fold.ndim != 3 or fold.shape[2] != FRAME_LEN:
+        raise ValueError(f"fold: float64 [B, D, {FRAME_LEN}]")
+    B, D, H = fold.shape[0], fold.shape[1], _int(H, "H")
+    if not 1 <= H <= PICK_MAX_H:
+        raise ValueError(f"H = {H}: a list of 1 .. {PICK_MAX_H} entries")
+    nwarp = np.full(B, D, np.int64) if nwarp is None else np.clip(np.asarray(nwarp, np.int64).reshape(-1), 0, D)
+    if nwarp.size != B:
+        raise ValueError("nwarp: one row count per record")
+    hyp = np.full((B, H, 2), -1, np.int32)
+    val = np.full((B, H), -np.inf, np.float64)
+    for b in range(B):
+        v = fold[b, :nwarp[b]].reshape(-1)
+        idx = np.flatnonzero(~np.isnan(v) & ~np.isneginf(v))
+        rank = np.where(v[idx] == 0.0, 0.0, v[idx])                         # one zero
+        top = idx[np.lexsort((idx, -rank))][:H]                             # by the value, largest first; then by the index
+        hyp[b, :top.size, 0], hyp[b, :top.size, 1] = top // FRAME_LEN, top % FRAME_LEN
+        val[b, :top.size] = v[top]
+    return hyp, val
+
+
+# ---- the presence timeline of a clip: windows, marked stretches and splices (DESIGN 4.26) ----
+MAP_HOP_BYTES = 256 << 20        # the most bytes of one group's hop table, [K][HR][Ccols] uint8: windows go to the search in groups within it
+
+
+@dataclass
+class Stretch:
+    """A maximal run of adjacent windows first .. last, each detected and each consistent with the one before it.  start, end: the
+    samples [start, end) at fs_target from the first window's first to the last window's last slot; t: the grid anchor of the first
+    window, the clip sample at which frame 0 would start (col + phase - 1215 ctr); ctr0: the counter origin of the first window
+    (acquire.origin_of at its column); score: the smallest own score in the run; confirmed: the run has at least `confirm` windows."""
+    first: int
+    last: int
+    start: int
+    end: int
+    t: int
+    ctr0: int
+    score: float
+    confirmed: bool
+
+
+@dataclass
+class Splice:
+    """A change of grid between two successive confirmed stretches A and B, whatever lies between them: somewhere in samples [lo, hi)
+    -- from the column of A's last window to the end of B's first -- `removed` samples are missing (negative: were inserted):
+    the anchor of A's last window minus the anchor of B's first."""
+    lo: int
+    hi: int
+    removed: int
+
+
+@dataclass
+class PresenceMap:
+    """The presence timeline of a clip.  windows: the Presence of each window (its ctr0 taken at the window's column); starts: the slot
+    each window starts at; stretches, splices: as above; marked: the samples at fs_target covered by confirmed stretches (the union of
+    their [start, end))."""
+    windows: list
+    starts: list
+    stretches: list
+    splices: list
+    marked: int
+
+
+def check_map(window, step, confirm, phases) -> tuple[int, int, int, int]:
+    """The arguments of a presence map: integers, 1 <= step <= window slots, confirm >= 1 windows, 1 <= phases <= 64 (the device picks
+    the lists: ES_PICK_MAX_H)."""
+    W, S, C, P = _int(window, "window"), _int(step, "step"), _int(confirm, "confirm"), check_phases(phases)
+    if S < 1 or S > W:
+        raise ValueError(f"step = {S}, window = {W}: windows of `window` 1215-sample slots every `step` slots, 1 <= step <= window")
+    if C < 1:
+        raise ValueError(f"confirm = {C}: the windows that confirm a stretch, 1 or more")
+    if P > PICK_MAX_H:
+        raise ValueError(f"phases = {P}: a presence map searches at most {PICK_MAX_H} phases per window")
+    return W, S, C, P
+
+
+def map_windows(nlag: int, window: int = 40, step: int = 20) -> list[tuple[int, int, int]]:
+    """The windows of a clip of nlag lags -> [(first slot s, column 1215 s, lags)], J = nlag // 1215: none for J == 0; the whole clip,
+    (0, 0, nlag), for J <= window; else windows of `window` slots at s = 0, step, 2 step .. <= J - window, and one at J - window
+    where the steps do not end there."""
+    W, S, _, _ = check_map(window, step, 1, 1)
+    nlag = max(int(nlag), 0)
+    J = nlag // FRAME_LEN
+    if J == 0:
+        return []
+    if J <= W:
+        return [(0, 0, nlag)]
+    starts = list(range(0, J - W + 1, S))
+    if (J - W) % S:
+        starts.append(J - W)
+    return [(s, FRAME_LEN * s, FRAME_LEN * W) for s in starts]
+
+
+def window_span(span, s: int, J: int) -> tuple[int, int]:
+    """The span of the window that starts s slots into a clip whose slot 0 may carry the counters of `span`: (lo + s, hi + s), lowered
+    at 2^32 as live_span lowers it (hi + J - 1 <= 2^32 for the window's J slots; never below lo; possibly empty)."""
+    lo, hi = check_span(span)
+    lo = min(lo + int(s), CTR_END)
+    return lo, max(lo, min(hi + int(s), CTR_END - max(int(J), 1) + 1))
+
+
+def anchor(p: Presence, col: int) -> int:
+    """t of a window whose own key was found: the clip sample at which frame 0 would start."""
+    return int(col) + p.phase - FRAME_LEN * p.ctr
+
+
+def consistent(t_a: int, col_a: int, t_b: int, col_b: int, drift_ppm=0.0) -> bool:
+    """Do two windows lie on one frame grid?  |t_a - t_b| <= 1 + ceil(drift_ppm |col_b - col_a| / 10^6), the ceiling exact."""
+    return abs(int(t_a) - int(t_b)) <= 1 + math.ceil(Fraction(check_drift(drift_ppm)) * abs(int(col_b) - int(col_a)) / 10 ** 6)
+
+
+def stretches(windows, cols, nlags, drift_ppm=0.0, confirm: int = 2):
+    """The stretches, the splices and the marked samples of a list of windows -> (list of Stretch, list of Splice, marked).  windows[w]:
+    the Presence of window w or None; cols[w], nlags[w]: its first column and its lags."""
+    C = _int(confirm, "confirm")
+    out, run = [], []
+
+    def close():
+        if run:
+            a, b = run[0], run[-1]
+            out.append(Stretch(a, b, int(cols[a]), int(cols[b]) + FRAME_LEN * (int(nlags[b]) // FRAME_LEN), anchor(windows[a], cols[a]),
+                               origin_of(windows[a].ctr, windows[a].phase, int(cols[a])), min(float(windows[w].score) for w in run), len(run) >= C))
+            run.clear()
+
+    for w, p in enumerate(windows):
+        if p is None or not p.detected or p.ctr < 0:
+            close()
+            continue
+        if run and not consistent(anchor(windows[run[-1]], cols[run[-1]]), cols[run[-1]], anchor(p, cols[w]), cols[w], drift_ppm):
+            close()
+        run.append(w)
+    close()
+    sure = [s for s in out if s.confirmed]
+    splices = [Splice(int(cols[a.last]), int(cols[b.first]) + FRAME_LEN * (int(nlags[b.first]) // FRAME_LEN),
+                      anchor(windows[a.last], cols[a.last]) - anchor(windows[b.first], cols[b.first])) for a, b in zip(sure[:-1], sure[1:])]
+    marked, reach = 0, 0
+    for s in sure:                                                          # ascending starts: the union of [start, end)
+        marked += max(s.end - max(s.start, reach), 0)
+        reach = max(reach, s.end)
+    return out, splices, marked
+
+
+def make_map(windows, wins, drift_ppm, confirm) -> PresenceMap:
+    """The PresenceMap of a clip from its windows' verdicts and map_windows' list."""
+    st, sp, marked = stretches(windows, [c for _, c, _ in wins], [n for _, _, n in wins], drift_ppm, confirm)
+    return PresenceMap(list(windows), [s for s, _, _ in wins], st, sp, marked)
+
+
+def map_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2, phases: int = 8,
+              decoys: int = 32, drift_ppm=0.0) -> PresenceMap | None:
+    """WatermarkDetector.presence_map from one clip's four correlation rows, on the host: presence_model on the window_rows block of each
+    window of map_windows, under the window's own span, then stretches.  None where the clip has no whole slot."""
+    corr4 = np.asarray(corr4, np.float64)
+    W, S, C, P = check_map(window, step, confirm, phases)
+    nlag = min(max(int(nlag), 0), corr4.shape[1])
+    wins = map_windows(nlag, W, S)
+    if not wins:
+        return None
+    verdicts = []
+    for s, col, n in wins:
+        p = presence_model(window_rows(corr4, range(NBANDS), col, n), n, key, span=window_span(span, s, n // FRAME_LEN), phases=P, decoys=decoys,
+                           drift_ppm=drift_ppm)
+        if p is not None and p.ctr >= 0:
+            p.ctr0 = origin_of(p.ctr, p.phase, col)
+        verdicts.append(p)
+    return make_map(verdicts, wins, drift_ppm, C)
+
+
+def search_map(eng, ring, n_own: int, corr, clip_nlag, spans, drift: float, P: int, window: int, step: int, confirm: int) -> list:
+    """The windows of every clip of one launch through `search` (at=, device_pick=True) -> per clip None (no whole slot) or n_own
+    PresenceMap, one per own key.  Clip c owns rows 4 c .. 4 c + 3 of corr; spans[c] is its span.  Windows go in groups of consecutive
+    windows whose hop table -- a hop row per distinct span base, K HR Ccols bytes -- stays within MAP_HOP_BYTES: per group ONE fold, ONE
+    pick, ONE hop window and ONE score per span width, never a launch per window."""
+    recs = []                                                               # (clip, window of it, rows4, col, lags, span)
+    wins = [map_windows(n, window, step) for n in np.asarray(clip_nlag, np.int64).reshape(-1).tolist()]
+    for c, ws in enumerate(wins):
+        recs += [(c, w, [NBANDS * c + band for band in range(NBANDS)], col, n, window_span(spans[c], s, n // FRAME_LEN)) for w, (s, col, n) in enumerate(ws)]
+    verdicts = [[None] * len(ws) for ws in wins]
+    i = 0
+    while i < len(recs):
+        bases, ccols, j = set(), 0, i
+        while j < len(recs):                                                # grow the group while its hop table fits
+            lo, hi = recs[j][5]
+            grown = bases | {min(lo, CTR_END - 1)}
+            cols = max(ccols, hi - lo + recs[j][4] // FRAME_LEN - 1)
+            if j > i and ring.n * len(grown) * cols > MAP_HOP_BYTES:
+                break
+            bases, ccols, j = grown, cols, j + 1
+        group = recs[i:j]
+        res = search(eng, ring, n_own, corr, [r[4] for r in group], [r[5] for r in group], drift, P,
+                     at=(np.array([r[2] for r in group], np.int64), np.array([r[3] for r in group], np.int64)), pos0=[r[3] for r in group],
+                     device_pick=True)
+        for r, v in zip(group, res):
+            verdicts[r[0]][r[1]] = v
+        i = j
+    return [None if not ws else [make_map([None if v is None else v[k] for v in vs], ws, drift, confirm) for k in range(n_own)]
+            for ws, vs in zip(wins, verdicts)]
+
+
 def _torch():
     import torch
     return torch
 
 
-__all__ = ["DECOY_LABEL", "Presence", "check_decoys", "check_drift", "check_phases", "check_reach", "clip_spans", "decoy_keys", "drift_verdict",
-           "fold_model", "hop_model", "live_model", "live_span", "pick_hypotheses", "pick_phases", "presence_model", "score_model", "search", "skew_table", "slots",
-           "table_rows", "verdict", "warp_fold_model", "warp_score_model", "window_rows"]
+__all__ = ["DECOY_LABEL", "MAP_HOP_BYTES", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor", "check_decoys", "check_drift",
+           "check_map", "check_phases", "check_reach", "clip_spans", "consistent", "decoy_keys", "drift_verdict", "fold_model", "hop_model",
+           "live_model", "live_span", "make_map", "map_model", "map_windows", "pick_hypotheses", "pick_model", "pick_phases", "presence_model",
+           "score_model", "search", "search_map", "skew_table", "slots", "stretches", "table_rows", "verdict", "warp_fold_model", "warp_score_model",
+           "window_rows", "window_span"]
