@@ -139,6 +139,18 @@ if (set(PICK_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set(WAR
     raise NativeError(f"{PICK_HEADER_PATH} declares a name another header already has")
 globals().update(PICK_CONSTANTS)         # ES_PICK_MAX_H
 
+# The companion header of the coherent presence test, bound the same way into three more tables.
+COHERENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_coherent.h")
+try:
+    with open(COHERENT_HEADER_PATH) as _f:
+        COHERENT_DECLARATIONS, COHERENT_SIGNATURES, COHERENT_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{COHERENT_HEADER_PATH}: the coherent presence calls are bound from this header ({e})") from None
+if (set(COHERENT_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set(WARP_SIGNATURES) | set(LIVE_PRESENCE_SIGNATURES) | set(PICK_SIGNATURES))
+        or set(COHERENT_CONSTANTS) & (set(CONSTANTS) | set(PRESENCE_CONSTANTS) | set(WARP_CONSTANTS) | set(LIVE_PRESENCE_CONSTANTS) | set(PICK_CONSTANTS))):
+    raise NativeError(f"{COHERENT_HEADER_PATH} declares a name another header already has")
+globals().update(COHERENT_CONSTANTS)     # ES_MF_TILE, ES_COH_TILE, ES_COH_HDR_PN
+
 _lib = None
 
 
@@ -160,7 +172,8 @@ def load() -> ctypes.CDLL:
     if got != CONSTANTS["ES_ABI_VERSION"]:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
-    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES, **PICK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES, **PICK_SIGNATURES,
+                             **COHERENT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

@@ -3,6 +3,7 @@
 #include "es_internal.h"
 #include "es_exp_tab.h"
 
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -191,6 +192,9 @@ int es_set_tables(es_ctx* ctx, const double* ba, const double* tpl, const float*
         h.ntaps[b] = ntaps[b];
         if (b == 0 || ntaps[b] > ctx->max_ntaps) ctx->max_ntaps = ntaps[b];
         for (int k = 0; k < ntaps[b]; ++k) h.taps[b][k] = taps[b * ES_MAX_TAPS + k];
+        double e = 0.0;                                                     // c_b of include/echoseal_coherent.h: the taps in forward order
+        for (int k = ntaps[b] - 1; k >= 0; --k) e = e + (double)h.taps[b][k] * (double)h.taps[b][k];
+        ctx->mf_norm[b] = std::sqrt(191.0 * e);
     }
     uint16_t dpos[ES_POLAR_N];
     std::memset(dpos, 0, sizeof dpos);
@@ -1089,6 +1093,45 @@ int es_hop_score_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, int64_
     DeviceGuard g(ctx->device);
     return es_launch_hop_score(ctx, corr_dev, stride, nlag_dev, B, phase_dev, P, hop_dev, K, Ccols, n_origins, score_dev, origin_dev, rank_dev,
                                scratch_dev, (hipStream_t)stream);
+}
+
+// ---- the coherent presence test (include/echoseal_coherent.h) ----
+int es_mf_rows_batch(es_ctx* ctx, const double* y_dev, int64_t rows, int64_t T, const int32_t* len_dev, const uint8_t* band_dev,
+                     double* m_dev, double* a_dev, double* d_dev, void* stream)
+{
+    ES_REQUIRE_READY(ctx);
+    if (rows < 0 || T < 0) return fail(ctx, ES_EINVAL, "es_mf_rows_batch: negative count");
+    if (T > 0x7FFFFFFFll) return fail(ctx, ES_EINVAL, "es_mf_rows_batch: T above 2^31 - 1");
+    if (rows == 0 || T == 0) return ES_OK;
+    if (rows > 0x7FFFFFFFll / ((T + ES_MF_TILE - 1) / ES_MF_TILE))
+        return fail(ctx, ES_EINVAL, "es_mf_rows_batch: more than 2^31 - 1 blocks of (record, 256 outputs) in one call");
+    if (!y_dev || !len_dev || !band_dev || !m_dev || !a_dev || !d_dev) return fail(ctx, ES_EINVAL, "es_mf_rows_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_mf_rows(ctx, y_dev, rows, T, len_dev, band_dev, m_dev, a_dev, d_dev, (hipStream_t)stream);
+}
+
+int es_coherent_score_batch(es_ctx* ctx, const double* m_dev, const double* a_dev, const double* d_dev, int64_t rows, int64_t T,
+                            const int32_t* nslot_dev, int64_t B, const int32_t* phase_dev, int P, const uint8_t* ring_dev,
+                            const uint8_t* hop_dev, int64_t K, int64_t Ccols, uint32_t lo, int64_t n_origins, double* score_dev,
+                            int64_t* origin_dev, int32_t* rank_dev, void* scratch_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_rows(rows, T, B)) return fail(ctx, ES_EINVAL, (std::string("es_coherent_score_batch") + why).c_str());
+    if (K < 0 || Ccols < 0 || n_origins < 0) return fail(ctx, ES_EINVAL, "es_coherent_score_batch: negative count");
+    if (P < 1 || P > ES_FRAME_LEN) return fail(ctx, ES_EINVAL, "es_coherent_score_batch: P must be in 1 .. 1215");
+    const int64_t Jmax = T > 190 ? (T - 190) / ES_FRAME_LEN : 0, NB = n_origins / ES_HOP_ORIGINS + (n_origins % ES_HOP_ORIGINS != 0);
+    if (Ccols < n_origins + Jmax - 1)
+        return fail(ctx, ES_EINVAL, "es_coherent_score_batch: Ccols < n_origins + Jmax - 1 (Jmax = max(0, T - 190) / 1215)");
+    if (B == 0 || K == 0) return ES_OK;
+    if (K > 0x7FFFFFFFll / B || (NB > 0 && B * K > 0x7FFFFFFFll / NB))
+        return fail(ctx, ES_EINVAL, "es_coherent_score_batch: more than 2^31 - 1 blocks of (clip, key, 256 origins) in one call");
+    const bool scored = NB > 0 && Jmax > 0;                                 // otherwise no block reads rows, phases, ring or hop bytes
+    if (!nslot_dev || !score_dev || !origin_dev || !rank_dev || (NB > 0 && (!scratch_dev || !phase_dev || !ring_dev)) ||
+        (scored && (!m_dev || !a_dev || !d_dev || !hop_dev)))
+        return fail(ctx, ES_EINVAL, "es_coherent_score_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_coherent_score(ctx, m_dev, a_dev, d_dev, T, nslot_dev, B, phase_dev, P, ring_dev, hop_dev, K, Ccols, lo, n_origins, score_dev,
+                                    origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
 }
 
 // ---- presence along a table of per-slot offsets (include/echoseal_warp.h) ----

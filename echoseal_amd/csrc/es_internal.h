@@ -13,6 +13,7 @@
 #include "../../include/echoseal_warp.h"
 #include "../../include/echoseal_live_presence.h"
 #include "../../include/echoseal_pick.h"
+#include "../../include/echoseal_coherent.h"
 
 /* global memory by its address space: what the integer kernels (es_aead.hip, es_keyring.hip) read and write through */
 typedef __attribute__((address_space(1))) const uint8_t g_cu8;
@@ -43,6 +44,7 @@ struct es_ctx {
     es_frozen_mask frozen{};
     int n_info = 0;
     int max_ntaps = 0;                /* longest matched filter of the tables (picks the demodulator's instantiation) */
+    double mf_norm[ES_NBANDS] = {};   /* c_b of include/echoseal_coherent.h: sqrt(191 * sum of the band's squared taps), formed by es_set_tables */
 
     /* device-resident tables */
     es_band_tables* d_tables = nullptr;
@@ -305,6 +307,12 @@ int es_launch_warp_score_at(es_ctx* ctx, const double* corr, int64_t rows, int64
                             const int32_t* hop_row, int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st);
 /* the hypothesis list picked on the device (es_keyring.hip; include/echoseal_pick.h): a workgroup per record, B checked by the entry point */
 int es_launch_fold_pick(es_ctx* ctx, const double* fold, int64_t B, int64_t D, const int32_t* nwarp, int64_t H, int32_t* hyp, double* val, hipStream_t st);
+/* the coherent presence test (es_coherent_body.inc; include/echoseal_coherent.h): counts and both grids are checked by the entry points */
+int es_launch_mf_rows(es_ctx* ctx, const double* y, int64_t rows, int64_t T, const int32_t* len, const uint8_t* band, double* m, double* a,
+                      double* d, hipStream_t st);
+int es_launch_coherent_score(es_ctx* ctx, const double* m, const double* a, const double* d, int64_t T, const int32_t* nslot, int64_t B,
+                             const int32_t* phase, int P, const uint8_t* ring, const uint8_t* hop, int64_t K, int64_t Ccols, uint32_t lo,
+                             int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

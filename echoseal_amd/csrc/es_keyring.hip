@@ -21,6 +21,7 @@
 #include "es_internal.h"
 #include "es_crypto_dev.h"
 #include "es_wave.h"
+#include "es_hop_best.h"
 
 namespace {
 
@@ -429,29 +430,7 @@ __global__ __launch_bounds__(256) void es_phase_fold_kernel(const double* __rest
     fold_p[b * ES_FRAME_LEN + phi] = acc;
 }
 
-// what a lane, a block or a (clip, key) pair has found so far: `a` is replaced by `b` where b is scored and a is not, or b's score is
-// larger, or equal at a lower origin (an origin is owned by one lane, which keeps its earliest list entry itself)
-struct hs_best { double score; long long origin; int rank; };
-__device__ __forceinline__ bool hs_better(const hs_best& b, const hs_best& a)
-{
-    return b.origin >= 0 && (a.origin < 0 || b.score > a.score || (b.score == a.score && b.origin < a.origin));
-}
-
-// the best of a block's 256 lanes, to slot blockIdx.x of the scratch arrays: the end of both score kernels
-__device__ __forceinline__ void hs_block_best(hs_best* red, const hs_best& best, int tid, double* __restrict__ sc_score,
-        long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
-{
-    red[tid] = best;
-    __syncthreads();
-    #pragma unroll 1
-    for (int w = HS_ORIGINS / 2; w > 0; w >>= 1) {                                         // a maximum under a total order: any shape gives the same winner
-        if (tid < w && hs_better(red[tid + w], red[tid])) red[tid] = red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        sc_score[blockIdx.x] = red[0].score; sc_origin[blockIdx.x] = red[0].origin; sc_rank[blockIdx.x] = red[0].rank;
-    }
-}
+// hs_best, hs_better, hs_block_best: what a lane, a block or a (clip, key) pair has found so far (es_hop_best.h)
 
 // One block per (clip b, key k, chunk of 256 origins), one lane per origin.  Per list entry the [J][4] values of its phase pass through
 // LDS in tiles of HS_TILE slots; the lane adds vals[j][hop[k][origin + j]] slot by slot, so neighbouring lanes read neighbouring hop bytes.
@@ -864,15 +843,8 @@ int es_launch_phase_fold(es_ctx* ctx, const double* corr, int64_t stride, const 
     return es_launch(ctx, es_phase_fold_kernel, (unsigned)(B * 5), 256, 0, st, corr, (long long)stride, nlag, fold);
 }
 
-// the caller's scratch as the three arrays of the blocks' bests, one slot per (clip, key, chunk), and the launch that reduces them
-struct hs_scratch {
-    long long NB, pairs, slots;
-    double* score; long long* origin; long long* rank;
-    hs_scratch(void* scratch, int64_t B, int64_t K, int64_t n_origins)
-        : NB((n_origins + ES_HOP_ORIGINS - 1) / ES_HOP_ORIGINS), pairs((long long)B * K), slots(pairs * NB), score((double*)scratch),
-          origin((long long*)scratch + slots), rank((long long*)scratch + 2 * slots) {}
-};
-static int es_launch_hop_best(es_ctx* ctx, const hs_scratch& sc, double* score, int64_t* origin, int32_t* rank, hipStream_t st)
+// the launch that reduces the blocks' bests in the caller's scratch (hs_scratch: es_hop_best.h), for the score kernels here and in es_coherent_body.inc
+int es_launch_hop_best(es_ctx* ctx, const hs_scratch& sc, double* score, int64_t* origin, int32_t* rank, hipStream_t st)
 {
     return es_launch(ctx, es_hop_best_kernel, (unsigned)((sc.pairs + 255) / 256), 256, 0, st, (const double*)sc.score, (const long long*)sc.origin,
                      (const long long*)sc.rank, sc.pairs, sc.NB, score, (long long*)origin, rank);
@@ -933,3 +905,6 @@ int es_launch_fold_pick(es_ctx* ctx, const double* fold, int64_t B, int64_t D, c
 {
     return es_launch(ctx, es_fold_pick_kernel, (unsigned)B, FP_BLOCK, 0, st, fold, (long long)D, nwarp, (int)H, hyp, val);
 }
+
+// the coherent presence test (include/echoseal_coherent.h): its two kernels and launchers, a file of their own in this unit
+#include "es_coherent_body.inc"

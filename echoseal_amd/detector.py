@@ -405,6 +405,73 @@ class WatermarkDetector:
                     out[ids[i]] = res[k]
         return out
 
+    # ------------------------------------------------------------------ the coherent presence test
+    def presence_coherent(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = FRAME_LEN,
+                          decoys: int = 32):
+        return self.presence_coherent_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys)[0]
+
+    def presence_coherent_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = FRAME_LEN, decoys: int = 32) -> list:
+        """presence_batch with a statistic that also works on loud hosts: -> per clip a presence.Presence, or None for a clip without
+        one whole slot.  Per hypothesised (key, counter) the receiver knows 191 chips of every frame: the 63 of the preamble and the 128
+        of the header, the counter's low 16 bits over 8 chips each times the key's header PN.  The score of a key is the mean, over the
+        clip's frame slots on one 1215-sample grid, of the normalised correlation of all 191 with the matched-filter row of the band
+        the key hops to (presence.coherent_score_model), maximised over the span and over EVERY phase of the grid (phases = 1215, the
+        identity list): no keyless guess of the phase is needed, which is what failed on loud hosts.  phases < 1215 searches the top
+        of presence_batch's keyless fold instead: the cheap mode, kept for comparison.  The verdict is presence_batch's
+        (presence.verdict): strictly above every decoy, every key scored on the same rows, span and phases; statistical, never
+        authenticated.  Presence.frames is J = max(0, n - 189 - L_max) // 1215 for a clip of n samples and a longest matched filter of
+        L_max taps.  ctr0 as for presence_batch.
+        The front is presence_batch's (cut_launches; mixed rates, int16 and unequal lengths included: equal lengths run bpf, ragged
+        ones sync_ragged, whose y is kept); per launch, for each span, ONE mf_rows, ONE hop window over the ring [key] + decoys and ONE
+        score call (es_mf_rows_batch, es_coherent_score_batch).  session_nonce and the traces are not touched.  ValueError before any
+        engine exists: what presence_batch refuses of span, ctr0, phases and decoys, the reach of the span judged with this J."""
+        from . import presence as pr
+        import torch
+        from .tables import pack_tables
+        clips = list(clips)
+        fs_list = rate_list(fs_in, len(clips))
+        P, R = pr.check_phases(phases), pr.check_decoys(decoys)
+        spans = pr.clip_spans(ctr0, span, len(clips))
+        g, _ = pr.mf_tables(tables=pack_tables(self.fs_target))
+        for c, f, s in zip(clips, fs_list, spans):                          # refused by name before any engine exists
+            pr.check_coherent_reach(s, resampled_length(int(np.size(c)), int(f), self.fs_target), g)
+        out: list = [None] * len(clips)
+        band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
+        nb = band_ids.size
+        for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
+            ids = [i for i, s in enumerate(spans) if s == (lo, hi)]
+            for la in cut_launches([clips[i] for i in ids], [fs_list[i] for i in ids], self.fs_target, nb, self._conditioned):
+                J = np.array([pr.coherent_slots(n, g) for n in la.sizes], np.int64)
+                if not J.max():
+                    continue
+                eng = self.engine
+                x, sizes = la.rows(eng, nb)
+                bid = dev(eng, np.tile(band_ids, len(sizes)), np.uint8)
+                M = max(sizes)
+                lens = np.repeat(np.array(sizes, np.int32), nb)
+                if min(sizes) < M:
+                    sy = eng.sync_ragged(x, torch.from_numpy(lens), bid, keep_corr=P < FRAME_LEN)
+                    y, corr = sy.y, sy.corr
+                else:
+                    y = eng.bpf(x[:, :M], bid)
+                    corr = eng.xcorr(y, bid) if P < FRAME_LEN else None
+                if P < FRAME_LEN:                                           # the cheap mode: the top of the keyless fold (presence_batch's list)
+                    fold = eng.phase_fold(corr, np.array(sizes, np.int64) - (PRE_L - 1)).cpu().numpy()
+                    lists = [pr.pick_phases(f, P) for f in fold]
+                else:
+                    lists = [list(range(FRAME_LEN))] * len(sizes)
+                rows = eng.mf_rows(y, lens, bid)
+                ring = self._presence_ring(R)
+                base = min(lo, CTR_END - 1)
+                hop = eng.hop_window(ring, [base], max(hi - lo + max(0, y.shape[1] - 190) // FRAME_LEN - 1, 0))
+                score, origin, rank = (t.cpu().numpy() for t in eng.coherent_score(*rows, J, np.array(lists, np.int32), ring, hop, base, hi - lo))
+                if self._presence_rows is not None:
+                    self._presence_rows.append(([ids[i] for i in la.idx], y.cpu().numpy(), np.array(sizes, np.int64)))
+                for k, i in enumerate(la.idx):
+                    if J[k]:
+                        out[ids[i]] = pr.verdict(score[k], origin[k], rank[k], lo, lists[k], int(J[k]))
+        return out
+
     def _presence_ring(self, decoys: int, keys=None):
         """The ring [own keys] + the first `decoys` public decoy keys (keys None: this detector's key alone), derived once per engine,
         count and key list."""

@@ -678,6 +678,52 @@ class RxEngine(TxChain, MonitorChain):
                    scratch if scratch.numel() else None)
         return score, origin, rank
 
+    # ------------------------------------------------------------------ the coherent presence test (include/echoseal_coherent.h)
+    def mf_rows(self, y: torch.Tensor, lens, bands, *, out=None):
+        """The keyless rows of the coherent presence test (es_mf_rows_batch; presence.mf_rows_model is the host twin): y float64
+        [rows, T] band-passed records (bpf, or sync_ragged's y), lens [rows] the samples of each (clamped to [0, T]; nothing at or past
+        them is read), bands [rows] their BAND_PLAN indices -> (M, A, D) float64 [rows, T]: the matched-filter row, the preamble sum at
+        every start and its normaliser, written where they are defined (M: t + L <= len; A, D: s + 190 + L <= len) and nowhere else.
+        out: three tensors to write into (what is not defined keeps its value); new ones are zero-filled."""
+        if y.dim() != 2 or y.dtype != torch.float64 or not y.is_contiguous() or y.device != self.device:
+            raise ValueError("y must be a contiguous float64 [rows, T] tensor on the engine's device")
+        rows, T = y.shape
+        lens, bands = self._lens(lens, rows), self._dev(bands, torch.uint8).reshape(-1)
+        if bands.numel() != rows:
+            raise ValueError("bands: one band index per row")
+        M, A, D = out if out is not None else (torch.zeros((rows, T), dtype=torch.float64, device=self.device) for _ in range(3))
+        if any(t.shape != (rows, T) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device for t in (M, A, D)):
+            raise ValueError("out: three contiguous float64 [rows, T] tensors on the engine's device")
+        self._call("es_mf_rows_batch", y, rows, T, lens, bands, M, A, D)
+        return M, A, D
+
+    def coherent_score(self, M: torch.Tensor, A: torch.Tensor, D: torch.Tensor, nslot, phases, ring: KeyRing, hop: torch.Tensor, lo: int,
+                       n_origins: int):
+        """The keyed score of the coherent presence test (es_coherent_score_batch; presence.coherent_score_model is the host twin).
+        M, A, D: mf_rows' three [rows, T] tensors, clip b in rows 4 b .. 4 b + 3 in BAND_PLAN order; nslot [B] the slots J of each clip
+        (presence.coherent_slots; clamped to (T - 190) // 1215); phases int [B, P], 1 <= P <= 1215; ring: the K keys, whose header PN
+        signs the header sums; hop uint8 [K, Ccols] (or hop_window's [K, 1, Ccols]): column i = the band of counter lo + i under key row
+        k, Ccols >= n_origins + max(0, T - 190) // 1215 - 1; lo: the counter of column 0; origins 0 .. n_origins - 1 are searched
+        -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K]) as hop_score gives them."""
+        for t in (M, A, D):
+            if t.dim() != 2 or t.shape != M.shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("M, A, D must be contiguous float64 [rows, T] tensors of one shape on the engine's device")
+        nslot = self._dev(nslot, torch.int32).reshape(-1)
+        B = nslot.numel()
+        if 4 * B > M.shape[0]:
+            raise ValueError("M, A, D: four rows per clip, row 4 * clip + band")
+        phases = self._dev(phases, torch.int32)
+        if phases.dim() != 2 or phases.shape[0] != B:
+            raise ValueError("phases: int [B, P], one list per clip")
+        if not 0 <= int(lo) < 1 << 32:
+            raise ValueError("lo: the counter of hop column 0, in [0, 2^32)")
+        hop, K, n_origins, score, origin, rank, scratch = self._score_io(hop, B, n_origins)
+        if K != ring.n:
+            raise ValueError("hop: one row per key of the ring")
+        self._call("es_coherent_score_batch", M, A, D, M.shape[0], M.shape[1], nslot, B, phases, phases.shape[1], ring.ring, hop, K, hop.shape[1],
+                   int(lo), n_origins, score, origin, rank, scratch if scratch.numel() else None)
+        return score, origin, rank
+
     # ------------------------------------------------------------------ presence under clock drift (DESIGN 4.24; include/echoseal_warp.h)
     def _warp_table(self, warp, nwarp, nslot, B: int):
         """The table of per-slot offsets of a warp call, checked: -> (warp int32 [B, D, Jw], nwarp int32 [B], nslot int32 [B], D, Jw)."""

@@ -21,6 +21,10 @@ The timeline: which parts of a clip carry the mark, and where it w
 (es_fold_pick_batch; include/echoseal_pick.h); map_windows cuts a clip into overlapping windows, each a record of the _at calls with its own
 span; stretches joins the detected windows that lie on one frame grid and names the splices between confirmed stretches; map_model is the
 whole call on the host, search_map its launches.
+
+The coherent test: the preamble and the keyed header of every frame start on matched-filter rows, over every phase.
+mf_rows_model / coherent_score_model are the twins of es_mf_rows_batch / es_coherent_score_batch (include/echoseal_coherent.h),
+coherent_model the whole of WatermarkDetector.presence_coherent for one clip on the host.
 """
 from __future__ import annotations
 
@@ -705,13 +709,193 @@ def search_map(eng, ring, n_own: int, corr, clip_nlag, spans, drift: float, P: i
             for ws, vs in zip(wins, verdicts)]
 
 
+# ---- the coherent presence test: preamble and keyed header on matched-filter rows, every phase (include/echoseal_coherent.h) ----
+HDR_L, HDR_REPEAT = 128, 8       # the header: the counter's low 16 bits, each over 8 chips, times the key's header PN
+COH_SPAN = PRE_L + HDR_L - 1     # 190: the last chip of a frame start that the receiver can know, from its first
+
+
+def mf_tables(fs: int = 48_000, tables=None):
+    """What the coherent rows need of an engine's tables (tables.pack_tables(fs), or `tables` = its tuple) -> (g, c): g[b] float64 [L_b],
+    g[b][i] = taps[b][L_b - 1 - i], the matched filter in forward order; c float64 [4], c[b] = sqrt(191 * sum_i g[b][i]^2), the sum taken
+    term by term from +0.0 in ascending i."""
+    if tables is None:
+        from .tables import pack_tables
+        tables = pack_tables(fs)
+    taps, ntaps = tables[2], tables[3]
+    g = [np.asarray(taps[b][:int(ntaps[b])], np.float32)[::-1].astype(np.float64) for b in range(NBANDS)]
+    c = np.zeros(NBANDS, np.float64)
+    for b in range(NBANDS):
+        s = np.float64(0.0)
+        for v in g[b]:
+            s = s + v * v
+        c[b] = np.sqrt(np.float64(COH_SPAN + 1) * s)
+    return g, c
+
+
+def coherent_slots(samples: int, g) -> int:
+    """J of a clip of `samples` samples: max(0, n - 189 - L_max) // 1215 -- every start phi + 1215 j, phi <= 1214, j < J, is then
+    defined in every band."""
+    return max(0, int(samples) - (COH_SPAN - 1) - max(len(t) for t in g)) // FRAME_LEN
+
+
+def check_coherent_reach(span, samples: int, g) -> tuple[int, int]:
+    """check_reach with the coherent J: the window of the last origin, hi - 1 + J - 1, must be a counter."""
+    lo, hi = check_span(span)
+    J = coherent_slots(samples, g)
+    if hi > lo and hi + J - 1 > CTR_END:
+        raise ValueError(f"span = ({lo}, {hi}): a clip of {int(samples)} samples has {J} frames, and hi + {J} - 1 > 2^32 "
+                         "(spans that wrap past 2^32 are out of scope)")
+    return lo, hi
+
+
+def mf_rows_model(y, lens, bands, g, c):
+    """es_mf_rows_batch in NumPy: y float64 [rows, T], lens [rows] (clamped to [0, T]), bands [rows] -> (M, A, D) float64 [rows, T], NaN
+    where a value is not defined.  With L = len(g[band]), W = 190 + L and n the row's length:
+        M[t] = sum_{i < L} y[t + i] g[i]                   t + L <= n
+        A[s] = sum_{q < 63} p_q M[s + q]                   s + W <= n        p = the preamble symbols, +-1
+        D[s] = sqrt(sum_{m < W} y[s + m]^2) c[band]        s + W <= n
+    every sum term by term from +0.0 in ascending index, a product formed and then added.  Nothing at or past n is read."""
+    from .utils import mseq_63
+    y = np.asarray(y, np.float64)
+    if y.ndim != 2:
+        raise ValueError("y: float64 [rows, T]")
+    rows, T = y.shape
+    lens = np.clip(np.asarray(lens, np.int64).reshape(-1), 0, T)
+    bands = np.asarray(bands, np.int64).reshape(-1)
+    if lens.size != rows or bands.size != rows or (rows and (bands.min() < 0 or bands.max() >= NBANDS)):
+        raise ValueError("lens, bands: one length and one band index 0 .. 3 per row")
+    pre = 2.0 * mseq_63().astype(np.float64) - 1.0
+    M, A, D = (np.full((rows, T), np.nan, np.float64) for _ in range(3))
+    for r in range(rows):
+        n, gb = int(lens[r]), g[int(bands[r])]
+        L = len(gb)
+        nm, ns = n - L + 1, n - (COH_SPAN + L) + 1
+        if nm <= 0:
+            continue
+        m = np.zeros(nm, np.float64)
+        for i in range(L):
+            m = m + y[r, i:i + nm] * gb[i]
+        M[r, :nm] = m
+        if ns <= 0:
+            continue
+        a, q = np.zeros(ns, np.float64), np.zeros(ns, np.float64)
+        for k in range(PRE_L):
+            a = a + pre[k] * m[k:k + ns]
+        for k in range(COH_SPAN + L):
+            q = q + y[r, k:k + ns] * y[r, k:k + ns]
+        A[r, :ns], D[r, :ns] = a, np.sqrt(q) * c[int(bands[r])]
+    return M, A, D
+
+
+def header_signs(keys) -> np.ndarray:
+    """u float64 [K, 128], +-1: the header PN of each master key, as ring bytes 272 .. 287 hold it (MSB first)."""
+    from .crypto import SecureChannel
+    return np.stack([2.0 * np.asarray(SecureChannel(bytes(k)).pn_bits(0, HDR_L), np.float64) - 1.0 for k in keys]) if len(keys) else np.zeros((0, HDR_L))
+
+
+def ring_signs(hdr_pn) -> np.ndarray:
+    """The same from packed rows: hdr_pn uint8 [K, 16] (KeyRing.hdr_pn)."""
+    return 2.0 * np.unpackbits(np.asarray(hdr_pn, np.uint8).reshape(-1, HDR_L // 8), axis=1).astype(np.float64) - 1.0
+
+
+def coherent_score_model(M, A, D, nslot, phases, u, hop, lo: int, n_origins: int):
+    """es_coherent_score_batch in NumPy.  Clip b owns rows 4 b .. 4 b + 3 of M, A, D [rows, T]; nslot [B] its slots J (clamped to
+    [0, max(0, T - 190) // 1215]: no index can pass a row); phases int [B, P]; u [K, 128] +-1 (header_signs); hop uint8 [K, Ccols], column i
+    the band of counter lo + i; origins 0 .. n_origins - 1.  For key k, origin o, entry p with phi = phases[b][p], and per slot j:
+        c = lo + o + j, band = hop[k][o + j], s = phi + 1215 j, v = c & 0xFFFF, sigma_i = 2 ((v >> (15 - i)) & 1) - 1
+        Z_i = sum_{m < 8} u[k][8 i + m] M[band][s + 63 + 8 i + m]
+        N = (A[band][s] + sum_{i < 8} sigma_i Z_i) + sum_{i = 8 .. 15} sigma_i Z_i,     R = N / D[band][s], +0.0 where D == 0
+        S(k, o, p) = (sum_{j < J} R) / J
+    -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K]): the largest S, ties to the lowest origin, then the earliest entry;
+    (-inf, -1, -1) where nothing is scored (J == 0, no origin whose window is free of bytes above 3, no entry in 0 .. 1214).  Vectorised
+    over the phase list; the two header sums are tabulated per (band, byte) present, each entry summed in the order above."""
+    M, A, D = (np.asarray(a, np.float64) for a in (M, A, D))
+    if M.ndim != 2 or A.shape != M.shape or D.shape != M.shape:
+        raise ValueError("M, A, D: float64 [rows, T], the three of one shape")
+    T = M.shape[1]
+    nslot = np.clip(np.asarray(nslot, np.int64).reshape(-1), 0, max(0, T - COH_SPAN) // FRAME_LEN)
+    B = nslot.size
+    if M.shape[0] < NBANDS * B:
+        raise ValueError("M, A, D: four rows per clip")
+    phases = np.asarray(phases, np.int64).reshape(B, -1)
+    u, hop = np.asarray(u, np.float64).reshape(-1, HDR_L), np.asarray(hop, np.uint8)
+    K, n_origins, lo = hop.shape[0], int(n_origins), int(lo)
+    if u.shape[0] != K:
+        raise ValueError("u: one row of 128 signs per hop row")
+    score = np.full((B, K), -np.inf, np.float64)
+    origin = np.full((B, K), -1, np.int64)
+    rank = np.full((B, K), -1, np.int32)
+    bit = lambda v, i: 2.0 * ((v >> (7 - i)) & 1) - 1.0                     # sign i of a byte, MSB first
+    for b, J in enumerate(nslot.tolist()):
+        if J == 0 or n_origins == 0:
+            continue
+        if hop.shape[1] < n_origins + J - 1:
+            raise ValueError("hop: fewer than n_origins + J - 1 columns")
+        good = np.flatnonzero((phases[b] >= 0) & (phases[b] < FRAME_LEN))
+        if not good.size:
+            continue
+        phi = phases[b][good]
+        Mb, Ab, Db = (a[NBANDS * b:NBANDS * b + NBANDS] for a in (M, A, D))
+        for k in range(K):
+            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]
+            scored = np.flatnonzero((win < NBANDS).all(axis=0))
+            if not scored.size:
+                continue
+            acc = np.zeros((scored.size, good.size), np.float64)
+            for j in range(J):
+                s = phi + FRAME_LEN * j
+                band = (win[j, scored] & 3).astype(np.int64)
+                v = (lo + scored + j) & 0xFFFF
+                hi8, lo8 = v >> 8, v & 0xFF
+                Z = np.zeros((NBANDS, 16, s.size), np.float64)
+                for i in range(16):
+                    for m in range(HDR_REPEAT):
+                        Z[:, i] = Z[:, i] + u[k, 8 * i + m] * Mb[:, s + (PRE_L + 8 * i + m)]
+                tabs = []
+                for byte, half in ((hi8, 0), (lo8, 8)):                      # the sum of a byte's eight terms, per value present
+                    vals, inv = np.unique(byte, return_inverse=True)
+                    t = np.zeros((NBANDS, vals.size, s.size), np.float64)
+                    for i in range(8):
+                        t = t + bit(vals, i)[None, :, None] * Z[:, half + i][:, None, :]
+                    tabs.append(t[band, inv])                                # [scored, P]
+                num = (Ab[:, s][band] + tabs[0]) + tabs[1]
+                den = Db[:, s][band]
+                acc = acc + np.where(den == 0.0, 0.0, num / np.where(den == 0.0, 1.0, den))
+            S = acc / np.float64(J)
+            for col, p in enumerate(good.tolist()):
+                i = int(np.argmax(S[:, col]))                                # the first of equal values: the lowest origin
+                if origin[b, k] < 0 or S[i, col] > score[b, k] or (S[i, col] == score[b, k] and scored[i] < origin[b, k]):
+                    score[b, k], origin[b, k], rank[b, k] = S[i, col], scored[i], p
+    return score, origin, rank
+
+
+def coherent_model(y4, n: int, key: bytes, *, span=(0, 4096), phases=FRAME_LEN, decoys: int = 32, fs: int = 48_000, tables=None) -> Presence | None:
+    """WatermarkDetector.presence_coherent from one clip's four band-passed rows y4 [4, >= n] (BAND_PLAN order), on the host: the rows,
+    the hop rows and header signs of `key` and the decoys, the score over every phase and the verdict.  phases: 1215, every phase in
+    order, or an explicit list (what the keyless fold picked).  None where the clip has no whole slot (J == 0)."""
+    y4 = np.asarray(y4, np.float64)
+    n = min(max(int(n), 0), y4.shape[1])
+    g, c = mf_tables(fs, tables)
+    lo, hi = check_coherent_reach(span, n, g)
+    plist = list(range(FRAME_LEN)) if isinstance(phases, (int, np.integer)) and int(phases) == FRAME_LEN else [int(p) for p in phases]
+    J = coherent_slots(n, g)
+    if J == 0:
+        return None
+    keys = [bytes(key)] + decoy_keys(decoys)
+    M, A, D = mf_rows_model(y4[:NBANDS, :n], [n] * NBANDS, range(NBANDS), g, c)
+    hop = hop_model(keys, lo, max(hi - lo + J - 1, 0))
+    score, origin, rank = coherent_score_model(M, A, D, [J], [plist], header_signs(keys), hop, lo, hi - lo)
+    return verdict(score[0], origin[0], rank[0], lo, plist, J)
+
+
 def _torch():
     import torch
     return torch
 
 
-__all__ = ["DECOY_LABEL", "MAP_HOP_BYTES", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor", "check_decoys", "check_drift",
-           "check_map", "check_phases", "check_reach", "clip_spans", "consistent", "decoy_keys", "drift_verdict", "fold_model", "hop_model",
-           "live_model", "live_span", "make_map", "map_model", "map_windows", "pick_hypotheses", "pick_model", "pick_phases", "presence_model",
-           "score_model", "search", "search_map", "skew_table", "slots", "stretches", "table_rows", "verdict", "warp_fold_model", "warp_score_model",
-           "window_rows", "window_span"]
+__all__ = ["COH_SPAN", "DECOY_LABEL", "MAP_HOP_BYTES", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor",
+           "check_coherent_reach", "check_decoys", "check_drift", "check_map", "check_phases", "check_reach", "clip_spans", "coherent_model",
+           "coherent_score_model", "coherent_slots", "consistent", "decoy_keys", "drift_verdict", "fold_model", "header_signs", "hop_model",
+           "live_model", "live_span", "make_map", "map_model", "map_windows", "mf_rows_model", "mf_tables", "pick_hypotheses", "pick_model",
+           "pick_phases", "presence_model", "ring_signs", "score_model", "search", "search_map", "skew_table", "slots", "stretches",
+           "table_rows", "verdict", "warp_fold_model", "warp_score_model", "window_rows", "window_span"]
