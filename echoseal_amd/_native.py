@@ -151,6 +151,20 @@ if (set(COHERENT_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set
     raise NativeError(f"{COHERENT_HEADER_PATH} declares a name another header already has")
 globals().update(COHERENT_CONSTANTS)     # ES_MF_TILE, ES_COH_TILE, ES_COH_HDR_PN
 
+# The companion header of the coherent score over records anywhere in a table of rows, bound the same way into three more tables.
+COHERENT_AT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "echoseal_coherent_at.h")
+try:
+    with open(COHERENT_AT_HEADER_PATH) as _f:
+        COHERENT_AT_DECLARATIONS, COHERENT_AT_SIGNATURES, COHERENT_AT_CONSTANTS = bind_header(_f.read())
+except OSError as e:
+    raise NativeError(f"{COHERENT_AT_HEADER_PATH}: the coherent score over records is bound from this header ({e})") from None
+if (set(COHERENT_AT_SIGNATURES) & (set(SIGNATURES) | set(PRESENCE_SIGNATURES) | set(WARP_SIGNATURES) | set(LIVE_PRESENCE_SIGNATURES) | set(PICK_SIGNATURES)
+                                   | set(COHERENT_SIGNATURES))
+        or set(COHERENT_AT_CONSTANTS) & (set(CONSTANTS) | set(PRESENCE_CONSTANTS) | set(WARP_CONSTANTS) | set(LIVE_PRESENCE_CONSTANTS) | set(PICK_CONSTANTS)
+                                         | set(COHERENT_CONSTANTS))):
+    raise NativeError(f"{COHERENT_AT_HEADER_PATH} declares a name another header already has")
+globals().update(COHERENT_AT_CONSTANTS)  # none so far
+
 _lib = None
 
 
@@ -173,7 +187,7 @@ def load() -> ctypes.CDLL:
         raise NativeError(f"{LIB_PATH} reports ABI version {got}, this package binds version {CONSTANTS['ES_ABI_VERSION']} "
                           "(table strides and signatures differ between versions): rebuild it with `make -C echoseal_amd/csrc`")
     for name, (res, args) in {**SIGNATURES, **PRESENCE_SIGNATURES, **WARP_SIGNATURES, **LIVE_PRESENCE_SIGNATURES, **PICK_SIGNATURES,
-                             **COHERENT_SIGNATURES}.items():
+                             **COHERENT_SIGNATURES, **COHERENT_AT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args

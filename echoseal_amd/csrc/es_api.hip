@@ -1228,6 +1228,34 @@ int es_warp_score_at_batch(es_ctx* ctx, const double* corr_dev, int64_t rows, in
                                    H, hop_dev, K, HR, Ccols, hop_row_dev, n_origins, score_dev, origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
 }
 
+// ---- the coherent score over records anywhere in the three tables (include/echoseal_coherent_at.h) ----
+int es_coherent_score_at_batch(es_ctx* ctx, const double* m_dev, const double* a_dev, const double* d_dev, int64_t rows, int64_t stride,
+                               const int64_t* row_dev, const int64_t* col_dev, const int32_t* nslot_dev, int64_t B, int64_t Jw,
+                               const int32_t* phase_dev, int P, const uint8_t* ring_dev, const uint8_t* hop_dev, int64_t K, int64_t HR,
+                               int64_t Ccols, const int32_t* hop_row_dev, const uint32_t* lo_dev, int64_t n_origins, double* score_dev,
+                               int64_t* origin_dev, int32_t* rank_dev, void* scratch_dev, void* stream)
+{
+    if (!ctx) return ES_EINVAL;
+    if (const char* why = presence_table(rows, stride, B)) return fail(ctx, ES_EINVAL, (std::string("es_coherent_score_at_batch") + why).c_str());
+    if (Jw < 0 || K < 0 || Ccols < 0 || n_origins < 0) return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: negative count");
+    if (P < 1 || P > ES_FRAME_LEN) return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: P must be in 1 .. 1215");
+    if (HR < 1 || HR > 0x7FFFFFFFll) return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: HR must be in 1 .. 2^31 - 1");
+    const int64_t NB = n_origins / ES_HOP_ORIGINS + (n_origins % ES_HOP_ORIGINS != 0);
+    if (Ccols - n_origins < Jw - 1)                                         // (the counts are >= 0 here: a difference cannot wrap, their sum could)
+        return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: Ccols < n_origins + Jw - 1");
+    if (B == 0 || K == 0) return ES_OK;
+    if (K > 0x7FFFFFFFll / B || (NB > 0 && B * K > 0x7FFFFFFFll / NB))
+        return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: more than 2^31 - 1 blocks of (record, key, 256 origins) in one call");
+    const bool scored = NB > 0 && Jw > 0 && rows > 0 && stride >= ES_FRAME_LEN + 190;   // otherwise J == 0 everywhere: no block reads the tables or hop bytes
+    if (!score_dev || !origin_dev || !rank_dev ||
+        (NB > 0 && (!scratch_dev || !row_dev || !col_dev || !nslot_dev || !hop_row_dev || !lo_dev || !phase_dev || !ring_dev)) ||
+        (scored && (!m_dev || !a_dev || !d_dev || !hop_dev)))
+        return fail(ctx, ES_EINVAL, "es_coherent_score_at_batch: null pointer");
+    DeviceGuard g(ctx->device);
+    return es_launch_coherent_score_at(ctx, m_dev, a_dev, d_dev, rows, stride, row_dev, col_dev, nslot_dev, B, Jw, phase_dev, P, ring_dev, hop_dev, K,
+                                       HR, Ccols, hop_row_dev, lo_dev, n_origins, score_dev, origin_dev, rank_dev, scratch_dev, (hipStream_t)stream);
+}
+
 // ---- the hypothesis list picked on the device (include/echoseal_pick.h) ----
 int es_fold_pick_batch(es_ctx* ctx, const double* fold_dev, int64_t B, int64_t D, const int32_t* nwarp_dev, int64_t H, int32_t* hyp_dev,
                        double* val_dev, void* stream)

@@ -6,6 +6,8 @@
 // Two kernels.  es_mf_rows_kernel: the keyless rows of a band-passed record, a tiled FIR with the taps and a tile of samples in LDS, one
 // lane per output.  es_coherent_score_kernel: one lane per counter origin, as es_hop_score_kernel; what the lanes of a (list entry, slot)
 // share -- the preamble sum, the normaliser and the sixteen 8-chip header sums of each band -- passes through LDS in tiles of slots.
+// es_coherent_score_at_kernel (include/echoseal_coherent_at.h; DESIGN 4.28) is the same device body over records that name their rows,
+// column, hop row and counter base: the windows of a clip's timeline on the clip's own rows.
 //
 // Float64 throughout; every sum is added term by term in ascending order from +0.0 by ONE lane, a product formed and then added (the unit
 // is built with -ffp-contract=off), so a plain host loop gives the same bits.  No atomic, no workspace of the context.
@@ -93,36 +95,34 @@ __device__ __forceinline__ double byte_sum(const double* z, unsigned byte)
     return s;
 }
 
-// One block per (clip b, key k, chunk of 256 origins), one lane per origin o: its counter at slot j is lo + o + j.  Per list entry and tile
-// of CT slots: (1) every lane forms four of the tile's CT x 4 x 16 header sums Z from m and the key's header PN, and the tile's hop bytes
-// and a, d go to LDS; (2) STRAIGHT false: (a + H) is tabulated per (slot, band, high byte) -- the block's counters at one slot are 256
-// consecutive values, so two high bytes; (3) the lane adds its slot terms in ascending slot order.  STRAIGHT true is the definition
-// written out, 17 signed adds per (origin, slot); both give the same bits, because a table entry is summed in the defined order.
+// The one body of es_coherent_score_kernel and es_coherent_score_at_kernel (DESIGN 4.14, 4.28): a block serves (record, key, chunk of 256
+// origins), one lane per origin; the kernels differ only in where a record's rows, hop bytes and counters start, which they hand over as
+//   mine   the index in m, a, d of sample 0 of the record's row of band (tid >> 4) & 3 -- the one band this lane stages (64-bit: a row
+//          base may pass 2^31)
+//   J      the record's slots, decided by the kernel before any read;  phase_p its P list entries
+//   hop    column 0 of the chunk's hop bytes under this key, hop_n how many of them exist;  ctr0 lane 0's counter at slot 0
+//   pn     the eight PN bits of header bit tid & 15 under this key, MSB first
+// Its counter at slot j is ctr0 + tid + j.  Per list entry and tile of CT slots: (1) every lane forms four of the tile's CT x 4 x 16 header
+// sums Z from m and the key's header PN, and the tile's hop bytes and a, d go to LDS; (2) STRAIGHT false: (a + H) is tabulated per (slot,
+// band, high byte) -- the block's counters at one slot are 256 consecutive values, so two high bytes whatever ctr0 is; (3) the lane adds
+// its slot terms in ascending slot order.  STRAIGHT true is the definition written out, 17 signed adds per (origin, slot); both give the
+// same bits, because a table entry is summed in the defined order.
 template <bool STRAIGHT>
-__global__ __launch_bounds__(256) void es_coherent_score_kernel(const double* __restrict__ m_p, const double* __restrict__ a_p,
-        const double* __restrict__ d_p, long long T, const int32_t* __restrict__ nslot_p, const int32_t* __restrict__ phase_p, int P,
-        const uint8_t* __restrict__ ring_p, const uint8_t* __restrict__ hop_p, long long K, long long Ccols, uint32_t lo, long long n_origins,
-        long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+__device__ __forceinline__ void coherent_score_body(const double* __restrict__ m_p, const double* __restrict__ a_p, const double* __restrict__ d_p,
+        long long mine, long long J, g_cu8* hop, long long hop_n, uint32_t ctr0, unsigned pn, const int32_t* __restrict__ phase_p, int P, bool live,
+        long long origin, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
 {
     __shared__ double sh[CT * ES_NBANDS * CS_REC];
     __shared__ uint8_t hops[CO + CT];
     __shared__ hs_best red[CO];
     const int tid = threadIdx.x;
-    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
-    const long long origin = chunk * CO + tid;
-    const bool live = origin < n_origins;
-    const long long J = coh_slots(nslot_p, b, T);
-    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + chunk * CO;                                   // columns chunk 256 + i, i < 256 + J - 1, exist where i < n_origins - chunk 256 + J - 1
-    const long long hop_n = n_origins - chunk * CO + J - 1;                                // ... of them (<= Ccols - chunk 256: the entry point's check)
-    const long long row0 = 4 * b * T;
-    const uint32_t ctr0 = lo + (uint32_t)(chunk * CO);                                     // lane 0's counter at slot 0
-    // this lane's header sums of a tile: (slot, band) pair tid >> 4 and pair 16 .. 48 further on, header bit i = tid & 15
+    __builtin_assume(J >= 0 && J <= 0x7FFFFFFFll / ES_FRAME_LEN);                          // both kernels clamp J so: the body is compiled before it is inlined
+    // this lane's header sums of a tile: (slot, band) pair tid >> 4 and pair 16 .. 48 further on (the same band), header bit i = tid & 15
     const int zi = tid & 15;
-    const unsigned pn = ((g_cu8*)ring_p)[k * ES_KEYRING_BYTES + ES_COH_HDR_PN + zi];     // the eight PN bits of header bit zi, MSB first
     hs_best best = {-__builtin_inf(), -1, -1};
     #pragma unroll 1
     for (int p = 0; p < P; ++p) {
-        const int phi = ((g_ci32*)phase_p)[b * P + p];
+        const int phi = ((g_ci32*)phase_p)[p];
         if (phi < 0 || phi >= ES_FRAME_LEN || J == 0) continue;                           // (block-uniform) an entry that is no phase is not scored
         double acc = 0.0;
         bool ok = live;
@@ -132,9 +132,9 @@ __global__ __launch_bounds__(256) void es_coherent_score_kernel(const double* __
             __syncthreads();                                                              // the tile before has been read
             #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int pair = (tid >> 4) + 16 * e, j = pair >> 2, band = pair & 3;     // 64 pairs: slot j of the tile, band
+                const int pair = (tid >> 4) + 16 * e, j = pair >> 2;                      // 64 pairs: slot j of the tile, band pair & 3 = (tid >> 4) & 3
                 if (j < nt) {
-                    const long long s = row0 + band * T + phi + (j0 + j) * ES_FRAME_LEN;
+                    const long long s = mine + phi + (j0 + j) * ES_FRAME_LEN;
                     const double* mm = m_p + s + COH_PRE + 8 * zi;
                     double z = 0.0;
                     #pragma unroll
@@ -177,6 +177,58 @@ __global__ __launch_bounds__(256) void es_coherent_score_kernel(const double* __
     hs_block_best(red, best, tid, sc_score, sc_origin, sc_rank);
 }
 
+// Clip b owns rows 4 b .. 4 b + 3 from column 0; one lo and one hop row per key serve the whole call.
+template <bool STRAIGHT>
+__global__ __launch_bounds__(256) void es_coherent_score_kernel(const double* __restrict__ m_p, const double* __restrict__ a_p,
+        const double* __restrict__ d_p, long long T, const int32_t* __restrict__ nslot_p, const int32_t* __restrict__ phase_p, int P,
+        const uint8_t* __restrict__ ring_p, const uint8_t* __restrict__ hop_p, long long K, long long Ccols, uint32_t lo, long long n_origins,
+        long long NB, double* __restrict__ sc_score, long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * CO + tid;
+    const long long J = coh_slots(nslot_p, b, T);
+    g_cu8* hop = (g_cu8*)hop_p + k * Ccols + chunk * CO;                                   // columns chunk 256 + i, i < 256 + J - 1, exist where i < n_origins - chunk 256 + J - 1
+    const long long hop_n = n_origins - chunk * CO + J - 1;                                // ... of them (<= Ccols - chunk 256: the entry point's check)
+    const unsigned pn = ((g_cu8*)ring_p)[k * ES_KEYRING_BYTES + ES_COH_HDR_PN + (tid & 15)];
+    coherent_score_body<STRAIGHT>(m_p, a_p, d_p, (4 * b + ((tid >> 4) & 3)) * T, J, hop, hop_n, lo + (uint32_t)(chunk * CO), pn, phase_p + b * P, P,
+                                  origin < n_origins, origin, sc_score, sc_origin, sc_rank);
+}
+
+// The same over records that lie anywhere in the three tables (include/echoseal_coherent_at.h): record b names its four rows, its column,
+// its hop row and the counter of that hop row's column 0.  Whether it is addressable, its J and its hop row are decided here, from the
+// arrays alone and alike for the whole block, before anything of the tables or the hop bytes is read; J == 0 reads none of them.
+struct es_coh_at { const long long* row; const long long* col; const int32_t* nslot; const int32_t* hop_row; const uint32_t* lo; long long rows, stride, Jw, HR; };
+
+template <bool STRAIGHT>
+__global__ __launch_bounds__(256) void es_coherent_score_at_kernel(const double* __restrict__ m_p, const double* __restrict__ a_p,
+        const double* __restrict__ d_p, es_coh_at at, const int32_t* __restrict__ phase_p, int P, const uint8_t* __restrict__ ring_p,
+        const uint8_t* __restrict__ hop_p, long long K, long long Ccols, long long n_origins, long long NB, double* __restrict__ sc_score,
+        long long* __restrict__ sc_origin, long long* __restrict__ sc_rank)
+{
+    const int tid = threadIdx.x;
+    const long long chunk = blockIdx.x % NB, bk = blockIdx.x / NB, k = bk % K, b = bk / K;
+    const long long origin = chunk * CO + tid;
+    const long long col = ((g_ci64*)at.col)[b], hr = ((g_ci32*)at.hop_row)[b];
+    bool ok = col >= 0 && col <= at.stride && hr >= 0 && hr < at.HR;
+    long long mine = 0;                                                                    // the row of the one band this lane stages
+    #pragma unroll
+    for (int band = 0; band < 4; ++band) {
+        const long long q = ((g_ci64*)at.row)[4 * b + band];
+        ok = ok && q >= 0 && q < at.rows;
+        mine = ((tid >> 4) & 3) == band ? q : mine;
+    }
+    long long most = ok && at.stride - col > COH_SPAN ? (at.stride - col - COH_SPAN) / ES_FRAME_LEN : 0, J = ((g_ci32*)at.nslot)[b];
+    most = most > at.Jw ? at.Jw : most;
+    J = J < 0 ? 0 : (J > most ? most : J);
+    mine = ok ? mine * at.stride + col : 0;                                               // (rows, stride < 2^31: the entry point's check)
+    g_cu8* hop = (g_cu8*)hop_p + (k * at.HR + (ok ? hr : 0)) * Ccols + chunk * CO;         // hop_n <= Ccols - chunk 256: J <= Jw
+    const long long hop_n = n_origins - chunk * CO + J - 1;
+    const unsigned pn = ((g_cu8*)ring_p)[k * ES_KEYRING_BYTES + ES_COH_HDR_PN + (tid & 15)];
+    coherent_score_body<STRAIGHT>(m_p, a_p, d_p, mine, J, hop, hop_n, ((g_cu32*)at.lo)[b] + (uint32_t)(chunk * CO), pn, phase_p + b * P, P,
+                                  origin < n_origins, origin, sc_score, sc_origin, sc_rank);
+}
+
 }  // namespace
 
 // the exact grids: the entry points refuse a call whose grid would pass 2^31 - 1 blocks, and hold tables_ready
@@ -207,6 +259,21 @@ int es_launch_coherent_score(es_ctx* ctx, const double* m, const double* a, cons
     if (sc.slots > 0)
         if (const int rc = es_launch(ctx, es_coherent_score_kernel<COH_STRAIGHT>, (unsigned)sc.slots, 256, 0, st, m, a, d, (long long)T, nslot, phase,
                                      P, ring, hop, (long long)K, (long long)Ccols, lo, (long long)n_origins, sc.NB, sc.score, sc.origin, sc.rank))
+            return rc;
+    return es_launch_hop_best(ctx, sc, score, origin, rank, st);
+}
+
+int es_launch_coherent_score_at(es_ctx* ctx, const double* m, const double* a, const double* d, int64_t rows, int64_t stride, const int64_t* row,
+                                const int64_t* col, const int32_t* nslot, int64_t B, int64_t Jw, const int32_t* phase, int P, const uint8_t* ring,
+                                const uint8_t* hop, int64_t K, int64_t HR, int64_t Ccols, const int32_t* hop_row, const uint32_t* lo,
+                                int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st)
+{
+    const hs_scratch sc(scratch, B, K, n_origins);
+    if (sc.slots > 0)
+        if (const int rc = es_launch(ctx, es_coherent_score_at_kernel<COH_STRAIGHT>, (unsigned)sc.slots, 256, 0, st, m, a, d,
+                                     es_coh_at{(const long long*)row, (const long long*)col, nslot, hop_row, lo, (long long)rows, (long long)stride,
+                                               (long long)Jw, (long long)HR},
+                                     phase, P, ring, hop, (long long)K, (long long)Ccols, (long long)n_origins, sc.NB, sc.score, sc.origin, sc.rank))
             return rc;
     return es_launch_hop_best(ctx, sc, score, origin, rank, st);
 }

@@ -14,6 +14,7 @@
 #include "../../include/echoseal_live_presence.h"
 #include "../../include/echoseal_pick.h"
 #include "../../include/echoseal_coherent.h"
+#include "../../include/echoseal_coherent_at.h"
 
 /* global memory by its address space: what the integer kernels (es_aead.hip, es_keyring.hip) read and write through */
 typedef __attribute__((address_space(1))) const uint8_t g_cu8;
@@ -313,6 +314,11 @@ int es_launch_mf_rows(es_ctx* ctx, const double* y, int64_t rows, int64_t T, con
 int es_launch_coherent_score(es_ctx* ctx, const double* m, const double* a, const double* d, int64_t T, const int32_t* nslot, int64_t B,
                              const int32_t* phase, int P, const uint8_t* ring, const uint8_t* hop, int64_t K, int64_t Ccols, uint32_t lo,
                              int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st);
+/* the same over records that lie anywhere in the three tables (include/echoseal_coherent_at.h): the same device body */
+int es_launch_coherent_score_at(es_ctx* ctx, const double* m, const double* a, const double* d, int64_t rows, int64_t stride, const int64_t* row,
+                                const int64_t* col, const int32_t* nslot, int64_t B, int64_t Jw, const int32_t* phase, int P, const uint8_t* ring,
+                                const uint8_t* hop, int64_t K, int64_t HR, int64_t Ccols, const int32_t* hop_row, const uint32_t* lo,
+                                int64_t n_origins, double* score, int64_t* origin, int32_t* rank, void* scratch, hipStream_t st);
 int es_launch_header(es_ctx* ctx, const double* y, int64_t B, int T, const int32_t* start, const es_rec_at& at, const uint8_t* band,
                      const uint8_t* hdr_pn, uint8_t* ok, int32_t* val, float* score, int32_t* best_s, hipStream_t st);
 /* the verdict memo (es_memo.hip).  The slot of record (k0, k1) in a table of `slots` entries is es_memo_mix(k0, k1) & (slots - 1): the

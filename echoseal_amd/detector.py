@@ -425,17 +425,54 @@ class WatermarkDetector:
         ones sync_ragged, whose y is kept); per launch, for each span, ONE mf_rows, ONE hop window over the ring [key] + decoys and ONE
         score call (es_mf_rows_batch, es_coherent_score_batch).  session_nonce and the traces are not touched.  ValueError before any
         engine exists: what presence_batch refuses of span, ctr0, phases and decoys, the reach of the span judged with this J."""
+        return [None if r is None else r[0] for r in self._presence_coherent_clips(clips, fs_in, ctr0, span, phases, decoys, None)]
+
+    # ------------------------------------------------------------------ the coherent presence timeline (DESIGN 4.28)
+    def presence_coherent_map(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), window: int = 40, step: int = 20,
+                              confirm: int = 2, decoys: int = 32):
+        return self.presence_coherent_map_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, window=window, step=step,
+                                                confirm=confirm, decoys=decoys)[0]
+
+    def presence_coherent_map_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2,
+                                    decoys: int = 32) -> list:
+        """presence_map_batch with the statistic that works on loud hosts: -> per clip a presence.PresenceMap, or None for a clip without
+        one whole slot.  The coherent test (presence_coherent_batch) runs on windows of `window` slots every `step` slots
+        (presence.coherent_windows, cut by the coherent J = max(0, n - 189 - L_max) // 1215), each on its own frame grid and under its
+        own span (presence.window_span); detected windows whose grid anchors agree form stretches, one of at least `confirm` windows is
+        confirmed, and successive confirmed stretches are joined by a Splice (presence.stretches, on the rigid grid).  A clip of at
+        most `window` slots is one window: the map's single entry is presence_coherent() on the clip, field for field -- except for a
+        span that reaches past 2^32 from its last origin, which presence_coherent() refuses and the window lowers.  Every phase
+        is always searched -- the keyless cheap mode is what fails on loud hosts -- and there is no drift search.  A lone detected
+        window is the 1 / (decoys + 1) event the rule allows per window and confirms nothing; every verdict stays statistical.
+        The front is presence_coherent_batch's (cut_launches; mixed rates, int16 and unequal lengths; bpf or sync_ragged) with ONE
+        mf_rows per launch; the windows of all its clips then read the clip's own rows in place (presence.search_coherent_map): per
+        group of windows ONE hop window and ONE score call per span width (es_coherent_score_at_batch), never a launch per window.
+        ValueError before any engine exists: what presence_coherent_batch refuses of span, ctr0 and decoys (the reach is judged per
+        window, which lowers its span at 2^32), and what presence.check_map refuses of window, step and confirm."""
+        return [None if r is None else r[0] for r in self._presence_coherent_clips(clips, fs_in, ctr0, span, FRAME_LEN, decoys, None,
+                                                                                   grid=(window, step, confirm))]
+
+    def _presence_coherent_clips(self, clips, fs_in, ctr0, span, phases, decoys, keys, grid=None) -> list:
+        """presence_coherent_batch under each of `keys` (None: this detector's key alone) -> per clip None or one Presence per key: the
+        rows are keyless, so one front and one score call over the ring keys + decoys serve them all.  grid = (window, step, confirm):
+        presence_coherent_map_batch instead, one PresenceMap per key, the same front with presence.search_coherent_map behind it."""
         from . import presence as pr
         import torch
         from .tables import pack_tables
         clips = list(clips)
         fs_list = rate_list(fs_in, len(clips))
         P, R = pr.check_phases(phases), pr.check_decoys(decoys)
+        if grid is not None:
+            grid = pr.check_map(*grid, 1)[:3]
         spans = pr.clip_spans(ctr0, span, len(clips))
         g, _ = pr.mf_tables(tables=pack_tables(self.fs_target))
-        for c, f, s in zip(clips, fs_list, spans):                          # refused by name before any engine exists
-            pr.check_coherent_reach(s, resampled_length(int(np.size(c)), int(f), self.fs_target), g)
+        if grid is None:
+            for c, f, s in zip(clips, fs_list, spans):                      # refused by name before any engine exists
+                pr.check_coherent_reach(s, resampled_length(int(np.size(c)), int(f), self.fs_target), g)
+        n_own = 1 if keys is None else len(keys)
         out: list = [None] * len(clips)
+        if not n_own:
+            return out
         band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
         nb = band_ids.size
         for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
@@ -461,7 +498,14 @@ class WatermarkDetector:
                 else:
                     lists = [list(range(FRAME_LEN))] * len(sizes)
                 rows = eng.mf_rows(y, lens, bid)
-                ring = self._presence_ring(R)
+                ring = self._presence_ring(R, keys)
+                if grid is not None:
+                    res = pr.search_coherent_map(eng, ring, n_own, *rows, sizes, [(lo, hi)] * len(sizes), g, *grid)
+                    if self._presence_rows is not None:
+                        self._presence_rows.append(([ids[i] for i in la.idx], y.cpu().numpy(), np.array(sizes, np.int64)))
+                    for k, i in enumerate(la.idx):
+                        out[ids[i]] = res[k]
+                    continue
                 base = min(lo, CTR_END - 1)
                 hop = eng.hop_window(ring, [base], max(hi - lo + max(0, y.shape[1] - 190) // FRAME_LEN - 1, 0))
                 score, origin, rank = (t.cpu().numpy() for t in eng.coherent_score(*rows, J, np.array(lists, np.int32), ring, hop, base, hi - lo))
@@ -469,7 +513,8 @@ class WatermarkDetector:
                     self._presence_rows.append(([ids[i] for i in la.idx], y.cpu().numpy(), np.array(sizes, np.int64)))
                 for k, i in enumerate(la.idx):
                     if J[k]:
-                        out[ids[i]] = pr.verdict(score[k], origin[k], rank[k], lo, lists[k], int(J[k]))
+                        make = lambda s, o, r: pr.verdict(s, o, r, lo, lists[k], int(J[k]))
+                        out[ids[i]] = pr._verdicts(n_own, score[k], origin[k], rank[k], make)
         return out
 
     def _presence_ring(self, decoys: int, keys=None):

@@ -724,6 +724,45 @@ class RxEngine(TxChain, MonitorChain):
                    int(lo), n_origins, score, origin, rank, scratch if scratch.numel() else None)
         return score, origin, rank
 
+    def coherent_score_at(self, M: torch.Tensor, A: torch.Tensor, D: torch.Tensor, rows4, col, nslot, phases, ring: KeyRing, hop: torch.Tensor,
+                          hop_row, lo, n_origins: int):
+        """coherent_score over records that lie anywhere in the three tables (es_coherent_score_at_batch, include/echoseal_coherent_at.h;
+        presence.coherent_score_at_model is the host twin).  M, A, D: mf_rows' three [rows, stride] tensors; rows4 int
+        [B, 4]: rows4[b, band] the row that holds BAND_PLAN band `band` of record b; col [B] the column of its sample 0; nslot [B] its
+        slots (clamped to (stride - col - 190) // 1215; a record with a row or a column outside the tables has none; Jw is the largest
+        of them).  Nothing outside columns [col, col + 1215 J + 190) of a record's own rows is read; records may share rows and overlap.
+        phases int [B, P]; ring: the K keys; hop uint8 [K, HR, Ccols] as hop_window gives it ([K, Ccols]: one hop row),
+        Ccols >= n_origins + Jw - 1; hop_row int [B]: record b reads hop row hop_row[b] of every key, one outside [0, HR) scores
+        nothing; lo [B]: the counter of column 0 of that hop row, in [0, 2^32) -> (score float64 [B, K], origin int64 [B, K], rank
+        int32 [B, K]) as coherent_score gives them."""
+        for t in (M, A, D):
+            if t.dim() != 2 or t.shape != M.shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("M, A, D must be contiguous float64 [rows, stride] tensors of one shape on the engine's device")
+        rows4 = self._dev(rows4, torch.int64)
+        nslot = torch.as_tensor(nslot).reshape(-1)
+        Jw = max(int(nslot.max()), 0) if nslot.numel() else 0               # read where the values are: host values cost no sync
+        col, nslot = self._dev(col, torch.int64).reshape(-1), self._dev(nslot, torch.int32)
+        B = nslot.numel()
+        if rows4.dim() != 2 or tuple(rows4.shape) != (B, 4) or col.numel() != B:
+            raise ValueError("rows4: int [B, 4], the row of each band of each record; col, nslot: one value per record")
+        phases = self._dev(phases, torch.int32)
+        if phases.dim() != 2 or phases.shape[0] != B:
+            raise ValueError("phases: int [B, P], one list per record")
+        if hop.dim() == 2:
+            hop = hop[:, None, :]
+        if hop.dim() != 3 or hop.dtype != torch.uint8:
+            raise ValueError("hop must be uint8 [K, HR, Ccols]")
+        HR, Ccols = hop.shape[1], hop.shape[2]
+        hop_row, lo = self._dev(hop_row, torch.int32).reshape(-1), self._ctr_dev(lo).reshape(-1)
+        if hop_row.numel() != B or lo.numel() != B:
+            raise ValueError("hop_row, lo: one hop row index and one counter per record")
+        hop, K, n_origins, score, origin, rank, scratch = self._score_io(hop.reshape(hop.shape[0], HR * Ccols), B, n_origins)
+        if K != ring.n:
+            raise ValueError("hop: one row per key of the ring")
+        self._call("es_coherent_score_at_batch", M, A, D, M.shape[0], M.shape[1], rows4, col, nslot, B, Jw, phases, phases.shape[1], ring.ring, hop,
+                   K, HR, Ccols, hop_row, lo, n_origins, score, origin, rank, scratch if scratch.numel() else None)
+        return score, origin, rank
+
     # ------------------------------------------------------------------ presence under clock drift (DESIGN 4.24; include/echoseal_warp.h)
     def _warp_table(self, warp, nwarp, nslot, B: int):
         """The table of per-slot offsets of a warp call, checked: -> (warp int32 [B, D, Jw], nwarp int32 [B], nslot int32 [B], D, Jw)."""

@@ -174,6 +174,33 @@ class WatermarkIdentifier:
         falsely is at most N / (decoys + 1).  Arguments and ValueErrors are WatermarkDetector.presence_map_batch's."""
         return self._det._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, self.keys, grid=(window, step, confirm))
 
+    def presence_coherent(self, audio, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = FRAME_LEN, decoys: int = 32):
+        return self.presence_coherent_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, phases=phases, decoys=decoys)[0]
+
+    def presence_coherent_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), phases: int = FRAME_LEN, decoys: int = 32) -> list:
+        """WatermarkDetector.presence_coherent_batch under every key at once -> per clip None (no whole slot) or a list with one
+        presence.Presence per key: entry k is field for field what WatermarkDetector(keys[k]).presence_coherent_batch gives for the clip.
+        The matched-filter rows are keyless, so the front and the launches are the single detector's, with the ring keys + decoys in
+        place of [key] + decoys: entry k has score = key row k and null = the decoy rows.  Each entry keeps its own bound
+        of 1 / (decoys + 1) on a false alarm; the chance that SOME key of the N is flagged on unmarked audio is bounded by
+        N / (decoys + 1), not 1 / (decoys + 1): ask for decoys accordingly.  Arguments and ValueErrors are
+        WatermarkDetector.presence_coherent_batch's."""
+        return self._det._presence_coherent_clips(clips, fs_in, ctr0, span, phases, decoys, self.keys)
+
+    def presence_coherent_map(self, audio, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), window: int = 40, step: int = 20,
+                              confirm: int = 2, decoys: int = 32):
+        return self.presence_coherent_map_batch([audio], fs_in, None if ctr0 is None else [ctr0], span=span, window=window, step=step,
+                                                confirm=confirm, decoys=decoys)[0]
+
+    def presence_coherent_map_batch(self, clips, fs_in, ctr0=None, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2,
+                                    decoys: int = 32) -> list:
+        """WatermarkDetector.presence_coherent_map_batch under every key at once -> per clip None (no whole slot) or a list with one
+        presence.PresenceMap per key: entry k is field for field what WatermarkDetector(keys[k]).presence_coherent_map_batch gives for
+        the clip.  One front, one mf_rows and one score call per group of windows and span width cover the ring keys + decoys; each key
+        is ranked against the decoys alone, so for N keys the chance that some key's window is detected falsely is at most
+        N / (decoys + 1).  Arguments and ValueErrors are WatermarkDetector.presence_coherent_map_batch's."""
+        return self._det._presence_coherent_clips(clips, fs_in, ctr0, span, FRAME_LEN, decoys, self.keys, grid=(window, step, confirm))
+
     def open_streams(self, n: int, *, fs=None, window_s: float = 5.0, chunk_max: int | None = None, trace: bool = False,
                      memo_slots: int | None = None, ctr0=None) -> "LiveIdentifier":
         """A monitor of n live streams that says, per push and stream, which of this identifier's keys marks the stream's last window_s

@@ -25,6 +25,10 @@ whole call on the host, search_map its launches.
 The coherent test: the preamble and the keyed header of every frame start on matched-filter rows, over every phase.
 mf_rows_model / coherent_score_model are the twins of es_mf_rows_batch / es_coherent_score_batch (include/echoseal_coherent.h),
 coherent_model the whole of WatermarkDetector.presence_coherent for one clip on the host.
+
+The coherent timeline: the coherent test on the windows of the timeline, for loud hosts.  coherent_score_at_model is the twin
+of es_coherent_score_at_batch (include/echoseal_coherent_at.h), coherent_windows cuts a clip by its coherent slots, coherent_map_model is
+the whole of WatermarkDetector.presence_coherent_map on the host, search_coherent_map its launches (it too is handed an engine).
 """
 from __future__ import annotations
 
@@ -888,14 +892,142 @@ def coherent_model(y4, n: int, key: bytes, *, span=(0, 4096), phases=FRAME_LEN, 
     return verdict(score[0], origin[0], rank[0], lo, plist, J)
 
 
+# ---- the coherent presence timeline: the coherent test on the windows of a clip (include/echoseal_coherent_at.h) ----
+def coherent_score_at_model(M, A, D, rows4, col, nslot, Jw: int, phases, u, hop, hop_row, lo, n_origins: int):
+    """es_coherent_score_at_batch in NumPy.  M, A, D float64 [rows, stride]; record b: rows4[b][band] the row of its band `band`, col[b]
+    the column of its sample 0, nslot[b] its slots.  It is addressable iff its four rows lie in [0, rows) and 0 <= col <= stride; its J is
+    nslot clamped to [0, min(Jw, max(0, stride - col - 190) // 1215)], 0 where it is not addressable or hop_row[b] lies outside [0, HR).
+    hop uint8 [K, HR, Ccols] ([K, Ccols]: HR = 1); lo[b] the counter of column 0 of hop row hop_row[b], counters taken mod 2^32.  The
+    record's block -- columns [col, col + 1215 J + 190) of its four rows, all the kernel may read -- goes through coherent_score_model
+    under its own hop row and lo, as window_rows serves the folds -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K])."""
+    M, A, D = (np.asarray(a, np.float64) for a in (M, A, D))
+    if M.ndim != 2 or A.shape != M.shape or D.shape != M.shape:
+        raise ValueError("M, A, D: float64 [rows, stride], the three of one shape")
+    rows, stride = M.shape
+    nslot = np.asarray(nslot, np.int64).reshape(-1)
+    B, Jw = nslot.size, int(Jw)
+    rows4, col = np.asarray(rows4, np.int64).reshape(B, NBANDS), np.asarray(col, np.int64).reshape(-1)
+    hop_row, lo = np.asarray(hop_row, np.int64).reshape(-1), np.asarray(lo, np.int64).reshape(-1)
+    if col.size != B or hop_row.size != B or lo.size != B:
+        raise ValueError("col, nslot, hop_row, lo: one value per record")
+    hop = np.asarray(hop, np.uint8)
+    if hop.ndim == 2:
+        hop = hop[:, None, :]
+    K, HR = hop.shape[0], hop.shape[1]
+    phases = np.asarray(phases, np.int64).reshape(B, -1)
+    if Jw < 0 or hop.shape[2] < int(n_origins) + Jw - 1:
+        raise ValueError("Jw >= 0 and hop with at least n_origins + Jw - 1 columns")
+    score = np.full((B, K), -np.inf, np.float64)
+    origin = np.full((B, K), -1, np.int64)
+    rank = np.full((B, K), -1, np.int32)
+    for b in range(B):
+        c = int(col[b])
+        if not (0 <= c <= stride and all(0 <= int(r) < rows for r in rows4[b]) and 0 <= int(hop_row[b]) < HR):
+            continue
+        J = min(max(int(nslot[b]), 0), Jw, max(0, stride - c - COH_SPAN) // FRAME_LEN)
+        if J == 0:
+            continue
+        n = FRAME_LEN * J + COH_SPAN
+        block = [np.stack([a[int(r), c:c + n] for r in rows4[b]]) for a in (M, A, D)]
+        score[b], origin[b], rank[b] = (v[0] for v in coherent_score_model(*block, [J], [phases[b]], u, hop[:, int(hop_row[b])],
+                                                                            int(lo[b]) & 0xFFFFFFFF, n_origins))
+    return score, origin, rank
+
+
+def coherent_windows(samples: int, g, window: int = 40, step: int = 20) -> list[tuple[int, int, int]]:
+    """The windows of a clip of `samples` samples -> [(first slot s, column 1215 s, slots)], J = coherent_slots(samples, g): none for
+    J == 0; the whole clip, (0, 0, J), for J <= window; else windows of `window` slots at s = 0, step, 2 step .. <= J - window, and one
+    at J - window where the steps do not end there (map_windows, counted in slots: a window reads 1215 slots + 189 + L_max samples)."""
+    W, S, _, _ = check_map(window, step, 1, 1)
+    J = coherent_slots(samples, g)
+    if J == 0:
+        return []
+    if J <= W:
+        return [(0, 0, J)]
+    starts = list(range(0, J - W + 1, S))
+    if (J - W) % S:
+        starts.append(J - W)
+    return [(s, FRAME_LEN * s, W) for s in starts]
+
+
+def coherent_map_model(y4, n: int, key: bytes, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2, decoys: int = 32,
+                       fs: int = 48_000, tables=None) -> PresenceMap | None:
+    """WatermarkDetector.presence_coherent_map from one clip's four band-passed rows y4 [4, >= n], on the host: coherent_model on the
+    samples [col, col + 1215 slots + 189 + L_max) of each window of coherent_windows, under the window's own span (window_span), every
+    phase searched; then stretches on the rigid grid.  M, A and D are FIR outputs of y, so the rows of a slice are the clip's rows bit
+    for bit wherever the slice defines them.  None where the clip has no whole slot."""
+    y4 = np.asarray(y4, np.float64)
+    W, S, C, _ = check_map(window, step, confirm, 1)
+    n = min(max(int(n), 0), y4.shape[1])
+    g, _ = mf_tables(fs, tables)
+    wins = coherent_windows(n, g, W, S)
+    if not wins:
+        return None
+    tail = COH_SPAN - 1 + max(len(t) for t in g)
+    verdicts = []
+    for s, col, J in wins:
+        m = FRAME_LEN * J + tail
+        p = coherent_model(y4[:NBANDS, col:col + m], m, key, span=window_span(span, s, J), decoys=decoys, fs=fs, tables=tables)
+        if p is not None and p.ctr >= 0:
+            p.ctr0 = origin_of(p.ctr, p.phase, col)
+        verdicts.append(p)
+    return make_map(verdicts, [(s, col, FRAME_LEN * J) for s, col, J in wins], 0.0, C)
+
+
+def search_coherent_map(eng, ring, n_own: int, M, A, D, clip_samples, spans, g, window: int, step: int, confirm: int) -> list:
+    """The coherent windows of every clip of one launch through the device -> per clip None (no whole slot) or n_own PresenceMap, one per
+    own key.  Clip c owns rows 4 c .. 4 c + 3 of M, A, D (mf_rows' tensors) and has clip_samples[c] samples; spans[c] is its span; g the
+    matched filters (mf_tables).  Windows go in groups of consecutive windows whose hop table -- a hop row per distinct span base,
+    K HR Ccols bytes -- stays within MAP_HOP_BYTES, as search_map groups them: per group ONE hop window and ONE coherent_score_at per
+    distinct span width, never a launch per window.  Every record searches every phase: the identity list."""
+    torch = _torch()
+    recs = []                                                               # (clip, window of it, rows4, col, slots, span)
+    wins = [coherent_windows(n, g, window, step) for n in np.asarray(clip_samples, np.int64).reshape(-1).tolist()]
+    for c, ws in enumerate(wins):
+        recs += [(c, w, [NBANDS * c + band for band in range(NBANDS)], col, J, window_span(spans[c], s, J)) for w, (s, col, J) in enumerate(ws)]
+    verdicts = [[None] * len(ws) for ws in wins]
+    i = 0
+    while i < len(recs):
+        bases, ccols, j = set(), 0, i
+        while j < len(recs):                                                # grow the group while its hop table fits
+            lo, hi = recs[j][5]
+            grown = bases | {min(lo, CTR_END - 1)}
+            cols = max(ccols, hi - lo + recs[j][4] - 1)
+            if j > i and ring.n * len(grown) * cols > MAP_HOP_BYTES:
+                break
+            bases, ccols, j = grown, cols, j + 1
+        group, bases = recs[i:j], sorted(bases)
+        hop = eng.hop_window(ring, bases, max(ccols, 0))
+        for width in sorted({hi - lo for _, _, _, _, _, (lo, hi) in group}):
+            ids = [r for r in group if r[5][1] - r[5][0] == width]
+            base = [min(r[5][0], CTR_END - 1) for r in ids]
+            lists = torch.arange(FRAME_LEN, dtype=torch.int32, device=eng.device).repeat(len(ids), 1)
+            res = eng.coherent_score_at(M, A, D, np.array([r[2] for r in ids], np.int64), np.array([r[3] for r in ids], np.int64),
+                                        np.array([r[4] for r in ids], np.int32), lists, ring, hop,
+                                        np.array([bases.index(v) for v in base], np.int32), np.array(base, np.int64), width)
+            score, origin, rank = (t.cpu().numpy() for t in res)
+            plist = list(range(FRAME_LEN))
+            for k, r in enumerate(ids):
+                make = lambda s, o, q: verdict(s, o, q, r[5][0], plist, r[4])
+                v = _verdicts(n_own, score[k], origin[k], rank[k], make)
+                for p in v:
+                    if p.ctr >= 0:
+                        p.ctr0 = origin_of(p.ctr, p.phase, r[3])
+                verdicts[r[0]][r[1]] = v
+        i = j
+    return [None if not ws else [make_map([v[k] for v in vs], [(s, col, FRAME_LEN * J) for s, col, J in ws], 0.0, confirm) for k in range(n_own)]
+            for ws, vs in zip(wins, verdicts)]
+
+
 def _torch():
     import torch
     return torch
 
 
 __all__ = ["COH_SPAN", "DECOY_LABEL", "MAP_HOP_BYTES", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor",
-           "check_coherent_reach", "check_decoys", "check_drift", "check_map", "check_phases", "check_reach", "clip_spans", "coherent_model",
-           "coherent_score_model", "coherent_slots", "consistent", "decoy_keys", "drift_verdict", "fold_model", "header_signs", "hop_model",
-           "live_model", "live_span", "make_map", "map_model", "map_windows", "mf_rows_model", "mf_tables", "pick_hypotheses", "pick_model",
-           "pick_phases", "presence_model", "ring_signs", "score_model", "search", "search_map", "skew_table", "slots", "stretches",
-           "table_rows", "verdict", "warp_fold_model", "warp_score_model", "window_rows", "window_span"]
+           "check_coherent_reach", "check_decoys", "check_drift", "check_map", "check_phases", "check_reach", "clip_spans", "coherent_map_model",
+           "coherent_model", "coherent_score_at_model", "coherent_score_model", "coherent_slots", "coherent_windows", "consistent", "decoy_keys",
+           "drift_verdict", "fold_model", "header_signs", "hop_model", "live_model", "live_span", "make_map", "map_model", "map_windows",
+           "mf_rows_model", "mf_tables", "pick_hypotheses", "pick_model", "pick_phases", "presence_model", "ring_signs", "score_model", "search",
+           "search_coherent_map", "search_map", "skew_table", "slots", "stretches", "table_rows", "verdict", "warp_fold_model", "warp_score_model",
+           "window_rows", "window_span"]
