@@ -83,6 +83,17 @@ class _Scan:
     pos0: int = 0               # absolute sample of the scan's first sample in its stream (a monitor window's w0; 0 for a clip)
 
 
+@dataclass(eq=False)
+class _Front:
+    """One launch of the presence calls' front (WatermarkDetector._presence_front): row 4 * clip + band is BAND_PLAN band `band` of a clip."""
+    sizes: list                 # samples of each clip at fs_target
+    lens: np.ndarray            # int32, the same per row
+    bid: object                 # uint8 per row on the device: its band index
+    y: object                   # float64 [rows, >= longest clip] on the device: the band-passed rows
+    corr: object                # their correlation rows, or None where they were not asked for
+    J: np.ndarray | None        # the slots of each clip, where the caller counts them
+
+
 def clip_origins(ctr0, clips, fs_list, fs_target: int) -> list:
     """The counter origins of a batch call's clips (scan.counter_origins), each checked against its clip's length at fs_target
     (scan.check_counter_reach).  Host arithmetic only."""
@@ -350,8 +361,8 @@ class WatermarkDetector:
         stretches are joined by a Splice that says how many samples are missing between their grids.  A lone detected window is the
         1 / (decoys + 1) event the rule allows per window and confirms nothing; every verdict stays statistical.
         drift_ppm > 0 gives each window the drift search of DESIGN 4.24 over its own length.
-        The front is presence_batch's; then per launch the windows of all its clips go through presence.search_map: per group of windows
-        ONE fold, ONE device pick (es_fold_pick_batch), ONE hop window and ONE score per span width, never a launch per window.
+        The front is presence_batch's; then per launch the windows of all its clips go through presence_search.search_map: per group of
+        windows ONE fold, ONE device pick (es_fold_pick_batch), ONE hop window and ONE score per span width, never a launch per window.
         ValueError before any engine exists: what presence_batch refuses of span, ctr0, decoys and drift_ppm (the drift judged on a
         window), window, step or confirm that are no integers, step < 1, step > window, confirm < 1, phases outside 1 .. 64."""
         return [None if r is None else r[0] for r in self._presence_clips(clips, fs_in, ctr0, span, phases, decoys, drift_ppm, None,
@@ -360,10 +371,9 @@ class WatermarkDetector:
     def _presence_clips(self, clips, fs_in, ctr0, span, phases, decoys, drift_ppm, keys, grid=None) -> list:
         """presence_batch under each of `keys` (None: this detector's key alone) -> per clip None or one Presence per key.  The checks,
         the front and the launches are the same whatever the keys: the fold and the hypothesis list are keyless, so one front and one
-        score call over the ring keys + decoys serve them all (presence.search).  grid = (window, step, confirm): presence_map_batch
-        instead, one PresenceMap per key, the same front with presence.search_map behind it."""
-        from . import presence as pr
-        import torch
+        score call over the ring keys + decoys serve them all (presence_search.search).  grid = (window, step, confirm):
+        presence_map_batch instead, one PresenceMap per key, the same front with presence_search.search_map behind it."""
+        from . import presence as pr, presence_search as ps
         clips = list(clips)
         fs_list = rate_list(fs_in, len(clips))
         P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
@@ -379,31 +389,47 @@ class WatermarkDetector:
                     pr.skew_table(n, drift)
         out: list = [None] * len(clips)
         n_own = 1 if keys is None else len(keys)
+        for span, ids, f in self._presence_front(clips, fs_list, spans, want_corr=True):
+            nlag = np.array(f.sizes, np.int64) - (PRE_L - 1)
+            if not n_own:
+                res = [None] * len(ids)
+            elif grid is None:
+                res = ps.search(self.engine, self._presence_ring(R, keys), n_own, f.corr, nlag, [span] * len(ids), drift, P)
+            else:
+                res = ps.search_map(self.engine, self._presence_ring(R, keys), n_own, f.corr, nlag, [span] * len(ids), drift, P, *grid)
+            if self._presence_rows is not None and any(r is not None for r in res):
+                self._presence_rows.append((ids, f.corr.cpu().numpy(), nlag))
+            for i, r in zip(ids, res):
+                out[i] = r
+        return out
+
+    def _presence_front(self, clips, fs_list, spans, want_corr: bool, slots=None):
+        """The front the presence calls share -> per span, in sorted order, and per launch of the clips of that span (cut_launches: clips
+        of one span share launches; one span: the whole call): (span, the clips' indices in the call, _Front) with the launch's
+        band-passed rows y and, where want_corr, its correlation rows -- four rows per clip in BAND_PLAN order; equal lengths run bpf
+        and xcorr, unequal ones sync_ragged.  slots(sizes) -> the slots of each clip: a launch without any is skipped before an engine
+        is touched, and the others carry them as _Front.J."""
+        import torch
         band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
         nb = band_ids.size
-        for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
-            ids = [i for i, s in enumerate(spans) if s == (lo, hi)]
+        for span in sorted(set(spans)):
+            ids = [i for i, s in enumerate(spans) if s == span]
             for la in cut_launches([clips[i] for i in ids], [fs_list[i] for i in ids], self.fs_target, nb, self._conditioned):
+                J = None if slots is None else slots(la.sizes)
+                if J is not None and not J.max():
+                    continue
                 eng = self.engine
                 x, sizes = la.rows(eng, nb)
                 bid = dev(eng, np.tile(band_ids, len(sizes)), np.uint8)
                 M = max(sizes)
+                lens = np.repeat(np.array(sizes, np.int32), nb)
                 if min(sizes) < M:
-                    corr = eng.sync_ragged(x, torch.from_numpy(np.repeat(np.array(sizes, np.int32), nb)), bid, keep_corr=True).corr
+                    sy = eng.sync_ragged(x, torch.from_numpy(lens), bid, keep_corr=want_corr)
+                    y, corr = sy.y, sy.corr
                 else:
-                    corr = eng.xcorr(eng.bpf(x[:, :M], bid), bid)
-                nlag = np.array(sizes, np.int64) - (PRE_L - 1)
-                if not n_own:
-                    res = [None] * len(sizes)
-                elif grid is None:
-                    res = pr.search(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P)
-                else:
-                    res = pr.search_map(eng, self._presence_ring(R, keys), n_own, corr, nlag, [(lo, hi)] * len(sizes), drift, P, *grid)
-                if self._presence_rows is not None and any(r is not None for r in res):
-                    self._presence_rows.append(([ids[i] for i in la.idx], corr.cpu().numpy(), nlag))
-                for k, i in enumerate(la.idx):
-                    out[ids[i]] = res[k]
-        return out
+                    y = eng.bpf(x[:, :M], bid)
+                    corr = eng.xcorr(y, bid) if want_corr else None
+                yield span, [ids[i] for i in la.idx], _Front(sizes, lens, bid, y, corr, J)
 
     # ------------------------------------------------------------------ the coherent presence test (DESIGN 4.27)
     def presence_coherent(self, audio: np.ndarray, fs_in: int, ctr0: int | None = None, *, span=(0, 4096), phases: int = FRAME_LEN,
@@ -445,8 +471,8 @@ class WatermarkDetector:
         is always searched -- the keyless cheap mode is what fails on loud hosts -- and there is no drift search.  A lone detected
         window is the 1 / (decoys + 1) event the rule allows per window and confirms nothing; every verdict stays statistical.
         The front is presence_coherent_batch's (cut_launches; mixed rates, int16 and unequal lengths; bpf or sync_ragged) with ONE
-        mf_rows per launch; the windows of all its clips then read the clip's own rows in place (presence.search_coherent_map): per
-        group of windows ONE hop window and ONE score call per span width (es_coherent_score_at_batch), never a launch per window.
+        mf_rows per launch; the windows of all its clips then read the clip's own rows in place (presence_search.search_coherent_map):
+        per group of windows ONE hop window and ONE score call per span width (es_coherent_score_at_batch), never a launch per window.
         ValueError before any engine exists: what presence_coherent_batch refuses of span, ctr0 and decoys (the reach is judged per
         window, which lowers its span at 2^32), and what presence.check_map refuses of window, step and confirm."""
         return [None if r is None else r[0] for r in self._presence_coherent_clips(clips, fs_in, ctr0, span, FRAME_LEN, decoys, None,
@@ -455,9 +481,9 @@ class WatermarkDetector:
     def _presence_coherent_clips(self, clips, fs_in, ctr0, span, phases, decoys, keys, grid=None) -> list:
         """presence_coherent_batch under each of `keys` (None: this detector's key alone) -> per clip None or one Presence per key: the
         rows are keyless, so one front and one score call over the ring keys + decoys serve them all.  grid = (window, step, confirm):
-        presence_coherent_map_batch instead, one PresenceMap per key, the same front with presence.search_coherent_map behind it."""
-        from . import presence as pr
-        import torch
+        presence_coherent_map_batch instead, one PresenceMap per key, the same front with presence_search.search_coherent_map behind it
+        (without one: presence_search.search_coherent)."""
+        from . import presence as pr, presence_search as ps
         from .tables import pack_tables
         clips = list(clips)
         fs_list = rate_list(fs_in, len(clips))
@@ -473,48 +499,24 @@ class WatermarkDetector:
         out: list = [None] * len(clips)
         if not n_own:
             return out
-        band_ids = np.arange(len(BAND_PLAN), dtype=np.uint8)
-        nb = band_ids.size
-        for lo, hi in sorted(set(spans)):                                   # clips of one span share launches (one span: the whole call)
-            ids = [i for i, s in enumerate(spans) if s == (lo, hi)]
-            for la in cut_launches([clips[i] for i in ids], [fs_list[i] for i in ids], self.fs_target, nb, self._conditioned):
-                J = np.array([pr.coherent_slots(n, g) for n in la.sizes], np.int64)
-                if not J.max():
-                    continue
-                eng = self.engine
-                x, sizes = la.rows(eng, nb)
-                bid = dev(eng, np.tile(band_ids, len(sizes)), np.uint8)
-                M = max(sizes)
-                lens = np.repeat(np.array(sizes, np.int32), nb)
-                if min(sizes) < M:
-                    sy = eng.sync_ragged(x, torch.from_numpy(lens), bid, keep_corr=P < FRAME_LEN)
-                    y, corr = sy.y, sy.corr
-                else:
-                    y = eng.bpf(x[:, :M], bid)
-                    corr = eng.xcorr(y, bid) if P < FRAME_LEN else None
-                if P < FRAME_LEN:                                           # the cheap mode: the top of the keyless fold (presence_batch's list)
-                    fold = eng.phase_fold(corr, np.array(sizes, np.int64) - (PRE_L - 1)).cpu().numpy()
-                    lists = [pr.pick_phases(f, P) for f in fold]
-                else:
-                    lists = [list(range(FRAME_LEN))] * len(sizes)
-                rows = eng.mf_rows(y, lens, bid)
-                ring = self._presence_ring(R, keys)
-                if grid is not None:
-                    res = pr.search_coherent_map(eng, ring, n_own, *rows, sizes, [(lo, hi)] * len(sizes), g, *grid)
-                    if self._presence_rows is not None:
-                        self._presence_rows.append(([ids[i] for i in la.idx], y.cpu().numpy(), np.array(sizes, np.int64)))
-                    for k, i in enumerate(la.idx):
-                        out[ids[i]] = res[k]
-                    continue
-                base = min(lo, CTR_END - 1)
-                hop = eng.hop_window(ring, [base], max(hi - lo + max(0, y.shape[1] - 190) // FRAME_LEN - 1, 0))
-                score, origin, rank = (t.cpu().numpy() for t in eng.coherent_score(*rows, J, np.array(lists, np.int32), ring, hop, base, hi - lo))
-                if self._presence_rows is not None:
-                    self._presence_rows.append(([ids[i] for i in la.idx], y.cpu().numpy(), np.array(sizes, np.int64)))
-                for k, i in enumerate(la.idx):
-                    if J[k]:
-                        make = lambda s, o, r: pr.verdict(s, o, r, lo, lists[k], int(J[k]))
-                        out[ids[i]] = pr._verdicts(n_own, score[k], origin[k], rank[k], make)
+        slots = lambda sizes: np.array([pr.coherent_slots(n, g) for n in sizes], np.int64)
+        for (lo, hi), ids, f in self._presence_front(clips, fs_list, spans, want_corr=P < FRAME_LEN, slots=slots):
+            eng = self.engine
+            if P < FRAME_LEN:                                               # the cheap mode: the top of the keyless fold (presence_batch's list)
+                fold = eng.phase_fold(f.corr, np.array(f.sizes, np.int64) - (PRE_L - 1)).cpu().numpy()
+                lists = [pr.pick_phases(row, P) for row in fold]
+            else:
+                lists = [list(range(FRAME_LEN))] * len(ids)
+            rows = eng.mf_rows(f.y, f.lens, f.bid)
+            ring = self._presence_ring(R, keys)
+            if grid is None:
+                res = ps.search_coherent(eng, ring, n_own, *rows, f.J, lists, lo, hi)
+            else:
+                res = ps.search_coherent_map(eng, ring, n_own, *rows, f.sizes, [(lo, hi)] * len(ids), g, *grid)
+            if self._presence_rows is not None:
+                self._presence_rows.append((ids, f.y.cpu().numpy(), np.array(f.sizes, np.int64)))
+            for i, r in zip(ids, res):
+                out[i] = r
         return out
 
     def _presence_ring(self, decoys: int, keys=None):

@@ -372,6 +372,7 @@ class LiveTable:
         host before any GPU work; the table is only read."""
         from . import presence as pr
         from .acquire import check_span
+        from .presence_search import search
         tab = self.table
         P, R, drift = pr.check_phases(phases), pr.check_decoys(decoys), pr.check_drift(drift_ppm)
         span = check_span(span)
@@ -391,8 +392,8 @@ class LiveTable:
         n_own = 1 if keys is None else len(keys)
         if some.size and n_own:
             rows4 = np.array([pr.table_rows(tab.bands, s) for s in ids[some].tolist()], np.int64)
-            res = pr.search(det.engine, det._presence_ring(R, keys), n_own, tab.corr_hist, nlag[some], [spans[i] for i in some.tolist()], drift, P,
-                            at=(rows4, (w0 - base)[some]), pos0=w0[some])
+            res = search(det.engine, det._presence_ring(R, keys), n_own, tab.corr_hist, nlag[some], [spans[i] for i in some.tolist()], drift, P,
+                         at=(rows4, (w0 - base)[some]), pos0=w0[some])
             for i, r in zip(some.tolist(), res):
                 out[i] = r
         return out

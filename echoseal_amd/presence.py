@@ -1,7 +1,8 @@
 """Presence on the host: does a clip carry preamble peaks on one 1215-sample grid that follow a key's band-hop sequence from
 some counter?  A NumPy twin that the kernels behind es_phase_fold_batch / es_hop_score_batch (csrc/es_keyring.hip) are held to bit for
 bit, the public decoy keys the verdict is ranked against, and the argument checks of WatermarkDetector.presence.  No engine is needed for
-anything here.
+anything here: the dataclasses, the checks, the geometry of spans and windows, and every *_model twin.  What is handed an engine -- the
+launches and the verdict fan-out of every public presence call -- is presence_search.py.
 
 The rows: clip b owns rows 4 b .. 4 b + 3 of `corr`, row 4 b + band the float64 correlation row (es_xcorr_batch) of BAND_PLAN band `band`,
 lags [0, nlag[b]); J = nlag // 1215 whole slots.  Every sum is float64, added term by term in ascending slot order from 0.0 -- the loops
@@ -15,12 +16,11 @@ include/echoseal_warp.h), and presence_model(..., drift_ppm=...) the whole searc
 Live windows: a record may lie anywhere in a table of rows, such as a stream's window in a monitor table's correlation
 history.  window_rows cuts the block es_warp_fold_at_batch / es_warp_score_at_batch may read (include/echoseal_live_presence.h), so the
 models above are their twins too; live_span is the counter span of a stream with an origin, live_model the whole call for one stream.
-`search`: the launches and verdicts behind every public presence call; it and search_map are the functions here that are handed an engine.
 
 The timeline: which parts of a clip carry the mark, and where it was cut.  pick_model is the twin of the device's pick
 (es_fold_pick_batch; include/echoseal_pick.h); map_windows cuts a clip into overlapping windows, each a record of the _at calls with its own
 span; stretches joins the detected windows that lie on one frame grid and names the splices between confirmed stretches; map_model is the
-whole call on the host, search_map its launches.
+whole call on the host (presence_search.search_map: its launches).
 
 The coherent test: the preamble and the keyed header of every frame start on matched-filter rows, over every phase.
 mf_rows_model / coherent_score_model are the twins of es_mf_rows_batch / es_coherent_score_batch (include/echoseal_coherent.h),
@@ -28,7 +28,7 @@ coherent_model the whole of WatermarkDetector.presence_coherent for one clip on 
 
 The coherent timeline: the coherent test on the windows of the timeline, for loud hosts.  coherent_score_at_model is the twin
 of es_coherent_score_at_batch (include/echoseal_coherent_at.h), coherent_windows cuts a clip by its coherent slots, coherent_map_model is
-the whole of WatermarkDetector.presence_coherent_map on the host, search_coherent_map its launches (it too is handed an engine).
+the whole of WatermarkDetector.presence_coherent_map on the host (presence_search.search_coherent_map: its launches).
 """
 from __future__ import annotations
 
@@ -105,14 +105,19 @@ def slots(samples: int) -> int:
     return max(0, int(samples) - (PRE_L - 1)) // FRAME_LEN
 
 
-def check_reach(span, samples: int) -> tuple[int, int]:
-    """The span (acquire.check_span) of a clip of `samples` samples: the window of the last origin, hi - 1 + J - 1, must be a counter."""
+def _reach(span, J: int, samples: int) -> tuple[int, int]:
+    """The span (acquire.check_span) of a clip of `samples` samples and J slots: the window of the last origin, hi - 1 + J - 1, must be a
+    counter."""
     lo, hi = check_span(span)
-    J = slots(samples)
     if hi > lo and hi + J - 1 > CTR_END:
         raise ValueError(f"span = ({lo}, {hi}): a clip of {int(samples)} samples has {J} frames, and hi + {J} - 1 > 2^32 "
                          "(spans that wrap past 2^32 are out of scope)")
     return lo, hi
+
+
+def check_reach(span, samples: int) -> tuple[int, int]:
+    """The span of a clip of `samples` samples, checked (_reach) with J = slots(samples)."""
+    return _reach(span, slots(samples), samples)
 
 
 def clip_spans(ctr0, span, n: int) -> list:
@@ -131,20 +136,15 @@ def _rows(corr, nlag):
     return corr, nlag
 
 
-def fold_model(corr, nlag) -> np.ndarray:
-    """es_phase_fold_batch in NumPy -> fold float64 [B, 1215]."""
+def _rigid(corr, nlag):
+    """The rigid grid as a warp table: one row of zeros per clip, every whole slot of it -> (warp, nwarp, nslot) of the warp models."""
     corr, nlag = _rows(corr, nlag)
-    fold = np.zeros((nlag.size, FRAME_LEN), np.float64)
-    for b, n in enumerate(nlag.tolist()):
-        acc = np.zeros(FRAME_LEN, np.float64)
-        for j in range(n // FRAME_LEN):
-            v = corr[NBANDS * b:NBANDS * b + NBANDS, FRAME_LEN * j:FRAME_LEN * (j + 1)]
-            m = v[0].copy()
-            for band in range(1, NBANDS):                                   # a later band only where strictly larger
-                np.copyto(m, v[band], where=v[band] > m)
-            acc = acc + m
-        fold[b] = acc
-    return fold
+    return np.zeros((nlag.size, 1, corr.shape[1] // FRAME_LEN), np.int64), np.ones(nlag.size, np.int64), nlag // FRAME_LEN
+
+
+def fold_model(corr, nlag) -> np.ndarray:
+    """es_phase_fold_batch in NumPy -> fold float64 [B, 1215]: warp_fold_model on the rigid grid, as the kernels share one body."""
+    return warp_fold_model(corr, nlag, *_rigid(corr, nlag))[:, 0]
 
 
 def pick_phases(fold_row, phases: int) -> list[int]:
@@ -166,38 +166,11 @@ def hop_model(keys, lo: int, cols: int) -> np.ndarray:
 
 
 def score_model(corr, nlag, phases, hop, n_origins: int):
-    """es_hop_score_batch in NumPy -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K])."""
-    corr, nlag = _rows(corr, nlag)
-    phases = np.asarray(phases, np.int64).reshape(nlag.size, -1)
-    hop = np.asarray(hop, np.uint8)
-    K, n_origins = hop.shape[0], int(n_origins)
-    score = np.full((nlag.size, K), -np.inf, np.float64)
-    origin = np.full((nlag.size, K), -1, np.int64)
-    rank = np.full((nlag.size, K), -1, np.int32)
-    for b, n in enumerate(nlag.tolist()):
-        J = n // FRAME_LEN
-        if J == 0 or n_origins == 0:
-            continue
-        if hop.shape[1] < n_origins + J - 1:
-            raise ValueError("hop: fewer than n_origins + J - 1 columns")
-        rows = corr[NBANDS * b:NBANDS * b + NBANDS]
-        for k in range(K):
-            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]: slot j of every origin's window
-            scored = np.flatnonzero((win < NBANDS).all(axis=0))
-            if not scored.size:
-                continue
-            win = (win & 3).astype(np.int64)
-            for p, phi in enumerate(phases[b].tolist()):
-                if not 0 <= phi < FRAME_LEN:
-                    continue
-                acc = np.zeros(n_origins, np.float64)
-                for j in range(J):
-                    acc = acc + rows[win[j], phi + FRAME_LEN * j]
-                s = (acc / np.float64(J))[scored]
-                i = int(np.argmax(s))                                                    # the first of equal values: the lowest origin
-                if origin[b, k] < 0 or s[i] > score[b, k] or (s[i] == score[b, k] and scored[i] < origin[b, k]):
-                    score[b, k], origin[b, k], rank[b, k] = s[i], scored[i], p
-    return score, origin, rank
+    """es_hop_score_batch in NumPy -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K]): warp_score_model on the rigid grid,
+    list entry p = (row 0, phases[b][p])."""
+    warp, nwarp, nslot = _rigid(corr, nlag)
+    phases = np.asarray(phases, np.int64).reshape(nslot.size, -1)
+    return warp_score_model(corr, nlag, warp, nwarp, nslot, np.stack([np.zeros_like(phases), phases], axis=2), hop, n_origins)
 
 
 def check_drift(drift_ppm) -> float:
@@ -268,6 +241,35 @@ def warp_fold_model(corr, nlag, warp, nwarp, nslot) -> np.ndarray:
     return fold
 
 
+def _score_frame(hop, nslot, n_origins: int, record):
+    """What the score twins share around their inner sums -> (score float64 [B, K], origin int64 [B, K], rank int32 [B, K]).  Record b
+    has nslot[b] slots J; hop uint8 [K, Ccols] holds, per key, the window of every origin: slot j of origin o is hop[k][o + j].  Scored
+    are the origins whose J bytes are all bands (none above 3).  record(b, J) -> term, and term(k, win, scored) yields (entry, s) in list
+    order: s float64 [scored.size], the score of list entry `entry` at each scored origin under key k, win int64 [J, n_origins] the bands.
+    Kept per (record, key) is the largest s, of equal values the lowest origin, then the earliest entry; (-inf, -1, -1) where nothing is
+    scored (J == 0, no origin, no scored origin, no entry)."""
+    K, B = hop.shape[0], len(nslot)
+    score = np.full((B, K), -np.inf, np.float64)
+    origin = np.full((B, K), -1, np.int64)
+    rank = np.full((B, K), -1, np.int32)
+    for b, J in enumerate(nslot):
+        if J == 0 or n_origins == 0:
+            continue
+        if hop.shape[1] < n_origins + J - 1:
+            raise ValueError("hop: fewer than n_origins + J - 1 columns")
+        term = record(b, J)
+        for k in range(K):
+            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]: slot j of every origin's window
+            scored = np.flatnonzero((win < NBANDS).all(axis=0))
+            if not scored.size:
+                continue
+            for entry, s in term(k, (win & 3).astype(np.int64), scored):
+                i = int(np.argmax(s))                                                    # the first of equal values: the lowest origin
+                if origin[b, k] < 0 or s[i] > score[b, k] or (s[i] == score[b, k] and scored[i] < origin[b, k]):
+                    score[b, k], origin[b, k], rank[b, k] = s[i], scored[i], entry
+    return score, origin, rank
+
+
 def pick_hypotheses(fold_rows, phases: int) -> list[tuple[int, int]]:
     """The min(phases, D 1215) pairs (row d, phase phi) of largest fold over the usable rows of one clip's fold [D, 1215] (an unusable
     row is all -inf), largest first; of equal values the lower row first, then the lower phase."""
@@ -285,59 +287,49 @@ def warp_score_model(corr, nlag, warp, nwarp, nslot, hyp, hop, n_origins: int):
     corr, nlag = _rows(corr, nlag)
     warp, nwarp, nslot = _table(warp, nwarp, nslot, nlag)
     hyp = np.asarray(hyp, np.int64).reshape(nlag.size, -1, 2)
-    hop = np.asarray(hop, np.uint8)
-    K, n_origins = hop.shape[0], int(n_origins)
-    score = np.full((nlag.size, K), -np.inf, np.float64)
-    origin = np.full((nlag.size, K), -1, np.int64)
-    rank = np.full((nlag.size, K), -1, np.int32)
-    for b, (n, J) in enumerate(zip(nlag.tolist(), nslot.tolist())):
-        if J == 0 or n_origins == 0:
-            continue
-        if hop.shape[1] < n_origins + J - 1:
-            raise ValueError("hop: fewer than n_origins + J - 1 columns")
+    n_origins = int(n_origins)
+
+    def record(b, J):
         rows = corr[NBANDS * b:NBANDS * b + NBANDS]
-        good = [bool(0 <= phi < FRAME_LEN) and _usable(warp[b], d, int(nwarp[b]), J, n) for d, phi in hyp[b].tolist()]
-        for k in range(K):
-            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]: slot j of every origin's window
-            scored = np.flatnonzero((win < NBANDS).all(axis=0))
-            if not scored.size:
-                continue
-            win = (win & 3).astype(np.int64)
-            for h, (d, phi) in enumerate(hyp[b].tolist()):
-                if not good[h]:
-                    continue
+        good = [(h, d, phi) for h, (d, phi) in enumerate(hyp[b].tolist())
+                if 0 <= phi < FRAME_LEN and _usable(warp[b], d, int(nwarp[b]), J, int(nlag[b]))]
+
+        def term(k, win, scored):
+            for h, d, phi in good:
                 acc = np.zeros(n_origins, np.float64)
                 for j in range(J):
                     acc = acc + rows[win[j], phi + FRAME_LEN * j + int(warp[b, d, j])]
-                s = (acc / np.float64(J))[scored]
-                i = int(np.argmax(s))                                                    # the first of equal values: the lowest origin
-                if origin[b, k] < 0 or s[i] > score[b, k] or (s[i] == score[b, k] and scored[i] < origin[b, k]):
-                    score[b, k], origin[b, k], rank[b, k] = s[i], scored[i], h
-    return score, origin, rank
+                yield h, (acc / np.float64(J))[scored]
+        return term
+
+    return _score_frame(np.asarray(hop, np.uint8), nslot.tolist(), n_origins, record)
 
 
-def verdict(score_row, origin_row, rank_row, lo: int, phases: list, frames: int) -> Presence:
-    """The Presence of one clip from its row of the score call: key row 0 is the detector's key, rows 1 .. R the decoys."""
+def verdict(score_row, origin_row, rank_row, lo: int, phases: list, frames: int, pos0: int = 0) -> Presence:
+    """The Presence of one record from its row of the score call: key row 0 is the detector's key, rows 1 .. R the decoys.  pos0: the
+    absolute first sample of the record (a clip: 0; a live window: w0; a window of a timeline: its column), for ctr0."""
     own, null = float(score_row[0]), np.array(score_row[1:], np.float64)
     found = int(origin_row[0]) >= 0
     ctr = int(lo) + int(origin_row[0]) if found else -1
     phase = int(phases[int(rank_row[0])]) if found else -1
-    return Presence(bool(null.size and own > null.max()), own, null, ctr, phase, origin_of(ctr, phase) if found else -1, int(frames), list(phases))
+    return Presence(bool(null.size and own > null.max()), own, null, ctr, phase, origin_of(ctr, phase, int(pos0)) if found else -1, int(frames),
+                    list(phases))
 
 
-def drift_verdict(score_row, origin_row, rank_row, lo: int, hyps: list, skews: list, frames: int) -> Presence:
-    """The Presence of one clip from its row of the warp score call: hyps its (row, phase) list, skews the skew of each table row."""
-    p = verdict(score_row, origin_row, rank_row, lo, [phi for _, phi in hyps], frames)
+def drift_verdict(score_row, origin_row, rank_row, lo: int, hyps: list, skews: list, frames: int, pos0: int = 0) -> Presence:
+    """The Presence of one record from its row of the warp score call: hyps its (row, phase) list, skews the skew of each table row."""
+    p = verdict(score_row, origin_row, rank_row, lo, [phi for _, phi in hyps], frames, pos0)
     p.skew = int(skews[hyps[int(rank_row[0])][0]]) if p.ctr >= 0 else 0
     p.drift_ppm = 1e6 * p.skew / (FRAME_LEN * int(frames))
     p.hypotheses = [(int(skews[d]), int(phi)) for d, phi in hyps]
     return p
 
 
-def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0) -> Presence | None:
+def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int = 8, decoys: int = 32, drift_ppm=0.0, pos0: int = 0) -> Presence | None:
     """WatermarkDetector.presence from one clip's four correlation rows (BAND_PLAN order), on the host: the fold, the phase list, the hop
     rows of `key` and the decoys, the score and the verdict.  None where the clip has no whole slot.  drift_ppm > 0: the same along every
-    row of skew_table(nlag, drift_ppm), the list being the (row, phase) pairs of largest fold."""
+    row of skew_table(nlag, drift_ppm), the list being the (row, phase) pairs of largest fold.  pos0: the absolute first sample of the
+    rows, where they are a window of something longer (verdict)."""
     corr4 = np.asarray(corr4, np.float64)
     nlag = min(max(int(nlag), 0), corr4.shape[1])
     lo, hi = check_reach(span, nlag + PRE_L - 1)
@@ -349,14 +341,14 @@ def presence_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), phases: int 
         hyps = pick_hypotheses(warp_fold_model(corr4, [nlag], *tab)[0], phases)
         hop = hop_model([bytes(key)] + decoy_keys(decoys), lo, max(hi - lo + J - 1, 0))
         score, origin, rank = warp_score_model(corr4, [nlag], *tab, [hyps], hop, hi - lo)
-        return drift_verdict(score[0], origin[0], rank[0], lo, hyps, skews, J)
+        return drift_verdict(score[0], origin[0], rank[0], lo, hyps, skews, J, pos0)
     J = nlag // FRAME_LEN
     if J == 0:
         return None
     plist = pick_phases(fold_model(corr4, [nlag])[0], phases)
     hop = hop_model([bytes(key)] + decoy_keys(decoys), lo, max(hi - lo + J - 1, 0))
     score, origin, rank = score_model(corr4, [nlag], [plist], hop, hi - lo)
-    return verdict(score[0], origin[0], rank[0], lo, plist, J)
+    return verdict(score[0], origin[0], rank[0], lo, plist, J, pos0)
 
 
 # ---- records anywhere in a table of rows: the windows of live streams (include/echoseal_live_presence.h) ----
@@ -406,106 +398,7 @@ def live_model(hist, stream: int, bands, base: int, w0: int, n: int, key: bytes,
         return None
     block = window_rows(hist, table_rows(bands, stream), int(w0) - int(base), nlag)
     sp = check_reach(span, nlag + PRE_L - 1) if origin is None or int(origin) < 0 else live_span(origin, w0, J)
-    p = presence_model(block, nlag, key, span=sp, phases=phases, decoys=decoys, drift_ppm=drift_ppm)
-    if p is not None and p.ctr >= 0:
-        p.ctr0 = origin_of(p.ctr, p.phase, int(w0))
-    return p
-
-
-def _verdicts(n_own: int, score_row, origin_row, rank_row, make) -> list:
-    """One Presence per own key from a record's row of a score call over the ring [own keys] + decoys: entry k ranks key row k against
-    the decoy rows.  make(score, origin, rank) is verdict / drift_verdict with the record's own arguments bound."""
-    pick = lambda a, k: np.concatenate((a[k:k + 1], a[n_own:]))
-    return [make(pick(score_row, k), pick(origin_row, k), pick(rank_row, k)) for k in range(n_own)]
-
-
-def search(eng, ring, n_own: int, corr, nlag, spans, drift: float, P: int, at=None, pos0=None, device_pick: bool = False) -> list:
-    """The launches and verdicts of every presence call (WatermarkDetector.presence_batch, WatermarkIdentifier.presence_batch,
-    LiveMonitor.presence, LiveIdentifier.presence) -> per record None (no whole slot) or a list of n_own Presence, one per own key.
-    ring: the device key ring [the n_own own keys] + decoys.  corr, nlag: the records' rows; spans: (lo, hi) per record.
-    at None: clips, record b = rows 4 b .. 4 b + 3 from column 0, all of ONE span -- the rigid grid (drift 0) through phase_fold /
-    hop_score, a drift search through warp_fold / warp_score, as presence_batch always called them.
-    at = (rows4 [B, 4], col [B]): records anywhere in the table `corr`, each with its own span -- ONE warp_fold_at over all of them (drift 0:
-    a one-row table of zeros), ONE download and pick, ONE hop_window with a hop row per distinct span base, and ONE warp_score_at per
-    group of equal span width.  pos0 [B]: the absolute first sample of each record, for the verdict's ctr0 (None: 0).
-    device_pick (the at= route only, P <= ES_PICK_MAX_H): the fold stays on the device, ONE fold_pick replaces the download
-    and the host's pick, its lists go into warp_score_at as they are, and only they are downloaded, for the verdicts' phase lists -- the
-    same verdicts, field for field.  False: the launches and bits every call had before."""
-    if device_pick and at is None:
-        raise ValueError("device_pick: the route of records anywhere in a table (at=)")
-    if device_pick and P > PICK_MAX_H:
-        raise ValueError(f"phases = {P}: the device picks lists of at most {PICK_MAX_H} entries")
-    nlag = np.asarray(nlag, np.int64).reshape(-1)
-    B = nlag.size
-    out: list = [None] * B
-    spans = [(int(lo), int(hi)) for lo, hi in spans]
-    rigid = not drift > 0
-    made = {} if rigid else {n: skew_table(n, drift) for n in set(nlag.tolist())}       # records of one length share a table
-    tabs = None if rigid else [made[n] for n in nlag.tolist()]
-    J = np.maximum(nlag, 0) // FRAME_LEN if rigid else np.array([t[1] for t in tabs], np.int64)
-    if not B or not J.max():
-        return out
-    dev = lambda a, dt: _torch().from_numpy(np.ascontiguousarray(a, dt)).to(eng.device)
-    table = None
-    if rigid and at is None:
-        fold = eng.phase_fold(corr, nlag).cpu().numpy()
-        lists = [pick_phases(f, P) for f in fold]
-        jw = corr.shape[1] // FRAME_LEN                                     # the slots hop_score sizes the hop table for
-    else:
-        nwarp = np.ones(B, np.int32) if rigid else np.array([len(t[0]) for t in tabs], np.int32)
-        warp = np.zeros((B, int(nwarp.max()), int(J.max())), np.int32)      # zeros past a record's own rows and slots: nwarp and nslot say where they end
-        for k, t in enumerate(tabs or ()):
-            warp[k, :t[2].shape[0], :t[1]] = t[2]
-        table = (dev(warp, np.int32), dev(nwarp, np.int32), dev(J, np.int32))
-        fold = eng.warp_fold(corr, nlag, *table) if at is None else eng.warp_fold_at(corr, at[0], at[1], nlag, *table)
-        if device_pick:
-            hyp_dev = eng.fold_pick(fold, table[1], P, want_val=False)[0]
-            lists = [[(d, phi) for d, phi in h if d >= 0] for h in hyp_dev.cpu().numpy().tolist()]
-        else:
-            fold = fold.cpu().numpy()
-            lists = [pick_hypotheses(f[:d], P) for f, d in zip(fold, nwarp)]
-        jw = int(J.max())
-    bases = sorted({min(lo, CTR_END - 1) for lo, _ in spans})               # one hop row per distinct span base
-    hop = eng.hop_window(ring, bases, max(max(hi - lo for lo, hi in spans) + jw - 1, 0))
-    for width in sorted({hi - lo for lo, hi in spans}):
-        ids = [b for b, (lo, hi) in enumerate(spans) if hi - lo == width]
-        if at is None:
-            if len(ids) != B or len(bases) != 1:
-                raise ValueError("clips of one launch share one span")
-            if rigid:
-                res = eng.hop_score(corr, nlag, np.array(lists, np.int32), hop, width)
-            else:
-                hyp = np.full((B, P, 2), -1, np.int32)                      # a list is P entries long; a shorter one ends in entries that name nothing
-                for k, h in enumerate(lists):
-                    hyp[k, :len(h)] = h
-                res = eng.warp_score(corr, nlag, *table, hyp, hop, width)
-        else:
-            sel = dev(ids, np.int64)
-            if device_pick:
-                hyp = hyp_dev[sel]
-            else:
-                hyp = np.full((len(ids), P, 2), -1, np.int32)
-                for k, b in enumerate(ids):
-                    hyp[k, :len(lists[b])] = lists[b]
-            rows4, col = dev(at[0], np.int64).reshape(B, NBANDS), dev(at[1], np.int64).reshape(B)
-            hop_row = np.array([bases.index(min(spans[b][0], CTR_END - 1)) for b in ids], np.int32)
-            res = eng.warp_score_at(corr, rows4[sel], col[sel], nlag[ids], table[0][sel], table[1][sel], table[2][sel], hyp, hop, hop_row, width)
-        score, origin, rank = (t.cpu().numpy() for t in res)
-        for k, b in enumerate(ids):
-            if not J[b]:
-                continue
-            lo = spans[b][0]
-            if rigid:
-                phis = lists[b] if at is None else [phi for _, phi in lists[b]]
-                make = lambda s, o, r: verdict(s, o, r, lo, phis, int(J[b]))
-            else:
-                make = lambda s, o, r: drift_verdict(s, o, r, lo, lists[b], tabs[b][0], int(J[b]))
-            out[b] = _verdicts(n_own, score[k], origin[k], rank[k], make)
-            if pos0 is not None:
-                for p in out[b]:
-                    if p.ctr >= 0:
-                        p.ctr0 = origin_of(p.ctr, p.phase, int(pos0[b]))
-    return out
+    return presence_model(block, nlag, key, span=sp, phases=phases, decoys=decoys, drift_ppm=drift_ppm, pos0=w0)
 
 
 # ---- the hypothesis list as the device picks it (DESIGN 4.26; include/echoseal_pick.h) ----
@@ -536,9 +429,6 @@ def pick_model(fold, nwarp=None, H: int = 8):
 
 
 # ---- the presence timeline of a clip: windows, marked stretches and splices ----
-MAP_HOP_BYTES = 256 << 20        # the most bytes of one group's hop table, [K][HR][Ccols] uint8: windows go to the search in groups within it
-
-
 @dataclass
 class Stretch:
     """A maximal run of adjacent windows first .. last, each detected and each consistent with the one before it.  start, end: the
@@ -594,17 +484,21 @@ def map_windows(nlag: int, window: int = 40, step: int = 20) -> list[tuple[int, 
     """The windows of a clip of nlag lags -> [(first slot s, column 1215 s, lags)], J = nlag // 1215: none for J == 0; the whole clip,
     (0, 0, nlag), for J <= window; else windows of `window` slots at s = 0, step, 2 step .. <= J - window, and one at J - window
     where the steps do not end there."""
-    W, S, _, _ = check_map(window, step, 1, 1)
     nlag = max(int(nlag), 0)
     J = nlag // FRAME_LEN
-    if J == 0:
-        return []
+    return [(s, FRAME_LEN * s, FRAME_LEN * n if n < J else nlag) for s, n in _cut(J, window, step)]
+
+
+def _cut(J: int, window: int, step: int) -> list[tuple[int, int]]:
+    """The windows of J slots -> [(first slot s, slots)]: none for J == 0; all of them, (0, J), for J <= window; else windows of `window`
+    slots at s = 0, step, 2 step .. <= J - window, and one at J - window where the steps do not end there."""
+    W, S, _, _ = check_map(window, step, 1, 1)
     if J <= W:
-        return [(0, 0, nlag)]
+        return [(0, J)] if J else []
     starts = list(range(0, J - W + 1, S))
     if (J - W) % S:
         starts.append(J - W)
-    return [(s, FRAME_LEN * s, FRAME_LEN * W) for s in starts]
+    return [(s, W) for s in starts]
 
 
 def window_span(span, s: int, J: int) -> tuple[int, int]:
@@ -672,45 +566,9 @@ def map_model(corr4, nlag: int, key: bytes, *, span=(0, 4096), window: int = 40,
     wins = map_windows(nlag, W, S)
     if not wins:
         return None
-    verdicts = []
-    for s, col, n in wins:
-        p = presence_model(window_rows(corr4, range(NBANDS), col, n), n, key, span=window_span(span, s, n // FRAME_LEN), phases=P, decoys=decoys,
-                           drift_ppm=drift_ppm)
-        if p is not None and p.ctr >= 0:
-            p.ctr0 = origin_of(p.ctr, p.phase, col)
-        verdicts.append(p)
+    verdicts = [presence_model(window_rows(corr4, range(NBANDS), col, n), n, key, span=window_span(span, s, n // FRAME_LEN), phases=P, decoys=decoys,
+                               drift_ppm=drift_ppm, pos0=col) for s, col, n in wins]
     return make_map(verdicts, wins, drift_ppm, C)
-
-
-def search_map(eng, ring, n_own: int, corr, clip_nlag, spans, drift: float, P: int, window: int, step: int, confirm: int) -> list:
-    """The windows of every clip of one launch through `search` (at=, device_pick=True) -> per clip None (no whole slot) or n_own
-    PresenceMap, one per own key.  Clip c owns rows 4 c .. 4 c + 3 of corr; spans[c] is its span.  Windows go in groups of consecutive
-    windows whose hop table -- a hop row per distinct span base, K HR Ccols bytes -- stays within MAP_HOP_BYTES: per group ONE fold, ONE
-    pick, ONE hop window and ONE score per span width, never a launch per window."""
-    recs = []                                                               # (clip, window of it, rows4, col, lags, span)
-    wins = [map_windows(n, window, step) for n in np.asarray(clip_nlag, np.int64).reshape(-1).tolist()]
-    for c, ws in enumerate(wins):
-        recs += [(c, w, [NBANDS * c + band for band in range(NBANDS)], col, n, window_span(spans[c], s, n // FRAME_LEN)) for w, (s, col, n) in enumerate(ws)]
-    verdicts = [[None] * len(ws) for ws in wins]
-    i = 0
-    while i < len(recs):
-        bases, ccols, j = set(), 0, i
-        while j < len(recs):                                                # grow the group while its hop table fits
-            lo, hi = recs[j][5]
-            grown = bases | {min(lo, CTR_END - 1)}
-            cols = max(ccols, hi - lo + recs[j][4] // FRAME_LEN - 1)
-            if j > i and ring.n * len(grown) * cols > MAP_HOP_BYTES:
-                break
-            bases, ccols, j = grown, cols, j + 1
-        group = recs[i:j]
-        res = search(eng, ring, n_own, corr, [r[4] for r in group], [r[5] for r in group], drift, P,
-                     at=(np.array([r[2] for r in group], np.int64), np.array([r[3] for r in group], np.int64)), pos0=[r[3] for r in group],
-                     device_pick=True)
-        for r, v in zip(group, res):
-            verdicts[r[0]][r[1]] = v
-        i = j
-    return [None if not ws else [make_map([None if v is None else v[k] for v in vs], ws, drift, confirm) for k in range(n_own)]
-            for ws, vs in zip(wins, verdicts)]
 
 
 # ---- the coherent presence test: preamble and keyed header on matched-filter rows, every phase (DESIGN 4.27; include/echoseal_coherent.h) ----
@@ -743,13 +601,8 @@ def coherent_slots(samples: int, g) -> int:
 
 
 def check_coherent_reach(span, samples: int, g) -> tuple[int, int]:
-    """check_reach with the coherent J: the window of the last origin, hi - 1 + J - 1, must be a counter."""
-    lo, hi = check_span(span)
-    J = coherent_slots(samples, g)
-    if hi > lo and hi + J - 1 > CTR_END:
-        raise ValueError(f"span = ({lo}, {hi}): a clip of {int(samples)} samples has {J} frames, and hi + {J} - 1 > 2^32 "
-                         "(spans that wrap past 2^32 are out of scope)")
-    return lo, hi
+    """check_reach with the coherent J."""
+    return _reach(span, coherent_slots(samples, g), samples)
 
 
 def mf_rows_model(y, lens, bands, g, c):
@@ -826,29 +679,20 @@ def coherent_score_model(M, A, D, nslot, phases, u, hop, lo: int, n_origins: int
     K, n_origins, lo = hop.shape[0], int(n_origins), int(lo)
     if u.shape[0] != K:
         raise ValueError("u: one row of 128 signs per hop row")
-    score = np.full((B, K), -np.inf, np.float64)
-    origin = np.full((B, K), -1, np.int64)
-    rank = np.full((B, K), -1, np.int32)
     bit = lambda v, i: 2.0 * ((v >> (7 - i)) & 1) - 1.0                     # sign i of a byte, MSB first
-    for b, J in enumerate(nslot.tolist()):
-        if J == 0 or n_origins == 0:
-            continue
-        if hop.shape[1] < n_origins + J - 1:
-            raise ValueError("hop: fewer than n_origins + J - 1 columns")
+
+    def record(b, J):
         good = np.flatnonzero((phases[b] >= 0) & (phases[b] < FRAME_LEN))
-        if not good.size:
-            continue
         phi = phases[b][good]
         Mb, Ab, Db = (a[NBANDS * b:NBANDS * b + NBANDS] for a in (M, A, D))
-        for k in range(K):
-            win = np.stack([hop[k, j:j + n_origins] for j in range(J)])                  # [J, n_origins]
-            scored = np.flatnonzero((win < NBANDS).all(axis=0))
-            if not scored.size:
-                continue
+
+        def term(k, win, scored):
+            if not good.size:
+                return
             acc = np.zeros((scored.size, good.size), np.float64)
             for j in range(J):
                 s = phi + FRAME_LEN * j
-                band = (win[j, scored] & 3).astype(np.int64)
+                band = win[j, scored]
                 v = (lo + scored + j) & 0xFFFF
                 hi8, lo8 = v >> 8, v & 0xFF
                 Z = np.zeros((NBANDS, 16, s.size), np.float64)
@@ -867,16 +711,18 @@ def coherent_score_model(M, A, D, nslot, phases, u, hop, lo: int, n_origins: int
                 acc = acc + np.where(den == 0.0, 0.0, num / np.where(den == 0.0, 1.0, den))
             S = acc / np.float64(J)
             for col, p in enumerate(good.tolist()):
-                i = int(np.argmax(S[:, col]))                                # the first of equal values: the lowest origin
-                if origin[b, k] < 0 or S[i, col] > score[b, k] or (S[i, col] == score[b, k] and scored[i] < origin[b, k]):
-                    score[b, k], origin[b, k], rank[b, k] = S[i, col], scored[i], p
-    return score, origin, rank
+                yield p, S[:, col]
+        return term
+
+    return _score_frame(hop, nslot.tolist(), n_origins, record)
 
 
-def coherent_model(y4, n: int, key: bytes, *, span=(0, 4096), phases=FRAME_LEN, decoys: int = 32, fs: int = 48_000, tables=None) -> Presence | None:
+def coherent_model(y4, n: int, key: bytes, *, span=(0, 4096), phases=FRAME_LEN, decoys: int = 32, fs: int = 48_000, tables=None,
+                   pos0: int = 0) -> Presence | None:
     """WatermarkDetector.presence_coherent from one clip's four band-passed rows y4 [4, >= n] (BAND_PLAN order), on the host: the rows,
     the hop rows and header signs of `key` and the decoys, the score over every phase and the verdict.  phases: 1215, every phase in
-    order, or an explicit list (what the keyless fold picked).  None where the clip has no whole slot (J == 0)."""
+    order, or an explicit list (what the keyless fold picked).  None where the clip has no whole slot (J == 0).  pos0: the absolute first
+    sample of the rows, where they are a window of something longer (verdict)."""
     y4 = np.asarray(y4, np.float64)
     n = min(max(int(n), 0), y4.shape[1])
     g, c = mf_tables(fs, tables)
@@ -889,7 +735,7 @@ def coherent_model(y4, n: int, key: bytes, *, span=(0, 4096), phases=FRAME_LEN, 
     M, A, D = mf_rows_model(y4[:NBANDS, :n], [n] * NBANDS, range(NBANDS), g, c)
     hop = hop_model(keys, lo, max(hi - lo + J - 1, 0))
     score, origin, rank = coherent_score_model(M, A, D, [J], [plist], header_signs(keys), hop, lo, hi - lo)
-    return verdict(score[0], origin[0], rank[0], lo, plist, J)
+    return verdict(score[0], origin[0], rank[0], lo, plist, J, pos0)
 
 
 # ---- the coherent presence timeline: the coherent test on the windows of a clip (include/echoseal_coherent_at.h) ----
@@ -938,16 +784,7 @@ def coherent_windows(samples: int, g, window: int = 40, step: int = 20) -> list[
     """The windows of a clip of `samples` samples -> [(first slot s, column 1215 s, slots)], J = coherent_slots(samples, g): none for
     J == 0; the whole clip, (0, 0, J), for J <= window; else windows of `window` slots at s = 0, step, 2 step .. <= J - window, and one
     at J - window where the steps do not end there (map_windows, counted in slots: a window reads 1215 slots + 189 + L_max samples)."""
-    W, S, _, _ = check_map(window, step, 1, 1)
-    J = coherent_slots(samples, g)
-    if J == 0:
-        return []
-    if J <= W:
-        return [(0, 0, J)]
-    starts = list(range(0, J - W + 1, S))
-    if (J - W) % S:
-        starts.append(J - W)
-    return [(s, FRAME_LEN * s, W) for s in starts]
+    return [(s, FRAME_LEN * s, n) for s, n in _cut(coherent_slots(samples, g), window, step)]
 
 
 def coherent_map_model(y4, n: int, key: bytes, *, span=(0, 4096), window: int = 40, step: int = 20, confirm: int = 2, decoys: int = 32,
@@ -964,70 +801,14 @@ def coherent_map_model(y4, n: int, key: bytes, *, span=(0, 4096), window: int = 
     if not wins:
         return None
     tail = COH_SPAN - 1 + max(len(t) for t in g)
-    verdicts = []
-    for s, col, J in wins:
-        m = FRAME_LEN * J + tail
-        p = coherent_model(y4[:NBANDS, col:col + m], m, key, span=window_span(span, s, J), decoys=decoys, fs=fs, tables=tables)
-        if p is not None and p.ctr >= 0:
-            p.ctr0 = origin_of(p.ctr, p.phase, col)
-        verdicts.append(p)
+    verdicts = [coherent_model(y4[:NBANDS, col:col + FRAME_LEN * J + tail], FRAME_LEN * J + tail, key, span=window_span(span, s, J), decoys=decoys,
+                               fs=fs, tables=tables, pos0=col) for s, col, J in wins]
     return make_map(verdicts, [(s, col, FRAME_LEN * J) for s, col, J in wins], 0.0, C)
 
 
-def search_coherent_map(eng, ring, n_own: int, M, A, D, clip_samples, spans, g, window: int, step: int, confirm: int) -> list:
-    """The coherent windows of every clip of one launch through the device -> per clip None (no whole slot) or n_own PresenceMap, one per
-    own key.  Clip c owns rows 4 c .. 4 c + 3 of M, A, D (mf_rows' tensors) and has clip_samples[c] samples; spans[c] is its span; g the
-    matched filters (mf_tables).  Windows go in groups of consecutive windows whose hop table -- a hop row per distinct span base,
-    K HR Ccols bytes -- stays within MAP_HOP_BYTES, as search_map groups them: per group ONE hop window and ONE coherent_score_at per
-    distinct span width, never a launch per window.  Every record searches every phase: the identity list."""
-    torch = _torch()
-    recs = []                                                               # (clip, window of it, rows4, col, slots, span)
-    wins = [coherent_windows(n, g, window, step) for n in np.asarray(clip_samples, np.int64).reshape(-1).tolist()]
-    for c, ws in enumerate(wins):
-        recs += [(c, w, [NBANDS * c + band for band in range(NBANDS)], col, J, window_span(spans[c], s, J)) for w, (s, col, J) in enumerate(ws)]
-    verdicts = [[None] * len(ws) for ws in wins]
-    i = 0
-    while i < len(recs):
-        bases, ccols, j = set(), 0, i
-        while j < len(recs):                                                # grow the group while its hop table fits
-            lo, hi = recs[j][5]
-            grown = bases | {min(lo, CTR_END - 1)}
-            cols = max(ccols, hi - lo + recs[j][4] - 1)
-            if j > i and ring.n * len(grown) * cols > MAP_HOP_BYTES:
-                break
-            bases, ccols, j = grown, cols, j + 1
-        group, bases = recs[i:j], sorted(bases)
-        hop = eng.hop_window(ring, bases, max(ccols, 0))
-        for width in sorted({hi - lo for _, _, _, _, _, (lo, hi) in group}):
-            ids = [r for r in group if r[5][1] - r[5][0] == width]
-            base = [min(r[5][0], CTR_END - 1) for r in ids]
-            lists = torch.arange(FRAME_LEN, dtype=torch.int32, device=eng.device).repeat(len(ids), 1)
-            res = eng.coherent_score_at(M, A, D, np.array([r[2] for r in ids], np.int64), np.array([r[3] for r in ids], np.int64),
-                                        np.array([r[4] for r in ids], np.int32), lists, ring, hop,
-                                        np.array([bases.index(v) for v in base], np.int32), np.array(base, np.int64), width)
-            score, origin, rank = (t.cpu().numpy() for t in res)
-            plist = list(range(FRAME_LEN))
-            for k, r in enumerate(ids):
-                make = lambda s, o, q: verdict(s, o, q, r[5][0], plist, r[4])
-                v = _verdicts(n_own, score[k], origin[k], rank[k], make)
-                for p in v:
-                    if p.ctr >= 0:
-                        p.ctr0 = origin_of(p.ctr, p.phase, r[3])
-                verdicts[r[0]][r[1]] = v
-        i = j
-    return [None if not ws else [make_map([v[k] for v in vs], [(s, col, FRAME_LEN * J) for s, col, J in ws], 0.0, confirm) for k in range(n_own)]
-            for ws, vs in zip(wins, verdicts)]
-
-
-def _torch():
-    import torch
-    return torch
-
-
-__all__ = ["COH_SPAN", "DECOY_LABEL", "MAP_HOP_BYTES", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor",
+__all__ = ["COH_SPAN", "DECOY_LABEL", "PICK_MAX_H", "Presence", "PresenceMap", "Splice", "Stretch", "anchor",
            "check_coherent_reach", "check_decoys", "check_drift", "check_map", "check_phases", "check_reach", "clip_spans", "coherent_map_model",
            "coherent_model", "coherent_score_at_model", "coherent_score_model", "coherent_slots", "coherent_windows", "consistent", "decoy_keys",
            "drift_verdict", "fold_model", "header_signs", "hop_model", "live_model", "live_span", "make_map", "map_model", "map_windows",
-           "mf_rows_model", "mf_tables", "pick_hypotheses", "pick_model", "pick_phases", "presence_model", "ring_signs", "score_model", "search",
-           "search_coherent_map", "search_map", "skew_table", "slots", "stretches", "table_rows", "verdict", "warp_fold_model", "warp_score_model",
+           "mf_rows_model", "mf_tables", "pick_hypotheses", "pick_model", "pick_phases", "presence_model", "ring_signs", "score_model", "skew_table", "slots", "stretches", "table_rows", "verdict", "warp_fold_model", "warp_score_model",
            "window_rows", "window_span"]

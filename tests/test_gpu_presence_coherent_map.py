@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 import echoseal_amd._native as nat
 import presence_cases as PC
 from echoseal_amd import presence as pr
+from echoseal_amd import presence_search as ps
 from echoseal_amd.detector import WatermarkDetector
 from echoseal_amd.identify import WatermarkIdentifier
 
@@ -368,7 +369,7 @@ def test_one_rows_call_per_launch_one_hop_window_and_one_score_per_group_and_wid
     det = WatermarkDetector(PC.KEY, list_size=8, engine=engine)
 
     def count(limit, **kw):
-        monkeypatch.setattr(pr, "MAP_HOP_BYTES", limit)
+        monkeypatch.setattr(ps, "MAP_HOP_BYTES", limit)
         calls, real = [], engine._call
         engine._call = lambda name, *a: (calls.append(name), real(name, *a))[1]
         try:
@@ -378,7 +379,7 @@ def test_one_rows_call_per_launch_one_hop_window_and_one_score_per_group_and_wid
         assert calls.count("es_mf_rows_batch") == 1 and not any(n in ("es_coherent_score_batch", "es_warp_score_at_batch", "es_xcorr_batch") for n in calls)
         return m, [n for n in calls if n in ("es_hop_window_batch", AT)]
 
-    assert pr.MAP_HOP_BYTES == 256 << 20
+    assert ps.MAP_HOP_BYTES == 256 << 20
     m, back = count(256 << 20, **SMALL)
     _same_map(m, map3[0])
     assert back == ["es_hop_window_batch", AT]                              # five windows, five hop rows, one width: one group

@@ -1,6 +1,6 @@
 """GPU: the presence timeline -- es_fold_pick_batch exactly (ints equal, values as uint64 views) against its host twin
 presence.pick_model on folds that hold every edge of its definition, without val_dev, every refusal with its outputs unwritten, the empty
-calls, two runs, capture and replay; the device pick inside presence.search against the host's pick, field for field, with the default
+calls, two runs, capture and replay; the device pick inside presence_search.search against the host's pick, field for field, with the default
 route's call sequence unchanged; and presence_map / presence_map_batch of detector and identifier against presence.map_model on the
 downloaded rows, against each other, and launch by launch."""
 import numpy as np
@@ -13,6 +13,7 @@ import echoseal_amd._native as nat
 import presence_cases as PC
 import presence_map_cases as MC
 from echoseal_amd import presence as pr
+from echoseal_amd import presence_search as ps
 from echoseal_amd.detector import WatermarkDetector
 from echoseal_amd.identify import WatermarkIdentifier
 
@@ -201,9 +202,9 @@ def test_the_search_with_the_device_pick_is_the_search_without(engine, records, 
     calls, real = [], engine._call
     engine._call = lambda name, *a: (calls.append(name), real(name, *a))[1]
     try:
-        host = pr.search(engine, ring, 3, corr, nlags, spans, drift, 8, at=at, pos0=at[1])
+        host = ps.search(engine, ring, 3, corr, nlags, spans, drift, 8, at=at, pos0=at[1])
         mark = len(calls)
-        device = pr.search(engine, ring, 3, corr, nlags, spans, drift, 8, at=at, pos0=at[1], device_pick=True)
+        device = ps.search(engine, ring, 3, corr, nlags, spans, drift, 8, at=at, pos0=at[1], device_pick=True)
     finally:
         del engine._call
     assert calls[:mark] == ["es_warp_fold_at_batch", "es_hop_window_batch", "es_warp_score_at_batch"]       # the default route: as it was
@@ -215,9 +216,9 @@ def test_the_search_with_the_device_pick_is_the_search_without(engine, records, 
             _same(p, q)
     assert all(r[1].detected for r in device)
     with pytest.raises(ValueError):
-        pr.search(engine, ring, 3, corr[:, :nlags[0]].contiguous(), nlags[:1], spans[:1], drift, 8, device_pick=True)      # the at= route only
+        ps.search(engine, ring, 3, corr[:, :nlags[0]].contiguous(), nlags[:1], spans[:1], drift, 8, device_pick=True)      # the at= route only
     with pytest.raises(ValueError):
-        pr.search(engine, ring, 3, corr, nlags, spans, drift, 65, at=at, device_pick=True)
+        ps.search(engine, ring, 3, corr, nlags, spans, drift, 65, at=at, device_pick=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the public calls
@@ -272,7 +273,7 @@ def test_one_fold_one_pick_and_one_hop_window_per_group(engine, monkeypatch):
 
     def count(limit):
         if limit is not None:
-            monkeypatch.setattr(pr, "MAP_HOP_BYTES", limit)
+            monkeypatch.setattr(ps, "MAP_HOP_BYTES", limit)
         calls, real = [], engine._call
         engine._call = lambda name, *a: (calls.append(name), real(name, *a))[1]
         try:
@@ -282,7 +283,7 @@ def test_one_fold_one_pick_and_one_hop_window_per_group(engine, monkeypatch):
         _same_map(m, whole)
         return [n for n in calls if n in ("es_warp_fold_at_batch", "es_fold_pick_batch", "es_hop_window_batch", "es_warp_score_at_batch")], calls
 
-    assert pr.MAP_HOP_BYTES == 256 << 20
+    assert ps.MAP_HOP_BYTES == 256 << 20
     back, calls = count(None)
     assert back == ["es_warp_fold_at_batch", "es_fold_pick_batch", "es_hop_window_batch", "es_warp_score_at_batch"]        # nine windows, one group
     assert not any("phase_fold" in n or n in ("es_warp_fold_batch", "es_hop_score_batch", "es_warp_score_batch") for n in calls)

@@ -187,3 +187,60 @@ def test_the_twin_refuses_another_key_and_the_unmarked_host(rows, name):
 
 def test_a_clip_without_a_whole_slot_has_no_result():
     assert pr.presence_model(np.zeros((4, 1214)), 1214, PC.KEY, span=PC.SPAN) is None
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_the_rigid_twins_are_the_warp_twins_under_a_table_of_zeros(seed):
+    """fold_model / score_model against warp_fold_model / warp_score_model under one row of zeros and list entries (0, phi), byte for byte
+    -- the identity the kernels' shared bodies rest on -- on rows with ties (one decimal), zeros of both signs and a NaN, a 0xFF hop byte,
+    phases at -1 and 1215, lags below 0 and past the stride, and a clip without a whole slot."""
+    FL = 1215
+    rng = np.random.default_rng(900 + seed)
+    stride, n_origins = 4 * FL + 17, 9
+    nlag = [stride + 50, 3 * FL + int(rng.integers(0, FL)), -5, FL - 1, 2 * FL]
+    B, Jw = len(nlag), stride // FL
+    corr = rng.uniform(-1.0, 1.0, (4 * B, stride)).round(1)
+    corr[rng.integers(0, 4 * B, 60), rng.integers(0, stride, 60)] = 0.0
+    corr[rng.integers(0, 4 * B, 60), rng.integers(0, stride, 60)] = -0.0
+    corr[0, 7] = corr[4, FL + 3] = corr[17, 11] = np.nan                    # in band 0 a NaN stays; in a later band it is never larger
+    hop = rng.integers(0, 4, (3, n_origins + Jw - 1)).astype(np.uint8)
+    hop[1, 4] = 0xFF
+    phases = rng.integers(0, FL, (B, 6))
+    phases[:, 1], phases[:, 4], phases[0, 2], phases[1, 3] = -1, FL, 7, 3
+    zeros = (np.zeros((B, 1, Jw), np.int32), np.ones(B, np.int32), np.clip(nlag, 0, stride) // FL)
+    fold, warp = pr.fold_model(corr, nlag), pr.warp_fold_model(corr, nlag, *zeros)
+    assert fold.shape == (B, FL) and warp.shape == (B, 1, FL) and fold.tobytes() == warp[:, 0].tobytes()
+    assert np.isnan(fold[0, 7]) and np.isnan(fold[1, 3]) and np.isfinite(fold[4, 11]) and not fold[2].any() and not fold[3].any() and np.isfinite(fold[4]).all()
+    rigid = pr.score_model(corr, nlag, phases, hop, n_origins)
+    warped = pr.warp_score_model(corr, nlag, *zeros, np.stack([np.zeros_like(phases), phases], axis=2), hop, n_origins)
+    for a, b in zip(rigid, warped):
+        assert a.dtype == b.dtype and a.shape == (B, 3) and a.tobytes() == b.tobytes()
+    score, origin, rank = rigid
+    assert np.isneginf(score[2:4]).all() and (origin[2:4] == -1).all() and (rank[2:4] == -1).all()          # no lags; no whole slot
+    assert (origin[[0, 1, 4]] >= 0).all() and not np.isin(rank[[0, 1, 4]], (1, 4)).any()                     # the entries outside 0 .. 1214 are never kept
+    assert (origin[0, 1] + np.arange(Jw) != 4).all()                        # no origin whose window holds the 0xFF byte
+
+
+def test_windows_go_to_the_device_in_groups_within_the_hop_table_limit(monkeypatch):
+    """presence_search's group generator on records made by hand: one group at the default limit, a limit that cuts after exactly k hop
+    rows, and a limit of 1, under which a group still holds one window; the base of a span at 2^32 is 2^32 - 1."""
+    from echoseal_amd import presence_search as ps
+    K, W, width, E = 33, 40, 256, 2 ** 32
+    recs = [ps.Record(0, w, [0, 1, 2, 3], 1215 * s, 1215 * W, W, (s, s + width)) for w, s in enumerate(range(0, 180, 20))]
+    ccols = width + W - 1
+
+    def groups(limit, records=recs, keys=K):
+        monkeypatch.setattr(ps, "MAP_HOP_BYTES", limit)                     # read at every call
+        return list(ps._groups(records, keys))
+
+    assert ps.MAP_HOP_BYTES == 256 << 20
+    assert groups(256 << 20) == [(recs, list(range(0, 180, 20)), ccols)]    # nine windows, nine hop rows, one group
+    for limit, sizes in ((K * 4 * ccols, [4, 4, 1]), (K * 4 * ccols - 1, [3, 3, 3]), (K * 9 * ccols - 1, [8, 1]), (1, [1] * 9)):
+        got = groups(limit)
+        assert [len(g) for g, _, _ in got] == sizes and [r for g, _, _ in got for r in g] == recs
+        assert all(bases == [r.span[0] for r in g] and cols == ccols for g, bases, cols in got)
+    assert groups(256 << 20, []) == []
+    top = [ps.Record(0, w, [0, 1, 2, 3], 1215 * s, 5, 5, span) for w, (s, span) in
+           enumerate([(0, (E - 10, E - 6)), (3, (E - 7, E - 4)), (6, (E - 4, E - 4)), (7, (E, E)), (8, (E - 10, E - 9))])]
+    assert groups(256 << 20, top, 4) == [(top, [E - 10, E - 7, E - 4, E - 1], 8)]           # a base per distinct min(lo, 2^32 - 1), the widest window
+    assert [(len(g), bases, cols) for g, bases, cols in groups(4 * 2 * 8, top, 4)] == [(2, [E - 10, E - 7], 8), (3, [E - 10, E - 4, E - 1], 5)]

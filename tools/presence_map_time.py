@@ -7,7 +7,7 @@ es_fold_pick_batch between two device events, fold_pick plus the download of its
 (b) The map.  WatermarkDetector.presence_map on the clip by the host clock, against the only route there was before for the same
 question: presence_batch over the samples of the same windows (upload, band-pass, correlation and search again per window).  Where both
 routes detect a window their counters and phases are compared.  The map's two halves are timed apart: the front end of the whole clip
-(band-pass and correlation, device events) and presence.search_map over its windows (host clock).
+(band-pass and correlation, device events) and presence_search.search_map over its windows (host clock).
 One run, one card.
 
     python tools/presence_map_time.py [--out profiles/presence_map.json]
@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from echoseal_amd import presence as pr  # noqa: E402
 from echoseal_amd.detector import WatermarkDetector  # noqa: E402
 from echoseal_amd.engine import RxEngine  # noqa: E402
+from echoseal_amd.presence_search import search_map  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
@@ -89,8 +90,8 @@ for B in (64, 1024):
 
 # ---- (b) the map against presence_batch over the windows' samples; first its two halves, the clip's front end and the search of its windows
 _, t_front = events(lambda: eng.xcorr(eng.bpf(x, bid), bid))
-_, t_search = clocked(lambda: pr.search_map(eng, det._presence_ring(DECOYS), 1, corr, [TOTAL - 62], [SPAN], 0.0, PHASES, W, S, 2))
-_, t_search_drift = clocked(lambda: pr.search_map(eng, det._presence_ring(DECOYS), 1, corr, [TOTAL - 62], [SPAN], DRIFT, PHASES, W, S, 2))
+_, t_search = clocked(lambda: search_map(eng, det._presence_ring(DECOYS), 1, corr, [TOTAL - 62], [SPAN], 0.0, PHASES, W, S, 2))
+_, t_search_drift = clocked(lambda: search_map(eng, det._presence_ring(DECOYS), 1, corr, [TOTAL - 62], [SPAN], DRIFT, PHASES, W, S, 2))
 del x, corr
 m, t_map = clocked(lambda: det.presence_map(audio, 48_000, span=SPAN, window=W, step=S, phases=PHASES, decoys=DECOYS), reps=10)
 clips = [audio[c:c + n + 62] for _, c, n in wins]
